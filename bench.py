@@ -8,7 +8,14 @@ outputs resident in HBM.  For N > 1 each rank owns a contiguous shard of the sta
 --frames per rank) and the flow fields are re-assembled with one RCCL all-gather per field inside the
 timed step.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N --steps K --warmup W] [--size 1024 --frames 256]
+    python bench.py [--gpus N --steps K --warmup W] [--size 1024 --frames 256] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps and K timed steps and prints the headline line.  --full adds the informational
+figures, each of which costs runs or profiling of its own: the per-kernel HIP-event profile and the HBM roofline of the
+dominant kernel class, the variant settings, vary_regularisation, the end-to-end drop-in call and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0's view) as DIR/<name>.npy, float64: the fields
+v_x, v_y, remodelling, speed (whole if they hold at most DUMP_SAMPLE values each, else the same seeded sample of
+DUMP_SAMPLE of their flat indices in every run) and the per-pair statistics.
 
 `python bench.py --gpus N` (N > 1) without a torch.distributed environment starts the N ranks itself (fresh child
 processes through torch.distributed.run, before anything touches the GPU) and relays rank 0's line.
@@ -24,6 +31,41 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
+DUMP_SAMPLE = 1 << 20  # values per dumped field: 4 fields x 8 MB at most
+DUMP_STATS = ("iterations", "converged", "relative_residual", "L1_functional", "speed_functional", "remodelling_functional")
+
+
+def sample_index(numel, limit=DUMP_SAMPLE):
+    """Flat indices of a dumped field: all of them if there are at most `limit`, else a fixed, seeded, sorted sample."""
+    import numpy as np
+    if numel <= limit:
+        return None
+    return np.sort(np.random.default_rng(20251016).choice(numel, limit, replace=False))
+
+
+def dump_outputs(path, fields, stats, limit=DUMP_SAMPLE):
+    """Write `fields` (name -> list of tensors that concatenate along dim 0 to the field) and the per-pair `stats` as
+    float64 .npy files under `path`.  A field of more than `limit` values is reduced to the values at sample_index()
+    of its flattened concatenation, gathered on the tensors' device."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, parts in fields.items():
+        numel = sum(p.numel() for p in parts)
+        idx = sample_index(numel, limit)
+        if idx is None:
+            arr = torch.cat(list(parts)).cpu().numpy()
+        else:
+            pieces, off = [], 0
+            for p in parts:
+                lo, hi = np.searchsorted(idx, [off, off + p.numel()])
+                local = torch.from_numpy(idx[lo:hi] - off).to(p.device)
+                pieces.append(p.reshape(-1).index_select(0, local).cpu().numpy())
+                off += p.numel()
+            arr = np.concatenate(pieces)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    for name in DUMP_STATS:
+        np.save(os.path.join(path, name + ".npy"), np.asarray(stats[name], dtype=np.float64))
 
 
 def algorithmic_bytes_per_pixel(kernel, coarse_bytes):
@@ -143,15 +185,24 @@ def main():
     ap.add_argument("--warm-start-stride", type=int, default=None, help="0/1: every pair starts from the constant initial fields (library default: 3)")
     ap.add_argument("--krylov-method", type=int, default=None, help="0 BiCGStab only, 1 restarted GMRES only, 2 (library default) BiCGStab with GMRES fallback")
     ap.add_argument("--wobble", type=float, default=0.0, help="time-varying flow of the synthetic stack (0: uniform translation)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the informational variant runs")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the informational figures: per-kernel profile and roofline, variants, "
+                         "vary_regularisation, end-to-end drop-in call, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fields and per-pair statistics of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="(with --full) skip the informational variant runs")
+    ap.add_argument("--no-end-to-end", action="store_true", help="(with --full) skip the host-buffer (PCIe-inclusive) measurement")
     ap.add_argument("--no-allgather", action="store_true")
     ap.add_argument("--gather-chunks", type=int, default=0, help="equal chunks of the rank's pairs whose all-gather overlaps the next solve (default: distributed.chunk_plan)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the all-gather even at world size 1 (test)")
-    ap.add_argument("--profile-table", action="store_true", help="print the per-kernel HIP-event table (stderr)")
+    ap.add_argument("--profile-table", action="store_true", help="(with --full) print the per-kernel HIP-event table (stderr)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.profile_table and not args.full:
+        ap.error("--profile-table needs --full (a plain run does not profile)")
 
     # ---- `python bench.py --gpus N` started by hand: become the launcher of N fresh rank processes.  Nothing has
     # touched the GPU (torch is not even imported) - the parent only relays rank 0's line and the exit code.
@@ -203,7 +254,8 @@ def main():
     n_chunks = len(sizes)
     cp_arg = {"float64": 0, "float32": 1, "bfloat16": 2, "float8": 3}[args.coarse_precision]
     vp_arg = {"float64": 0, "float32": 1, "auto": 2, "coarse_float32": 3}[args.vcycle_precision]
-    # the variant runs below widen the stencil storage of the same context up to float64 (the context re-allocates it)
+    # the variant runs of --full widen the stencil storage of the same context up to float64 (the context re-allocates it);
+    # the batch is sized for that with and without --full, so that both time the same batches
     per_pair = _native.query_workspace(n, n, 1, cp_arg if (args.no_variants or world > 1 or use_dist) else 0, vp_arg)
     free, total = _native.device_memory(local_rank)
     gathered_bytes = 3 * world * P * n * n * 8 if gather else 0
@@ -258,35 +310,39 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up with the full per-kernel profile: finds the dominant kernel class
-    solver.profile_enable(True)
-    solver.profile_filter(-1, -1)
     stats = None
-    for _ in range(max(1, args.warmup)):
-        stats = step()
-    torch.cuda.synchronize()
-    table = solver.profile_table()
-    total_ms = sum(r[3] for r in table) or 1.0
-    # dominant kernel class = largest share of GPU time among the classes with an algorithmic byte count (the streaming
-    # kernels); on tiny stacks the latency-bound set-up kernels (dense inversion, Galerkin products) can be larger
-    with_bytes = [r for r in table if solver.profile_bytes(r[0], r[1]) > 0]
-    dom = max(with_bytes or table, key=lambda r: r[3])
-    alg_total = sum(solver.profile_bytes(r[0], r[1]) for r in table)
-    moved_total = sum(solver.profile_moved(r[0], r[1]) for r in table)
-    counted_ms = sum(r[3] for r in with_bytes)
-    if args.profile_table and rank == 0:
-        for name, lvl, cnt, ms in sorted(table, key=lambda r: -r[3]):
-            gb = solver.profile_bytes(name, lvl) / 1e9
-            mv = solver.profile_moved(name, lvl) / 1e9
-            print(f"  {name:13s} L{lvl:<2d} launches {cnt:7d}  total {ms:10.3f} ms  avg {1e3 * ms / cnt:9.2f} us  "
-                  f"{100 * ms / total_ms:5.1f}%  {gb / (ms * 1e-3) if gb else 0:8.0f} GB/s"
-                  + (f"  ({mv / (ms * 1e-3):.0f} GB/s moved)" if abs(mv - gb) > 1e-6 * gb else ""), file=sys.stderr)
-        print(f"  all kernels: {total_ms:.1f} ms of GPU time per warm-up step set, {alg_total / 1e9:.1f} GB algorithmic "
-              f"({alg_total / 1e9 / (total_ms * 1e-3):.0f} GB/s over all kernel time)", file=sys.stderr)
-    dom_name, dom_level = dom[0], dom[1]
-    warm_steps = max(1, args.warmup)
-    solver.profile_reset()
-    solver.profile_filter(dom_name, dom_level)       # timed region: events only around the dominant kernel
+    if args.full:
+        # ---- warm-up with the full per-kernel profile: finds the dominant kernel class
+        solver.profile_enable(True)
+        solver.profile_filter(-1, -1)
+        for _ in range(max(1, args.warmup)):
+            stats = step()
+        torch.cuda.synchronize()
+        table = solver.profile_table()
+        total_ms = sum(r[3] for r in table) or 1.0
+        # dominant kernel class = largest share of GPU time among the classes with an algorithmic byte count (the streaming
+        # kernels); on tiny stacks the latency-bound set-up kernels (dense inversion, Galerkin products) can be larger
+        with_bytes = [r for r in table if solver.profile_bytes(r[0], r[1]) > 0]
+        dom = max(with_bytes or table, key=lambda r: r[3])
+        alg_total = sum(solver.profile_bytes(r[0], r[1]) for r in table)
+        moved_total = sum(solver.profile_moved(r[0], r[1]) for r in table)
+        counted_ms = sum(r[3] for r in with_bytes)
+        if args.profile_table and rank == 0:
+            for name, lvl, cnt, ms in sorted(table, key=lambda r: -r[3]):
+                gb = solver.profile_bytes(name, lvl) / 1e9
+                mv = solver.profile_moved(name, lvl) / 1e9
+                print(f"  {name:13s} L{lvl:<2d} launches {cnt:7d}  total {ms:10.3f} ms  avg {1e3 * ms / cnt:9.2f} us  "
+                      f"{100 * ms / total_ms:5.1f}%  {gb / (ms * 1e-3) if gb else 0:8.0f} GB/s"
+                      + (f"  ({mv / (ms * 1e-3):.0f} GB/s moved)" if abs(mv - gb) > 1e-6 * gb else ""), file=sys.stderr)
+            print(f"  all kernels: {total_ms:.1f} ms of GPU time per warm-up step set, {alg_total / 1e9:.1f} GB algorithmic "
+                  f"({alg_total / 1e9 / (total_ms * 1e-3):.0f} GB/s over all kernel time)", file=sys.stderr)
+        dom_name, dom_level = dom[0], dom[1]
+        warm_steps = max(1, args.warmup)
+        solver.profile_reset()
+        solver.profile_filter(dom_name, dom_level)       # timed region: events only around the dominant kernel
+    else:
+        for _ in range(args.warmup):
+            step()
 
     # ---- timed region
     barrier()
@@ -295,7 +351,8 @@ def main():
         stats = step()
     barrier()
     dt = time.perf_counter() - t0
-    cnt, ms = solver.profile_get(dom_name, dom_level)
+    if args.full:
+        cnt, ms = solver.profile_get(dom_name, dom_level)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -303,27 +360,6 @@ def main():
 
     pairs_total = world * P * args.steps
     value = pairs_total / dt
-    li, lj = solver.level_shape(dom_level)
-    units = solver.profile_units(dom_name, dom_level)      # frame pairs actually processed, summed over launches
-    pix_per_launch = (units / cnt) * li * lj if cnt else 0.0
-    alg_bytes = solver.profile_bytes(dom_name, dom_level)   # exact: summed by the library per launch
-    moved_bytes = solver.profile_moved(dom_name, dom_level)
-    solver.profile_enable(False)
-    bpp = algorithmic_bytes_per_pixel(dom_name, coarse_bytes)
-    avg_s = (ms / cnt) * 1e-3 if cnt else float("nan")
-    bytes_per_launch = (alg_bytes / cnt) if (cnt and alg_bytes > 0) else (bpp * pix_per_launch if bpp else None)
-    achieved = (bytes_per_launch / avg_s) / 1e9 if (bytes_per_launch and cnt) else None
-    achieved_moved = (moved_bytes / cnt / avg_s / 1e9) if (cnt and moved_bytes > 0) else achieved
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    # the PMC passes were taken with all pairs of the stack in one batch; with chunked solves (multi-GPU overlap) a
-    # launch processes fewer pairs and the per-launch traffic figure does not apply
-    if os.path.exists(tpath) and B >= P and n_chunks == 1 and not args.wobble:
-        try:
-            tj = json.load(open(tpath))
-            traffic = tj.get(f"{dom_name}_L{dom_level}_{n}x{n}x{T}", {}).get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
     if world == 1:
         workload = (f"{n}x{n}x{T} synthetic translating texture (seed {seed}), speed_alpha=1, remodelling_alpha=1e4, "
                     f"rtol={args.rtol:g}, all {P} pairs solved to the stopping rule")
@@ -344,28 +380,56 @@ def main():
                    "allgather": gathered is not None, "gather_chunks": n_chunks, "chunk_sizes": sizes,
                    "iterations_max": int(stats["iterations"].max()), "iterations_mean": float(stats["iterations"].mean()),
                    "relres_max": float(stats["relative_residual"].max()),
-                   "converged": bool(stats["converged"].all())},
+                   "converged": bool(stats["converged"].all())}}
+    if args.full:
+        li, lj = solver.level_shape(dom_level)
+        units = solver.profile_units(dom_name, dom_level)      # frame pairs actually processed, summed over launches
+        pix_per_launch = (units / cnt) * li * lj if cnt else 0.0
+        alg_bytes = solver.profile_bytes(dom_name, dom_level)   # exact: summed by the library per launch
+        moved_bytes = solver.profile_moved(dom_name, dom_level)
+        solver.profile_enable(False)
+        bpp = algorithmic_bytes_per_pixel(dom_name, coarse_bytes)
+        avg_s = (ms / cnt) * 1e-3 if cnt else float("nan")
+        bytes_per_launch = (alg_bytes / cnt) if (cnt and alg_bytes > 0) else (bpp * pix_per_launch if bpp else None)
+        achieved = (bytes_per_launch / avg_s) / 1e9 if (bytes_per_launch and cnt) else None
+        achieved_moved = (moved_bytes / cnt / avg_s / 1e9) if (cnt and moved_bytes > 0) else achieved
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        # the PMC passes were taken with all pairs of the stack in one batch; with chunked solves (multi-GPU overlap) a
+        # launch processes fewer pairs and the per-launch traffic figure does not apply
+        if os.path.exists(tpath) and B >= P and n_chunks == 1 and not args.wobble:
+            try:
+                tj = json.load(open(tpath))
+                traffic = tj.get(f"{dom_name}_L{dom_level}_{n}x{n}x{T}", {}).get("hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
         # `achieved` = the bytes one launch HAS TO MOVE (every stream read / written once per pass) over the
         # average launch time from HIP events on the solver's stream; `frac` = achieved / peak is an HBM fraction.  `traffic` is
         # the PMC figure of the same launch (halo re-reads included) and is to be compared with `bytes_per_launch`.
         # `effective_per_sweep` counts SURVEY.md 8(d)'s 80 B per pixel for EVERY sweep a pass performs (the level-0 pass performs
         # two): a rate of work, not of traffic - it may exceed the peak and is not a roofline fraction.
-        "roofline": {"bound": "hbm", "kernel": f"{dom_name}@L{dom_level}", "achieved": achieved_moved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": (achieved_moved / HBM_PEAK_GBS) if achieved_moved else None, "traffic": traffic,
-                     "traffic_over_moved": (traffic / (moved_bytes / cnt)) if (traffic and cnt and moved_bytes) else None,
-                     "launches": cnt, "pairs_per_launch": (units / cnt) if cnt else None, "avg_launch_us": 1e6 * avg_s if cnt else None,
-                     "bytes_per_launch": (moved_bytes / cnt) if cnt else None,
-                     "effective_per_sweep": {"bytes_per_launch": bytes_per_launch, "rate": achieved, "unit": "GB/s"},
-                     "share_of_gpu_time": dom[3] / total_ms,
-                     # the whole solve, not only the dominant kernel: bytes every byte-counted launch of the warm-up step(s)
-                     # has to move over the step time (set-up kernels without a byte count count as time only)
-                     "whole_solve": {"bytes_per_step": moved_total / warm_steps,
-                                     "achieved": moved_total / warm_steps / (dt / args.steps) / 1e9,
-                                     "frac": moved_total / warm_steps / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                                     "effective_per_sweep": alg_total / warm_steps / (dt / args.steps) / 1e9,
-                                     "kernel_time_share_with_byte_count": counted_ms / total_ms}},
-    }
-    if world == 1 and not use_dist and not args.no_variants:
+        out["roofline"] = {"bound": "hbm", "kernel": f"{dom_name}@L{dom_level}", "achieved": achieved_moved, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": (achieved_moved / HBM_PEAK_GBS) if achieved_moved else None, "traffic": traffic,
+                           "traffic_over_moved": (traffic / (moved_bytes / cnt)) if (traffic and cnt and moved_bytes) else None,
+                           "launches": cnt, "pairs_per_launch": (units / cnt) if cnt else None, "avg_launch_us": 1e6 * avg_s if cnt else None,
+                           "bytes_per_launch": (moved_bytes / cnt) if cnt else None,
+                           "effective_per_sweep": {"bytes_per_launch": bytes_per_launch, "rate": achieved, "unit": "GB/s"},
+                           "share_of_gpu_time": dom[3] / total_ms,
+                           # the whole solve, not only the dominant kernel: bytes every byte-counted launch of the warm-up step(s)
+                           # has to move over the step time (set-up kernels without a byte count count as time only)
+                           "whole_solve": {"bytes_per_step": moved_total / warm_steps,
+                                           "achieved": moved_total / warm_steps / (dt / args.steps) / 1e9,
+                                           "frac": moved_total / warm_steps / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                                           "effective_per_sweep": alg_total / warm_steps / (dt / args.steps) / 1e9,
+                                           "kernel_time_share_with_byte_count": counted_ms / total_ms}}
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step, before the runs of --full overwrite it
+        names = ("v_x", "v_y", "remodelling", "speed")
+        fields = {k: [o[j] for o in outs] for j, k in enumerate(names)}
+        if gathered is not None:
+            fields.update({k: [g] for k, g in zip(names, gathered)})
+        dump_outputs(args.dump_outputs, fields, stats)
+    if args.full and world == 1 and not use_dist and not args.no_variants:
         # informational, not the headline: the same step with other settings (headline = library defaults: float8 /
         # float32 row-sum-preserving Galerkin stencils, float64 V-cycle vectors, two-phase warm start).  Arithmetic, Krylov vectors, stopping rule
         # and results are float64 in all of them.
@@ -433,7 +497,7 @@ def main():
                 "what": "the stack as two halves solved at the same time by two contexts (two streams, two host threads)"}
             for sub in subs:
                 sub.close()
-    if world == 1 and not use_dist and not args.no_variants:
+    if args.full and world == 1 and not use_dist and not args.no_variants:
         # the reference's second consumer of the path: vary_regularisation (OF.py:1918-1998) in the shape of its own sweep,
         # AVOF.py:608-615 - a 20 x 20 logspace(-1, 4) grid of (speed_alpha, remodelling_alpha) on a down-sampled 8-bit
         # pair with smoothing_sigma = 1; one native call, host arrays in, summary tables out
@@ -453,7 +517,7 @@ def main():
             "what": "vary_regularisation(128x128x3 8-bit texture, logspace(-1, 4, 20)^2, smoothing_sigma=1, use_direct_solver=True) - "
                     "the reference script's own call, AVOF.py:608-615: 400 combinations x 2 frame pairs"}
         of.release_device_memory()
-    if world == 1 and not use_dist and not args.no_end_to_end:
+    if args.full and world == 1 and not use_dist and not args.no_end_to_end:
         # end-to-end rate of the drop-in call, pageable numpy arrays in and out (the reference's
         # contract), i.e. including the float64 copy, H2D of the movie and D2H of the four result stacks.  Never `value`.
         from opticalflow_amd import optical_flow as of
@@ -475,7 +539,7 @@ def main():
                                      "in and out: float64 copy, H2D, solve, D2H of v_x, v_y, speed, remodelling "
                                      f"({movie_host.nbytes / 1e9:.1f} GB up, {4 * P * n * n * 8 / 1e9:.1f} GB down)"}
         del movie_host
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(n, seed)
     if rank == 0:
         sys.stdout.flush()

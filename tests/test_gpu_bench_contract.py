@@ -1,10 +1,12 @@
-"""The bench.py contract the driver relies on: one JSON line on stdout with the agreed keys, for the plain single-GPU
-launch and for the torch.distributed launch (one rank here; RCCL init, chunked solve + asynchronous all-gather path)."""
+"""The bench.py contract the driver relies on: one JSON line on stdout with the agreed keys, for the single-GPU launch
+and for the torch.distributed launch (one rank here; RCCL init, chunked solve + asynchronous all-gather path), with
+--full (roofline, CPU baseline, end-to-end) and without it (the headline only, --dump-outputs)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -41,7 +43,7 @@ def check(d, n_gpus):
 
 
 def test_single_gpu_line_with_cpu_baseline():
-    d = run([sys.executable, "bench.py"] + SMALL)
+    d = run([sys.executable, "bench.py", "--full"] + SMALL)
     check(d, 1)
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["unit"] == "frame-pairs/s" and c["sample"]
@@ -55,6 +57,45 @@ def test_single_gpu_line_with_cpu_baseline():
 
 def test_distributed_launch_line():
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-             "--master-port", "29517", "bench.py", "--gpus", "1", "--force-dist", "--no-cpu-baseline", "--gather-chunks", "3"] + SMALL)
+             "--master-port", "29517", "bench.py", "--full", "--gpus", "1", "--force-dist", "--no-cpu-baseline", "--gather-chunks", "3"] + SMALL)
     check(d, 1)
     assert d["config"]["allgather"] is True and d["config"]["gather_chunks"] == 3 and d["config"]["chunk_sizes"] == [3, 3, 3]
+
+
+PLAIN_KEYS = KEYS - {"roofline"}
+FULL_ONLY = {"roofline", "variants", "end_to_end", "cpu_baseline"}
+
+
+def test_plain_line_and_output_dump(tmp_path):
+    """Without --full: the headline line only; --dump-outputs writes the last timed step's fields and statistics, the
+    same in two runs with the same arguments."""
+    args = ["--size", "256", "--frames", "10", "--steps", "2", "--warmup", "1"]
+    runs = [run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path / r)] + args) for r in "ab"]
+    for d in runs:
+        assert PLAIN_KEYS <= set(d) and not FULL_ONLY & set(d)
+        assert d["metric"] == "frame-pairs/sec" and d["unit"] == "frame-pairs/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["steps"] == 2 and d["warmup"] == 1 and d["config"]["converged"] is True
+        assert d["value"] == pytest.approx(9 * 1e3 / d["ms_per_step"])       # 9 pairs per step
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"v_x.npy", "v_y.npy", "remodelling.npy", "speed.npy", "iterations.npy", "relative_residual.npy"} <= set(names)
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, b, err_msg=f)
+    vx = np.load(tmp_path / "a" / "v_x.npy")
+    assert vx.shape == (9, 256, 256) and np.isfinite(vx).all()
+    it = np.load(tmp_path / "a" / "iterations.npy")
+    assert it.shape == (9,) and it.mean() == pytest.approx(runs[0]["config"]["iterations_mean"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 * 2 ** 20
+
+
+def test_plain_dump_samples_a_large_field(tmp_path):
+    """A field of more than DUMP_SAMPLE values is dumped as its seeded sample."""
+    import bench
+    d = run([sys.executable, "bench.py", "--size", "512", "--frames", "6", "--steps", "1", "--warmup", "0",
+             "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 1 and d["config"]["converged"] is True
+    for k in ("v_x", "v_y", "remodelling", "speed"):
+        a = np.load(tmp_path / (k + ".npy"))
+        assert a.shape == (bench.DUMP_SAMPLE,) and a.dtype == np.float64 and np.isfinite(a).all()
