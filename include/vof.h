@@ -89,11 +89,12 @@ typedef struct vof_pair_stats {
     double L1_functional;      /* OF.py:1178-1180 */
     double speed_functional;   /* OF.py:1181-1182 (the true one; the dict-level bug is applied by the caller) */
     double remodelling_functional; /* OF.py:1183 */
-    double batch_ms;           /* GPU time (HIP events on the solver's stream) of the batch this pair was solved in: hierarchy
-                                  set-up + Krylov iteration + epilogue of batch_pairs pairs advancing together, i.e. this
-                                  pair's share is batch_ms / batch_pairs (the reference prints per-pair wall times,
-                                  OF.py:1073-1076, 1156-1157); a pair re-solved by a fallback carries the sum of its shares */
-    int32_t batch_pairs;       /* pairs in that batch */
+    double batch_ms;           /* GPU time (HIP events on the stream of the lane that solved it, see VOF_LANES) of the batch this
+                                  pair was solved in: hierarchy set-up + Krylov iteration + epilogue of batch_pairs pairs advancing
+                                  together, i.e. this pair's share is batch_ms / batch_pairs (the reference prints per-pair wall
+                                  times, OF.py:1073-1076, 1156-1157); a pair re-solved by a fallback carries the sum of its shares.
+                                  The batches of concurrent lanes overlap in time: their shares add up to more than the wall time */
+    int32_t batch_pairs;       /* pairs in that batch (a per-lane batch when the solve ran in lanes) */
     int32_t reserved;          /* 0 */
 } vof_pair_stats;
 
@@ -142,6 +143,13 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *   VOF_FOLD_STORED=1          stored levels: coarse-grid correction interpolated inside the first post-sweep
  *   VOF_SKIP_COLOUR0=0         W-cycle revisits: full first pre-smoothing sweep (default: colour 0 is left alone, same bits)
  *   VOF_TRACE=1                direct preconditioner: progress lines on stderr
+ * Read at every vof_solve_stack_dev call (speed only; per pair the same arithmetic, partial sums may add in another order):
+ *   VOF_LANES=1|2|3            the multigrid solve of the stack as this many concurrent pair groups ("lanes"), each on a stream
+ *                              and host thread of its own with an equal share of the context's pair slots (default 2); lanes
+ *                              join between the two warm-start phases and before the direct re-solve, which runs on the
+ *                              context's stream.  One lane while vof_profile_enable is on or with VOF_DEBUG_SYNC;
+ *                              vof_solve_stack_host and vof_vary_regularisation_host always run one
+ *   VOF_LANES_MIN_MPIX=x       fewer lanes while a lane's share of a phase would be below x Mpixel of frame pairs (default 16)
  * Debug switches (fault attribution; they change timing, never results):
  *   VOF_DEBUG_SYNC=1           the context's stream is synchronised and asked for its error after every launch scope; the
  *                              first failure is reported on stderr and appended to every later error text as

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -38,6 +39,7 @@ int coarsest_max() {                 // experiment switch VOF_COARSEST_MAX=3..9 
     return COARSEST_MAX;
 }
 constexpr int MAX_PROF_RECS = 32768;
+constexpr int MAX_LANES = 3;        // concurrent pair groups of one device solve (solve_range_dev, VOF_LANES)
 constexpr int AUTO_F64_AFTER = 8;   // vcycle_precision == 2: switch the V-cycle vectors to float64 after this many iterations
 
 struct Level {
@@ -194,6 +196,15 @@ struct vof_ctx {
     bool dbg_canary = false;     // VOF_DEBUG_CANARY=1: every device buffer sits between two guard pages of a known pattern
     bool dbg_alloc_log = false;  // VOF_DEBUG_ALLOC_LOG=1: base / size / name of every device buffer on stderr
     bool dbg_poison = false;     // VOF_DEBUG_POISON=1: every new device buffer is filled with 0xFF bytes (NaN as float / double, -1 as int)
+    size_t part_per_pair = 0;    // doubles of `partials` per batch slot
+    // lanes (solve_range_dev): a lane is a copy of the context whose per-pair buffers are views of the slots [lane_lo, lane_lo +
+    // lane_slots) of the parent's, with a stream and batch events of its own (make_lane); it allocates nothing itself
+    vof_ctx* lane_parent = nullptr;
+    int lane_lo = 0, lane_slots = 0;
+    int dir_ok = -1;             // lane: the parent's direct_ok_for_fallback, decided before the lanes start (-1: ask)
+    hipStream_t lane_stream[MAX_LANES] = {};
+    hipEvent_t lane_ev[MAX_LANES][2] = {};
+    hipEvent_t ev_fork = nullptr;
 };
 
 static std::string g_create_error;
@@ -1144,13 +1155,35 @@ int gmres_buffers(vof_ctx* c, int want_m) {
 // Restarted, right-preconditioned GMRES on the pairs that are not converged yet: x = x_0 + M (V_k y), M = one
 // multigrid cycle (float64 vectors), restart from the true residual b - A x.  `iterations` keeps counting Krylov steps
 // (one cycle application each) on top of the BiCGStab iterations already spent.
+// A lane's GMRES buffers are the parent's (allocated on first use, under a lock: two lanes may ask at once), viewed at the
+// lane's slots; the basis keeps the parent's stride of B pairs per vector.  0, or -3 when the basis does not fit.
+std::mutex g_lane_alloc;
+int lane_gmres_attach(vof_ctx* c, bool basis, int want_m) {
+    vof_ctx* p = c->lane_parent;
+    std::lock_guard<std::mutex> lock(g_lane_alloc);
+    int rc = 0;
+    if (!p->gm_cycle) rc = dev_alloc(p, &p->gm_cycle, (size_t)p->B);
+    if (!rc && basis && !p->gm_V) rc = gmres_buffers(p, want_m);
+    if (rc) { c->err = p->err; p->err.clear(); return rc; }
+    const size_t lo = (size_t)c->lane_lo;
+    c->gm_cycle = p->gm_cycle + lo;
+    if (p->gm_V) {
+        c->gm_V = p->gm_V + lo * 3 * c->L[0].npts;
+        c->gm_state = p->gm_state + lo;
+        c->gm_partials = p->gm_partials + lo * (GM_NV + 1) * c->nblk;
+        c->gm_m = p->gm_m;
+    }
+    return 0;
+}
+
 int gmres_phase(vof_ctx* c, int np, int* handed_over) {
     const vof_params& P = c->prm;
     hipStream_t s = c->stream;
     const size_t len = 3 * c->L[0].npts;
     const size_t vstride = (size_t)c->B * len;
     if (!c->gm_cycle) {   // flags are needed before the (large) basis is
-        if (int rc = dev_alloc(c, &c->gm_cycle, (size_t)c->B)) return rc;
+        if (c->lane_parent) { if (int rc = lane_gmres_attach(c, false, 0)) return rc; }
+        else if (int rc = dev_alloc(c, &c->gm_cycle, (size_t)c->B)) return rc;
     }
     k_gm_begin<<<(np + 63) / 64, 64, 0, s>>>(c->sc, c->active, c->gm_cycle, np, P.max_iterations);
     dbg_sync_check(c, "gm_begin", 0);
@@ -1159,7 +1192,8 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
     if (nact == 0) return 0;
     *handed_over = nact;
     if (!c->gm_V) {
-        int rc = gmres_buffers(c, P.gmres_restart > 0 ? P.gmres_restart : 100);
+        const int want = P.gmres_restart > 0 ? P.gmres_restart : 100;
+        int rc = c->lane_parent ? lane_gmres_attach(c, true, want) : gmres_buffers(c, want);
         if (rc == -3) { c->err.clear(); return 0; }   // no room: leave the pairs unconverged (reported per pair)
         if (rc) return rc;
     }
@@ -1296,7 +1330,7 @@ int direct_ld(const vof_ctx* c) {
 
 // The automatic re-solve (preconditioner 2) needs nothing but room for the buffers.
 int direct_capacity(vof_ctx* c, int want);
-bool direct_ok_for_fallback(vof_ctx* c) { return direct_capacity(c, 1) >= 1; }
+bool direct_ok_for_fallback(vof_ctx* c) { return c->dir_ok >= 0 ? c->dir_ok != 0 : direct_capacity(c, 1) >= 1; }
 
 // device bytes the direct preconditioner needs per pair in flight
 size_t direct_bytes_per_pair(const vof_ctx* c) {
@@ -1778,6 +1812,11 @@ void vof_destroy(vof_ctx* c) {
         if (c->ev_uploaded[i]) hipEventDestroy(c->ev_uploaded[i]);
     }
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
+    for (int i = 0; i < MAX_LANES; ++i) {
+        if (c->lane_stream[i]) hipStreamDestroy(c->lane_stream[i]);
+        for (int j = 0; j < 2; ++j) if (c->lane_ev[i][j]) hipEventDestroy(c->lane_ev[i][j]);
+    }
+    if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1908,7 +1947,8 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     {
         int nblk_apply = ((l0.nj + AP_OUT - 1) / AP_OUT) * ((l0.ni + 31) / 32 + 1);   // smallest band height: 32 rows
         nblk_apply = std::max(nblk_apply, ((l0.nj + 99) / 100) * ((l0.ni + 1 + 31) / 32 + 1));   // k_sweep0m's trailing stage (strips >= 108 columns)
-        if (int rc = dev_alloc(c, &c->partials, (size_t)B * 3 * std::max(c->nblk, nblk_apply))) return rc;
+        c->part_per_pair = (size_t)3 * std::max(c->nblk, nblk_apply);
+        if (int rc = dev_alloc(c, &c->partials, (size_t)B * c->part_per_pair)) return rc;
     }
     if (int rc = dev_alloc(c, &c->sc, (size_t)B)) return rc;
     if (int rc = dev_alloc(c, &c->active, (size_t)B)) return rc;
@@ -1935,13 +1975,171 @@ int vof_create(vof_ctx** out, int device_id, int n_i, int n_j, int max_pairs_in_
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
+// ---- lanes: the pairs of one device solve as concurrent groups, each on a stream of its own
+//
+// One stream runs a solve as a chain of dependent launches: each one ends with a tail in which the chip drains, many are
+// under-filled by design (the coarse levels; k_tail_cycle runs one workgroup per pair), and the Krylov loop waits on the host
+// once per iteration.  Two groups of pairs on two streams fill each other's gaps.  A lane is driven by
+// a host thread of its own because its Krylov loop blocks on the host; one thread polling the events of all lanes instead
+// would have to turn solve_batch inside out into a resumable state machine.
+//
+// Lanes of this solve: VOF_LANES (1 .. MAX_LANES, default 2), fewer while a lane's share of a phase would drop below
+// VOF_LANES_MIN_MPIX (default 16) Mpixel of pairs - the same kind of rule as the two-phase one; one lane while profiling
+// (per-launch times mean something only when launches do not overlap) or with VOF_DEBUG_SYNC.
+int lanes_for(const vof_ctx* c, int pairs_per_phase) {
+    if (c->prof || c->dbg_sync) return 1;
+    int n = 2;
+    if (const char* e = getenv("VOF_LANES")) { const int v = atoi(e); if (v >= 1 && v <= MAX_LANES) n = v; }
+    double mpix = 16.0;
+    if (const char* e = getenv("VOF_LANES_MIN_MPIX")) { const double v = atof(e); if (v >= 0.0) mpix = v; }
+    n = std::min(n, c->B);
+    while (n > 1 && (pairs_per_phase < n || (double)pairs_per_phase / n * c->Ni * c->Nj < mpix * 1e6)) --n;
+    return n;
+}
+
+// Pairs a context runs in one batch: its own B, or a lane's share of the parent's slots.
+inline int batch_slots(const vof_ctx* c) { return c->lane_parent ? c->lane_slots : c->B; }
+
+// Lane i of n of context c: a copy of c whose per-pair buffers view the slots [B i / n, B (i + 1) / n).  Every kernel addresses
+// a pair's data as base + pair * (per-pair size), with a per-pair size no larger than what the buffer holds per slot (B of
+// them), so offset bases keep the lanes apart.  Shared and read-only: the level geometry, the parameters, the tail operation
+// list, the frames and outputs (PairParam tables and pointers of the range), warm_x (indexed by the phase-1 position of a pair).
+int make_lane(vof_ctx* c, int i, int n, vof_ctx* L) {
+    if (!c->lane_stream[i]) {
+        HIPCHK(hipStreamCreate(&c->lane_stream[i]));
+        for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&c->lane_ev[i][j]));
+    }
+    *L = *c;
+    const size_t lo = (size_t)c->B * i / n;
+    L->lane_parent = c;
+    L->lane_lo = (int)lo;
+    L->lane_slots = (int)((size_t)c->B * (i + 1) / n - lo);
+    for (int j = 0; j < MAX_LANES; ++j) { L->lane_stream[j] = nullptr; L->lane_ev[j][0] = L->lane_ev[j][1] = nullptr; }
+    L->ev_fork = nullptr;
+    L->stream = c->lane_stream[i];
+    L->own_stream = false;
+    L->ev_batch[0] = c->lane_ev[i][0];
+    L->ev_batch[1] = c->lane_ev[i][1];
+    L->allocs.clear();
+    L->recs.clear();
+    L->free_events.clear();
+    L->prof = false;
+    L->err.clear();
+    L->h_bounce = nullptr;
+    L->pp = nullptr;
+    L->guess_src = nullptr;
+    L->gmres_pairs = 0;
+    L->dir_ok = direct_ok_for_fallback(c) ? 1 : 0;
+    const size_t len0 = 3 * c->L[0].npts;
+    for (double** v : {&L->kx, &L->kb, &L->kr, &L->krh, &L->kp, &L->kv, &L->kt, &L->ky, &L->kz, &L->b32, &L->gm_V})
+        if (*v) *v += lo * len0;
+    const int nl = (int)c->L.size();
+    for (int l = 0; l < nl; ++l) {   // vectors: sized for float64 (a float32 view of a slot uses its first half)
+        Level& lv = L->L[l];
+        const size_t vb = 3 * lv.npts * sizeof(double);
+        const size_t cb = (size_t)(nl == 1 ? 81 * 8 : c->c_bytes_per_point) * CLay(lv.ni, lv.nj).plane;
+        for (void** q : {&lv.x, &lv.b, &lv.r, &lv.x2}) if (*q) *q = (char*)*q + lo * vb;
+        if (lv.C) lv.C = (char*)lv.C + lo * cb;
+    }
+    L->W += lo * c->nd * 2 * c->nd;
+    L->invT += lo * c->nd * c->nd;
+    L->partials += lo * c->part_per_pair;
+    L->sc += lo; L->h_sc += lo;
+    L->active += lo; L->h_active += lo;
+    L->func3 += 3 * lo; L->h_func3 += 3 * lo;
+    if (L->pp_buf) L->pp_buf += lo;
+    if (L->warm_src) L->warm_src += lo;
+    if (L->gm_cycle) L->gm_cycle += lo;
+    if (L->gm_state) L->gm_state += lo;
+    if (L->gm_partials) L->gm_partials += lo * (GM_NV + 1) * c->nblk;
+    return 0;
+}
+
+// Runs fn(lane, i) for the n lanes of c, each on a host thread of its own and after the work queued so far on c's stream, and
+// joins them all (a lane's stream is drained before its thread ends).  The first failing lane's message goes to c->err.
+template <typename F>
+int run_lanes(vof_ctx* c, int n, F&& fn) {
+    std::vector<vof_ctx> lanes((size_t)n);
+    for (int i = 0; i < n; ++i)
+        if (int rc = make_lane(c, i, n, &lanes[i])) return rc;
+    if (!c->ev_fork) HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c->ev_fork, c->stream));
+    for (int i = 0; i < n; ++i) HIPCHK(hipStreamWaitEvent(lanes[i].stream, c->ev_fork, 0));
+    std::vector<int> rc((size_t)n, 0);
+    std::vector<std::thread> th;
+    auto body = [&](int i) {
+        vof_ctx* L = &lanes[i];
+        if (hipSetDevice(c->device) != hipSuccess) { L->err = "hipSetDevice failed"; rc[i] = -2; return; }
+        rc[i] = fn(L, i);
+        const hipError_t e = hipStreamSynchronize(L->stream);
+        if (!rc[i] && e != hipSuccess) { L->err = std::string("stream synchronize failed: ") + hipGetErrorString(e); rc[i] = -2; }
+    };
+    try {
+        for (int i = 0; i < n; ++i) th.emplace_back(body, i);
+    } catch (...) {   // no thread: the remaining lanes run here, one after the other
+        for (int i = (int)th.size(); i < n; ++i) body(i);
+    }
+    for (auto& t : th) t.join();
+    for (int i = 0; i < n; ++i) c->gmres_pairs += lanes[i].gmres_pairs;
+    for (int i = 0; i < n; ++i)
+        if (rc[i]) { c->err = "lane " + std::to_string(i) + ": " + lanes[i].err; return rc[i]; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Entries [a, b) of `list` (pairs of the stack) as one phase of the two-phase solve on context or lane c, in batches of its
+// slots.  Phase 1 saves each solution in warm_x at the pair's position in the list and marks it in `usable`; phase 2 starts
+// every pair from the saved solution of its nearest phase-1 neighbour (all of phase 1 has finished by then).
+static int two_phase_part(vof_ctx* c, const double* movie, const std::vector<int>& list, size_t a, size_t b, bool phase2, int stride,
+                          std::vector<char>& usable, double* v_x, double* v_y, double* remodelling, double* speed, vof_pair_stats* stats) {
+    const vof_params prm = c->prm;
+    const size_t len = 3 * c->L[0].npts;
+    const int cap = batch_slots(c);
+    const int n1 = (int)usable.size();
+    std::vector<PairParam> hp((size_t)cap);
+    std::vector<int> hsrc((size_t)cap);
+    std::vector<vof_pair_stats> st((size_t)cap);
+    for (size_t o = a; o < b; o += (size_t)cap) {
+        const int np = (int)std::min<size_t>((size_t)cap, b - o);
+        for (int i = 0; i < np; ++i) {
+            const int k = list[o + i];
+            hp[i] = PairParam{prm.speed_alpha, prm.remodelling_alpha, k, k};
+            const int src = std::min((k + stride / 2) / stride, n1 - 1);
+            hsrc[i] = phase2 && usable[src] ? src : -1;   // -1: constant initial fields (a failed pair must not poison its neighbours)
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));   // the host tables are re-used
+        HIPCHK(hipMemcpyAsync(c->pp_buf, hp.data(), (size_t)np * sizeof(PairParam), hipMemcpyHostToDevice, c->stream));
+        if (phase2) HIPCHK(hipMemcpyAsync(c->warm_src, hsrc.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        c->pp = c->pp_buf;
+        c->guess_src = phase2 ? c->warm_src : nullptr;
+        int rc = solve_batch(c, movie, np, v_x, v_y, remodelling, speed, st.data());
+        c->pp = nullptr;
+        c->guess_src = nullptr;
+        if (rc) return rc;
+        if (!phase2) {
+            HIPCHK(hipMemcpyAsync(c->warm_x + o * len, c->kx, (size_t)np * len * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            for (int i = 0; i < np; ++i) usable[o + i] = st[i].converged && std::isfinite(st[i].relative_residual);
+        }
+        if (stats)
+            for (int i = 0; i < np; ++i) stats[list[o + i]] = st[i];
+    }
+    return 0;
+}
+
 // Two-phase solve of a stack with warm starts (the reference warm-starts pair k from pair k-1, OF.py:803-806, which
 // serialises the pairs; here every stride-th pair is solved first from the constant initial fields, then all the others
 // start from the solution of their nearest solved neighbour).  Pairs are addressed through the PairParam table
-// (frame / output slot), so both phases are ordinary batches.
+// (frame / output slot), so both phases are ordinary batches.  With several lanes each phase is cut into equal contiguous
+// shares and the lanes join between the phases (a warm pair's source may be another lane's).
 static int solve_stack_two_phase(vof_ctx* c, const double* movie, int P, double* v_x, double* v_y, double* remodelling,
-                                 double* speed, vof_pair_stats* stats, int stride) {
-    const vof_params prm = c->prm;
+                                 double* speed, vof_pair_stats* stats, int stride, int lanes) {
     const size_t len = 3 * c->L[0].npts;
     const int B = c->B;
     std::vector<int> first, rest;
@@ -1955,39 +2153,19 @@ static int solve_stack_two_phase(vof_ctx* c, const double* movie, int P, double*
         if (int rc = dev_alloc(c, &c->warm_x, (size_t)n1 * len)) return rc;
         c->warm_cap = (size_t)n1 * len;
     }
-    std::vector<PairParam> hp((size_t)B);
-    std::vector<int> hsrc((size_t)B);
-    std::vector<vof_pair_stats> st((size_t)B);
     std::vector<char> usable((size_t)n1, 0);   // phase-1 solutions that may seed a neighbour: converged and finite
-    auto run = [&](const std::vector<int>& list, bool phase2) -> int {
-        for (size_t o = 0; o < list.size(); o += (size_t)B) {
-            const int np = (int)std::min<size_t>((size_t)B, list.size() - o);
-            for (int i = 0; i < np; ++i) {
-                const int k = list[o + i];
-                hp[i] = PairParam{prm.speed_alpha, prm.remodelling_alpha, k, k};
-                const int src = std::min((k + stride / 2) / stride, n1 - 1);
-                hsrc[i] = usable[src] ? src : -1;   // -1: constant initial fields (a failed pair must not poison its neighbours)
-            }
-            HIPCHK(hipStreamSynchronize(c->stream));   // the host tables are re-used
-            HIPCHK(hipMemcpyAsync(c->pp_buf, hp.data(), (size_t)np * sizeof(PairParam), hipMemcpyHostToDevice, c->stream));
-            if (phase2) HIPCHK(hipMemcpyAsync(c->warm_src, hsrc.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice, c->stream));
-            c->pp = c->pp_buf;
-            c->guess_src = phase2 ? c->warm_src : nullptr;
-            int rc = solve_batch(c, movie, np, v_x, v_y, remodelling, speed, st.data());
-            c->pp = nullptr;
-            c->guess_src = nullptr;
-            if (rc) return rc;
-            if (!phase2) {
-                HIPCHK(hipMemcpyAsync(c->warm_x + o * len, c->kx, (size_t)np * len * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-                for (int i = 0; i < np; ++i) usable[o + i] = st[i].converged && std::isfinite(st[i].relative_residual);
-            }
-            if (stats)
-                for (int i = 0; i < np; ++i) stats[list[o + i]] = st[i];
+    for (int phase = 0; phase < 2; ++phase) {
+        const std::vector<int>& list = phase ? rest : first;
+        if (lanes <= 1) {
+            if (int rc = two_phase_part(c, movie, list, 0, list.size(), phase == 1, stride, usable, v_x, v_y, remodelling, speed, stats)) return rc;
+            continue;
         }
-        return 0;
-    };
-    if (int rc = run(first, false)) return rc;
-    if (int rc = run(rest, true)) return rc;
+        int rc = run_lanes(c, lanes, [&](vof_ctx* L, int i) {
+            return two_phase_part(L, movie, list, list.size() * i / lanes, list.size() * (i + 1) / lanes, phase == 1, stride, usable,
+                                  v_x, v_y, remodelling, speed, stats);
+        });
+        if (rc) return rc;
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2022,8 +2200,9 @@ static int direct_solve_list(vof_ctx* c, const double* frames, const std::vector
 // batches otherwise.  Outputs are indexed by the pair's position in the range.
 // preconditioner 1: every pair with the direct preconditioner; 2 (default): the multigrid cycle, and the pairs it leaves
 // unconverged (the grad-div dominated regimes) once more with the direct preconditioner if that fits.
+// allow_lanes: the multigrid solve may run as concurrent lanes (lanes_for); the direct solves always run on c's stream.
 static int solve_range_dev(vof_ctx* c, const double* frames, int P, double* v_x, double* v_y, double* remodelling,
-                           double* speed, vof_pair_stats* stats) {
+                           double* speed, vof_pair_stats* stats, bool allow_lanes) {
     const vof_params prm = c->prm;
     const int stride = prm.warm_start_stride;
     const size_t fs = frame_stride(c);
@@ -2038,14 +2217,24 @@ static int solve_range_dev(vof_ctx* c, const double* frames, int P, double* v_x,
     // alone keeps the chip busy (>= 16 Mpixel of frame pairs; measured: 128^2 x 8 loses 45 %, 512^2 x 64 is neutral,
     // 1024^2 x 129 gains 22 %)
     if (stride > 1 && P >= 2 * stride && (double)(P / stride) * (double)c->Ni * (double)c->Nj >= 16e6) {
-        if (int rc = solve_stack_two_phase(c, frames, P, v_x, v_y, remodelling, speed, stats, stride)) return rc;
+        const int lanes = allow_lanes ? lanes_for(c, (P + stride - 1) / stride) : 1;
+        if (int rc = solve_stack_two_phase(c, frames, P, v_x, v_y, remodelling, speed, stats, stride, lanes)) return rc;
     } else {
-        for (int k0 = 0; k0 < P; k0 += c->B) {
-            int np = std::min(c->B, P - k0);
-            int rc = solve_batch(c, frames + (size_t)k0 * fs, np, v_x + (size_t)k0 * fs, v_y + (size_t)k0 * fs,
-                                 remodelling + (size_t)k0 * fs, speed ? speed + (size_t)k0 * fs : nullptr,
-                                 stats ? stats + k0 : nullptr);
-            if (rc) return rc;
+        auto plain = [&](vof_ctx* L, int a, int b) -> int {   // pairs [a, b) in batches of L's slots
+            for (int k0 = a; k0 < b; k0 += batch_slots(L)) {
+                int np = std::min(batch_slots(L), b - k0);
+                int rc = solve_batch(L, frames + (size_t)k0 * fs, np, v_x + (size_t)k0 * fs, v_y + (size_t)k0 * fs,
+                                     remodelling + (size_t)k0 * fs, speed ? speed + (size_t)k0 * fs : nullptr,
+                                     stats ? stats + k0 : nullptr);
+                if (rc) return rc;
+            }
+            return 0;
+        };
+        const int lanes = allow_lanes ? lanes_for(c, P) : 1;
+        if (lanes <= 1) {
+            if (int rc = plain(c, 0, P)) return rc;
+        } else if (int rc = run_lanes(c, lanes, [&](vof_ctx* L, int i) { return plain(L, (int)((long)P * i / lanes), (int)((long)P * (i + 1) / lanes)); })) {
+            return rc;
         }
     }
     if (prm.preconditioner == 2 && stats) {
@@ -2080,7 +2269,7 @@ int vof_solve_stack_dev(vof_ctx* c, const double* movie, int n_frames, const vof
     if (n_frames < 2) { c->err = "need at least two frames"; return -1; }
     if (int rc = check_params(c, p)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    if (int rc = solve_range_dev(c, movie, n_frames - 1, v_x, v_y, remodelling, speed, stats)) return rc;
+    if (int rc = solve_range_dev(c, movie, n_frames - 1, v_x, v_y, remodelling, speed, stats, true)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2269,7 +2458,7 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
             rc_all = fail_msg("stream wait failed", e);
             break;
         }
-        int rc = solve_range_dev(c, frames_buf[set], bt.np, so[0], so[1], so[2], so[3], stats ? stats + bt.k0 : nullptr);
+        int rc = solve_range_dev(c, frames_buf[set], bt.np, so[0], so[1], so[2], so[3], stats ? stats + bt.k0 : nullptr, false);
         if (rc) { rc_all = rc; break; }
         hmark("batch solved");
         wait_batch_regions(bi);
