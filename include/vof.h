@@ -52,7 +52,9 @@ typedef struct vof_params {
                                   bytes); 0: float64 */
     int32_t vcycle_precision;  /* storage of the V-cycle vectors: 0 float64; 1 float32; 2 auto = float32 for the first 8
                                   iterations, float64 afterwards; 3 (default) = float64 on level 0, float32 on the levels below
-                                  for the first 8 iterations.  Krylov vectors, operator products, residuals and the stopping rule are
+                                  for the first 8 iterations - and there also float32 for the vectors that only pass between
+                                  level-0 passes (the pre-smoothed iterate, the cycle's result) where the register-resident
+                                  passes run the whole level-0 part of the cycle.  Krylov vectors, operator products, residuals and the stopping rule are
                                   always FP64; so is the arithmetic of every cycle kernel, except the level-0 smoother of the
                                   float32-vector modes 1 / 2 (k_sweep0p: packed float32 - part of the preconditioner only) */
     int32_t nu_pre_coarse;     /* sweeps on the levels >= 1 (default 1); 0 = same as nu_pre / nu_post */
@@ -128,6 +130,8 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *                              (default: k_sweep0m, two sweeps per pass)
  *   VOF_SWEEP0R=0              level 0, float64 vectors: the LDS-ring pass k_sweep0m instead of the register-resident k_sweep0r
  *   VOF_SWEEP0R_MIN_BLOCKS=n   ... k_sweep0r from n one-wave blocks per launch on (default 512; smaller launches use k_sweep0m)
+ *   VOF_L0_HANDOFF=0           vcycle_precision 3: the level-0 hand-off vectors of the cycle stay float64 (default: float32 where
+ *                              the first 8 iterations run their level-0 passes in k_sweep0r)
  *   VOF_FUSE_B=0               the BiCGStab updates s = r - alpha v and p = r + beta (p - omega v) by their stand-alone kernels instead
  *                              of inside the first pre-smoothing pass of the cycle that consumes them (same bits)
  *   VOF_FUSE_RR=0              level 0: the coarse right-hand side R (b - A x) by the stand-alone residual + restriction kernel instead

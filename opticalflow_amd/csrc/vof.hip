@@ -76,6 +76,10 @@ struct vof_ctx {
     bool emit64 = false;    // vcycle_precision 3: the level-1 visit in progress hands its result up as float64 (see vcycle_t)
     bool vcoarse32 = false; // vcycle_precision 3: float64 vectors on level 0, float32 on the levels below (the two meet in the fused
                             // residual + restriction kernel and in the post-smoothing pass that interpolates the correction)
+    bool l0_handoff = true; // VOF_L0_HANDOFF=0: the level-0 hand-off vectors stay float64 in vcycle_precision 3 (see h32)
+    bool h32 = false;       // the cycles run now store their level-0 hand-off vectors as float32: the pre-smoothed iterate x and the
+                            // cycle's result (y, z).  Set per BiCGStab iteration where handoff32_ok holds, and by vof_debug_vcycle*
+    bool h32_bad = false;   // ... and a level-0 pass of such a cycle was not one of the k_sweep0r passes that store float32
     const PairParam* pp = nullptr;   // per-pair (alpha, beta, frame) overrides of the current batch ("virtual pairs") or nullptr
     PairParam* pp_buf = nullptr;     // device storage for them (B entries, lazy)
     // warm start (two-phase solve of a stack): interior solutions of the phase-1 pairs, and per pair of the current
@@ -415,6 +419,13 @@ inline size_t frame_stride(const vof_ctx* c) { return (size_t)c->Ni * c->Nj; }
         else { using VT = double; __VA_ARGS__; }            \
     } while (0)
 
+// ... for the kernels that read the cycle's results y, z (float32 also under h32)
+#define YDISPATCH(c, ...)                                                  \
+    do {                                                                   \
+        if ((c)->vfloat || (c)->h32) { using VT = float; __VA_ARGS__; }    \
+        else { using VT = double; __VA_ARGS__; }                           \
+    } while (0)
+
 template <typename T> struct TypeTag { typedef T type; };
 // CT = storage format of the stored stencil of level l (word type CW)
 #define CDISPATCH(c, l, ...)                                                                        \
@@ -525,7 +536,7 @@ int krylov_apply(vof_ctx* c, const void* y, double* out, int np, const int* acti
                  int want_yy = 0) {
     if (c->L[0].C) { apply_stored_t<double>(c, 0, (const double*)y, nullptr, out, 0, np, active); return 0; }
     const bool fuse = c->stream_apply && (dotvec || want_yy);
-    if (c->vfloat) apply_fine_t<float, double, double>(c, (const float*)y, nullptr, out, 0, np, active, fuse ? dotvec : nullptr, fuse ? want_yy : 0);
+    if (c->vfloat || c->h32) apply_fine_t<float, double, double>(c, (const float*)y, nullptr, out, 0, np, active, fuse ? dotvec : nullptr, fuse ? want_yy : 0);
     else apply_fine_t<double, double, double>(c, (const double*)y, nullptr, out, 0, np, active, fuse ? dotvec : nullptr, fuse ? want_yy : 0);
     return fuse ? apply_grid(c, np).nblk : 0;
 }
@@ -643,6 +654,9 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
     Level& lv = c->L[l];
     int po = reverse ? 1 : 0;
     int rows = lv.ni + po;
+    // h32: a level-0 pass that does not store float32 would break the cycle (handoff32_ok has promised k_sweep0r throughout)
+    auto h32_refuse = [c](const char* what) { c->err = std::string("float32 level-0 hand-off: ") + what; c->h32_bad = true; };
+    if (l == 0 && c->h32 && !(std::is_same<VT, double>::value && lv.C == nullptr && sweep0m_usable(c))) { h32_refuse("no k_sweep0r pass"); return; }
     if constexpr (std::is_same<VT, double>::value) {
         if (l == 0 && lv.C == nullptr && sweep0m_usable(c)) {
             // k_sweep0m: merged colours, 16-byte accesses, `nsweeps` (1 or 2) sweeps per pass; strips are not shifted by po
@@ -660,18 +674,20 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
                 if (x_in || NSW != 2 || po || !geo.s0r || ecoarse || trail) { c->err = "folded vector update: the cycle did not start with the expected pass"; c->bf_mode = -1; return; }
                 const int mode = c->bf_mode;
                 c->bf_mode = 0;
+                if (c->h32 && !(rr && c->rr_f32)) { h32_refuse("pass from zero without the residual + restriction stage"); return; }
                 Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, 1, c->pp};
                 S0Trail tr{rr ? (double*)c->rr_out : nullptr, nullptr, 0, nullptr};
                 const size_t ldsr = rr ? S0R<2, 2>::LDS_TOTAL : S0R<2, 0>::LDS_TOTAL;
                 const int kci = c->L[1].ni, kcj = c->L[1].nj;
                 {   // I + r(3) + v(3) (+ p_old(3)) in, x(3) + b(3) out (+ the coarse right-hand side)
                     const double cb = rr ? (c->rr_f32 ? 12.0 : 24.0) * c->L[1].npts : 0.0;
-                    const double moved = (8.0 + (mode == 2 ? 15.0 : 12.0) * 8.0) * lv.npts + cb;
+                    const double moved = (8.0 + (mode == 2 ? 12.0 : 9.0) * 8.0 + 3.0 * (c->h32 ? 4.0 : 8.0)) * lv.npts + cb;
                     Prof p(c, VOF_K_GS0, 0, moved + 80.0 * lv.npts + (rr ? 56.0 * lv.npts : 0.0), moved);
-#define VOF_LAUNCH_BF(TR_, ET_, BF_) k_sweep0r<2, false, true, TR_, ET_, 0, 1, BF_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, 0, nx, ny, np, nullptr, x_out, b, active, nullptr, kci, kcj, tr, 0, 0, c->bf)
-                    if (rr && c->rr_f32) { if (mode == 1) VOF_LAUNCH_BF(2, float, 1); else VOF_LAUNCH_BF(2, float, 2); }
-                    else if (rr) { if (mode == 1) VOF_LAUNCH_BF(2, double, 1); else VOF_LAUNCH_BF(2, double, 2); }
-                    else { if (mode == 1) VOF_LAUNCH_BF(0, double, 1); else VOF_LAUNCH_BF(0, double, 2); }
+#define VOF_LAUNCH_BF(TR_, ET_, BF_, XT_) k_sweep0r<2, false, true, TR_, ET_, 0, 1, BF_, XT_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, 0, nx, ny, np, nullptr, (XT_*)x_out, b, active, nullptr, kci, kcj, tr, 0, 0, c->bf)
+                    if (c->h32) { if (mode == 1) VOF_LAUNCH_BF(2, float, 1, float); else VOF_LAUNCH_BF(2, float, 2, float); }
+                    else if (rr && c->rr_f32) { if (mode == 1) VOF_LAUNCH_BF(2, float, 1, double); else VOF_LAUNCH_BF(2, float, 2, double); }
+                    else if (rr) { if (mode == 1) VOF_LAUNCH_BF(2, double, 1, double); else VOF_LAUNCH_BF(2, double, 2, double); }
+                    else { if (mode == 1) VOF_LAUNCH_BF(0, double, 1, double); else VOF_LAUNCH_BF(0, double, 2, double); }
 #undef VOF_LAUNCH_BF
                     if (rr) c->rr_done = true;
                 }
@@ -679,14 +695,15 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
                     const size_t len = 3 * lv.npts;
                     { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_S><<<np, 64, 0, c->stream>>>(c->sc, c->partials, nx * ny, c->active, c->prm.rtol, c->prm.max_iterations); }
                     { Prof p(c, VOF_K_VECTOR, 0);
-                      k_fix_half<double><<<dim3(64, np), RBLK, 0, c->stream>>>(c->kx, (const double*)c->ky, len, c->sc);
+                      if (c->h32) k_fix_half<float><<<dim3(64, np), RBLK, 0, c->stream>>>(c->kx, (const float*)c->ky, len, c->sc);
+                      else k_fix_half<double><<<dim3(64, np), RBLK, 0, c->stream>>>(c->kx, (const double*)c->ky, len, c->sc);
                       k_clear_half<<<(np + 255) / 256, 256, 0, c->stream>>>(c->sc, np); }
                 }
                 return;
             }
             // bytes the pass moves: I + b(3) + x(3) in, x(3) out (+ coarse e), whatever the number of fused sweeps; algorithmic
             // bytes (80 per sweep performed): the second sweep of a double pass counts as a full sweep
-            double moved = (8.0 + (x_in ? 9.0 : 6.0) * 8.0) * lv.npts + ebytes;
+            double moved = (8.0 + 24.0 + (x_in ? 6.0 : 3.0) * (c->h32 ? 4.0 : 8.0)) * lv.npts + ebytes;
             double algo = moved + (NSW - 1) * 80.0 * lv.npts;
             S0Trail tr{nullptr, nullptr, 0, nullptr};
             if (trail) {   // + the operator product v = A x_out with its dot products: algorithmic 56 (+24 for the dot partner)
@@ -730,15 +747,26 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
             } while (0)
             // (the register-resident pass is compiled with the reference's derivative quirk built in; one wave per block needs
             // a few waves per SIMD-slot to fill the chip: tiny stacks - 128 x 128 x 8: 14 blocks - stay with the 4-wave LDS pass)
+            if (c->h32 && !(geo.s0r && NSW == 2 && (rr ? c->rr_f32 : (po && x_in && ecoarse)))) { h32_refuse("not a float32 k_sweep0r pass"); return; }
             if (rr) {
                 S0Trail trr{(double*)c->rr_out, nullptr, 0, nullptr};
                 const size_t ldsr = S0R<2, 2>::LDS_TOTAL;
-                if (c->rr_f32) k_sweep0r<2, false, true, 2, float, 0, 1, 3><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, c->L[1].ni, c->L[1].nj, trr);
+                if (c->h32) k_sweep0r<2, false, true, 2, float, 0, 1, 3, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, nullptr, (float*)x_out, b, active, nullptr, c->L[1].ni, c->L[1].nj, trr);
+                else if (c->rr_f32) k_sweep0r<2, false, true, 2, float, 0, 1, 3><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, c->L[1].ni, c->L[1].nj, trr);
                 else k_sweep0r<2, false, true, 2, double, 0, 1, 3><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, c->L[1].ni, c->L[1].nj, trr);
                 c->rr_done = true;
                 return;
             }
-            if (geo.s0r) {
+            if (c->h32) {   // the post-smoothing pass: float32 x in (+ the interpolated correction), float32 y out
+                const size_t ldsr = trail ? S0R<2, 1>::LDS_TOTAL : S0R<2, 0>::LDS_TOTAL;
+                const float* xi = (const float*)x_in;
+                float* xo = (float*)x_out;
+                if (trail && ec32) k_sweep0r<2, true, false, 1, float, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, (const float*)ecoarse, nci, ncj, tr);
+                else if (trail) k_sweep0r<2, true, false, 1, double, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, ecoarse, nci, ncj, tr);
+                else if (ec32) k_sweep0r<2, true, false, 0, float, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, (const float*)ecoarse, nci, ncj, tr);
+                else k_sweep0r<2, true, false, 0, double, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, ecoarse, nci, ncj, tr);
+            }
+            else if (geo.s0r) {
                 if (NSW == 2) { if (po) VOF_LAUNCH_S0R(2, 1); else VOF_LAUNCH_S0R(2, 0); }
                 else { if (po) VOF_LAUNCH_S0R(1, 1); else VOF_LAUNCH_S0R(1, 0); }
             }
@@ -936,6 +964,16 @@ inline bool coarse32_ok(const vof_ctx* c, int nu_post) {
            c->fuse_restrict && c->stream_apply && nu_post > 0;
 }
 
+// ... and its level-0 hand-off vectors - the pre-smoothed iterate x and the cycle's result y / z - are stored as float32 (h32)
+// when every level-0 pass of the cycle is a k_sweep0r pass that can store them: the two-sweep pass from zero with the residual +
+// restriction stage (nu_pre 2) and the two-sweep post-smoothing pass that interpolates the correction (nu_post 2)
+inline bool handoff32_ok(const vof_ctx* c) {
+    const vof_params& P = c->prm;
+    return c->l0_handoff && P.nu_pre == 2 && P.nu_post == 2 && coarse32_ok(c, P.nu_post) && c->sweep0m_pairs && c->fuse_rr &&
+           VOF_S0R_BCARRY && s0_geometry(c, c->L[0].ni, 2, true).s0r && s0_geometry(c, c->L[0].ni + 1, 2, true).s0r &&
+           s0_geometry(c, c->L[0].ni + 1, 2, false).s0r;
+}
+
 // One multigrid cycle on level l for A_l x = b, starting from a zero guess (from_zero) or from the contents of x.
 // (x, tmp) are the level's ping-pong buffers.  Returns the buffer holding the result: `x`, or - on the levels >= 1,
 // where the caller only reads it - `tmp`.  With prm.w_cycle_level == l the next coarser level is visited twice
@@ -971,6 +1009,11 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
         smooth_level_t<VT>(c, l, x, tmp, b, nu1, from_zero, false, np, active);
     }
     if (l == 0 && c->rr_out) { rr_fused = c->rr_done; c->rr_out = nullptr; c->rr_done = false; }
+    if (l == 0 && c->h32 && !(rr_fused && coarse32_ok(c, nu2))) {
+        c->err = "float32 level-0 hand-off: the pre-smoothing pass did not form the coarse right-hand side";
+        c->h32_bad = true;
+        return x;
+    }
     if constexpr (std::is_same<VT, double>::value) {
         if (l == 0 && coarse32_ok(c, nu2)) {
             // float64 vectors on level 0, float32 below: the fused residual + restriction writes the coarse right-hand side as
@@ -1477,6 +1520,7 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
     // precision after 8 iterations, GMRES fallback)
     c->vfloat = (P.vcycle_precision == 1 || P.vcycle_precision == 2) && c->fused && c->L.size() > 1 && !c->direct_on;
     c->vcoarse32 = P.vcycle_precision == 3 && !c->direct_on;
+    c->h32 = c->h32_bad = false;
     if (c->direct_on) {   // direct preconditioner: block-tridiagonal LU instead of the Galerkin hierarchy
         if (np > c->dir_cap) { c->err = "batch larger than the direct preconditioner's buffers"; return -1; }
         c->frames = frames_dev;
@@ -1539,10 +1583,12 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
         // (in the slowly converging regimes float32 storage costs iterations)
         if (it_total == AUTO_F64_AFTER) { if (P.vcycle_precision == 2) c->vfloat = false; c->vcoarse32 = false; }
         c->cur_units = nact;
+        // float32 level-0 hand-off vectors under the same rule (y and z of one iteration have the same type)
+        c->h32 = handoff32_ok(c);
         const int* act = c->active;
         void* vrhs_p = c->vfloat ? (void*)c->b32 : (void*)c->kp;   // V-cycle right-hand sides (V-typed)
         void* vrhs_s = c->vfloat ? (void*)c->b32 : (void*)c->kr;
-        const double vsz = c->vfloat ? 4.0 : 8.0;
+        const double vsz = (c->vfloat || c->h32) ? 4.0 : 8.0;
         // p = r + beta (p - omega v).  The iteration after a (re)start has p = r: the cycle then runs straight on r (unless it
         // needs a float32 copy of its right-hand side) and no p is written - the next iteration finds that p in r^ = r0.
         const bool on_r = it == 0 && !c->vfloat;
@@ -1569,6 +1615,7 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
         vcycle(c, &c->ky, vrhs_p, np, act);
         c->trail_set = false;
         if (c->bf_mode) { if (c->err.empty()) c->err = "folded vector update (p): not consumed by the cycle"; c->bf_mode = 0; return -1; }
+        if (c->h32_bad) { c->h32_bad = c->h32 = false; return -1; }
         int nb1 = c->trail_done ? c->trail_nblk : krylov_apply(c, c->ky, c->kv, np, act, rh, 0);
         if (!nb1) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(rh, c->kv, nullptr, nullptr, len, c->partials, act); nb1 = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_ALPHA><<<np, 64, 0, s>>>(c->sc, c->partials, nb1, c->active, P.rtol, P.max_iterations); }
@@ -1584,7 +1631,7 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
           VDISPATCH(c, (k_update_s<VT><<<rgrid(c, np), RBLK, 0, s>>>(c->kr, c->kv, len, c->sc, c->partials, act, c->vfloat ? (VT*)c->b32 : (VT*)nullptr))); }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_S><<<np, 64, 0, s>>>(c->sc, c->partials, c->nblk, c->active, P.rtol, P.max_iterations); }
         { Prof p(c, VOF_K_VECTOR, 0);                                  // pairs done at the half step: x += alpha y
-          VDISPATCH(c, (k_fix_half<VT><<<dim3(64, np), RBLK, 0, s>>>(c->kx, (const VT*)c->ky, len, c->sc)));
+          YDISPATCH(c, (k_fix_half<VT><<<dim3(64, np), RBLK, 0, s>>>(c->kx, (const VT*)c->ky, len, c->sc)));
           k_clear_half<<<(np + 255) / 256, 256, 0, s>>>(c->sc, np); }
         }
         // z = M s and t = A z with (t, s) and (t, t)
@@ -1593,13 +1640,15 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
         vcycle(c, &c->kz, vrhs_s, np, act);
         c->trail_set = false;
         if (c->bf_mode) { if (c->err.empty()) c->err = "folded vector update (s): not consumed by the cycle"; c->bf_mode = 0; return -1; }
+        if (c->h32_bad) { c->h32_bad = c->h32 = false; return -1; }
         int nb2 = c->trail_done ? c->trail_nblk : krylov_apply(c, c->kz, c->kt, np, act, c->kr, 1);
         if (!nb2) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kt, c->kr, c->kt, c->kt, len, c->partials, act); nb2 = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_OMEGA><<<np, 64, 0, s>>>(c->sc, c->partials, nb2, c->active, P.rtol, P.max_iterations); }
         { Prof p(c, VOF_K_VECTOR, 0, 8.0 * len * 6 + 2.0 * vsz * len);   // x += alpha y + omega z; r = s - omega t; (r,r), (r^,r)
-          VDISPATCH(c, (k_update_xr<VT><<<rgrid(c, np), RBLK, 0, s>>>(c->kx, (const VT*)c->ky, (const VT*)c->kz, c->kr, c->kt, rh, len, c->sc, c->partials, act))); }
+          YDISPATCH(c, (k_update_xr<VT><<<rgrid(c, np), RBLK, 0, s>>>(c->kx, (const VT*)c->ky, (const VT*)c->kz, c->kr, c->kt, rh, len, c->sc, c->partials, act))); }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_R><<<np, 64, 0, s>>>(c->sc, c->partials, c->nblk, c->active, P.rtol, P.max_iterations); }
     }
+    c->h32 = false;   // (the other users of the cycle - GMRES, the debug entry points - decide for themselves)
     return 0;
     };
     if (int rc = bicg_loop(bicg_limit)) return rc;
@@ -1861,6 +1910,7 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     if (const char* e = getenv("VOF_SWEEP0")) c->sweep0 = e[0] != '0';
     if (const char* e = getenv("VOF_FUSE_APPLY")) c->trail_enabled = e[0] != '0';
     if (const char* e = getenv("VOF_SWEEP0R")) c->sweep0r = e[0] != '0';
+    if (const char* e = getenv("VOF_L0_HANDOFF")) c->l0_handoff = e[0] != '0';
     if (const char* e = getenv("VOF_SWEEP0P")) c->sweep0p = e[0] != '0';
     if (const char* e = getenv("VOF_SWEEP0R_MIN_BLOCKS")) c->sweep0r_min_blocks = atol(e);
     if (const char* e = getenv("VOF_FUSE_B")) c->fuse_b = e[0] != '0';
@@ -2933,7 +2983,7 @@ static int dbg_up(vof_ctx* c, void* dst_v, const double* host, size_t n) {
     return 0;
 }
 static int dbg_down(vof_ctx* c, double* host, const void* src_v, size_t n) {
-    if (c->vfloat) {
+    if (c->vfloat || c->h32) {   // (h32: the result of vof_debug_vcycle*)
         k_convert<float, double><<<256, 256, 0, c->stream>>>((const float*)src_v, c->krh, n);
         HIPCHK(hipMemcpyAsync(host, c->krh, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     } else {
@@ -3103,8 +3153,11 @@ int vof_debug_vcycle(vof_ctx* c, const double* r_host, double* e_host) {
     DBG_LEVEL(0)
     size_t n = nbytes / sizeof(double);
     if (int rc = dbg_up(c, c->kp, r_host, n)) return rc;
+    c->h32 = handoff32_ok(c);   // the cycle as the BiCGStab loop's first iterations run it
     vcycle(c, &c->ky, c->kp, c->npairs, nullptr);
-    return dbg_down(c, e_host, c->ky, n);
+    const int rc = c->h32_bad ? -1 : dbg_down(c, e_host, c->ky, n);
+    c->h32 = c->h32_bad = false;
+    return rc;
 }
 
 // One multigrid cycle y = M r followed by the Krylov product v = A y with the dot products (v, r) and (v, v) per pair, as the
@@ -3118,14 +3171,18 @@ int vof_debug_vcycle_apply(vof_ctx* c, const double* r_host, double* y_host, dou
     HIPCHK(hipMemcpyAsync(c->krh, r_host, nbytes, hipMemcpyHostToDevice, c->stream));   // dot partner (float64)
     c->trail_req = S0Trail{c->kv, c->krh, 1, c->partials};
     c->trail_set = true; c->trail_done = false;
+    c->h32 = handoff32_ok(c);
     vcycle(c, &c->ky, c->kp, np, nullptr);
     c->trail_set = false;
+    if (c->h32_bad) { c->h32 = c->h32_bad = false; return -1; }
     int nb = c->trail_done ? c->trail_nblk : krylov_apply(c, c->ky, c->kv, np, nullptr, c->krh, 1);
     if (fused) *fused = c->trail_done ? 1 : 0;
-    if (!nb) { c->err = "the operator kernel did not fuse the dot products"; return -1; }
+    if (!nb) { c->h32 = false; c->err = "the operator kernel did not fuse the dot products"; return -1; }
     std::vector<double> part((size_t)np * 3 * nb);
     HIPCHK(hipMemcpyAsync(part.data(), c->partials, part.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (int rc = dbg_down(c, y_host, c->ky, n)) return rc;
+    const int rcd = dbg_down(c, y_host, c->ky, n);
+    c->h32 = false;
+    if (rcd) return rcd;
     if (int rc = d2h_bounced(c, v_host, c->kv, nbytes)) return rc;
     for (int k = 0; k < np; ++k)
         for (int sl = 0; sl < 2; ++sl) {

@@ -94,6 +94,12 @@ template <int NS, int TRAIL = 0> struct S0R {
 
 struct S0RRow { double2 u, w, g; };   // one x row of the strip: .x = column 2 lane, .y = column 2 lane + 1
 
+// the row rounded to float32 (to nearest) and widened back: the values a float32 x_out holds
+__device__ __forceinline__ S0RRow round_row32(const S0RRow& s) {
+    auto r = [](double2 v) { return double2{(double)(float)v.x, (double)(float)v.y}; };
+    return S0RRow{r(s.u), r(s.w), r(s.g)};
+}
+
 // PO: 0 = forward colour order 0, 1, 2, 3; 1 = reverse order (rows shifted by one, odd columns first) - a template parameter
 // so that the column parity of a phase is a compile-time constant (one code path per phase)
 // QK: the reference's 'dy' == 'dx' quirk (OF.py:698-699) as a compile-time constant (the select costs four instructions per point)
@@ -101,10 +107,14 @@ struct S0RRow { double2 u, w, g; };   // one x row of the strip: .x = column 2 l
 // it is folded into the pass (S0BSrc): 1: s = r - alpha v (+ the block partial sums of (s, s)), 2: p = r + beta (p_old - omega v).
 // Stages 0 / 1 (first sweep) read the operand rows, form b, store the owned part and hand the row on to stages 2 / 3 (second
 // sweep, one step later) in registers, so b is neither written and re-read nor read twice.  One wave per SIMD (register budget).
-template <int NS, bool EC, bool FROM_ZERO, int TRAIL, typename ET, int PO, int QK = 1, int BF = 0>
+// XT: storage type of x_in / x_out (double, or float: the cycle's level-0 hand-off vectors in float32).  Rows
+// are widened to float64 when they enter the window and rounded to nearest at the store; the arithmetic stays FP64.  With a
+// trailing stage the final rows are rounded IN the window before it reads them: v = A x_out (TRAIL = 1) and the residual
+// b - A x_out (TRAIL = 2) are formed from exactly the values that are stored.
+template <int NS, bool EC, bool FROM_ZERO, int TRAIL, typename ET, int PO, int QK = 1, int BF = 0, typename XT = double>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO && (BF == 0 || BF == 3) && TRAIL != 2) ? VOF_S0R_FZ_WAVES : 1, (FROM_ZERO && (BF == 0 || BF == 3) && TRAIL != 2) ? VOF_S0R_FZ_WAVES : 1))) void k_sweep0r(
-    Fine0 pol, int ni, int nj, int TI, int /*po*/, int nx, int ny, int nz, const double* __restrict__ x_in,
-    double* __restrict__ x_out, const double* __restrict__ b, const int* __restrict__ active,
+    Fine0 pol, int ni, int nj, int TI, int /*po*/, int nx, int ny, int nz, const XT* __restrict__ x_in,
+    XT* __restrict__ x_out, const double* __restrict__ b, const int* __restrict__ active,
     const ET* __restrict__ ecoarse, int nci, int ncj, S0Trail tr, int skip_first = 0, int skip_count = 0,
     S0BSrc bsrc = S0BSrc{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) {
     static_assert(BF == 0 || NS == 2, "b is handed from the first sweep's stages to the second's");
@@ -114,6 +124,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
     // residual + restriction kernel's pass over x, b and the image is gone.  ET = type of the coarse right-hand side, written to tr.v.
     static_assert(TRAIL != 2 || (FROM_ZERO && !EC && PO == 0 && BF != 0), "the residual + restriction stage belongs to the pre-smoothing pass");
     constexpr bool RR = TRAIL == 2;
+    static_assert(std::is_same<XT, double>::value || std::is_same<XT, float>::value, "x is stored as float64 or float32");
+    constexpr bool X32 = std::is_same<XT, float>::value;
     // (skip_first, skip_count: the strips [skip_first, skip_first + skip_count) belong to another launch - k_sweep0p takes the
     // interior strips in its mode -; nx counts the strips of THIS launch)
     typedef S0R<NS, TRAIL> G;
@@ -138,8 +150,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
     const int p0 = by * TI - po;                 // true row of relative row 0 (reverse order: rows shifted by one)
     const int qs = bx * G::OUT - G::HALO;        // true column of local column 0 (even: 16-byte aligned pairs)
     const size_t npts = (size_t)ni * nj, off = (size_t)pair * 3 * npts;
-    const double* xin = FROM_ZERO ? nullptr : x_in + off;
-    double* xout = x_out + off;
+    const XT* xin = FROM_ZERO ? nullptr : x_in + off;
+    XT* xout = x_out + off;
     const double* bp = b + off;
     const size_t ncpts = (size_t)nci * ncj;
     const ET* ec = EC ? ecoarse + (size_t)pair * 3 * ncpts : nullptr;
@@ -186,6 +198,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
             for (int f = 0; f < 3; ++f) { BV[a][f] = BQ[a][f] = BC[0][a][f] = BC[1][a][f] = double2{0.0, 0.0}; }
     }
     double2 li[2] = {{0, 0}, {0, 0}}, lix[2] = {{0, 0}, {0, 0}};           // image rows e + 2, e + 3 in flight
+    float2 xf[2][3] = {{{0, 0}, {0, 0}, {0, 0}}, {{0, 0}, {0, 0}, {0, 0}}};   // X32: x rows e + 2, e + 3 in flight (widened at (6))
     ET crv[3] = {0, 0, 0};                                                 // EC: the coarse row in flight
     double CR[2][3];                                                       // EC: coarse rows (cp0, cp0 + 1) of the rows entering the window
     double2 tn[2][3];                                                      // TRAIL: dot partner of the next step's two rows
@@ -232,12 +245,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
         for (int r = 0; r < 2; ++r) {
             const int pL = p0 + e + 2 + r;
             if (FROM_ZERO) X[LO + 2 + r].u = X[LO + 2 + r].w = X[LO + 2 + r].g = double2{0.0, 0.0};
-            if (!FROM_ZERO) {
+            if (!FROM_ZERO && X32) {   // 8-byte column pairs; the window slot is written when the row enters it (6)
+                const bool rowok = EDGE ? (do_load && pL >= 0 && pL < ni) : true;
+                if (EDGE) xf[r][0] = xf[r][1] = xf[r][2] = float2{0.0f, 0.0f};
+                if (EDGE ? (rowok && pair_ok) : true) {
+                    const XT* src = xin + (size_t)pL * nj + qg;
+#pragma unroll
+                    for (int f = 0; f < 3; ++f) xf[r][f] = *reinterpret_cast<const float2*>(src + f * npts);
+                }
+            } else if (!FROM_ZERO) {
                 const bool rowok = EDGE ? (do_load && pL >= 0 && pL < ni) : true;
                 S0RRow& d = X[LO + 2 + r];
                 if (EDGE) d.u = d.w = d.g = double2{0.0, 0.0};
                 if (EDGE ? (rowok && pair_ok) : true) {   // (steady state = interior strip: every lane's pair exists)
-                    const double* src = xin + (size_t)pL * nj + qg;
+                    const XT* src = xin + (size_t)pL * nj + qg;
                     d.u = *reinterpret_cast<const double2*>(src);
                     d.w = *reinterpret_cast<const double2*>(src + npts);
                     d.g = *reinterpret_cast<const double2*>(src + 2 * npts);
@@ -458,10 +479,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
         const bool rowok = EDGE ? (rr >= (RR ? -1 : 0) && rr < TI && p >= 0 && p < ni) : true;   // (RR: the coarse row of fine row 0 takes row -1 in)
         if (!rowok) return false;
         const bool oU = EDGE && p - 1 < 0, oD = EDGE && p + 1 >= ni;
-        S0RRow RU = X[jc - 1], RD = X[jc + 1];
+        // X32: rows e - 2 NS - EXT .. e - 2 NS + 1 are rounded in the window (step (3)); row e - 2 NS + 2 is final too, but the next
+        // step's last stage still reads it in float64 - the operator gets a rounded copy
+        const S0RRow XD = (X32 && jc + 1 == LO - 2 * NS + 2) ? round_row32(X[jc + 1]) : X[jc + 1];
+        S0RRow RU = X[jc - 1], RD = XD;
         const S0RRow RC = X[jc];
         if (EDGE) {
-            if (oU) RU = X[jc + 1];
+            if (oU) RU = XD;
             if (oD) RD = X[jc - 1];
         }
         const char* iu = irow(jc - 1);
@@ -626,6 +650,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
             run_stage(std::integral_constant<int, 3>{});
         }
         // ---- (3) trailing stage on the rows that have just become final: e - 2 NS + 1 and e - 2 NS
+        if constexpr (X32 && TRAIL != 0) {   // the rows it reads are the rows the store writes (the stages are done with these two)
+            X[LO - 2 * NS] = round_row32(X[LO - 2 * NS]);
+            X[LO - 2 * NS + 1] = round_row32(X[LO - 2 * NS + 1]);
+        }
         if constexpr (TRAIL == 1) {
             double2 yd[3];
             trail_row(edge_tag, border_tag, std::integral_constant<int, LO - 2 * NS + 1>{}, e - 2 * NS + 1, std::integral_constant<int, 1>{}, yd);
@@ -668,10 +696,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
             const bool rowok = EDGE ? (rrW >= 0 && rrW < TI && pW >= 0 && pW < ni) : true;
             if (rowok && st_ok) {
                 const S0RRow& s = X[LO - 2 * NS + r];
-                double* dst = xout + (size_t)pW * nj + qg;
-                *reinterpret_cast<double2*>(dst) = s.u;
-                *reinterpret_cast<double2*>(dst + npts) = s.w;
-                *reinterpret_cast<double2*>(dst + 2 * npts) = s.g;
+                XT* dst = xout + (size_t)pW * nj + qg;
+                if constexpr (X32) {   // round to nearest (exact where step (3) has rounded the row already)
+                    *reinterpret_cast<float2*>(dst) = float2{(float)s.u.x, (float)s.u.y};
+                    *reinterpret_cast<float2*>(dst + npts) = float2{(float)s.w.x, (float)s.w.y};
+                    *reinterpret_cast<float2*>(dst + 2 * npts) = float2{(float)s.g.x, (float)s.g.y};
+                } else {
+                    *reinterpret_cast<double2*>(dst) = s.u;
+                    *reinterpret_cast<double2*>(dst + npts) = s.w;
+                    *reinterpret_cast<double2*>(dst + 2 * npts) = s.g;
+                }
             }
         }
         // ---- (5) the image rows in flight take the ring slots of rows e - LO, e - LO + 1 (dead from here on)
@@ -697,6 +731,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
             __builtin_amdgcn_wave_barrier();                         // moving next step's reads above these writes
         }
         // ---- (6) rotation of the window by two rows; the rows that enter get the interpolated coarse-grid correction (EC)
+        if constexpr (X32 && !FROM_ZERO) {   // the float32 rows in flight enter the window as float64
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                S0RRow& d = X[LO + 2 + r];
+                d.u = double2{(double)xf[r][0].x, (double)xf[r][0].y};
+                d.w = double2{(double)xf[r][1].x, (double)xf[r][1].y};
+                d.g = double2{(double)xf[r][2].x, (double)xf[r][2].y};
+            }
+        }
         if constexpr (EC) {
             // fine rows pL = p0 + e + 2 + r; coarse rows cp = pL >> 1 (and cp + 1 for an odd row).  CR[0] = coarse row of the LOWER of
             // the two entering rows' cp; after this step CR shifts by one coarse row (two fine rows = one coarse row)
