@@ -149,11 +149,18 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *   VOF_TRACE=1                direct preconditioner: progress lines on stderr
  * Read at every vof_solve_stack_dev call (speed only; per pair the same arithmetic, partial sums may add in another order):
  *   VOF_LANES=1|2|3            the multigrid solve of the stack as this many concurrent pair groups ("lanes"), each on a stream
- *                              and host thread of its own with an equal share of the context's pair slots (default 2); lanes
- *                              join between the two warm-start phases and before the direct re-solve, which runs on the
- *                              context's stream.  One lane while vof_profile_enable is on or with VOF_DEBUG_SYNC;
- *                              vof_solve_stack_host and vof_vary_regularisation_host always run one
- *   VOF_LANES_MIN_MPIX=x       fewer lanes while a lane's share of a phase would be below x Mpixel of frame pairs (default 16)
+ *                              and host thread of its own with an equal share of the context's pair slots (default 3).  In
+ *                              the two-phase warm start a lane runs phase 1 then phase 2 of its own groups of pairs and waits
+ *                              only for the phase 1 of the group that holds the guess of its group's last pairs; the lanes
+ *                              join once, before the direct re-solve, which runs on the context's stream.  One lane while
+ *                              vof_profile_enable is on or with VOF_DEBUG_SYNC; vof_solve_stack_host and
+ *                              vof_vary_regularisation_host always run one
+ *   VOF_LANE_GROUPS=1|2        groups of pairs per lane in the two-phase warm start (default 1: equal shares, one group per
+ *                              lane).  2: a lane's share is cut in two at a place that differs from lane to lane, so that the
+ *                              lanes reach the under-filled last Krylov iterations of a batch at different times (measured
+ *                              slower on 1024^2 x 256: every extra batch ends in such iterations of its own)
+ *   VOF_LANES_MIN_MPIX=x       fewer lanes while a lane's share of a phase would be below x Mpixel of frame pairs (default 16);
+ *                              one group per lane where two would leave a group with fewer phase-1 pairs than that
  * Debug switches (fault attribution; they change timing, never results):
  *   VOF_DEBUG_SYNC=1           the context's stream is synchronised and asked for its error after every launch scope; the
  *                              first failure is reported on stderr and appended to every later error text as

@@ -20,6 +20,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,6 +41,7 @@ int coarsest_max() {                 // experiment switch VOF_COARSEST_MAX=3..9 
 }
 constexpr int MAX_PROF_RECS = 32768;
 constexpr int MAX_LANES = 3;        // concurrent pair groups of one device solve (solve_range_dev, VOF_LANES)
+constexpr int MAX_LANE_GROUPS = 2;  // groups of pairs a lane runs one after the other in the two-phase solve (VOF_LANE_GROUPS)
 constexpr int AUTO_F64_AFTER = 8;   // vcycle_precision == 2: switch the V-cycle vectors to float64 after this many iterations
 
 struct Level {
@@ -209,6 +211,7 @@ struct vof_ctx {
     hipStream_t lane_stream[MAX_LANES] = {};
     hipEvent_t lane_ev[MAX_LANES][2] = {};
     hipEvent_t ev_fork = nullptr;
+    hipEvent_t group_ev[MAX_LANES * MAX_LANE_GROUPS] = {};   // two-phase solve: a group's phase-1 solutions are in warm_x
 };
 
 static std::string g_create_error;
@@ -1866,6 +1869,7 @@ void vof_destroy(vof_ctx* c) {
         for (int j = 0; j < 2; ++j) if (c->lane_ev[i][j]) hipEventDestroy(c->lane_ev[i][j]);
     }
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
+    for (hipEvent_t e : c->group_ev) if (e) hipEventDestroy(e);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2037,19 +2041,77 @@ namespace {
 // a host thread of its own because its Krylov loop blocks on the host; one thread polling the events of all lanes instead
 // would have to turn solve_batch inside out into a resumable state machine.
 //
-// Lanes of this solve: VOF_LANES (1 .. MAX_LANES, default 2), fewer while a lane's share of a phase would drop below
+// Lanes of this solve: VOF_LANES (1 .. MAX_LANES, default 3), fewer while a lane's share of a phase would drop below
 // VOF_LANES_MIN_MPIX (default 16) Mpixel of pairs - the same kind of rule as the two-phase one; one lane while profiling
 // (per-launch times mean something only when launches do not overlap) or with VOF_DEBUG_SYNC.
-int lanes_for(const vof_ctx* c, int pairs_per_phase) {
-    if (c->prof || c->dbg_sync) return 1;
-    int n = 2;
-    if (const char* e = getenv("VOF_LANES")) { const int v = atoi(e); if (v >= 1 && v <= MAX_LANES) n = v; }
+double lanes_min_pixels() {
     double mpix = 16.0;
     if (const char* e = getenv("VOF_LANES_MIN_MPIX")) { const double v = atof(e); if (v >= 0.0) mpix = v; }
+    return mpix * 1e6;
+}
+
+int lanes_for(const vof_ctx* c, int pairs_per_phase) {
+    if (c->prof || c->dbg_sync) return 1;
+    int n = 3;
+    if (const char* e = getenv("VOF_LANES")) { const int v = atoi(e); if (v >= 1 && v <= MAX_LANES) n = v; }
+    const double minpix = lanes_min_pixels();
     n = std::min(n, c->B);
-    while (n > 1 && (pairs_per_phase < n || (double)pairs_per_phase / n * c->Ni * c->Nj < mpix * 1e6)) --n;
+    while (n > 1 && (pairs_per_phase < n || (double)pairs_per_phase / n * c->Ni * c->Nj < minpix)) --n;
     return n;
 }
+
+// ---- groups: what a lane runs in the two-phase solve
+//
+// The phase-1 pairs of a stack (every stride-th one) are cut into contiguous groups; a group is those phase-1 pairs and the
+// warm pairs between them, and a lane runs phase 1 then phase 2 of each of its groups without meeting the other lanes.  The
+// last warm pairs of a group take their guess from the first phase-1 pair of the NEXT group, so a group's phase 2 waits for
+// the next group's phase 1 and for nothing else (GroupSync).  The order that keeps every such wait short and free of cycles:
+// with G groups per lane, lane i owns the groups i, i + L, ... and runs them from the highest down - then the group a lane
+// waits for is either one that the next lane started at the same moment or one of an earlier turn.
+// The lanes get equal shares; with two groups per lane the cut inside a share differs from lane to lane ((L - i) / (L + 1) of
+// the share first, so that the next lane's phase 1 is the shorter one and ends first), which keeps the lanes' under-filled last
+// Krylov iterations of a batch apart: one lane's stragglers run beside the other lanes' full launches instead of beside their
+// stragglers.  No group below the lanes' size rule (VOF_LANES_MIN_MPIX of phase-1 pairs): the cut is clamped to it, and a share
+// too small for two such groups stays one group.
+struct LaneGroup { int lo, hi, lane; };   // phase-1 positions [lo, hi) of the stack, run by `lane`
+
+int lane_groups_wanted() {
+    int g = 1;   // two groups per lane measured slower on the flagship stack: every extra batch ends in under-filled iterations of its own
+    if (const char* e = getenv("VOF_LANE_GROUPS")) { const int v = atoi(e); if (v >= 1 && v <= MAX_LANE_GROUPS) g = v; }
+    return g;
+}
+
+// n1 phase-1 pairs on L lanes, G groups per lane where the size rule allows it (else one).  Groups in the order of the pairs.
+std::vector<LaneGroup> plan_groups(const vof_ctx* c, int n1, int L, int G) {
+    const int min_pairs = std::max(1, (int)std::ceil(lanes_min_pixels() / ((double)c->Ni * c->Nj)));
+    std::vector<int> share((size_t)L), head((size_t)L);
+    for (int i = 0; i < L; ++i) {
+        share[i] = (int)((long)n1 * (i + 1) / L - (long)n1 * i / L);
+        if (G < 2 || share[i] < 2 * min_pairs) G = 1;
+    }
+    std::vector<LaneGroup> g;
+    int at = 0;
+    if (G == 2) {
+        for (int i = 0; i < L; ++i)   // head: the group lane i runs first, the upper one in pair order
+            head[i] = std::min(std::max((int)std::lround((double)share[i] * (L - i) / (L + 1)), min_pairs), share[i] - min_pairs);
+        for (int i = 0; i < L; ++i) { g.push_back({at, at + share[i] - head[i], i}); at += share[i] - head[i]; }
+        for (int i = 0; i < L; ++i) { g.push_back({at, at + head[i], i}); at += head[i]; }
+    } else {
+        for (int i = 0; i < L; ++i) { g.push_back({at, at + share[i], i}); at += share[i]; }
+    }
+    return g;
+}
+
+// Publication of the groups' phase-1 results between the lane threads.  `usable` (phase-1 solutions that may seed a neighbour:
+// converged and finite) and `state` are read and written under the mutex only.  A group is published once the copy of its
+// solutions into warm_x is queued on its lane's stream and the event behind it recorded - or once its lane has failed, with
+// none of its pairs usable, so that nobody waits for it for ever.
+struct GroupSync {
+    std::mutex m;
+    std::condition_variable cv;
+    std::vector<char> usable;
+    std::vector<int> state;   // per group: 0 not yet, 1 published with its event recorded, -1 published by a lane that failed
+};
 
 // Pairs a context runs in one batch: its own B, or a lane's share of the parent's slots.
 inline int batch_slots(const vof_ctx* c) { return c->lane_parent ? c->lane_slots : c->B; }
@@ -2111,8 +2173,11 @@ int make_lane(vof_ctx* c, int i, int n, vof_ctx* L) {
 
 // Runs fn(lane, i) for the n lanes of c, each on a host thread of its own and after the work queued so far on c's stream, and
 // joins them all (a lane's stream is drained before its thread ends).  The first failing lane's message goes to c->err.
+// concurrent_only: the lanes wait for each other (the groups of the two-phase solve), so where not even one thread can be
+// started nothing is run and LANES_NO_THREAD returned; otherwise lanes without a thread run here one after the other.
+constexpr int LANES_NO_THREAD = -100;
 template <typename F>
-int run_lanes(vof_ctx* c, int n, F&& fn) {
+int run_lanes(vof_ctx* c, int n, F&& fn, bool concurrent_only = false) {
     std::vector<vof_ctx> lanes((size_t)n);
     for (int i = 0; i < n; ++i)
         if (int rc = make_lane(c, i, n, &lanes[i])) return rc;
@@ -2128,10 +2193,13 @@ int run_lanes(vof_ctx* c, int n, F&& fn) {
         const hipError_t e = hipStreamSynchronize(L->stream);
         if (!rc[i] && e != hipSuccess) { L->err = std::string("stream synchronize failed: ") + hipGetErrorString(e); rc[i] = -2; }
     };
+    // from the last lane down: a group of the two-phase solve waits for one of the next lane, or for the first group of lane 0
+    // (plan_groups) - with the last lane on a thread, lanes that run here one after the other find what they wait for
     try {
-        for (int i = 0; i < n; ++i) th.emplace_back(body, i);
+        for (int i = n - 1; i >= 0; --i) th.emplace_back(body, i);
     } catch (...) {   // no thread: the remaining lanes run here, one after the other
-        for (int i = (int)th.size(); i < n; ++i) body(i);
+        if (th.empty() && concurrent_only) return LANES_NO_THREAD;
+        for (int i = n - 1 - (int)th.size(); i >= 0; --i) body(i);
     }
     for (auto& t : th) t.join();
     for (int i = 0; i < n; ++i) c->gmres_pairs += lanes[i].gmres_pairs;
@@ -2145,24 +2213,27 @@ int run_lanes(vof_ctx* c, int n, F&& fn) {
 extern "C" {
 
 // Entries [a, b) of `list` (pairs of the stack) as one phase of the two-phase solve on context or lane c, in batches of its
-// slots.  Phase 1 saves each solution in warm_x at the pair's position in the list and marks it in `usable`; phase 2 starts
-// every pair from the saved solution of its nearest phase-1 neighbour (all of phase 1 has finished by then).
+// slots.  Phase 1 saves each solution in warm_x at the pair's position in the list and marks it in sync.usable; phase 2 starts
+// every pair from the saved solution of its nearest phase-1 neighbour (whose phase 1 the caller has waited for).
 static int two_phase_part(vof_ctx* c, const double* movie, const std::vector<int>& list, size_t a, size_t b, bool phase2, int stride,
-                          std::vector<char>& usable, double* v_x, double* v_y, double* remodelling, double* speed, vof_pair_stats* stats) {
+                          GroupSync& sync, double* v_x, double* v_y, double* remodelling, double* speed, vof_pair_stats* stats) {
     const vof_params prm = c->prm;
     const size_t len = 3 * c->L[0].npts;
     const int cap = batch_slots(c);
-    const int n1 = (int)usable.size();
+    const int n1 = (int)sync.usable.size();
     std::vector<PairParam> hp((size_t)cap);
     std::vector<int> hsrc((size_t)cap);
     std::vector<vof_pair_stats> st((size_t)cap);
     for (size_t o = a; o < b; o += (size_t)cap) {
         const int np = (int)std::min<size_t>((size_t)cap, b - o);
-        for (int i = 0; i < np; ++i) {
-            const int k = list[o + i];
-            hp[i] = PairParam{prm.speed_alpha, prm.remodelling_alpha, k, k};
-            const int src = std::min((k + stride / 2) / stride, n1 - 1);
-            hsrc[i] = phase2 && usable[src] ? src : -1;   // -1: constant initial fields (a failed pair must not poison its neighbours)
+        {
+            std::lock_guard<std::mutex> lk(sync.m);
+            for (int i = 0; i < np; ++i) {
+                const int k = list[o + i];
+                hp[i] = PairParam{prm.speed_alpha, prm.remodelling_alpha, k, k};
+                const int src = std::min((k + stride / 2) / stride, n1 - 1);
+                hsrc[i] = phase2 && sync.usable[src] ? src : -1;   // -1: constant initial fields (a failed pair must not poison its neighbours)
+            }
         }
         HIPCHK(hipStreamSynchronize(c->stream));   // the host tables are re-used
         HIPCHK(hipMemcpyAsync(c->pp_buf, hp.data(), (size_t)np * sizeof(PairParam), hipMemcpyHostToDevice, c->stream));
@@ -2175,7 +2246,8 @@ static int two_phase_part(vof_ctx* c, const double* movie, const std::vector<int
         if (rc) return rc;
         if (!phase2) {
             HIPCHK(hipMemcpyAsync(c->warm_x + o * len, c->kx, (size_t)np * len * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            for (int i = 0; i < np; ++i) usable[o + i] = st[i].converged && std::isfinite(st[i].relative_residual);
+            std::lock_guard<std::mutex> lk(sync.m);
+            for (int i = 0; i < np; ++i) sync.usable[o + i] = st[i].converged && std::isfinite(st[i].relative_residual);
         }
         if (stats)
             for (int i = 0; i < np; ++i) stats[list[o + i]] = st[i];
@@ -2183,11 +2255,56 @@ static int two_phase_part(vof_ctx* c, const double* movie, const std::vector<int
     return 0;
 }
 
+// The groups of one lane (plan_groups), from the highest down: phase 1, publication, the wait for the next group's phase 1,
+// phase 2.  `ev`: the parent's event per group.  Whatever happens, every group of the lane is published before this returns.
+static int two_phase_lane(vof_ctx* c, int lane, const std::vector<LaneGroup>& groups, hipEvent_t* ev, GroupSync& sync, const double* movie,
+                          const std::vector<int>& first, const std::vector<int>& rest, int stride, double* v_x, double* v_y,
+                          double* remodelling, double* speed, vof_pair_stats* stats) {
+    const int ng = (int)groups.size();
+    auto publish = [&](int g, bool ok) {
+        {
+            std::lock_guard<std::mutex> lk(sync.m);
+            if (sync.state[g]) return;
+            if (!ok) for (int o = groups[g].lo; o < groups[g].hi; ++o) sync.usable[o] = 0;
+            sync.state[g] = ok ? 1 : -1;
+        }
+        sync.cv.notify_all();
+    };
+    auto run_group = [&](int g) -> int {
+        const LaneGroup& G = groups[g];
+        if (int rc = two_phase_part(c, movie, first, (size_t)G.lo, (size_t)G.hi, false, stride, sync, v_x, v_y, remodelling, speed, stats)) return rc;
+        HIPCHK(hipEventRecord(ev[g], c->stream));   // behind the last copy into warm_x
+        publish(g, true);
+        if (g + 1 < ng) {   // the source of this group's last warm pairs: the first phase-1 pair of the next group
+            int state;
+            {
+                std::unique_lock<std::mutex> lk(sync.m);
+                if (!sync.cv.wait_for(lk, std::chrono::seconds(60), [&] { return sync.state[g + 1] != 0; })) {
+                    c->err = "timed out waiting for the phase-1 solutions of the next pair group";
+                    return -2;
+                }
+                state = sync.state[g + 1];
+            }
+            if (state > 0) HIPCHK(hipStreamWaitEvent(c->stream, ev[g + 1], 0));
+        }
+        // the group's warm pairs: those of `rest` between its first phase-1 pair and the next group's
+        const size_t ra = (size_t)(std::lower_bound(rest.begin(), rest.end(), G.lo * stride) - rest.begin());
+        const size_t rb = g + 1 < ng ? (size_t)(std::lower_bound(rest.begin(), rest.end(), G.hi * stride) - rest.begin()) : rest.size();
+        return two_phase_part(c, movie, rest, ra, rb, true, stride, sync, v_x, v_y, remodelling, speed, stats);
+    };
+    int rc = 0;
+    for (int g = ng - 1; g >= 0 && !rc; --g)
+        if (groups[g].lane == lane) rc = run_group(g);
+    for (int g = 0; g < ng; ++g)
+        if (groups[g].lane == lane) publish(g, false);   // (what is published already stays as it is)
+    return rc;
+}
+
 // Two-phase solve of a stack with warm starts (the reference warm-starts pair k from pair k-1, OF.py:803-806, which
 // serialises the pairs; here every stride-th pair is solved first from the constant initial fields, then all the others
 // start from the solution of their nearest solved neighbour).  Pairs are addressed through the PairParam table
-// (frame / output slot), so both phases are ordinary batches.  With several lanes each phase is cut into equal contiguous
-// shares and the lanes join between the phases (a warm pair's source may be another lane's).
+// (frame / output slot), so both phases are ordinary batches.  With several lanes the stack is cut into groups of pairs and a
+// lane runs both phases of its groups without meeting the others (plan_groups, GroupSync); the lanes join once, at the end.
 static int solve_stack_two_phase(vof_ctx* c, const double* movie, int P, double* v_x, double* v_y, double* remodelling,
                                  double* speed, vof_pair_stats* stats, int stride, int lanes) {
     const size_t len = 3 * c->L[0].npts;
@@ -2203,19 +2320,25 @@ static int solve_stack_two_phase(vof_ctx* c, const double* movie, int P, double*
         if (int rc = dev_alloc(c, &c->warm_x, (size_t)n1 * len)) return rc;
         c->warm_cap = (size_t)n1 * len;
     }
-    std::vector<char> usable((size_t)n1, 0);   // phase-1 solutions that may seed a neighbour: converged and finite
-    for (int phase = 0; phase < 2; ++phase) {
-        const std::vector<int>& list = phase ? rest : first;
-        if (lanes <= 1) {
-            if (int rc = two_phase_part(c, movie, list, 0, list.size(), phase == 1, stride, usable, v_x, v_y, remodelling, speed, stats)) return rc;
-            continue;
-        }
-        int rc = run_lanes(c, lanes, [&](vof_ctx* L, int i) {
-            return two_phase_part(L, movie, list, list.size() * i / lanes, list.size() * (i + 1) / lanes, phase == 1, stride, usable,
-                                  v_x, v_y, remodelling, speed, stats);
-        });
-        if (rc) return rc;
+    GroupSync sync;
+    sync.usable.assign((size_t)n1, 0);
+    int rc = LANES_NO_THREAD;
+    if (lanes > 1) {
+        const std::vector<LaneGroup> groups = plan_groups(c, n1, lanes, lane_groups_wanted());
+        sync.state.assign(groups.size(), 0);
+        for (size_t g = 0; g < groups.size(); ++g)
+            if (!c->group_ev[g]) HIPCHK(hipEventCreateWithFlags(&c->group_ev[g], hipEventDisableTiming));
+        rc = run_lanes(c, lanes, [&](vof_ctx* L, int i) {
+            return two_phase_lane(L, i, groups, c->group_ev, sync, movie, first, rest, stride, v_x, v_y, remodelling, speed, stats);
+        }, true);
     }
+    if (rc == LANES_NO_THREAD) {   // one lane: all of phase 1, then all of phase 2, on the context's stream
+        for (int phase = 0; phase < 2; ++phase) {
+            const std::vector<int>& list = phase ? rest : first;
+            if ((rc = two_phase_part(c, movie, list, 0, list.size(), phase == 1, stride, sync, v_x, v_y, remodelling, speed, stats))) return rc;
+        }
+    }
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
