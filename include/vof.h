@@ -161,6 +161,9 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *                              slower on 1024^2 x 256: every extra batch ends in such iterations of its own)
  *   VOF_LANES_MIN_MPIX=x       fewer lanes while a lane's share of a phase would be below x Mpixel of frame pairs (default 16);
  *                              one group per lane where two would leave a group with fewer phase-1 pairs than that
+ * Read at every vof_box_flow_dev / _host call:
+ *   VOF_BOXFLOW_FUSED=0        box flow: the general three-kernel path through device scratch planes also for box sizes up to 31
+ *                              (default: the fused LDS kernel k_boxflow_fused there); same window sums in another order
  * Debug switches (fault attribution; they change timing, never results):
  *   VOF_DEBUG_SYNC=1           the context's stream is synchronised and asked for its error after every launch scope; the
  *                              first failure is reported on stderr and appended to every later error text as
@@ -210,6 +213,23 @@ int vof_solve_stack_dev(vof_ctx* ctx, const double* movie, int n_frames, const v
  * reference's skimage call).  The context fixes the frame size; any number of frames. */
 int vof_blur_stack_dev(vof_ctx* ctx, const double* in_dev, double* out_dev, int n_frames, const double* weights, int radius);
 int vof_blur_stack_host(vof_ctx* ctx, const double* in_host, double* out_host, int n_frames, const double* weights, int radius);
+
+/* Replaces conduct_optical_flow_jit (OF.py:24-157), the reference's windowed least-squares flow (Vig et al. 2016): per pair
+ * (frame k, frame k + 1) the sums of dIdx^2, dIdx dIdy, dIdy^2, dI dIdx, dI dIdy (and, with include_remodelling, of dIdx, dIdy, dI)
+ * over the box_size x box_size window of every pixel (half width int(box_size / 2), clipped at the image edge) and the closed-form
+ * 2 x 2 / 3 x 3 solve.  v_x, v_y, speed come in delta_x / delta_t units, net_remodelling unscaled; a singular pixel holds what
+ * IEEE division gives.  reference_quirks != 0 keeps OF.py:108 (column window clamped with N_i: for N_j > N_i the columns
+ * j >= N_i + h have empty windows), n = box_size^2 for clipped windows and even box sizes, and - with include_remodelling - speed
+ * all zero and zeros at the pixels whose determinant is 0.0; 0: n = pixels in the window, speed filled, such pixels NaN.
+ * movie: (n_frames, n_i, n_j) float64; outputs (n_frames - 1, n_i, n_j) float64, caller allocated, every element written;
+ * net_remodelling may be NULL without include_remodelling (zeros are written otherwise).  Box sizes up to 31 run in one fused
+ * kernel, larger ones through scratch planes of the context.  _dev: device pointers; _host: host pointers, staged by the library. */
+int vof_box_flow_dev(vof_ctx* ctx, const double* movie, int n_frames, int box_size, double delta_x, double delta_t,
+                     int include_remodelling, int reference_quirks,
+                     double* v_x, double* v_y, double* speed, double* net_remodelling);
+int vof_box_flow_host(vof_ctx* ctx, const double* movie, int n_frames, int box_size, double delta_x, double delta_t,
+                      int include_remodelling, int reference_quirks,
+                      double* v_x, double* v_y, double* speed, double* net_remodelling);
 
 /* Summary of one (speed_alpha, remodelling_alpha) combination of vary_regularisation (OF.py:1978-1983). */
 typedef struct vof_variation_stats {

@@ -72,6 +72,8 @@ SIGNATURES = {
     "vof_bench_sweeps_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), C.c_int]),
     "vof_blur_stack_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int]),
     "vof_blur_stack_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int]),
+    "vof_box_flow_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "vof_box_flow_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "vof_vary_regularisation_host": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
@@ -267,6 +269,28 @@ class Solver:
         weights = np.ascontiguousarray(weights, dtype=np.float64)
         self._check(self.lib.vof_blur_stack_dev(self.h, _ptr(movie), _ptr(out), int(n_frames), _ptr(weights),
                                                 weights.size // 2), "vof_blur_stack_dev")
+
+    def box_flow_host(self, movie: np.ndarray, box_size=15, delta_x=1.0, delta_t=1.0, include_remodelling=False,
+                      reference_quirks=True):
+        """Box least-squares flow (conduct_optical_flow_jit, OF.py:24-157) of a host movie; returns
+        ``(v_x, v_y, speed, net_remodelling)``, float64 ``(T - 1, n_i, n_j)`` each (``net_remodelling`` all zero without
+        ``include_remodelling``)."""
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        T = movie.shape[0]
+        out = [np.empty((max(T - 1, 0), self.n_i, self.n_j)) for _ in range(4)]
+        rc = self.lib.vof_box_flow_host(self.h, _ptr(movie), T, int(box_size), float(delta_x), float(delta_t),
+                                        int(bool(include_remodelling)), int(bool(reference_quirks)), *[_ptr(o) for o in out])
+        self._check(rc, "vof_box_flow_host")
+        return tuple(out)
+
+    def box_flow_dev(self, movie, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks, v_x, v_y, speed,
+                     net_remodelling=None):
+        """The same on device memory (torch tensors or raw pointers); every element of the outputs is written."""
+        rc = self.lib.vof_box_flow_dev(self.h, _ptr(movie), int(n_frames), int(box_size), float(delta_x), float(delta_t),
+                                       int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(v_x), _ptr(v_y),
+                                       _ptr(speed), _ptr(net_remodelling))
+        self._check(rc, "vof_box_flow_dev")
 
     def vary_regularisation_host(self, movie: np.ndarray, params: VofParams, speed_alphas, remodelling_alphas, weights=None):
         """The whole (speed_alpha, remodelling_alpha) sweep of vary_regularisation on the device; returns a structured

@@ -10,6 +10,7 @@
 #include "vof_sweep0r.hpp"
 #include "vof_sweep0p.hpp"
 #include "vof_direct.hpp"
+#include "vof_boxflow.hpp"
 #include "../../include/vof.h"
 
 #include <dlfcn.h>
@@ -111,6 +112,8 @@ struct vof_ctx {
     hipEvent_t ev_solved[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr}, ev_uploaded[2] = {nullptr, nullptr};
     double* st_movie2 = nullptr;                                 // second frame buffer (upload of the next batch under the solve)
     double *blur_tmp = nullptr, *blur_w = nullptr, *blur_io = nullptr;   // Gaussian blur scratch (lazy)
+    double* bf_scratch = nullptr;                                        // box flow, general path: derived planes + row sums (lazy)
+    bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
     double* tex_tab = nullptr;                                           // synthetic-texture tables (lazy)
     size_t tex_cap = 0;
     // GMRES fallback (allocated on first use): basis vectors V_0..V_m (each B * len0), per-pair state, partials, flags
@@ -3323,6 +3326,123 @@ int vof_debug_coarse_solve(vof_ctx* c, const double* r_host, double* e_host) {
     if (int rc = dbg_up(c, c->kp, r_host, n)) return rc;
     VDISPATCH(c, coarse_solve_t<VT>(c, (const VT*)c->kp, (VT*)c->kv, c->npairs, nullptr));
     return dbg_down(c, e_host, c->kv, n);
+}
+
+// ---- box least-squares flow (conduct_optical_flow, OF.py:24-218) ------------------------------------------------
+// Pageable host memory -> device through the pinned bounce buffer (the counterpart of d2h_bounced).
+static int h2d_bounced(vof_ctx* c, void* dev, const void* host, size_t bytes) {
+    if (!c->h_bounce) HIPCHK(hipHostMalloc((void**)&c->h_bounce, BOUNCE_BYTES));
+    for (size_t off = 0; off < bytes; off += BOUNCE_BYTES) {
+        const size_t n = std::min(BOUNCE_BYTES, bytes - off);
+        memcpy(c->h_bounce, (const char*)host + off, n);
+        HIPCHK(hipMemcpyAsync((char*)dev + off, c->h_bounce, n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+constexpr int BF_GENERAL_CHUNK = 4;       // pairs per launch of the general path (its scratch: 11 planes per pair)
+constexpr int BF_FUSED_CHUNK = 16384;     // pairs per launch of the fused kernel (grid z)
+
+static int box_flow_check(vof_ctx* c, const double* movie, int n_frames, int box_size, double delta_t, int include_remodelling,
+                          const double* v_x, const double* v_y, const double* speed, const double* net_remodelling) {
+    if (!movie || !v_x || !v_y || !speed) { c->err = "NULL array pointer"; return -1; }
+    if (include_remodelling && !net_remodelling) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
+    if (n_frames < 2) { c->err = "need at least two frames"; return -1; }
+    if (box_size < 1) { c->err = "box_size must be >= 1"; return -1; }
+    if (delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
+    return 0;
+}
+
+// P pairs of a device-resident movie into device-resident outputs, enqueued on the context's stream.
+static int box_flow_pairs(vof_ctx* c, const double* movie, int P, int box_size, double delta_x, double delta_t, int include_remodelling,
+                          int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
+    const size_t fs = frame_stride(c);
+    BoxArgs a{};
+    a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj; a.h = box_size / 2;
+    a.cend = reference_quirks ? std::min(c->Ni, c->Nj) : c->Nj;      // OF.py:108 clamps the column window with N_i
+    a.quirks = reference_quirks ? 1 : 0;
+    a.n_box = (double)box_size * (double)box_size;
+    a.scale = delta_x / delta_t;
+    bool fused = a.h <= BF_HMAX;
+    if (const char* e = getenv("VOF_BOXFLOW_FUSED")) fused = fused && e[0] != '0';
+    auto at = [&](int k0) {
+        a.movie = movie + (size_t)k0 * fs;
+        a.vx = v_x + (size_t)k0 * fs; a.vy = v_y + (size_t)k0 * fs; a.speed = speed + (size_t)k0 * fs;
+        a.gamma = net_remodelling ? net_remodelling + (size_t)k0 * fs : nullptr;
+    };
+    if (fused) {
+        if (!c->bf_lds_set) {
+            const int lds = (int)bf_fused_lds(BF_HMAX);
+            HIPCHK(hipFuncSetAttribute((const void*)k_boxflow_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIPCHK(hipFuncSetAttribute((const void*)k_boxflow_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            c->bf_lds_set = true;
+        }
+        const size_t lds = bf_fused_lds(a.h);
+        for (int k0 = 0; k0 < P; k0 += BF_FUSED_CHUNK) {
+            const int np = std::min(BF_FUSED_CHUNK, P - k0);
+            at(k0);
+            const dim3 g((c->Nj + BF_TJ - 1) / BF_TJ, (c->Ni + BF_TI - 1) / BF_TI, np);
+            c->cur_units = np;
+            Prof prof(c, VOF_K_RHS, 0);
+            if (include_remodelling) k_boxflow_fused<true><<<g, BF_THREADS, lds, c->stream>>>(a);
+            else k_boxflow_fused<false><<<g, BF_THREADS, lds, c->stream>>>(a);
+        }
+    } else {
+        if (!c->bf_scratch) { if (int rc = dev_alloc(c, &c->bf_scratch, (size_t)BF_GENERAL_CHUNK * 11 * fs)) return rc; }
+        double* der = c->bf_scratch;
+        double* rows = c->bf_scratch + (size_t)BF_GENERAL_CHUNK * 3 * fs;
+        for (int k0 = 0; k0 < P; k0 += BF_GENERAL_CHUNK) {
+            const int np = std::min(BF_GENERAL_CHUNK, P - k0);
+            at(k0);
+            const dim3 g = grid2d(c->Ni, c->Nj, np);
+            c->cur_units = np;
+            Prof prof(c, VOF_K_RHS, 0);
+            k_bf_derived<<<g, blk2d, 0, c->stream>>>(a, der);
+            if (include_remodelling) {
+                k_bf_hsum<true><<<g, blk2d, 0, c->stream>>>(a, der, rows);
+                k_bf_vsum<true><<<g, blk2d, 0, c->stream>>>(a, rows);
+            } else {
+                k_bf_hsum<false><<<g, blk2d, 0, c->stream>>>(a, der, rows);
+                k_bf_vsum<false><<<g, blk2d, 0, c->stream>>>(a, rows);
+            }
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int vof_box_flow_dev(vof_ctx* c, const double* movie, int n_frames, int box_size, double delta_x, double delta_t, int include_remodelling,
+                     int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
+    if (!c) return -1;
+    if (int rc = box_flow_check(c, movie, n_frames, box_size, delta_t, include_remodelling, v_x, v_y, speed, net_remodelling)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = box_flow_pairs(c, movie, n_frames - 1, box_size, delta_x, delta_t, include_remodelling, reference_quirks, v_x, v_y, speed,
+                                net_remodelling)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_size, double delta_x, double delta_t, int include_remodelling,
+                      int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
+    if (!c) return -1;
+    if (int rc = box_flow_check(c, movie, n_frames, box_size, delta_t, include_remodelling, v_x, v_y, speed, net_remodelling)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = ensure_staging(c, false)) return rc;
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const int P = n_frames - 1;
+    double* outs[4] = {v_x, v_y, speed, include_remodelling ? net_remodelling : nullptr};
+    for (int k0 = 0; k0 < P; k0 += c->B) {
+        const int np = std::min(c->B, P - k0);
+        if (int rc = h2d_bounced(c, c->st_movie, movie + (size_t)k0 * fs, (size_t)(np + 1) * fb)) return rc;
+        if (int rc = box_flow_pairs(c, c->st_movie, np, box_size, delta_x, delta_t, include_remodelling, reference_quirks, c->st_out[0],
+                                    c->st_out[1], c->st_out[2], include_remodelling ? c->st_out[3] : nullptr)) return rc;
+        for (int f = 0; f < 4; ++f)
+            if (outs[f])
+                if (int rc = d2h_bounced(c, outs[f] + (size_t)k0 * fs, c->st_out[f], (size_t)np * fb)) return rc;
+    }
+    if (!include_remodelling && net_remodelling) memset(net_remodelling, 0, (size_t)P * fb);
+    return 0;
 }
 
 }  // extern "C"

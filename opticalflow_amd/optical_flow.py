@@ -63,7 +63,7 @@ def release_device_memory(_locked=False):
 
 atexit.register(release_device_memory)
 
-__all__ = ["variational_optical_flow", "vary_regularisation", "make_fake_data_frame", "blur_movie",
+__all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "vary_regularisation", "make_fake_data_frame", "blur_movie",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -404,6 +404,127 @@ def _variational_optical_flow_device(movie, smoothing_sigma, device, max_pairs_i
                                   else float(np.sum(stats["speed_functional"])))
     if return_stats:
         result["stats"] = stats
+    return result
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Box least-squares flow (Vig et al. 2016): the reference's other estimator, OF.py:24-218.
+# ---------------------------------------------------------------------------------------------------------
+def _box_flow_context(n_i, n_j, n_pairs, device):
+    # the host entry point stages one batch of the context's pairs at a time; the kernels need no per-pair workspace
+    return _device_context(n_i, n_j, max(1, min(int(n_pairs), 8)), device)
+
+
+def conduct_optical_flow_jit(movie, box_size=15, delta_x=1.0, delta_t=1.0, include_remodelling=False, *,
+                             reference_quirks=True, device=0):
+    """Windowed least-squares flow of every frame pair on the GPU; arguments and the returned 4-tuple
+    ``(v_x, v_y, speed, net_remodelling)`` as OF.py:24-157 (float64 ``(T-1, N_i, N_j)``; ``net_remodelling`` all zero
+    without ``include_remodelling``).  Field ``k`` is computed from frames ``k`` and ``k + 1``.  See ``conduct_optical_flow``
+    for ``reference_quirks``."""
+    frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
+    if frames.ndim != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    T, N_i, N_j = frames.shape
+    if T < 2:
+        raise ValueError("movie needs at least two frames")
+    if int(box_size) < 1:
+        raise ValueError("box_size must be >= 1")
+    with _box_flow_context(N_i, N_j, T - 1, device) as solver:
+        return solver.box_flow_host(frames, int(box_size), delta_x, delta_t, include_remodelling, reference_quirks)
+
+
+def conduct_optical_flow(movie, boxsize=15, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, background=None,
+                         include_remodelling=False, *, reference_quirks=True, device=0, output="numpy"):
+    """Optical flow as in Vig et al., Biophysical Journal 110, 1469-1475 (2016), on one MI355X; positional arguments and
+    result dict as OF.py:159-218.
+
+    Per frame pair the products of the image derivatives (central differences of the two frames' mean, zero on the border
+    lines) and of the frame difference are summed over the ``boxsize`` x ``boxsize`` window of every pixel (half width
+    ``int(boxsize / 2)``, clipped at the image edge) and a 2 x 2 system - 3 x 3 with ``include_remodelling`` - is solved in
+    closed form.  ``background``: the movie is blurred with sigma 10, ``movie - background`` is kept where the blurred value
+    exceeds ``background`` and zero elsewhere; then the optional blur with ``smoothing_sigma`` (OF.py:195-203).
+
+    Returns ``v_x``, ``v_y``, ``speed`` (float64 ``(T-1, N_i, N_j)``, in ``delta_x / delta_t`` units), ``original_data``
+    (the array passed in), ``blurred_data`` (the analysed movie: the input itself when nothing was blurred or
+    subtracted), ``delta_x``, ``delta_t`` and, with ``include_remodelling``, ``net_remodelling``.  A pixel whose system is
+    singular holds what IEEE division gives (NaN / Inf), as in the reference.
+
+    Keyword-only extras: ``reference_quirks`` (True reproduces OF.py:108, the column window clamped with ``N_i`` - for
+    ``N_j > N_i`` the columns ``j >= N_i + h`` have empty windows -, ``n = boxsize**2`` also for clipped windows and even
+    ``boxsize``, and with ``include_remodelling`` an all-zero ``speed`` and zeros at pixels whose determinant is exactly 0;
+    False: the window is clamped with ``N_j``, ``n`` is the number of pixels in the window, ``speed`` is filled and such
+    pixels are NaN), ``device``, ``output`` ("numpy", or "torch": ``movie`` may be a device tensor and every array of the
+    result stays on the device as a float64 tensor; ``blurred_data`` is then float64 even for an integer movie)."""
+    if output == "torch":
+        return _conduct_optical_flow_device(movie, boxsize, delta_x, delta_t, smoothing_sigma, background,
+                                            include_remodelling, reference_quirks, device)
+    if output != "numpy":
+        raise ValueError("output must be 'numpy' or 'torch'")
+    source = np.asarray(movie)
+    if source.ndim != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    T, N_i, N_j = source.shape
+    if T < 2:
+        raise ValueError("movie needs at least two frames")
+    if int(boxsize) < 1:
+        raise ValueError("boxsize must be >= 1")
+    with _box_flow_context(N_i, N_j, T - 1, device) as solver:
+        movie_to_analyse = source
+        if background is not None:                                          # OF.py:195-198
+            movie_for_thresholding = blur_movie(source, smoothing_sigma=10, device=device, _solver=solver)
+            movie_to_analyse = np.zeros_like(movie_for_thresholding)
+            mask = movie_for_thresholding > background
+            movie_to_analyse[mask] = source[mask] - background
+        if smoothing_sigma is not None:                                     # OF.py:202-203
+            movie_to_analyse = blur_movie(movie_to_analyse, smoothing_sigma=smoothing_sigma, device=device, _solver=solver)
+        v_x, v_y, speed, net_remodelling = solver.box_flow_host(movie_to_analyse, int(boxsize), delta_x, delta_t,
+                                                                include_remodelling, reference_quirks)
+    result = dict()
+    result["v_x"] = v_x
+    result["v_y"] = v_y
+    result["speed"] = speed
+    result["original_data"] = movie
+    result["delta_x"] = delta_x
+    result["delta_t"] = delta_t
+    result["blurred_data"] = movie if (background is None and smoothing_sigma is None) else movie_to_analyse
+    if include_remodelling:
+        result["net_remodelling"] = net_remodelling
+    return result
+
+
+def _conduct_optical_flow_device(movie, boxsize, delta_x, delta_t, smoothing_sigma, background, include_remodelling,
+                                 reference_quirks, device):
+    """``output="torch"`` branch of ``conduct_optical_flow``: torch only allocates and masks the device arrays."""
+    import torch
+    dev = torch.device("cuda", int(device))
+    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
+    if frames.ndim != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    T, N_i, N_j = frames.shape
+    if T < 2:
+        raise ValueError("movie needs at least two frames")
+    if int(boxsize) < 1:
+        raise ValueError("boxsize must be >= 1")
+    out = [torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4 if include_remodelling else 3)]
+    with _box_flow_context(N_i, N_j, 1, device) as solver:
+        movie_to_analyse = frames
+        if background is not None:
+            blurred = torch.empty_like(frames)
+            torch.cuda.synchronize(dev)          # the library launches on its own stream
+            solver.blur_dev(frames, blurred, T, gaussian_taps(10))
+            movie_to_analyse = torch.where(blurred > background, frames - background, torch.zeros_like(frames))
+        if smoothing_sigma is not None:
+            blurred = torch.empty_like(frames)
+            torch.cuda.synchronize(dev)
+            solver.blur_dev(movie_to_analyse, blurred, T, gaussian_taps(smoothing_sigma))
+            movie_to_analyse = blurred
+        torch.cuda.synchronize(dev)
+        solver.box_flow_dev(movie_to_analyse, T, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks,
+                            out[0], out[1], out[2], out[3] if include_remodelling else None)
+    result = dict(v_x=out[0], v_y=out[1], speed=out[2],
+                  original_data=movie, delta_x=delta_x, delta_t=delta_t, blurred_data=movie_to_analyse)
+    if include_remodelling:
+        result["net_remodelling"] = out[3]
     return result
 
 
