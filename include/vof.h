@@ -115,37 +115,15 @@ size_t vof_params_size(void);
 int vof_default_params(vof_params* p, size_t struct_size);
 
 /* Environment variables read once by vof_create (A/B experiment switches; results are identical, only speed changes):
- *   VOF_SWEEP_GEO=AA|AB|BA|BB  strip geometry of the fused sweep on (level 0, stored levels); default AB
- *   VOF_STREAM_APPLY=0         level-0 operator: simple kernel instead of the LDS-streaming one
- *   VOF_FUSE_RESTRICT=0        level 0: separate residual and restriction kernels
- *   VOF_FUSE_PROLONG=0         level 0: separate prolongation kernel instead of interpolating inside the first post-sweep
- *   VOF_SWEEP0=0               level 0: the generic fused sweep kernel instead of the dedicated k_sweep0
- *   VOF_DIRECT_LU=own|blocked|rocsolver  direct preconditioner: dense inverse of the Schur blocks by the one-workgroup kernel / the
- *                              blocked inverse on the matrix cores / rocSOLVER (default: own up to 192 unknowns per image row,
- *                              blocked beyond; rocSOLVER only when asked for here - an A/B reference, loaded with dlopen)
- *   VOF_ROCSOLVER_LIB=path     rocSOLVER library to load (VOF_DIRECT_LU=rocsolver only)
- *   VOF_FUSE_APPLY=0           the Krylov product after a cycle: separate operator kernel instead of the trailing stage of the
- *                              cycle's last smoothing pass
- *   VOF_SWEEP0M=0|1            level 0, float64 vectors: 0 = the 4-wave kernel k_sweep0; 1 = k_sweep0m with one sweep per pass
- *                              (default: k_sweep0m, two sweeps per pass)
- *   VOF_SWEEP0R=0              level 0, float64 vectors: the LDS-ring pass k_sweep0m instead of the register-resident k_sweep0r
- *   VOF_SWEEP0R_MIN_BLOCKS=n   ... k_sweep0r from n one-wave blocks per launch on (default 512; smaller launches use k_sweep0m)
+ *   VOF_SWEEP0R_MIN_BLOCKS=n   level 0, float64 vectors: the register-resident pass k_sweep0r from n one-wave blocks per launch on
+ *                              (default 512; smaller launches use the LDS-ring pass k_sweep0m)
  *   VOF_L0_HANDOFF=0           vcycle_precision 3: the level-0 hand-off vectors of the cycle stay float64 (default: float32 where
  *                              the first 8 iterations run their level-0 passes in k_sweep0r)
  *   VOF_FUSE_B=0               the BiCGStab updates s = r - alpha v and p = r + beta (p - omega v) by their stand-alone kernels instead
  *                              of inside the first pre-smoothing pass of the cycle that consumes them (same bits)
  *   VOF_FUSE_RR=0              level 0: the coarse right-hand side R (b - A x) by the stand-alone residual + restriction kernel instead
  *                              of as the trailing stage of the pre-smoothing pass
- *   VOF_SWEEP0P=0              level 0, float32 vectors: k_sweep0 (float64 arithmetic) instead of the packed-float32 k_sweep0p
- *   VOF_PRECOND_QUIRKS=hs      experiment: hierarchy (h) / smoother (s) of the preconditioner with (1) or without (0) the 'dy' == 'dx' quirk
- *   VOF_COARSEST_MAX=3..9      coarsen until max(n_i, n_j) <= this (default 5); changes the hierarchy depth, hence iteration counts
- *   VOF_COARSE_TAIL=0          levels whose whole grid fits one workgroup: one launch per operation instead of the fused
- *                              LDS-resident coarse-tail kernel
- *   VOF_FUSE_RESU=0            stored levels: stand-alone residual + restriction kernels instead of the coarse right-hand side
- *                              from the last sweep's update (k_resrestrict_u)
- *   VOF_SWEEP_ST=0             stored levels, packed stencil formats: the generic k_sweep instead of k_sweep_st
  *   VOF_FOLD_STORED=1          stored levels: coarse-grid correction interpolated inside the first post-sweep
- *   VOF_SKIP_COLOUR0=0         W-cycle revisits: full first pre-smoothing sweep (default: colour 0 is left alone, same bits)
  *   VOF_TRACE=1                direct preconditioner: progress lines on stderr
  * Read at every vof_solve_stack_dev call (speed only; per pair the same arithmetic, partial sums may add in another order):
  *   VOF_LANES=1|2|3            the multigrid solve of the stack as this many concurrent pair groups ("lanes"), each on a stream

@@ -13,7 +13,6 @@
 #include "vof_boxflow.hpp"
 #include "../../include/vof.h"
 
-#include <dlfcn.h>
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -36,10 +35,6 @@ namespace {
 
 constexpr int COARSEST_MAX = 5;      // coarsen until max(n_i, n_j) <= COARSEST_MAX (5: dense inverse of <= 75 unknowns; was 9 = 243 unknowns, whose
                                      // Gauss-Jordan inversion took 4.4 ms per batch - the fused coarse-tail kernel makes the extra level free)
-int coarsest_max() {                 // experiment switch VOF_COARSEST_MAX=3..9 (read per call: create and workspace query agree)
-    if (const char* e = getenv("VOF_COARSEST_MAX")) { int v = atoi(e); if (v >= 3 && v <= 9) return v; }
-    return COARSEST_MAX;
-}
 constexpr int MAX_PROF_RECS = 32768;
 constexpr int MAX_LANES = 3;        // concurrent pair groups of one device solve (solve_range_dev, VOF_LANES)
 constexpr int MAX_LANE_GROUPS = 2;  // groups of pairs a lane runs one after the other in the two-phase solve (VOF_LANE_GROUPS)
@@ -135,17 +130,9 @@ struct vof_ctx {
     int cfmt = 0;   // storage format of the stored stencils of the current hierarchy: 0 double, 1 float, 2 CoefB16 (levels >= 1;
                     // the stored level 0 of a one-level grid is always double)
     bool fused = true;   // fused streaming 4-colour sweeps (false: one launch per colour)
-    bool geo_b_fine = false, geo_b_stored = true;   // strip geometry of the fused sweep per level class
-    bool fuse_prolong = true;   // level 0: coarse-grid correction interpolated inside the first post-sweep
-    bool fuse_restrict = true;  // level 0: residual + restriction in one streaming pass
-    bool sweep_st = true;       // stored levels, packed bfloat16 stencils: k_sweep_st (VOF_SWEEP_ST=0: the generic k_sweep)
-    bool skip_colour0 = true;   // ... revisits of a W-cycle: the first pre-smoothing sweep leaves colour 0 alone (VOF_SKIP_COLOUR0=0: full sweep)
-    bool fold_stored = false;   // ... with the coarse-grid correction interpolated inside the first post-sweep (VOF_FOLD_STORED=1; measured:
-                                // the sweep gets slower by what the stand-alone prolongation kernel costs, so that one stays)
-    bool fuse_resu = true;      // stored levels: coarse right-hand side from the last pre-smoothing sweep's update (k_resrestrict_u;
-                                // VOF_FUSE_RESU=0: stand-alone residual + restriction kernels)
-    bool stream_apply = true;   // LDS-streaming level-0 operator kernel with fused reductions (false: simple kernel)
-    bool sweep0 = true;         // level 0: dedicated k_sweep0 kernel (VOF_SWEEP0=0: the generic k_sweep<SweepFine, GeoA>)
+    bool fold_stored = false;   // stored levels, packed stencils (k_sweep_st): the coarse-grid correction interpolated inside the first
+                                // post-sweep (VOF_FOLD_STORED=1; measured: the sweep gets slower by what the stand-alone prolongation
+                                // kernel costs, so that one stays)
     // direct preconditioner (block-tridiagonal LU by image rows, vof_direct.hpp); buffers allocated on first use
     bool direct_on = false;          // the current batch is preconditioned by the direct solver instead of the multigrid cycle
     int dir_cap = 0;                 // pairs the direct buffers hold
@@ -153,11 +140,9 @@ struct vof_ctx {
     int *dir_ipiv = nullptr, *dir_info = nullptr;
     double *dir_R = nullptr, *dir_C = nullptr, *dir_D = nullptr;   // blocked inverse: row panel, column panel, inverted diagonal tile
     int dir_ld = 0;                  // leading dimension of the dense blocks (m, or m rounded up to the tile size of the blocked inverse)
-    void* roc_handle = nullptr;      // rocblas_handle for rocSOLVER
     long long direct_pairs = 0;      // pairs solved with the direct preconditioner since the context was created
     // Krylov product fused into the last smoothing pass of a cycle (k_sweep0m's trailing stage): requested by the Krylov loop
     // before the cycle, consumed by the final level-0 smoothing call if the fused path applies
-    bool trail_enabled = true;  // VOF_FUSE_APPLY=0: always the separate operator kernel
     bool trail_set = false, trail_done = false;
     S0Trail trail_req;
     // BiCGStab vector update folded into the cycle's first pre-smoothing pass (k_sweep0r, BF): set by the Krylov loop, consumed by
@@ -171,13 +156,8 @@ struct vof_ctx {
     int bf_mode = 0;            // 0: none pending; 1: s = r - alpha v (+ (s, s), half-step test); 2: p = r + beta (p_old - omega v)
     S0BSrc bf{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int trail_nblk = 0;         // per-pair partial sums the fused pass wrote
-    bool sweep0m = true;        // level 0, float64 vectors, even n_j: k_sweep0m (VOF_SWEEP0M=0: k_sweep0)
-    bool sweep0m_pairs = true;  // ... two sweeps per pass (VOF_SWEEP0M=1: one sweep per pass)
-    bool sweep0r = true;        // ... the register-resident pass k_sweep0r (VOF_SWEEP0R=0: the LDS-ring pass k_sweep0m)
-    long sweep0r_min_blocks = 512;   // ... for launches of at least this many one-wave blocks (VOF_SWEEP0R_MIN_BLOCKS; the tests set 0)
-    bool sweep0p = true;        // level 0, float32 cycle vectors (vcycle_precision 1 / 2): the packed-float32 register-resident pass
-                                // k_sweep0p, two sweeps per pass (VOF_SWEEP0P=0: the LDS-ring kernel k_sweep0 with float64 arithmetic)
-    bool tail_enabled = true;   // fused LDS-resident coarse-tail kernel (VOF_COARSE_TAIL=0: one launch per operation)
+    long sweep0r_min_blocks = 512;   // level 0, float64 vectors, even n_j: the register-resident pass k_sweep0r for launches of at least
+                                     // this many one-wave blocks, the LDS-ring pass k_sweep0m below (VOF_SWEEP0R_MIN_BLOCKS; the tests set 0)
     int tail_first = -1;        // first level of the tail (-1: no tail for this grid)
     size_t tail_lds = 0;        // dynamic LDS bytes of k_tail_cycle
     TailArgs tail;              // levels / LDS layout; the operation list is rebuilt when the cycle parameters change
@@ -194,9 +174,6 @@ struct vof_ctx {
     double prof_bytes[VOF_K_COUNT][16];
     double prof_moved[VOF_K_COUNT][16];
     int cur_units = 0;  // frame pairs the next launches process (active pairs of the batch)
-    // experiment (VOF_PRECOND_QUIRKS=hs, two digits): does the PRECONDITIONER see the reference's 'dy' == 'dx' quirk (OF.py:698-699)
-    // in its Galerkin hierarchy (h) / in its level-0 smoother and residual (s)?  The Krylov product always does.
-    bool pq_hier = true, pq_smooth = true;
     // fault attribution (see the "debug switches" paragraph of include/vof.h)
     int dbg_sync = 0;            // VOF_DEBUG_SYNC=1: synchronise + check after every launch scope; the first failure names its kernel class
     long long dbg_seq = 0;       // launch scopes checked so far
@@ -493,29 +470,16 @@ void apply_fine_t(vof_ctx* c, const XT* x, const BT* b, YT* y, int mode, int np,
     const double bytes = (8.0 + 3.0 * sizeof(XT) + ((y ? 3.0 : 0.0) + (ycopy ? 3.0 : 0.0)) * sizeof(YT) + (mode ? 3.0 * sizeof(BT) : 0.0) +
                           (dotvec ? 24.0 : 0.0)) * lv.npts;
     Prof p(c, VOF_K_APPLY0, 0, bytes);
-    if (c->stream_apply) {
-        ApplyGrid ag = apply_grid(c, np);
-        double* part = (dotvec || want_yy) ? c->partials : nullptr;
-        if (mode)
-            k_stream_apply0<1, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-                c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-                c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy);
-        else
-            k_stream_apply0<0, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-                c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-                c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy);
-        return;
-    }
-    if (ycopy) { c->err = "internal: second output without the streaming operator kernel"; return; }
-    dim3 g = grid2d(lv.ni, lv.nj, np);
+    ApplyGrid ag = apply_grid(c, np);
+    double* part = (dotvec || want_yy) ? c->partials : nullptr;
     if (mode)
-        k_apply0<1, XT, BT, YT><<<g, blk2d, 0, c->stream>>>(c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj,
-                                                            c->prm.speed_alpha, c->prm.remodelling_alpha,
-                                                            c->prm.reference_quirks, x, b, y, active, c->pp);
+        k_stream_apply0<1, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
+            c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
+            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy);
     else
-        k_apply0<0, XT, BT, YT><<<g, blk2d, 0, c->stream>>>(c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj,
-                                                            c->prm.speed_alpha, c->prm.remodelling_alpha,
-                                                            c->prm.reference_quirks, x, b, y, active, c->pp);
+        k_stream_apply0<0, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
+            c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
+            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy);
 }
 
 template <typename VT>
@@ -535,28 +499,25 @@ void apply_level_t(vof_ctx* c, int l, const VT* x, const VT* b, VT* y, int mode,
 }
 
 // Krylov-level products on level 0 with FP64 results: out = A y (y V-typed) and out = b - A x (all double).
-// When `fuse` is set and the streaming kernel is in use, the reductions (out.dotvec and/or out.out) are fused
-// into the operator kernel and the function returns the number of per-pair partials it wrote; otherwise 0
-// (the caller then launches k_dot2).
+// On the matrix-free level 0 the reductions asked for (out.dotvec and/or out.out) are fused into the operator kernel
+// and the function returns the number of per-pair partials it wrote; otherwise 0 (the caller then launches k_dot2).
 int krylov_apply(vof_ctx* c, const void* y, double* out, int np, const int* active, const double* dotvec = nullptr,
                  int want_yy = 0) {
     if (c->L[0].C) { apply_stored_t<double>(c, 0, (const double*)y, nullptr, out, 0, np, active); return 0; }
-    const bool fuse = c->stream_apply && (dotvec || want_yy);
-    if (c->vfloat || c->h32) apply_fine_t<float, double, double>(c, (const float*)y, nullptr, out, 0, np, active, fuse ? dotvec : nullptr, fuse ? want_yy : 0);
-    else apply_fine_t<double, double, double>(c, (const double*)y, nullptr, out, 0, np, active, fuse ? dotvec : nullptr, fuse ? want_yy : 0);
-    return fuse ? apply_grid(c, np).nblk : 0;
+    if (c->vfloat || c->h32) apply_fine_t<float, double, double>(c, (const float*)y, nullptr, out, 0, np, active, dotvec, want_yy);
+    else apply_fine_t<double, double, double>(c, (const double*)y, nullptr, out, 0, np, active, dotvec, want_yy);
+    return (dotvec || want_yy) ? apply_grid(c, np).nblk : 0;
 }
 // (out == nullptr with want_norm: only the norm is wanted - the streaming kernel then writes nothing; returns 0 if that is
 // not possible, and the caller falls back to a residual vector)
 // out2 (streaming kernel only, see residual_copy_ok): a second copy of the residual
-inline bool residual_copy_ok(const vof_ctx* c) { return c->stream_apply && !c->L[0].C; }
+inline bool residual_copy_ok(const vof_ctx* c) { return !c->L[0].C; }
 int residual_d(vof_ctx* c, const double* x, const double* b, double* out, int np, const int* active, int want_norm = 0,
                double* out2 = nullptr) {
-    if (!out && !(want_norm && c->stream_apply && !c->L[0].C)) return 0;
+    if (!out && !(want_norm && !c->L[0].C)) return 0;
     if (c->L[0].C) { apply_stored_t<double>(c, 0, x, b, out, 1, np, active); return 0; }
-    const bool fuse = c->stream_apply && want_norm;
-    apply_fine_t<double, double, double>(c, x, b, out, 1, np, active, nullptr, fuse ? 1 : 0, out2);
-    return fuse ? apply_grid(c, np).nblk : 0;
+    apply_fine_t<double, double, double>(c, x, b, out, 1, np, active, nullptr, want_norm ? 1 : 0, out2);
+    return want_norm ? apply_grid(c, np).nblk : 0;
 }
 
 template <typename VT>
@@ -575,7 +536,7 @@ void resrestrict_fine_t(vof_ctx* c, const VT* x, const VT* b, CVT* bc, int np, c
     Prof p(c, VOF_K_APPLY0, 0, (8.0 + 6.0 * sizeof(VT)) * f.npts + 3.0 * sizeof(CVT) * k.npts);
     k_stream_resrestrict0<VT, VT, CVT><<<g, AP_THREADS, 0, c->stream>>>(
         c->frames, frame_stride(c), c->Nj, f.ni, f.nj, TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-        c->prm.reference_quirks && c->pq_smooth, x, b, bc, k.ni, k.nj, active, c->pp);
+        c->prm.reference_quirks, x, b, bc, k.ni, k.nj, active, c->pp);
 }
 
 // stored level l >= 1, straight after ONE forward Gauss-Seidel sweep x_old -> x_new (x_old == nullptr: from zero): the coarse
@@ -614,18 +575,17 @@ void coarse_solve_t(vof_ctx* c, const VT* r, VT* e, int np, const int* active) {
 
 // k_sweep0m (merged colours, 16-byte accesses, up to two sweeps per pass) needs float64 vectors and an even row length
 inline bool sweep0m_usable(const vof_ctx* c) {
-    return c->sweep0m && c->sweep0 && c->fused && !c->geo_b_fine && !c->vfloat && (c->L[0].nj % 2 == 0) && c->L[0].C == nullptr;
+    return c->fused && !c->vfloat && (c->L[0].nj % 2 == 0) && c->L[0].C == nullptr;
 }
 
 // k_sweep0p (float32 cycle vectors: packed float32 arithmetic, two strips per wave, up to two sweeps per pass)
 inline bool sweep0p_usable(const vof_ctx* c) {
-    return c->sweep0p && c->sweep0r && c->sweep0 && c->fused && !c->geo_b_fine && c->vfloat && (c->L[0].nj % 2 == 0) && c->L[0].C == nullptr &&
-           c->prm.reference_quirks && c->pq_smooth;
+    return c->fused && c->vfloat && (c->L[0].nj % 2 == 0) && c->L[0].C == nullptr && c->prm.reference_quirks;
 }
 
 // k_sweep_st: stored levels with packed bfloat16 stencils and the 128-column strip geometry
 inline bool sweep_st_usable(const vof_ctx* c, int l) {
-    return l > 0 && c->L[l].C != nullptr && c->sweep_st && c->geo_b_stored && c->cfmt >= 2;
+    return l > 0 && c->L[l].C != nullptr && c->cfmt >= 2;
 }
 
 // Strips and bands of a level-0 pass of k_sweep0m / k_sweep0r (NSW sweeps per pass) and whether the register-resident kernel takes it
@@ -637,7 +597,7 @@ inline S0Geo s0_geometry(const vof_ctx* c, int rows, int NSW, bool trail) {
     g.nx = (lv.nj + out - 1) / out;
     g.TI = pick_band_height(rows, g.nx, c->cur_units);
     g.ny = (rows + g.TI - 1) / g.TI;
-    g.s0r = c->sweep0r && c->prm.reference_quirks && c->pq_smooth && (long)g.nx * g.ny * std::max(1, c->cur_units) >= c->sweep0r_min_blocks;
+    g.s0r = c->prm.reference_quirks && (long)g.nx * g.ny * std::max(1, c->cur_units) >= c->sweep0r_min_blocks;
     return g;
 }
 
@@ -645,7 +605,7 @@ inline S0Geo s0_geometry(const vof_ctx* c, int rows, int NSW, bool trail) {
 // right-hand side is folded into that pass (the conditions mirror vcycle_t -> smooth_level_t -> sweep_level_t).
 inline bool fold_b_usable(const vof_ctx* c) {
     return c->fuse_b && !c->direct_on && !c->vfloat && c->L.size() > 1 && c->tail_first != 0 && c->fused && c->prm.nu_pre >= 2 &&
-           sweep0m_usable(c) && c->sweep0m_pairs && s0_geometry(c, c->L[0].ni, 2, false).s0r && s0_geometry(c, c->L[0].ni, 2, true).s0r;
+           sweep0m_usable(c) && s0_geometry(c, c->L[0].ni, 2, false).s0r && s0_geometry(c, c->L[0].ni, 2, true).s0r;
 }
 
 // One full 4-colour sweep x_in -> x_out (x_in == nullptr: zero initial guess); reverse = colours 3,2,1,0.
@@ -727,7 +687,7 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
                 moved += cb;
             }
             Prof p(c, VOF_K_GS0, 0, algo, moved);
-            Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, c->prm.reference_quirks && c->pq_smooth, c->pp};
+            Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, c->prm.reference_quirks, c->pp};
             const size_t lds = (size_t)(6 * NSW + 2 + (trail ? 4 : 0)) * s0_row_bytes(8) + (ecoarse ? (size_t)9 * (S0_W / 2 + 2) * 8 : 0);
 #define VOF_LAUNCH_S0M(NS_)                                                                                                        \
             do {                                                                                                                    \
@@ -810,31 +770,25 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
             return;
         }
     }
-    const bool geoB = (l > 0) ? c->geo_b_stored : c->geo_b_fine;
-    const int out = geoB ? GeoB::OUT : GeoA::OUT, W = geoB ? GeoB::W : GeoA::W, IW = geoB ? GeoB::IW : GeoA::IW;
-    const int TI = pick_band_height(rows, (lv.nj + (geoB ? 0 : po) + out - 1) / out, c->cur_units);
-    const int nx = (lv.nj + (geoB ? 0 : po) + out - 1) / out, ny = (rows + TI - 1) / TI;
+    // k_sweep0 on the matrix-free level 0: strips of 120 owned columns, shifted by the pass's direction; the stored levels: 128-column aligned strips
+    const bool fine0 = l == 0 && lv.C == nullptr;
+    const int out = fine0 ? S0_OUT : GeoB::OUT, W = fine0 ? S0_W : GeoB::W;
+    const int nx = (lv.nj + (fine0 ? po : 0) + out - 1) / out;
+    const int TI = pick_band_height(rows, nx, c->cur_units);
+    const int ny = (rows + TI - 1) / TI;
     dim3 g((unsigned)nx * ny * np, 1, 1);
     const double vs = sizeof(VT);
     int nci = 0, ncj = 0;
     double ebytes = 0.0;
     if (ecoarse) { nci = c->L[l + 1].ni; ncj = c->L[l + 1].nj; ebytes = 3.0 * vs * c->L[l + 1].npts; }
-    if (l == 0 && lv.C == nullptr) {
+    if (fine0) {
         Prof p(c, VOF_K_GS0, 0, (8.0 + (x_in ? 9.0 : 6.0) * vs) * lv.npts + ebytes);   // I + b(3) + x(3) in, x(3) out (+ coarse e)
-        SweepFine pol;
-        pol.frames = c->frames; pol.frame_stride = frame_stride(c); pol.Nj = c->Nj;
-        pol.alpha = c->prm.speed_alpha; pol.beta = c->prm.remodelling_alpha; pol.quirks = c->prm.reference_quirks && c->pq_smooth;
-        pol.pp = c->pp;
-        size_t lds = (size_t)(SW_RING * 3 * W) * sizeof(VT) + (size_t)(SW_RING * IW) * sizeof(double) +
+        Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, c->prm.reference_quirks, c->pp};
+        size_t lds = (size_t)(SW_RING * 3 * W) * sizeof(VT) + (size_t)(SW_RING * S0_IW) * sizeof(double) +
                      (ecoarse ? (size_t)(3 * 3 * (W / 2 + 2)) * sizeof(VT) : 0);
-        if (geoB) k_sweep<SweepFine, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-        else if (c->sweep0) {   // the dedicated level-0 kernel (same geometry, schedule and bits as k_sweep<SweepFine, GeoA>)
-            Fine0 f0{pol.frames, pol.frame_stride, pol.Nj, pol.alpha, pol.beta, pol.quirks, pol.pp};
-            if (ecoarse) k_sweep0<VT, true, false><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-            else if (!x_in) k_sweep0<VT, false, true><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-            else k_sweep0<VT, false, false><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-        }
-        else k_sweep<SweepFine, GeoA, VT><<<g, GeoA::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
+        if (ecoarse) k_sweep0<VT, true, false><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
+        else if (!x_in) k_sweep0<VT, false, true><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
+        else k_sweep0<VT, false, false><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
     } else {
         Prof p(c, VOF_K_GS, l, (coef_bytes(c, l) + (x_in ? 9.0 : 6.0) * vs) * lv.npts + ebytes);   // C + b(3) + x(3) in, x(3) out (+ coarse e)
         size_t lds = (size_t)(SW_RING * 3 * W) * sizeof(VT);
@@ -857,8 +811,7 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
         }
         CDISPATCH(c, l, {
             SweepStored<CT> pol; pol.C = (const CW*)lv.C; pol.plane = CLay(lv.ni, lv.nj).plane;
-            if (geoB) k_sweep<SweepStored<CT>, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-            else k_sweep<SweepStored<CT>, GeoA, VT><<<g, GeoA::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
+            k_sweep<SweepStored<CT>, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
         });
     }
 }
@@ -873,8 +826,8 @@ VT* smooth_level_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int nu, bool 
     // ecoarse: coarse-grid correction still to be added (x += P ecoarse).  On the matrix-free level 0 it is folded
     // into the first sweep (coarse rows streamed through LDS); otherwise the prolongation kernel runs first.
     const size_t bytes = (size_t)np * 3 * c->L[l].npts * sizeof(VT);
-    const bool fold = ecoarse && nu > 0 && c->fused && c->fuse_prolong && !from_zero &&
-                      ((l == 0 && c->L[0].C == nullptr && !c->geo_b_fine) || (sweep_st_usable(c, l) && c->fold_stored));
+    const bool fold = ecoarse && nu > 0 && c->fused && !from_zero &&
+                      ((l == 0 && c->L[0].C == nullptr) || (sweep_st_usable(c, l) && c->fold_stored));
     if (ecoarse && !fold) {
         prolong_add_level_t<VT>(c, l, x, ecoarse, np, active);
         ecoarse = nullptr;
@@ -892,8 +845,7 @@ VT* smooth_level_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int nu, bool 
     }
     // out-of-place fused sweeps: choose the first destination so that the last pass writes into x.  On level 0 a pass of
     // k_sweep0m performs two sweeps (temporal blocking): nu sweeps = ceil(nu / 2) passes over the data.
-    const bool two = l == 0 && ((std::is_same<VT, double>::value && sweep0m_usable(c) && c->sweep0m_pairs) ||
-                                (std::is_same<VT, float>::value && sweep0p_usable(c) && c->sweep0m_pairs));
+    const bool two = l == 0 && (std::is_same<VT, double>::value ? sweep0m_usable(c) : sweep0p_usable(c));
     const int npass = two ? (nu + 1) / 2 : nu;
     const VT* src = from_zero ? nullptr : x;
     VT* dst = (from_zero && (npass % 2 == 1)) ? x : tmp;
@@ -901,7 +853,7 @@ VT* smooth_level_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int nu, bool 
     for (int s = 0; s < npass; ++s) {
         const int ns = two ? std::min(2, left) : 1;
         // the cycle's very last pass also delivers the Krylov product of its result, if one was requested
-        const bool trail = final_smooth && s == npass - 1 && c->trail_set && c->trail_enabled && l == 0 &&
+        const bool trail = final_smooth && s == npass - 1 && c->trail_set && l == 0 &&
                            std::is_same<VT, double>::value && sweep0m_usable(c) && src != nullptr;
         sweep_level_t<VT>(c, l, src, dst, b, reverse, np, active, s == 0 ? ecoarse : (const VT*)nullptr, ns, trail, ec32,
                           out64 && s == npass - 1, skip0 && s == 0);
@@ -937,7 +889,7 @@ void tail_emit(const vof_ctx* c, std::vector<unsigned char>* ops, int l, bool fr
 
 // (Re)build the operation list for the current cycle parameters; false: the tail cannot be used (too many operations)
 bool tail_prepare(vof_ctx* c) {
-    if (c->tail_first < 0 || !c->tail_enabled || !c->fused) return false;
+    if (c->tail_first < 0 || !c->fused) return false;
     const vof_params& P = c->prm;
     const int key[6] = {P.nu_pre, P.nu_post, P.nu_pre_coarse, P.nu_post_coarse, P.w_cycle_level, P.w_cycle_visits};
     if (memcmp(key, c->tail_key, sizeof key) != 0) {
@@ -966,8 +918,7 @@ void tail_cycle_t(vof_ctx* c, VT* x, const VT* b, int np, const int* active, boo
 // vcycle_precision 3 applies when level 0 runs the kernels in which the two storage types meet: k_stream_resrestrict0 (float64
 // in, float32 out) and k_sweep0m with the interpolated correction (float32 in); anything else keeps float64 everywhere
 inline bool coarse32_ok(const vof_ctx* c, int nu_post) {
-    return c->vcoarse32 && !c->vfloat && c->L.size() > 1 && c->L[0].C == nullptr && sweep0m_usable(c) && c->fuse_prolong &&
-           c->fuse_restrict && c->stream_apply && nu_post > 0;
+    return c->vcoarse32 && c->L.size() > 1 && sweep0m_usable(c) && nu_post > 0;
 }
 
 // ... and its level-0 hand-off vectors - the pre-smoothed iterate x and the cycle's result y / z - are stored as float32 (h32)
@@ -975,7 +926,7 @@ inline bool coarse32_ok(const vof_ctx* c, int nu_post) {
 // restriction stage (nu_pre 2) and the two-sweep post-smoothing pass that interpolates the correction (nu_post 2)
 inline bool handoff32_ok(const vof_ctx* c) {
     const vof_params& P = c->prm;
-    return c->l0_handoff && P.nu_pre == 2 && P.nu_post == 2 && coarse32_ok(c, P.nu_post) && c->sweep0m_pairs && c->fuse_rr &&
+    return c->l0_handoff && P.nu_pre == 2 && P.nu_post == 2 && coarse32_ok(c, P.nu_post) && c->fuse_rr &&
            VOF_S0R_BCARRY && s0_geometry(c, c->L[0].ni, 2, true).s0r && s0_geometry(c, c->L[0].ni + 1, 2, true).s0r &&
            s0_geometry(c, c->L[0].ni + 1, 2, false).s0r;
 }
@@ -998,10 +949,10 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
     // pre-smoothing.  Level 0: result forced into x (the Krylov loop owns that buffer).  Stored levels: the result may end in
     // the ping-pong partner (the caller only reads the buffer this function returns), so the two just trade names - and the
     // partner then still holds the input of the last sweep, which is all k_resrestrict_u needs besides the result.
-    const bool resu = l > 0 && lv.C != nullptr && c->fused && c->fuse_resu && nu1 >= 1;
+    const bool resu = l > 0 && lv.C != nullptr && c->fused && nu1 >= 1;
     bool rr_fused = false;   // level 0: the coarse right-hand side came out of the pre-smoothing pass (k_sweep0r, TRAIL = 2)
     if constexpr (std::is_same<VT, double>::value) {
-        if (l == 0 && c->fuse_rr && from_zero && nu1 == 2 && lv.C == nullptr && c->stream_apply && c->fuse_restrict && sweep0m_usable(c) && c->sweep0m_pairs) {
+        if (l == 0 && c->fuse_rr && from_zero && nu1 == 2 && sweep0m_usable(c)) {
             c->rr_f32 = coarse32_ok(c, nu2);
             c->rr_out = nx.b;
             c->rr_done = false;
@@ -1009,7 +960,7 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
     }
     if (l > 0 && c->fused) {
         VT* xr = smooth_level_t<VT>(c, l, x, tmp, b, nu1, from_zero, false, np, active, nullptr, /*allow_swap=*/true, false, false, false,
-                                    /*skip0=*/after_post && !from_zero && nu2 >= 1 && c->skip_colour0);
+                                    /*skip0=*/after_post && !from_zero && nu2 >= 1);
         if (xr != x) std::swap(x, tmp);
     } else {
         smooth_level_t<VT>(c, l, x, tmp, b, nu1, from_zero, false, np, active);
@@ -1032,8 +983,7 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
             // the correction as it does in the all-float64 cycle - measured: interpolating from float32 rows costs that pass
             // 6 % (5 ms per step at 255 pairs), widening the stores of the level-1 sweep costs 1 ms
             const int nu2c = c->prm.nu_post_coarse > 0 ? c->prm.nu_post_coarse : c->prm.nu_post;
-            const bool can64 = 1 < last && !(c->tail_first == 1 && tail_prepare(c)) && c->L[1].C != nullptr && c->sweep_st &&
-                               c->geo_b_stored && c->cfmt >= 2 && nu2c > 0;
+            const bool can64 = 1 < last && !(c->tail_first == 1 && tail_prepare(c)) && sweep_st_usable(c, 1) && nu2c > 0;
             const int visits = (c->prm.w_cycle_level == 0 && 1 < last) ? (c->prm.w_cycle_visits > 0 ? c->prm.w_cycle_visits : 2) : 1;
             c->emit64 = can64 && visits == 1;
             float* fe = vcycle_t<float>(c, 1, fx, ft, (const float*)nx.b, np, active, true);
@@ -1050,7 +1000,7 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
     if (resu) {
         const VT* x_old = (from_zero && nu1 == 1) ? nullptr : tmp;
         resrestrict_u_t<VT>(c, l, x, x_old, (VT*)nx.b, np, active);
-    } else if (l == 0 && lv.C == nullptr && c->stream_apply && c->fuse_restrict) {
+    } else if (l == 0 && lv.C == nullptr) {   // matrix-free level 0: residual + restriction in one streaming pass
         if (!rr_fused) resrestrict_fine_t<VT>(c, x, b, (VT*)nx.b, np, active);
     } else {
         apply_level_t<VT>(c, l, x, b, (VT*)lv.r, 1, np, active);
@@ -1100,7 +1050,7 @@ int build_hierarchy(vof_ctx* c, int np) {
         if (l == 0) {
             Prof p(c, VOF_K_GALERKIN0, 0);
             CDISPATCH(c, 1, (k_galerkin<double, CT, true><<<g, blk2d, 0, c->stream>>>(
-                                 c->frames, frame_stride(c), c->Nj, P.speed_alpha, P.remodelling_alpha, P.reference_quirks && c->pq_hier,
+                                 c->frames, frame_stride(c), c->Nj, P.speed_alpha, P.remodelling_alpha, P.reference_quirks,
                                  nullptr, f.ni, f.nj, (CW*)k.C, k.ni, k.nj, c->pp)));
         } else {
             Prof p(c, VOF_K_GALERKIN, l);
@@ -1312,66 +1262,11 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
 }
 
 // ---------------------------------------------------------------------------------------------- direct preconditioner
-// rocSOLVER (dense LU + inverse of the m x m Schur blocks) is loaded on first use: the multigrid path has no such dependency.
-struct RocSolverApi {
-    void* lib = nullptr;
-    int (*create_handle)(void**) = nullptr;
-    int (*destroy_handle)(void*) = nullptr;
-    int (*set_stream)(void*, hipStream_t) = nullptr;
-    int (*getrf)(void*, int, int, double*, int, long long, int*, long long, int*, int) = nullptr;
-    int (*getri)(void*, int, double*, int, long long, int*, long long, int*, int) = nullptr;
-    std::string err;
-    // already in the process (loaded by us earlier, or e.g. by PyTorch)?  Then using it costs nothing; a first load of the
-    // ~0.9 GB library can take minutes on a machine that has never read it.
-    bool resident() {
-        if (lib) return true;
-        const char* names[] = {"librocsolver.so.0", "librocsolver.so"};
-        for (const char* n : names)
-            if (void* h = dlopen(n, RTLD_NOLOAD | RTLD_LAZY)) { dlclose(h); return true; }
-        return false;
-    }
-    bool load() {
-        if (lib) return true;
-        const char* names[] = {getenv("VOF_ROCSOLVER_LIB"), "librocsolver.so.0", "librocsolver.so", "/opt/rocm/lib/librocsolver.so.0"};
-        for (const char* n : names) {
-            if (!n || !*n) continue;
-            lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-            if (lib) break;
-        }
-        if (!lib) {
-            const char* e = dlerror();   // (one call: dlerror() clears the message it returns)
-            err = std::string("cannot load rocSOLVER: ") + (e ? e : "not found");
-            return false;
-        }
-        create_handle = (int (*)(void**))dlsym(lib, "rocblas_create_handle");
-        destroy_handle = (int (*)(void*))dlsym(lib, "rocblas_destroy_handle");
-        set_stream = (int (*)(void*, hipStream_t))dlsym(lib, "rocblas_set_stream");
-        getrf = (int (*)(void*, int, int, double*, int, long long, int*, long long, int*, int))dlsym(lib, "rocsolver_dgetrf_strided_batched");
-        getri = (int (*)(void*, int, double*, int, long long, int*, long long, int*, int))dlsym(lib, "rocsolver_dgetri_strided_batched");
-        if (!create_handle || !destroy_handle || !set_stream || !getrf || !getri) {
-            err = "rocSOLVER / rocBLAS symbols missing";
-            dlclose(lib);
-            lib = nullptr;
-            return false;
-        }
-        return true;
-    }
-};
-RocSolverApi g_roc;
-
 // Dense inverse of the Schur blocks, all in-house: the one-workgroup Gauss-Jordan kernel with partial pivoting up to
 // DIRECT_OWN_MAX unknowns per image row (images up to 66 pixels wide), the blocked Gauss-Jordan on the FP64 matrix cores
-// beyond (vof_direct.hpp).  VOF_DIRECT_LU=own|blocked|rocsolver forces one (rocSOLVER getrf + getri,
-// round 2's choice for wide images, is loaded with dlopen only when asked for: an A/B reference, not a product path).
+// beyond (vof_direct.hpp).  (Round 2 used rocSOLVER's getrf + getri for wide images.)
 constexpr int DIRECT_OWN_MAX = 192;   // (round 2: 640; the blocked inverse is 6.6 x faster on the reference's 400-combination sweep at 128 x 128: 29.6 -> 4.5 s)
-bool direct_uses_rocsolver(const vof_ctx*) {
-    const char* e = getenv("VOF_DIRECT_LU");
-    return e && e[0] == 'r';
-}
-bool direct_uses_blocked(const vof_ctx* c) {
-    if (const char* e = getenv("VOF_DIRECT_LU")) return e[0] == 'b';
-    return 3 * c->L[0].nj > DIRECT_OWN_MAX;
-}
+bool direct_uses_blocked(const vof_ctx* c) { return 3 * c->L[0].nj > DIRECT_OWN_MAX; }
 int direct_ld(const vof_ctx* c) {
     const int m = 3 * c->L[0].nj;
     return direct_uses_blocked(c) ? ((m + DNB - 1) / DNB) * DNB : m;
@@ -1403,15 +1298,8 @@ int direct_capacity(vof_ctx* c, int want) {
 int direct_alloc(vof_ctx* c, int pairs) {
     if (c->dir_cap >= pairs) return 0;
     if (c->dir_cap > 0) { c->err = "direct preconditioner buffers already allocated for a smaller batch"; return -3; }
-    const bool trace = getenv("VOF_TRACE") != nullptr;
     const size_t ni = c->L[0].ni, nj = c->L[0].nj, m = 3 * nj, P = (size_t)pairs, ld = (size_t)direct_ld(c);
     c->dir_ld = (int)ld;
-    if (direct_uses_rocsolver(c)) {
-        // (the library is ~0.9 GB: its first load on a machine can take minutes; the small blocks use the built-in kernel)
-        if (trace) { fprintf(stderr, "[vof] direct_alloc: loading rocSOLVER\n"); fflush(stderr); }
-        if (!g_roc.load()) { c->err = g_roc.err; return -3; }
-        if (trace) { fprintf(stderr, "[vof] direct_alloc: rocSOLVER loaded, allocating for %d pairs\n", pairs); fflush(stderr); }
-    }
     if (int rc = dev_alloc(c, &c->dir_T, P * ni * ld * ld)) return rc;
     if (int rc = dev_alloc(c, &c->dir_W, P * ld * ld)) return rc;
     if (direct_uses_blocked(c)) {
@@ -1429,12 +1317,6 @@ int direct_alloc(vof_ctx* c, int pairs) {
     if (int rc = dev_alloc(c, &c->dir_t, P * m)) return rc;
     if (int rc = dev_alloc(c, &c->dir_ipiv, P * m)) return rc;
     if (int rc = dev_alloc(c, &c->dir_info, P)) return rc;
-    if (direct_uses_rocsolver(c) && !c->roc_handle) {
-        if (trace) { fprintf(stderr, "[vof] direct_alloc: rocblas_create_handle\n"); fflush(stderr); }
-        if (g_roc.create_handle(&c->roc_handle) != 0) { c->err = "rocblas_create_handle failed"; return -2; }
-        if (g_roc.set_stream(c->roc_handle, c->stream) != 0) { c->err = "rocblas_set_stream failed"; return -2; }
-        if (trace) { fprintf(stderr, "[vof] direct_alloc: handle ready\n"); fflush(stderr); }
-    }
     c->dir_cap = pairs;
     return 0;
 }
@@ -1464,24 +1346,17 @@ int direct_setup(vof_ctx* c, int np) {
                 k_dir_bgj_panel<<<dim3(nt, 2, np), 256, bgj_lds, s>>>(Tp, sT, ld, kt, c->dir_R, c->dir_C, c->dir_D, c->dir_info);
                 k_dir_bgj_update<<<dim3(nt, nt, np), 256, bgj_lds, s>>>(Tp, sT, ld, kt, c->dir_R, c->dir_C, c->dir_D);
             }
-        } else if (direct_uses_rocsolver(c)) {
-            if (g_roc.getrf(c->roc_handle, m, m, Tp, m, (long long)sT, c->dir_ipiv, (long long)m, c->dir_info, np) != 0 ||
-                g_roc.getri(c->roc_handle, m, Tp, m, (long long)sT, c->dir_ipiv, (long long)m, c->dir_info, np) != 0) {
-                c->err = "rocSOLVER getrf / getri failed";
-                return -2;
-            }
         } else {
             k_dir_invert<<<np, 1024, 2 * (size_t)m * sizeof(double), s>>>(Tp, sT, m, c->dir_ipiv, c->dir_info);
         }
     }
     HIPCHK(hipGetLastError());
-    if (!direct_uses_rocsolver(c)) {   // a singular pivot anywhere makes the preconditioner useless for that pair: report it instead of iterating on garbage
-        std::vector<int> info((size_t)np);
-        HIPCHK(hipMemcpyAsync(info.data(), c->dir_info, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (int k = 0; k < np; ++k)
-            if (info[k] != 0) { c->err = "direct preconditioner: a Schur block of pair " + std::to_string(k) + " of the batch is singular"; return -2; }
-    }
+    // a singular pivot anywhere makes the preconditioner useless for that pair: report it instead of iterating on garbage
+    std::vector<int> info((size_t)np);
+    HIPCHK(hipMemcpyAsync(info.data(), c->dir_info, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < np; ++k)
+        if (info[k] != 0) { c->err = "direct preconditioner: a Schur block of pair " + std::to_string(k) + " of the batch is singular"; return -2; }
     return 0;
 }
 
@@ -1807,7 +1682,7 @@ size_t vof_query_workspace_for(int n_i, int n_j, int B, int coarse_precision, in
     if (n_i < 4 || n_j < 4 || B < 1 || coarse_precision < 0 || coarse_precision > 3) return 0;
     size_t ni = n_i - 2, nj = n_j - 2, total = 0, b = (size_t)B;
     std::vector<std::pair<size_t, size_t>> lv{{ni, nj}};
-    while (std::max(lv.back().first, lv.back().second) > (size_t)coarsest_max())
+    while (std::max(lv.back().first, lv.back().second) > (size_t)COARSEST_MAX)
         lv.push_back({(lv.back().first + 1) / 2, (lv.back().second + 1) / 2});
     size_t words = 0;   // 32-bit words of stencil storage
     total += (9 + ((vcycle_precision == 1 || vcycle_precision == 2) && lv.size() > 1 ? 1 : 0)) * b * 3 * ni * nj;
@@ -1900,33 +1775,15 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     if (const char* e = getenv("VOF_DEBUG_POISON")) c->dbg_poison = e[0] != '0';
     if (c->dbg_sync)
         if (const char* e = getenv("VOF_DEBUG_SYNC_FILE")) c->dbg_fd = open(e, O_WRONLY | O_CREAT, 0644);
-    if (const char* e = getenv("VOF_PRECOND_QUIRKS")) { c->pq_hier = e[0] != '0'; c->pq_smooth = e[0] && e[1] != '0'; }
-    if (!c->pq_smooth) c->trail_enabled = false;   // the fused Krylov product shares the smoother's operator
-    if (const char* e = getenv("VOF_SWEEP_GEO")) {   // experiment switch: "AA", "AB" (default), "BA", "BB" = fine,stored
-        c->geo_b_fine = e[0] == 'B';
-        c->geo_b_stored = e[0] && e[1] == 'B';
-    }
-    if (const char* e = getenv("VOF_STREAM_APPLY")) c->stream_apply = e[0] != '0';
-    if (const char* e = getenv("VOF_FUSE_RESTRICT")) c->fuse_restrict = e[0] != '0';
-    if (const char* e = getenv("VOF_FUSE_PROLONG")) c->fuse_prolong = e[0] != '0';
-    if (const char* e = getenv("VOF_FUSE_RESU")) c->fuse_resu = e[0] != '0';
-    if (const char* e = getenv("VOF_SWEEP_ST")) c->sweep_st = e[0] != '0';
     if (const char* e = getenv("VOF_FOLD_STORED")) c->fold_stored = e[0] != '0';
-    if (const char* e = getenv("VOF_SKIP_COLOUR0")) c->skip_colour0 = e[0] != '0';
-    if (const char* e = getenv("VOF_COARSE_TAIL")) c->tail_enabled = e[0] != '0';
-    if (const char* e = getenv("VOF_SWEEP0")) c->sweep0 = e[0] != '0';
-    if (const char* e = getenv("VOF_FUSE_APPLY")) c->trail_enabled = e[0] != '0';
-    if (const char* e = getenv("VOF_SWEEP0R")) c->sweep0r = e[0] != '0';
     if (const char* e = getenv("VOF_L0_HANDOFF")) c->l0_handoff = e[0] != '0';
-    if (const char* e = getenv("VOF_SWEEP0P")) c->sweep0p = e[0] != '0';
     if (const char* e = getenv("VOF_SWEEP0R_MIN_BLOCKS")) c->sweep0r_min_blocks = atol(e);
     if (const char* e = getenv("VOF_FUSE_B")) c->fuse_b = e[0] != '0';
     if (const char* e = getenv("VOF_FUSE_RR")) c->fuse_rr = e[0] != '0';
-    if (const char* e = getenv("VOF_SWEEP0M")) { c->sweep0m = e[0] != '0'; c->sweep0m_pairs = e[0] != '0' && e[0] != '1'; }
     // level shapes
     Level l0; l0.ni = n_i - 2; l0.nj = n_j - 2; l0.npts = (size_t)l0.ni * l0.nj;
     c->L.push_back(l0);
-    while (std::max(c->L.back().ni, c->L.back().nj) > coarsest_max()) {
+    while (std::max(c->L.back().ni, c->L.back().nj) > COARSEST_MAX) {
         Level k; k.ni = (c->L.back().ni + 1) / 2; k.nj = (c->L.back().nj + 1) / 2; k.npts = (size_t)k.ni * k.nj;
         c->L.push_back(k);
     }
@@ -1939,8 +1796,8 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     for (int l = 0; l < nl; ++l) {
         Level& lv = c->L[l];
         auto valloc = [&](void** q) { double* t = nullptr; int rc = dev_alloc(c, &t, (size_t)B * 3 * lv.npts); *q = t; return rc; };
-        // residual scratch: level 0 needs it only with the stand-alone residual + restriction kernels (experiment switches)
-        if (l + 1 < nl && (l > 0 || !(c->stream_apply && c->fuse_restrict))) if (int rc = valloc(&lv.r)) return rc;
+        // residual scratch (level 0 forms its coarse right-hand side without a residual vector)
+        if (l + 1 < nl && l > 0) if (int rc = valloc(&lv.r)) return rc;
         if (l + 1 < nl) if (int rc = valloc(&lv.x2)) return rc;
         if (l > 0) {
             if (int rc = valloc(&lv.x)) return rc;
@@ -2424,7 +2281,7 @@ static int solve_range_dev(vof_ctx* c, const double* frames, int P, double* v_x,
         if (!items.empty() && direct_ok_for_fallback(c)) {
             std::vector<vof_pair_stats> st(items.size());
             if (int rc = direct_solve_list(c, frames, items, v_x, v_y, remodelling, speed, st.data())) {
-                if (rc != -3) return rc;     // -3: no room / no rocSOLVER: keep the reported non-convergence
+                if (rc != -3) return rc;     // -3: no room: keep the reported non-convergence
                 c->err.clear();
             } else {
                 for (size_t i = 0; i < which.size(); ++i) {

@@ -432,41 +432,6 @@ __global__ __launch_bounds__(NT) void k_rhs(const double* __restrict__ frames, s
 }
 
 // ------------------------------------------------------------------------------------------
-// k_apply0: y = A x (MODE 0) or y = b - A x (MODE 1) on the fine level, matrix-free.
-// ------------------------------------------------------------------------------------------
-// XT / BT / YT: storage types of x, b, y (float for the mixed-precision V-cycle; arithmetic is always FP64).
-template <int MODE, typename XT, typename BT, typename YT>
-__global__ __launch_bounds__(NT) void k_apply0(const double* __restrict__ frames, size_t frame_stride, int Nj, int ni,
-                                               int nj, double alpha, double beta, int quirks,
-                                               const XT* __restrict__ x, const BT* __restrict__ b,
-                                               YT* __restrict__ y, const int* __restrict__ active,
-                                               const PairParam* __restrict__ pp) {
-    int q = blockIdx.x * BX + threadIdx.x, p = blockIdx.y * BY + threadIdx.y, pair = blockIdx.z;
-    if (active && !active[pair]) return;
-    if (p >= ni || q >= nj) return;
-    int fidx = pair;
-    if (pp) { alpha = pp[pair].alpha; beta = pp[pair].beta; fidx = pp[pair].frame; }
-    size_t npts = (size_t)ni * nj, idx = (size_t)p * nj + q, off = (size_t)pair * 3 * npts;
-    PixCoef k = pix_coef(frames + (size_t)fidx * frame_stride, Nj, p, q, quirks);
-    Nbr n;
-    load_nbr(x + off, npts, ni, nj, p, q, n);
-    double y0, y1, y2;
-    offdiag0(k, alpha, beta, n, y0, y1, y2);
-    const double P = k.P;
-    y0 += (P * (k.Dxx - 2 * P) - 4 * alpha) * n.u[4] + P * k.Dxy * n.w[4];
-    y1 += (P * (k.Dyy - 2 * P) - 4 * alpha) * n.w[4] + P * k.Dxy * n.u[4];
-    y2 += (-1 - 4 * beta) * n.g[4] + k.Dx * n.u[4] + k.Dy * n.w[4];
-    if (MODE == 1) {
-        y0 = (double)b[off + idx] - y0;
-        y1 = (double)b[off + npts + idx] - y1;
-        y2 = (double)b[off + 2 * npts + idx] - y2;
-    }
-    y[off + idx] = (YT)y0;
-    y[off + npts + idx] = (YT)y1;
-    y[off + 2 * npts + idx] = (YT)y2;
-}
-
-// ------------------------------------------------------------------------------------------
 // k_gs0: one colour of the 4-colour 3x3-block Gauss-Seidel sweep on the fine level (in place).
 // colour = 2 (p mod 2) + (q mod 2).  The diagonal block is lower-triangular in gamma:
 //   [[axx, c, 0], [c, ayy, 0], [Dx, Dy, -1-4 beta]]  ->  2x2 solve, then back-substitution.
@@ -1868,52 +1833,6 @@ struct SweepRows {
     size_t cp;        // stored levels: row part of the colour-split coefficient index
 };
 
-// ---- policy: level 0, matrix-free -----------------------------------------------------------
-struct SweepFine {
-    const double* frames;  // previous frame of pair 0
-    size_t frame_stride;
-    int Nj;
-    double alpha, beta;
-    int quirks;
-    const PairParam* pp;   // per-pair overrides (virtual pairs) or nullptr
-    static constexpr bool kHasImage = true;
-    static constexpr int kPrefetch = 0;   // no per-point coefficient planes
-    static constexpr int kMinWaves = 1;
-    struct cset_t { __device__ __forceinline__ void clear() {} };
-    __device__ __forceinline__ void prefetch(const SweepCols&, size_t, int, cset_t&) const {}
-    __device__ __forceinline__ void prefetch_u(size_t, unsigned, int, cset_t&) const {}
-
-    template <class G, typename VT>
-    __device__ __forceinline__ void update(const SweepCols& cc, const SweepRows& rw, const VT* xs, const double* im,
-                                           int /*pair*/, const cset_t& /*cf*/, double b0, double b1, double b2,
-                                           double& u, double& w, double& gm) const {
-        constexpr int W = G::W;
-        const double* r0 = im + rw.iU;
-        const double* r1 = im + rw.iC;
-        const double* r2 = im + rw.iD;
-        double imm = r0[cc.iL], im0 = r0[cc.iC], imp = r0[cc.iR];
-        double i0m = r1[cc.iL], i00 = r1[cc.iC], i0p = r1[cc.iR];
-        double ipm = r2[cc.iL], ip0 = r2[cc.iC], ipp = r2[cc.iR];
-        const VT* ru = xs + rw.xU;
-        const VT* rc = xs + rw.xC;
-        const VT* rd = xs + rw.xD;
-        // corner ghosts carry the factor 2 (x(0,0) = x(2,0) + x(0,2) = 2 x(2,2))
-        const double sUL = (rw.oU && cc.oL) ? 2.0 : 1.0, sUR = (rw.oU && cc.oR) ? 2.0 : 1.0;
-        const double sDL = (rw.oD && cc.oL) ? 2.0 : 1.0, sDR = (rw.oD && cc.oR) ? 2.0 : 1.0;
-        Nbr n;
-        n.u[0] = (double)ru[cc.cL]; n.w[0] = (double)ru[W + cc.cL];
-        n.u[1] = (double)ru[cc.cC]; n.w[1] = (double)ru[W + cc.cC]; n.g[1] = (double)ru[2 * W + cc.cC];
-        n.u[2] = (double)ru[cc.cR]; n.w[2] = (double)ru[W + cc.cR];
-        n.u[3] = (double)rc[cc.cL]; n.w[3] = (double)rc[W + cc.cL]; n.g[3] = (double)rc[2 * W + cc.cL];
-        n.u[5] = (double)rc[cc.cR]; n.w[5] = (double)rc[W + cc.cR]; n.g[5] = (double)rc[2 * W + cc.cR];
-        n.u[6] = (double)rd[cc.cL]; n.w[6] = (double)rd[W + cc.cL];
-        n.u[7] = (double)rd[cc.cC]; n.w[7] = (double)rd[W + cc.cC]; n.g[7] = (double)rd[2 * W + cc.cC];
-        n.u[8] = (double)rd[cc.cR]; n.w[8] = (double)rd[W + cc.cR];
-        const double imv[9] = {imm, im0, imp, i0m, i00, i0p, ipm, ip0, ipp};
-        gs0_point<true>(imv, n, sUL, sUR, sDL, sDR, alpha, beta, 1.0 / (-1 - 4 * beta), quirks, b0, b1, b2, u, w, gm);
-    }
-};
-
 // ---- policy: stored Galerkin stencil (levels >= 1) -------------------------------------------
 template <typename CT>
 struct SweepStored {
@@ -2713,10 +2632,10 @@ __global__ __launch_bounds__(GeoB::THREADS, SweepStBudget<CT>::kMinWaves) void k
 }
 
 // k_sweep0: the fused 4-colour sweep of level 0 (matrix-free), the north-star kernel.  Same schedule, strip geometry
-// (120 owned + 2 x 4 halo columns, 4 colour waves, 12-row ring, bands of TI rows) and results as
-// k_sweep<SweepFine, GeoA> above - bit for bit - but the row loop is rebuilt around its instruction budget (the PMC
-// profile of the generic kernel showed more scalar than vector instructions per wave and a fifth of its time lost to
-// the compute stage not overlapping the row traffic):
+// (120 owned + 2 x 4 halo columns, 4 colour waves, 12-row ring, bands of TI rows) and results as the first-generation
+// level-0 instantiation of the generic k_sweep above (retired) - bit for bit - but the row loop is rebuilt around its
+// instruction budget (the PMC profile of the generic kernel showed more scalar than vector instructions per wave and a
+// fifth of its time lost to the compute stage not overlapping the row traffic):
 //  * x rows and image rows share ONE ring row (3 x 128 VT + 132 doubles), so a single running byte offset per row
 //    addresses both; ring offsets and global row offsets are advanced incrementally (no per-step multiplications);
 //  * the steps of a band in which every row touched is an interior row that exists (58 of 71 steps of a 128-row band) run

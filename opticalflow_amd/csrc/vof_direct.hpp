@@ -3,7 +3,7 @@
 // With the unknowns of one image row as a block (m = 3 n_j: field-major inside the row), the 9-point operator is block
 // tridiagonal: A = tridiag(L_p, D_p, U_p), L_p = A(row p, row p-1), U_p = A(row p, row p+1) (the mirror rows of the
 // reference, OF.py:964-1070, fold onto rows 1 and n-2, i.e. stay inside the pattern).  Block elimination
-//     S_0 = D_0,   S_p = D_p - L_p S_{p-1}^{-1} U_{p-1},   T_p = S_p^{-1} (dense m x m, rocSOLVER getrf + getri),
+//     S_0 = D_0,   S_p = D_p - L_p S_{p-1}^{-1} U_{p-1},   T_p = S_p^{-1} (dense m x m, inverted in-house),
 // then z = A^{-1} r by  y_p = r_p - L_p T_{p-1} y_{p-1}  (forward)  and  x_p = T_p (y_p - U_p x_{p+1})  (backward).
 // L, D, U are never stored as matrices: their 3x3 blocks come from a per-row table of the folded stencil blocks, so the
 // Schur update costs 9 terms per entry instead of a dense product, and only the dense inverses T_p are kept
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_dir_schur(const double* __restrict__ ta
 // of 1024 threads per matrix of the batch.  Row exchanges are recorded and undone as column exchanges at the end
 // (A^{-1} = (P A)^{-1} P).  Every step rewrites the whole matrix through one CU (~2 x 8 m^2 bytes), i.e. ~10 ms per 444 x 444
 // matrix: fine for the down-sampled images the reference runs its parameter sweeps on (150^2: 148 Schur blocks per pair,
-// pairs in parallel on different CUs); wide images go to rocSOLVER instead (vof.hip).  info[pair] = 1: a zero pivot.
+// pairs in parallel on different CUs); wide images go to the blocked inverse below instead (vof.hip).  info[pair] = 1: a zero pivot.
 __global__ __launch_bounds__(1024) void k_dir_invert(double* __restrict__ A, size_t strideA, int m, int* __restrict__ ipiv,
                                                      int* __restrict__ info) {
     extern __shared__ double dinv_sh[];

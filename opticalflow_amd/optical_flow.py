@@ -204,9 +204,9 @@ def _solver_params(speed_alpha, remodelling_alpha, delta_x, delta_t, initial_v_x
 
 def _direct_unavailable(exc):
     """True if a native call failed only because the direct preconditioner cannot be used here (too large for the free
-    device memory, or no rocSOLVER): ``use_direct_solver=True`` then falls back to the multigrid path at rtol 1e-10."""
+    device memory): ``use_direct_solver=True`` then falls back to the multigrid path at rtol 1e-10."""
     msg = str(exc)
-    return "direct preconditioner does not fit" in msg or "cannot load rocSOLVER" in msg or "rocSOLVER / rocBLAS symbols" in msg
+    return "direct preconditioner does not fit" in msg
 
 
 def variational_optical_flow(movie,

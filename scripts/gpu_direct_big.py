@@ -1,5 +1,5 @@
 """Direct preconditioner at 514x514 in the regime where the multigrid cycle stagnates (8-bit data, speed_alpha = 1e4):
-rocSOLVER path (Schur blocks of 1536 unknowns).  Prints timings; VOF_TRACE=1 shows the library load."""
+Schur blocks of 1536 unknowns, inverted by the blocked Gauss-Jordan kernels.  Prints timings; VOF_TRACE=1 shows the progress."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np

@@ -1,5 +1,5 @@
 """Fixed-work timing of the level-0 smoother (vof_bench_sweeps_dev): n sweeps on P pairs, HIP-event time per launch.
-usage: python scripts/gpu_sweep_micro.py [pairs] [sweeps] ; VOF_LIB selects an alternative build, VOF_SWEEP0M the kernel."""
+usage: python scripts/gpu_sweep_micro.py [pairs] [sweeps] ; VOF_LIB selects an alternative build."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
