@@ -142,6 +142,9 @@ int vof_default_params(vof_params* p, size_t struct_size);
  * Read at every vof_box_flow_dev / _host call:
  *   VOF_BOXFLOW_FUSED=0        box flow: the general three-kernel path through device scratch planes also for box sizes up to 31
  *                              (default: the fused LDS kernel k_boxflow_fused there); same window sums in another order
+ * Read at every vof_liu_shen_dev / _host call:
+ *   VOF_LIUSHEN_FUSE=k         Liu-Shen flow: k = 1 .. 8 Jacobi iterations per launch (default 4: the LDS kernel k_ls_fused);
+ *                              1: one iteration per launch from and to device memory (k_ls_step).  Same bits for every k
  * Debug switches (fault attribution; they change timing, never results):
  *   VOF_DEBUG_SYNC=1           the context's stream is synchronised and asked for its error after every launch scope; the
  *                              first failure is reported on stderr and appended to every later error text as
@@ -208,6 +211,25 @@ int vof_box_flow_dev(vof_ctx* ctx, const double* movie, int n_frames, int box_si
 int vof_box_flow_host(vof_ctx* ctx, const double* movie, int n_frames, int box_size, double delta_x, double delta_t,
                       int include_remodelling, int reference_quirks,
                       double* v_x, double* v_y, double* speed, double* net_remodelling);
+
+/* Replaces liu_shen_optical_flow_jit (OF.py:426-673), the physics-based flow of Liu and Shen without remodelling as exactly
+ * max_iterations Jacobi iterations per pair (frame k, frame k + 1): every pixel is updated from the old iterate by a 9-point
+ * stencil and the closed-form solve of its constant 2 x 2 block [[I Ixx - 2 I^2 - n alpha, I Ixy], [I Ixy, I Iyy - 2 I^2 - n alpha]]
+ * (n = 8 / 5 / 3 in the interior / on an edge line / in a corner).  Frames and fields are mirrored over the image edge
+ * (row -1 = row 1), except in the 8-neighbour sums, which take outside neighbours as zero.  Every pair starts from
+ * initial_v_x * delta_t / delta_x (no warm start between pairs); v_x, v_y come back times delta_x / delta_t, speed is their
+ * norm, remodelling the initial one.  A singular block stores what IEEE division gives.
+ * initial_kind 0: initial_v_x, initial_v_y, initial_remodelling each point to ONE double in host memory (both variants);
+ * 1: to an (n_i, n_j) plane used for every pair; 2: to an (n_frames - 1, n_i, n_j) stack.  With 1 and 2 they are device
+ * arrays for _dev and host arrays for _host; initial_remodelling must not be one of the outputs of _dev.
+ * movie: (n_frames, n_i, n_j) float64 (n_i, n_j >= 3); outputs (n_frames - 1, n_i, n_j) float64, caller allocated, every element
+ * written (speed and remodelling hold iterates on the way).  max_iterations >= 1. */
+int vof_liu_shen_dev(vof_ctx* ctx, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
+                     const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
+                     int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling);
+int vof_liu_shen_host(vof_ctx* ctx, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
+                      const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
+                      int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling);
 
 /* Summary of one (speed_alpha, remodelling_alpha) combination of vary_regularisation (OF.py:1978-1983). */
 typedef struct vof_variation_stats {

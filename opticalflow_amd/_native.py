@@ -74,6 +74,8 @@ SIGNATURES = {
     "vof_blur_stack_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int]),
     "vof_box_flow_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "vof_box_flow_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "vof_liu_shen_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "vof_liu_shen_host": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "vof_vary_regularisation_host": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
@@ -291,6 +293,46 @@ class Solver:
                                        int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(v_x), _ptr(v_y),
                                        _ptr(speed), _ptr(net_remodelling))
         self._check(rc, "vof_box_flow_dev")
+
+    @staticmethod
+    def _initial_kind(fields, pairs_shape):
+        """The common kind of the three initial fields of the Liu-Shen flow: 0 scalar, 1 plane, 2 stack."""
+        kinds = {(): 0, tuple(pairs_shape[1:]): 1, tuple(pairs_shape): 2}
+        try:
+            return max(kinds[tuple(f.shape)] for f in fields)
+        except KeyError:
+            raise ValueError(f"initial fields must be scalars, {tuple(pairs_shape[1:])} planes or {tuple(pairs_shape)} stacks") from None
+
+    def liu_shen_host(self, movie: np.ndarray, delta_x=1.0, delta_t=1.0, alpha=100.0, initial_v_x=0.0, initial_v_y=0.0,
+                      initial_remodelling=0.0, max_iterations=10):
+        """Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) of a host movie; returns
+        ``(v_x, v_y, speed, remodelling)``, float64 ``(T - 1, n_i, n_j)`` each.  The initial fields are scalars, ``(n_i, n_j)``
+        planes or ``(T - 1, n_i, n_j)`` stacks; they are passed in the widest of the three forms."""
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        T = movie.shape[0]
+        shape = (max(T - 1, 0), self.n_i, self.n_j)
+        init = [np.asarray(f, dtype=np.float64) for f in (initial_v_x, initial_v_y, initial_remodelling)]
+        kind = self._initial_kind(init, shape)
+        init = [np.ascontiguousarray(np.broadcast_to(f, ((), shape[1:], shape)[kind])).reshape(-1) for f in init]
+        out = [np.empty(shape) for _ in range(4)]
+        rc = self.lib.vof_liu_shen_host(self.h, _ptr(movie), T, float(delta_x), float(delta_t), float(alpha), *[_ptr(f) for f in init],
+                                        kind, int(max_iterations), *[_ptr(o) for o in out])
+        self._check(rc, "vof_liu_shen_host")
+        return tuple(out)
+
+    def liu_shen_dev(self, movie, n_frames, delta_x, delta_t, alpha, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
+                     max_iterations, v_x, v_y, speed, remodelling):
+        """The same on device memory (torch tensors or raw pointers).  ``initial_kind`` 0: the three initial fields are Python
+        floats; 1 / 2: device planes / stacks.  Every element of the outputs is written."""
+        if initial_kind == 0:
+            keep = [np.array([float(f)]) for f in (initial_v_x, initial_v_y, initial_remodelling)]
+        else:
+            keep = [initial_v_x, initial_v_y, initial_remodelling]
+        rc = self.lib.vof_liu_shen_dev(self.h, _ptr(movie), int(n_frames), float(delta_x), float(delta_t), float(alpha),
+                                       *[_ptr(f) for f in keep], int(initial_kind), int(max_iterations), _ptr(v_x), _ptr(v_y),
+                                       _ptr(speed), _ptr(remodelling))
+        self._check(rc, "vof_liu_shen_dev")
 
     def vary_regularisation_host(self, movie: np.ndarray, params: VofParams, speed_alphas, remodelling_alphas, weights=None):
         """The whole (speed_alpha, remodelling_alpha) sweep of vary_regularisation on the device; returns a structured

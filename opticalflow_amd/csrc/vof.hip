@@ -11,6 +11,7 @@
 #include "vof_sweep0p.hpp"
 #include "vof_direct.hpp"
 #include "vof_boxflow.hpp"
+#include "vof_liushen.hpp"
 #include "../../include/vof.h"
 
 #include <fcntl.h>
@@ -109,6 +110,7 @@ struct vof_ctx {
     double *blur_tmp = nullptr, *blur_w = nullptr, *blur_io = nullptr;   // Gaussian blur scratch (lazy)
     double* bf_scratch = nullptr;                                        // box flow, general path: derived planes + row sums (lazy)
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
+    bool ls_lds_set = false;                                             // Liu-Shen flow, fused kernel: dynamic LDS limit raised
     double* tex_tab = nullptr;                                           // synthetic-texture tables (lazy)
     size_t tex_cap = 0;
     // GMRES fallback (allocated on first use): basis vectors V_0..V_m (each B * len0), per-pair state, partials, flags
@@ -3299,6 +3301,134 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
                 if (int rc = d2h_bounced(c, outs[f] + (size_t)k0 * fs, c->st_out[f], (size_t)np * fb)) return rc;
     }
     if (!include_remodelling && net_remodelling) memset(net_remodelling, 0, (size_t)P * fb);
+    return 0;
+}
+
+// ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------
+constexpr int LS_CHUNK = 16384;           // pairs per launch (grid z)
+
+static int liu_shen_check(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, const double* ix, const double* iy,
+                          const double* ir, int initial_kind, int max_iterations, const double* v_x, const double* v_y,
+                          const double* speed, const double* remodelling) {
+    if (!movie || !v_x || !v_y || !speed || !remodelling || !ix || !iy || !ir) { c->err = "NULL array pointer"; return -1; }
+    if (n_frames < 2) { c->err = "need at least two frames"; return -1; }
+    if (initial_kind < 0 || initial_kind > 2) { c->err = "initial_kind must be 0 (scalar), 1 (plane) or 2 (stack)"; return -1; }
+    if (max_iterations < 1) { c->err = "max_iterations must be >= 1"; return -1; }
+    if (c->Ni < 3 || c->Nj < 3) { c->err = "the Liu-Shen flow needs image sides >= 3"; return -1; }
+    if (delta_x == 0.0 || delta_t == 0.0) { c->err = "delta_x and delta_t must not be 0"; return -1; }
+    return 0;
+}
+
+// iterations per launch: VOF_LIUSHEN_FUSE, read at every call
+static int liu_shen_depth(vof_ctx* c, int* depth) {
+    *depth = LS_KDEF;
+    if (const char* e = getenv("VOF_LIUSHEN_FUSE")) {
+        *depth = atoi(e);
+        if (*depth < 1 || *depth > LS_KMAX) { c->err = "VOF_LIUSHEN_FUSE must be 1 .. 8"; return -1; }
+    }
+    return 0;
+}
+
+// P pairs of a device-resident movie into device-resident outputs, enqueued on the context's stream.  The iterates
+// ping-pong between (v_x, v_y) and (speed, remodelling); ix / iy / ir are device arrays of initial_kind 1 / 2 (ix, iy may be
+// any of the four outputs), sx / sy / sr the scalars of kind 0.  write_remodelling false leaves remodelling as scratch.
+static int liu_shen_pairs(vof_ctx* c, const double* movie, int P, double delta_x, double delta_t, double alpha, const double* ix,
+                          const double* iy, const double* ir, double sx, double sy, double sr, int kind, int iterations, int depth,
+                          double* v_x, double* v_y, double* speed, double* remodelling, bool write_remodelling) {
+    const size_t fs = frame_stride(c);
+    if (depth > 1 && !c->ls_lds_set) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_ls_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls_fused_lds(LS_KMAX)));
+        c->ls_lds_set = true;
+    }
+    for (int k0 = 0; k0 < P; k0 += LS_CHUNK) {
+        const int np = std::min(LS_CHUNK, P - k0);
+        const size_t off = (size_t)k0 * fs, n = (size_t)np * fs;
+        const unsigned nb = (unsigned)((n + 255) / 256);
+        double* buf[2][2] = {{v_x + off, v_y + off}, {speed + off, remodelling + off}};
+        const size_t ioff = kind == 2 ? off : 0;
+        c->cur_units = np;
+        Prof prof(c, VOF_K_RHS, 0);
+        k_ls_init<<<nb, 256, 0, c->stream>>>(buf[0][0], buf[0][1], kind ? ix + ioff : nullptr, kind ? iy + ioff : nullptr, sx, sy, kind,
+                                             fs, n, delta_t, delta_x);
+        LsArgs a{};
+        a.movie = movie + off; a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj; a.alpha = alpha;
+        int cur = 0;
+        for (int done = 0; done < iterations;) {
+            const int k = std::min(depth, iterations - done);
+            a.k = k;
+            a.sx = buf[cur][0]; a.sy = buf[cur][1]; a.dx = buf[cur ^ 1][0]; a.dy = buf[cur ^ 1][1];
+            if (depth == 1) {
+                k_ls_step<<<grid2d(c->Ni, c->Nj, np), blk2d, 0, c->stream>>>(a);
+            } else {
+                const dim3 g((c->Nj + LS_TJ - 1) / LS_TJ, (c->Ni + LS_TI - 1) / LS_TI, np);
+                k_ls_fused<<<g, LS_THREADS, ls_fused_lds(k), c->stream>>>(a);
+            }
+            done += k;
+            cur ^= 1;
+        }
+        k_ls_finish<<<nb, 256, 0, c->stream>>>(buf[cur][0], buf[cur][1], buf[0][0], buf[0][1], buf[1][0],
+                                               write_remodelling ? buf[1][1] : nullptr, kind ? ir + ioff : nullptr, sr, kind, fs, n,
+                                               delta_x / delta_t);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int vof_liu_shen_dev(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
+                     const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
+                     int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling) {
+    if (!c) return -1;
+    if (int rc = liu_shen_check(c, movie, n_frames, delta_x, delta_t, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
+                                max_iterations, v_x, v_y, speed, remodelling)) return rc;
+    if (initial_kind && (initial_remodelling == remodelling || initial_remodelling == speed || initial_remodelling == v_x ||
+                         initial_remodelling == v_y)) { c->err = "initial_remodelling must not be an output array"; return -1; }
+    int depth;
+    if (int rc = liu_shen_depth(c, &depth)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const bool s = initial_kind == 0;
+    if (int rc = liu_shen_pairs(c, movie, n_frames - 1, delta_x, delta_t, alpha, initial_v_x, initial_v_y, initial_remodelling,
+                                s ? *initial_v_x : 0.0, s ? *initial_v_y : 0.0, s ? *initial_remodelling : 0.0, initial_kind,
+                                max_iterations, depth, v_x, v_y, speed, remodelling, true)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vof_liu_shen_host(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
+                      const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
+                      int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling) {
+    if (!c) return -1;
+    if (int rc = liu_shen_check(c, movie, n_frames, delta_x, delta_t, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
+                                max_iterations, v_x, v_y, speed, remodelling)) return rc;
+    int depth;
+    if (int rc = liu_shen_depth(c, &depth)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = ensure_staging(c, false)) return rc;
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const int P = n_frames - 1;
+    const bool s = initial_kind == 0;
+    double* outs[3] = {v_x, v_y, speed};
+    for (int k0 = 0; k0 < P; k0 += c->B) {
+        const int np = std::min(c->B, P - k0);
+        if (int rc = h2d_bounced(c, c->st_movie, movie + (size_t)k0 * fs, (size_t)(np + 1) * fb)) return rc;
+        // the initial fields travel through the second pair of iterate buffers, which the first iteration overwrites
+        if (initial_kind) {
+            const size_t io = initial_kind == 2 ? (size_t)k0 * fs : 0, ib = (initial_kind == 2 ? (size_t)np : 1) * fb;
+            if (int rc = h2d_bounced(c, c->st_out[2], initial_v_x + io, ib)) return rc;
+            if (int rc = h2d_bounced(c, c->st_out[3], initial_v_y + io, ib)) return rc;
+        }
+        if (int rc = liu_shen_pairs(c, c->st_movie, np, delta_x, delta_t, alpha, c->st_out[2], c->st_out[3], nullptr,
+                                    s ? *initial_v_x : 0.0, s ? *initial_v_y : 0.0, 0.0, initial_kind, max_iterations, depth,
+                                    c->st_out[0], c->st_out[1], c->st_out[2], c->st_out[3], false)) return rc;
+        for (int f = 0; f < 3; ++f)
+            if (int rc = d2h_bounced(c, outs[f] + (size_t)k0 * fs, c->st_out[f], (size_t)np * fb)) return rc;
+    }
+    // OF.py:507, 668: the initial remodelling comes back untouched
+    for (int k = 0; k < P; ++k) {
+        double* r = remodelling + (size_t)k * fs;
+        if (initial_kind == 0) std::fill(r, r + fs, *initial_remodelling);
+        else if (initial_remodelling + (initial_kind == 2 ? (size_t)k * fs : 0) != r)
+            memcpy(r, initial_remodelling + (initial_kind == 2 ? (size_t)k * fs : 0), fb);
+    }
     return 0;
 }
 

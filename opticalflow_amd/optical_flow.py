@@ -63,7 +63,8 @@ def release_device_memory(_locked=False):
 
 atexit.register(release_device_memory)
 
-__all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "vary_regularisation", "make_fake_data_frame", "blur_movie",
+__all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
+           "conduct_variational_optical_flow_deprecated", "vary_regularisation", "make_fake_data_frame", "blur_movie",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -525,6 +526,149 @@ def _conduct_optical_flow_device(movie, boxsize, delta_x, delta_t, smoothing_sig
                   original_data=movie, delta_x=delta_x, delta_t=delta_t, blurred_data=movie_to_analyse)
     if include_remodelling:
         result["net_remodelling"] = out[3]
+    return result
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Liu-Shen physics-based flow as Jacobi iterations: the reference's third estimator, OF.py:426-673, and the wrapper
+# that records its iterates, OF.py:1318-1529.
+# ---------------------------------------------------------------------------------------------------------
+def liu_shen_optical_flow_jit(movie, delta_x=1.0, delta_t=1.0, alpha=100, remodelling_alpha=1.0, initial_v_x=0.0,
+                              initial_v_y=0.0, initial_remodelling=0.0, max_iterations=10, tolerance=1e-9,
+                              include_remodelling=True, *, device=0, output="numpy"):
+    """Physics-based optical flow of Liu and Shen without remodelling, exactly ``max_iterations`` Jacobi iterations per
+    frame pair on one MI355X; positional arguments and the returned 5-tuple
+    ``(v_x, v_y, speed, remodelling, max_iterations - 1)`` as OF.py:426-673.
+
+    Pair ``k`` uses ``p`` = frame ``k`` and ``c`` = frame ``k + 1`` (float64, mirrored over the image edge: row -1 = row 1)
+    and starts from ``initial_v_x * delta_t / delta_x``, ``initial_v_y * delta_t / delta_x``; there is no warm start
+    between pairs.  Every iteration updates every pixel from the old iterate: the right-hand side of OF.py:621-630 (central
+    differences and ``v[i+1] + v[i-1]`` read the mirrored border, the 8-neighbour sums take neighbours outside the image
+    as zero) and the inverse of the pixel's constant 2 x 2 block, whose diagonal holds ``-n * alpha`` with ``n`` = 8 in the
+    interior, 5 on an edge line and 3 in a corner.  The velocities come back times ``delta_x / delta_t``, ``speed`` is their
+    norm, ``remodelling`` the initial one, untouched.  ``remodelling_alpha``, ``tolerance`` and ``include_remodelling``
+    are accepted and ignored, as in the reference.
+
+    Deviations from the reference: the initial fields may be scalars, ``(N_i, N_j)`` planes or ``(T-1, N_i, N_j)`` stacks
+    and default to 0.0 (the reference's 10 x 10 default arrays cannot broadcast); ``max_iterations < 1`` and an image side
+    below 3 raise ``ValueError`` (the device context itself needs sides of at least 4); a singular 2 x 2 block stores what
+    IEEE division gives where the reference's ``numpy.linalg.inv`` raises.  The inverse is the closed form, so results
+    agree with the reference to rounding, not bit for bit.
+
+    Keyword-only extras: ``device``, ``output`` ("numpy", or "torch": ``movie`` and the initial fields may be device
+    tensors and the four arrays come back as float64 device tensors)."""
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    shape = tuple(movie.shape)
+    if len(shape) != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    T, N_i, N_j = shape
+    if T < 2:
+        raise ValueError("movie needs at least two frames")
+    if min(N_i, N_j) < 3:
+        raise ValueError("the Liu-Shen flow needs image sides of at least 3")
+    if int(max_iterations) < 1:
+        raise ValueError("max_iterations must be >= 1")
+    initial = (initial_v_x, initial_v_y, initial_remodelling)
+    if output == "numpy":
+        frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
+        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
+            out = solver.liu_shen_host(frames, delta_x, delta_t, alpha, *initial, int(max_iterations))
+        return out + (int(max_iterations) - 1,)
+    import torch
+    dev = torch.device("cuda", int(device))
+    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
+    pairs = (T - 1, N_i, N_j)
+    # a Python float must not pass through torch's default float32
+    fields = [(f if isinstance(f, torch.Tensor) else torch.as_tensor(np.asarray(f, dtype=np.float64))).to(device=dev, dtype=torch.float64)
+              for f in initial]
+    kind = _native.Solver._initial_kind(fields, pairs)
+    if kind == 0:
+        fields = [float(f) for f in fields]
+    else:
+        fields = [f.expand(pairs[1:] if kind == 1 else pairs).contiguous() for f in fields]
+    out = [torch.empty(pairs, dtype=torch.float64, device=dev) for _ in range(4)]
+    with _box_flow_context(N_i, N_j, 1, device) as solver:
+        torch.cuda.synchronize(dev)          # the library launches on its own stream
+        solver.liu_shen_dev(frames, T, delta_x, delta_t, alpha, *fields, kind, int(max_iterations), *out)
+    return tuple(out) + (int(max_iterations) - 1,)
+
+
+def conduct_variational_optical_flow_deprecated(movie, delta_x=1.0, delta_t=1.0, speed_alpha=1.0, remodelling_alpha=1000.0,
+                                                v_x_guess=0.1, v_y_guess=0.1, remodelling_guess=0.5, max_iterations=10,
+                                                smoothing_sigma=None, return_iterations=False, iteration_stepsize=1,
+                                                tolerance=1e-10, include_remodelling=True, use_liu_shen=False, *,
+                                                device=0, output="numpy"):
+    """The reference's wrapper around ``liu_shen_optical_flow_jit`` that can record the iterates; signature and result
+    dict as OF.py:1318-1529.  ``use_liu_shen=False`` raises the reference's ``ValueError``.
+
+    Returns ``v_x``, ``v_y``, ``speed``, ``remodelling`` (float64 ``(T-1, N_i, N_j)``), ``original_data``,
+    ``blurred_data``, ``delta_x``, ``delta_t``, ``max_iterations``, ``total_iterations`` and, with ``return_iterations``,
+    ``v_x_steps``, ``v_y_steps``, ``speed_steps``, ``remodelling_steps`` of shape
+    ``(T-1, max_iterations // iteration_stepsize + 1, N_i, N_j)`` plus ``iteration_stepsize``.  Record 0 holds the guesses;
+    record ``r`` is produced as the reference does: a fresh call of ``iteration_stepsize`` iterations that starts from
+    record ``r - 1``, so the fields make the round trip through ``delta_x / delta_t`` and back between records, and the
+    final fields are the last record (``max_iterations`` rounded down to a multiple of ``iteration_stepsize``).
+
+    Deviations from the reference, whose wrapper cannot run as written: it unpacks 4 of the function's 5 return values -
+    here all 5 are unpacked; its restart passes the ``(T-1, N_i, N_j)`` result as the initial field of every pair, which
+    cannot broadcast for more than one pair - here the restart is per pair (pair ``k`` restarts from its own record);
+    ``total_iterations`` is ``max_iterations`` also without ``return_iterations`` (undefined there); an
+    ``iteration_stepsize`` outside ``1 .. max_iterations`` raises ``ValueError``; nothing is printed.
+
+    Keyword-only extras: ``device``, ``output`` ("numpy", or "torch": every array of the result stays on the device)."""
+    if not use_liu_shen:
+        raise ValueError("I can currently only really do this for the liu shen jitted method")
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    if len(movie.shape) != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    if return_iterations and not 1 <= int(iteration_stepsize) <= int(max_iterations):
+        raise ValueError("iteration_stepsize must be between 1 and max_iterations")
+    movie_to_analyse = movie
+    if smoothing_sigma is not None:
+        if output == "torch":
+            import torch
+            dev = torch.device("cuda", int(device))
+            frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
+            movie_to_analyse = torch.empty_like(frames)
+            with _box_flow_context(frames.shape[1], frames.shape[2], 1, device) as solver:
+                torch.cuda.synchronize(dev)
+                solver.blur_dev(frames, movie_to_analyse, frames.shape[0], gaussian_taps(smoothing_sigma))
+        else:
+            movie_to_analyse = blur_movie(np.asarray(movie), smoothing_sigma=smoothing_sigma, device=device)
+    guesses = (float(v_x_guess), float(v_y_guess), float(remodelling_guess))
+
+    def flow(initial, iterations):
+        return liu_shen_optical_flow_jit(movie_to_analyse, delta_x, delta_t, speed_alpha, remodelling_alpha, *initial,
+                                         max_iterations=iterations, tolerance=tolerance,
+                                         include_remodelling=include_remodelling, device=device, output=output)
+
+    result = dict()
+    if return_iterations:
+        stepsize = int(iteration_stepsize)
+        records = int(max_iterations) // stepsize
+        this = flow(guesses, stepsize)
+        steps = [f.new_zeros((f.shape[0], records + 1) + tuple(f.shape[1:])) if output == "torch"
+                 else np.zeros((f.shape[0], records + 1) + f.shape[1:]) for f in this[:4]]
+        steps[0][:, 0], steps[1][:, 0], steps[3][:, 0] = guesses
+        steps[2][:, 0] = float(np.sqrt(np.float64(guesses[0]) ** 2 + np.float64(guesses[1]) ** 2))
+        for record in range(1, records + 1):
+            if record > 1:
+                this = flow((this[0], this[1], this[3]), stepsize)
+            for f in range(4):
+                steps[f][:, record] = this[f]
+        result["v_x"], result["v_y"], result["speed"], result["remodelling"] = (s[:, -1] for s in steps)
+        result["v_x_steps"], result["v_y_steps"], result["speed_steps"], result["remodelling_steps"] = steps
+        result["iteration_stepsize"] = iteration_stepsize
+    else:
+        result["v_x"], result["v_y"], result["speed"], result["remodelling"] = flow(guesses, max_iterations)[:4]
+    result["original_data"] = movie
+    result["delta_x"] = delta_x
+    result["delta_t"] = delta_t
+    result["blurred_data"] = movie_to_analyse
+    result["max_iterations"] = max_iterations
+    result["total_iterations"] = max_iterations
     return result
 
 
