@@ -72,13 +72,11 @@ struct vof_ctx {
     double* kz = nullptr;
     double* b32 = nullptr;  // V-typed copy of the V-cycle right-hand side (p or s) when vfloat
     bool vfloat = false;    // V-cycle vectors stored as float32 (arithmetic stays FP64)
-    bool emit64 = false;    // vcycle_precision 3: the level-1 visit in progress hands its result up as float64 (see vcycle_t)
     bool vcoarse32 = false; // vcycle_precision 3: float64 vectors on level 0, float32 on the levels below (the two meet in the fused
                             // residual + restriction kernel and in the post-smoothing pass that interpolates the correction)
     bool l0_handoff = true; // VOF_L0_HANDOFF=0: the level-0 hand-off vectors stay float64 in vcycle_precision 3 (see h32)
     bool h32 = false;       // the cycles run now store their level-0 hand-off vectors as float32: the pre-smoothed iterate x and the
                             // cycle's result (y, z).  Set per BiCGStab iteration where handoff32_ok holds, and by vof_debug_vcycle*
-    bool h32_bad = false;   // ... and a level-0 pass of such a cycle was not one of the k_sweep0r passes that store float32
     const PairParam* pp = nullptr;   // per-pair (alpha, beta, frame) overrides of the current batch ("virtual pairs") or nullptr
     PairParam* pp_buf = nullptr;     // device storage for them (B entries, lazy)
     // warm start (two-phase solve of a stack): interior solutions of the phase-1 pairs, and per pair of the current
@@ -143,21 +141,11 @@ struct vof_ctx {
     double *dir_R = nullptr, *dir_C = nullptr, *dir_D = nullptr;   // blocked inverse: row panel, column panel, inverted diagonal tile
     int dir_ld = 0;                  // leading dimension of the dense blocks (m, or m rounded up to the tile size of the blocked inverse)
     long long direct_pairs = 0;      // pairs solved with the direct preconditioner since the context was created
-    // Krylov product fused into the last smoothing pass of a cycle (k_sweep0m's trailing stage): requested by the Krylov loop
-    // before the cycle, consumed by the final level-0 smoothing call if the fused path applies
-    bool trail_set = false, trail_done = false;
-    S0Trail trail_req;
-    // BiCGStab vector update folded into the cycle's first pre-smoothing pass (k_sweep0r, BF): set by the Krylov loop, consumed by
-    // the first level-0 pass from zero of the cycle (sweep_level_t), which resets bf_mode
-    // residual + restriction of level 0 as the trailing stage of the pre-smoothing pass (k_sweep0r, TRAIL = 2): requested by
-    // vcycle_t around the pre-smoothing of level 0, honoured by sweep_level_t when the pass is the two-sweep pass from zero
-    bool fuse_rr = true;        // VOF_FUSE_RR=0: the stand-alone kernel k_stream_resrestrict0
-    void* rr_out = nullptr;     // coarse right-hand side to write (nullptr: not requested)
-    bool rr_f32 = false, rr_done = false;
-    bool fuse_b = true;         // VOF_FUSE_B=0: the stand-alone kernels k_update_s / k_update_p
-    int bf_mode = 0;            // 0: none pending; 1: s = r - alpha v (+ (s, s), half-step test); 2: p = r + beta (p_old - omega v)
-    S0BSrc bf{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int trail_nblk = 0;         // per-pair partial sums the fused pass wrote
+    // what a level-0 pass may take on besides its sweeps (plan_l0_pass decides; the requests travel in CycleIO / SmoothArgs)
+    bool fuse_rr = true;        // VOF_FUSE_RR=0: the stand-alone kernel k_stream_resrestrict0 instead of the trailing stage of the
+                                // pre-smoothing pass (k_sweep0r, TRAIL = 2)
+    bool fuse_b = true;         // VOF_FUSE_B=0: the stand-alone kernels k_update_s / k_update_p instead of the vector update folded
+                                // into the cycle's first pre-smoothing pass (k_sweep0r, BF = 1 / 2)
     long sweep0r_min_blocks = 512;   // level 0, float64 vectors, even n_j: the register-resident pass k_sweep0r for launches of at least
                                      // this many one-wave blocks, the LDS-ring pass k_sweep0m below (VOF_SWEEP0R_MIN_BLOCKS; the tests set 0)
     int tail_first = -1;        // first level of the tail (-1: no tail for this grid)
@@ -590,6 +578,65 @@ inline bool sweep_st_usable(const vof_ctx* c, int l) {
     return l > 0 && c->L[l].C != nullptr && c->cfmt >= 2;
 }
 
+// vcycle_precision 3 applies when level 0 runs the kernels in which the two storage types meet: the residual + restriction
+// (float64 in, float32 out) and the k_sweep0m / k_sweep0r pass with the interpolated correction (float32 in); anything else
+// keeps float64 everywhere
+inline bool coarse32_ok(const vof_ctx* c, int nu_post) {
+    return c->vcoarse32 && c->L.size() > 1 && sweep0m_usable(c) && nu_post > 0;
+}
+
+// ---- level-0 smoothing passes: what a caller wants (L0Req), what is launched for it (L0Pass), decided in plan_l0_pass
+
+// Requests to and results of one multigrid cycle that concern its level-0 passes.  The Krylov loop (or a debug entry point)
+// fills in the inputs, hands the struct down vcycle -> vcycle_t -> smooth_level_t -> sweep_level_t and reads the outputs.
+struct CycleIO {
+    // in: the Krylov product v = A y of the cycle's result, wanted from its last smoothing pass (trail.v == nullptr: not wanted)
+    S0Trail trail{nullptr, nullptr, 0, nullptr};
+    // in: the BiCGStab vector update that forms the cycle's right-hand side, to be folded into the first pre-smoothing pass.
+    // bf_mode 0: none; 1: s = r - alpha v (+ (s, s), half-step test); 2: p = r + beta (p_old - omega v)
+    S0BSrc bf{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int bf_mode = 0;
+    // out
+    int trail_nblk = 0;      // per-pair partial sums the fused product wrote (0: not fused, the caller launches the operator)
+    bool rr_done = false;    // the last pre-smoothing pass of level 0 wrote the coarse right-hand side (read by vcycle_t)
+    bool bf_done = false;    // the folded vector update was performed
+    bool failed = false;     // c->err says why; nothing the cycle wrote may be used
+};
+
+struct L0Req {
+    bool from_zero = false;                    // start from a zero guess instead of x_in
+    int po = 0;                                // direction: 1 = reverse (colours 3,2,1,0)
+    int nsweeps = 1;                           // sweeps wanted from the pass (1 or 2)
+    bool ec = false, ec32 = false;             // start from x_in + P ecoarse; ecoarse is float32 data
+    bool trail = false, trail_dot = false;     // the Krylov product of the result is wanted; it has a dot partner
+    bool rr = false, rr_f32 = false;           // the coarse right-hand side R (b - A x_out) is wanted; as float32
+    int bf = 0;                                // folded vector update wanted (CycleIO::bf_mode)
+    bool x32 = false;                          // x_in / x_out are float32 hand-off vectors (c->h32)
+};
+
+enum L0Family { L0_SWEEP0R, L0_SWEEP0M, L0_SWEEP0P, L0_SWEEP0 };
+
+struct L0Pass {
+    L0Family fam = L0_SWEEP0;
+    // the family's template arguments (those it has)
+    int NS = 1;                  // sweeps per pass
+    bool EC = false, FROM_ZERO = false;
+    int TRAIL = 0;               // 1: Krylov product, 2: residual + restriction
+    bool ET32 = false;           // ET: float32 coarse data (the correction read, or the coarse right-hand side written)
+    int PO = 0;
+    int BF = 0;                  // 1 / 2: folded vector update; 3: b read once and carried in registers
+    bool XT32 = false;           // XT: float32 x_in / x_out
+    // launch
+    int nx = 0, nxp = 0, ny = 0, TI = 0, nci = 0, ncj = 0;
+    unsigned blocks = 0, block = 0;   // blocks per pair (the grid is blocks x pairs), threads per block
+    size_t lds = 0;
+    double algo = 0.0, moved = 0.0;   // profiler: algorithmic / minimal bytes per pair
+    // requests honoured
+    bool trail() const { return TRAIL == 1; }
+    bool rr() const { return TRAIL == 2; }
+    int bf() const { return BF == 3 ? 0 : BF; }
+};
+
 // Strips and bands of a level-0 pass of k_sweep0m / k_sweep0r (NSW sweeps per pass) and whether the register-resident kernel takes it
 struct S0Geo { int nx, ny, TI; bool s0r; };
 inline S0Geo s0_geometry(const vof_ctx* c, int rows, int NSW, bool trail) {
@@ -599,183 +646,302 @@ inline S0Geo s0_geometry(const vof_ctx* c, int rows, int NSW, bool trail) {
     g.nx = (lv.nj + out - 1) / out;
     g.TI = pick_band_height(rows, g.nx, c->cur_units);
     g.ny = (rows + g.TI - 1) / g.TI;
+    // (the register-resident pass is compiled with the reference's derivative quirk built in; one wave per block needs a few
+    // waves per SIMD-slot to fill the chip: tiny stacks - 128 x 128 x 8: 14 blocks - stay with the 4-wave LDS pass)
     g.s0r = c->prm.reference_quirks && (long)g.nx * g.ny * std::max(1, c->cur_units) >= c->sweep0r_min_blocks;
     return g;
 }
 
-// Will the next cycle start with a two-sweep level-0 pass from zero of k_sweep0r?  Then the vector update that forms the cycle's
-// right-hand side is folded into that pass (the conditions mirror vcycle_t -> smooth_level_t -> sweep_level_t).
-inline bool fold_b_usable(const vof_ctx* c) {
-    return c->fuse_b && !c->direct_on && !c->vfloat && c->L.size() > 1 && c->tail_first != 0 && c->fused && c->prm.nu_pre >= 2 &&
-           sweep0m_usable(c) && s0_geometry(c, c->L[0].ni, 2, false).s0r && s0_geometry(c, c->L[0].ni, 2, true).s0r;
+// k_sweep0r from zero: the two-sweep pass reads b once and hands it on in registers (vof_sweep0r.hpp)
+constexpr int s0r_bf_from_zero(int ns) { return (VOF_S0R_BCARRY && ns == 2) ? 3 : 0; }
+inline size_t s0r_lds(int ns, int trail) {
+    if (ns == 2) return trail == 2 ? S0R<2, 2>::LDS_TOTAL : (trail == 1 ? S0R<2, 1>::LDS_TOTAL : S0R<2, 0>::LDS_TOTAL);
+    return trail == 1 ? S0R<1, 1>::LDS_TOTAL : S0R<1, 0>::LDS_TOTAL;
 }
 
-// One full 4-colour sweep x_in -> x_out (x_in == nullptr: zero initial guess); reverse = colours 3,2,1,0.
-// nsweeps = 2 (level 0, k_sweep0m only): two consecutive sweeps in one pass.
+// The pass the matrix-free level 0 runs for `rq` with cycle vectors of type VT.  Reads the context, launches and writes nothing.
 template <typename VT>
-void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bool reverse, int np,
-                   const int* active, const VT* ecoarse = nullptr, int nsweeps = 1, bool with_trail = false, bool ec32 = false,
-                   bool out64 = false, bool skip0 = false) {
-    // out64: x_out is written as float64 although VT is float (k_sweep_st only; the caller has checked that it applies)
-    // skip0: x_in comes straight from a reverse sweep with the same b - colour 0 needs no update (k_sweep_st; elsewhere ignored)
-    // ec32: `ecoarse` really points at float32 data (float64 level 0 above float32 coarse levels; k_sweep0m only)
-    Level& lv = c->L[l];
-    int po = reverse ? 1 : 0;
-    int rows = lv.ni + po;
-    // h32: a level-0 pass that does not store float32 would break the cycle (handoff32_ok has promised k_sweep0r throughout)
-    auto h32_refuse = [c](const char* what) { c->err = std::string("float32 level-0 hand-off: ") + what; c->h32_bad = true; };
-    if (l == 0 && c->h32 && !(std::is_same<VT, double>::value && lv.C == nullptr && sweep0m_usable(c))) { h32_refuse("no k_sweep0r pass"); return; }
-    if constexpr (std::is_same<VT, double>::value) {
-        if (l == 0 && lv.C == nullptr && sweep0m_usable(c)) {
-            // k_sweep0m: merged colours, 16-byte accesses, `nsweeps` (1 or 2) sweeps per pass; strips are not shifted by po
-            const int NSW = nsweeps >= 2 ? 2 : 1;
-            const bool trail = with_trail && x_in != nullptr;
-            // the coarse right-hand side R (b - A x_out) as the trailing stage of the two-sweep pass from zero (k_sweep0r only)
-            const bool rr = c->rr_out && !x_in && NSW == 2 && !po && !ecoarse && VOF_S0R_BCARRY && s0_geometry(c, rows, NSW, true).s0r;
-            const S0Geo geo = s0_geometry(c, rows, NSW, trail || rr);
-            const int nx = geo.nx, TI = geo.TI, ny = geo.ny;
-            dim3 g((unsigned)nx * ny * np, 1, 1);
-            int nci = 0, ncj = 0;
-            double ebytes = 0.0;
-            if (ecoarse) { nci = c->L[1].ni; ncj = c->L[1].nj; ebytes = (ec32 ? 12.0 : 24.0) * c->L[1].npts; }
-            if (c->bf_mode) {   // the pass forms its right-hand side itself (the Krylov loop has checked fold_b_usable)
-                if (x_in || NSW != 2 || po || !geo.s0r || ecoarse || trail) { c->err = "folded vector update: the cycle did not start with the expected pass"; c->bf_mode = -1; return; }
-                const int mode = c->bf_mode;
-                c->bf_mode = 0;
-                if (c->h32 && !(rr && c->rr_f32)) { h32_refuse("pass from zero without the residual + restriction stage"); return; }
-                Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, 1, c->pp};
-                S0Trail tr{rr ? (double*)c->rr_out : nullptr, nullptr, 0, nullptr};
-                const size_t ldsr = rr ? S0R<2, 2>::LDS_TOTAL : S0R<2, 0>::LDS_TOTAL;
-                const int kci = c->L[1].ni, kcj = c->L[1].nj;
-                {   // I + r(3) + v(3) (+ p_old(3)) in, x(3) + b(3) out (+ the coarse right-hand side)
-                    const double cb = rr ? (c->rr_f32 ? 12.0 : 24.0) * c->L[1].npts : 0.0;
-                    const double moved = (8.0 + (mode == 2 ? 12.0 : 9.0) * 8.0 + 3.0 * (c->h32 ? 4.0 : 8.0)) * lv.npts + cb;
-                    Prof p(c, VOF_K_GS0, 0, moved + 80.0 * lv.npts + (rr ? 56.0 * lv.npts : 0.0), moved);
-#define VOF_LAUNCH_BF(TR_, ET_, BF_, XT_) k_sweep0r<2, false, true, TR_, ET_, 0, 1, BF_, XT_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, 0, nx, ny, np, nullptr, (XT_*)x_out, b, active, nullptr, kci, kcj, tr, 0, 0, c->bf)
-                    if (c->h32) { if (mode == 1) VOF_LAUNCH_BF(2, float, 1, float); else VOF_LAUNCH_BF(2, float, 2, float); }
-                    else if (rr && c->rr_f32) { if (mode == 1) VOF_LAUNCH_BF(2, float, 1, double); else VOF_LAUNCH_BF(2, float, 2, double); }
-                    else if (rr) { if (mode == 1) VOF_LAUNCH_BF(2, double, 1, double); else VOF_LAUNCH_BF(2, double, 2, double); }
-                    else { if (mode == 1) VOF_LAUNCH_BF(0, double, 1, double); else VOF_LAUNCH_BF(0, double, 2, double); }
-#undef VOF_LAUNCH_BF
-                    if (rr) c->rr_done = true;
-                }
-                if (mode == 1) {   // (s, s): stopping rule at the half step; pairs done there get their x += alpha y and leave the cycle
-                    const size_t len = 3 * lv.npts;
-                    { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_S><<<np, 64, 0, c->stream>>>(c->sc, c->partials, nx * ny, c->active, c->prm.rtol, c->prm.max_iterations); }
-                    { Prof p(c, VOF_K_VECTOR, 0);
-                      if (c->h32) k_fix_half<float><<<dim3(64, np), RBLK, 0, c->stream>>>(c->kx, (const float*)c->ky, len, c->sc);
-                      else k_fix_half<double><<<dim3(64, np), RBLK, 0, c->stream>>>(c->kx, (const double*)c->ky, len, c->sc);
-                      k_clear_half<<<(np + 255) / 256, 256, 0, c->stream>>>(c->sc, np); }
-                }
-                return;
-            }
+L0Pass plan_l0_pass(const vof_ctx* c, const L0Req& rq) {
+    const Level& lv = c->L[0];
+    const double npts = (double)lv.npts, npc = c->L.size() > 1 ? (double)c->L[1].npts : 0.0;
+    const int rows = lv.ni + rq.po;
+    L0Pass p;
+    p.NS = rq.nsweeps >= 2 ? 2 : 1;
+    p.EC = rq.ec;
+    p.FROM_ZERO = rq.from_zero && !rq.ec;
+    p.PO = rq.po;
+    if (rq.ec) { p.nci = c->L[1].ni; p.ncj = c->L[1].nj; }
+    if (std::is_same<VT, double>::value && sweep0m_usable(c)) {
+        // merged colours, 16-byte accesses, one or two sweeps per pass; strips are not shifted by po.  k_sweep0r: registers;
+        // k_sweep0m: LDS ring
+        const bool trail = rq.trail && !rq.from_zero;
+        // the coarse right-hand side as the trailing stage of the two-sweep pass from zero (k_sweep0r only)
+        const bool rr = rq.rr && c->fuse_rr && rq.from_zero && p.NS == 2 && !rq.po && !rq.ec && VOF_S0R_BCARRY &&
+                        s0_geometry(c, rows, 2, true).s0r;
+        const S0Geo geo = s0_geometry(c, rows, p.NS, trail || rr);
+        // the vector update that forms b: the same pass, whether or not it also forms the coarse right-hand side
+        const int bf = (rq.bf && c->fuse_b && geo.s0r && rq.from_zero && p.NS == 2 && !rq.po && !rq.ec) ? rq.bf : 0;
+        p.fam = geo.s0r ? L0_SWEEP0R : L0_SWEEP0M;
+        p.nx = p.nxp = geo.nx; p.ny = geo.ny; p.TI = geo.TI;
+        p.TRAIL = rr ? 2 : (trail ? 1 : 0);
+        p.ET32 = rr ? rq.rr_f32 : (rq.ec && rq.ec32);
+        p.BF = bf ? bf : ((geo.s0r && p.FROM_ZERO) ? s0r_bf_from_zero(p.NS) : 0);
+        // float32 hand-off: the pass from zero that writes the float32 coarse right-hand side, and the post-smoothing pass
+        p.XT32 = rq.x32 && geo.s0r && p.NS == 2 && (rr ? rq.rr_f32 : (rq.po && !rq.from_zero && rq.ec));
+        if (rr || bf) { p.nci = c->L[1].ni; p.ncj = c->L[1].nj; }
+        const double xs = p.XT32 ? 4.0 : 8.0;
+        const double cb = rr ? (rq.rr_f32 ? 12.0 : 24.0) * npc : 0.0;
+        if (bf) {   // I + r(3) + v(3) (+ p_old(3)) in, x(3) + b(3) out (+ the coarse right-hand side)
+            p.moved = (8.0 + (bf == 2 ? 12.0 : 9.0) * 8.0 + 3.0 * xs) * npts + cb;
+            p.algo = p.moved + 80.0 * npts + (rr ? 56.0 * npts : 0.0);
+        } else {
             // bytes the pass moves: I + b(3) + x(3) in, x(3) out (+ coarse e), whatever the number of fused sweeps; algorithmic
             // bytes (80 per sweep performed): the second sweep of a double pass counts as a full sweep
-            double moved = (8.0 + 24.0 + (x_in ? 6.0 : 3.0) * (c->h32 ? 4.0 : 8.0)) * lv.npts + ebytes;
-            double algo = moved + (NSW - 1) * 80.0 * lv.npts;
-            S0Trail tr{nullptr, nullptr, 0, nullptr};
+            p.moved = (8.0 + 24.0 + (rq.from_zero ? 3.0 : 6.0) * xs) * npts + (rq.ec ? (rq.ec32 ? 12.0 : 24.0) * npc : 0.0);
+            p.algo = p.moved + (p.NS - 1) * 80.0 * npts;
             if (trail) {   // + the operator product v = A x_out with its dot products: algorithmic 56 (+24 for the dot partner)
-                tr = c->trail_req;
-                const double dv = tr.dotvec ? 24.0 : 0.0;
-                algo += (56.0 + dv) * lv.npts;
-                moved += (24.0 + dv) * lv.npts;     // only v out and the dot partner in: x_out and the image are in LDS
-                c->trail_nblk = nx * ny;
-                c->trail_done = true;
+                const double dv = rq.trail_dot ? 24.0 : 0.0;
+                p.algo += (56.0 + dv) * npts;
+                p.moved += (24.0 + dv) * npts;     // only v out and the dot partner in: x_out and the image are in LDS
             }
-            if (rr) {   // + the coarse right-hand side out (x_out, b and the image are in registers / LDS); algorithmic: the 56 B per
-                        // pixel the stand-alone residual + restriction kernel reads
-                const double cb = (c->rr_f32 ? 12.0 : 24.0) * c->L[1].npts;
-                algo += 56.0 * lv.npts + cb;
-                moved += cb;
+            if (rr) {   // + the coarse right-hand side out (x_out, b and the image are in registers / LDS); algorithmic: the 56 B
+                        // per pixel the stand-alone residual + restriction kernel reads
+                p.algo += 56.0 * npts + cb;
+                p.moved += cb;
             }
-            Prof p(c, VOF_K_GS0, 0, algo, moved);
-            Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, c->prm.reference_quirks, c->pp};
-            const size_t lds = (size_t)(6 * NSW + 2 + (trail ? 4 : 0)) * s0_row_bytes(8) + (ecoarse ? (size_t)9 * (S0_W / 2 + 2) * 8 : 0);
-#define VOF_LAUNCH_S0M(NS_)                                                                                                        \
-            do {                                                                                                                    \
-                if (trail && ecoarse && ec32) k_sweep0m<NS_, true, false, 1, float><<<g, 128 * NS_, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, (const float*)ecoarse, nci, ncj, tr); \
-                else if (ecoarse && ec32) k_sweep0m<NS_, true, false, 0, float><<<g, 128 * NS_, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, (const float*)ecoarse, nci, ncj, tr); \
-                else if (trail && ecoarse) k_sweep0m<NS_, true, false, 1><<<g, 128 * NS_, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else if (trail) k_sweep0m<NS_, false, false, 1><<<g, 128 * NS_, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else if (ecoarse) k_sweep0m<NS_, true, false, 0><<<g, 128 * NS_, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else if (!x_in) k_sweep0m<NS_, false, true, 0><<<g, 128 * NS_, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else k_sweep0m<NS_, false, false, 0><<<g, 128 * NS_, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-            } while (0)
-#define S0R_BF(NS_) ((VOF_S0R_BCARRY && (NS_) == 2) ? 3 : 0)   /* the two-sweep pass from zero reads b once (vof_sweep0r.hpp) */
-#define VOF_LAUNCH_S0R(NS_, PO_)                                                                                                   \
-            do {                                                                                                                    \
-                const size_t ldsr = trail ? S0R<NS_, 1>::LDS_TOTAL : S0R<NS_, 0>::LDS_TOTAL;                                         \
-                if (trail && ecoarse && ec32) k_sweep0r<NS_, true, false, 1, float, PO_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, (const float*)ecoarse, nci, ncj, tr); \
-                else if (ecoarse && ec32) k_sweep0r<NS_, true, false, 0, float, PO_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, (const float*)ecoarse, nci, ncj, tr); \
-                else if (trail && ecoarse) k_sweep0r<NS_, true, false, 1, double, PO_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else if (trail) k_sweep0r<NS_, false, false, 1, double, PO_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else if (ecoarse) k_sweep0r<NS_, true, false, 0, double, PO_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else if (!x_in) k_sweep0r<NS_, false, true, 0, double, PO_, 1, S0R_BF(NS_)><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-                else k_sweep0r<NS_, false, false, 0, double, PO_><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, tr); \
-            } while (0)
-            // (the register-resident pass is compiled with the reference's derivative quirk built in; one wave per block needs
-            // a few waves per SIMD-slot to fill the chip: tiny stacks - 128 x 128 x 8: 14 blocks - stay with the 4-wave LDS pass)
-            if (c->h32 && !(geo.s0r && NSW == 2 && (rr ? c->rr_f32 : (po && x_in && ecoarse)))) { h32_refuse("not a float32 k_sweep0r pass"); return; }
-            if (rr) {
-                S0Trail trr{(double*)c->rr_out, nullptr, 0, nullptr};
-                const size_t ldsr = S0R<2, 2>::LDS_TOTAL;
-                if (c->h32) k_sweep0r<2, false, true, 2, float, 0, 1, 3, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, nullptr, (float*)x_out, b, active, nullptr, c->L[1].ni, c->L[1].nj, trr);
-                else if (c->rr_f32) k_sweep0r<2, false, true, 2, float, 0, 1, 3><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, c->L[1].ni, c->L[1].nj, trr);
-                else k_sweep0r<2, false, true, 2, double, 0, 1, 3><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, c->L[1].ni, c->L[1].nj, trr);
-                c->rr_done = true;
-                return;
-            }
-            if (c->h32) {   // the post-smoothing pass: float32 x in (+ the interpolated correction), float32 y out
-                const size_t ldsr = trail ? S0R<2, 1>::LDS_TOTAL : S0R<2, 0>::LDS_TOTAL;
-                const float* xi = (const float*)x_in;
-                float* xo = (float*)x_out;
-                if (trail && ec32) k_sweep0r<2, true, false, 1, float, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, (const float*)ecoarse, nci, ncj, tr);
-                else if (trail) k_sweep0r<2, true, false, 1, double, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, ecoarse, nci, ncj, tr);
-                else if (ec32) k_sweep0r<2, true, false, 0, float, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, (const float*)ecoarse, nci, ncj, tr);
-                else k_sweep0r<2, true, false, 0, double, 1, 1, 0, float><<<g, 64, ldsr, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, xi, xo, b, active, ecoarse, nci, ncj, tr);
-            }
-            else if (geo.s0r) {
-                if (NSW == 2) { if (po) VOF_LAUNCH_S0R(2, 1); else VOF_LAUNCH_S0R(2, 0); }
-                else { if (po) VOF_LAUNCH_S0R(1, 1); else VOF_LAUNCH_S0R(1, 0); }
-            }
-            else if (NSW == 2) VOF_LAUNCH_S0M(2); else VOF_LAUNCH_S0M(1);
-#undef VOF_LAUNCH_S0R
-#undef S0R_BF
-#undef VOF_LAUNCH_S0M
-            return;
         }
+        if (geo.s0r) { p.block = 64; p.lds = s0r_lds(p.NS, p.TRAIL); }
+        else { p.block = 128 * p.NS; p.lds = (size_t)(6 * p.NS + 2 + (trail ? 4 : 0)) * s0_row_bytes(8) + (rq.ec ? (size_t)9 * (S0_W / 2 + 2) * 8 : 0); }
+    } else if (std::is_same<VT, float>::value && sweep0p_usable(c)) {
+        // k_sweep0p: packed float32 arithmetic, two strips per wave, one or two sweeps per pass
+        const int out = S0_W - 8 * p.NS;
+        p.fam = L0_SWEEP0P;
+        p.nx = (lv.nj + out - 1) / out; p.nxp = (p.nx + 1) / 2;
+        p.TI = pick_band_height(rows, p.nxp, c->cur_units);
+        p.ny = (rows + p.TI - 1) / p.TI;
+        p.moved = (8.0 + (rq.from_zero ? 6.0 : 9.0) * 4.0) * npts + (rq.ec ? 12.0 * npc : 0.0);   // I + b(3) + x(3) in, x(3) out, float32 vectors
+        p.algo = p.moved + (p.NS - 1) * 44.0 * npts;
+        p.block = 64; p.lds = p.NS == 2 ? S0R<2, 0>::LDS_BYTES : S0R<1, 0>::LDS_BYTES;
+    } else {
+        // k_sweep0: one sweep per pass, strips of 120 owned columns, shifted by the pass's direction
+        const double vs = sizeof(VT);
+        p.fam = L0_SWEEP0;
+        p.NS = 1;
+        p.nx = p.nxp = (lv.nj + rq.po + S0_OUT - 1) / S0_OUT;
+        p.TI = pick_band_height(rows, p.nx, c->cur_units);
+        p.ny = (rows + p.TI - 1) / p.TI;
+        p.algo = p.moved = (8.0 + (rq.from_zero ? 6.0 : 9.0) * vs) * npts + (rq.ec ? 3.0 * vs * npc : 0.0);   // I + b(3) + x(3) in, x(3) out (+ coarse e)
+        p.block = S0_THREADS;
+        p.lds = (size_t)(SW_RING * 3 * S0_W) * sizeof(VT) + (size_t)(SW_RING * S0_IW) * sizeof(double) +
+                (rq.ec ? (size_t)(3 * 3 * (S0_W / 2 + 2)) * sizeof(VT) : 0);
     }
-    if constexpr (std::is_same<VT, float>::value) {
-        if (l == 0 && lv.C == nullptr && sweep0p_usable(c)) {
-            const int NSW = nsweeps >= 2 ? 2 : 1;
-            const int out = S0_W - 8 * NSW;
-            const int nx = (lv.nj + out - 1) / out, nxp = (nx + 1) / 2;
-            const int TI = pick_band_height(rows, nxp, c->cur_units);
-            const int ny = (rows + TI - 1) / TI;
-            dim3 g((unsigned)nxp * ny * np, 1, 1);
-            int nci = 0, ncj = 0;
-            double ebytes = 0.0;
-            if (ecoarse) { nci = c->L[1].ni; ncj = c->L[1].nj; ebytes = 12.0 * c->L[1].npts; }
-            const double moved = (8.0 + (x_in ? 9.0 : 6.0) * 4.0) * lv.npts + ebytes;   // I + b(3) + x(3) in, x(3) out, float32 vectors
-            Prof p(c, VOF_K_GS0, 0, moved + (NSW - 1) * 44.0 * lv.npts, moved);
-            Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, 1, c->pp};
-#define VOF_LAUNCH_S0P(NS_, PO_)                                                                                                    \
-            do {                                                                                                                    \
-                const size_t ldsp = S0R<NS_, 0>::LDS_BYTES;                                                                         \
-                if (ecoarse) k_sweep0p<NS_, true, false, PO_><<<g, 64, ldsp, c->stream>>>(f0, lv.ni, lv.nj, TI, nx, nxp, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj); \
-                else if (!x_in) k_sweep0p<NS_, false, true, PO_><<<g, 64, ldsp, c->stream>>>(f0, lv.ni, lv.nj, TI, nx, nxp, ny, np, x_in, x_out, b, active, nullptr, 0, 0); \
-                else k_sweep0p<NS_, false, false, PO_><<<g, 64, ldsp, c->stream>>>(f0, lv.ni, lv.nj, TI, nx, nxp, ny, np, x_in, x_out, b, active, nullptr, 0, 0); \
-            } while (0)
-            if (NSW == 2) { if (po) VOF_LAUNCH_S0P(2, 1); else VOF_LAUNCH_S0P(2, 0); }
-            else { if (po) VOF_LAUNCH_S0P(1, 1); else VOF_LAUNCH_S0P(1, 0); }
-#undef VOF_LAUNCH_S0P
-            return;
+    p.blocks = (unsigned)p.nxp * p.ny;
+    return p;
+}
+
+// The level-0 passes of the cycle the current parameters describe, as vcycle_t -> smooth_level_t will request them
+inline L0Req l0_pre_request(const vof_ctx* c, int bf) {    // first pre-smoothing pass
+    L0Req rq;
+    rq.from_zero = true;
+    rq.nsweeps = std::min(2, c->prm.nu_pre);
+    rq.rr = c->prm.nu_pre <= 2;   // (it is also the last one)
+    rq.rr_f32 = coarse32_ok(c, c->prm.nu_post);
+    rq.bf = bf;
+    return rq;
+}
+inline L0Req l0_post_request(const vof_ctx* c, bool trail) {   // post-smoothing in one pass (nu_post 2)
+    L0Req rq;
+    rq.po = 1; rq.nsweeps = 2; rq.ec = true;   // (the correction's storage type does not change the choice)
+    rq.trail = rq.trail_dot = trail;
+    return rq;
+}
+
+// Will the next cycle start with a level-0 pass that takes the vector update forming its right-hand side?
+inline bool fold_b_usable(const vof_ctx* c) {
+    return !c->direct_on && c->L.size() > 1 && c->tail_first != 0 && c->prm.nu_pre >= 2 &&
+           plan_l0_pass<double>(c, l0_pre_request(c, 1)).bf() == 1;
+}
+
+// vcycle_precision 3: the level-0 hand-off vectors - the pre-smoothed iterate x and the cycle's result y / z - are stored as
+// float32 (h32) when every level-0 pass of the cycle can store them: one pre-smoothing pass from zero that forms the float32
+// coarse right-hand side (nu_pre 2) and one post-smoothing pass that interpolates the correction (nu_post 2)
+inline bool handoff32_ok(const vof_ctx* c) {
+    const vof_params& P = c->prm;
+    if (!(c->l0_handoff && P.nu_pre == 2 && P.nu_post == 2 && coarse32_ok(c, P.nu_post))) return false;
+    L0Req pre = l0_pre_request(c, 0), post = l0_post_request(c, false), post_trail = l0_post_request(c, true);
+    pre.x32 = post.x32 = post_trail.x32 = true;
+    return plan_l0_pass<double>(c, pre).XT32 && plan_l0_pass<double>(c, post).XT32 && plan_l0_pass<double>(c, post_trail).XT32;
+}
+
+// ---- one launcher per kernel family.  A row names one instantiation and launches it if the plan asks for exactly that one;
+// the rows are the kernels the library contains (a plan that matches no row is an error, not a reason to instantiate more):
+//
+//   family     rows  template arguments
+//   k_sweep0r   28   <NS 1|2, EC, FROM_ZERO, TRAIL, ET, PO 0|1, 1, BF, double>, for each NS x PO the seven shapes
+//                      (EC, FROM_ZERO, TRAIL, ET) = (1,0,1,float) (1,0,0,float) (1,0,1,double) (0,0,1,double) (1,0,0,double)
+//                      (0,1,0,double; BF = 3 for NS 2, else 0) (0,0,0,double)
+//                3   <2, 0, 1, 2, ET, 0, 1, 3, XT>       (ET, XT) = (float,float) (float,double) (double,double): + coarse rhs
+//                8   <2, 0, 1, TRAIL, ET, 0, 1, BF 1|2, XT>  (TRAIL, ET, XT) = the three above with TRAIL 2, and (0,double,double)
+//                4   <2, 1, 0, TRAIL 0|1, ET float|double, 1, 1, 0, float>   float32 hand-off, post-smoothing
+//   k_sweep0m   14   <NS 1|2, EC, FROM_ZERO, TRAIL, ET>, the same seven shapes
+//   k_sweep0p   12   <NS 1|2, EC, FROM_ZERO, PO 0|1>, (EC, FROM_ZERO) = (1,0) (0,1) (0,0)
+//   k_sweep0     6   <VT double|float, EC, FROM_ZERO>, (EC, FROM_ZERO) = (1,0) (0,1) (0,0)
+struct L0Ptrs {
+    const void* x_in; void* x_out; const void* b; const int* active; const void* ecoarse;
+    S0Trail tr; S0BSrc bsrc;
+};
+template <int V> using IntTag = std::integral_constant<int, V>;
+template <typename T> constexpr bool is_f32() { return std::is_same<T, float>::value; }
+
+template <int NS, bool EC, bool FZ, int TR, typename ET, int PO, int BF = 0, typename XT = double>
+bool s0r_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    if (p.NS != NS || p.EC != EC || p.FROM_ZERO != FZ || p.TRAIL != TR || p.ET32 != is_f32<ET>() || p.PO != PO || p.BF != BF || p.XT32 != is_f32<XT>()) return false;
+    k_sweep0r<NS, EC, FZ, TR, ET, PO, 1, BF, XT><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, np, (const XT*)a.x_in, (XT*)a.x_out, (const double*)a.b, a.active,
+        (const ET*)a.ecoarse, p.nci, p.ncj, a.tr, 0, 0, a.bsrc);
+    return true;
+}
+bool launch_s0r(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    auto shapes = [&](auto ns, auto po) {
+        constexpr int NS = decltype(ns)::value, PO = decltype(po)::value;
+        return s0r_row<NS, true, false, 1, float, PO>(c, p, f0, np, a) || s0r_row<NS, true, false, 0, float, PO>(c, p, f0, np, a) ||
+               s0r_row<NS, true, false, 1, double, PO>(c, p, f0, np, a) || s0r_row<NS, false, false, 1, double, PO>(c, p, f0, np, a) ||
+               s0r_row<NS, true, false, 0, double, PO>(c, p, f0, np, a) ||
+               s0r_row<NS, false, true, 0, double, PO, s0r_bf_from_zero(NS)>(c, p, f0, np, a) ||
+               s0r_row<NS, false, false, 0, double, PO>(c, p, f0, np, a);
+    };
+    auto from_zero = [&](auto bf) {   // the two-sweep pass from zero with the coarse right-hand side and / or the vector update
+        constexpr int BF = decltype(bf)::value;
+        return s0r_row<2, false, true, 2, float, 0, BF, float>(c, p, f0, np, a) || s0r_row<2, false, true, 2, float, 0, BF, double>(c, p, f0, np, a) ||
+               s0r_row<2, false, true, 2, double, 0, BF, double>(c, p, f0, np, a);
+    };
+    return from_zero(IntTag<3>{}) || from_zero(IntTag<1>{}) || from_zero(IntTag<2>{}) ||
+           s0r_row<2, false, true, 0, double, 0, 1, double>(c, p, f0, np, a) || s0r_row<2, false, true, 0, double, 0, 2, double>(c, p, f0, np, a) ||
+           s0r_row<2, true, false, 1, float, 1, 0, float>(c, p, f0, np, a) || s0r_row<2, true, false, 1, double, 1, 0, float>(c, p, f0, np, a) ||
+           s0r_row<2, true, false, 0, float, 1, 0, float>(c, p, f0, np, a) || s0r_row<2, true, false, 0, double, 1, 0, float>(c, p, f0, np, a) ||
+           shapes(IntTag<2>{}, IntTag<0>{}) || shapes(IntTag<2>{}, IntTag<1>{}) || shapes(IntTag<1>{}, IntTag<0>{}) || shapes(IntTag<1>{}, IntTag<1>{});
+}
+
+template <int NS, bool EC, bool FZ, int TR, typename ET = double>
+bool s0m_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    if (p.NS != NS || p.EC != EC || p.FROM_ZERO != FZ || p.TRAIL != TR || p.ET32 != is_f32<ET>()) return false;
+    k_sweep0m<NS, EC, FZ, TR, ET><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, np, (const double*)a.x_in, (double*)a.x_out, (const double*)a.b, a.active,
+        (const ET*)a.ecoarse, p.nci, p.ncj, a.tr);
+    return true;
+}
+bool launch_s0m(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    auto shapes = [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        return s0m_row<NS, true, false, 1, float>(c, p, f0, np, a) || s0m_row<NS, true, false, 0, float>(c, p, f0, np, a) ||
+               s0m_row<NS, true, false, 1>(c, p, f0, np, a) || s0m_row<NS, false, false, 1>(c, p, f0, np, a) ||
+               s0m_row<NS, true, false, 0>(c, p, f0, np, a) || s0m_row<NS, false, true, 0>(c, p, f0, np, a) ||
+               s0m_row<NS, false, false, 0>(c, p, f0, np, a);
+    };
+    return shapes(IntTag<2>{}) || shapes(IntTag<1>{});
+}
+
+template <int NS, bool EC, bool FZ, int PO>
+bool s0p_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    if (p.NS != NS || p.EC != EC || p.FROM_ZERO != FZ || p.PO != PO) return false;
+    k_sweep0p<NS, EC, FZ, PO><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.nx, p.nxp, p.ny, np, (const float*)a.x_in, (float*)a.x_out, (const float*)a.b, a.active,
+        (const float*)a.ecoarse, p.nci, p.ncj);
+    return true;
+}
+bool launch_s0p(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    auto shapes = [&](auto ns, auto po) {
+        constexpr int NS = decltype(ns)::value, PO = decltype(po)::value;
+        return s0p_row<NS, true, false, PO>(c, p, f0, np, a) || s0p_row<NS, false, true, PO>(c, p, f0, np, a) ||
+               s0p_row<NS, false, false, PO>(c, p, f0, np, a);
+    };
+    return shapes(IntTag<2>{}, IntTag<0>{}) || shapes(IntTag<2>{}, IntTag<1>{}) || shapes(IntTag<1>{}, IntTag<0>{}) || shapes(IntTag<1>{}, IntTag<1>{});
+}
+
+template <typename VT, bool EC, bool FZ>
+bool s0_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    if (p.EC != EC || p.FROM_ZERO != FZ) return false;
+    k_sweep0<VT, EC, FZ><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, np, (const VT*)a.x_in, (VT*)a.x_out, (const VT*)a.b, a.active,
+        (const VT*)a.ecoarse, p.nci, p.ncj);
+    return true;
+}
+template <typename VT>
+bool launch_s0(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+    return s0_row<VT, true, false>(c, p, f0, np, a) || s0_row<VT, false, true>(c, p, f0, np, a) || s0_row<VT, false, false>(c, p, f0, np, a);
+}
+
+// The folded s update (BF = 1) is followed, in stream order, by what follows the stand-alone k_update_s: (s, s) and the stopping
+// rule at the half step; pairs done there get their x += alpha y and leave the cycle
+void fold_s_epilogue(vof_ctx* c, int np, const L0Pass& p) {
+    const size_t len = 3 * c->L[0].npts;
+    { Prof pr(c, VOF_K_VECTOR, 0); k_scalar<S_S><<<np, 64, 0, c->stream>>>(c->sc, c->partials, (int)p.blocks, c->active, c->prm.rtol, c->prm.max_iterations); }
+    { Prof pr(c, VOF_K_VECTOR, 0);
+      if (p.XT32) k_fix_half<float><<<dim3(64, np), RBLK, 0, c->stream>>>(c->kx, (const float*)c->ky, len, c->sc);
+      else k_fix_half<double><<<dim3(64, np), RBLK, 0, c->stream>>>(c->kx, (const double*)c->ky, len, c->sc);
+      k_clear_half<<<(np + 255) / 256, 256, 0, c->stream>>>(c->sc, np); }
+}
+
+// Options of smooth_level_t, and of the passes it issues through sweep_level_t
+template <typename VT>
+struct SmoothArgs {
+    bool from_zero = false;        // smooth_level_t: start from a zero guess instead of the contents of x
+    bool reverse = false;          // colours 3,2,1,0
+    const VT* ecoarse = nullptr;   // coarse-grid correction still to be added (x += P ecoarse)
+    bool ec32 = false;             // ... which really is float32 data (float64 level 0 above float32 coarse levels)
+    bool allow_swap = false;       // smooth_level_t: the result may be left in `tmp`
+    bool final_smooth = false;     // smooth_level_t: the last pass is the cycle's last (it takes the Krylov product, if one is wanted)
+    bool out64 = false;            // the result is written as float64 although VT is float (k_sweep_st; the caller has checked that it applies)
+    bool skip0 = false;            // x comes straight from a reverse sweep with the same b: colour 0 needs no update (k_sweep_st)
+    void* rr_out = nullptr;        // level 0: the coarse right-hand side is wanted from the last pass, written here ...
+    bool rr_f32 = false;           // ... as float32
+    int nsweeps = 1;               // sweep_level_t: sweeps of this pass (2: level 0 only)
+    bool trail = false;            // sweep_level_t: this pass is the cycle's last
+};
+
+// One pass x_in -> x_out (x_in == nullptr: zero initial guess): a.nsweeps full 4-colour sweeps.
+template <typename VT>
+void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, int np, const int* active, const SmoothArgs<VT>& a,
+                   CycleIO& io) {
+    Level& lv = c->L[l];
+    const VT* ecoarse = a.ecoarse;
+    const int po = a.reverse ? 1 : 0;
+    if (l == 0 && lv.C == nullptr) {   // matrix-free level 0
+        L0Req rq;
+        rq.from_zero = x_in == nullptr; rq.po = po; rq.nsweeps = a.nsweeps;
+        rq.ec = ecoarse != nullptr; rq.ec32 = a.ec32;
+        rq.trail = a.trail && io.trail.v != nullptr; rq.trail_dot = io.trail.dotvec != nullptr;
+        rq.rr = a.rr_out != nullptr; rq.rr_f32 = a.rr_f32;
+        rq.bf = io.bf_done ? 0 : io.bf_mode;
+        rq.x32 = c->h32;
+        const L0Pass p = plan_l0_pass<VT>(c, rq);
+        // handoff32_ok asked the same planner, so this holds unless a caller set h32 for a cycle it was not asked about
+        if (p.XT32 != c->h32) { c->err = "float32 level-0 hand-off: the planned pass does not store float32"; io.failed = true; return; }
+        const S0Trail no_trail{nullptr, nullptr, 0, nullptr};
+        const L0Ptrs ptrs{x_in, x_out, b, active, ecoarse,
+                          p.rr() ? S0Trail{(double*)a.rr_out, nullptr, 0, nullptr} : (p.trail() ? io.trail : no_trail),
+                          p.bf() ? io.bf : S0BSrc{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};
+        const Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, c->prm.reference_quirks, c->pp};
+        bool launched = false;
+        {
+            Prof pr(c, VOF_K_GS0, 0, p.algo, p.moved);
+            switch (p.fam) {
+                case L0_SWEEP0R: launched = launch_s0r(c, p, f0, np, ptrs); break;
+                case L0_SWEEP0M: launched = launch_s0m(c, p, f0, np, ptrs); break;
+                case L0_SWEEP0P: launched = launch_s0p(c, p, f0, np, ptrs); break;
+                case L0_SWEEP0: launched = launch_s0<VT>(c, p, f0, np, ptrs); break;
+            }
         }
+        if (!launched) { c->err = "internal: the library holds no kernel for the planned level-0 pass"; io.failed = true; return; }
+        if (p.trail()) io.trail_nblk = (int)p.blocks;
+        if (p.rr()) io.rr_done = true;
+        if (p.bf()) { io.bf_done = true; if (p.bf() == 1) fold_s_epilogue(c, np, p); }
+        return;
     }
-    // k_sweep0 on the matrix-free level 0: strips of 120 owned columns, shifted by the pass's direction; the stored levels: 128-column aligned strips
-    const bool fine0 = l == 0 && lv.C == nullptr;
-    const int out = fine0 ? S0_OUT : GeoB::OUT, W = fine0 ? S0_W : GeoB::W;
-    const int nx = (lv.nj + (fine0 ? po : 0) + out - 1) / out;
+    // the stored levels: 128-column aligned strips
+    const int rows = lv.ni + po;
+    const int W = GeoB::W;
+    const int nx = (lv.nj + GeoB::OUT - 1) / GeoB::OUT;
     const int TI = pick_band_height(rows, nx, c->cur_units);
     const int ny = (rows + TI - 1) / TI;
     dim3 g((unsigned)nx * ny * np, 1, 1);
@@ -783,88 +949,78 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, bo
     int nci = 0, ncj = 0;
     double ebytes = 0.0;
     if (ecoarse) { nci = c->L[l + 1].ni; ncj = c->L[l + 1].nj; ebytes = 3.0 * vs * c->L[l + 1].npts; }
-    if (fine0) {
-        Prof p(c, VOF_K_GS0, 0, (8.0 + (x_in ? 9.0 : 6.0) * vs) * lv.npts + ebytes);   // I + b(3) + x(3) in, x(3) out (+ coarse e)
-        Fine0 f0{c->frames, frame_stride(c), c->Nj, c->prm.speed_alpha, c->prm.remodelling_alpha, c->prm.reference_quirks, c->pp};
-        size_t lds = (size_t)(SW_RING * 3 * W) * sizeof(VT) + (size_t)(SW_RING * S0_IW) * sizeof(double) +
-                     (ecoarse ? (size_t)(3 * 3 * (W / 2 + 2)) * sizeof(VT) : 0);
-        if (ecoarse) k_sweep0<VT, true, false><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-        else if (!x_in) k_sweep0<VT, false, true><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-        else k_sweep0<VT, false, false><<<g, S0_THREADS, lds, c->stream>>>(f0, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-    } else {
-        Prof p(c, VOF_K_GS, l, (coef_bytes(c, l) + (x_in ? 9.0 : 6.0) * vs) * lv.npts + ebytes);   // C + b(3) + x(3) in, x(3) out (+ coarse e)
-        size_t lds = (size_t)(SW_RING * 3 * W) * sizeof(VT);
-        if (sweep_st_usable(c, l)) {   // packed stencil formats: the kernel with the decoupled coefficient stream
-            const uint32_t* Cw = (const uint32_t*)lv.C;
-            auto launch = [&](auto ct_tag) {
-            using PCT = typename decltype(ct_tag)::type;
-            if (ecoarse) {   // the sweep starts from x_in + P ecoarse (coarse rows through a 3-row LDS ring)
-                const size_t lds_e = lds + (size_t)9 * (W / 2 + 2) * sizeof(VT);
-                if (out64) k_sweep_st<PCT, VT, double, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, (double*)x_out, b, active, ecoarse, nci, ncj, 0);
-                else k_sweep_st<PCT, VT, VT, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, 0);
-            } else {
-                const int sk = (skip0 && x_in && !reverse) ? 1 : 0;
-                if (out64) k_sweep_st<PCT, VT, double><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, (double*)x_out, b, active, nullptr, 0, 0, sk);
-                else k_sweep_st<PCT, VT><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, 0, 0, sk);
-            }
-            };
-            if (c->cfmt == 3) launch(TypeTag<CoefF8>{}); else launch(TypeTag<CoefB16>{});
-            return;
+    Prof p(c, VOF_K_GS, l, (coef_bytes(c, l) + (x_in ? 9.0 : 6.0) * vs) * lv.npts + ebytes);   // C + b(3) + x(3) in, x(3) out (+ coarse e)
+    size_t lds = (size_t)(SW_RING * 3 * W) * sizeof(VT);
+    if (sweep_st_usable(c, l)) {   // packed stencil formats: the kernel with the decoupled coefficient stream
+        const uint32_t* Cw = (const uint32_t*)lv.C;
+        auto launch = [&](auto ct_tag) {
+        using PCT = typename decltype(ct_tag)::type;
+        if (ecoarse) {   // the sweep starts from x_in + P ecoarse (coarse rows through a 3-row LDS ring)
+            const size_t lds_e = lds + (size_t)9 * (W / 2 + 2) * sizeof(VT);
+            if (a.out64) k_sweep_st<PCT, VT, double, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, (double*)x_out, b, active, ecoarse, nci, ncj, 0);
+            else k_sweep_st<PCT, VT, VT, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, 0);
+        } else {
+            const int sk = (a.skip0 && x_in && !a.reverse) ? 1 : 0;
+            if (a.out64) k_sweep_st<PCT, VT, double><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, (double*)x_out, b, active, nullptr, 0, 0, sk);
+            else k_sweep_st<PCT, VT><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, 0, 0, sk);
         }
-        CDISPATCH(c, l, {
-            SweepStored<CT> pol; pol.C = (const CW*)lv.C; pol.plane = CLay(lv.ni, lv.nj).plane;
-            k_sweep<SweepStored<CT>, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
-        });
+        };
+        if (c->cfmt == 3) launch(TypeTag<CoefF8>{}); else launch(TypeTag<CoefB16>{});
+        return;
     }
+    CDISPATCH(c, l, {
+        SweepStored<CT> pol; pol.C = (const CW*)lv.C; pol.plane = CLay(lv.ni, lv.nj).plane;
+        k_sweep<SweepStored<CT>, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
+    });
 }
 
-// nu sweeps (from a zero guess if from_zero, else from x); the result is guaranteed to end in `x`.
+// nu sweeps (from a zero guess if a.from_zero, else from x); the result is guaranteed to end in `x`, or - with a.allow_swap - in
+// the buffer returned: `x`, or `tmp` when the last out-of-place sweep ended there (saves a device-to-device copy on the coarse levels).
+// a.ecoarse: on the matrix-free level 0 it is folded into the first sweep (coarse rows streamed through LDS); otherwise the
+// prolongation kernel runs first.
 template <typename VT>
-VT* smooth_level_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int nu, bool from_zero, bool reverse, int np,
-                   const int* active, const VT* ecoarse = nullptr, bool allow_swap = false, bool final_smooth = false,
-                   bool ec32 = false, bool out64 = false, bool skip0 = false) {
-    // Returns the buffer that holds the result: `x`, or `tmp` when allow_swap is set and the last out-of-place sweep
-    // ended there (saves a device-to-device copy on the coarse levels).
-    // ecoarse: coarse-grid correction still to be added (x += P ecoarse).  On the matrix-free level 0 it is folded
-    // into the first sweep (coarse rows streamed through LDS); otherwise the prolongation kernel runs first.
+VT* smooth_level_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int nu, int np, const int* active, SmoothArgs<VT> a, CycleIO& io) {
     const size_t bytes = (size_t)np * 3 * c->L[l].npts * sizeof(VT);
-    const bool fold = ecoarse && nu > 0 && c->fused && !from_zero &&
-                      ((l == 0 && c->L[0].C == nullptr) || (sweep_st_usable(c, l) && c->fold_stored));
-    if (ecoarse && !fold) {
-        prolong_add_level_t<VT>(c, l, x, ecoarse, np, active);
-        ecoarse = nullptr;
+    const bool fine0 = l == 0 && c->L[0].C == nullptr;
+    const bool fold = a.ecoarse && nu > 0 && c->fused && !a.from_zero && (fine0 || (sweep_st_usable(c, l) && c->fold_stored));
+    if (a.ecoarse && !fold) {
+        prolong_add_level_t<VT>(c, l, x, a.ecoarse, np, active);
+        a.ecoarse = nullptr;
     }
     if (nu <= 0) {
-        if (from_zero) hipMemsetAsync(x, 0, bytes, c->stream);
+        if (a.from_zero) hipMemsetAsync(x, 0, bytes, c->stream);
         return x;
     }
     if (!c->fused) {   // reference path: one launch per colour, in place (double vectors only)
-        if (from_zero) hipMemsetAsync(x, 0, bytes, c->stream);
+        if (a.from_zero) hipMemsetAsync(x, 0, bytes, c->stream);
         for (int s = 0; s < nu; ++s)
             for (int k = 0; k < 4; ++k)
-                gs_colour(c, l, (double*)x, (const double*)b, reverse ? 3 - k : k, np, active);
+                gs_colour(c, l, (double*)x, (const double*)b, a.reverse ? 3 - k : k, np, active);
         return x;
     }
-    // out-of-place fused sweeps: choose the first destination so that the last pass writes into x.  On level 0 a pass of
-    // k_sweep0m performs two sweeps (temporal blocking): nu sweeps = ceil(nu / 2) passes over the data.
-    const bool two = l == 0 && (std::is_same<VT, double>::value ? sweep0m_usable(c) : sweep0p_usable(c));
+    // out-of-place fused sweeps: choose the first destination so that the last pass writes into x.  On level 0 a pass may
+    // perform two sweeps (temporal blocking): nu sweeps = ceil(nu / 2) passes over the data.
+    L0Req two_rq;
+    two_rq.nsweeps = 2;
+    const bool two = fine0 && plan_l0_pass<VT>(c, two_rq).NS == 2;
     const int npass = two ? (nu + 1) / 2 : nu;
-    const VT* src = from_zero ? nullptr : x;
-    VT* dst = (from_zero && (npass % 2 == 1)) ? x : tmp;
+    const VT* src = a.from_zero ? nullptr : x;
+    VT* dst = (a.from_zero && (npass % 2 == 1)) ? x : tmp;
     int left = nu;
-    for (int s = 0; s < npass; ++s) {
-        const int ns = two ? std::min(2, left) : 1;
-        // the cycle's very last pass also delivers the Krylov product of its result, if one was requested
-        const bool trail = final_smooth && s == npass - 1 && c->trail_set && l == 0 &&
-                           std::is_same<VT, double>::value && sweep0m_usable(c) && src != nullptr;
-        sweep_level_t<VT>(c, l, src, dst, b, reverse, np, active, s == 0 ? ecoarse : (const VT*)nullptr, ns, trail, ec32,
-                          out64 && s == npass - 1, skip0 && s == 0);
-        left -= ns;
+    for (int s = 0; s < npass && !io.failed; ++s) {
+        const bool first = s == 0, last = s == npass - 1;
+        SmoothArgs<VT> pa = a;
+        pa.nsweeps = two ? std::min(2, left) : 1;
+        pa.trail = a.final_smooth && last && l == 0;
+        if (!first) { pa.ecoarse = nullptr; pa.skip0 = false; }
+        if (!last) { pa.out64 = false; pa.rr_out = nullptr; }
+        sweep_level_t<VT>(c, l, src, dst, b, np, active, pa, io);
+        left -= pa.nsweeps;
         src = dst;
         dst = (dst == x) ? tmp : x;
     }
     if (src != x) {
-        if (allow_swap) return tmp;
+        if (a.allow_swap) return tmp;
         hipMemcpyAsync(x, src, bytes, hipMemcpyDeviceToDevice, c->stream);
     }
     return x;
@@ -917,30 +1073,15 @@ void tail_cycle_t(vof_ctx* c, VT* x, const VT* b, int np, const int* active, boo
     CDISPATCH(c, l0, (k_tail_cycle<CT, VT><<<np, TAIL_THREADS, c->tail_lds, c->stream>>>(A, b, x, from_zero ? 1 : 0, active)));
 }
 
-// vcycle_precision 3 applies when level 0 runs the kernels in which the two storage types meet: k_stream_resrestrict0 (float64
-// in, float32 out) and k_sweep0m with the interpolated correction (float32 in); anything else keeps float64 everywhere
-inline bool coarse32_ok(const vof_ctx* c, int nu_post) {
-    return c->vcoarse32 && c->L.size() > 1 && sweep0m_usable(c) && nu_post > 0;
-}
-
-// ... and its level-0 hand-off vectors - the pre-smoothed iterate x and the cycle's result y / z - are stored as float32 (h32)
-// when every level-0 pass of the cycle is a k_sweep0r pass that can store them: the two-sweep pass from zero with the residual +
-// restriction stage (nu_pre 2) and the two-sweep post-smoothing pass that interpolates the correction (nu_post 2)
-inline bool handoff32_ok(const vof_ctx* c) {
-    const vof_params& P = c->prm;
-    return c->l0_handoff && P.nu_pre == 2 && P.nu_post == 2 && coarse32_ok(c, P.nu_post) && c->fuse_rr &&
-           VOF_S0R_BCARRY && s0_geometry(c, c->L[0].ni, 2, true).s0r && s0_geometry(c, c->L[0].ni + 1, 2, true).s0r &&
-           s0_geometry(c, c->L[0].ni + 1, 2, false).s0r;
-}
-
 // One multigrid cycle on level l for A_l x = b, starting from a zero guess (from_zero) or from the contents of x.
 // (x, tmp) are the level's ping-pong buffers.  Returns the buffer holding the result: `x`, or - on the levels >= 1,
 // where the caller only reads it - `tmp`.  With prm.w_cycle_level == l the next coarser level is visited twice
 // (the second visit continues from the first one's result): a W-cycle restricted to one level.
 template <typename VT>
 // after_post: x holds the result of a previous visit of this level with the same b, i.e. of its reverse post-smoothing sweep
-VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* active, bool from_zero = true,
-             bool after_post = false) {
+// emit64 (level 1 under a float64 level 0, vcycle_precision 3): the last post-smoothing sweep writes the result as float64
+VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* active, CycleIO& io, bool from_zero = true,
+             bool after_post = false, bool emit64 = false) {
     int last = (int)c->L.size() - 1;
     if (l == last) { coarse_solve_t<VT>(c, b, x, np, active); return x; }
     if (l == c->tail_first && l > 0 && tail_prepare(c)) { tail_cycle_t<VT>(c, x, b, np, active, from_zero); return x; }
@@ -952,27 +1093,19 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
     // the ping-pong partner (the caller only reads the buffer this function returns), so the two just trade names - and the
     // partner then still holds the input of the last sweep, which is all k_resrestrict_u needs besides the result.
     const bool resu = l > 0 && lv.C != nullptr && c->fused && nu1 >= 1;
-    bool rr_fused = false;   // level 0: the coarse right-hand side came out of the pre-smoothing pass (k_sweep0r, TRAIL = 2)
-    if constexpr (std::is_same<VT, double>::value) {
-        if (l == 0 && c->fuse_rr && from_zero && nu1 == 2 && sweep0m_usable(c)) {
-            c->rr_f32 = coarse32_ok(c, nu2);
-            c->rr_out = nx.b;
-            c->rr_done = false;
-        }
+    SmoothArgs<VT> pre;
+    pre.from_zero = from_zero;
+    if (l == 0) {   // the coarse right-hand side is wanted from the last pre-smoothing pass (plan_l0_pass says whether it can)
+        pre.rr_out = nx.b;
+        pre.rr_f32 = coarse32_ok(c, nu2);
+        io.rr_done = false;
+    } else if (c->fused) {
+        pre.allow_swap = true;
+        pre.skip0 = after_post && !from_zero && nu2 >= 1;
     }
-    if (l > 0 && c->fused) {
-        VT* xr = smooth_level_t<VT>(c, l, x, tmp, b, nu1, from_zero, false, np, active, nullptr, /*allow_swap=*/true, false, false, false,
-                                    /*skip0=*/after_post && !from_zero && nu2 >= 1);
-        if (xr != x) std::swap(x, tmp);
-    } else {
-        smooth_level_t<VT>(c, l, x, tmp, b, nu1, from_zero, false, np, active);
-    }
-    if (l == 0 && c->rr_out) { rr_fused = c->rr_done; c->rr_out = nullptr; c->rr_done = false; }
-    if (l == 0 && c->h32 && !(rr_fused && coarse32_ok(c, nu2))) {
-        c->err = "float32 level-0 hand-off: the pre-smoothing pass did not form the coarse right-hand side";
-        c->h32_bad = true;
-        return x;
-    }
+    if (smooth_level_t<VT>(c, l, x, tmp, b, nu1, np, active, pre, io) != x) std::swap(x, tmp);
+    if (io.failed) return x;
+    const bool rr_fused = l == 0 && io.rr_done;   // ... and it did (k_sweep0r, TRAIL = 2)
     if constexpr (std::is_same<VT, double>::value) {
         if (l == 0 && coarse32_ok(c, nu2)) {
             // float64 vectors on level 0, float32 below: the fused residual + restriction writes the coarse right-hand side as
@@ -987,16 +1120,16 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
             const int nu2c = c->prm.nu_post_coarse > 0 ? c->prm.nu_post_coarse : c->prm.nu_post;
             const bool can64 = 1 < last && !(c->tail_first == 1 && tail_prepare(c)) && sweep_st_usable(c, 1) && nu2c > 0;
             const int visits = (c->prm.w_cycle_level == 0 && 1 < last) ? (c->prm.w_cycle_visits > 0 ? c->prm.w_cycle_visits : 2) : 1;
-            c->emit64 = can64 && visits == 1;
-            float* fe = vcycle_t<float>(c, 1, fx, ft, (const float*)nx.b, np, active, true);
+            float* fe = vcycle_t<float>(c, 1, fx, ft, (const float*)nx.b, np, active, io, true, false, /*emit64=*/can64 && visits == 1);
             for (int v = 1; v < visits; ++v) {
                 float* other = (fe == fx) ? ft : fx;
-                c->emit64 = can64 && v == visits - 1;
-                fe = vcycle_t<float>(c, 1, fe, other, (const float*)nx.b, np, active, false);
+                fe = vcycle_t<float>(c, 1, fe, other, (const float*)nx.b, np, active, io, false, false, /*emit64=*/can64 && v == visits - 1);
             }
-            c->emit64 = false;
-            return smooth_level_t<double>(c, 0, x, tmp, b, nu2, false, true, np, active, (const double*)fe, /*allow_swap=*/true,
-                                          /*final_smooth=*/true, /*ec32=*/!can64);
+            SmoothArgs<double> post;
+            post.reverse = post.allow_swap = post.final_smooth = true;
+            post.ecoarse = (const double*)fe;
+            post.ec32 = !can64;
+            return smooth_level_t<double>(c, 0, x, tmp, b, nu2, np, active, post, io);
         }
     }
     if (resu) {
@@ -1010,31 +1143,33 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* 
     }
     VT* cx = (VT*)nx.x;
     VT* ct = (VT*)nx.x2;
-    VT* ec = vcycle_t<VT>(c, l + 1, cx, ct, (const VT*)nx.b, np, active, true);
+    VT* ec = vcycle_t<VT>(c, l + 1, cx, ct, (const VT*)nx.b, np, active, io, true);
     if (c->prm.w_cycle_level == l && l + 1 < last) {
         const int visits = c->prm.w_cycle_visits > 0 ? c->prm.w_cycle_visits : 2;
         for (int v = 1; v < visits; ++v) {
             VT* other = (ec == cx) ? ct : cx;
-            ec = vcycle_t<VT>(c, l + 1, ec, other, (const VT*)nx.b, np, active, false, /*after_post=*/true);
+            ec = vcycle_t<VT>(c, l + 1, ec, other, (const VT*)nx.b, np, active, io, false, /*after_post=*/true);
         }
     }
-    // (level 1 under a float64 level 0, vcycle_precision 3: the last post-smoothing sweep writes the result as float64)
-    const bool out64 = c->emit64 && l == 1 && std::is_same<VT, float>::value && nu2 > 0;
-    return smooth_level_t<VT>(c, l, x, tmp, b, nu2, false, true, np, active, ec, /*allow_swap=*/true, /*final_smooth=*/l == 0,
-                              /*ec32=*/false, out64);
+    SmoothArgs<VT> post;
+    post.reverse = post.allow_swap = true;
+    post.final_smooth = l == 0;
+    post.ecoarse = ec;
+    post.out64 = emit64 && l == 1 && std::is_same<VT, float>::value && nu2 > 0;
+    return smooth_level_t<VT>(c, l, x, tmp, b, nu2, np, active, post, io);
 }
 
 template <typename VT> int direct_apply_t(vof_ctx* c, VT* z, const VT* r, int np);   // direct preconditioner, below
 
 // One cycle M b -> *xslot (c->ky or c->kz).  The out-of-place sweeps may leave the result in the level-0 ping-pong partner
 // instead (an odd number of passes); the two buffers then trade places - a pointer swap instead of a copy of the vector.
-void vcycle(vof_ctx* c, double** xslot, const void* b, int np, const int* active) {
+void vcycle(vof_ctx* c, double** xslot, const void* b, int np, const int* active, CycleIO& io) {
     if (c->direct_on) {   // the direct preconditioner takes the place of the cycle (every pair of the batch, active or not)
         VDISPATCH(c, direct_apply_t<VT>(c, (VT*)*xslot, (const VT*)b, np));
         return;
     }
     void* res = nullptr;
-    VDISPATCH(c, res = (void*)vcycle_t<VT>(c, 0, (VT*)*xslot, (VT*)c->L[0].x2, (const VT*)b, np, active));
+    VDISPATCH(c, res = (void*)vcycle_t<VT>(c, 0, (VT*)*xslot, (VT*)c->L[0].x2, (const VT*)b, np, active, io));
     if (res != (void*)*xslot) {
         c->L[0].x2 = (void*)*xslot;
         *xslot = (double*)res;
@@ -1220,7 +1355,9 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
         int jdone = 0;
         for (int j = 0; j < m; ++j) {
             const int* act = c->active;
-            vcycle(c, &c->ky, V + (size_t)j * vstride, np, act);             // z = M v_j
+            CycleIO io;
+            vcycle(c, &c->ky, V + (size_t)j * vstride, np, act, io);         // z = M v_j
+            if (io.failed) return -1;
             krylov_apply(c, c->ky, w, np, act);                              // w = A z
             for (int pass = 0; pass < 2; ++pass) {                           // classical Gram-Schmidt, twice
                 for (int i0 = 0; i0 <= j; i0 += GM_NV) {
@@ -1255,7 +1392,9 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
             k_gm_axpy<<<rg, RBLK, 0, s>>>(V + (size_t)i0 * vstride, vstride, i0, cnt, c->gm_state, coef_y, 1.0,
                                           i0 ? c->kp : nullptr, c->kp, len, c->gm_cycle, 1, nullptr);
         }
-        vcycle(c, &c->ky, c->kp, np, c->gm_cycle);
+        CycleIO io;
+        vcycle(c, &c->ky, c->kp, np, c->gm_cycle, io);
+        if (io.failed) return -1;
         { Prof p(c, VOF_K_VECTOR, 0, 24.0 * len); k_gm_xpy<<<rg, RBLK, 0, s>>>(c->kx, c->ky, len, c->gm_cycle); }
         HIPCHK(hipGetLastError());
     }
@@ -1403,7 +1542,7 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
     // precision after 8 iterations, GMRES fallback)
     c->vfloat = (P.vcycle_precision == 1 || P.vcycle_precision == 2) && c->fused && c->L.size() > 1 && !c->direct_on;
     c->vcoarse32 = P.vcycle_precision == 3 && !c->direct_on;
-    c->h32 = c->h32_bad = false;
+    c->h32 = false;
     if (c->direct_on) {   // direct preconditioner: block-tridiagonal LU instead of the Galerkin hierarchy
         if (np > c->dir_cap) { c->err = "batch larger than the direct preconditioner's buffers"; return -1; }
         c->frames = frames_dev;
@@ -1476,13 +1615,21 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
         // needs a float32 copy of its right-hand side) and no p is written - the next iteration finds that p in r^ = r0.
         const bool on_r = it == 0 && !c->vfloat;
         const bool fold_b = fold_b_usable(c);
+        // a cycle's requests were met or the iteration ends here (the folded update is only requested where fold_b_usable holds)
+        auto cycle_ok = [c](const CycleIO& io, const char* which) {
+            if (io.failed) c->h32 = false;
+            else if (io.bf_mode && !io.bf_done) c->err = std::string("folded vector update (") + which + "): not consumed by the cycle";
+            else return true;
+            return false;
+        };
+        CycleIO io_p, io_s;
         if (on_r) vrhs_p = (void*)c->kr;
         else if (fold_b && it > 0) {
             // folded into the cycle's first pass (k_sweep0r, BF = 2).  The new p goes to the buffer of t, which is dead here,
             // and the two trade names (the bands of the pass overlap: no update in place)
             const double* p_old = (it == 1 && ran_on_r) ? rh : c->kp;
-            c->bf = S0BSrc{c->kr, c->kv, p_old, c->kt, c->sc, nullptr};
-            c->bf_mode = 2;
+            io_p.bf = S0BSrc{c->kr, c->kv, p_old, c->kt, c->sc, nullptr};
+            io_p.bf_mode = 2;
             std::swap(c->kp, c->kt);
             vrhs_p = (void*)c->kp;
         } else {
@@ -1493,20 +1640,17 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
         }
         if (it == 0) ran_on_r = on_r;
         // y = M p and v = A y with (r^, v): the product comes out of the cycle's last smoothing pass when that path applies
-        c->trail_req = S0Trail{c->kv, rh, 0, c->partials};
-        c->trail_set = true; c->trail_done = false;
-        vcycle(c, &c->ky, vrhs_p, np, act);
-        c->trail_set = false;
-        if (c->bf_mode) { if (c->err.empty()) c->err = "folded vector update (p): not consumed by the cycle"; c->bf_mode = 0; return -1; }
-        if (c->h32_bad) { c->h32_bad = c->h32 = false; return -1; }
-        int nb1 = c->trail_done ? c->trail_nblk : krylov_apply(c, c->ky, c->kv, np, act, rh, 0);
+        io_p.trail = S0Trail{c->kv, rh, 0, c->partials};
+        vcycle(c, &c->ky, vrhs_p, np, act, io_p);
+        if (!cycle_ok(io_p, "p")) return -1;
+        int nb1 = io_p.trail_nblk ? io_p.trail_nblk : krylov_apply(c, c->ky, c->kv, np, act, rh, 0);
         if (!nb1) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(rh, c->kv, nullptr, nullptr, len, c->partials, act); nb1 = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_ALPHA><<<np, 64, 0, s>>>(c->sc, c->partials, nb1, c->active, P.rtol, P.max_iterations); }
         if (fold_b) {
             // s = r - alpha v, (s, s), the half-step test and its x += alpha y: in / right after the first pass of the cycle on s
             // (k_sweep0r, BF = 1).  s goes to the buffer of t (dead until the end of this cycle); r's buffer becomes t's
-            c->bf = S0BSrc{c->kr, c->kv, nullptr, c->kt, c->sc, c->partials};
-            c->bf_mode = 1;
+            io_s.bf = S0BSrc{c->kr, c->kv, nullptr, c->kt, c->sc, c->partials};
+            io_s.bf_mode = 1;
             std::swap(c->kr, c->kt);
             vrhs_s = (void*)c->kr;
         } else {
@@ -1518,13 +1662,10 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
           k_clear_half<<<(np + 255) / 256, 256, 0, s>>>(c->sc, np); }
         }
         // z = M s and t = A z with (t, s) and (t, t)
-        c->trail_req = S0Trail{c->kt, c->kr, 1, c->partials};
-        c->trail_set = true; c->trail_done = false;
-        vcycle(c, &c->kz, vrhs_s, np, act);
-        c->trail_set = false;
-        if (c->bf_mode) { if (c->err.empty()) c->err = "folded vector update (s): not consumed by the cycle"; c->bf_mode = 0; return -1; }
-        if (c->h32_bad) { c->h32_bad = c->h32 = false; return -1; }
-        int nb2 = c->trail_done ? c->trail_nblk : krylov_apply(c, c->kz, c->kt, np, act, c->kr, 1);
+        io_s.trail = S0Trail{c->kt, c->kr, 1, c->partials};
+        vcycle(c, &c->kz, vrhs_s, np, act, io_s);
+        if (!cycle_ok(io_s, "s")) return -1;
+        int nb2 = io_s.trail_nblk ? io_s.trail_nblk : krylov_apply(c, c->kz, c->kt, np, act, c->kr, 1);
         if (!nb2) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kt, c->kr, c->kt, c->kt, len, c->partials, act); nb2 = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_OMEGA><<<np, 64, 0, s>>>(c->sc, c->partials, nb2, c->active, P.rtol, P.max_iterations); }
         { Prof p(c, VOF_K_VECTOR, 0, 8.0 * len * 6 + 2.0 * vsz * len);   // x += alpha y + omega z; r = s - omega t; (r,r), (r^,r)
@@ -2810,13 +2951,19 @@ int vof_bench_sweeps_dev(vof_ctx* c, const double* movie, int n_pairs, const vof
         k_rhs<<<grid2d(f.ni, f.nj, n_pairs), blk2d, 0, c->stream>>>(movie, frame_stride(c), c->Nj, f.ni, f.nj, c->kb, nullptr);
     }
     HIPCHK(hipMemsetAsync(c->kx, 0, (size_t)n_pairs * 3 * f.npts * sizeof(double), c->stream));
+    CycleIO io;
     if (c->vfloat) {
         size_t n = (size_t)n_pairs * 3 * f.npts;
         k_convert<double, float><<<1024, 256, 0, c->stream>>>(c->kb, (float*)c->b32, n);
-        smooth_level_t<float>(c, 0, (float*)c->ky, (float*)f.x2, (const float*)c->b32, n_sweeps, true, false, n_pairs, nullptr);
+        SmoothArgs<float> a;
+        a.from_zero = true;
+        smooth_level_t<float>(c, 0, (float*)c->ky, (float*)f.x2, (const float*)c->b32, n_sweeps, n_pairs, nullptr, a, io);
     } else {
-        smooth_level_t<double>(c, 0, c->kx, (double*)f.x2, c->kb, n_sweeps, true, false, n_pairs, nullptr);
+        SmoothArgs<double> a;
+        a.from_zero = true;
+        smooth_level_t<double>(c, 0, c->kx, (double*)f.x2, c->kb, n_sweeps, n_pairs, nullptr, a, io);
     }
+    if (io.failed) return -1;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -3021,9 +3168,13 @@ int vof_debug_sweep(vof_ctx* c, int level, double* x_host, const double* b_host,
     size_t n = nbytes / sizeof(double);
     if (int rc = dbg_up(c, c->kp, x_host, n)) return rc;
     if (int rc = dbg_up(c, c->kv, b_host, n)) return rc;
-    VDISPATCH(c, sweep_level_t<VT>(c, level, from_zero ? (const VT*)nullptr : (const VT*)c->kp, (VT*)c->kt,
-                                   (const VT*)c->kv, reverse != 0, c->npairs, nullptr));
-    return dbg_down(c, x_host, c->kt, n);
+    CycleIO io;
+    VDISPATCH(c, {
+        SmoothArgs<VT> a;
+        a.reverse = reverse != 0;
+        sweep_level_t<VT>(c, level, from_zero ? (const VT*)nullptr : (const VT*)c->kp, (VT*)c->kt, (const VT*)c->kv, c->npairs, nullptr, a, io);
+    });
+    return io.failed ? -1 : dbg_down(c, x_host, c->kt, n);
 }
 
 int vof_debug_smooth(vof_ctx* c, int level, double* x_host, const double* b_host, int nu, int reverse, int from_zero) {
@@ -3033,8 +3184,14 @@ int vof_debug_smooth(vof_ctx* c, int level, double* x_host, const double* b_host
     size_t n = nbytes / sizeof(double);
     if (int rc = dbg_up(c, c->kp, x_host, n)) return rc;
     if (int rc = dbg_up(c, c->kv, b_host, n)) return rc;
-    VDISPATCH(c, smooth_level_t<VT>(c, level, (VT*)c->kp, (VT*)c->kt, (const VT*)c->kv, nu, from_zero != 0, reverse != 0, c->npairs, nullptr));
-    return dbg_down(c, x_host, c->kp, n);
+    CycleIO io;
+    VDISPATCH(c, {
+        SmoothArgs<VT> a;
+        a.from_zero = from_zero != 0;
+        a.reverse = reverse != 0;
+        smooth_level_t<VT>(c, level, (VT*)c->kp, (VT*)c->kt, (const VT*)c->kv, nu, c->npairs, nullptr, a, io);
+    });
+    return io.failed ? -1 : dbg_down(c, x_host, c->kp, n);
 }
 
 int vof_set_fused_sweeps(vof_ctx* c, int on) {
@@ -3139,9 +3296,10 @@ int vof_debug_vcycle(vof_ctx* c, const double* r_host, double* e_host) {
     size_t n = nbytes / sizeof(double);
     if (int rc = dbg_up(c, c->kp, r_host, n)) return rc;
     c->h32 = handoff32_ok(c);   // the cycle as the BiCGStab loop's first iterations run it
-    vcycle(c, &c->ky, c->kp, c->npairs, nullptr);
-    const int rc = c->h32_bad ? -1 : dbg_down(c, e_host, c->ky, n);
-    c->h32 = c->h32_bad = false;
+    CycleIO io;
+    vcycle(c, &c->ky, c->kp, c->npairs, nullptr, io);
+    const int rc = io.failed ? -1 : dbg_down(c, e_host, c->ky, n);
+    c->h32 = false;
     return rc;
 }
 
@@ -3154,14 +3312,13 @@ int vof_debug_vcycle_apply(vof_ctx* c, const double* r_host, double* y_host, dou
     const int np = c->npairs;
     c->cur_units = np;
     HIPCHK(hipMemcpyAsync(c->krh, r_host, nbytes, hipMemcpyHostToDevice, c->stream));   // dot partner (float64)
-    c->trail_req = S0Trail{c->kv, c->krh, 1, c->partials};
-    c->trail_set = true; c->trail_done = false;
+    CycleIO io;
+    io.trail = S0Trail{c->kv, c->krh, 1, c->partials};
     c->h32 = handoff32_ok(c);
-    vcycle(c, &c->ky, c->kp, np, nullptr);
-    c->trail_set = false;
-    if (c->h32_bad) { c->h32 = c->h32_bad = false; return -1; }
-    int nb = c->trail_done ? c->trail_nblk : krylov_apply(c, c->ky, c->kv, np, nullptr, c->krh, 1);
-    if (fused) *fused = c->trail_done ? 1 : 0;
+    vcycle(c, &c->ky, c->kp, np, nullptr, io);
+    if (io.failed) { c->h32 = false; return -1; }
+    int nb = io.trail_nblk ? io.trail_nblk : krylov_apply(c, c->ky, c->kv, np, nullptr, c->krh, 1);
+    if (fused) *fused = io.trail_nblk ? 1 : 0;
     if (!nb) { c->h32 = false; c->err = "the operator kernel did not fuse the dot products"; return -1; }
     std::vector<double> part((size_t)np * 3 * nb);
     HIPCHK(hipMemcpyAsync(part.data(), c->partials, part.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));

@@ -1792,18 +1792,12 @@ __global__ void k_subsample(const double* __restrict__ field, int Ni, int Nj, in
 constexpr int SW_HALO = 4;    // halo columns each side
 constexpr int SW_RING = 12;   // rows in the LDS ring
 
-// Two strip geometries:
-//  GeoA: 4 waves, 128 columns in LDS, 120 owned; every colour wave also recomputes the halo columns it needs
-//        (column ranges shrink by one per colour).  Best for level 0 (no coefficient planes, 3 blocks/CU).
+// The strip geometry of the stored levels (the matrix-free level 0 has kernels of its own, k_sweep0*, with 120 owned columns
+// of 128 in LDS):
 //  GeoB: 128 owned columns, 128-column aligned, so the coefficient rows of the colour-split stencil planes are
-//        read in whole aligned cache lines; a 5th wave recomputes the six halo points.  For the stored levels.
-struct GeoA {
-    static constexpr int OUT = 120, W = 128, IW = 132, THREADS = 256;
-    static constexpr bool HALO_WAVE = false;
-};
+//        read in whole aligned cache lines; four colour waves, and a 5th wave that recomputes the six halo points.
 struct GeoB {
     static constexpr int OUT = 128, W = 136, IW = 140, THREADS = 320;
-    static constexpr bool HALO_WAVE = true;
 };
 template <class G> __device__ __forceinline__ int sw_cs(int lc) { return (lc & 1) * (G::W / 2) + (lc >> 1); }
 template <class G> __device__ __forceinline__ int sw_ci(int lci) { return (lci & 1) * (G::IW / 2) + (lci >> 1); }
@@ -1839,8 +1833,7 @@ struct SweepStored {
     typedef typename CoefFmt<CT>::word_t word_t;
     const word_t* C;  // [pair][PLANES][colour-split plane]
     size_t plane;     // CLay(ni, nj).plane
-    static constexpr bool kHasImage = false;
-    // dummies so the kernel template compiles for both policies
+    // unused; kept because the policy is a kernel argument passed by value: dropping them would move every argument of k_sweep
     const double* frames = nullptr;
     size_t frame_stride = 0;
     int Nj = 0;
@@ -1870,9 +1863,8 @@ struct SweepStored {
     }
 
     template <class G, typename VT>
-    __device__ __forceinline__ void update(const SweepCols& cc, const SweepRows& rw, const VT* xs,
-                                           const double* /*im*/, int pair, const cset_t& cfp, double b0, double b1,
-                                           double b2, double& u, double& w, double& gm) const {
+    __device__ __forceinline__ void update(const SweepCols& cc, const SweepRows& rw, const VT* xs, int pair, const cset_t& cfp,
+                                           double b0, double b1, double b2, double& u, double& w, double& gm) const {
         constexpr int W = G::W;
         cset_t cl;
         if (!kPrefetch) cl.load(C + (size_t)pair * CoefFmt<CT>::PLANES * plane + rw.cp + cc.cq, plane);
@@ -1931,15 +1923,10 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
                                                const VT* __restrict__ x_in, VT* __restrict__ x_out,
                                                const VT* __restrict__ b, const int* __restrict__ active,
                                                const VT* __restrict__ ecoarse, int nci, int ncj) {
-    // ecoarse != nullptr (GeoA only): the sweep starts from x_in + P ecoarse.  The coarse rows are streamed through
-    // a 3-row LDS ring (one new coarse row per step, prefetched a step ahead) and interpolated while the fine rows
-    // are loaded, so the separate prolongation pass over x (read + write of x) disappears.
-    constexpr int W = G::W, IW = G::IW, OUT = G::OUT, THREADS = G::THREADS;
+    // (ecoarse, nci, ncj are not read: on these levels the correction is added by k_prolong_add before the sweep)
+    constexpr int W = G::W, OUT = G::OUT, THREADS = G::THREADS;
     extern __shared__ double sw_lds[];
     VT* xs = reinterpret_cast<VT*>(sw_lds);                                                     // [SW_RING][3][W]
-    double* im = reinterpret_cast<double*>(reinterpret_cast<char*>(sw_lds) + SW_RING * 3 * W * sizeof(VT));  // [SW_RING][IW]
-    constexpr int CRW = W / 2 + 2;                                                              // coarse ring width
-    VT* cr = reinterpret_cast<VT*>(im + (Pol::kHasImage ? SW_RING * IW : 0));                   // [3][3][CRW] (if ecoarse)
     const unsigned nblocks = (unsigned)nx * ny * nz;
     unsigned lb = blockIdx.x;
     if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // bijective when nblocks % 8 == 0
@@ -1951,41 +1938,25 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
     SweepGeom g;
     g.ni = ni; g.nj = nj; g.TI = TI;
     g.p0 = by * TI - po;
-    // GeoB: strips always 128-aligned, po only swaps the column parity of the stages.  GeoA: strip origin shifted by po.
-    const int q0 = G::HALO_WAVE ? bx * OUT : bx * OUT - po;
-    g.qs = q0 - SW_HALO;
+    // strips are always 128-aligned, po only swaps the column parity of the stages
+    g.qs = bx * OUT - SW_HALO;
     const size_t npts = (size_t)ni * nj, off = (size_t)pair * 3 * npts;
     const VT* xin = x_in ? x_in + off : nullptr;
     VT* xout = x_out + off;
     const VT* bp = b + off;
-    const size_t ncpts = (size_t)nci * ncj;
-    const VT* ec = (ecoarse && !G::HALO_WAVE) ? ecoarse + (size_t)pair * 3 * ncpts : nullptr;
-    const double* img = nullptr;
-    if constexpr (Pol::kHasImage) {
-        int fidx = pair;
-        if (pol.pp) { pol.alpha = pol.pp[pair].alpha; pol.beta = pol.pp[pair].beta; fidx = pol.pp[pair].frame; }
-        img = pol.frames + (size_t)fidx * pol.frame_stride;
-    }
     const CLay L(ni, nj);
 
-    // ---- stage of this lane.  Waves 0-3: colour = wave.  GeoB: wave 4 recomputes the six halo points.
-    int stage = wave, lc;
+    // ---- stage of this lane.  Waves 0-3: colour = wave.  Wave 4 recomputes the six halo points.
+    // column parity of stage c is (c & 1) ^ po; for po = 1 the halo pattern is the mirror image
+    int stage = wave, lc = SW_HALO + 2 * lane + ((wave & 1) ^ po);
     bool lane_on = true;
-    if (G::HALO_WAVE) {
-        // column parity of stage c is (c & 1) ^ po; for po = 1 the halo pattern is the mirror image
-        lc = SW_HALO + 2 * lane + ((wave & 1) ^ po);
-        if (wave == 4) {
-            const int hs[6] = {0, 0, 0, 1, 1, 2};
-            const int hl[6] = {2, SW_HALO + OUT, SW_HALO + OUT + 2, 3, SW_HALO + OUT + 1, SW_HALO + OUT};
-            lane_on = lane < 6;
-            stage = hs[lane_on ? lane : 0];
-            lc = hl[lane_on ? lane : 0];
-            if (po) lc = W - 1 - lc;
-        }
-    } else {
-        // every colour wave covers its whole parity class of the strip; valid ranges 2..126, 3..125, 4..124, 5..123
-        lc = 2 * lane + (wave & 1);
-        lane_on = (lc >= 2 + wave) && (lc <= W - 2 - wave);
+    if (wave == 4) {
+        const int hs[6] = {0, 0, 0, 1, 1, 2};
+        const int hl[6] = {2, SW_HALO + OUT, SW_HALO + OUT + 2, 3, SW_HALO + OUT + 1, SW_HALO + OUT};
+        lane_on = lane < 6;
+        stage = hs[lane_on ? lane : 0];
+        lc = hl[lane_on ? lane : 0];
+        if (po) lc = W - 1 - lc;
     }
     const int q = g.qs + lc;
     const bool col_ok = lane_on && (q >= 0) && (q < nj);
@@ -2005,77 +1976,24 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
     }
     const size_t bcol = col_ok ? (size_t)q : 0;
 
-    // ---- cooperative load-in / write-out of 2 rows x 3 fields x W columns per step.
-    // GeoA (W = 128, 256 threads): waves {0,1} own row A, waves {2,3} row B, a thread owns one column and the
-    // three fields -> the row is wave-uniform (scalar predicates / offsets), the fields are unrolled.
-    // GeoB (W = 136, 320 threads): generic element mapping.
-    constexpr bool ROWMAP = !G::HALO_WAVE;
-    const int crow = wave >> 1;
-    const int ccol = tid & 127;
-    const int cq = g.qs + ccol;
-    const bool ccv = ROWMAP && cq >= 0 && cq < nj;
-    const bool cown = ccv && ccol >= SW_HALO && ccol < SW_HALO + OUT;
-    const int clds = sw_cs<G>(ccol);
-    const size_t cqg = ccv ? (size_t)cq : 0;
-    const int fc0 = g.qs + ccol, fc1 = g.qs + 128 + ccol;     // full-image columns of image-ring columns ccol, 128 + ccol
-    const bool iv0 = fc0 >= 0 && fc0 <= nj + 1, iv1 = ccol < 2 && fc1 >= 0 && fc1 <= nj + 1;
-    const int ilds0 = sw_ci<G>(ccol), ilds1 = sw_ci<G>(ccol < 2 ? 128 + ccol : 0);
-    // coarse-correction ring: thread <-> (field, coarse column) of the row being prefetched; fine column q of
-    // this thread interpolates from coarse columns (q >> 1) and (q >> 1) + 1
-    const int cqs = g.qs >> 1;                                  // coarse column of ring column 0 (floor)
-    const int crf = tid / CRW, crc = tid % CRW;
-    const bool cr_on = ec && tid < 3 * CRW;
-    const int crq = cqs + crc;
-    const bool cr_cv = cr_on && crq >= 0 && crq < ncj;
-    const int ilcq = (int)(cqg >> 1) - cqs;                     // ring column of (q >> 1)
-    const bool ipj = ccv && (cq & 1) && ((cq >> 1) + 1 < ncj);
-    auto cr_slot = [](int k) { return ((k % 3) + 3) % 3; };
-    if (ec) {   // prologue: the two coarse rows the first load-in step needs
-        const int k0 = (g.p0 - 2) >> 1;
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            const int k = k0 + d;
-            VT v = (VT)0;
-            if (cr_cv && k >= 0 && k < nci) v = ec[(size_t)crf * ncpts + (size_t)k * ncj + crq];
-            if (cr_on) cr[(cr_slot(k) * 3 + crf) * CRW + crc] = v;
-        }
-        __syncthreads();
-    }
+    // ---- cooperative load-in / write-out of 2 rows x 3 fields x W columns per step (W = 136, 320 threads): generic
+    // element mapping, up to three elements per thread
     int m_lds[3], m_rs[3];
     size_t m_g[3];
     bool m_ld[3], m_st[3];
-    constexpr int NIMG = 2 * (W + 2);
-    constexpr int KIMG = (NIMG + THREADS - 1) / THREADS;
-    int i_lds[KIMG], i_rs[KIMG], i_fc[KIMG];
-    bool i_ok[KIMG];
-    if (!ROWMAP) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            int idx = tid + THREADS * k;
-            bool on = idx < 2 * 3 * W;
-            idx = on ? idx : 0;
-            int f = (idx % (3 * W)) / W, mlc = idx % W, qq = g.qs + mlc;
-            bool cv = on && qq >= 0 && qq < nj;
-            m_rs[k] = idx / (3 * W);
-            m_lds[k] = f * W + sw_cs<G>(mlc);
-            m_g[k] = (size_t)f * npts + (size_t)(cv ? qq : 0);
-            m_ld[k] = cv;
-            m_st[k] = cv && mlc >= SW_HALO && mlc < SW_HALO + OUT;
-            if (!on) m_lds[k] = -1;
-        }
-        if (Pol::kHasImage) {
-#pragma unroll
-            for (int k = 0; k < KIMG; ++k) {
-                int idx = tid + THREADS * k;
-                bool on = idx < NIMG;
-                idx = on ? idx : 0;
-                int lci = idx % (W + 2), fc = g.qs + lci;
-                i_rs[k] = idx / (W + 2);
-                i_lds[k] = on ? sw_ci<G>(lci) : -1;
-                i_ok[k] = on && fc >= 0 && fc <= nj + 1;
-                i_fc[k] = i_ok[k] ? fc : 0;
-            }
-        }
+    for (int k = 0; k < 3; ++k) {
+        int idx = tid + THREADS * k;
+        bool on = idx < 2 * 3 * W;
+        idx = on ? idx : 0;
+        int f = (idx % (3 * W)) / W, mlc = idx % W, qq = g.qs + mlc;
+        bool cv = on && qq >= 0 && qq < nj;
+        m_rs[k] = idx / (3 * W);
+        m_lds[k] = f * W + sw_cs<G>(mlc);
+        m_g[k] = (size_t)f * npts + (size_t)(cv ? qq : 0);
+        m_ld[k] = cv;
+        m_st[k] = cv && mlc >= SW_HALO && mlc < SW_HALO + OUT;
+        if (!on) m_lds[k] = -1;
     }
 
     const int stage_row_off = (stage == 0) ? 0 : (stage == 1) ? -2 : (stage == 2) ? -5 : -7;
@@ -2090,94 +2008,33 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
         // the two rows that leave (e-10, e-9) / enter (e+2, e+3) the ring share the slots slotA, slotA + 1
         const int slotB = slotA + 1;
         VT lx[3];
-        double li[KIMG > 2 ? KIMG : 2];
         const bool do_load = (e + 2 <= TI + 1);
-        VT crv = (VT)0;                                   // element of the coarse row prefetched in this step
-        const int knew = ((g.p0 + e + 4) >> 1) + 1;
-        if (ROWMAP) {
-            const int slotR = crow ? slotB : slotA;
-            // (1) write-out of the row that became final: relative row e - 10 + crow
-            {
-                const int rrW = e - 10 + crow, pW = g.p0 + rrW;
-                if (rrW >= 0 && rrW < TI && pW >= 0 && pW < ni && cown) {
-                    VT* orow = xout + (size_t)pW * nj + cqg;
-                    const VT* lrow = xs + slotR * 3 * W + clds;
-                    orow[0] = lrow[0]; orow[npts] = lrow[W]; orow[2 * npts] = lrow[2 * W];
-                }
-            }
-            // (2) global loads of relative row e + 2 + crow into registers
-            const int pL = g.p0 + e + 2 + crow;
-            lx[0] = lx[1] = lx[2] = (VT)0;
-            li[0] = li[1] = 0.0;
-            if (do_load && xin && pL >= 0 && pL < ni && ccv) {
-                const VT* irow = xin + (size_t)pL * nj + cqg;
-                lx[0] = irow[0]; lx[1] = irow[npts]; lx[2] = irow[2 * npts];
-                if (ec) {   // + (P e)(pL, q) from the coarse ring
-                    const int cp = pL >> 1;
-                    const bool ipi = (pL & 1) && (cp + 1 < nci);
-                    const double wi0 = ipi ? 0.5 : 1.0, wj0 = ipj ? 0.5 : 1.0;
-                    const VT* c0 = cr + cr_slot(cp) * 3 * CRW + ilcq;
-                    const VT* c1 = cr + cr_slot(cp + 1) * 3 * CRW + ilcq;
-#pragma unroll
-                    for (int f = 0; f < 3; ++f) {
-                        double v = wi0 * wj0 * (double)c0[f * CRW];
-                        if (ipj) v += wi0 * 0.5 * (double)c0[f * CRW + 1];
-                        if (ipi) {
-                            v += 0.5 * wj0 * (double)c1[f * CRW];
-                            if (ipj) v += 0.25 * (double)c1[f * CRW + 1];
-                        }
-                        lx[f] = (VT)((double)lx[f] + v);
-                    }
-                }
-            }
-            // coarse row needed by the NEXT step: ((p0 + e + 4) >> 1) + 1
-            if (ec && cr_cv && knew >= 0 && knew < nci) crv = ec[(size_t)crf * ncpts + (size_t)knew * ncj + crq];
-            if (Pol::kHasImage) {
-                const int fr = pL + 1;
-                if (do_load && fr >= 0 && fr <= ni + 1) {
-                    const double* frow = img + (size_t)fr * pol.Nj;
-                    if (iv0) li[0] = frow[fc0];
-                    if (iv1) li[1] = frow[fc1];
-                }
-            }
-        } else {
-            // (1) write-out of the rows that became final: relative rows e-10, e-9
-            {
-                const int rrA = e - 10, rrB = e - 9, pA = g.p0 + rrA, pB = g.p0 + rrB;
-                const bool okA = rrA >= 0 && rrA < TI && pA >= 0 && pA < ni;
-                const bool okB = rrB >= 0 && rrB < TI && pB >= 0 && pB < ni;
-                if (okA || okB) {
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const bool rowok = m_rs[k] ? okB : okA;
-                        if (m_st[k] && rowok) {
-                            const int slot = m_rs[k] ? slotB : slotA;
-                            const size_t prow = (size_t)(m_rs[k] ? pB : pA) * nj;
-                            xout[prow + m_g[k]] = xs[slot * 3 * W + m_lds[k]];
-                        }
-                    }
-                }
-            }
-            // (2) global loads of relative rows e+2, e+3 into registers
-            {
-                const int pA = g.p0 + e + 2, pB = pA + 1;
-                const bool okA = do_load && xin && pA >= 0 && pA < ni, okB = do_load && xin && pB >= 0 && pB < ni;
+        // (1) write-out of the rows that became final: relative rows e-10, e-9
+        {
+            const int rrA = e - 10, rrB = e - 9, pA = g.p0 + rrA, pB = g.p0 + rrB;
+            const bool okA = rrA >= 0 && rrA < TI && pA >= 0 && pA < ni;
+            const bool okB = rrB >= 0 && rrB < TI && pB >= 0 && pB < ni;
+            if (okA || okB) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    lx[k] = (VT)0;
                     const bool rowok = m_rs[k] ? okB : okA;
-                    if (m_ld[k] && rowok) lx[k] = xin[(size_t)(m_rs[k] ? pB : pA) * nj + m_g[k]];
-                }
-                if (Pol::kHasImage) {
-                    const int fA = pA + 1, fB = pB + 1;   // full-image rows
-                    const bool iokA = do_load && fA >= 0 && fA <= ni + 1, iokB = do_load && fB >= 0 && fB <= ni + 1;
-#pragma unroll
-                    for (int k = 0; k < KIMG; ++k) {
-                        li[k] = 0.0;
-                        const bool rowok = i_rs[k] ? iokB : iokA;
-                        if (i_ok[k] && rowok) li[k] = img[(size_t)(i_rs[k] ? fB : fA) * pol.Nj + i_fc[k]];
+                    if (m_st[k] && rowok) {
+                        const int slot = m_rs[k] ? slotB : slotA;
+                        const size_t prow = (size_t)(m_rs[k] ? pB : pA) * nj;
+                        xout[prow + m_g[k]] = xs[slot * 3 * W + m_lds[k]];
                     }
                 }
+            }
+        }
+        // (2) global loads of relative rows e+2, e+3 into registers
+        {
+            const int pA = g.p0 + e + 2, pB = pA + 1;
+            const bool okA = do_load && xin && pA >= 0 && pA < ni, okB = do_load && xin && pB >= 0 && pB < ni;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                lx[k] = (VT)0;
+                const bool rowok = m_rs[k] ? okB : okA;
+                if (m_ld[k] && rowok) lx[k] = xin[(size_t)(m_rs[k] ? pB : pA) * nj + m_g[k]];
             }
         }
         // (3) this step's b (prefetched during the previous step) and the prefetch for the next step
@@ -2189,14 +2046,14 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
                 bn0 = (double)brow[bcol]; bn1 = (double)brow[npts + bcol]; bn2 = (double)brow[2 * npts + bcol];
             }
         }
-        // (4) the stage of this wave (row quantities are scalar for the colour waves of GeoA)
+        // (4) the stage of this wave
         {
             const int rr = e + stage_row_off, p = g.p0 + rr;
 #ifndef SW_EXP_NOCOMPUTE   // experiment build: data movement only
             if (col_ok && rr >= rr_lo && rr <= rr_hi && p >= 0 && p < ni) {
                 const SweepRows rw = sweep_rows<G>(g, rr, slotA, stage_row_off, (size_t)L.hj, L.sub);
                 double u, w, gm;
-                pol.template update<G, VT>(cc, rw, xs, im, pair, cf, b0, b1, b2, u, w, gm);
+                pol.template update<G, VT>(cc, rw, xs, pair, cf, b0, b1, b2, u, w, gm);
                 VT* row = xs + rw.pC + cc.cC;
                 row[0] = (VT)u; row[W] = (VT)w; row[2 * W] = (VT)gm;
             }
@@ -2204,25 +2061,9 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
         }
         // (5) loaded rows -> LDS ring (the slots freed by (1), same thread <-> element mapping)
         if (do_load) {
-            if (ROWMAP) {
-                const int slotR = crow ? slotB : slotA;
-                VT* lrow = xs + slotR * 3 * W + clds;
-                lrow[0] = lx[0]; lrow[W] = lx[1]; lrow[2 * W] = lx[2];
-                if (Pol::kHasImage) {
-                    im[slotR * IW + ilds0] = li[0];
-                    if (ccol < 2) im[slotR * IW + ilds1] = li[1];
-                }
-                if (cr_on) cr[(cr_slot(knew) * 3 + crf) * CRW + crc] = crv;
-            } else {
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    if (m_lds[k] >= 0) xs[(m_rs[k] ? slotB : slotA) * 3 * W + m_lds[k]] = lx[k];
-                if (Pol::kHasImage) {
-#pragma unroll
-                    for (int k = 0; k < KIMG; ++k)
-                        if (i_lds[k] >= 0) im[(i_rs[k] ? slotB : slotA) * IW + i_lds[k]] = li[k];
-                }
-            }
+            for (int k = 0; k < 3; ++k)
+                if (m_lds[k] >= 0) xs[(m_rs[k] ? slotB : slotA) * 3 * W + m_lds[k]] = lx[k];
         }
         // (6) coefficient prefetch for the next step's point (stored float stencils)
         if (Pol::kPrefetch) {
@@ -2231,7 +2072,7 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
             if (col_ok && rrn >= rr_lo && rrn <= rr_hi && pn >= 0 && pn < ni)
                 pol.prefetch(cc, (size_t)((pn & 1) << 1) * L.sub + (size_t)(pn >> 1) * L.hj, pair, cf);
 #else
-            if (!G::HALO_WAVE || wave < 4) {   // colour waves: the row is wave-uniform -> scalar row / plane offsets
+            if (wave < 4) {   // colour waves: the row is wave-uniform -> scalar row / plane offsets
                 const int pnu = __builtin_amdgcn_readfirstlane(pn);
                 if (col_ok && rrn >= rr_lo && rrn <= rr_hi && pn >= 0 && pn < ni)
                     pol.prefetch_u((size_t)((pnu & 1) << 1) * L.sub + (size_t)(pnu >> 1) * L.hj, (unsigned)cc.cq, pair, cf);
