@@ -77,14 +77,14 @@ struct vof_ctx {
     bool l0_handoff = true; // VOF_L0_HANDOFF=0: the level-0 hand-off vectors stay float64 in vcycle_precision 3 (see h32)
     bool h32 = false;       // the cycles run now store their level-0 hand-off vectors as float32: the pre-smoothed iterate x and the
                             // cycle's result (y, z).  Set per BiCGStab iteration where handoff32_ok holds, and by vof_debug_vcycle*
-    const PairParam* pp = nullptr;   // per-pair (alpha, beta, frame) overrides of the current batch ("virtual pairs") or nullptr
+    const PairParam* pp = nullptr;   // per-pair (alpha, beta, frame) overrides of the batch in solve_batch ("virtual pairs") or nullptr;
+                                     // written by solve_batch alone (BatchReq), nullptr outside it - the debug entry points rely on that
     PairParam* pp_buf = nullptr;     // device storage for them (B entries, lazy)
-    // warm start (two-phase solve of a stack): interior solutions of the phase-1 pairs, and per pair of the current
-    // batch the index of the saved solution to start from (nullptr: constant initial fields)
+    // warm start (two-phase solve of a stack): interior solutions of the phase-1 pairs, and device storage for a batch's
+    // table of the saved solutions its pairs start from (BatchReq::guess; B entries, lazy)
     double* warm_x = nullptr;
     size_t warm_cap = 0;
     int* warm_src = nullptr;
-    const int* guess_src = nullptr;
     double* partials = nullptr;
     int nblk = 0;
     PairScalars* sc = nullptr;
@@ -134,7 +134,8 @@ struct vof_ctx {
                                 // post-sweep (VOF_FOLD_STORED=1; measured: the sweep gets slower by what the stand-alone prolongation
                                 // kernel costs, so that one stays)
     // direct preconditioner (block-tridiagonal LU by image rows, vof_direct.hpp); buffers allocated on first use
-    bool direct_on = false;          // the current batch is preconditioned by the direct solver instead of the multigrid cycle
+    bool direct_on = false;          // the batch in solve_batch is preconditioned by the direct solver instead of the multigrid cycle
+                                     // (BatchReq::direct; written by solve_batch alone)
     int dir_cap = 0;                 // pairs the direct buffers hold
     double *dir_T = nullptr, *dir_tabs = nullptr, *dir_W = nullptr, *dir_r = nullptr, *dir_y = nullptr, *dir_x = nullptr, *dir_t = nullptr;
     int *dir_ipiv = nullptr, *dir_info = nullptr;
@@ -273,7 +274,50 @@ void prof_collect(vof_ctx* c) {
         }                                                                                          \
     } while (0)
 
-constexpr size_t DBG_GUARD = 4096;        // bytes of guard pattern on either side of a buffer (VOF_DEBUG_CANARY=1)
+// Caller host memory (pageable) <-> device through a pinned bounce buffer on the context's stream: no null stream, and nothing
+// for the runtime to pin on the fly.  Every copy of the debug entry points and of the box / Liu-Shen
+// host variants; the caller's memory is free again on return.
+constexpr size_t BOUNCE_BYTES = (size_t)8 << 20;
+int d2h_bounced(vof_ctx* c, void* host, const void* dev, size_t bytes) {
+    if (!c->h_bounce) HIPCHK(hipHostMalloc((void**)&c->h_bounce, BOUNCE_BYTES));
+    for (size_t off = 0; off < bytes; off += BOUNCE_BYTES) {
+        const size_t n = std::min(BOUNCE_BYTES, bytes - off);
+        HIPCHK(hipMemcpyAsync(c->h_bounce, (const char*)dev + off, n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        memcpy((char*)host + off, c->h_bounce, n);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int h2d_bounced(vof_ctx* c, void* dev, const void* host, size_t bytes) {
+    if (!c->h_bounce) HIPCHK(hipHostMalloc((void**)&c->h_bounce, BOUNCE_BYTES));
+    for (size_t off = 0; off < bytes; off += BOUNCE_BYTES) {
+        const size_t n = std::min(BOUNCE_BYTES, bytes - off);
+        memcpy(c->h_bounce, (const char*)host + off, n);
+        HIPCHK(hipMemcpyAsync((char*)dev + off, c->h_bounce, n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+// A range of caller host memory registered (pinned in place) while the object lives; move-only.  Where the registration does
+// not hold, copies from / to the range run as pageable ones.
+class HostPin {
+    void* p_ = nullptr;
+public:
+    HostPin() = default;
+    HostPin(const void* p, size_t bytes) {
+        if (hipHostRegister((void*)p, bytes, hipHostRegisterDefault) == hipSuccess) p_ = (void*)p;
+        else (void)hipGetLastError();
+    }
+    HostPin(HostPin&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    HostPin& operator=(HostPin&& o) noexcept { std::swap(p_, o.p_); return *this; }
+    ~HostPin() { release(); }
+    bool ok() const { return p_ != nullptr; }
+    void release() { if (p_) (void)hipHostUnregister(p_); p_ = nullptr; }   // (the return code is discarded, as it always was)
+};
+
+constexpr size_t DBG_GUARD = 4096;       // bytes of guard pattern on either side of a buffer (VOF_DEBUG_CANARY=1)
 constexpr int DBG_GUARD_BYTE = 0xC5;
 
 template <typename T>
@@ -1416,6 +1460,8 @@ int direct_ld(const vof_ctx* c) {
 // The automatic re-solve (preconditioner 2) needs nothing but room for the buffers.
 int direct_capacity(vof_ctx* c, int want);
 bool direct_ok_for_fallback(vof_ctx* c) { return c->dir_ok >= 0 ? c->dir_ok != 0 : direct_capacity(c, 1) >= 1; }
+// preconditioner 1: every pair with the direct preconditioner (a one-level grid is solved by its dense inverse anyway)
+inline bool direct_only(const vof_ctx* c) { return c->prm.preconditioner == 1 && c->L.size() > 1; }
 
 // device bytes the direct preconditioner needs per pair in flight
 size_t direct_bytes_per_pair(const vof_ctx* c) {
@@ -1524,9 +1570,40 @@ int direct_apply_t(vof_ctx* c, VT* z, const VT* r, int np) {
     return 0;
 }
 
-int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double* vy, double* gm, double* speed,
-                vof_pair_stats* stats) {
+// What one call of solve_batch is to do.  The tables are host arrays of np entries; solve_batch uploads them (after the work
+// queued on the stream has ended, so the caller may re-use them between calls).
+struct BatchReq {
+    const double* frames;     // device pointer to frame 0 of the batch
+    int np;
+    const PairParam* table;   // per pair (alpha, beta, frame, output slot), or nullptr: pair k = frame k, the context's alphas
+    const int* guess;         // per pair the saved solution in warm_x to start from (-1: constant initial fields), or nullptr: no warm start
+    bool direct;              // precondition with the direct solver instead of the multigrid cycle (np <= dir_cap)
+    double *vx, *vy, *gm, *speed;
+    vof_pair_stats* stats;    // per pair, or nullptr
+};
+
+int solve_batch(vof_ctx* c, const BatchReq& rq) {
     const vof_params& P = c->prm;
+    const double* const frames_dev = rq.frames;
+    const int np = rq.np;
+    vof_pair_stats* const stats = rq.stats;
+    // the request as the kernels' launchers read it: c->pp / c->direct_on for the duration of this call, whatever way it ends
+    struct ReqGuard { vof_ctx* c; ~ReqGuard() { c->pp = nullptr; c->direct_on = false; } } req_guard{c};
+    const int* guess_src = nullptr;
+    if (rq.table || rq.guess) {
+        if (rq.table && !c->pp_buf) { if (int rc = dev_alloc(c, &c->pp_buf, (size_t)c->B)) return rc; }
+        if (rq.guess && !c->warm_src) { if (int rc = dev_alloc(c, &c->warm_src, (size_t)c->B)) return rc; }
+        HIPCHK(hipStreamSynchronize(c->stream));   // the host tables are re-used
+        if (rq.table) {
+            HIPCHK(hipMemcpyAsync(c->pp_buf, rq.table, (size_t)np * sizeof(PairParam), hipMemcpyHostToDevice, c->stream));
+            c->pp = c->pp_buf;
+        }
+        if (rq.guess) {
+            HIPCHK(hipMemcpyAsync(c->warm_src, rq.guess, (size_t)np * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            guess_src = c->warm_src;
+        }
+    }
+    c->direct_on = rq.direct;
     // preconditioner 2 ("auto"): when the direct re-solve is available, the multigrid attempt is not run to the reference's
     // 1000 iterations (OF.py:1120) - where the cycle works it needs 3 .. 100 Krylov steps, and a pair that
     // has not converged after MG_ATTEMPT_CAP of them is handed to the direct preconditioner, which settles it in one or two
@@ -1557,7 +1634,7 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
     // right-hand side and its norm
     // initial guess (OF.py:799-802: constants, in pixels/frame), right-hand side, initial residual r0 and shadow residual r^ = r0
     double sx = P.delta_t / P.delta_x;
-    const bool zero_guess = !c->guess_src && (P.initial_v_x == 0.0 && P.initial_v_y == 0.0 && P.initial_remodelling == 0.0);
+    const bool zero_guess = !guess_src && (P.initial_v_x == 0.0 && P.initial_v_y == 0.0 && P.initial_remodelling == 0.0);
     double* rh = c->krh;   // r^: from the zero guess it IS b (read-only from here on) - no copy; a restart switches to the real buffer
     {   // b and the block partial sums of (b, b) in one pass; from the zero guess r0 = b is written along
         Prof p(c, VOF_K_RHS, 0);
@@ -1570,9 +1647,9 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
         HIPCHK(hipMemsetAsync(c->kx, 0, (size_t)np * len * sizeof(double), s));
         rh = c->kb;
     } else {
-        if (c->guess_src) {   // warm start from the solution of a neighbouring, already solved pair (cf. OF.py:803-806)
+        if (guess_src) {   // warm start from the solution of a neighbouring, already solved pair (cf. OF.py:803-806)
             Prof p(c, VOF_K_VECTOR, 0, 16.0 * len);
-            k_gather_guess<<<rgrid(c, np), RBLK, 0, s>>>(c->kx, c->warm_x, c->guess_src, len, f.npts, P.initial_v_x * sx, P.initial_v_y * sx,
+            k_gather_guess<<<rgrid(c, np), RBLK, 0, s>>>(c->kx, c->warm_x, guess_src, len, f.npts, P.initial_v_x * sx, P.initial_v_y * sx,
                                                         P.initial_remodelling);
         } else {
             Prof p(c, VOF_K_VECTOR, 0); k_fill<<<dim3(c->nblk, np), 256, 0, s>>>(c->kx, f.npts, P.initial_v_x * sx, P.initial_v_y * sx, P.initial_remodelling);
@@ -1718,7 +1795,7 @@ int solve_batch(vof_ctx* c, const double* frames_dev, int np, double* vx, double
     // functionals (OF.py:1167-1183) and epilogue (OF.py:1159-1166, 1189-1191)
     { Prof p(c, VOF_K_FINALIZE, 0);   // one pass over the solution: outputs + functionals
       k_finalize_functionals<<<rgrid(c, np), RBLK, 0, s>>>(frames_dev, frame_stride(c), f.ni, f.nj, P.speed_alpha, P.remodelling_alpha,
-                                                           P.reference_quirks, c->kx, P.delta_x / P.delta_t, vx, vy, gm, speed,
+                                                           P.reference_quirks, c->kx, P.delta_x / P.delta_t, rq.vx, rq.vy, rq.gm, rq.speed,
                                                            c->partials, c->pp);
       k_sum3<<<np, 64, 0, s>>>(c->partials, c->nblk, c->func3); }
     HIPCHK(hipGetLastError());
@@ -2145,8 +2222,6 @@ int make_lane(vof_ctx* c, int i, int n, vof_ctx* L) {
     L->prof = false;
     L->err.clear();
     L->h_bounce = nullptr;
-    L->pp = nullptr;
-    L->guess_src = nullptr;
     L->gmres_pairs = 0;
     L->dir_ok = direct_ok_for_fallback(c) ? 1 : 0;
     const size_t len0 = 3 * c->L[0].npts;
@@ -2211,6 +2286,50 @@ int run_lanes(vof_ctx* c, int n, F&& fn, bool concurrent_only = false) {
     return 0;
 }
 
+// ---- plans of vof_solve_stack_host (no runtime call in them)
+
+// Batch schedule: full batches, and the remainder split so that the LAST batch is small - its device-to-host copies are the
+// only ones that cannot hide under a solve.
+struct HostBatch { int k0, np; };
+std::vector<HostBatch> plan_host_batches(int P, int B) {
+    std::vector<HostBatch> batches;
+    for (int k0 = 0; k0 < P;) {
+        const int rest = P - k0;
+        int np = std::min(B, rest);
+        if (P > B && rest <= B && rest > 48) np = rest - std::max(16, rest / 4);   // e.g. 127 -> 96 + 31
+        batches.push_back({k0, np});
+        k0 += np;
+    }
+    return batches;
+}
+
+inline size_t next_page(uintptr_t base, size_t offset) { return (size_t)(((base + offset + 4095) & ~(uintptr_t)4095) - base); }
+
+// Bytes of the movie (at address `base`) that are pinned right away; the rest is pinned by a helper thread while the first batch
+// is solved.  The split lies behind the first batch's frames, on a page boundary so that the two registrations share no page.
+size_t plan_movie_split(uintptr_t base, size_t movie_bytes, size_t first_batch_bytes, bool one_batch) {
+    return one_batch ? movie_bytes : std::min(movie_bytes, next_page(base, first_batch_bytes));
+}
+
+// Output regions: array i is cut at the batch boundaries, each moved up to the next page so that no two registrations share a
+// page; region (bi, i) - entry bi * 4 + i - is what batch bi's copy of array i writes, apart from the < 4 KB before its first
+// page, which belong to region bi - 1.  Arrays not asked for have empty regions.
+struct HostRegion { char* ptr; size_t bytes; };
+std::vector<HostRegion> plan_output_regions(double* const* outs, const std::vector<HostBatch>& batches, size_t frame_bytes, size_t out_bytes) {
+    const size_t nb = batches.size();
+    std::vector<HostRegion> regions(nb * 4, HostRegion{nullptr, 0});
+    for (int i = 0; i < 4; ++i) {
+        if (!outs[i]) continue;
+        size_t prev = 0;
+        for (size_t bi = 0; bi < nb; ++bi) {
+            const size_t end = bi + 1 < nb ? std::min(out_bytes, next_page((uintptr_t)outs[i], (size_t)batches[bi + 1].k0 * frame_bytes)) : out_bytes;
+            regions[bi * 4 + i] = HostRegion{(char*)outs[i] + prev, end - prev};
+            prev = end;
+        }
+    }
+    return regions;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2238,15 +2357,8 @@ static int two_phase_part(vof_ctx* c, const double* movie, const std::vector<int
                 hsrc[i] = phase2 && sync.usable[src] ? src : -1;   // -1: constant initial fields (a failed pair must not poison its neighbours)
             }
         }
-        HIPCHK(hipStreamSynchronize(c->stream));   // the host tables are re-used
-        HIPCHK(hipMemcpyAsync(c->pp_buf, hp.data(), (size_t)np * sizeof(PairParam), hipMemcpyHostToDevice, c->stream));
-        if (phase2) HIPCHK(hipMemcpyAsync(c->warm_src, hsrc.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        c->pp = c->pp_buf;
-        c->guess_src = phase2 ? c->warm_src : nullptr;
-        int rc = solve_batch(c, movie, np, v_x, v_y, remodelling, speed, st.data());
-        c->pp = nullptr;
-        c->guess_src = nullptr;
-        if (rc) return rc;
+        if (int rc = solve_batch(c, BatchReq{movie, np, hp.data(), phase2 ? hsrc.data() : nullptr, false, v_x, v_y, remodelling, speed, st.data()}))
+            return rc;
         if (!phase2) {
             HIPCHK(hipMemcpyAsync(c->warm_x + o * len, c->kx, (size_t)np * len * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             std::lock_guard<std::mutex> lk(sync.m);
@@ -2315,6 +2427,7 @@ static int solve_stack_two_phase(vof_ctx* c, const double* movie, int P, double*
     std::vector<int> first, rest;
     for (int k = 0; k < P; ++k) (k % stride == 0 ? first : rest).push_back(k);
     const int n1 = (int)first.size();
+    // (the lanes are copies of the context that allocate nothing: the tables' device storage has to exist before they are made)
     if (!c->pp_buf) { if (int rc = dev_alloc(c, &c->pp_buf, (size_t)B)) return rc; }
     if (!c->warm_src) { if (int rc = dev_alloc(c, &c->warm_src, (size_t)B)) return rc; }
     if (c->warm_cap < (size_t)n1 * len) {
@@ -2354,20 +2467,39 @@ static int direct_solve_list(vof_ctx* c, const double* frames, const std::vector
     const int cap = direct_capacity(c, std::min<int>(c->B, (int)items.size()));
     if (cap < 1) { c->err = "the direct preconditioner does not fit into the free device memory (3 n_j x 3 n_j doubles per image row and pair)"; return -3; }
     if (int rc = direct_alloc(c, cap)) return rc;
-    if (!c->pp_buf) { if (int rc = dev_alloc(c, &c->pp_buf, (size_t)c->B)) return rc; }
     std::vector<vof_pair_stats> st((size_t)c->dir_cap);
     for (size_t o = 0; o < items.size(); o += (size_t)c->dir_cap) {
         const int np = (int)std::min<size_t>((size_t)c->dir_cap, items.size() - o);
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpyAsync(c->pp_buf, items.data() + o, (size_t)np * sizeof(PairParam), hipMemcpyHostToDevice, c->stream));
-        c->pp = c->pp_buf;
-        c->direct_on = true;
-        int rc = solve_batch(c, frames, np, v_x, v_y, remodelling, speed, st.data());
-        c->direct_on = false;
-        c->pp = nullptr;
-        if (rc) return rc;
+        if (int rc = solve_batch(c, BatchReq{frames, np, items.data() + o, nullptr, true, v_x, v_y, remodelling, speed, st.data()})) return rc;
         if (stats)
             for (int i = 0; i < np; ++i) stats[o + i] = st[i];
+    }
+    return 0;
+}
+
+// Preconditioner 2 ("auto"), after the multigrid attempt on the n pairs of `table` (nullptr: pair k = frame k, the context's
+// alphas) whose records are in stats: those it left unconverged once more with the direct preconditioner, if that fits.
+static int resolve_unconverged(vof_ctx* c, const double* frames, const PairParam* table, int n, double* const* outs, vof_pair_stats* stats) {
+    if (c->prm.preconditioner != 2 || !stats) return 0;   // (without the first attempt's records there is nothing to select by)
+    std::vector<PairParam> items;
+    std::vector<int> which;
+    for (int k = 0; k < n; ++k)
+        if (!stats[k].converged && std::isfinite(stats[k].relative_residual)) {   // a NaN frame stays a reported failure
+            items.push_back(table ? table[k] : PairParam{c->prm.speed_alpha, c->prm.remodelling_alpha, k, k});
+            which.push_back(k);
+        }
+    if (items.empty() || !direct_ok_for_fallback(c)) return 0;
+    std::vector<vof_pair_stats> st(items.size());
+    if (int rc = direct_solve_list(c, frames, items, outs[0], outs[1], outs[2], outs[3], st.data())) {
+        if (rc != -3) return rc;     // -3: no room: keep the reported non-convergence
+        c->err.clear();
+        return 0;
+    }
+    for (size_t i = 0; i < which.size(); ++i) {
+        const vof_pair_stats& first = stats[which[i]];
+        st[i].iterations += first.iterations;                                                   // Krylov steps of both attempts
+        st[i].batch_ms += first.batch_ms / std::max(1, first.batch_pairs) * st[i].batch_pairs;   // and their time (per-pair share kept)
+        stats[which[i]] = st[i];
     }
     return 0;
 }
@@ -2382,7 +2514,7 @@ static int solve_range_dev(vof_ctx* c, const double* frames, int P, double* v_x,
     const vof_params prm = c->prm;
     const int stride = prm.warm_start_stride;
     const size_t fs = frame_stride(c);
-    if (prm.preconditioner == 1 && c->L.size() > 1) {   // (a one-level grid is solved by its dense inverse anyway)
+    if (direct_only(c)) {
         std::vector<PairParam> items((size_t)P);
         for (int k = 0; k < P; ++k) items[k] = PairParam{prm.speed_alpha, prm.remodelling_alpha, k, k};
         return direct_solve_list(c, frames, items, v_x, v_y, remodelling, speed, stats);
@@ -2399,10 +2531,9 @@ static int solve_range_dev(vof_ctx* c, const double* frames, int P, double* v_x,
         auto plain = [&](vof_ctx* L, int a, int b) -> int {   // pairs [a, b) in batches of L's slots
             for (int k0 = a; k0 < b; k0 += batch_slots(L)) {
                 int np = std::min(batch_slots(L), b - k0);
-                int rc = solve_batch(L, frames + (size_t)k0 * fs, np, v_x + (size_t)k0 * fs, v_y + (size_t)k0 * fs,
-                                     remodelling + (size_t)k0 * fs, speed ? speed + (size_t)k0 * fs : nullptr,
-                                     stats ? stats + k0 : nullptr);
-                if (rc) return rc;
+                const size_t o = (size_t)k0 * fs;
+                if (int rc = solve_batch(L, BatchReq{frames + o, np, nullptr, nullptr, false, v_x + o, v_y + o, remodelling + o,
+                                                     speed ? speed + o : nullptr, stats ? stats + k0 : nullptr})) return rc;
             }
             return 0;
         };
@@ -2413,29 +2544,8 @@ static int solve_range_dev(vof_ctx* c, const double* frames, int P, double* v_x,
             return rc;
         }
     }
-    if (prm.preconditioner == 2 && stats) {
-        std::vector<PairParam> items;
-        std::vector<int> which;
-        for (int k = 0; k < P; ++k)
-            if (!stats[k].converged && std::isfinite(stats[k].relative_residual)) {   // a NaN frame stays a reported failure
-                items.push_back(PairParam{prm.speed_alpha, prm.remodelling_alpha, k, k});
-                which.push_back(k);
-            }
-        if (!items.empty() && direct_ok_for_fallback(c)) {
-            std::vector<vof_pair_stats> st(items.size());
-            if (int rc = direct_solve_list(c, frames, items, v_x, v_y, remodelling, speed, st.data())) {
-                if (rc != -3) return rc;     // -3: no room: keep the reported non-convergence
-                c->err.clear();
-            } else {
-                for (size_t i = 0; i < which.size(); ++i) {
-                    st[i].iterations += stats[which[i]].iterations;   // Krylov steps of both attempts
-                    st[i].batch_ms += stats[which[i]].batch_ms / std::max(1, stats[which[i]].batch_pairs) * st[i].batch_pairs;   // and their time (per-pair share kept)
-                    stats[which[i]] = st[i];
-                }
-            }
-        }
-    }
-    return 0;
+    double* const outs[4] = {v_x, v_y, remodelling, speed};
+    return resolve_unconverged(c, frames, nullptr, P, outs, stats);
 }
 
 int vof_solve_stack_dev(vof_ctx* c, const double* movie, int n_frames, const vof_params* p, double* v_x, double* v_y,
@@ -2484,84 +2594,40 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
     const int P = n_frames - 1;
     const bool multi = P > c->B;                       // more than one batch: overlap the copies with the solves
     if (int rc = ensure_staging(c, multi)) return rc;
-    // Batch schedule: full batches, and the remainder split so that the LAST batch is small - its device-to-host copies
-    // are the only ones that cannot hide under a solve.
-    struct Batch { int k0, np; };
-    std::vector<Batch> batches;
-    for (int k0 = 0; k0 < P;) {
-        int np = std::min(c->B, P - k0);
-        const int rest = P - k0;
-        if (multi && rest <= c->B && rest > 48) np = rest - std::max(16, rest / 4);   // e.g. 127 -> 96 + 31
-        batches.push_back({k0, np});
-        k0 += np;
-    }
+    const std::vector<HostBatch> batches = plan_host_batches(P, c->B);
     const int nb = (int)batches.size();
     // Pageable host-to-device copies run at ~2 GB/s on this platform, pinned ones at ~55 GB/s: the caller's movie is
     // pinned in place for the duration of the call (0.04 s/GB) - the frames of the first batch right away, the rest by a
-    // helper thread while the first batch is solved.  The split point is page aligned so that the two registrations do
-    // not share a page.  Unpinned parts fall back to pageable copies.
+    // helper thread while the first batch is solved (plan_movie_split).  Unpinned parts fall back to pageable copies.
     const char* mbase = (const char*)movie;
     const size_t movie_bytes = (size_t)n_frames * fs * sizeof(double);
-    size_t split = movie_bytes;
-    if (nb > 1) {
-        size_t want = (size_t)(batches[0].np + 1) * fs * sizeof(double);
-        size_t addr = ((size_t)(uintptr_t)mbase + want + 4095) & ~(size_t)4095;
-        split = std::min(movie_bytes, addr - (size_t)(uintptr_t)mbase);
-    }
+    const size_t split = plan_movie_split((uintptr_t)mbase, movie_bytes, (size_t)(batches[0].np + 1) * fs * sizeof(double), nb == 1);
     const bool htrace = getenv("VOF_TRACE_HOST") != nullptr;
     const auto ht0 = std::chrono::steady_clock::now();
     auto hmark = [&](const char* what) {
         if (htrace) fprintf(stderr, "[vof host] %8.1f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ht0).count(), what);
     };
-    const bool pinned_a = hipHostRegister((void*)mbase, split, hipHostRegisterDefault) == hipSuccess;
-    if (!pinned_a) (void)hipGetLastError();
-    hmark("first movie part pinned");
-    bool pinned_b = false;
-    // Freshly allocated output arrays (np.empty) are not resident yet: first-touch page faults would serialise with
-    // the device-to-host copies (0.6 s for 8 GB).  Helper threads prepare them while the GPU solves the first batch
-    // (the arrays are outputs: every byte is overwritten below): they are pinned in place (which faults them in), so
-    // that the copies run at the pinned rate and asynchronously; arrays below 1 MB are only touched.
+    HostPin pin_a(mbase, split), pin_b;
+    hmark(pin_a.ok() ? "first movie part pinned" : "first movie part not pinned: pageable copies");
     double* outs[4] = {v_x, v_y, remodelling, speed};
     const size_t out_bytes = (size_t)P * fs * sizeof(double);
     std::vector<std::thread> helpers;
     std::thread movie_helper;
     if (split < movie_bytes)
-        movie_helper = std::thread([&pinned_b, mbase, split, movie_bytes, dev = c->device]() {
-            if (hipSetDevice(dev) == hipSuccess &&
-                hipHostRegister((void*)(mbase + split), movie_bytes - split, hipHostRegisterDefault) == hipSuccess) pinned_b = true;
+        movie_helper = std::thread([&pin_b, mbase, split, movie_bytes, dev = c->device]() {
+            if (hipSetDevice(dev) == hipSuccess) pin_b = HostPin(mbase + split, movie_bytes - split);
         });
-    // Output regions: array i is cut at the batch boundaries (moved up to the next page so that no two registrations share
-    // a page); region (bi, i) is what batch bi's copy of array i writes, apart from the < 4 KB before its first page, which
-    // belongs to region bi - 1.  A pool of helper threads prepares the regions IN BATCH ORDER while the GPU solves: a region
-    // is pinned in place (which faults its pages in; 8.6 GB of fresh np.empty pages cost ~0.4 s of first-touch faults -
-    // round 2 pinned each array whole and the first batch's copies waited for all of it), arrays below 1 MB are only
-    // touched.  The copies of batch bi wait for batch bi's regions alone.
+    // Freshly allocated output arrays (np.empty) are not resident yet: first-touch page faults would serialise with the
+    // device-to-host copies (8.6 GB of fresh pages cost ~0.4 s).  The arrays are outputs - every byte is overwritten below -,
+    // so a pool of helper threads touches their regions (plan_output_regions) IN BATCH ORDER while the GPU solves, and the
+    // calling thread pins a batch's regions in place just before its copies (round 2 pinned each array whole and the first
+    // batch's copies waited for all of it); arrays below 1 MB are only touched.  The copies of batch bi wait for batch bi's
+    // regions alone.
     const bool pin_outputs = out_bytes >= ((size_t)1 << 20);   // pageable device-to-host copies can drop to ~2 GB/s
-    std::vector<size_t> bound((size_t)nb + 1);                 // byte offsets of the region boundaries inside an output array
-    struct Region { char* ptr; size_t bytes; bool pinned; };
-    std::vector<Region> regions((size_t)nb * 4, Region{nullptr, 0, false});
+    const std::vector<HostRegion> regions = plan_output_regions(outs, batches, fs * sizeof(double), out_bytes);
+    std::vector<HostPin> region_pins(regions.size());
     std::vector<std::atomic<int>> batch_ready((size_t)nb);
     for (auto& a : batch_ready) a.store(0);
-    int n_outs = 0;
-    for (int i = 0; i < 4; ++i) if (outs[i]) ++n_outs;
-    for (int i = 0; i < 4; ++i) {
-        if (!outs[i]) continue;
-        const uintptr_t base = (uintptr_t)outs[i];
-        for (int bi = 0; bi <= nb; ++bi) {
-            size_t o = bi == nb ? out_bytes : (size_t)batches[bi].k0 * fs * sizeof(double);
-            if (bi > 0 && bi < nb) o = std::min(out_bytes, (size_t)(((base + o + 4095) & ~(uintptr_t)4095) - base));
-            bound[(size_t)bi] = o;   // (the same for every array only if their bases share the page offset: kept per array below)
-            if (bi > 0) regions[(size_t)(bi - 1) * 4 + i].bytes = o;   // provisional: end offset
-        }
-        size_t prev = 0;
-        for (int bi = 0; bi < nb; ++bi) {
-            Region& r = regions[(size_t)bi * 4 + i];
-            const size_t end = r.bytes;
-            r.ptr = (char*)outs[i] + prev;
-            r.bytes = end - prev;
-            prev = end;
-        }
-    }
     std::atomic<int> next_task{0};
     const int n_tasks = nb * 4;
     // The helpers only TOUCH the pages (plain stores: no runtime call, no lock shared with the launching thread - eight
@@ -2571,7 +2637,7 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
         for (;;) {
             const int t = next_task.fetch_add(1);
             if (t >= n_tasks) return;
-            Region& r = regions[(size_t)t];
+            const HostRegion& r = regions[(size_t)t];
             if (r.ptr && r.bytes) {
                 volatile char* q = (volatile char*)r.ptr;
                 for (size_t o = 0; o < r.bytes; o += 4096) q[o] = 0;
@@ -2591,10 +2657,8 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
             while (batch_ready[(size_t)b].load() < 4) std::this_thread::yield();
         for (; regions_pinned_upto <= bi; ++regions_pinned_upto)
             for (int i = 0; i < 4 && pin_outputs; ++i) {
-                Region& r = regions[(size_t)regions_pinned_upto * 4 + i];
-                if (!r.ptr || !r.bytes) continue;
-                if (hipHostRegister((void*)r.ptr, r.bytes, hipHostRegisterDefault) == hipSuccess) r.pinned = true;
-                else (void)hipGetLastError();
+                const size_t t = (size_t)regions_pinned_upto * 4 + i;
+                if (regions[t].ptr && regions[t].bytes) region_pins[t] = HostPin(regions[t].ptr, regions[t].bytes);
             }
     };
     auto join_helpers = [&]() { for (auto& t : helpers) if (t.joinable()) t.join(); };
@@ -2602,7 +2666,7 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
     int rc_all = 0;
     double* frames_buf[2] = {c->st_movie, multi ? c->st_movie2 : c->st_movie};
     auto upload = [&](int bi, hipStream_t st) {   // frames k0 .. k0 + np of batch bi; a copy never straddles the two pinned regions
-        const Batch& bt = batches[bi];
+        const HostBatch& bt = batches[bi];
         const size_t o0 = (size_t)bt.k0 * fs * sizeof(double), o1 = o0 + (size_t)(bt.np + 1) * fs * sizeof(double);
         char* dst = (char*)frames_buf[bi & 1];
         hipError_t e = hipSuccess;
@@ -2618,7 +2682,7 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
         if (e != hipSuccess) rc_all = fail_msg("H2D copy failed", e);
     }
     for (int bi = 0; bi < nb && !rc_all; ++bi) {
-        const Batch& bt = batches[bi];
+        const HostBatch& bt = batches[bi];
         const int set = bi & 1;
         double** so = (multi && set) ? c->st_out2 : c->st_out;
         hipError_t e;
@@ -2669,10 +2733,9 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
     if (multi && hipStreamSynchronize(c->copy_stream) != hipSuccess && !rc_all) { c->err = "copy stream synchronize failed"; rc_all = -2; }
     if (hipStreamSynchronize(c->stream) != hipSuccess && !rc_all) { c->err = "stream synchronize failed"; rc_all = -2; }
     hmark("copies done");
-    for (auto& r : regions)
-        if (r.pinned) (void)hipHostUnregister((void*)r.ptr);
-    if (pinned_a) (void)hipHostUnregister((void*)mbase);
-    if (pinned_b) (void)hipHostUnregister((void*)(mbase + split));
+    for (auto& r : region_pins) r.release();   // in the order they always had: regions, first movie part, second
+    pin_a.release();
+    pin_b.release();
     hmark("unpinned");
     return rc_all;
 }
@@ -2781,35 +2844,12 @@ int vof_subsample_dev(vof_ctx* c, const double* field, int n_fields, int box, in
 // preconditioner policy of solve_range_dev: direct only, or multigrid with the direct re-solve of what it leaves unconverged.
 static int solve_virtual_pairs(vof_ctx* c, const double* dmovie, const std::vector<PairParam>& hp, int np, double* const* outs,
                                vof_pair_stats* st) {
-    if (c->prm.preconditioner == 1 && c->L.size() > 1) {
+    if (direct_only(c)) {
         std::vector<PairParam> items(hp.begin(), hp.begin() + np);
         return direct_solve_list(c, dmovie, items, outs[0], outs[1], outs[2], outs[3], st);
     }
-    if (!c->pp_buf) { if (int rc = dev_alloc(c, &c->pp_buf, (size_t)c->B)) return rc; }
-    HIPCHK(hipStreamSynchronize(c->stream));   // hp is re-used by the caller: the previous upload must have completed
-    HIPCHK(hipMemcpyAsync(c->pp_buf, hp.data(), (size_t)np * sizeof(PairParam), hipMemcpyHostToDevice, c->stream));
-    c->pp = c->pp_buf;
-    int rc = solve_batch(c, dmovie, np, outs[0], outs[1], outs[2], outs[3], st);
-    c->pp = nullptr;
-    if (rc) return rc;
-    if (c->prm.preconditioner == 2) {
-        std::vector<PairParam> items;
-        std::vector<int> which;
-        for (int i = 0; i < np; ++i)
-            if (!st[i].converged && std::isfinite(st[i].relative_residual)) { items.push_back(hp[i]); which.push_back(i); }
-        if (!items.empty() && direct_ok_for_fallback(c)) {
-            std::vector<vof_pair_stats> s2(items.size());
-            int rc2 = direct_solve_list(c, dmovie, items, outs[0], outs[1], outs[2], outs[3], s2.data());
-            if (rc2 == 0) {
-                for (size_t i = 0; i < which.size(); ++i) { s2[i].iterations += st[which[i]].iterations; st[which[i]] = s2[i]; }
-            } else if (rc2 != -3) {
-                return rc2;
-            } else {
-                c->err.clear();
-            }
-        }
-    }
-    return 0;
+    if (int rc = solve_batch(c, BatchReq{dmovie, np, hp.data(), nullptr, false, outs[0], outs[1], outs[2], outs[3], st})) return rc;
+    return resolve_unconverged(c, dmovie, hp.data(), np, outs, st);
 }
 
 int vof_vary_regularisation_host(vof_ctx* c, const double* movie, int n_frames, const vof_params* base,
@@ -2830,11 +2870,10 @@ int vof_vary_regularisation_host(vof_ctx* c, const double* movie, int n_frames, 
     auto fail = [&](int rc) { (void)hipFree(dmovie); return rc; };
     {   // pinned in place for the upload (pageable copies run at ~2 GB/s here, see vof_solve_stack_host)
         const size_t movie_bytes = (size_t)n_frames * fs * sizeof(double);
-        const bool pinned = hipHostRegister((void*)movie, movie_bytes, hipHostRegisterDefault) == hipSuccess;
-        if (!pinned) (void)hipGetLastError();
+        HostPin pin(movie, movie_bytes);
         hipError_t e = hipMemcpyAsync(dmovie, movie, movie_bytes, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (pinned) (void)hipHostUnregister((void*)movie);
+        pin.release();
         if (e != hipSuccess) { c->err = std::string("H2D copy failed: ") + hipGetErrorString(e); return fail(-2); }
     }
     if (blur_weights)
@@ -2867,7 +2906,6 @@ int vof_vary_regularisation_host(vof_ctx* c, const double* movie, int n_frames, 
         // G * P "virtual pairs" of one batch - pair v = (combination v / P, frame pair v % P) reads its own
         // (alpha, beta) and frame index from the PairParam table.
         const int G = std::max(1, c->B / P);
-        if (!c->pp_buf) { if (int rc = dev_alloc(c, &c->pp_buf, (size_t)c->B)) return fail(rc); }
         std::vector<PairParam> hp((size_t)G * P);
         std::vector<vof_pair_stats> st((size_t)G * P);
         for (int t0 = 0; t0 < n_comb; t0 += G) {
@@ -3056,8 +3094,7 @@ int vof_debug_setup(vof_ctx* c, const double* movie_host, int n_pairs, const vof
     HIPCHK(hipSetDevice(c->device));
     size_t fs = frame_stride(c);
     if (int rc = ensure_staging(c, false)) return rc;
-    HIPCHK(hipMemcpyAsync(c->st_movie, movie_host, (size_t)(n_pairs + 1) * fs * sizeof(double), hipMemcpyHostToDevice,
-                          c->stream));
+    if (int rc = h2d_bounced(c, c->st_movie, movie_host, (size_t)(n_pairs + 1) * fs * sizeof(double))) return rc;
     if (int rc = setup_batch(c, c->st_movie, n_pairs)) return rc;
     c->vcoarse32 = p->vcycle_precision == 3;   // vof_debug_vcycle* run the cycle as a solve would (the per-level entry points: float64)
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -3089,49 +3126,22 @@ int vof_debug_level_shape(vof_ctx* c, int level, int* n_i, int* n_j) {
     size_t nbytes = (size_t)c->npairs * 3 * lv.npts * sizeof(double);                 \
     (void)nbytes;
 
-// Device -> pageable host memory through a pinned bounce buffer on the context's stream (the debug entry points used the
-// runtime's blocking hipMemcpy on the null stream, which pins the destination on the fly for copies above 1 MiB).
-constexpr size_t BOUNCE_BYTES = (size_t)8 << 20;
-static int d2h_bounced(vof_ctx* c, void* host, const void* dev, size_t bytes) {
-    if (!c->h_bounce) HIPCHK(hipHostMalloc((void**)&c->h_bounce, BOUNCE_BYTES));
-    for (size_t off = 0; off < bytes; off += BOUNCE_BYTES) {
-        const size_t n = std::min(BOUNCE_BYTES, bytes - off);
-        HIPCHK(hipMemcpyAsync(c->h_bounce, (const char*)dev + off, n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        memcpy((char*)host + off, c->h_bounce, n);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
 // The debug API moves host float64 arrays in and out of V-typed device buffers (kp, kv, kt; staging: krh).
 static int dbg_up(vof_ctx* c, void* dst_v, const double* host, size_t n) {
-    if (c->vfloat) {
-        HIPCHK(hipMemcpyAsync(c->krh, host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        k_convert<double, float><<<256, 256, 0, c->stream>>>(c->krh, (float*)dst_v, n);
-    } else {
-        HIPCHK(hipMemcpyAsync(dst_v, host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
+    if (int rc = h2d_bounced(c, c->vfloat ? (void*)c->krh : dst_v, host, n * sizeof(double))) return rc;
+    if (c->vfloat) k_convert<double, float><<<256, 256, 0, c->stream>>>(c->krh, (float*)dst_v, n);
     return 0;
 }
 static int dbg_down(vof_ctx* c, double* host, const void* src_v, size_t n) {
-    if (c->vfloat || c->h32) {   // (h32: the result of vof_debug_vcycle*)
-        k_convert<float, double><<<256, 256, 0, c->stream>>>((const float*)src_v, c->krh, n);
-        HIPCHK(hipMemcpyAsync(host, c->krh, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    } else {
-        HIPCHK(hipMemcpyAsync(host, src_v, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipGetLastError());
-    return 0;
+    const bool f32 = c->vfloat || c->h32;   // (h32: the result of vof_debug_vcycle*)
+    if (f32) k_convert<float, double><<<256, 256, 0, c->stream>>>((const float*)src_v, c->krh, n);
+    return d2h_bounced(c, host, f32 ? (const void*)c->krh : src_v, n * sizeof(double));
 }
 
 int vof_debug_rhs(vof_ctx* c, double* b_host) {
     DBG_LEVEL(0)
     k_rhs<<<grid2d(lv.ni, lv.nj, c->npairs), blk2d, 0, c->stream>>>(c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, c->kb, nullptr);
-    HIPCHK(hipMemcpyAsync(b_host, c->kb, nbytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return d2h_bounced(c, b_host, c->kb, nbytes);
 }
 
 int vof_debug_apply(vof_ctx* c, int level, const double* x_host, double* y_host) {
@@ -3140,10 +3150,7 @@ int vof_debug_apply(vof_ctx* c, int level, const double* x_host, double* y_host)
     if (int rc = dbg_up(c, c->kp, x_host, n)) return rc;
     if (level == 0) {   // the Krylov product: V-typed x, FP64 result
         krylov_apply(c, c->kp, c->kv, c->npairs, nullptr);
-        HIPCHK(hipMemcpyAsync(y_host, c->kv, nbytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipGetLastError());
-        return 0;
+        return d2h_bounced(c, y_host, c->kv, nbytes);
     }
     VDISPATCH(c, apply_level_t<VT>(c, level, (const VT*)c->kp, (const VT*)nullptr, (VT*)c->kv, 0, c->npairs, nullptr));
     return dbg_down(c, y_host, c->kv, n);
@@ -3153,13 +3160,10 @@ int vof_debug_gs(vof_ctx* c, int level, double* x_host, const double* b_host, in
     DBG_LEVEL(level)
     if (colour < 0 || colour > 3) { c->err = "bad colour"; return -1; }
     if (c->vfloat) { c->err = "the per-colour reference smoother works on float64 vectors only"; return -1; }
-    HIPCHK(hipMemcpyAsync(c->kp, x_host, nbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->kv, b_host, nbytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = h2d_bounced(c, c->kp, x_host, nbytes)) return rc;
+    if (int rc = h2d_bounced(c, c->kv, b_host, nbytes)) return rc;
     gs_colour(c, level, c->kp, c->kv, colour, c->npairs, nullptr);
-    HIPCHK(hipMemcpyAsync(x_host, c->kp, nbytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipGetLastError());
-    return 0;
+    return d2h_bounced(c, x_host, c->kp, nbytes);
 }
 
 int vof_debug_sweep(vof_ctx* c, int level, double* x_host, const double* b_host, int reverse, int from_zero) {
@@ -3311,7 +3315,7 @@ int vof_debug_vcycle_apply(vof_ctx* c, const double* r_host, double* y_host, dou
     if (int rc = dbg_up(c, c->kp, r_host, n)) return rc;
     const int np = c->npairs;
     c->cur_units = np;
-    HIPCHK(hipMemcpyAsync(c->krh, r_host, nbytes, hipMemcpyHostToDevice, c->stream));   // dot partner (float64)
+    if (int rc = h2d_bounced(c, c->krh, r_host, nbytes)) return rc;   // dot partner (float64)
     CycleIO io;
     io.trail = S0Trail{c->kv, c->krh, 1, c->partials};
     c->h32 = handoff32_ok(c);
@@ -3320,12 +3324,12 @@ int vof_debug_vcycle_apply(vof_ctx* c, const double* r_host, double* y_host, dou
     int nb = io.trail_nblk ? io.trail_nblk : krylov_apply(c, c->ky, c->kv, np, nullptr, c->krh, 1);
     if (fused) *fused = io.trail_nblk ? 1 : 0;
     if (!nb) { c->h32 = false; c->err = "the operator kernel did not fuse the dot products"; return -1; }
-    std::vector<double> part((size_t)np * 3 * nb);
-    HIPCHK(hipMemcpyAsync(part.data(), c->partials, part.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     const int rcd = dbg_down(c, y_host, c->ky, n);
     c->h32 = false;
     if (rcd) return rcd;
     if (int rc = d2h_bounced(c, v_host, c->kv, nbytes)) return rc;
+    std::vector<double> part((size_t)np * 3 * nb);
+    if (int rc = d2h_bounced(c, part.data(), c->partials, part.size() * sizeof(double))) return rc;
     for (int k = 0; k < np; ++k)
         for (int sl = 0; sl < 2; ++sl) {
             double a = 0;
@@ -3345,18 +3349,6 @@ int vof_debug_coarse_solve(vof_ctx* c, const double* r_host, double* e_host) {
 }
 
 // ---- box least-squares flow (conduct_optical_flow, OF.py:24-218) ------------------------------------------------
-// Pageable host memory -> device through the pinned bounce buffer (the counterpart of d2h_bounced).
-static int h2d_bounced(vof_ctx* c, void* dev, const void* host, size_t bytes) {
-    if (!c->h_bounce) HIPCHK(hipHostMalloc((void**)&c->h_bounce, BOUNCE_BYTES));
-    for (size_t off = 0; off < bytes; off += BOUNCE_BYTES) {
-        const size_t n = std::min(BOUNCE_BYTES, bytes - off);
-        memcpy(c->h_bounce, (const char*)host + off, n);
-        HIPCHK(hipMemcpyAsync((char*)dev + off, c->h_bounce, n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
-}
-
 constexpr int BF_GENERAL_CHUNK = 4;       // pairs per launch of the general path (its scratch: 11 planes per pair)
 constexpr int BF_FUSED_CHUNK = 16384;     // pairs per launch of the fused kernel (grid z)
 

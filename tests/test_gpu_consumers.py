@@ -53,6 +53,37 @@ def test_native_sweep_batches_and_blur(of):
     np.testing.assert_allclose(a["remodelling_means"][0, 1], np.mean(one["remodelling"]), rtol=1e-12)
 
 
+def test_native_sweep_resolves_hard_regime_in_both_branches(of):
+    """A regime the multigrid cycle does not settle in 60 steps (8-bit data, speed_alpha 1e4; see
+    test_hard_regimes_are_rescued_by_the_direct_preconditioner), so the re-solve with the direct preconditioner fires in
+    the sweep: once in its long-movie branch (3 pairs in batches of 2) and once in its virtual-pair branch (one batch of 3).
+    Both end with every pair converged, and their tables agree with each other and with numpy statistics of
+    variational_optical_flow at the same arguments.
+
+    Tolerance 1e-4, by reasoning (the figure of the commit before the re-solve policy was written once has not been measured
+    yet; the bound is to become ten times that figure, and can only get tighter): all three results meet rtol 1e-9 on the
+    independent residual, and in this regime test_hard_regimes_are_rescued_by_the_direct_preconditioner holds such a
+    result to 1e-5 of the exact fields; two results therefore differ by at most 2e-5 in the fields, the means by as much,
+    the quadratic tables (variances, functional) by twice that: 4e-5, rounded up.  Where the per-pair arithmetic does not
+    depend on the batch shape the three agree far better (test_native_sweep_batches_and_blur: 1e-12)."""
+    movie = np.round(orc.make_texture_stack(66, 4, seed=5) * 255.0)
+    sa, ra = np.array([1e4]), np.array([1e2])
+    kw = dict(rtol=1e-9, max_iterations=60)
+    a = of.vary_regularisation(movie, sa, ra, max_pairs_in_flight=2, return_stats=True, **kw)
+    b = of.vary_regularisation(movie, sa, ra, max_pairs_in_flight=3, return_stats=True, **kw)
+    one = of.variational_optical_flow(movie, speed_alpha=1e4, remodelling_alpha=1e2, **kw)
+    assert a["stats"]["converged_all"].all() and b["stats"]["converged_all"].all()
+    ref = {"speed_means": np.mean(one["speed"]), "speed_variances": np.var(one["speed"]),
+           "remodelling_means": np.mean(one["remodelling"]), "remodelling_variances": np.var(one["remodelling"]),
+           "functional": one["L1_functional"] + one["speed_functional"] + one["remodelling_functional"]}
+    tol = 1e-4
+    for k, want in ref.items():
+        print(k, a[k][0, 0], b[k][0, 0], want)
+        np.testing.assert_allclose(a[k], b[k], rtol=tol, err_msg=k)
+        np.testing.assert_allclose(a[k][0, 0], want, rtol=tol, err_msg=k)
+        np.testing.assert_allclose(b[k][0, 0], want, rtol=tol, err_msg=k)
+
+
 def test_native_sweep_empty_grid_and_errors(of):
     movie = orc.make_texture_stack(16, 2, seed=3)
     r = of.vary_regularisation(movie, np.array([]), np.array([1.0, 2.0]))
