@@ -253,6 +253,44 @@ int vof_vary_regularisation_host(vof_ctx* ctx, const double* movie, int n_frames
                                  const double* remodelling_alphas, int n_remodelling_alphas,
                                  const double* blur_weights, int blur_radius, vof_variation_stats* out);
 
+/* Summary of one box size of vary_boxsize. */
+typedef struct vof_boxsize_stats {
+    double speed_mean, speed_variance;             /* np.mean / np.var of the box's speed stack; NaN propagates as in numpy */
+    double remodelling_mean, remodelling_variance; /* ... of net_remodelling; 0 without include_remodelling */
+    int64_t nonfinite_count;                       /* NaN / Inf values in the speed stack */
+    int32_t box_size;                              /* box_sizes[b], echoed */
+    int32_t reserved;
+} vof_boxsize_stats;
+
+/* The box-size sweep the reference's scripts run around conduct_optical_flow (compare_rho_and_actin.py:387-419, 853-894):
+ * what vof_box_flow_* computes for every box_sizes[b] (n_boxes >= 1 entries, any order, duplicates allowed, each >= 1) of the
+ * same movie in one call.  The derived planes of a pair are computed once and the window grows by one ring per step from
+ * half width 0 to max int(box / 2), only ever adding terms to float64 accumulators, so a box costs O(1) per pixel; the fields
+ * of a box do not depend on the other boxes of the list.  The frames are blurred first if blur_weights != NULL (taps as for
+ * vof_blur_stack_*).  Pairs are processed in chunks sized by the free device memory (_host: at most the context's
+ * max_pairs_in_flight at a time); scratch planes are kept on the context.
+ * stats: n_boxes records, host memory, required.  Mean / variance are two-pass reductions on the device.
+ * histogram_edges: NULL, or the histogram_bins + 1 edges of np.linspace(lo, hi, bins + 1) in host memory; histograms (host,
+ *   n_boxes x histogram_bins int64) then receives np.histogram(speed, bins, (lo, hi))[0] of every box exactly.
+ * probe_ij: NULL, or n_probes (i, j) index pairs in host memory; probe_speeds (host, n_boxes x (n_frames - 1) x n_probes)
+ *   then receives speed[k][i][j].
+ * v_x, v_y, speed, net_remodelling: NULL (stats only: no full-size stack exists anywhere), or (n_boxes, n_frames - 1, n_i, n_j)
+ *   float64, all of v_x, v_y, speed together; net_remodelling may be NULL also then (required with include_remodelling).
+ * _dev: movie and the four field stacks are device pointers; _host: host pointers, staged through the context's pinned
+ * bounce buffer.  Everything else is host memory in both. */
+int vof_vary_boxsize_dev(vof_ctx* ctx, const double* movie, int n_frames, const int32_t* box_sizes, int n_boxes,
+                         double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                         const double* blur_weights, int blur_radius,
+                         const double* histogram_edges, int histogram_bins, int64_t* histograms,
+                         const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_boxsize_stats* stats,
+                         double* v_x, double* v_y, double* speed, double* net_remodelling);
+int vof_vary_boxsize_host(vof_ctx* ctx, const double* movie, int n_frames, const int32_t* box_sizes, int n_boxes,
+                          double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                          const double* blur_weights, int blur_radius,
+                          const double* histogram_edges, int histogram_bins, int64_t* histograms,
+                          const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_boxsize_stats* stats,
+                          double* v_x, double* v_y, double* speed, double* net_remodelling);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

@@ -50,6 +50,11 @@ VARIATION_DTYPE = np.dtype([("speed_mean", np.float64), ("speed_variance", np.fl
                             ("converged_all", np.int32), ("max_iterations_used", np.int32), ("reserved", np.int32)])
 assert VARIATION_DTYPE.itemsize == 80     # sizeof(vof_variation_stats)
 
+BOXSIZE_DTYPE = np.dtype([("speed_mean", np.float64), ("speed_variance", np.float64), ("remodelling_mean", np.float64),
+                          ("remodelling_variance", np.float64), ("nonfinite_count", np.int64), ("box_size", np.int32),
+                          ("reserved", np.int32)])
+assert BOXSIZE_DTYPE.itemsize == 48       # sizeof(vof_boxsize_stats)
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
@@ -77,6 +82,10 @@ SIGNATURES = {
     "vof_liu_shen_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "vof_liu_shen_host": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "vof_vary_regularisation_host": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "vof_vary_boxsize_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vof_vary_boxsize_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                        _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -347,6 +356,48 @@ class Solver:
                                                    _ptr(ra), ra.size, _ptr(w), 0 if w is None else w.size // 2, _ptr(out))
         self._check(rc, "vof_vary_regularisation_host")
         return out
+
+    def _vary_boxsize(self, fn, movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks, weights,
+                      histogram_edges, probe_locations, fields):
+        boxes = np.ascontiguousarray(box_sizes, dtype=np.int32).ravel()
+        P = max(int(n_frames) - 1, 0)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        edges = None if histogram_edges is None else np.ascontiguousarray(histogram_edges, dtype=np.float64).ravel()
+        bins = 0 if edges is None else edges.size - 1
+        hist = None if edges is None else np.zeros((boxes.size, bins), dtype=np.int64)
+        pij = None if probe_locations is None else np.ascontiguousarray(probe_locations, dtype=np.int32).reshape(-1, 2)
+        probes = None if pij is None else np.zeros((boxes.size, P, pij.shape[0]))
+        stats = np.zeros(boxes.size, dtype=BOXSIZE_DTYPE)
+        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), _ptr(boxes), boxes.size, float(delta_x), float(delta_t),
+                                   int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(w),
+                                   0 if w is None else w.size // 2, _ptr(edges), bins, _ptr(hist), _ptr(pij),
+                                   0 if pij is None else pij.shape[0], _ptr(probes), _ptr(stats), *[_ptr(f) for f in fields])
+        self._check(rc, fn)
+        return stats, hist, probes
+
+    def vary_boxsize_host(self, movie: np.ndarray, box_sizes, delta_x=1.0, delta_t=1.0, include_remodelling=False,
+                          reference_quirks=True, weights=None, histogram_edges=None, probe_locations=None, return_fields=False):
+        """The box-size sweep of the box flow of a host movie in one native call; returns ``(stats, histograms, probe_speeds,
+        fields)``: a BOXSIZE_DTYPE record per box, int64 ``(n_boxes, bins)`` counts or None, ``(n_boxes, T - 1, n_probes)``
+        speeds or None, and None or ``(v_x, v_y, speed, net_remodelling)`` of shape ``(n_boxes, T - 1, n_i, n_j)``
+        (``net_remodelling`` is None without ``include_remodelling``)."""
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        T, n_boxes = movie.shape[0], np.size(box_sizes)
+        fields = [None] * 4
+        if return_fields:               # net_remodelling only where it is computed
+            for f in range(4 if include_remodelling else 3):
+                fields[f] = np.empty((n_boxes, max(T - 1, 0), self.n_i, self.n_j))
+        out = self._vary_boxsize("vof_vary_boxsize_host", movie, T, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks,
+                                 weights, histogram_edges, probe_locations, fields)
+        return (*out, tuple(fields) if return_fields else None)
+
+    def vary_boxsize_dev(self, movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks, weights=None,
+                         histogram_edges=None, probe_locations=None, v_x=None, v_y=None, speed=None, net_remodelling=None):
+        """The same on device memory (torch tensors or raw pointers): ``movie`` and the optional field stacks
+        ``(n_boxes, n_frames - 1, n_i, n_j)``; returns ``(stats, histograms, probe_speeds)`` as host arrays."""
+        return self._vary_boxsize("vof_vary_boxsize_dev", movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling,
+                                  reference_quirks, weights, histogram_edges, probe_locations, [v_x, v_y, speed, net_remodelling])
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

@@ -11,6 +11,7 @@
 #include "vof_sweep0p.hpp"
 #include "vof_direct.hpp"
 #include "vof_boxflow.hpp"
+#include "vof_boxsweep.hpp"
 #include "vof_liushen.hpp"
 #include "../../include/vof.h"
 
@@ -107,6 +108,11 @@ struct vof_ctx {
     double* st_movie2 = nullptr;                                 // second frame buffer (upload of the next batch under the solve)
     double *blur_tmp = nullptr, *blur_w = nullptr, *blur_io = nullptr;   // Gaussian blur scratch (lazy)
     double* bf_scratch = nullptr;                                        // box flow, general path: derived planes + row sums (lazy)
+    double* bs_scratch = nullptr;                                        // box-size sweep: frames, derived planes, accumulators, chunk outputs (lazy)
+    size_t bs_planes = 0;                                                // planes of bs_scratch
+    bool bs_by_budget = false;                                           // bs_scratch was sized by the free memory, not by the request
+    char* bs_aux = nullptr;                                              // box-size sweep: edges, probe indices, counters, probe values (lazy)
+    size_t bs_aux_bytes = 0;
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
     bool ls_lds_set = false;                                             // Liu-Shen flow, fused kernel: dynamic LDS limit raised
     double* tex_tab = nullptr;                                           // synthetic-texture tables (lazy)
@@ -2740,18 +2746,19 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
     return rc_all;
 }
 
-int vof_blur_stack_dev(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius) {
-    if (!c) return -1;
-    if (!in || !out || !weights) { c->err = "NULL pointer"; return -1; }
-    if (n_frames < 1 || radius < 0 || radius > 4096) { c->err = "bad n_frames / radius"; return -1; }
-    HIPCHK(hipSetDevice(c->device));
-    size_t fs = frame_stride(c);
-    const int chunk = std::min(n_frames, 16);
+// workspace of the blur: one chunk of row-filtered frames and the taps
+static int blur_alloc(vof_ctx* c) {
     if (!c->blur_tmp) {
-        if (int rc = dev_alloc(c, &c->blur_tmp, (size_t)16 * fs)) return rc;
+        if (int rc = dev_alloc(c, &c->blur_tmp, (size_t)16 * frame_stride(c))) return rc;
         if (int rc = dev_alloc(c, &c->blur_w, (size_t)2 * 4096 + 1)) return rc;
     }
-    HIPCHK(hipMemcpyAsync(c->blur_w, weights, (size_t)(2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// n_frames device-resident frames with the taps already in c->blur_w, enqueued on the context's stream (out may alias in)
+static int blur_frames(vof_ctx* c, const double* in, double* out, int n_frames, int radius) {
+    size_t fs = frame_stride(c);
+    const int chunk = std::min(n_frames, 16);
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         int nf = std::min(chunk, n_frames - f0);
         dim3 g = grid2d(c->Ni, c->Nj, nf);
@@ -2760,6 +2767,17 @@ int vof_blur_stack_dev(vof_ctx* c, const double* in, double* out, int n_frames, 
         k_blur1d<1><<<g, blk2d, 0, c->stream>>>(c->blur_tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, c->blur_w, radius);
     }
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int vof_blur_stack_dev(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius) {
+    if (!c) return -1;
+    if (!in || !out || !weights) { c->err = "NULL pointer"; return -1; }
+    if (n_frames < 1 || radius < 0 || radius > 4096) { c->err = "bad n_frames / radius"; return -1; }
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = blur_alloc(c)) return rc;
+    HIPCHK(hipMemcpyAsync(c->blur_w, weights, (size_t)(2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = blur_frames(c, in, out, n_frames, radius)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -3451,6 +3469,263 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
     }
     if (!include_remodelling && net_remodelling) memset(net_remodelling, 0, (size_t)P * fb);
     return 0;
+}
+
+// ---- box-size sweep of the box flow (vary_boxsize; vof_boxsweep.hpp) ---------------------------------------------
+constexpr int BS_MAX_CHUNK = 32;          // pairs per launch (grid z) at most; more adds nothing once the chip is full
+
+struct SweepReq {
+    const double* movie; int n_frames;
+    const int32_t* boxes; int n_boxes;
+    double delta_x, delta_t; int remodel, quirks;
+    const double* blur_w; int blur_r;
+    const double* edges; int bins; int64_t* hist;
+    const int32_t* probe_ij; int n_probes; double* probe_out;
+    vof_boxsize_stats* stats;
+    double* outs[4];                      // v_x, v_y, speed, net_remodelling: all NULL = stats only
+    bool host;                            // movie and outs are host memory
+};
+
+static int vary_boxsize_check(vof_ctx* c, const SweepReq& r) {
+    if (!r.movie) { c->err = "movie is NULL"; return -1; }
+    if (!r.stats) { c->err = "stats is NULL"; return -1; }
+    if (r.n_frames < 2) { c->err = "need at least two frames"; return -1; }
+    if (!r.boxes || r.n_boxes < 1) { c->err = "the list of box sizes is empty"; return -1; }
+    for (int b = 0; b < r.n_boxes; ++b)
+        if (r.boxes[b] < 1) { c->err = "every box size must be >= 1"; return -1; }
+    if (r.delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
+    if (r.blur_w && (r.blur_r < 0 || r.blur_r > 4096)) { c->err = "bad blur_radius"; return -1; }
+    if (r.edges && (r.bins < 1 || !r.hist)) { c->err = "histogram_edges needs histogram_bins >= 1 and histograms"; return -1; }
+    if (r.edges && !(r.edges[r.bins] > r.edges[0])) { c->err = "histogram_edges must increase"; return -1; }
+    if (r.probe_ij) {
+        if (r.n_probes < 1 || !r.probe_out) { c->err = "probe_ij needs n_probes >= 1 and probe_speeds"; return -1; }
+        for (int l = 0; l < r.n_probes; ++l)
+            if (r.probe_ij[2 * l] < 0 || r.probe_ij[2 * l] >= c->Ni || r.probe_ij[2 * l + 1] < 0 || r.probe_ij[2 * l + 1] >= c->Nj) {
+                c->err = "probe outside the image"; return -1;
+            }
+    }
+    const bool any = r.outs[0] || r.outs[1] || r.outs[2] || r.outs[3];
+    if (any && (!r.outs[0] || !r.outs[1] || !r.outs[2])) { c->err = "v_x, v_y and speed must be given together (or all NULL)"; return -1; }
+    if (any && r.remodel && !r.outs[3]) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
+    return 0;
+}
+
+static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
+    if (!c) return -1;
+    if (int rc = vary_boxsize_check(c, r)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const int P = r.n_frames - 1, NQ = r.remodel ? 8 : 5;
+    const bool fields = r.outs[0] != nullptr;
+    // scratch planes: cap + 1 frames, and per pair 3 derived planes, R / C / W of every quantity and 4 chunk outputs
+    const size_t per_pair = 1 + 3 + 3 * (size_t)NQ + 4;
+    const int want = std::min(std::min(P, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
+    int cap = c->bs_planes ? (int)std::min<size_t>((c->bs_planes - 1) / per_pair, (size_t)want) : 0;
+    // a buffer the free memory sized is kept: asking again would free and re-allocate it at every call
+    if (cap < want && !(c->bs_by_budget && cap >= 1)) {
+        if (c->bs_scratch) { if (int rc = dev_free(c, c->bs_scratch)) return rc; }
+        c->bs_scratch = nullptr; c->bs_planes = 0;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        const size_t budget = (size_t)(0.8 * (double)free_b) / fb;
+        cap = budget > 1 ? (int)std::min<size_t>((budget - 1) / per_pair, (size_t)want) : 0;
+        if (cap < 1) {
+            c->err = "the box-size sweep does not fit into the free device memory (" + std::to_string(1 + per_pair) +
+                     " planes of n_i x n_j doubles for one pair)";
+            return -3;
+        }
+        if (int rc = dev_alloc(c, &c->bs_scratch, (1 + per_pair * cap) * fs)) return rc;
+        c->bs_planes = 1 + per_pair * cap;
+        c->bs_by_budget = cap < want;
+    }
+    double* frames = c->bs_scratch;
+    double* der = frames + (size_t)(cap + 1) * fs;
+    SweepArgs s{};
+    s.der = der; s.fs = fs; s.Ni = c->Ni; s.Nj = c->Nj;
+    s.R = der + (size_t)cap * 3 * fs;
+    s.C = s.R + (size_t)cap * NQ * fs;
+    s.W = s.C + (size_t)cap * NQ * fs;
+    double* chunk_out[4];
+    for (int f = 0; f < 4; ++f) chunk_out[f] = s.W + (size_t)cap * NQ * fs + (size_t)f * cap * fs;
+
+    // what the statistics kernels read and write: edges, probe indices, counters, probe values (kept on the context, grown on demand)
+    const size_t n_hist = r.edges ? (size_t)r.n_boxes * r.bins : 0, n_probe = r.probe_ij ? (size_t)r.n_boxes * P * r.n_probes : 0;
+    // moments: per field (speed, net_remodelling), pass, box and pair the three sums of k_sum3; then the partials of a chunk
+    const size_t n_mom = (size_t)r.n_boxes * P * 3, n_fields_mom = r.remodel ? 2 : 1;
+    const int mom_blk = (int)std::min<size_t>(256, std::max<size_t>(1, (fs + 4 * RBLK - 1) / (4 * RBLK)));
+    const size_t n_part = (size_t)cap * 3 * mom_blk;
+    const size_t aux_doubles = (r.edges ? r.bins + 1 : 0) + n_probe + 2 * n_fields_mom * n_mom + n_part;
+    const size_t aux_counters = (size_t)r.n_boxes + n_hist;
+    const size_t aux_bytes = (aux_doubles + aux_counters) * 8 + (r.probe_ij ? (size_t)2 * r.n_probes * sizeof(int32_t) : 0);
+    if (c->bs_aux_bytes < aux_bytes) {
+        if (int rc = dev_free(c, c->bs_aux)) return rc;
+        c->bs_aux = nullptr; c->bs_aux_bytes = 0;
+        if (int rc = dev_alloc(c, &c->bs_aux, aux_bytes)) return rc;
+        c->bs_aux_bytes = aux_bytes;
+    }
+    char* aux = c->bs_aux;
+    double* d_edges = (double*)aux;
+    double* d_probe = d_edges + (r.edges ? r.bins + 1 : 0);
+    double* d_mom = d_probe + n_probe;                    // [field][pass][box][pair][3]
+    double* d_part = d_mom + 2 * n_fields_mom * n_mom;
+    unsigned long long* d_bad = (unsigned long long*)(d_part + n_part);
+    unsigned long long* d_hist = d_bad + r.n_boxes;
+    int32_t* d_pij = (int32_t*)(d_hist + n_hist);
+    if (hipMemsetAsync(d_bad, 0, aux_counters * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
+    if (r.edges) if (int rc = h2d_bounced(c, d_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
+    if (r.probe_ij) if (int rc = h2d_bounced(c, d_pij, r.probe_ij, (size_t)2 * r.n_probes * sizeof(int32_t))) return rc;
+    if (r.blur_w) {
+        if (int rc = blur_alloc(c)) return rc;
+        if (int rc = h2d_bounced(c, c->blur_w, r.blur_w, (size_t)(2 * r.blur_r + 1) * sizeof(double))) return rc;
+    }
+
+    // the steps: a half width past the longer image side adds only zeros, so the chain ends there
+    const int h_stop = std::max(c->Ni, c->Nj);
+    std::vector<std::vector<int>> at_h;                 // list entries that map to each half width
+    for (int b = 0; b < r.n_boxes; ++b) {
+        const int h = std::min(r.boxes[b] / 2, h_stop);
+        if ((int)at_h.size() <= h) at_h.resize((size_t)h + 1);
+        at_h[h].push_back(b);
+    }
+    const int h_max = (int)at_h.size() - 1;
+    // the two-pass reduction of vof_field_moments_dev per pair, enqueued behind the box's kernels: no host round trip in the sweep
+    auto pair_moments = [&](const double* x, int field, int b, int k0, int np) {
+        const dim3 gm(mom_blk, np);
+        double* first = d_mom + ((size_t)(2 * field) * r.n_boxes * P + (size_t)b * P + k0) * 3;
+        double* second = first + n_mom;
+        Prof prof(c, VOF_K_REDUCE, 0, 16.0 * fs);
+        k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, nullptr, d_part);
+        k_sum3<<<np, 64, 0, c->stream>>>(d_part, mom_blk, first);
+        k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, first, d_part);
+        k_sum3<<<np, 64, 0, c->stream>>>(d_part, mom_blk, second);
+    };
+    BoxArgs a{};
+    a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj;
+    a.cend = r.quirks ? std::min(c->Ni, c->Nj) : c->Nj;      // OF.py:108 clamps the column window with N_i
+    a.quirks = r.quirks ? 1 : 0;
+    a.scale = r.delta_x / r.delta_t;
+
+    for (int k0 = 0; k0 < P; k0 += cap) {
+        const int np = std::min(cap, P - k0);
+        const dim3 g = grid2d(c->Ni, c->Nj, np);
+        const double* chunk_frames = r.movie + (size_t)k0 * fs;
+        if (r.host) {
+            if (int rc = h2d_bounced(c, frames, chunk_frames, (size_t)(np + 1) * fb)) return rc;
+            chunk_frames = frames;
+        }
+        if (r.blur_w) {
+            if (int rc = blur_frames(c, chunk_frames, frames, np + 1, r.blur_r)) return rc;
+            chunk_frames = frames;
+        }
+        c->cur_units = np;
+        a.movie = chunk_frames;
+        { Prof prof(c, VOF_K_RHS, 0);
+          k_bf_derived<<<g, blk2d, 0, c->stream>>>(a, der);
+          if (r.remodel) k_bs_init<true><<<g, blk2d, 0, c->stream>>>(s);
+          else k_bs_init<false><<<g, blk2d, 0, c->stream>>>(s); }
+        for (int h = 0; h <= h_max; ++h) {
+            s.h = h;
+            a.h = h;
+            bool stepped = h == 0;
+            if (h >= 1) {
+                Prof prof(c, VOF_K_RHS, 0);
+                if (r.remodel) k_bs_grow<true><<<g, blk2d, 0, c->stream>>>(s);
+                else k_bs_grow<false><<<g, blk2d, 0, c->stream>>>(s);
+                if (at_h[h].empty()) {
+                    if (r.remodel) k_bs_window<true, true, false><<<g, blk2d, 0, c->stream>>>(s, a);
+                    else k_bs_window<false, true, false><<<g, blk2d, 0, c->stream>>>(s, a);
+                }
+            }
+            for (int b : at_h[h]) {
+                a.n_box = (double)r.boxes[b] * (double)r.boxes[b];
+                const size_t oo = ((size_t)b * P + k0) * fs;
+                double* dst[4];
+                for (int f = 0; f < 4; ++f) dst[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + oo : chunk_out[f];
+                const bool keep_v = fields, keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
+                a.vx = keep_v ? dst[0] : nullptr; a.vy = keep_v ? dst[1] : nullptr; a.speed = dst[2];
+                a.gamma = keep_g ? dst[3] : nullptr;
+                {
+                    Prof prof(c, VOF_K_RHS, 0);
+                    if (!stepped) {              // the first entry of this half width takes the step with it
+                        if (r.remodel) k_bs_window<true, true, true><<<g, blk2d, 0, c->stream>>>(s, a);
+                        else k_bs_window<false, true, true><<<g, blk2d, 0, c->stream>>>(s, a);
+                        stepped = true;
+                    } else {
+                        if (r.remodel) k_bs_window<true, false, true><<<g, blk2d, 0, c->stream>>>(s, a);
+                        else k_bs_window<false, false, true><<<g, blk2d, 0, c->stream>>>(s, a);
+                    }
+                    const size_t n = (size_t)np * fs;
+                    const int nb = (int)std::min<size_t>(1024, (n + 4 * 256 - 1) / (4 * 256));
+                    k_bs_counts<<<nb, 256, 0, c->stream>>>(a.speed, n, d_edges, r.edges ? r.bins : 0,
+                                                           r.edges ? d_hist + (size_t)b * r.bins : nullptr, d_bad + b);
+                    if (r.probe_ij) {
+                        const int nt = np * r.n_probes;
+                        k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(a.speed, fs, c->Nj, np, d_pij, r.n_probes,
+                                                                            d_probe + ((size_t)b * P + k0) * r.n_probes);
+                    }
+                }
+                pair_moments(a.speed, 0, b, k0, np);
+                if (r.remodel) pair_moments(a.gamma, 1, b, k0, np);
+                if (hipGetLastError() != hipSuccess) { c->err = "box-size sweep: launch failed"; return -2; }
+                if (fields && r.host)
+                    for (int f = 0; f < 4; ++f)
+                        if (r.outs[f] && (f < 3 || a.gamma))
+                            if (int rc = d2h_bounced(c, r.outs[f] + oo, dst[f], (size_t)np * fb)) return rc;
+            }
+        }
+    }
+    std::vector<unsigned long long> counters(aux_counters);
+    if (int rc = d2h_bounced(c, counters.data(), d_bad, aux_counters * 8)) return rc;
+    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, d_probe, n_probe * 8)) return rc;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
+    for (size_t t = 0; t < n_hist; ++t) r.hist[t] = (int64_t)counters[(size_t)r.n_boxes + t];
+    // pairs merged in order with Chan's formula; per pair the arithmetic of chunk_moments
+    std::vector<double> mom(2 * n_fields_mom * n_mom);
+    if (int rc = d2h_bounced(c, mom.data(), d_mom, mom.size() * 8)) return rc;
+    auto merged = [&](int field, int b) {
+        Moments acc;
+        const double* first = mom.data() + ((size_t)(2 * field) * r.n_boxes * P + (size_t)b * P) * 3;
+        const double* second = first + n_mom;
+        const double n = (double)fs;
+        for (int k = 0; k < P; ++k) {
+            double mean = first[3 * k] / n;
+            const double s0 = second[3 * k], s1 = second[3 * k + 1];
+            mean += s0 / n;                                         // first-order correction of the rounded mean
+            acc.merge(n, mean, s1 - s0 * s0 / n);
+        }
+        return acc;
+    };
+    for (int b = 0; b < r.n_boxes; ++b) {
+        vof_boxsize_stats& o = r.stats[b];
+        memset(&o, 0, sizeof o);
+        const Moments ms = merged(0, b);
+        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
+        if (r.remodel) { const Moments mr = merged(1, b); o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n; }
+        o.nonfinite_count = (int64_t)counters[b];
+        o.box_size = r.boxes[b];
+    }
+    return 0;
+}
+
+int vof_vary_boxsize_dev(vof_ctx* c, const double* movie, int n_frames, const int32_t* box_sizes, int n_boxes, double delta_x,
+                         double delta_t, int include_remodelling, int reference_quirks, const double* blur_weights, int blur_radius,
+                         const double* histogram_edges, int histogram_bins, int64_t* histograms, const int32_t* probe_ij, int n_probes,
+                         double* probe_speeds, vof_boxsize_stats* stats, double* v_x, double* v_y, double* speed, double* net_remodelling) {
+    return vary_boxsize_impl(c, SweepReq{movie, n_frames, box_sizes, n_boxes, delta_x, delta_t, include_remodelling, reference_quirks,
+                                         blur_weights, blur_radius, histogram_edges, histogram_bins, histograms, probe_ij, n_probes,
+                                         probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, false});
+}
+
+int vof_vary_boxsize_host(vof_ctx* c, const double* movie, int n_frames, const int32_t* box_sizes, int n_boxes, double delta_x,
+                          double delta_t, int include_remodelling, int reference_quirks, const double* blur_weights, int blur_radius,
+                          const double* histogram_edges, int histogram_bins, int64_t* histograms, const int32_t* probe_ij, int n_probes,
+                          double* probe_speeds, vof_boxsize_stats* stats, double* v_x, double* v_y, double* speed, double* net_remodelling) {
+    const int rc = vary_boxsize_impl(c, SweepReq{movie, n_frames, box_sizes, n_boxes, delta_x, delta_t, include_remodelling,
+                                                 reference_quirks, blur_weights, blur_radius, histogram_edges, histogram_bins, histograms,
+                                                 probe_ij, n_probes, probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, true});
+    if (!rc && !include_remodelling && net_remodelling)
+        memset(net_remodelling, 0, (size_t)n_boxes * (size_t)(n_frames - 1) * frame_stride(c) * sizeof(double));
+    return rc;
 }
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------

@@ -73,38 +73,43 @@ __device__ __forceinline__ double bf_window_count(int i, int j, int h, int Ni, i
     return (double)ri * (double)rj;
 }
 
-// S: the window sums in the order of bf_term.  Writes the pixel's results (OF.py:119-155 in the reference's operation order).
+// S: the window sums in the order of bf_term.  The pixel's unscaled results (OF.py:119-155 in the reference's operation order).
 template <bool REMODEL>
-__device__ __forceinline__ void bf_solve_store(const double* S, const BoxArgs& a, double n, size_t o) {
+__device__ __forceinline__ void bf_solve(const double* S, int quirks, double n, double& Vx, double& Vy, double& sp, double& g) {
 #pragma clang fp contract(off)
     if (!REMODEL) {
         const double A = S[0], B = S[1], C = S[2], s1 = S[3], s2 = S[4];
         const double det = A * C - B * B;
-        const double Vx = ((-C) * s1 + B * s2) / det;
-        const double Vy = ((-A) * s2 + B * s1) / det;
-        const double sp = __dsqrt_rn(Vx * Vx + Vy * Vy);
-        a.vx[o] = Vx * a.scale;
-        a.vy[o] = Vy * a.scale;
-        a.speed[o] = sp * a.scale;
-        if (a.gamma) a.gamma[o] = 0.0;
+        Vx = ((-C) * s1 + B * s2) / det;
+        Vy = ((-A) * s2 + B * s1) / det;
+        sp = __dsqrt_rn(Vx * Vx + Vy * Vy);
+        g = 0.0;
     } else {
         const double A = S[0], B = S[1], D = S[2], s1 = S[3], s2 = S[4], C = S[5], E = S[6], s3 = S[7];
         const double de = ((((n * A) * D - A * (E * E)) - n * (B * B)) - (C * C) * D) + ((2.0 * B) * C) * E;
-        double Vx = 0.0, Vy = 0.0, g = 0.0, sp = 0.0;
+        Vx = 0.0; Vy = 0.0; g = 0.0; sp = 0.0;
         if (de == 0.0) {
-            if (!a.quirks) { Vx = Vy = g = sp = __builtin_nan(""); }
+            if (!quirks) { Vx = Vy = g = sp = __builtin_nan(""); }
         } else {
             const double nBCE = n * B - C * E;
             Vx = (((E * E - n * D) * s1 + nBCE * s2) + (C * D - B * E) * s3) / de;
             Vy = ((nBCE * s1 + (C * C - n * A) * s2) + (A * E - B * C) * s3) / de;
             g = -((((B * E - C * D) * s1 + (B * C - A * E) * s2) + (A * D - B * B) * s3) / de);
-            if (!a.quirks) sp = __dsqrt_rn(Vx * Vx + Vy * Vy);
+            if (!quirks) sp = __dsqrt_rn(Vx * Vx + Vy * Vy);
         }
-        a.vx[o] = Vx * a.scale;
-        a.vy[o] = Vy * a.scale;
-        a.speed[o] = sp * a.scale;
-        a.gamma[o] = g;
     }
+}
+
+// Writes the pixel's results: v_x, v_y, speed in delta_x / delta_t units, net_remodelling unscaled.
+template <bool REMODEL>
+__device__ __forceinline__ void bf_solve_store(const double* S, const BoxArgs& a, double n, size_t o) {
+#pragma clang fp contract(off)
+    double Vx, Vy, sp, g;
+    bf_solve<REMODEL>(S, a.quirks, n, Vx, Vy, sp, g);
+    a.vx[o] = Vx * a.scale;
+    a.vy[o] = Vy * a.scale;
+    a.speed[o] = sp * a.scale;
+    if (REMODEL || a.gamma) a.gamma[o] = g;
 }
 
 // ---- fused kernel ---------------------------------------------------------------------------------------------
