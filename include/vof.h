@@ -142,6 +142,9 @@ int vof_default_params(vof_params* p, size_t struct_size);
  * Read at every vof_box_flow_dev / _host call:
  *   VOF_BOXFLOW_FUSED=0        box flow: the general three-kernel path through device scratch planes also for box sizes up to 31
  *                              (default: the fused LDS kernel k_boxflow_fused there); same window sums in another order
+ * Read at every blur (vof_blur_stack_dev / _host, and the blurs inside vof_vary_boxsize_* and vof_vary_blursize_*):
+ *   VOF_BLUR_TILED=0           the blur by k_blur1d, every tap from device memory, also for radii 1 .. 64 (default: the LDS-tiled
+ *                              k_blur1d_tiled there; larger radii always take k_blur1d); same bits
  * Read at every vof_liu_shen_dev / _host call:
  *   VOF_LIUSHEN_FUSE=k         Liu-Shen flow: k = 1 .. 8 Jacobi iterations per launch (default 4: the LDS kernel k_ls_fused);
  *                              1: one iteration per launch from and to device memory (k_ls_step).  Same bits for every k
@@ -290,6 +293,48 @@ int vof_vary_boxsize_host(vof_ctx* ctx, const double* movie, int n_frames, const
                           const double* histogram_edges, int histogram_bins, int64_t* histograms,
                           const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_boxsize_stats* stats,
                           double* v_x, double* v_y, double* speed, double* net_remodelling);
+
+/* Summary of one blur size of vary_blursize. */
+typedef struct vof_blursize_stats {
+    double speed_mean, speed_variance;             /* np.mean / np.var of the sigma's speed stack; NaN propagates as in numpy */
+    double remodelling_mean, remodelling_variance; /* ... of net_remodelling; 0 without include_remodelling */
+    int64_t nonfinite_count;                       /* NaN / Inf values in the speed stack */
+    int32_t sigma_index;                           /* s, the position in the list, echoed */
+    int32_t reserved;
+} vof_blursize_stats;
+
+/* The blur sweep the reference's scripts run around conduct_optical_flow (compare_rho_and_actin.py:485-614, and 120-196 for the
+ * intensity histogram): for each of the n_sigmas >= 1 tap vectors (blur_weights: 2 * blur_radii[s] + 1 taps as for
+ * vof_blur_stack_*, concatenated in list order; any order, duplicates allowed) the movie is blurred and what vof_box_flow_*
+ * computes for box_size from the blurred frames is reduced, in one call.  The movie is uploaded once; per entry all frames are
+ * blurred into a scratch stack of the context, the box flow runs with the kernels and the fused / general choice of
+ * vof_box_flow_dev (same bits), for pairs in chunks sized as in vof_vary_boxsize_*.  The results of an entry do not depend on
+ * the other entries of the list.
+ * stats: n_sigmas records, host memory, required.  Mean / variance are two-pass reductions on the device.
+ * histogram_edges / histogram_bins / histograms: as for vof_vary_boxsize_* (n_sigmas x histogram_bins int64).
+ * angle_bins: 0, or 1 .. 128 bins of the flow direction a = acos(v_y / speed) * sign(v_x) / pi (float64, sign(0) = 0) on (-1, 1):
+ *   angle_histograms (host, n_sigmas x angle_bins int64) receives np.histogram(a, angle_bins, (-1, 1))[0] and
+ *   weighted_angle_histograms (host, n_sigmas x angle_bins float64) np.histogram(a, angle_bins, (-1, 1), weights=speed)[0].
+ *   A sample whose speed is not finite counts in neither; NaN directions are dropped.  The weighted sums are deterministic:
+ *   a fixed-shape reduction per pair, the pairs added in pair order on the host; no floating-point atomics.
+ * intensity_edges: NULL, or the intensity_bins + 1 edges of np.linspace in host memory; intensity_histograms (host, n_sigmas x
+ *   intensity_bins int64) then receives np.histogram of the whole blurred stack (n_frames frames) of every entry.
+ * probe_ij / probe_speeds, v_x .. net_remodelling ((n_sigmas, n_frames - 1, n_i, n_j), or NULL: no full-size field stack exists
+ *   anywhere), _dev / _host: as for vof_vary_boxsize_*. */
+int vof_vary_blursize_dev(vof_ctx* ctx, const double* movie, int n_frames, const double* blur_weights, const int32_t* blur_radii,
+                          int n_sigmas, int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                          const double* histogram_edges, int histogram_bins, int64_t* histograms,
+                          int angle_bins, int64_t* angle_histograms, double* weighted_angle_histograms,
+                          const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
+                          const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats,
+                          double* v_x, double* v_y, double* speed, double* net_remodelling);
+int vof_vary_blursize_host(vof_ctx* ctx, const double* movie, int n_frames, const double* blur_weights, const int32_t* blur_radii,
+                           int n_sigmas, int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                           const double* histogram_edges, int histogram_bins, int64_t* histograms,
+                           int angle_bins, int64_t* angle_histograms, double* weighted_angle_histograms,
+                           const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
+                           const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats,
+                           double* v_x, double* v_y, double* speed, double* net_remodelling);
 
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);

@@ -55,6 +55,11 @@ BOXSIZE_DTYPE = np.dtype([("speed_mean", np.float64), ("speed_variance", np.floa
                           ("reserved", np.int32)])
 assert BOXSIZE_DTYPE.itemsize == 48       # sizeof(vof_boxsize_stats)
 
+BLURSIZE_DTYPE = np.dtype([("speed_mean", np.float64), ("speed_variance", np.float64), ("remodelling_mean", np.float64),
+                           ("remodelling_variance", np.float64), ("nonfinite_count", np.int64), ("sigma_index", np.int32),
+                           ("reserved", np.int32)])
+assert BLURSIZE_DTYPE.itemsize == 48      # sizeof(vof_blursize_stats)
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
@@ -86,6 +91,10 @@ SIGNATURES = {
                                        _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vof_vary_boxsize_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                         _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vof_vary_blursize_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp,
+                                        C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vof_vary_blursize_host": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp,
+                                         C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -398,6 +407,59 @@ class Solver:
         ``(n_boxes, n_frames - 1, n_i, n_j)``; returns ``(stats, histograms, probe_speeds)`` as host arrays."""
         return self._vary_boxsize("vof_vary_boxsize_dev", movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling,
                                   reference_quirks, weights, histogram_edges, probe_locations, [v_x, v_y, speed, net_remodelling])
+
+    def _vary_blursize(self, fn, movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
+                       histogram_edges, angle_bins, intensity_edges, probe_locations, fields):
+        taps = [np.ascontiguousarray(t, dtype=np.float64).ravel() for t in taps]
+        n, P = len(taps), max(int(n_frames) - 1, 0)
+        radii = np.array([t.size // 2 for t in taps], dtype=np.int32)
+        weights = np.concatenate(taps) if taps else np.zeros(0)
+        edges = None if histogram_edges is None else np.ascontiguousarray(histogram_edges, dtype=np.float64).ravel()
+        bins = 0 if edges is None else edges.size - 1
+        iedges = None if intensity_edges is None else np.ascontiguousarray(intensity_edges, dtype=np.float64).ravel()
+        ibins = 0 if iedges is None else iedges.size - 1
+        abins = int(angle_bins or 0)
+        hist = None if edges is None else np.zeros((n, bins), dtype=np.int64)
+        ihist = None if iedges is None else np.zeros((n, ibins), dtype=np.int64)
+        ahist = np.zeros((n, abins), dtype=np.int64) if abins else None
+        awhist = np.zeros((n, abins)) if abins else None
+        pij = None if probe_locations is None else np.ascontiguousarray(probe_locations, dtype=np.int32).reshape(-1, 2)
+        probes = None if pij is None else np.zeros((n, P, pij.shape[0]))
+        stats = np.zeros(n, dtype=BLURSIZE_DTYPE)
+        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), _ptr(weights), _ptr(radii), n, int(box_size), float(delta_x),
+                                   float(delta_t), int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(edges), bins,
+                                   _ptr(hist), abins, _ptr(ahist), _ptr(awhist), _ptr(iedges), ibins, _ptr(ihist), _ptr(pij),
+                                   0 if pij is None else pij.shape[0], _ptr(probes), _ptr(stats), *[_ptr(f) for f in fields])
+        self._check(rc, fn)
+        return stats, hist, ahist, awhist, ihist, probes
+
+    def vary_blursize_host(self, movie: np.ndarray, taps, box_size, delta_x=1.0, delta_t=1.0, include_remodelling=False,
+                           reference_quirks=True, histogram_edges=None, angle_bins=None, intensity_edges=None, probe_locations=None,
+                           return_fields=False):
+        """The blur sweep of the box flow of a host movie in one native call; ``taps`` is a list of tap vectors (one blur
+        each).  Returns ``(stats, histograms, angle_histograms, weighted_angle_histograms, intensity_histograms, probe_speeds,
+        fields)``: a BLURSIZE_DTYPE record per blur, the histograms ``(n, bins)`` or None where not asked for,
+        ``(n, T - 1, n_probes)`` speeds or None, and None or ``(v_x, v_y, speed, net_remodelling)`` of shape
+        ``(n, T - 1, n_i, n_j)`` (``net_remodelling`` is None without ``include_remodelling``)."""
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        T = movie.shape[0]
+        fields = [None] * 4
+        if return_fields:               # net_remodelling only where it is computed
+            for f in range(4 if include_remodelling else 3):
+                fields[f] = np.empty((len(taps), max(T - 1, 0), self.n_i, self.n_j))
+        out = self._vary_blursize("vof_vary_blursize_host", movie, T, taps, box_size, delta_x, delta_t, include_remodelling,
+                                  reference_quirks, histogram_edges, angle_bins, intensity_edges, probe_locations, fields)
+        return (*out, tuple(fields) if return_fields else None)
+
+    def vary_blursize_dev(self, movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
+                          histogram_edges=None, angle_bins=None, intensity_edges=None, probe_locations=None, v_x=None, v_y=None,
+                          speed=None, net_remodelling=None):
+        """The same on device memory (torch tensors or raw pointers): ``movie`` and the optional field stacks
+        ``(n, n_frames - 1, n_i, n_j)``; returns the six summaries as host arrays."""
+        return self._vary_blursize("vof_vary_blursize_dev", movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling,
+                                   reference_quirks, histogram_edges, angle_bins, intensity_edges, probe_locations,
+                                   [v_x, v_y, speed, net_remodelling])
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

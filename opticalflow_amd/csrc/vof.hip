@@ -12,6 +12,7 @@
 #include "vof_direct.hpp"
 #include "vof_boxflow.hpp"
 #include "vof_boxsweep.hpp"
+#include "vof_blursweep.hpp"
 #include "vof_liushen.hpp"
 #include "../../include/vof.h"
 
@@ -111,9 +112,12 @@ struct vof_ctx {
     double* bs_scratch = nullptr;                                        // box-size sweep: frames, derived planes, accumulators, chunk outputs (lazy)
     size_t bs_planes = 0;                                                // planes of bs_scratch
     bool bs_by_budget = false;                                           // bs_scratch was sized by the free memory, not by the request
-    char* bs_aux = nullptr;                                              // box-size sweep: edges, probe indices, counters, probe values (lazy)
+    char* bs_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
     size_t bs_aux_bytes = 0;
+    double* bz_scratch = nullptr;                                        // blur sweep: movie (_host), blurred stack, chunk outputs (lazy)
+    size_t bz_planes = 0;                                                // planes of bz_scratch
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
+    bool bl_lds_set = false;                                             // tiled blur: dynamic LDS limit raised
     bool ls_lds_set = false;                                             // Liu-Shen flow, fused kernel: dynamic LDS limit raised
     double* tex_tab = nullptr;                                           // synthetic-texture tables (lazy)
     size_t tex_cap = 0;
@@ -2755,16 +2759,29 @@ static int blur_alloc(vof_ctx* c) {
     return 0;
 }
 
-// n_frames device-resident frames with the taps already in c->blur_w, enqueued on the context's stream (out may alias in)
-static int blur_frames(vof_ctx* c, const double* in, double* out, int n_frames, int radius) {
+// n_frames device-resident frames with the taps already on the device at w (c->blur_w, or the sweep's own copy), enqueued on
+// the context's stream (out may alias in).  Radii BL_RMIN .. BL_RMAX take the LDS-tiled kernels, same bits as k_blur1d.
+static int blur_frames(vof_ctx* c, const double* in, double* out, int n_frames, int radius, const double* w) {
     size_t fs = frame_stride(c);
     const int chunk = std::min(n_frames, 16);
+    bool tiled = radius >= BL_RMIN && radius <= BL_RMAX;
+    if (const char* e = getenv("VOF_BLUR_TILED")) tiled = tiled && e[0] != '0';
+    if (tiled && !c->bl_lds_set) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_blur1d_tiled<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blur_tiled_lds(0, BL_RMAX)));
+        c->bl_lds_set = true;
+    }
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         int nf = std::min(chunk, n_frames - f0);
-        dim3 g = grid2d(c->Ni, c->Nj, nf);
         Prof p(c, VOF_K_RHS, 0);
-        k_blur1d<0><<<g, blk2d, 0, c->stream>>>(in + (size_t)f0 * fs, c->blur_tmp, c->Ni, c->Nj, c->blur_w, radius);
-        k_blur1d<1><<<g, blk2d, 0, c->stream>>>(c->blur_tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, c->blur_w, radius);
+        if (tiled) {
+            const dim3 g0((c->Nj + BX - 1) / BX, (c->Ni + BL_TI - 1) / BL_TI, nf), g1(g0.x, (c->Ni + BL_TR - 1) / BL_TR, nf);
+            k_blur1d_tiled<0><<<g0, blk2d, blur_tiled_lds(0, radius), c->stream>>>(in + (size_t)f0 * fs, c->blur_tmp, c->Ni, c->Nj, w, radius);
+            k_blur1d_tiled<1><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(c->blur_tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
+        } else {
+            dim3 g = grid2d(c->Ni, c->Nj, nf);
+            k_blur1d<0><<<g, blk2d, 0, c->stream>>>(in + (size_t)f0 * fs, c->blur_tmp, c->Ni, c->Nj, w, radius);
+            k_blur1d<1><<<g, blk2d, 0, c->stream>>>(c->blur_tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
+        }
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -2777,7 +2794,7 @@ int vof_blur_stack_dev(vof_ctx* c, const double* in, double* out, int n_frames, 
     HIPCHK(hipSetDevice(c->device));
     if (int rc = blur_alloc(c)) return rc;
     HIPCHK(hipMemcpyAsync(c->blur_w, weights, (size_t)(2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (int rc = blur_frames(c, in, out, n_frames, radius)) return rc;
+    if (int rc = blur_frames(c, in, out, n_frames, radius, c->blur_w)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -3474,6 +3491,43 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
 // ---- box-size sweep of the box flow (vary_boxsize; vof_boxsweep.hpp) ---------------------------------------------
 constexpr int BS_MAX_CHUNK = 32;          // pairs per launch (grid z) at most; more adds nothing once the chip is full
 
+// Mean and variance of a field per list entry, shared by the box-size and the blur sweep: the two-pass reduction of
+// vof_field_moments_dev per pair on the device, sums [field][pass][entry][pair][3]; a pair is the unit the host merges.
+struct PairMoments {
+    double* d_mom; double* d_part;        // device: the sums; the partials of one chunk
+    size_t n_mom;                         // n_entries * P * 3
+    int n_entries, P, mom_blk;
+};
+
+inline int pair_moments_blocks(size_t fs) { return (int)std::min<size_t>(256, std::max<size_t>(1, (fs + 4 * RBLK - 1) / (4 * RBLK))); }
+
+// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote x: no host round trip in a sweep
+static void pair_moments_enqueue(vof_ctx* c, const PairMoments& m, const double* x, size_t fs, int field, int b, int k0, int np) {
+    const dim3 gm(m.mom_blk, np);
+    double* first = m.d_mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P + k0) * 3;
+    double* second = first + m.n_mom;
+    Prof prof(c, VOF_K_REDUCE, 0, 16.0 * fs);
+    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, nullptr, m.d_part);
+    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, first);
+    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, first, m.d_part);
+    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, second);
+}
+
+// mom: the host copy of d_mom.  Pairs merged in order with Chan's formula; per pair the arithmetic of chunk_moments
+static Moments pair_moments_merged(const PairMoments& m, const double* mom, size_t fs, int field, int b) {
+    Moments acc;
+    const double* first = mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P) * 3;
+    const double* second = first + m.n_mom;
+    const double n = (double)fs;
+    for (int k = 0; k < m.P; ++k) {
+        double mean = first[3 * k] / n;
+        const double s0 = second[3 * k], s1 = second[3 * k + 1];
+        mean += s0 / n;                                         // first-order correction of the rounded mean
+        acc.merge(n, mean, s1 - s0 * s0 / n);
+    }
+    return acc;
+}
+
 struct SweepReq {
     const double* movie; int n_frames;
     const int32_t* boxes; int n_boxes;
@@ -3552,7 +3606,7 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     const size_t n_hist = r.edges ? (size_t)r.n_boxes * r.bins : 0, n_probe = r.probe_ij ? (size_t)r.n_boxes * P * r.n_probes : 0;
     // moments: per field (speed, net_remodelling), pass, box and pair the three sums of k_sum3; then the partials of a chunk
     const size_t n_mom = (size_t)r.n_boxes * P * 3, n_fields_mom = r.remodel ? 2 : 1;
-    const int mom_blk = (int)std::min<size_t>(256, std::max<size_t>(1, (fs + 4 * RBLK - 1) / (4 * RBLK)));
+    const int mom_blk = pair_moments_blocks(fs);
     const size_t n_part = (size_t)cap * 3 * mom_blk;
     const size_t aux_doubles = (r.edges ? r.bins + 1 : 0) + n_probe + 2 * n_fields_mom * n_mom + n_part;
     const size_t aux_counters = (size_t)r.n_boxes + n_hist;
@@ -3588,17 +3642,7 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
         at_h[h].push_back(b);
     }
     const int h_max = (int)at_h.size() - 1;
-    // the two-pass reduction of vof_field_moments_dev per pair, enqueued behind the box's kernels: no host round trip in the sweep
-    auto pair_moments = [&](const double* x, int field, int b, int k0, int np) {
-        const dim3 gm(mom_blk, np);
-        double* first = d_mom + ((size_t)(2 * field) * r.n_boxes * P + (size_t)b * P + k0) * 3;
-        double* second = first + n_mom;
-        Prof prof(c, VOF_K_REDUCE, 0, 16.0 * fs);
-        k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, nullptr, d_part);
-        k_sum3<<<np, 64, 0, c->stream>>>(d_part, mom_blk, first);
-        k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, first, d_part);
-        k_sum3<<<np, 64, 0, c->stream>>>(d_part, mom_blk, second);
-    };
+    const PairMoments pm{d_mom, d_part, n_mom, r.n_boxes, P, mom_blk};
     BoxArgs a{};
     a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj;
     a.cend = r.quirks ? std::min(c->Ni, c->Nj) : c->Nj;      // OF.py:108 clamps the column window with N_i
@@ -3614,7 +3658,7 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
             chunk_frames = frames;
         }
         if (r.blur_w) {
-            if (int rc = blur_frames(c, chunk_frames, frames, np + 1, r.blur_r)) return rc;
+            if (int rc = blur_frames(c, chunk_frames, frames, np + 1, r.blur_r, c->blur_w)) return rc;
             chunk_frames = frames;
         }
         c->cur_units = np;
@@ -3664,8 +3708,8 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
                                                                             d_probe + ((size_t)b * P + k0) * r.n_probes);
                     }
                 }
-                pair_moments(a.speed, 0, b, k0, np);
-                if (r.remodel) pair_moments(a.gamma, 1, b, k0, np);
+                pair_moments_enqueue(c, pm, a.speed, fs, 0, b, k0, np);
+                if (r.remodel) pair_moments_enqueue(c, pm, a.gamma, fs, 1, b, k0, np);
                 if (hipGetLastError() != hipSuccess) { c->err = "box-size sweep: launch failed"; return -2; }
                 if (fields && r.host)
                     for (int f = 0; f < 4; ++f)
@@ -3679,28 +3723,14 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, d_probe, n_probe * 8)) return rc;
     if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
     for (size_t t = 0; t < n_hist; ++t) r.hist[t] = (int64_t)counters[(size_t)r.n_boxes + t];
-    // pairs merged in order with Chan's formula; per pair the arithmetic of chunk_moments
     std::vector<double> mom(2 * n_fields_mom * n_mom);
     if (int rc = d2h_bounced(c, mom.data(), d_mom, mom.size() * 8)) return rc;
-    auto merged = [&](int field, int b) {
-        Moments acc;
-        const double* first = mom.data() + ((size_t)(2 * field) * r.n_boxes * P + (size_t)b * P) * 3;
-        const double* second = first + n_mom;
-        const double n = (double)fs;
-        for (int k = 0; k < P; ++k) {
-            double mean = first[3 * k] / n;
-            const double s0 = second[3 * k], s1 = second[3 * k + 1];
-            mean += s0 / n;                                         // first-order correction of the rounded mean
-            acc.merge(n, mean, s1 - s0 * s0 / n);
-        }
-        return acc;
-    };
     for (int b = 0; b < r.n_boxes; ++b) {
         vof_boxsize_stats& o = r.stats[b];
         memset(&o, 0, sizeof o);
-        const Moments ms = merged(0, b);
+        const Moments ms = pair_moments_merged(pm, mom.data(), fs, 0, b);
         o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
-        if (r.remodel) { const Moments mr = merged(1, b); o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n; }
+        if (r.remodel) { const Moments mr = pair_moments_merged(pm, mom.data(), fs, 1, b); o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n; }
         o.nonfinite_count = (int64_t)counters[b];
         o.box_size = r.boxes[b];
     }
@@ -3725,6 +3755,224 @@ int vof_vary_boxsize_host(vof_ctx* c, const double* movie, int n_frames, const i
                                                  probe_ij, n_probes, probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, true});
     if (!rc && !include_remodelling && net_remodelling)
         memset(net_remodelling, 0, (size_t)n_boxes * (size_t)(n_frames - 1) * frame_stride(c) * sizeof(double));
+    return rc;
+}
+
+// ---- blur sweep of the box flow (vary_blursize; vof_blursweep.hpp) -------------------------------------------------
+struct BlurSweepReq {
+    const double* movie; int n_frames;
+    const double* taps; const int32_t* radii; int n_sigmas;     // the tap vectors (2 radii[s] + 1 each), concatenated
+    int box_size; double delta_x, delta_t; int remodel, quirks;
+    const double* edges; int bins; int64_t* hist;               // speed
+    int abins; int64_t* ahist; double* awhist;                  // flow direction: counts and speed-weighted sums
+    const double* iedges; int ibins; int64_t* ihist;            // intensity of the blurred stack
+    const int32_t* probe_ij; int n_probes; double* probe_out;
+    vof_blursize_stats* stats;
+    double* outs[4];                      // v_x, v_y, speed, net_remodelling: all NULL = stats only
+    bool host;                            // movie and outs are host memory
+};
+
+static int vary_blursize_check(vof_ctx* c, const BlurSweepReq& r) {
+    if (!r.movie) { c->err = "movie is NULL"; return -1; }
+    if (!r.stats) { c->err = "stats is NULL"; return -1; }
+    if (r.n_frames < 2) { c->err = "need at least two frames"; return -1; }
+    if (!r.taps || !r.radii || r.n_sigmas < 1) { c->err = "the list of blur sizes is empty"; return -1; }
+    for (int s = 0; s < r.n_sigmas; ++s)
+        if (r.radii[s] < 0 || r.radii[s] > 4096) { c->err = "bad blur radius"; return -1; }
+    if (r.box_size < 1) { c->err = "box_size must be >= 1"; return -1; }
+    if (r.delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
+    if (r.edges && (r.bins < 1 || !r.hist)) { c->err = "histogram_edges needs histogram_bins >= 1 and histograms"; return -1; }
+    if (r.edges && !(r.edges[r.bins] > r.edges[0])) { c->err = "histogram_edges must increase"; return -1; }
+    if (r.iedges && (r.ibins < 1 || !r.ihist)) { c->err = "intensity_edges needs intensity_bins >= 1 and intensity_histograms"; return -1; }
+    if (r.iedges && !(r.iedges[r.ibins] > r.iedges[0])) { c->err = "intensity_edges must increase"; return -1; }
+    if (r.abins < 0 || r.abins > BZ_MAX_ANGLE_BINS) { c->err = "angle_bins must be 0 .. " + std::to_string(BZ_MAX_ANGLE_BINS); return -1; }
+    if (r.abins && (!r.ahist || !r.awhist)) { c->err = "angle_bins needs angle_histograms and weighted_angle_histograms"; return -1; }
+    if (r.probe_ij) {
+        if (r.n_probes < 1 || !r.probe_out) { c->err = "probe_ij needs n_probes >= 1 and probe_speeds"; return -1; }
+        for (int l = 0; l < r.n_probes; ++l)
+            if (r.probe_ij[2 * l] < 0 || r.probe_ij[2 * l] >= c->Ni || r.probe_ij[2 * l + 1] < 0 || r.probe_ij[2 * l + 1] >= c->Nj) {
+                c->err = "probe outside the image"; return -1;
+            }
+    }
+    const bool any = r.outs[0] || r.outs[1] || r.outs[2] || r.outs[3];
+    if (any && (!r.outs[0] || !r.outs[1] || !r.outs[2])) { c->err = "v_x, v_y and speed must be given together (or all NULL)"; return -1; }
+    if (any && r.remodel && !r.outs[3]) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
+    return 0;
+}
+
+static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
+    if (!c) return -1;
+    if (int rc = vary_blursize_check(c, r)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const int T = r.n_frames, P = T - 1, n = r.n_sigmas;
+    const bool fields = r.outs[0] != nullptr;
+    // scratch planes: the movie (_host), the blurred stack, and four chunk outputs per pair in flight (chunks as vary_boxsize)
+    const size_t base = (size_t)(r.host ? 2 : 1) * T;
+    const int want = std::min(std::min(P, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
+    int cap = c->bz_planes > base ? (int)std::min<size_t>((c->bz_planes - base) / 4, (size_t)want) : 0;
+    if (cap < want) {
+        if (int rc = dev_free(c, c->bz_scratch)) return rc;
+        c->bz_scratch = nullptr; c->bz_planes = 0;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        const size_t budget = (size_t)(0.8 * (double)free_b) / fb;
+        cap = budget > base ? (int)std::min<size_t>((budget - base) / 4, (size_t)want) : 0;
+        if (cap < 1) {
+            c->err = "the blur sweep does not fit into the free device memory (" + std::to_string(base + 4) + " planes of n_i x n_j doubles)";
+            return -3;
+        }
+        if (int rc = dev_alloc(c, &c->bz_scratch, (base + 4 * (size_t)cap) * fs)) return rc;
+        c->bz_planes = base + 4 * (size_t)cap;
+    }
+    double* blurred = c->bz_scratch;
+    double* chunk_out[4];
+    for (int f = 0; f < 4; ++f) chunk_out[f] = blurred + ((size_t)T + (size_t)f * cap) * fs;
+    const double* movie = r.movie;
+    if (r.host) {                                            // the movie goes up once
+        double* up = blurred + ((size_t)T + 4 * (size_t)cap) * fs;
+        if (int rc = h2d_bounced(c, up, r.movie, (size_t)T * fb)) return rc;
+        movie = up;
+    }
+    if (int rc = blur_alloc(c)) return rc;
+
+    // what the kernels read and the statistics they write (kept on the context, grown on demand): 8-byte items, then the probe indices
+    std::vector<size_t> tap_at(n);
+    size_t n_taps = 0;
+    for (int s = 0; s < n; ++s) { tap_at[s] = n_taps; n_taps += 2 * (size_t)r.radii[s] + 1; }
+    const size_t n_hist = r.edges ? (size_t)n * r.bins : 0, n_ahist = (size_t)n * r.abins, n_ihist = r.iedges ? (size_t)n * r.ibins : 0;
+    const size_t n_probe = r.probe_ij ? (size_t)n * P * r.n_probes : 0, n_awsum = (size_t)n * P * r.abins;
+    const size_t n_mom = (size_t)n * P * 3, n_fields_mom = r.remodel ? 2 : 1;
+    const int mom_blk = pair_moments_blocks(fs);
+    const int ang_blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));   // by the plane size only
+    size_t items = 0;
+    auto take = [&](size_t k) { const size_t at = items; items += k; return at; };
+    const size_t at_taps = take(n_taps), at_edges = take(r.edges ? r.bins + 1 : 0), at_aedges = take(r.abins ? r.abins + 1 : 0),
+                 at_iedges = take(r.iedges ? r.ibins + 1 : 0), at_probe = take(n_probe), at_mom = take(2 * n_fields_mom * n_mom),
+                 at_part = take((size_t)cap * 3 * mom_blk), at_awsum = take(n_awsum), at_apart = take((size_t)cap * ang_blk * r.abins),
+                 at_counters = take(0);
+    const size_t at_bad = take(n), at_hist = take(n_hist), at_ahist = take(n_ahist), at_ihist = take(n_ihist), at_ibad = take(1);
+    const size_t n_counters = items - at_counters;
+    const size_t aux_bytes = items * 8 + (r.probe_ij ? (size_t)2 * r.n_probes * sizeof(int32_t) : 0);
+    if (c->bs_aux_bytes < aux_bytes) {
+        if (int rc = dev_free(c, c->bs_aux)) return rc;
+        c->bs_aux = nullptr; c->bs_aux_bytes = 0;
+        if (int rc = dev_alloc(c, &c->bs_aux, aux_bytes)) return rc;
+        c->bs_aux_bytes = aux_bytes;
+    }
+    double* const ad = (double*)c->bs_aux;
+    unsigned long long* const au = (unsigned long long*)c->bs_aux;
+    int32_t* d_pij = (int32_t*)(ad + items);
+    if (hipMemsetAsync(au + at_counters, 0, n_counters * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
+    if (int rc = h2d_bounced(c, ad + at_taps, r.taps, n_taps * 8)) return rc;
+    if (r.edges) if (int rc = h2d_bounced(c, ad + at_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
+    if (r.iedges) if (int rc = h2d_bounced(c, ad + at_iedges, r.iedges, (size_t)(r.ibins + 1) * 8)) return rc;
+    if (r.abins) {                         // np.linspace(-1, 1, bins + 1): i * step + start, the last one the stop itself
+        std::vector<double> e((size_t)r.abins + 1);
+        const volatile double step = 2.0 / (double)r.abins;
+        for (int i = 0; i < r.abins; ++i) { const volatile double t = (double)i * step; e[i] = t + -1.0; }
+        e[r.abins] = 1.0;
+        if (int rc = h2d_bounced(c, ad + at_aedges, e.data(), e.size() * 8)) return rc;
+    }
+    if (r.probe_ij) if (int rc = h2d_bounced(c, d_pij, r.probe_ij, (size_t)2 * r.n_probes * sizeof(int32_t))) return rc;
+    const PairMoments pm{ad + at_mom, ad + at_part, n_mom, n, P, mom_blk};
+
+    for (int s = 0; s < n; ++s) {
+        if (int rc = blur_frames(c, movie, blurred, T, r.radii[s], ad + at_taps + tap_at[s])) return rc;
+        if (r.iedges) {
+            const size_t m = (size_t)T * fs;
+            const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
+            Prof prof(c, VOF_K_REDUCE, 0);
+            k_bs_counts<<<nb, 256, 0, c->stream>>>(blurred, m, ad + at_iedges, r.ibins, au + at_ihist + (size_t)s * r.ibins, au + at_ibad);
+        }
+        for (int k0 = 0; k0 < P; k0 += cap) {
+            const int np = std::min(cap, P - k0);
+            const size_t oo = ((size_t)s * P + k0) * fs;
+            double* dst[4];
+            for (int f = 0; f < 4; ++f) dst[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + oo : chunk_out[f];
+            const bool keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
+            // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
+            if (int rc = box_flow_pairs(c, blurred + (size_t)k0 * fs, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, dst[0], dst[1],
+                                        dst[2], keep_g ? dst[3] : nullptr)) return rc;
+            {
+                Prof prof(c, VOF_K_REDUCE, 0);
+                const size_t m = (size_t)np * fs;
+                const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
+                k_bs_counts<<<nb, 256, 0, c->stream>>>(dst[2], m, ad + at_edges, r.edges ? r.bins : 0,
+                                                       r.edges ? au + at_hist + (size_t)s * r.bins : nullptr, au + at_bad + s);
+                if (r.probe_ij) {
+                    const int nt = np * r.n_probes;
+                    k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(dst[2], fs, c->Nj, np, d_pij, r.n_probes,
+                                                                        ad + at_probe + ((size_t)s * P + k0) * r.n_probes);
+                }
+                if (r.abins) {
+                    k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
+                        dst[0], dst[1], dst[2], fs, ad + at_aedges, r.abins, au + at_ahist + (size_t)s * r.abins, ad + at_apart);
+                    const int nt = np * r.abins;
+                    k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_apart, ang_blk, r.abins, np,
+                                                                            ad + at_awsum + ((size_t)s * P + k0) * r.abins);
+                }
+            }
+            pair_moments_enqueue(c, pm, dst[2], fs, 0, s, k0, np);
+            if (r.remodel) pair_moments_enqueue(c, pm, dst[3], fs, 1, s, k0, np);
+            if (hipGetLastError() != hipSuccess) { c->err = "blur sweep: launch failed"; return -2; }
+            if (fields && r.host)
+                for (int f = 0; f < 4; ++f)
+                    if (r.outs[f] && (f < 3 || r.remodel))
+                        if (int rc = d2h_bounced(c, r.outs[f] + oo, dst[f], (size_t)np * fb)) return rc;
+        }
+    }
+    std::vector<unsigned long long> counters(n_counters);
+    if (int rc = d2h_bounced(c, counters.data(), au + at_counters, n_counters * 8)) return rc;
+    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, ad + at_probe, n_probe * 8)) return rc;
+    std::vector<double> mom(2 * n_fields_mom * n_mom), awsum(n_awsum);
+    if (int rc = d2h_bounced(c, mom.data(), ad + at_mom, mom.size() * 8)) return rc;
+    if (n_awsum) if (int rc = d2h_bounced(c, awsum.data(), ad + at_awsum, n_awsum * 8)) return rc;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
+    for (size_t t = 0; t < n_hist; ++t) r.hist[t] = (int64_t)counters[at_hist - at_counters + t];
+    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)counters[at_ahist - at_counters + t];
+    for (size_t t = 0; t < n_ihist; ++t) r.ihist[t] = (int64_t)counters[at_ihist - at_counters + t];
+    for (int s = 0; s < n; ++s) {
+        for (int b = 0; b < r.abins; ++b) {                  // the pairs' sums in pair order
+            double w = 0.0;
+            for (int k = 0; k < P; ++k) w += awsum[((size_t)s * P + k) * r.abins + b];
+            r.awhist[(size_t)s * r.abins + b] = w;
+        }
+        vof_blursize_stats& o = r.stats[s];
+        memset(&o, 0, sizeof o);
+        const Moments ms = pair_moments_merged(pm, mom.data(), fs, 0, s);
+        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
+        if (r.remodel) { const Moments mr = pair_moments_merged(pm, mom.data(), fs, 1, s); o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n; }
+        o.nonfinite_count = (int64_t)counters[at_bad - at_counters + s];
+        o.sigma_index = s;
+    }
+    return 0;
+}
+
+int vof_vary_blursize_dev(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, const int32_t* blur_radii, int n_sigmas,
+                           int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                           const double* histogram_edges, int histogram_bins, int64_t* histograms, int angle_bins, int64_t* angle_histograms,
+                           double* weighted_angle_histograms, const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
+                           const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats, double* v_x, double* v_y,
+                           double* speed, double* net_remodelling) {
+    return vary_blursize_impl(c, BlurSweepReq{movie, n_frames, blur_weights, blur_radii, n_sigmas, box_size, delta_x, delta_t, include_remodelling,
+                                               reference_quirks, histogram_edges, histogram_bins, histograms, angle_bins, angle_histograms,
+                                               weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, probe_ij,
+                                               n_probes, probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, false});
+}
+
+int vof_vary_blursize_host(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, const int32_t* blur_radii, int n_sigmas,
+                            int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                            const double* histogram_edges, int histogram_bins, int64_t* histograms, int angle_bins, int64_t* angle_histograms,
+                            double* weighted_angle_histograms, const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
+                            const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats, double* v_x, double* v_y,
+                            double* speed, double* net_remodelling) {
+    const int rc = vary_blursize_impl(c, BlurSweepReq{movie, n_frames, blur_weights, blur_radii, n_sigmas, box_size, delta_x, delta_t, include_remodelling,
+                                               reference_quirks, histogram_edges, histogram_bins, histograms, angle_bins, angle_histograms,
+                                               weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, probe_ij,
+                                               n_probes, probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, true});
+    if (!rc && !include_remodelling && net_remodelling)
+        memset(net_remodelling, 0, (size_t)n_sigmas * (size_t)(n_frames - 1) * frame_stride(c) * sizeof(double));
     return rc;
 }
 

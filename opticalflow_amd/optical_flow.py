@@ -64,7 +64,7 @@ def release_device_memory(_locked=False):
 atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
-           "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "make_fake_data_frame", "blur_movie",
+           "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "make_fake_data_frame", "blur_movie",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -529,6 +529,39 @@ def _conduct_optical_flow_device(movie, boxsize, delta_x, delta_t, smoothing_sig
     return result
 
 
+def _sweep_edges(name, bins, value_range):
+    """None, or the ``np.linspace`` edges ``np.histogram(x, bins, value_range)`` uses."""
+    if bins is None:
+        return None
+    if value_range is None:
+        raise ValueError(f"{name}_bins needs a {name}_range")
+    lo, hi = float(value_range[0]), float(value_range[1])
+    if int(bins) < 1 or not np.isfinite([lo, hi]).all() or not hi > lo:
+        raise ValueError(f"{name}_bins must be >= 1 and {name}_range finite and increasing")
+    return np.linspace(lo, hi, int(bins) + 1, endpoint=True, dtype=np.float64)
+
+
+def _sweep_shape(movie):
+    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
+    if len(shape) != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    if shape[0] < 2:
+        raise ValueError("movie needs at least two frames")
+    return shape
+
+
+def _sweep_probes(probe_locations, N_i, N_j):
+    if probe_locations is None:
+        return None
+    probes = np.asarray(probe_locations)
+    if probes.ndim != 2 or probes.shape[1] != 2 or probes.shape[0] < 1:
+        raise ValueError("probe_locations must have shape (n_loc, 2)")
+    probes = probes.astype(np.int64)
+    if (probes < 0).any() or (probes[:, 0] >= N_i).any() or (probes[:, 1] >= N_j).any():
+        raise ValueError("probe outside the image")
+    return probes
+
+
 def vary_boxsize(movie, boxsizes=np.arange(5, 150, 2), delta_x=1.0, delta_t=1.0, smoothing_sigma=None, background=None,
                  include_remodelling=False, filename=None, *, histogram_bins=None, histogram_range=None,
                  probe_locations=None, return_fields=False, reference_quirks=True, device=0, output="numpy"):
@@ -557,28 +590,9 @@ def vary_boxsize(movie, boxsizes=np.arange(5, 150, 2), delta_x=1.0, delta_t=1.0,
         raise ValueError("boxsizes is empty")
     if min(boxes) < 1:
         raise ValueError("every box size must be >= 1")
-    edges = None
-    if histogram_bins is not None:
-        if histogram_range is None:
-            raise ValueError("histogram_bins needs a histogram_range")
-        lo, hi = float(histogram_range[0]), float(histogram_range[1])
-        if int(histogram_bins) < 1 or not np.isfinite([lo, hi]).all() or not hi > lo:
-            raise ValueError("histogram_bins must be >= 1 and histogram_range finite and increasing")
-        edges = np.linspace(lo, hi, int(histogram_bins) + 1, endpoint=True, dtype=np.float64)
-    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
-    if len(shape) != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
-    probes = None
-    if probe_locations is not None:
-        probes = np.asarray(probe_locations)
-        if probes.ndim != 2 or probes.shape[1] != 2 or probes.shape[0] < 1:
-            raise ValueError("probe_locations must have shape (n_loc, 2)")
-        probes = probes.astype(np.int64)
-        if (probes < 0).any() or (probes[:, 0] >= N_i).any() or (probes[:, 1] >= N_j).any():
-            raise ValueError("probe outside the image")
+    edges = _sweep_edges("histogram", histogram_bins, histogram_range)
+    T, N_i, N_j = _sweep_shape(movie)
+    probes = _sweep_probes(probe_locations, N_i, N_j)
     taps = None if smoothing_sigma is None else gaussian_taps(smoothing_sigma)
     fields = None
     if output == "torch":
@@ -619,6 +633,111 @@ def vary_boxsize(movie, boxsizes=np.arange(5, 150, 2), delta_x=1.0, delta_t=1.0,
     if edges is not None:
         result["speed_histograms"] = hist
         result["histogram_edges"] = edges
+    if probes is not None:
+        result["probe_speeds"] = probe_speeds
+    if return_fields:
+        result["v_x"], result["v_y"], result["speed"] = fields[0], fields[1], fields[2]
+        if include_remodelling:
+            result["net_remodelling"] = fields[3]
+    result["delta_x"] = delta_x
+    result["delta_t"] = delta_t
+    if filename is not None:
+        np.save(filename, result)
+    return result
+
+
+def vary_blursize(movie, blursizes=np.arange(0.5, 15, 0.1), boxsize=21, delta_x=1.0, delta_t=1.0, background=None,
+                  include_remodelling=False, filename=None, *, histogram_bins=None, histogram_range=None, angle_bins=None,
+                  intensity_bins=None, intensity_range=None, probe_locations=None, return_fields=False, reference_quirks=True,
+                  device=0, output="numpy"):
+    """The blur sweep the reference's scripts run around ``conduct_optical_flow`` (compare_rho_and_actin.py:485-614, and
+    120-196 for the intensity histogram) as one native call (``vof_vary_blursize_*``): the movie goes up once, ``background``
+    is applied once exactly as in ``conduct_optical_flow``, and per entry of ``blursizes`` the frames are blurred with
+    ``gaussian_taps(s)``, the box flow of ``boxsize`` runs on them and only the summaries come back.
+
+    Every entry ``s`` (finite and ``> 0``; any order, duplicates allowed) is treated as ``conduct_optical_flow(movie, boxsize,
+    delta_x, delta_t, smoothing_sigma=s, background=background, include_remodelling=...)`` treats it, bit for bit; the fields
+    of an entry do not depend on the rest of the list.
+
+    Returns a dict with ``blursizes``, ``speed_means``, ``speed_stds`` (``np.mean`` / ``np.std`` of the entry's speed stack;
+    NaN propagates), ``nonfinite_counts``, ``delta_x``, ``delta_t`` and
+    with ``include_remodelling``: ``remodelling_means``, ``remodelling_stds`` (of ``net_remodelling``);
+    with ``histogram_bins`` (``histogram_range=(lo, hi)`` is then required): ``speed_histograms``, int64 ``(n, bins)``, equal
+    to ``np.histogram(speed.ravel(), bins, range)[0]``, and ``histogram_edges``;
+    with ``angle_bins`` (at most 128): ``angle_histograms``, int64 ``(n, angle_bins)``, ``np.histogram(a, angle_bins, (-1, 1))[0]``
+    of the flow direction ``a = np.arccos(v_y / speed) * np.sign(v_x) / np.pi``, ``weighted_angle_histograms``, float64, the
+    same with ``weights=speed`` (bit-identical from call to call and for every number of pairs in flight), and
+    ``angle_edges``; a sample whose speed is not finite counts in neither;
+    with ``intensity_bins`` (``intensity_range`` is then required): ``intensity_histograms``, int64, ``np.histogram`` of the
+    whole blurred, analysed stack of the entry, and ``intensity_edges``;
+    with ``probe_locations`` of shape ``(n_loc, 2)``: ``probe_speeds`` of shape ``(n, T-1, n_loc)``, ``speed[k, i, j]``;
+    with ``return_fields``: ``v_x``, ``v_y``, ``speed`` and, if asked for, ``net_remodelling`` of shape ``(n, T-1, N_i, N_j)``.
+    Without it no full-size field stack exists on either side.
+    ``filename``: the dict is saved with ``np.save``.  ``output="torch"``: ``movie`` may be a device tensor and the field
+    stacks stay on the device as float64 tensors; the summaries are numpy arrays in both modes."""
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    sigmas = np.asarray(blursizes, dtype=np.float64).ravel()
+    if sigmas.size == 0:
+        raise ValueError("blursizes is empty")
+    if not (np.isfinite(sigmas).all() and (sigmas > 0).all()):
+        raise ValueError("every blur size must be finite and > 0")
+    if int(boxsize) < 1:
+        raise ValueError("boxsize must be >= 1")
+    edges = _sweep_edges("histogram", histogram_bins, histogram_range)
+    intensity_edges = _sweep_edges("intensity", intensity_bins, intensity_range)
+    if angle_bins is not None and not 1 <= int(angle_bins) <= 128:
+        raise ValueError("angle_bins must be 1 .. 128")
+    T, N_i, N_j = _sweep_shape(movie)
+    probes = _sweep_probes(probe_locations, N_i, N_j)
+    taps = [gaussian_taps(s) for s in sigmas]
+    fields = None
+    if output == "torch":
+        import torch
+        dev = torch.device("cuda", int(device))
+        frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
+        with _box_flow_context(N_i, N_j, 1, device) as solver:
+            if background is not None:
+                blurred = torch.empty_like(frames)
+                torch.cuda.synchronize(dev)          # the library launches on its own stream
+                solver.blur_dev(frames, blurred, T, gaussian_taps(10))
+                frames = torch.where(blurred > background, frames - background, torch.zeros_like(frames))
+            if return_fields:
+                fields = [torch.empty((len(taps), T - 1, N_i, N_j), dtype=torch.float64, device=dev)
+                          for _ in range(4 if include_remodelling else 3)]
+            torch.cuda.synchronize(dev)
+            summaries = solver.vary_blursize_dev(frames, T, taps, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks,
+                                                 edges, angle_bins, intensity_edges, probes, *(fields or []))
+    else:
+        source = np.asarray(movie)
+        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
+            movie_to_analyse = source
+            if background is not None:                                          # OF.py:195-198
+                movie_for_thresholding = blur_movie(source, smoothing_sigma=10, device=device, _solver=solver)
+                movie_to_analyse = np.zeros_like(movie_for_thresholding)
+                mask = movie_for_thresholding > background
+                movie_to_analyse[mask] = source[mask] - background
+            *summaries, fields = solver.vary_blursize_host(movie_to_analyse, taps, int(boxsize), delta_x, delta_t, include_remodelling,
+                                                           reference_quirks, edges, angle_bins, intensity_edges, probes, return_fields)
+    rec, hist, angle_hist, weighted_angle_hist, intensity_hist, probe_speeds = summaries
+    result = dict()
+    result["blursizes"] = sigmas
+    result["speed_means"] = rec["speed_mean"].copy()
+    result["speed_stds"] = np.sqrt(rec["speed_variance"])
+    result["nonfinite_counts"] = rec["nonfinite_count"].copy()
+    if include_remodelling:
+        result["remodelling_means"] = rec["remodelling_mean"].copy()
+        result["remodelling_stds"] = np.sqrt(rec["remodelling_variance"])
+    if edges is not None:
+        result["speed_histograms"] = hist
+        result["histogram_edges"] = edges
+    if angle_bins is not None:
+        result["angle_histograms"] = angle_hist
+        result["weighted_angle_histograms"] = weighted_angle_hist
+        result["angle_edges"] = np.linspace(-1.0, 1.0, int(angle_bins) + 1, endpoint=True, dtype=np.float64)
+    if intensity_edges is not None:
+        result["intensity_histograms"] = intensity_hist
+        result["intensity_edges"] = intensity_edges
     if probes is not None:
         result["probe_speeds"] = probe_speeds
     if return_fields:
