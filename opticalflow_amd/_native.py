@@ -196,6 +196,23 @@ def _ptr(a):
     raise TypeError(type(a))
 
 
+def _edges_and_counts(edges, n):
+    """Histogram edges of a sweep of ``n`` entries as float64, the number of bins and zeroed int64 ``(n, bins)`` counts; (None, 0, None)
+    without edges."""
+    if edges is None:
+        return None, 0, None
+    edges = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+    return edges, edges.size - 1, np.zeros((n, edges.size - 1), dtype=np.int64)
+
+
+def _probes_and_speeds(probe_locations, n, n_frames):
+    """Probe indices as int32 ``(n_probes, 2)`` and zeroed ``(n, n_frames - 1, n_probes)`` speeds; (None, None) without probes."""
+    if probe_locations is None:
+        return None, None
+    pij = np.ascontiguousarray(probe_locations, dtype=np.int32).reshape(-1, 2)
+    return pij, np.zeros((n, max(int(n_frames) - 1, 0), pij.shape[0]))
+
+
 class Solver:
     """One context = one device; owns the device workspace for (n_i, n_j) images and a batch of
     ``max_pairs_in_flight`` frame pairs."""
@@ -366,16 +383,18 @@ class Solver:
         self._check(rc, "vof_vary_regularisation_host")
         return out
 
+    def _sweep_fields(self, n, n_frames, include_remodelling, return_fields):
+        """The four host field stacks of a sweep of ``n`` entries; None where not returned (net_remodelling only where it is
+        computed)."""
+        wanted = (4 if include_remodelling else 3) if return_fields else 0
+        return [np.empty((n, max(n_frames - 1, 0), self.n_i, self.n_j)) if f < wanted else None for f in range(4)]
+
     def _vary_boxsize(self, fn, movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks, weights,
                       histogram_edges, probe_locations, fields):
         boxes = np.ascontiguousarray(box_sizes, dtype=np.int32).ravel()
-        P = max(int(n_frames) - 1, 0)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
-        edges = None if histogram_edges is None else np.ascontiguousarray(histogram_edges, dtype=np.float64).ravel()
-        bins = 0 if edges is None else edges.size - 1
-        hist = None if edges is None else np.zeros((boxes.size, bins), dtype=np.int64)
-        pij = None if probe_locations is None else np.ascontiguousarray(probe_locations, dtype=np.int32).reshape(-1, 2)
-        probes = None if pij is None else np.zeros((boxes.size, P, pij.shape[0]))
+        edges, bins, hist = _edges_and_counts(histogram_edges, boxes.size)
+        pij, probes = _probes_and_speeds(probe_locations, boxes.size, n_frames)
         stats = np.zeros(boxes.size, dtype=BOXSIZE_DTYPE)
         rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), _ptr(boxes), boxes.size, float(delta_x), float(delta_t),
                                    int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(w),
@@ -392,11 +411,8 @@ class Solver:
         (``net_remodelling`` is None without ``include_remodelling``)."""
         movie = np.ascontiguousarray(movie, dtype=np.float64)
         assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
-        T, n_boxes = movie.shape[0], np.size(box_sizes)
-        fields = [None] * 4
-        if return_fields:               # net_remodelling only where it is computed
-            for f in range(4 if include_remodelling else 3):
-                fields[f] = np.empty((n_boxes, max(T - 1, 0), self.n_i, self.n_j))
+        T = movie.shape[0]
+        fields = self._sweep_fields(np.size(box_sizes), T, include_remodelling, return_fields)
         out = self._vary_boxsize("vof_vary_boxsize_host", movie, T, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks,
                                  weights, histogram_edges, probe_locations, fields)
         return (*out, tuple(fields) if return_fields else None)
@@ -411,20 +427,15 @@ class Solver:
     def _vary_blursize(self, fn, movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
                        histogram_edges, angle_bins, intensity_edges, probe_locations, fields):
         taps = [np.ascontiguousarray(t, dtype=np.float64).ravel() for t in taps]
-        n, P = len(taps), max(int(n_frames) - 1, 0)
+        n = len(taps)
         radii = np.array([t.size // 2 for t in taps], dtype=np.int32)
         weights = np.concatenate(taps) if taps else np.zeros(0)
-        edges = None if histogram_edges is None else np.ascontiguousarray(histogram_edges, dtype=np.float64).ravel()
-        bins = 0 if edges is None else edges.size - 1
-        iedges = None if intensity_edges is None else np.ascontiguousarray(intensity_edges, dtype=np.float64).ravel()
-        ibins = 0 if iedges is None else iedges.size - 1
+        edges, bins, hist = _edges_and_counts(histogram_edges, n)
+        iedges, ibins, ihist = _edges_and_counts(intensity_edges, n)
         abins = int(angle_bins or 0)
-        hist = None if edges is None else np.zeros((n, bins), dtype=np.int64)
-        ihist = None if iedges is None else np.zeros((n, ibins), dtype=np.int64)
         ahist = np.zeros((n, abins), dtype=np.int64) if abins else None
         awhist = np.zeros((n, abins)) if abins else None
-        pij = None if probe_locations is None else np.ascontiguousarray(probe_locations, dtype=np.int32).reshape(-1, 2)
-        probes = None if pij is None else np.zeros((n, P, pij.shape[0]))
+        pij, probes = _probes_and_speeds(probe_locations, n, n_frames)
         stats = np.zeros(n, dtype=BLURSIZE_DTYPE)
         rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), _ptr(weights), _ptr(radii), n, int(box_size), float(delta_x),
                                    float(delta_t), int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(edges), bins,
@@ -444,10 +455,7 @@ class Solver:
         movie = np.ascontiguousarray(movie, dtype=np.float64)
         assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
         T = movie.shape[0]
-        fields = [None] * 4
-        if return_fields:               # net_remodelling only where it is computed
-            for f in range(4 if include_remodelling else 3):
-                fields[f] = np.empty((len(taps), max(T - 1, 0), self.n_i, self.n_j))
+        fields = self._sweep_fields(len(taps), T, include_remodelling, return_fields)
         out = self._vary_blursize("vof_vary_blursize_host", movie, T, taps, box_size, delta_x, delta_t, include_remodelling,
                                   reference_quirks, histogram_edges, angle_bins, intensity_edges, probe_locations, fields)
         return (*out, tuple(fields) if return_fields else None)

@@ -109,13 +109,11 @@ struct vof_ctx {
     double* st_movie2 = nullptr;                                 // second frame buffer (upload of the next batch under the solve)
     double *blur_tmp = nullptr, *blur_w = nullptr, *blur_io = nullptr;   // Gaussian blur scratch (lazy)
     double* bf_scratch = nullptr;                                        // box flow, general path: derived planes + row sums (lazy)
-    double* bs_scratch = nullptr;                                        // box-size sweep: frames, derived planes, accumulators, chunk outputs (lazy)
-    size_t bs_planes = 0;                                                // planes of bs_scratch
-    bool bs_by_budget = false;                                           // bs_scratch was sized by the free memory, not by the request
-    char* bs_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
-    size_t bs_aux_bytes = 0;
-    double* bz_scratch = nullptr;                                        // blur sweep: movie (_host), blurred stack, chunk outputs (lazy)
-    size_t bz_planes = 0;                                                // planes of bz_scratch
+    double* sw_scratch = nullptr;                                        // box-size and blur sweep: the planes of the one in progress (lazy; sweep_scratch)
+    size_t sw_planes = 0;                                                // planes of sw_scratch
+    bool sw_by_budget = false;                                           // sw_scratch was sized by the free memory, not by the request
+    char* sw_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
+    size_t sw_aux_bytes = 0;
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
     bool bl_lds_set = false;                                             // tiled blur: dynamic LDS limit raised
     bool ls_lds_set = false;                                             // Liu-Shen flow, fused kernel: dynamic LDS limit raised
@@ -3488,7 +3486,7 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
     return 0;
 }
 
-// ---- box-size sweep of the box flow (vary_boxsize; vof_boxsweep.hpp) ---------------------------------------------
+// ---- sweeps of the box flow: what vary_boxsize and vary_blursize share --------------------------------------------
 constexpr int BS_MAX_CHUNK = 32;          // pairs per launch (grid z) at most; more adds nothing once the chip is full
 
 // Mean and variance of a field per list entry, shared by the box-size and the blur sweep: the two-pass reduction of
@@ -3528,27 +3526,21 @@ static Moments pair_moments_merged(const PairMoments& m, const double* mom, size
     return acc;
 }
 
-struct SweepReq {
+// what every sweep is asked for besides its list
+struct SweepBase {
     const double* movie; int n_frames;
-    const int32_t* boxes; int n_boxes;
     double delta_x, delta_t; int remodel, quirks;
-    const double* blur_w; int blur_r;
-    const double* edges; int bins; int64_t* hist;
+    const double* edges; int bins; int64_t* hist;               // speed
     const int32_t* probe_ij; int n_probes; double* probe_out;
-    vof_boxsize_stats* stats;
     double* outs[4];                      // v_x, v_y, speed, net_remodelling: all NULL = stats only
     bool host;                            // movie and outs are host memory
 };
 
-static int vary_boxsize_check(vof_ctx* c, const SweepReq& r) {
+static int sweep_check(vof_ctx* c, const SweepBase& r, const void* stats) {
     if (!r.movie) { c->err = "movie is NULL"; return -1; }
-    if (!r.stats) { c->err = "stats is NULL"; return -1; }
+    if (!stats) { c->err = "stats is NULL"; return -1; }
     if (r.n_frames < 2) { c->err = "need at least two frames"; return -1; }
-    if (!r.boxes || r.n_boxes < 1) { c->err = "the list of box sizes is empty"; return -1; }
-    for (int b = 0; b < r.n_boxes; ++b)
-        if (r.boxes[b] < 1) { c->err = "every box size must be >= 1"; return -1; }
     if (r.delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
-    if (r.blur_w && (r.blur_r < 0 || r.blur_r > 4096)) { c->err = "bad blur_radius"; return -1; }
     if (r.edges && (r.bins < 1 || !r.hist)) { c->err = "histogram_edges needs histogram_bins >= 1 and histograms"; return -1; }
     if (r.edges && !(r.edges[r.bins] > r.edges[0])) { c->err = "histogram_edges must increase"; return -1; }
     if (r.probe_ij) {
@@ -3564,35 +3556,190 @@ static int vary_boxsize_check(vof_ctx* c, const SweepReq& r) {
     return 0;
 }
 
+// pairs a sweep keeps in flight at most: a _host sweep stages no more than the context's slots
+inline int sweep_want(const vof_ctx* c, const SweepBase& r) {
+    return std::min(std::min(r.n_frames - 1, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
+}
+
+// The scratch planes of a sweep (one buffer on the context, lazy): `fixed` planes and `per_pair` for every pair in flight, `want`
+// pairs if the free memory allows.  Returns the pairs the buffer holds (1 .. want) or an error code (< 0).  A buffer the free
+// memory sized is kept as long as it holds one pair: asking again would free and re-allocate it at every call.
+static int sweep_scratch(vof_ctx* c, size_t fixed, size_t per_pair, int want, const char* name, const char* unit) {
+    const size_t fs = frame_stride(c);
+    int cap = c->sw_planes > fixed ? (int)std::min<size_t>((c->sw_planes - fixed) / per_pair, (size_t)want) : 0;
+    if (cap >= want || (c->sw_by_budget && cap >= 1)) return cap;
+    if (int rc = dev_free(c, c->sw_scratch)) return rc;
+    c->sw_scratch = nullptr; c->sw_planes = 0;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t budget = (size_t)(0.8 * (double)free_b) / (fs * sizeof(double));
+    cap = budget > fixed ? (int)std::min<size_t>((budget - fixed) / per_pair, (size_t)want) : 0;
+    if (cap < 1) {
+        c->err = std::string("the ") + name + " does not fit into the free device memory (" + std::to_string(fixed + per_pair) +
+                 " planes of n_i x n_j doubles" + unit + ")";
+        return -3;
+    }
+    if (int rc = dev_alloc(c, &c->sw_scratch, (fixed + per_pair * cap) * fs)) return rc;
+    c->sw_planes = fixed + per_pair * cap;
+    c->sw_by_budget = cap < want;
+    return cap;
+}
+
+// where the fields of pairs k0 .. of entry b go on the device: the caller's stacks (_dev with fields) or the chunk planes
+struct SweepDst {
+    double* f[4];
+    size_t oo;                            // offset of the chunk in the caller's stacks
+    bool keep_v, keep_g;                  // v_x / v_y and net_remodelling are wanted (speed always is)
+};
+
+static SweepDst sweep_dst(const SweepBase& r, double* const chunk_out[4], size_t fs, int b, int k0) {
+    SweepDst d;
+    const bool fields = r.outs[0] != nullptr;
+    d.oo = ((size_t)b * (r.n_frames - 1) + k0) * fs;
+    for (int f = 0; f < 4; ++f) d.f[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + d.oo : chunk_out[f];
+    d.keep_v = fields;
+    d.keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
+    return d;
+}
+
+// _host with fields: np pairs from the chunk planes into the caller's stacks; net_remodelling is zero where it was not computed
+static int sweep_copy_out(vof_ctx* c, const SweepBase& r, const SweepDst& d, size_t fs, int np) {
+    if (!r.host) return 0;
+    const size_t bytes = (size_t)np * fs * sizeof(double);
+    for (int f = 0; f < 4; ++f) {
+        if (!r.outs[f]) continue;
+        if (f == 3 && !r.remodel) memset(r.outs[f] + d.oo, 0, bytes);
+        else if (int rc = d2h_bounced(c, r.outs[f] + d.oo, d.f[f], bytes)) return rc;
+    }
+    return 0;
+}
+
+struct Take {                             // lays items out one after the other
+    size_t items = 0;
+    size_t operator()(size_t k) { const size_t at = items; items += k; return at; }
+};
+
+// The statistics every sweep keeps per list entry: histogram and non-finite count of the speed, the speed at the probes, mean
+// and variance of speed and net_remodelling.  What the kernels read and write lives in one buffer on the context, grown on
+// demand: 8-byte items - the tail's, then `own_doubles` of the sweep, then the counters (zeroed; the tail's, then `own_counters`
+// of the sweep) - and the probe indices.
+struct SweepTail {
+    const SweepBase* r; const char* name;
+    int n; size_t fs;
+    PairMoments pm;
+    size_t n_hist, n_probe, n_mom_all, n_counters;
+    double *d_edges, *d_probe, *own_doubles;
+    unsigned long long *d_bad, *d_hist, *own_counters;
+    int32_t* d_pij;
+    std::vector<unsigned long long> counters;     // host copy (sweep_tail_finish): n non-finite counts, the histograms, the sweep's own
+};
+
+static int sweep_tail_begin(vof_ctx* c, SweepTail& t, const SweepBase& r, const char* name, int n, int cap, size_t own_doubles,
+                            size_t own_counters) {
+    const int P = r.n_frames - 1;
+    t.r = &r; t.name = name; t.n = n; t.fs = frame_stride(c);
+    t.n_hist = r.edges ? (size_t)n * r.bins : 0;
+    t.n_probe = r.probe_ij ? (size_t)n * P * r.n_probes : 0;
+    // moments: per field (speed, net_remodelling), pass, entry and pair the three sums of k_sum3; then the partials of a chunk
+    const size_t n_mom = (size_t)n * P * 3;
+    const int mom_blk = pair_moments_blocks(t.fs);
+    t.n_mom_all = 2 * (r.remodel ? 2 : 1) * n_mom;
+    Take take;
+    const size_t at_edges = take(r.edges ? r.bins + 1 : 0), at_probe = take(t.n_probe), at_mom = take(t.n_mom_all),
+                 at_part = take((size_t)cap * 3 * mom_blk), at_own = take(own_doubles);
+    const size_t at_bad = take(n), at_hist = take(t.n_hist), at_own_counters = take(own_counters);
+    t.n_counters = take.items - at_bad;
+    const size_t pij_bytes = r.probe_ij ? (size_t)2 * r.n_probes * sizeof(int32_t) : 0, aux_bytes = take.items * 8 + pij_bytes;
+    if (c->sw_aux_bytes < aux_bytes) {
+        if (int rc = dev_free(c, c->sw_aux)) return rc;
+        c->sw_aux = nullptr; c->sw_aux_bytes = 0;
+        if (int rc = dev_alloc(c, &c->sw_aux, aux_bytes)) return rc;
+        c->sw_aux_bytes = aux_bytes;
+    }
+    double* const ad = (double*)c->sw_aux;
+    unsigned long long* const au = (unsigned long long*)c->sw_aux;
+    t.d_edges = ad + at_edges; t.d_probe = ad + at_probe; t.own_doubles = ad + at_own;
+    t.d_bad = au + at_bad; t.d_hist = au + at_hist; t.own_counters = au + at_own_counters;
+    t.d_pij = (int32_t*)(ad + take.items);
+    t.pm = PairMoments{ad + at_mom, ad + at_part, n_mom, n, P, mom_blk};
+    if (hipMemsetAsync(t.d_bad, 0, t.n_counters * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
+    if (r.edges) if (int rc = h2d_bounced(c, t.d_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
+    if (r.probe_ij) if (int rc = h2d_bounced(c, t.d_pij, r.probe_ij, pij_bytes)) return rc;
+    return 0;
+}
+
+// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote them: first the counts and the probes of the speed ...
+static void sweep_tail_speed(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed) {
+    const SweepBase& r = *t.r;
+    Prof prof(c, VOF_K_REDUCE, 0);
+    const size_t m = (size_t)np * t.fs;
+    const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
+    k_bs_counts<<<nb, 256, 0, c->stream>>>(speed, m, t.d_edges, r.edges ? r.bins : 0, r.edges ? t.d_hist + (size_t)b * r.bins : nullptr,
+                                           t.d_bad + b);
+    if (r.probe_ij) {
+        const int nt = np * r.n_probes;
+        k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(speed, t.fs, c->Nj, np, t.d_pij, r.n_probes,
+                                                            t.d_probe + ((size_t)b * t.pm.P + k0) * r.n_probes);
+    }
+}
+
+// ... then, behind whatever the sweep adds on the same fields, the moments; asks for the error of the chunk's launches
+static int sweep_tail_moments(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed, const double* gamma) {
+    const SweepBase& r = *t.r;
+    pair_moments_enqueue(c, t.pm, speed, t.fs, 0, b, k0, np);
+    if (r.remodel) pair_moments_enqueue(c, t.pm, gamma, t.fs, 1, b, k0, np);
+    if (hipGetLastError() != hipSuccess) { c->err = std::string(t.name) + ": launch failed"; return -2; }
+    return 0;
+}
+
+// waits for the sweep, brings the statistics back and fills the fields the two stats records share
+extern "C++" {
+template <class Stats>
+static int sweep_tail_finish(vof_ctx* c, SweepTail& t, Stats* stats) {
+    const SweepBase& r = *t.r;
+    t.counters.resize(t.n_counters);
+    if (int rc = d2h_bounced(c, t.counters.data(), t.d_bad, t.n_counters * 8)) return rc;
+    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, t.d_probe, t.n_probe * 8)) return rc;
+    std::vector<double> mom(t.n_mom_all);
+    if (int rc = d2h_bounced(c, mom.data(), t.pm.d_mom, mom.size() * 8)) return rc;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
+    for (size_t i = 0; i < t.n_hist; ++i) r.hist[i] = (int64_t)t.counters[(size_t)t.n + i];
+    for (int b = 0; b < t.n; ++b) {
+        Stats& o = stats[b];
+        memset(&o, 0, sizeof o);
+        const Moments ms = pair_moments_merged(t.pm, mom.data(), t.fs, 0, b);
+        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
+        if (r.remodel) {
+            const Moments mr = pair_moments_merged(t.pm, mom.data(), t.fs, 1, b);
+            o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n;
+        }
+        o.nonfinite_count = (int64_t)t.counters[b];
+    }
+    return 0;
+}
+}  // extern "C++"
+
+// ---- box-size sweep of the box flow (vary_boxsize; vof_boxsweep.hpp) ---------------------------------------------
+struct SweepReq : SweepBase {
+    const int32_t* boxes; int n_boxes;
+    const double* blur_w; int blur_r;
+    vof_boxsize_stats* stats;
+};
+
 static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     if (!c) return -1;
-    if (int rc = vary_boxsize_check(c, r)) return rc;
+    if (int rc = sweep_check(c, r, r.stats)) return rc;
+    if (!r.boxes || r.n_boxes < 1) { c->err = "the list of box sizes is empty"; return -1; }
+    for (int b = 0; b < r.n_boxes; ++b)
+        if (r.boxes[b] < 1) { c->err = "every box size must be >= 1"; return -1; }
+    if (r.blur_w && (r.blur_r < 0 || r.blur_r > 4096)) { c->err = "bad blur_radius"; return -1; }
     HIPCHK(hipSetDevice(c->device));
     const size_t fs = frame_stride(c), fb = fs * sizeof(double);
     const int P = r.n_frames - 1, NQ = r.remodel ? 8 : 5;
-    const bool fields = r.outs[0] != nullptr;
     // scratch planes: cap + 1 frames, and per pair 3 derived planes, R / C / W of every quantity and 4 chunk outputs
-    const size_t per_pair = 1 + 3 + 3 * (size_t)NQ + 4;
-    const int want = std::min(std::min(P, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
-    int cap = c->bs_planes ? (int)std::min<size_t>((c->bs_planes - 1) / per_pair, (size_t)want) : 0;
-    // a buffer the free memory sized is kept: asking again would free and re-allocate it at every call
-    if (cap < want && !(c->bs_by_budget && cap >= 1)) {
-        if (c->bs_scratch) { if (int rc = dev_free(c, c->bs_scratch)) return rc; }
-        c->bs_scratch = nullptr; c->bs_planes = 0;
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t budget = (size_t)(0.8 * (double)free_b) / fb;
-        cap = budget > 1 ? (int)std::min<size_t>((budget - 1) / per_pair, (size_t)want) : 0;
-        if (cap < 1) {
-            c->err = "the box-size sweep does not fit into the free device memory (" + std::to_string(1 + per_pair) +
-                     " planes of n_i x n_j doubles for one pair)";
-            return -3;
-        }
-        if (int rc = dev_alloc(c, &c->bs_scratch, (1 + per_pair * cap) * fs)) return rc;
-        c->bs_planes = 1 + per_pair * cap;
-        c->bs_by_budget = cap < want;
-    }
-    double* frames = c->bs_scratch;
+    const int cap = sweep_scratch(c, 1, 1 + 3 + 3 * (size_t)NQ + 4, sweep_want(c, r), "box-size sweep", " for one pair");
+    if (cap < 0) return cap;
+    double* frames = c->sw_scratch;
     double* der = frames + (size_t)(cap + 1) * fs;
     SweepArgs s{};
     s.der = der; s.fs = fs; s.Ni = c->Ni; s.Nj = c->Nj;
@@ -3601,33 +3748,8 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     s.W = s.C + (size_t)cap * NQ * fs;
     double* chunk_out[4];
     for (int f = 0; f < 4; ++f) chunk_out[f] = s.W + (size_t)cap * NQ * fs + (size_t)f * cap * fs;
-
-    // what the statistics kernels read and write: edges, probe indices, counters, probe values (kept on the context, grown on demand)
-    const size_t n_hist = r.edges ? (size_t)r.n_boxes * r.bins : 0, n_probe = r.probe_ij ? (size_t)r.n_boxes * P * r.n_probes : 0;
-    // moments: per field (speed, net_remodelling), pass, box and pair the three sums of k_sum3; then the partials of a chunk
-    const size_t n_mom = (size_t)r.n_boxes * P * 3, n_fields_mom = r.remodel ? 2 : 1;
-    const int mom_blk = pair_moments_blocks(fs);
-    const size_t n_part = (size_t)cap * 3 * mom_blk;
-    const size_t aux_doubles = (r.edges ? r.bins + 1 : 0) + n_probe + 2 * n_fields_mom * n_mom + n_part;
-    const size_t aux_counters = (size_t)r.n_boxes + n_hist;
-    const size_t aux_bytes = (aux_doubles + aux_counters) * 8 + (r.probe_ij ? (size_t)2 * r.n_probes * sizeof(int32_t) : 0);
-    if (c->bs_aux_bytes < aux_bytes) {
-        if (int rc = dev_free(c, c->bs_aux)) return rc;
-        c->bs_aux = nullptr; c->bs_aux_bytes = 0;
-        if (int rc = dev_alloc(c, &c->bs_aux, aux_bytes)) return rc;
-        c->bs_aux_bytes = aux_bytes;
-    }
-    char* aux = c->bs_aux;
-    double* d_edges = (double*)aux;
-    double* d_probe = d_edges + (r.edges ? r.bins + 1 : 0);
-    double* d_mom = d_probe + n_probe;                    // [field][pass][box][pair][3]
-    double* d_part = d_mom + 2 * n_fields_mom * n_mom;
-    unsigned long long* d_bad = (unsigned long long*)(d_part + n_part);
-    unsigned long long* d_hist = d_bad + r.n_boxes;
-    int32_t* d_pij = (int32_t*)(d_hist + n_hist);
-    if (hipMemsetAsync(d_bad, 0, aux_counters * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
-    if (r.edges) if (int rc = h2d_bounced(c, d_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
-    if (r.probe_ij) if (int rc = h2d_bounced(c, d_pij, r.probe_ij, (size_t)2 * r.n_probes * sizeof(int32_t))) return rc;
+    SweepTail tail;
+    if (int rc = sweep_tail_begin(c, tail, r, "box-size sweep", r.n_boxes, cap, 0, 0)) return rc;
     if (r.blur_w) {
         if (int rc = blur_alloc(c)) return rc;
         if (int rc = h2d_bounced(c, c->blur_w, r.blur_w, (size_t)(2 * r.blur_r + 1) * sizeof(double))) return rc;
@@ -3642,7 +3764,6 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
         at_h[h].push_back(b);
     }
     const int h_max = (int)at_h.size() - 1;
-    const PairMoments pm{d_mom, d_part, n_mom, r.n_boxes, P, mom_blk};
     BoxArgs a{};
     a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj;
     a.cend = r.quirks ? std::min(c->Ni, c->Nj) : c->Nj;      // OF.py:108 clamps the column window with N_i
@@ -3682,12 +3803,9 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
             }
             for (int b : at_h[h]) {
                 a.n_box = (double)r.boxes[b] * (double)r.boxes[b];
-                const size_t oo = ((size_t)b * P + k0) * fs;
-                double* dst[4];
-                for (int f = 0; f < 4; ++f) dst[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + oo : chunk_out[f];
-                const bool keep_v = fields, keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
-                a.vx = keep_v ? dst[0] : nullptr; a.vy = keep_v ? dst[1] : nullptr; a.speed = dst[2];
-                a.gamma = keep_g ? dst[3] : nullptr;
+                const SweepDst d = sweep_dst(r, chunk_out, fs, b, k0);
+                a.vx = d.keep_v ? d.f[0] : nullptr; a.vy = d.keep_v ? d.f[1] : nullptr; a.speed = d.f[2];
+                a.gamma = d.keep_g ? d.f[3] : nullptr;
                 {
                     Prof prof(c, VOF_K_RHS, 0);
                     if (!stepped) {              // the first entry of this half width takes the step with it
@@ -3698,42 +3816,15 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
                         if (r.remodel) k_bs_window<true, false, true><<<g, blk2d, 0, c->stream>>>(s, a);
                         else k_bs_window<false, false, true><<<g, blk2d, 0, c->stream>>>(s, a);
                     }
-                    const size_t n = (size_t)np * fs;
-                    const int nb = (int)std::min<size_t>(1024, (n + 4 * 256 - 1) / (4 * 256));
-                    k_bs_counts<<<nb, 256, 0, c->stream>>>(a.speed, n, d_edges, r.edges ? r.bins : 0,
-                                                           r.edges ? d_hist + (size_t)b * r.bins : nullptr, d_bad + b);
-                    if (r.probe_ij) {
-                        const int nt = np * r.n_probes;
-                        k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(a.speed, fs, c->Nj, np, d_pij, r.n_probes,
-                                                                            d_probe + ((size_t)b * P + k0) * r.n_probes);
-                    }
                 }
-                pair_moments_enqueue(c, pm, a.speed, fs, 0, b, k0, np);
-                if (r.remodel) pair_moments_enqueue(c, pm, a.gamma, fs, 1, b, k0, np);
-                if (hipGetLastError() != hipSuccess) { c->err = "box-size sweep: launch failed"; return -2; }
-                if (fields && r.host)
-                    for (int f = 0; f < 4; ++f)
-                        if (r.outs[f] && (f < 3 || a.gamma))
-                            if (int rc = d2h_bounced(c, r.outs[f] + oo, dst[f], (size_t)np * fb)) return rc;
+                sweep_tail_speed(c, tail, b, k0, np, a.speed);
+                if (int rc = sweep_tail_moments(c, tail, b, k0, np, a.speed, a.gamma)) return rc;
+                if (int rc = sweep_copy_out(c, r, d, fs, np)) return rc;
             }
         }
     }
-    std::vector<unsigned long long> counters(aux_counters);
-    if (int rc = d2h_bounced(c, counters.data(), d_bad, aux_counters * 8)) return rc;
-    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, d_probe, n_probe * 8)) return rc;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
-    for (size_t t = 0; t < n_hist; ++t) r.hist[t] = (int64_t)counters[(size_t)r.n_boxes + t];
-    std::vector<double> mom(2 * n_fields_mom * n_mom);
-    if (int rc = d2h_bounced(c, mom.data(), d_mom, mom.size() * 8)) return rc;
-    for (int b = 0; b < r.n_boxes; ++b) {
-        vof_boxsize_stats& o = r.stats[b];
-        memset(&o, 0, sizeof o);
-        const Moments ms = pair_moments_merged(pm, mom.data(), fs, 0, b);
-        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
-        if (r.remodel) { const Moments mr = pair_moments_merged(pm, mom.data(), fs, 1, b); o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n; }
-        o.nonfinite_count = (int64_t)counters[b];
-        o.box_size = r.boxes[b];
-    }
+    if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
+    for (int b = 0; b < r.n_boxes; ++b) r.stats[b].box_size = r.boxes[b];
     return 0;
 }
 
@@ -3741,91 +3832,47 @@ int vof_vary_boxsize_dev(vof_ctx* c, const double* movie, int n_frames, const in
                          double delta_t, int include_remodelling, int reference_quirks, const double* blur_weights, int blur_radius,
                          const double* histogram_edges, int histogram_bins, int64_t* histograms, const int32_t* probe_ij, int n_probes,
                          double* probe_speeds, vof_boxsize_stats* stats, double* v_x, double* v_y, double* speed, double* net_remodelling) {
-    return vary_boxsize_impl(c, SweepReq{movie, n_frames, box_sizes, n_boxes, delta_x, delta_t, include_remodelling, reference_quirks,
-                                         blur_weights, blur_radius, histogram_edges, histogram_bins, histograms, probe_ij, n_probes,
-                                         probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, false});
+    return vary_boxsize_impl(c, SweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
+                                          histogram_bins, histograms, probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, false},
+                                         box_sizes, n_boxes, blur_weights, blur_radius, stats});
 }
 
 int vof_vary_boxsize_host(vof_ctx* c, const double* movie, int n_frames, const int32_t* box_sizes, int n_boxes, double delta_x,
                           double delta_t, int include_remodelling, int reference_quirks, const double* blur_weights, int blur_radius,
                           const double* histogram_edges, int histogram_bins, int64_t* histograms, const int32_t* probe_ij, int n_probes,
                           double* probe_speeds, vof_boxsize_stats* stats, double* v_x, double* v_y, double* speed, double* net_remodelling) {
-    const int rc = vary_boxsize_impl(c, SweepReq{movie, n_frames, box_sizes, n_boxes, delta_x, delta_t, include_remodelling,
-                                                 reference_quirks, blur_weights, blur_radius, histogram_edges, histogram_bins, histograms,
-                                                 probe_ij, n_probes, probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, true});
-    if (!rc && !include_remodelling && net_remodelling)
-        memset(net_remodelling, 0, (size_t)n_boxes * (size_t)(n_frames - 1) * frame_stride(c) * sizeof(double));
-    return rc;
+    return vary_boxsize_impl(c, SweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
+                                          histogram_bins, histograms, probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, true},
+                                         box_sizes, n_boxes, blur_weights, blur_radius, stats});
 }
 
 // ---- blur sweep of the box flow (vary_blursize; vof_blursweep.hpp) -------------------------------------------------
-struct BlurSweepReq {
-    const double* movie; int n_frames;
+struct BlurSweepReq : SweepBase {
     const double* taps; const int32_t* radii; int n_sigmas;     // the tap vectors (2 radii[s] + 1 each), concatenated
-    int box_size; double delta_x, delta_t; int remodel, quirks;
-    const double* edges; int bins; int64_t* hist;               // speed
+    int box_size;
     int abins; int64_t* ahist; double* awhist;                  // flow direction: counts and speed-weighted sums
     const double* iedges; int ibins; int64_t* ihist;            // intensity of the blurred stack
-    const int32_t* probe_ij; int n_probes; double* probe_out;
     vof_blursize_stats* stats;
-    double* outs[4];                      // v_x, v_y, speed, net_remodelling: all NULL = stats only
-    bool host;                            // movie and outs are host memory
 };
 
-static int vary_blursize_check(vof_ctx* c, const BlurSweepReq& r) {
-    if (!r.movie) { c->err = "movie is NULL"; return -1; }
-    if (!r.stats) { c->err = "stats is NULL"; return -1; }
-    if (r.n_frames < 2) { c->err = "need at least two frames"; return -1; }
+static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
+    if (!c) return -1;
+    if (int rc = sweep_check(c, r, r.stats)) return rc;
     if (!r.taps || !r.radii || r.n_sigmas < 1) { c->err = "the list of blur sizes is empty"; return -1; }
     for (int s = 0; s < r.n_sigmas; ++s)
         if (r.radii[s] < 0 || r.radii[s] > 4096) { c->err = "bad blur radius"; return -1; }
     if (r.box_size < 1) { c->err = "box_size must be >= 1"; return -1; }
-    if (r.delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
-    if (r.edges && (r.bins < 1 || !r.hist)) { c->err = "histogram_edges needs histogram_bins >= 1 and histograms"; return -1; }
-    if (r.edges && !(r.edges[r.bins] > r.edges[0])) { c->err = "histogram_edges must increase"; return -1; }
     if (r.iedges && (r.ibins < 1 || !r.ihist)) { c->err = "intensity_edges needs intensity_bins >= 1 and intensity_histograms"; return -1; }
     if (r.iedges && !(r.iedges[r.ibins] > r.iedges[0])) { c->err = "intensity_edges must increase"; return -1; }
     if (r.abins < 0 || r.abins > BZ_MAX_ANGLE_BINS) { c->err = "angle_bins must be 0 .. " + std::to_string(BZ_MAX_ANGLE_BINS); return -1; }
     if (r.abins && (!r.ahist || !r.awhist)) { c->err = "angle_bins needs angle_histograms and weighted_angle_histograms"; return -1; }
-    if (r.probe_ij) {
-        if (r.n_probes < 1 || !r.probe_out) { c->err = "probe_ij needs n_probes >= 1 and probe_speeds"; return -1; }
-        for (int l = 0; l < r.n_probes; ++l)
-            if (r.probe_ij[2 * l] < 0 || r.probe_ij[2 * l] >= c->Ni || r.probe_ij[2 * l + 1] < 0 || r.probe_ij[2 * l + 1] >= c->Nj) {
-                c->err = "probe outside the image"; return -1;
-            }
-    }
-    const bool any = r.outs[0] || r.outs[1] || r.outs[2] || r.outs[3];
-    if (any && (!r.outs[0] || !r.outs[1] || !r.outs[2])) { c->err = "v_x, v_y and speed must be given together (or all NULL)"; return -1; }
-    if (any && r.remodel && !r.outs[3]) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
-    return 0;
-}
-
-static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
-    if (!c) return -1;
-    if (int rc = vary_blursize_check(c, r)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t fs = frame_stride(c), fb = fs * sizeof(double);
     const int T = r.n_frames, P = T - 1, n = r.n_sigmas;
-    const bool fields = r.outs[0] != nullptr;
-    // scratch planes: the movie (_host), the blurred stack, and four chunk outputs per pair in flight (chunks as vary_boxsize)
-    const size_t base = (size_t)(r.host ? 2 : 1) * T;
-    const int want = std::min(std::min(P, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
-    int cap = c->bz_planes > base ? (int)std::min<size_t>((c->bz_planes - base) / 4, (size_t)want) : 0;
-    if (cap < want) {
-        if (int rc = dev_free(c, c->bz_scratch)) return rc;
-        c->bz_scratch = nullptr; c->bz_planes = 0;
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t budget = (size_t)(0.8 * (double)free_b) / fb;
-        cap = budget > base ? (int)std::min<size_t>((budget - base) / 4, (size_t)want) : 0;
-        if (cap < 1) {
-            c->err = "the blur sweep does not fit into the free device memory (" + std::to_string(base + 4) + " planes of n_i x n_j doubles)";
-            return -3;
-        }
-        if (int rc = dev_alloc(c, &c->bz_scratch, (base + 4 * (size_t)cap) * fs)) return rc;
-        c->bz_planes = base + 4 * (size_t)cap;
-    }
-    double* blurred = c->bz_scratch;
+    // scratch planes: the blurred stack, four chunk outputs per pair in flight and the movie (_host)
+    const int cap = sweep_scratch(c, (size_t)(r.host ? 2 : 1) * T, 4, sweep_want(c, r), "blur sweep", "");
+    if (cap < 0) return cap;
+    double* blurred = c->sw_scratch;
     double* chunk_out[4];
     for (int f = 0; f < 4; ++f) chunk_out[f] = blurred + ((size_t)T + (size_t)f * cap) * fs;
     const double* movie = r.movie;
@@ -3836,36 +3883,21 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     }
     if (int rc = blur_alloc(c)) return rc;
 
-    // what the kernels read and the statistics they write (kept on the context, grown on demand): 8-byte items, then the probe indices
+    // what the sweep's own kernels read and write, behind the tail's: taps, direction and intensity edges, direction sums and counts
     std::vector<size_t> tap_at(n);
     size_t n_taps = 0;
     for (int s = 0; s < n; ++s) { tap_at[s] = n_taps; n_taps += 2 * (size_t)r.radii[s] + 1; }
-    const size_t n_hist = r.edges ? (size_t)n * r.bins : 0, n_ahist = (size_t)n * r.abins, n_ihist = r.iedges ? (size_t)n * r.ibins : 0;
-    const size_t n_probe = r.probe_ij ? (size_t)n * P * r.n_probes : 0, n_awsum = (size_t)n * P * r.abins;
-    const size_t n_mom = (size_t)n * P * 3, n_fields_mom = r.remodel ? 2 : 1;
-    const int mom_blk = pair_moments_blocks(fs);
+    const size_t n_ahist = (size_t)n * r.abins, n_ihist = r.iedges ? (size_t)n * r.ibins : 0, n_awsum = (size_t)n * P * r.abins;
     const int ang_blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));   // by the plane size only
-    size_t items = 0;
-    auto take = [&](size_t k) { const size_t at = items; items += k; return at; };
-    const size_t at_taps = take(n_taps), at_edges = take(r.edges ? r.bins + 1 : 0), at_aedges = take(r.abins ? r.abins + 1 : 0),
-                 at_iedges = take(r.iedges ? r.ibins + 1 : 0), at_probe = take(n_probe), at_mom = take(2 * n_fields_mom * n_mom),
-                 at_part = take((size_t)cap * 3 * mom_blk), at_awsum = take(n_awsum), at_apart = take((size_t)cap * ang_blk * r.abins),
-                 at_counters = take(0);
-    const size_t at_bad = take(n), at_hist = take(n_hist), at_ahist = take(n_ahist), at_ihist = take(n_ihist), at_ibad = take(1);
-    const size_t n_counters = items - at_counters;
-    const size_t aux_bytes = items * 8 + (r.probe_ij ? (size_t)2 * r.n_probes * sizeof(int32_t) : 0);
-    if (c->bs_aux_bytes < aux_bytes) {
-        if (int rc = dev_free(c, c->bs_aux)) return rc;
-        c->bs_aux = nullptr; c->bs_aux_bytes = 0;
-        if (int rc = dev_alloc(c, &c->bs_aux, aux_bytes)) return rc;
-        c->bs_aux_bytes = aux_bytes;
-    }
-    double* const ad = (double*)c->bs_aux;
-    unsigned long long* const au = (unsigned long long*)c->bs_aux;
-    int32_t* d_pij = (int32_t*)(ad + items);
-    if (hipMemsetAsync(au + at_counters, 0, n_counters * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
+    Take doubles, counts;
+    const size_t at_taps = doubles(n_taps), at_aedges = doubles(r.abins ? r.abins + 1 : 0), at_iedges = doubles(r.iedges ? r.ibins + 1 : 0),
+                 at_awsum = doubles(n_awsum), at_apart = doubles((size_t)cap * ang_blk * r.abins);
+    const size_t at_ahist = counts(n_ahist), at_ihist = counts(n_ihist), at_ibad = counts(1);
+    SweepTail tail;
+    if (int rc = sweep_tail_begin(c, tail, r, "blur sweep", n, cap, doubles.items, counts.items)) return rc;
+    double* const ad = tail.own_doubles;
+    unsigned long long* const au = tail.own_counters;
     if (int rc = h2d_bounced(c, ad + at_taps, r.taps, n_taps * 8)) return rc;
-    if (r.edges) if (int rc = h2d_bounced(c, ad + at_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
     if (r.iedges) if (int rc = h2d_bounced(c, ad + at_iedges, r.iedges, (size_t)(r.ibins + 1) * 8)) return rc;
     if (r.abins) {                         // np.linspace(-1, 1, bins + 1): i * step + start, the last one the stop itself
         std::vector<double> e((size_t)r.abins + 1);
@@ -3874,8 +3906,6 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
         e[r.abins] = 1.0;
         if (int rc = h2d_bounced(c, ad + at_aedges, e.data(), e.size() * 8)) return rc;
     }
-    if (r.probe_ij) if (int rc = h2d_bounced(c, d_pij, r.probe_ij, (size_t)2 * r.n_probes * sizeof(int32_t))) return rc;
-    const PairMoments pm{ad + at_mom, ad + at_part, n_mom, n, P, mom_blk};
 
     for (int s = 0; s < n; ++s) {
         if (int rc = blur_frames(c, movie, blurred, T, r.radii[s], ad + at_taps + tap_at[s])) return rc;
@@ -3887,64 +3917,36 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
         }
         for (int k0 = 0; k0 < P; k0 += cap) {
             const int np = std::min(cap, P - k0);
-            const size_t oo = ((size_t)s * P + k0) * fs;
-            double* dst[4];
-            for (int f = 0; f < 4; ++f) dst[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + oo : chunk_out[f];
-            const bool keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
+            const SweepDst d = sweep_dst(r, chunk_out, fs, s, k0);
             // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
-            if (int rc = box_flow_pairs(c, blurred + (size_t)k0 * fs, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, dst[0], dst[1],
-                                        dst[2], keep_g ? dst[3] : nullptr)) return rc;
-            {
+            if (int rc = box_flow_pairs(c, blurred + (size_t)k0 * fs, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d.f[0], d.f[1],
+                                        d.f[2], d.keep_g ? d.f[3] : nullptr)) return rc;
+            sweep_tail_speed(c, tail, s, k0, np, d.f[2]);
+            if (r.abins) {
                 Prof prof(c, VOF_K_REDUCE, 0);
-                const size_t m = (size_t)np * fs;
-                const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
-                k_bs_counts<<<nb, 256, 0, c->stream>>>(dst[2], m, ad + at_edges, r.edges ? r.bins : 0,
-                                                       r.edges ? au + at_hist + (size_t)s * r.bins : nullptr, au + at_bad + s);
-                if (r.probe_ij) {
-                    const int nt = np * r.n_probes;
-                    k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(dst[2], fs, c->Nj, np, d_pij, r.n_probes,
-                                                                        ad + at_probe + ((size_t)s * P + k0) * r.n_probes);
-                }
-                if (r.abins) {
-                    k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
-                        dst[0], dst[1], dst[2], fs, ad + at_aedges, r.abins, au + at_ahist + (size_t)s * r.abins, ad + at_apart);
-                    const int nt = np * r.abins;
-                    k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_apart, ang_blk, r.abins, np,
-                                                                            ad + at_awsum + ((size_t)s * P + k0) * r.abins);
-                }
+                k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
+                    d.f[0], d.f[1], d.f[2], fs, ad + at_aedges, r.abins, au + at_ahist + (size_t)s * r.abins, ad + at_apart);
+                const int nt = np * r.abins;
+                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_apart, ang_blk, r.abins, np,
+                                                                        ad + at_awsum + ((size_t)s * P + k0) * r.abins);
             }
-            pair_moments_enqueue(c, pm, dst[2], fs, 0, s, k0, np);
-            if (r.remodel) pair_moments_enqueue(c, pm, dst[3], fs, 1, s, k0, np);
-            if (hipGetLastError() != hipSuccess) { c->err = "blur sweep: launch failed"; return -2; }
-            if (fields && r.host)
-                for (int f = 0; f < 4; ++f)
-                    if (r.outs[f] && (f < 3 || r.remodel))
-                        if (int rc = d2h_bounced(c, r.outs[f] + oo, dst[f], (size_t)np * fb)) return rc;
+            if (int rc = sweep_tail_moments(c, tail, s, k0, np, d.f[2], d.f[3])) return rc;
+            if (int rc = sweep_copy_out(c, r, d, fs, np)) return rc;
         }
     }
-    std::vector<unsigned long long> counters(n_counters);
-    if (int rc = d2h_bounced(c, counters.data(), au + at_counters, n_counters * 8)) return rc;
-    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, ad + at_probe, n_probe * 8)) return rc;
-    std::vector<double> mom(2 * n_fields_mom * n_mom), awsum(n_awsum);
-    if (int rc = d2h_bounced(c, mom.data(), ad + at_mom, mom.size() * 8)) return rc;
+    if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
+    std::vector<double> awsum(n_awsum);
     if (n_awsum) if (int rc = d2h_bounced(c, awsum.data(), ad + at_awsum, n_awsum * 8)) return rc;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
-    for (size_t t = 0; t < n_hist; ++t) r.hist[t] = (int64_t)counters[at_hist - at_counters + t];
-    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)counters[at_ahist - at_counters + t];
-    for (size_t t = 0; t < n_ihist; ++t) r.ihist[t] = (int64_t)counters[at_ihist - at_counters + t];
+    const unsigned long long* own = tail.counters.data() + (tail.n_counters - counts.items);
+    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)own[at_ahist + t];
+    for (size_t t = 0; t < n_ihist; ++t) r.ihist[t] = (int64_t)own[at_ihist + t];
     for (int s = 0; s < n; ++s) {
         for (int b = 0; b < r.abins; ++b) {                  // the pairs' sums in pair order
             double w = 0.0;
             for (int k = 0; k < P; ++k) w += awsum[((size_t)s * P + k) * r.abins + b];
             r.awhist[(size_t)s * r.abins + b] = w;
         }
-        vof_blursize_stats& o = r.stats[s];
-        memset(&o, 0, sizeof o);
-        const Moments ms = pair_moments_merged(pm, mom.data(), fs, 0, s);
-        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
-        if (r.remodel) { const Moments mr = pair_moments_merged(pm, mom.data(), fs, 1, s); o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n; }
-        o.nonfinite_count = (int64_t)counters[at_bad - at_counters + s];
-        o.sigma_index = s;
+        r.stats[s].sigma_index = s;
     }
     return 0;
 }
@@ -3955,10 +3957,11 @@ int vof_vary_blursize_dev(vof_ctx* c, const double* movie, int n_frames, const d
                            double* weighted_angle_histograms, const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
                            const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats, double* v_x, double* v_y,
                            double* speed, double* net_remodelling) {
-    return vary_blursize_impl(c, BlurSweepReq{movie, n_frames, blur_weights, blur_radii, n_sigmas, box_size, delta_x, delta_t, include_remodelling,
-                                               reference_quirks, histogram_edges, histogram_bins, histograms, angle_bins, angle_histograms,
-                                               weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, probe_ij,
-                                               n_probes, probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, false});
+    return vary_blursize_impl(c, BlurSweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
+                                               histogram_bins, histograms, probe_ij, n_probes, probe_speeds,
+                                               {v_x, v_y, speed, net_remodelling}, false},
+                                              blur_weights, blur_radii, n_sigmas, box_size, angle_bins, angle_histograms,
+                                              weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, stats});
 }
 
 int vof_vary_blursize_host(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, const int32_t* blur_radii, int n_sigmas,
@@ -3967,13 +3970,11 @@ int vof_vary_blursize_host(vof_ctx* c, const double* movie, int n_frames, const 
                             double* weighted_angle_histograms, const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
                             const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats, double* v_x, double* v_y,
                             double* speed, double* net_remodelling) {
-    const int rc = vary_blursize_impl(c, BlurSweepReq{movie, n_frames, blur_weights, blur_radii, n_sigmas, box_size, delta_x, delta_t, include_remodelling,
-                                               reference_quirks, histogram_edges, histogram_bins, histograms, angle_bins, angle_histograms,
-                                               weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, probe_ij,
-                                               n_probes, probe_speeds, stats, {v_x, v_y, speed, net_remodelling}, true});
-    if (!rc && !include_remodelling && net_remodelling)
-        memset(net_remodelling, 0, (size_t)n_sigmas * (size_t)(n_frames - 1) * frame_stride(c) * sizeof(double));
-    return rc;
+    return vary_blursize_impl(c, BlurSweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
+                                               histogram_bins, histograms, probe_ij, n_probes, probe_speeds,
+                                               {v_x, v_y, speed, net_remodelling}, true},
+                                              blur_weights, blur_radii, n_sigmas, box_size, angle_bins, angle_histograms,
+                                              weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, stats});
 }
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------

@@ -416,6 +416,25 @@ def _box_flow_context(n_i, n_j, n_pairs, device):
     return _device_context(n_i, n_j, max(1, min(int(n_pairs), 8)), device)
 
 
+def _subtract_background(source, background, device, solver):
+    """OF.py:195-198 on host memory: ``source - background`` where the movie blurred with sigma 10 exceeds ``background``, zero
+    elsewhere."""
+    movie_for_thresholding = blur_movie(source, smoothing_sigma=10, device=device, _solver=solver)
+    movie_to_analyse = np.zeros_like(movie_for_thresholding)
+    mask = movie_for_thresholding > background
+    movie_to_analyse[mask] = source[mask] - background
+    return movie_to_analyse
+
+
+def _subtract_background_device(frames, background, solver):
+    """The same on a float64 device tensor."""
+    import torch
+    blurred = torch.empty_like(frames)
+    torch.cuda.synchronize(frames.device)          # the library launches on its own stream
+    solver.blur_dev(frames, blurred, frames.shape[0], gaussian_taps(10))
+    return torch.where(blurred > background, frames - background, torch.zeros_like(frames))
+
+
 def conduct_optical_flow_jit(movie, box_size=15, delta_x=1.0, delta_t=1.0, include_remodelling=False, *,
                              reference_quirks=True, device=0):
     """Windowed least-squares flow of every frame pair on the GPU; arguments and the returned 4-tuple
@@ -470,12 +489,7 @@ def conduct_optical_flow(movie, boxsize=15, delta_x=1.0, delta_t=1.0, smoothing_
     if int(boxsize) < 1:
         raise ValueError("boxsize must be >= 1")
     with _box_flow_context(N_i, N_j, T - 1, device) as solver:
-        movie_to_analyse = source
-        if background is not None:                                          # OF.py:195-198
-            movie_for_thresholding = blur_movie(source, smoothing_sigma=10, device=device, _solver=solver)
-            movie_to_analyse = np.zeros_like(movie_for_thresholding)
-            mask = movie_for_thresholding > background
-            movie_to_analyse[mask] = source[mask] - background
+        movie_to_analyse = source if background is None else _subtract_background(source, background, device, solver)
         if smoothing_sigma is not None:                                     # OF.py:202-203
             movie_to_analyse = blur_movie(movie_to_analyse, smoothing_sigma=smoothing_sigma, device=device, _solver=solver)
         v_x, v_y, speed, net_remodelling = solver.box_flow_host(movie_to_analyse, int(boxsize), delta_x, delta_t,
@@ -508,12 +522,7 @@ def _conduct_optical_flow_device(movie, boxsize, delta_x, delta_t, smoothing_sig
         raise ValueError("boxsize must be >= 1")
     out = [torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4 if include_remodelling else 3)]
     with _box_flow_context(N_i, N_j, 1, device) as solver:
-        movie_to_analyse = frames
-        if background is not None:
-            blurred = torch.empty_like(frames)
-            torch.cuda.synchronize(dev)          # the library launches on its own stream
-            solver.blur_dev(frames, blurred, T, gaussian_taps(10))
-            movie_to_analyse = torch.where(blurred > background, frames - background, torch.zeros_like(frames))
+        movie_to_analyse = frames if background is None else _subtract_background_device(frames, background, solver)
         if smoothing_sigma is not None:
             blurred = torch.empty_like(frames)
             torch.cuda.synchronize(dev)
@@ -562,6 +571,63 @@ def _sweep_probes(probe_locations, N_i, N_j):
     return probes
 
 
+def _run_sweep(name, native, movie, n, background, include_remodelling, probe_locations, return_fields, device, output):
+    """What the sweeps of the box flow share around their native call ``Solver.<name>_host`` / ``_dev``: the movie goes up (torch) or
+    becomes an array, ``background`` is applied as in ``conduct_optical_flow`` and the stacks of the ``n`` entries are allocated.
+    ``native(entry, head, probes, tail)`` calls ``entry`` with the arguments the two entries share between ``head`` and ``tail``.
+    Returns the summaries of the entry and the list of field stacks (None without ``return_fields``)."""
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    T, N_i, N_j = _sweep_shape(movie)
+    probes = _sweep_probes(probe_locations, N_i, N_j)
+    if output == "numpy":
+        source = np.asarray(movie)
+        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
+            movie_to_analyse = source if background is None else _subtract_background(source, background, device, solver)
+            *summaries, fields = native(getattr(solver, name + "_host"), (movie_to_analyse,), probes, (return_fields,))
+        return summaries, fields
+    import torch
+    dev = torch.device("cuda", int(device))
+    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
+    fields = None
+    with _box_flow_context(N_i, N_j, 1, device) as solver:
+        if background is not None:
+            frames = _subtract_background_device(frames, background, solver)
+        if return_fields:
+            fields = [torch.empty((n, T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4 if include_remodelling else 3)]
+        torch.cuda.synchronize(dev)
+        summaries = native(getattr(solver, name + "_dev"), (frames, T), probes, fields or ())
+    return summaries, fields
+
+
+def _sweep_result(listed, summaries, fields, own, edges, include_remodelling, delta_x, delta_t, filename):
+    """The dict a sweep returns: ``listed`` (its list), the statistics every sweep has, ``own`` behind the speed histogram, the
+    probes, the fields; saved with ``np.save`` if ``filename`` is given."""
+    rec, hist, probe_speeds = summaries[0], summaries[1], summaries[-1]
+    result = dict(listed)
+    result["speed_means"] = rec["speed_mean"].copy()
+    result["speed_stds"] = np.sqrt(rec["speed_variance"])
+    result["nonfinite_counts"] = rec["nonfinite_count"].copy()
+    if include_remodelling:
+        result["remodelling_means"] = rec["remodelling_mean"].copy()
+        result["remodelling_stds"] = np.sqrt(rec["remodelling_variance"])
+    if edges is not None:
+        result["speed_histograms"] = hist
+        result["histogram_edges"] = edges
+    result.update(own)
+    if probe_speeds is not None:
+        result["probe_speeds"] = probe_speeds
+    if fields is not None:
+        result["v_x"], result["v_y"], result["speed"] = fields[0], fields[1], fields[2]
+        if include_remodelling:
+            result["net_remodelling"] = fields[3]
+    result["delta_x"] = delta_x
+    result["delta_t"] = delta_t
+    if filename is not None:
+        np.save(filename, result)
+    return result
+
+
 def vary_boxsize(movie, boxsizes=np.arange(5, 150, 2), delta_x=1.0, delta_t=1.0, smoothing_sigma=None, background=None,
                  include_remodelling=False, filename=None, *, histogram_bins=None, histogram_range=None,
                  probe_locations=None, return_fields=False, reference_quirks=True, device=0, output="numpy"):
@@ -583,67 +649,20 @@ def vary_boxsize(movie, boxsizes=np.arange(5, 150, 2), delta_x=1.0, delta_t=1.0,
     ``(n_boxes, T-1, N_i, N_j)``.  Without it no full-size field stack exists on either side.
     ``filename``: the dict is saved with ``np.save``.  ``output="torch"``: ``movie`` may be a device tensor and the field
     stacks stay on the device as float64 tensors; the summaries are numpy arrays in both modes."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
     boxes = [int(round(float(b))) for b in np.asarray(boxsizes).ravel()]
     if not boxes:
         raise ValueError("boxsizes is empty")
     if min(boxes) < 1:
         raise ValueError("every box size must be >= 1")
     edges = _sweep_edges("histogram", histogram_bins, histogram_range)
-    T, N_i, N_j = _sweep_shape(movie)
-    probes = _sweep_probes(probe_locations, N_i, N_j)
     taps = None if smoothing_sigma is None else gaussian_taps(smoothing_sigma)
-    fields = None
-    if output == "torch":
-        import torch
-        dev = torch.device("cuda", int(device))
-        frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
-        with _box_flow_context(N_i, N_j, 1, device) as solver:
-            if background is not None:
-                blurred = torch.empty_like(frames)
-                torch.cuda.synchronize(dev)          # the library launches on its own stream
-                solver.blur_dev(frames, blurred, T, gaussian_taps(10))
-                frames = torch.where(blurred > background, frames - background, torch.zeros_like(frames))
-            if return_fields:
-                fields = [torch.empty((len(boxes), T - 1, N_i, N_j), dtype=torch.float64, device=dev)
-                          for _ in range(4 if include_remodelling else 3)]
-            torch.cuda.synchronize(dev)
-            rec, hist, probe_speeds = solver.vary_boxsize_dev(frames, T, boxes, delta_x, delta_t, include_remodelling,
-                                                              reference_quirks, taps, edges, probes, *(fields or []))
-    else:
-        source = np.asarray(movie)
-        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
-            movie_to_analyse = source
-            if background is not None:                                          # OF.py:195-198
-                movie_for_thresholding = blur_movie(source, smoothing_sigma=10, device=device, _solver=solver)
-                movie_to_analyse = np.zeros_like(movie_for_thresholding)
-                mask = movie_for_thresholding > background
-                movie_to_analyse[mask] = source[mask] - background
-            rec, hist, probe_speeds, fields = solver.vary_boxsize_host(movie_to_analyse, boxes, delta_x, delta_t, include_remodelling,
-                                                                       reference_quirks, taps, edges, probes, return_fields)
-    result = dict()
-    result["boxsizes"] = np.asarray(boxes)
-    result["speed_means"] = rec["speed_mean"].copy()
-    result["speed_stds"] = np.sqrt(rec["speed_variance"])
-    result["nonfinite_counts"] = rec["nonfinite_count"].copy()
-    if include_remodelling:
-        result["remodelling_means"] = rec["remodelling_mean"].copy()
-        result["remodelling_stds"] = np.sqrt(rec["remodelling_variance"])
-    if edges is not None:
-        result["speed_histograms"] = hist
-        result["histogram_edges"] = edges
-    if probes is not None:
-        result["probe_speeds"] = probe_speeds
-    if return_fields:
-        result["v_x"], result["v_y"], result["speed"] = fields[0], fields[1], fields[2]
-        if include_remodelling:
-            result["net_remodelling"] = fields[3]
-    result["delta_x"] = delta_x
-    result["delta_t"] = delta_t
-    if filename is not None:
-        np.save(filename, result)
-    return result
+
+    def native(entry, head, probes, tail):
+        return entry(*head, boxes, delta_x, delta_t, include_remodelling, reference_quirks, taps, edges, probes, *tail)
+
+    summaries, fields = _run_sweep("vary_boxsize", native, movie, len(boxes), background, include_remodelling, probe_locations,
+                                   return_fields, device, output)
+    return _sweep_result({"boxsizes": np.asarray(boxes)}, summaries, fields, {}, edges, include_remodelling, delta_x, delta_t, filename)
 
 
 def vary_blursize(movie, blursizes=np.arange(0.5, 15, 0.1), boxsize=21, delta_x=1.0, delta_t=1.0, background=None,
@@ -675,8 +694,6 @@ def vary_blursize(movie, blursizes=np.arange(0.5, 15, 0.1), boxsize=21, delta_x=
     Without it no full-size field stack exists on either side.
     ``filename``: the dict is saved with ``np.save``.  ``output="torch"``: ``movie`` may be a device tensor and the field
     stacks stay on the device as float64 tensors; the summaries are numpy arrays in both modes."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
     sigmas = np.asarray(blursizes, dtype=np.float64).ravel()
     if sigmas.size == 0:
         raise ValueError("blursizes is empty")
@@ -688,67 +705,22 @@ def vary_blursize(movie, blursizes=np.arange(0.5, 15, 0.1), boxsize=21, delta_x=
     intensity_edges = _sweep_edges("intensity", intensity_bins, intensity_range)
     if angle_bins is not None and not 1 <= int(angle_bins) <= 128:
         raise ValueError("angle_bins must be 1 .. 128")
-    T, N_i, N_j = _sweep_shape(movie)
-    probes = _sweep_probes(probe_locations, N_i, N_j)
     taps = [gaussian_taps(s) for s in sigmas]
-    fields = None
-    if output == "torch":
-        import torch
-        dev = torch.device("cuda", int(device))
-        frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
-        with _box_flow_context(N_i, N_j, 1, device) as solver:
-            if background is not None:
-                blurred = torch.empty_like(frames)
-                torch.cuda.synchronize(dev)          # the library launches on its own stream
-                solver.blur_dev(frames, blurred, T, gaussian_taps(10))
-                frames = torch.where(blurred > background, frames - background, torch.zeros_like(frames))
-            if return_fields:
-                fields = [torch.empty((len(taps), T - 1, N_i, N_j), dtype=torch.float64, device=dev)
-                          for _ in range(4 if include_remodelling else 3)]
-            torch.cuda.synchronize(dev)
-            summaries = solver.vary_blursize_dev(frames, T, taps, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks,
-                                                 edges, angle_bins, intensity_edges, probes, *(fields or []))
-    else:
-        source = np.asarray(movie)
-        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
-            movie_to_analyse = source
-            if background is not None:                                          # OF.py:195-198
-                movie_for_thresholding = blur_movie(source, smoothing_sigma=10, device=device, _solver=solver)
-                movie_to_analyse = np.zeros_like(movie_for_thresholding)
-                mask = movie_for_thresholding > background
-                movie_to_analyse[mask] = source[mask] - background
-            *summaries, fields = solver.vary_blursize_host(movie_to_analyse, taps, int(boxsize), delta_x, delta_t, include_remodelling,
-                                                           reference_quirks, edges, angle_bins, intensity_edges, probes, return_fields)
-    rec, hist, angle_hist, weighted_angle_hist, intensity_hist, probe_speeds = summaries
-    result = dict()
-    result["blursizes"] = sigmas
-    result["speed_means"] = rec["speed_mean"].copy()
-    result["speed_stds"] = np.sqrt(rec["speed_variance"])
-    result["nonfinite_counts"] = rec["nonfinite_count"].copy()
-    if include_remodelling:
-        result["remodelling_means"] = rec["remodelling_mean"].copy()
-        result["remodelling_stds"] = np.sqrt(rec["remodelling_variance"])
-    if edges is not None:
-        result["speed_histograms"] = hist
-        result["histogram_edges"] = edges
+
+    def native(entry, head, probes, tail):
+        return entry(*head, taps, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks, edges, angle_bins,
+                     intensity_edges, probes, *tail)
+
+    summaries, fields = _run_sweep("vary_blursize", native, movie, len(taps), background, include_remodelling, probe_locations,
+                                   return_fields, device, output)
+    own = dict()
     if angle_bins is not None:
-        result["angle_histograms"] = angle_hist
-        result["weighted_angle_histograms"] = weighted_angle_hist
-        result["angle_edges"] = np.linspace(-1.0, 1.0, int(angle_bins) + 1, endpoint=True, dtype=np.float64)
+        own["angle_histograms"], own["weighted_angle_histograms"] = summaries[2], summaries[3]
+        own["angle_edges"] = np.linspace(-1.0, 1.0, int(angle_bins) + 1, endpoint=True, dtype=np.float64)
     if intensity_edges is not None:
-        result["intensity_histograms"] = intensity_hist
-        result["intensity_edges"] = intensity_edges
-    if probes is not None:
-        result["probe_speeds"] = probe_speeds
-    if return_fields:
-        result["v_x"], result["v_y"], result["speed"] = fields[0], fields[1], fields[2]
-        if include_remodelling:
-            result["net_remodelling"] = fields[3]
-    result["delta_x"] = delta_x
-    result["delta_t"] = delta_t
-    if filename is not None:
-        np.save(filename, result)
-    return result
+        own["intensity_histograms"] = summaries[4]
+        own["intensity_edges"] = intensity_edges
+    return _sweep_result({"blursizes": sigmas}, summaries, fields, own, edges, include_remodelling, delta_x, delta_t, filename)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -277,3 +277,51 @@ def test_argument_errors():
             solver.vary_blursize_host(frames, [of.gaussian_taps(1.0)], 7, probe_locations=[(52, 0)])
         stats, *_rest = solver.vary_blursize_host(frames, [of.gaussian_taps(1.0)], 7)      # the context is still good
         assert np.isfinite(stats["speed_mean"]).all() and list(stats["sigma_index"]) == [0]
+
+
+# ---- 6. one statistics tail for both sweeps -----------------------------------------------------------------------------
+TAIL_SEED, TAIL_SIGMA = 237, 0.1
+TAIL_STATS = ("speed_mean", "speed_variance", "remodelling_mean", "remodelling_variance", "nonfinite_count")
+
+
+@pytest.mark.parametrize("rem", [False, True])
+def test_box_one_has_the_bits_of_the_box_size_sweep(rem):
+    """vary_boxsize(movie, [1], smoothing_sigma=s) against vary_blursize(movie, [s], boxsize=1): at half width 0 the ring growth
+    and the direct sums add the same terms in the same order, so fields and every shared summary agree bit for bit - through
+    the wrappers (both pairs in one chunk) and through the _host entries of a one-slot context (two chunks).
+
+    A one-pixel window makes det = dx^2 dy^2 - (dx dy)^2, which rounds to exactly 0 at about every other pixel and is 0 on the
+    border lines, where the derivatives are: over the seeds 0 .. 299 tests/boxsweep_restatement.py leaves 0.477 +- 0.010 of the
+    speed samples finite.  The seed is the one with the largest share, 977 of 1920 (0.509); with remodelling det is a sum of
+    five such terms and 644 of 1920 (0.335) stay finite, no seed comes near a half, so that run asks for a quarter.  sigma 0.1
+    has the single tap 1.0: both sweeps launch their blur, which changes no bit, so the shares counted on the CPU are those of
+    the kernels (a wider blur differs from the oracle's in last bits, which redraws the zeros of det)."""
+    from opticalflow_amd import optical_flow as of, _native
+    from oracle import vof_oracle as orc
+    movie = np.ascontiguousarray(orc.make_texture_stack(40, 3, seed=TAIL_SEED)[:, :24, :40])
+    probes = [(0, 0), (5, 7), (23, 39), (23, 0), (0, 39)]
+    kw = dict(DXDT, include_remodelling=rem, reference_quirks=False, histogram_bins=50, histogram_range=(0.0, 0.05),
+              probe_locations=probes, return_fields=True)
+    box = of.vary_boxsize(movie, [1], smoothing_sigma=TAIL_SIGMA, **kw)
+    blur = of.vary_blursize(movie, [TAIL_SIGMA], boxsize=1, **kw)
+    keys = FIELDS[:4 if rem else 3] + ("speed_means", "speed_stds", "nonfinite_counts", "speed_histograms", "probe_speeds")
+    keys += ("remodelling_means", "remodelling_stds") if rem else ()
+    share = np.isfinite(box["speed"]).mean()
+    print(f"rem {rem}: {share:.4f} of the speed samples finite, {box['speed_histograms'].sum()} in the histogram's range, "
+          f"differing keys {same(box, blur, keys)}")
+    assert share >= (0.25 if rem else 0.5)
+    assert not same(box, blur, keys)
+    assert box["nonfinite_counts"][0] == (~np.isfinite(box["speed"])).sum()
+    # two chunks of one pair
+    frames, taps, edges = np.ascontiguousarray(movie, dtype=np.float64), of.gaussian_taps(TAIL_SIGMA), box["histogram_edges"]
+    with _native.Solver(24, 40, 1) as solver:
+        b_stats, b_hist, b_probes, b_fields = solver.vary_boxsize_host(frames, [1], 0.0913, 10, rem, False, taps, edges, probes, True)
+        z_stats, z_hist, _, _, _, z_probes, z_fields = solver.vary_blursize_host(frames, [taps], 1, 0.0913, 10, rem, False, edges, None,
+                                                                                 None, probes, True)
+    for k in TAIL_STATS:
+        assert b_stats[k].tobytes() == z_stats[k].tobytes(), k
+    assert np.array_equal(b_hist, z_hist) and np.array_equal(b_probes, z_probes, equal_nan=True)
+    for f in range(4 if rem else 3):
+        assert np.array_equal(b_fields[f], z_fields[f], equal_nan=True), FIELDS[f]
+        assert np.array_equal(b_fields[f], box[FIELDS[f]], equal_nan=True), FIELDS[f]
+    assert np.array_equal(b_hist, box["speed_histograms"]) and np.array_equal(b_probes, box["probe_speeds"], equal_nan=True)
