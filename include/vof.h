@@ -160,6 +160,13 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *   VOF_DEBUG_POISON=1         every device buffer is filled with 0xFF bytes (NaN as floating point) when it is allocated: a read of
  *                              workspace nothing has written shows up as a non-finite result
  *   VOF_DEBUG_ALLOC_LOG=1      base, end, size and name of every device buffer on stderr (maps a faulting address to a buffer)
+ *   VOF_FUSED_ENDS=0|1|2|3     (read once by vof_create) the two ends of a batch on the matrix-free level 0.  Bit 0: the prologue of a
+ *                              batch that does not start from zero (right-hand side, initial guess, initial residual and its copy)
+ *                              in one pass of k_stream_apply0; bit 1: the epilogue (independent residual norm, the four outputs, the
+ *                              functionals) in one pass.  Default 3; 0: the stand-alone kernels k_rhs_norm, k_gather_guess /
+ *                              k_fill, the residual pass and k_finalize_functionals.  The four outputs are the same bits for the
+ *                              same solution (tested); the vectors are the same expressions in the same order (not compared
+ *                              bit by bit); the block partial sums add in another order
  *   VOF_TRACE_HOST=1           vof_solve_stack_host: timeline of the host pipeline (page touching, pinning, copies, batches) on stderr */
 
 /* One context = one device = one host thread at a time.  Owns device workspaces for images of

@@ -155,6 +155,8 @@ struct vof_ctx {
                                 // pre-smoothing pass (k_sweep0r, TRAIL = 2)
     bool fuse_b = true;         // VOF_FUSE_B=0: the stand-alone kernels k_update_s / k_update_p instead of the vector update folded
                                 // into the cycle's first pre-smoothing pass (k_sweep0r, BF = 1 / 2)
+    int fused_ends = 3;         // VOF_FUSED_ENDS: bit 0 the batch prologue (b, x0, r0, r^), bit 1 the epilogue (residual norm, outputs,
+                                // functionals) in one pass of k_stream_apply0 each; 0: the stand-alone kernels
     long sweep0r_min_blocks = 512;   // level 0, float64 vectors, even n_j: the register-resident pass k_sweep0r for launches of at least
                                      // this many one-wave blocks, the LDS-ring pass k_sweep0m below (VOF_SWEEP0R_MIN_BLOCKS; the tests set 0)
     int tail_first = -1;        // first level of the tail (-1: no tail for this grid)
@@ -517,11 +519,11 @@ void apply_fine_t(vof_ctx* c, const XT* x, const BT* b, YT* y, int mode, int np,
     if (mode)
         k_stream_apply0<1, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
             c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy);
+            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy, ApEnds{});
     else
         k_stream_apply0<0, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
             c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy);
+            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy, ApEnds{});
 }
 
 template <typename VT>
@@ -560,6 +562,38 @@ int residual_d(vof_ctx* c, const double* x, const double* b, double* out, int np
     if (c->L[0].C) { apply_stored_t<double>(c, 0, x, b, out, 1, np, active); return 0; }
     apply_fine_t<double, double, double>(c, x, b, out, 1, np, active, nullptr, want_norm ? 1 : 0, out2);
     return want_norm ? apply_grid(c, np).nblk : 0;
+}
+
+// The two ends of a batch on the matrix-free level 0, one pass each (k_stream_apply0, MODE 2 and 3; VOF_FUSED_ENDS).  Both
+// return the number of per-pair block partials they wrote.
+// Prologue of a batch that does not start from zero: b, x0 (the saved solution src[pair], or the constants where src[pair] < 0 or
+// src == nullptr), r0 = b - A x0 and r^ = r0, with the partials of (b, b) in slot 0 and of (r0, r0) in slot 1 of c->partials.
+int fused_prologue(vof_ctx* c, const int* src, double c0, double c1, double c2, int np) {
+    Level& lv = c->L[0];
+    // algorithmic: k_rhs_norm (16 + 24), k_gather_guess (24 + 24; k_fill 24) and the residual pass (8 + 24 + 24 + 24 + 24)
+    Prof p(c, VOF_K_RHS, 0, (src ? 192.0 : 168.0) * lv.npts, (src ? 136.0 : 112.0) * lv.npts);
+    ApplyGrid ag = apply_grid(c, np);
+    ApEnds e{};
+    e.saved = c->warm_x; e.src = src; e.c0 = c0; e.c1 = c1; e.c2 = c2; e.xo = c->kx; e.bo = c->kb;
+    k_stream_apply0<2, double, double, double><<<ag.grid, AP_THREADS, 0, c->stream>>>(
+        c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
+        c->prm.reference_quirks, nullptr, nullptr, c->kr, nullptr, 0, c->partials, ag.nblk, nullptr, c->pp, c->krh, e);
+    return ag.nblk;
+}
+// Epilogue: the norm of the independent residual b - A x (slot 0 of c->partials) and, from the same rows of x, the outputs and
+// the partials of the three functionals (`fpart`, [pair][3][nblk]).
+int fused_epilogue(vof_ctx* c, double* vx, double* vy, double* gm, double* speed, double* fpart, int np) {
+    Level& lv = c->L[0];
+    const double out = speed ? 32.0 : 24.0;
+    // algorithmic: the norm-only residual pass (8 + 24 + 24) and k_finalize_functionals (24 + 16 + outputs)
+    Prof p(c, VOF_K_FINALIZE, 0, (96.0 + out) * lv.npts, (64.0 + out) * lv.npts);
+    ApplyGrid ag = apply_grid(c, np);
+    ApEnds e{};
+    e.vscale = c->prm.delta_x / c->prm.delta_t; e.vx = vx; e.vy = vy; e.gm = gm; e.speed = speed; e.fpartials = fpart;
+    k_stream_apply0<3, double, double, double><<<ag.grid, AP_THREADS, 0, c->stream>>>(
+        c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
+        c->prm.reference_quirks, c->kx, c->kb, nullptr, nullptr, 1, c->partials, ag.nblk, nullptr, c->pp, nullptr, e);
+    return ag.nblk;
 }
 
 template <typename VT>
@@ -1644,17 +1678,26 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
     double sx = P.delta_t / P.delta_x;
     const bool zero_guess = !guess_src && (P.initial_v_x == 0.0 && P.initial_v_y == 0.0 && P.initial_remodelling == 0.0);
     double* rh = c->krh;   // r^: from the zero guess it IS b (read-only from here on) - no copy; a restart switches to the real buffer
-    {   // b and the block partial sums of (b, b) in one pass; from the zero guess r0 = b is written along
+    // the fused prologue (k_stream_apply0<2>): b, x0, r0 = b - A x0 and r^ = r0 in one pass over level 0, with (b, b) and
+    // (r0, r0) in slots 0 and 1 of the partials
+    const bool fuse_pro = (c->fused_ends & 1) && !zero_guess && residual_copy_ok(c) && !c->direct_on;
+    int nbb = c->nblk;                          // per-pair partial sums of (b, b) ...
+    int nb0 = c->nblk;                          // ... and of (r0, r0): from the zero guess those of (b, b), still in place
+    const double* part_r0 = c->partials;
+    if (fuse_pro) {
+        c->cur_units = np;
+        nbb = nb0 = fused_prologue(c, guess_src, P.initial_v_x * sx, P.initial_v_y * sx, P.initial_remodelling, np);
+        part_r0 = c->partials + nb0;
+    } else {   // b and the block partial sums of (b, b) in one pass; from the zero guess r0 = b is written along
         Prof p(c, VOF_K_RHS, 0);
         k_rhs_norm<<<rgrid(c, np), RBLK, 0, s>>>(frames_dev, frame_stride(c), c->Nj, f.ni, f.nj, c->kb, zero_guess ? c->kr : nullptr,
                                                 c->partials, c->pp);
     }
-    { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_BNORM><<<np, 64, 0, s>>>(c->sc, c->partials, c->nblk, c->active, P.rtol, P.max_iterations); }
-    int nb0 = c->nblk;   // per-pair partial sums of (r0, r0): from the zero guess they are those of (b, b), still in place
+    { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_BNORM><<<np, 64, 0, s>>>(c->sc, c->partials, nbb, c->active, P.rtol, P.max_iterations); }
     if (zero_guess) {
         HIPCHK(hipMemsetAsync(c->kx, 0, (size_t)np * len * sizeof(double), s));
         rh = c->kb;
-    } else {
+    } else if (!fuse_pro) {
         if (guess_src) {   // warm start from the solution of a neighbouring, already solved pair (cf. OF.py:803-806)
             Prof p(c, VOF_K_VECTOR, 0, 16.0 * len);
             k_gather_guess<<<rgrid(c, np), RBLK, 0, s>>>(c->kx, c->warm_x, guess_src, len, f.npts, P.initial_v_x * sx, P.initial_v_y * sx,
@@ -1666,13 +1709,13 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         const bool two = residual_copy_ok(c);
         nb0 = residual_d(c, c->kx, c->kb, c->kr, np, nullptr, 1, two ? c->krh : nullptr);
         if (!two) HIPCHK(hipMemcpyAsync(c->krh, c->kr, (size_t)np * len * sizeof(double), hipMemcpyDeviceToDevice, s));
+        // (p and v need no initialisation: the first iteration after a (re)start sets p = r without reading either)
+        if (!nb0) {   // the operator kernel in use does not fuse the norm
+            Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kr, c->kr, nullptr, nullptr, len, c->partials, nullptr);
+            nb0 = c->nblk;
+        }
     }
-    // (p and v need no initialisation: the first iteration after a (re)start sets p = r without reading either)
-    if (!nb0) {   // the operator kernel in use does not fuse the norm
-        Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kr, c->kr, nullptr, nullptr, len, c->partials, nullptr);
-        nb0 = c->nblk;
-    }
-    { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_R0><<<np, 64, 0, s>>>(c->sc, c->partials, nb0, c->active, P.rtol, P.max_iterations); }
+    { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_R0><<<np, 64, 0, s>>>(c->sc, part_r0, nb0, c->active, P.rtol, P.max_iterations); }
 
     // krylov_method: 0 = BiCGStab only (the reference's 'bcgs'); 1 = GMRES only; 2 = BiCGStab, and restarted GMRES for
     // the pairs that have not met the tolerance after `fallback_after` iterations (or broke down)
@@ -1772,7 +1815,18 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         HIPCHK(hipGetLastError());
         return 0;
     };
-    if (int rc = independent_residual(false)) return rc;
+    // ... and on the matrix-free level 0 the outputs and functionals from the same pass over x: they stand unless a pair is
+    // restarted or handed to GMRES below
+    bool finalized = false;
+    if ((c->fused_ends & 2) && residual_copy_ok(c)) {
+        c->cur_units = np;
+        double* fpart = c->partials + (size_t)np * 3 * apply_grid(c, np).nblk;   // (part_per_pair holds both)
+        const int nb3 = fused_epilogue(c, rq.vx, rq.vy, rq.gm, rq.speed, fpart, np);
+        { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_FINAL><<<np, 64, 0, s>>>(c->sc, c->partials, nb3, c->active, P.rtol, P.max_iterations); }
+        { Prof p(c, VOF_K_FINALIZE, 0); k_sum3<<<np, 64, 0, s>>>(fpart, nb3, c->func3); }
+        HIPCHK(hipGetLastError());
+        finalized = true;
+    } else if (int rc = independent_residual(false)) return rc;
     // The stopping rule is evaluated on the independent residual.  BiCGStab tests its recursively updated residual, which
     // drifts from the true one (by rounding; visibly so near the attainable accuracy): pairs it declared converged whose
     // recomputed residual misses the tolerance are restarted from that residual (r = r^ = b - A x, p = v = 0), which a
@@ -1783,6 +1837,7 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
             int nact = count_active(c, np);
             if (nact < 0) { c->err = "stream synchronize failed"; return -2; }
             if (nact == 0) break;
+            finalized = false;
             if (int rc = independent_residual(true)) return rc;   // the restart needs the residual vector itself (rare)
             c->cur_units = nact;
             rh = c->krh;   // (the restarting pairs get their new r^ written; the others are done and no longer read theirs)
@@ -1797,15 +1852,19 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         // tolerance while the true one does not (the usual drift of BiCGStab at tight tolerances)
         int handed_over = 0;
         if (int rc = gmres_phase(c, np, &handed_over)) return rc;
-        if (handed_over)
+        if (handed_over) {
+            finalized = false;
             if (int rc = independent_residual(false)) return rc;
+        }
     }
     // functionals (OF.py:1167-1183) and epilogue (OF.py:1159-1166, 1189-1191)
-    { Prof p(c, VOF_K_FINALIZE, 0);   // one pass over the solution: outputs + functionals
-      k_finalize_functionals<<<rgrid(c, np), RBLK, 0, s>>>(frames_dev, frame_stride(c), f.ni, f.nj, P.speed_alpha, P.remodelling_alpha,
-                                                           P.reference_quirks, c->kx, P.delta_x / P.delta_t, rq.vx, rq.vy, rq.gm, rq.speed,
-                                                           c->partials, c->pp);
-      k_sum3<<<np, 64, 0, s>>>(c->partials, c->nblk, c->func3); }
+    if (!finalized) {   // one pass over the solution: outputs + functionals
+        Prof p(c, VOF_K_FINALIZE, 0);
+        k_finalize_functionals<<<rgrid(c, np), RBLK, 0, s>>>(frames_dev, frame_stride(c), f.ni, f.nj, P.speed_alpha, P.remodelling_alpha,
+                                                             P.reference_quirks, c->kx, P.delta_x / P.delta_t, rq.vx, rq.vy, rq.gm, rq.speed,
+                                                             c->partials, c->pp);
+        k_sum3<<<np, 64, 0, s>>>(c->partials, c->nblk, c->func3);
+    }
     HIPCHK(hipGetLastError());
     if (stats) {
         HIPCHK(hipMemcpyAsync(c->h_sc, c->sc, np * sizeof(PairScalars), hipMemcpyDeviceToHost, s));
@@ -2008,6 +2067,7 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     if (const char* e = getenv("VOF_SWEEP0R_MIN_BLOCKS")) c->sweep0r_min_blocks = atol(e);
     if (const char* e = getenv("VOF_FUSE_B")) c->fuse_b = e[0] != '0';
     if (const char* e = getenv("VOF_FUSE_RR")) c->fuse_rr = e[0] != '0';
+    if (const char* e = getenv("VOF_FUSED_ENDS")) { const int v = atoi(e); if (v >= 0 && v <= 3) c->fused_ends = v; }
     // level shapes
     Level l0; l0.ni = n_i - 2; l0.nj = n_j - 2; l0.npts = (size_t)l0.ni * l0.nj;
     c->L.push_back(l0);
@@ -2089,7 +2149,8 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     {
         int nblk_apply = ((l0.nj + AP_OUT - 1) / AP_OUT) * ((l0.ni + 31) / 32 + 1);   // smallest band height: 32 rows
         nblk_apply = std::max(nblk_apply, ((l0.nj + 99) / 100) * ((l0.ni + 1 + 31) / 32 + 1));   // k_sweep0m's trailing stage (strips >= 108 columns)
-        c->part_per_pair = (size_t)3 * std::max(c->nblk, nblk_apply);
+        // twice three slots: the fused epilogue keeps the functionals' partials behind those of the residual norm
+        c->part_per_pair = (size_t)6 * std::max(c->nblk, nblk_apply);
         if (int rc = dev_alloc(c, &c->partials, (size_t)B * c->part_per_pair)) return rc;
     }
     if (int rc = dev_alloc(c, &c->sc, (size_t)B)) return rc;

@@ -3261,16 +3261,39 @@ constexpr int AP_OUT = 128, AP_W = 132, AP_THREADS = 256;
 constexpr int AP_RING = 6;
 __device__ __forceinline__ int ap_slot(int row) { return (row + 64 * AP_RING) % AP_RING; }   // row >= -64 * AP_RING
 
+// The two ends of a batch run the same ring (MODE 2 and 3, float64 vectors; their extra arguments travel in ApEnds):
+//   MODE 2, prologue of a batch that does not start from zero: the right-hand side b (the expressions of k_rhs_norm, the second
+//     frame through a ring of its own), the initial guess x0 (the saved solution src[pair] of `saved`, or the constants where
+//     src[pair] < 0 or src == nullptr, as k_gather_guess / k_fill write it), r0 = b - A x0 and its copy, with the block partials of
+//     (b, b) in slot 0 and of (r0, r0) in slot 1: frames and guess in, b, x0, r0, r^ out (136 B per pixel instead of 192).
+//   MODE 3, epilogue: the norm of b - A x (slot 0, no residual vector) and, from the same rows of x, what k_finalize_functionals
+//     computes: the four outputs on the full grid with the mirror fix-up (the owner of interior row / column 1 and n - 2 also
+//     writes the border that mirrors it) and the block partials of the three functionals in `fpartials` (96 B instead of 128).
+struct ApEnds {
+    const double* saved; const int* src; double c0, c1, c2;   // MODE 2: the guess
+    double* xo; double* bo;                                   // MODE 2: x0 and b (written)
+    double vscale; double *vx, *vy, *gm, *speed;              // MODE 3: outputs (speed may be nullptr)
+    double* fpartials;                                        // MODE 3: [pair][3][nblk] for k_sum3
+};
+
+// (MODE 3 carries the outputs and the functionals' sums on top of MODE 1: held to the three waves per SIMD of MODE 1.  For the
+// other modes the attribute says 1, which is the default lower bound of a 256-thread kernel: their code is what it was without it)
 template <int MODE, typename XT, typename BT, typename YT>
-__global__ __launch_bounds__(AP_THREADS) void k_stream_apply0(
+__global__ __launch_bounds__(AP_THREADS) __attribute__((amdgpu_waves_per_eu(MODE == 3 ? 3 : 1))) void k_stream_apply0(
     const double* __restrict__ frames, size_t frame_stride, int Nj, int ni, int nj, int TI, double alpha, double beta,
     int quirks, const XT* __restrict__ x, const BT* __restrict__ b, YT* __restrict__ y,
     const double* __restrict__ dotvec, int want_yy, double* __restrict__ partials, int nblk,
-    const int* __restrict__ active, const PairParam* __restrict__ pp, YT* __restrict__ ycopy) {
+    const int* __restrict__ active, const PairParam* __restrict__ pp, YT* __restrict__ ycopy, ApEnds e) {
     // ycopy (or nullptr): a second copy of the result (the shadow residual of a warm-started solve)
     __shared__ XT xs[AP_RING * 3 * AP_W];
     __shared__ double im[AP_RING * AP_W];
-    __shared__ double red[2][AP_THREADS / 64];
+    __shared__ double jm[MODE == 2 ? AP_RING * AP_W : 1];   // MODE 2: the pair's second frame, as im
+    __shared__ double red[MODE == 3 ? 5 : 2][AP_THREADS / 64];
+    // what a mode never takes is known when it is compiled (MODE 2 / 3: no dot partner; MODE 3: the norm alone, no vector)
+    const double* const dotv = MODE >= 2 ? nullptr : dotvec;
+    const int wyy = MODE == 3 ? 1 : want_yy;
+    YT* const yo = MODE == 3 ? nullptr : y;
+    YT* const yc = MODE == 3 ? nullptr : ycopy;
     const int pair = blockIdx.z;
     if (active && !active[pair]) return;
     int fidx = pair;
@@ -3284,6 +3307,13 @@ __global__ __launch_bounds__(AP_THREADS) void k_stream_apply0(
     const size_t npts = (size_t)ni * nj, off = (size_t)pair * 3 * npts;
     const XT* xp = x + off;
     const double* img = frames + (size_t)fidx * frame_stride;
+    if (MODE == 2) {   // the guess: a saved solution, or (xp == nullptr) the constants
+        const int sp = e.src ? e.src[pair] : -1;
+        xp = sp >= 0 ? (const XT*)(e.saved + (size_t)sp * 3 * npts) : nullptr;
+    }
+    const size_t obase = MODE == 3 ? (size_t)(pp ? pp[pair].out : pair) * (size_t)(ni + 2) * Nj : 0;
+    double f0 = 0.0, f1 = 0.0, f2 = 0.0;   // MODE 3: the functionals' sums
+    double jn = 0.0;                        // MODE 3: second frame at this thread's point of the next step
     // x ring local column of q is col + 1 (local 0 <-> q0 - 1); ghost columns fold onto their mirror
     const bool oL = q - 1 < 0, oR = q + 1 >= nj;
     const int cC = col + 1, cL = oL ? col + 2 : col, cR = oR ? col : col + 2;
@@ -3294,32 +3324,49 @@ __global__ __launch_bounds__(AP_THREADS) void k_stream_apply0(
     double dn0 = 0.0, dn1 = 0.0, dn2 = 0.0;
     for (int s = -2; s < nsteps; ++s) {
         const int r = 2 * s;
-        const BT bc0 = bn0, bc1 = bn1, bc2 = bn2;
+        BT bc0 = bn0, bc1 = bn1, bc2 = bn2;
+        const double jc = jn;
         const double dc0 = dn0, dc1 = dn1, dc2 = dn2;
         // ---- global loads of relative row r + 3 + half into registers
         const int rl = r + 3 + half, pl = p0 + rl;
         const bool row_ld = rl <= TI && pl >= 0 && pl < ni;
         const bool irow_ld = rl <= TI && pl + 1 >= 0 && pl + 1 <= ni + 1;
         XT l0 = (XT)0, l1 = (XT)0, l2 = (XT)0, h0 = (XT)0, h1 = (XT)0, h2 = (XT)0;
-        double li0 = 0.0, li1 = 0.0;
+        double li0 = 0.0, li1 = 0.0, lj0 = 0.0, lj1 = 0.0;
         if (row_ld) {
-            const XT* xr = xp + (size_t)pl * nj;
-            if (col_ok) { l0 = xr[q]; l1 = xr[npts + q]; l2 = xr[2 * npts + q]; }
             // halo columns q0 - 1 (lane 0) and q0 + 128 (lane 127)
             const int qh = (col == 0) ? q0 - 1 : q0 + AP_OUT;
-            if ((col == 0 || col == 127) && qh >= 0 && qh < nj) { h0 = xr[qh]; h1 = xr[npts + qh]; h2 = xr[2 * npts + qh]; }
+            const bool halo = (col == 0 || col == 127) && qh >= 0 && qh < nj;
+            if (MODE == 2 && !xp) {
+                if (col_ok) { l0 = (XT)e.c0; l1 = (XT)e.c1; l2 = (XT)e.c2; }
+                if (halo) { h0 = (XT)e.c0; h1 = (XT)e.c1; h2 = (XT)e.c2; }
+            } else {
+                const XT* xr = xp + (size_t)pl * nj;
+                if (col_ok) { l0 = xr[q]; l1 = xr[npts + q]; l2 = xr[2 * npts + q]; }
+                if (halo) { h0 = xr[qh]; h1 = xr[npts + qh]; h2 = xr[2 * npts + qh]; }
+            }
+            if (MODE == 2 && rl >= 0 && rl < TI && col_ok) {   // x0: the rows and columns this block owns
+                const size_t idl = off + (size_t)pl * nj + q;
+                e.xo[idl] = (double)l0; e.xo[npts + idl] = (double)l1; e.xo[2 * npts + idl] = (double)l2;
+            }
         }
         if (irow_ld) {
             const double* ir = img + (size_t)(pl + 1) * Nj;
             if (q0 + col <= nj + 1) li0 = ir[q0 + col];
             if (col < 2 && q0 + 128 + col <= nj + 1) li1 = ir[q0 + 128 + col];
+            if (MODE == 2) {
+                const double* jr = ir + frame_stride;
+                if (q0 + col <= nj + 1) lj0 = jr[q0 + col];
+                if (col < 2 && q0 + 128 + col <= nj + 1) lj1 = jr[q0 + 128 + col];
+            }
         }
         {   // b / dot partner of the row this thread computes in the next step
             const int rcn = r + 2 + half, pn = p0 + rcn;
             if (s + 1 >= 0 && rcn < TI && pn < ni && col_ok) {
                 const size_t idn = (size_t)pn * nj + q;
                 if (MODE == 1) { bn0 = b[off + idn]; bn1 = b[off + npts + idn]; bn2 = b[off + 2 * npts + idn]; }
-                if (dotvec) { dn0 = dotvec[off + idn]; dn1 = dotvec[off + npts + idn]; dn2 = dotvec[off + 2 * npts + idn]; }
+                if (dotv) { dn0 = dotv[off + idn]; dn1 = dotv[off + npts + idn]; dn2 = dotv[off + 2 * npts + idn]; }
+                if (MODE == 3) jn = img[frame_stride + (size_t)(pn + 1) * Nj + q + 1];
             }
         }
         // ---- compute relative row r + half
@@ -3362,26 +3409,77 @@ __global__ __launch_bounds__(AP_THREADS) void k_stream_apply0(
             y1 += (P * (k.Dyy - 2 * P) - 4 * alpha) * n.w[4] + P * k.Dxy * n.u[4];
             y2 += (-1 - 4 * beta) * n.g[4] + k.Dx * n.u[4] + k.Dy * n.w[4];
             const size_t idx = (size_t)p * nj + q;
-            if (MODE == 1) {
+            if (MODE == 2) {   // b as k_rhs_norm forms it (rounded products: no contraction into the residual below)
+                const double* j0 = jm + sU * AP_W;
+                const double* j1 = jm + sC * AP_W;
+                const double* j2 = jm + sD * AP_W;
+                const double dxt = (j2[col + 1] - j0[col + 1] - ip0 + im0) / 2;
+                const double dyt = (j1[col + 2] - j1[col] - i0p + i0m) / 2;
+                const double dt = j1[col + 1] - i00;
+                {
+#pragma clang fp contract(off)
+                    bc0 = -P * dxt; bc1 = -P * dyt; bc2 = -dt;
+                }
+                e.bo[off + idx] = bc0; e.bo[off + npts + idx] = bc1; e.bo[off + 2 * npts + idx] = bc2;
+                s0 += (double)bc0 * bc0 + (double)bc1 * bc1 + (double)bc2 * bc2;
+            }
+            if (MODE == 3) {   // functional terms of this pixel, as in k_finalize_functionals
+                const double u0 = n.u[4], w0 = n.w[4], g0 = n.g[4];
+                const double dt = jc - k.P;
+                const double dux = (n.u[7] - n.u[1]) / 2, dwx = (n.w[7] - n.w[1]) / 2, dgx = (n.g[7] - n.g[1]) / 2;
+                const double duy = quirks ? dux : (n.u[5] - n.u[3]) / 2;
+                const double dwy = quirks ? dwx : (n.w[5] - n.w[3]) / 2;
+                const double dgy = quirks ? dgx : (n.g[5] - n.g[3]) / 2;
+                const double ee = dt + u0 * k.Dx + w0 * k.Dy + k.P * dux + k.P * dwy - g0;
+                f0 += ee * ee;
+                f1 += dux * dux + duy * duy + dwx * dwx + dwy * dwy;
+                f2 += dgx * dgx + dgy * dgy;
+            }
+            if (MODE == 3) { bc0 = b[off + idx]; bc1 = b[off + npts + idx]; bc2 = b[off + 2 * npts + idx]; }
+            if (MODE >= 1) {
                 y0 = (double)bc0 - y0;
                 y1 = (double)bc1 - y1;
                 y2 = (double)bc2 - y2;
             }
-            if (y) {   // (nullptr: only the reductions are wanted)
-                y[off + idx] = (YT)y0;
-                y[off + npts + idx] = (YT)y1;
-                y[off + 2 * npts + idx] = (YT)y2;
+            if (yo) {   // (nullptr: only the reductions are wanted)
+                yo[off + idx] = (YT)y0;
+                yo[off + npts + idx] = (YT)y1;
+                yo[off + 2 * npts + idx] = (YT)y2;
             }
-            if (ycopy) {
-                ycopy[off + idx] = (YT)y0;
-                ycopy[off + npts + idx] = (YT)y1;
-                ycopy[off + 2 * npts + idx] = (YT)y2;
+            if (yc) {
+                yc[off + idx] = (YT)y0;
+                yc[off + npts + idx] = (YT)y1;
+                yc[off + 2 * npts + idx] = (YT)y2;
             }
-            if (dotvec) {
+            if (MODE == 2) {
+                s1 += y0 * y0 + y1 * y1 + y2 * y2;
+            } else if (dotv) {
                 s0 += y0 * dc0 + y1 * dc1 + y2 * dc2;
-                if (want_yy) s1 += y0 * y0 + y1 * y1 + y2 * y2;
-            } else if (want_yy) {
+                if (wyy) s1 += y0 * y0 + y1 * y1 + y2 * y2;
+            } else if (wyy) {
                 s0 += y0 * y0 + y1 * y1 + y2 * y2;
+            }
+            if (MODE == 3) {   // outputs of this pixel, as in k_finalize_functionals (last: only x of the pixel is still live)
+                const double u0 = n.u[4], w0 = n.w[4], g0 = n.g[4];
+                const double u = u0 * e.vscale, w = w0 * e.vscale;
+                const double sp = e.speed ? sqrt(u * u + w * w) : 0.0;
+                auto put = [&](int i, int j) {
+                    const size_t t = obase + (size_t)i * Nj + j;
+                    e.vx[t] = u; e.vy[t] = w; e.gm[t] = g0;
+                    if (e.speed) e.speed[t] = sp;
+                };
+                // border rows / columns mirror interior row / column 1 and n - 2 (fold): their owner writes them along
+                const int iA = p == 1 ? 0 : -1, iB = p == ni - 2 ? ni + 1 : -1;
+                const int jA = q == 1 ? 0 : -1, jB = q == nj - 2 ? nj + 1 : -1;
+                put(p + 1, q + 1);
+                if ((iA & iB & jA & jB) >= 0) {
+                    const int ri[3] = {p + 1, iA, iB}, cj[3] = {q + 1, jA, jB};
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+#pragma unroll
+                        for (int c2 = 0; c2 < 3; ++c2)
+                            if (a + c2 > 0 && ri[a] >= 0 && cj[c2] >= 0) put(ri[a], cj[c2]);
+                }
             }
         }
         // ---- loaded row -> LDS ring
@@ -3396,14 +3494,23 @@ __global__ __launch_bounds__(AP_THREADS) void k_stream_apply0(
             double* ir = im + sl * AP_W;
             ir[col] = li0;
             if (col < 2) ir[128 + col] = li1;
+            if (MODE == 2) {
+                double* jr = jm + sl * AP_W;
+                jr[col] = lj0;
+                if (col < 2) jr[128 + col] = lj1;
+            }
         }
         __syncthreads();
     }
-    if (partials && (dotvec || want_yy)) {
+    if (partials && (dotv || wyy || MODE == 2)) {
         s0 = wave_sum(s0);
         s1 = wave_sum(s1);
         const int lane = tid & 63, wv = tid >> 6;
         if (lane == 0) { red[0][wv] = s0; red[1][wv] = s1; }
+        if (MODE == 3) {
+            f0 = wave_sum(f0); f1 = wave_sum(f1); f2 = wave_sum(f2);
+            if (lane == 0) { red[2][wv] = f0; red[3][wv] = f1; red[4][wv] = f2; }
+        }
         __syncthreads();
         if (tid == 0) {
             double t0 = 0, t1 = 0;
@@ -3411,7 +3518,13 @@ __global__ __launch_bounds__(AP_THREADS) void k_stream_apply0(
             const int blk = blockIdx.y * gridDim.x + blockIdx.x;
             double* pp = partials + ((size_t)pair * 3) * nblk + blk;
             pp[0] = t0;
-            if (dotvec && want_yy) pp[nblk] = t1;
+            if ((dotv && wyy) || MODE == 2) pp[nblk] = t1;
+            if (MODE == 3) {
+                double g0 = 0, g1 = 0, g2 = 0;
+                for (int i = 0; i < AP_THREADS / 64; ++i) { g0 += red[2][i]; g1 += red[3][i]; g2 += red[4][i]; }
+                double* fp = e.fpartials + ((size_t)pair * 3) * nblk + blk;
+                fp[0] = g0; fp[nblk] = alpha * g1; fp[2 * (size_t)nblk] = beta * g2;
+            }
         }
     }
 }
