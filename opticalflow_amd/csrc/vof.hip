@@ -9,6 +9,7 @@
 #include "vof_device.hpp"
 #include "vof_sweep0r.hpp"
 #include "vof_sweep0p.hpp"
+#include "vof_stream0.hpp"
 #include "vof_direct.hpp"
 #include "vof_boxflow.hpp"
 #include "vof_boxsweep.hpp"
@@ -503,6 +504,12 @@ ApplyGrid apply_grid(const vof_ctx* c, int np) {
     g.nblk = g.grid.x * g.grid.y;
     return g;
 }
+// What both streaming level-0 kernels are given first: frames, level-0 grid, band height TI, model parameters, pair tables.
+ApArgs ap_args(const vof_ctx* c, int TI, const int* active) {
+    const Level& lv = c->L[0];
+    return ApArgs{c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
+                  c->prm.reference_quirks, active, c->pp};
+}
 
 // y = A x (mode 0) or y = b - A x (mode 1) on the matrix-free level 0.  Optional fused reductions into
 // c->partials (slot 0: y.dotvec, or y.y when dotvec == nullptr; slot 1: y.y when both are asked for); the
@@ -516,14 +523,11 @@ void apply_fine_t(vof_ctx* c, const XT* x, const BT* b, YT* y, int mode, int np,
     Prof p(c, VOF_K_APPLY0, 0, bytes);
     ApplyGrid ag = apply_grid(c, np);
     double* part = (dotvec || want_yy) ? c->partials : nullptr;
+    const ApArgs a = ap_args(c, ag.TI, active);
     if (mode)
-        k_stream_apply0<1, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-            c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy, ApEnds{});
+        k_stream_apply0<1, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(a, x, b, y, dotvec, want_yy, part, ag.nblk, ycopy, ApEnds{});
     else
-        k_stream_apply0<0, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-            c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-            c->prm.reference_quirks, x, b, y, dotvec, want_yy, part, ag.nblk, active, c->pp, ycopy, ApEnds{});
+        k_stream_apply0<0, XT, BT, YT><<<ag.grid, AP_THREADS, 0, c->stream>>>(a, x, b, y, dotvec, want_yy, part, ag.nblk, ycopy, ApEnds{});
 }
 
 template <typename VT>
@@ -576,8 +580,7 @@ int fused_prologue(vof_ctx* c, const int* src, double c0, double c1, double c2, 
     ApEnds e{};
     e.saved = c->warm_x; e.src = src; e.c0 = c0; e.c1 = c1; e.c2 = c2; e.xo = c->kx; e.bo = c->kb;
     k_stream_apply0<2, double, double, double><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-        c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-        c->prm.reference_quirks, nullptr, nullptr, c->kr, nullptr, 0, c->partials, ag.nblk, nullptr, c->pp, c->krh, e);
+        ap_args(c, ag.TI, nullptr), nullptr, nullptr, c->kr, nullptr, 0, c->partials, ag.nblk, c->krh, e);
     return ag.nblk;
 }
 // Epilogue: the norm of the independent residual b - A x (slot 0 of c->partials) and, from the same rows of x, the outputs and
@@ -591,8 +594,7 @@ int fused_epilogue(vof_ctx* c, double* vx, double* vy, double* gm, double* speed
     ApEnds e{};
     e.vscale = c->prm.delta_x / c->prm.delta_t; e.vx = vx; e.vy = vy; e.gm = gm; e.speed = speed; e.fpartials = fpart;
     k_stream_apply0<3, double, double, double><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-        c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, ag.TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-        c->prm.reference_quirks, c->kx, c->kb, nullptr, nullptr, 1, c->partials, ag.nblk, nullptr, c->pp, nullptr, e);
+        ap_args(c, ag.TI, nullptr), c->kx, c->kb, nullptr, nullptr, 1, c->partials, ag.nblk, nullptr, e);
     return ag.nblk;
 }
 
@@ -610,9 +612,7 @@ void resrestrict_fine_t(vof_ctx* c, const VT* x, const VT* b, CVT* bc, int np, c
     int TI = pick_band_height(f.ni, (k.nj + RR_CO - 1) / RR_CO, c->cur_units);
     dim3 g((k.nj + RR_CO - 1) / RR_CO, (k.ni + TI / 2 - 1) / (TI / 2), np);
     Prof p(c, VOF_K_APPLY0, 0, (8.0 + 6.0 * sizeof(VT)) * f.npts + 3.0 * sizeof(CVT) * k.npts);
-    k_stream_resrestrict0<VT, VT, CVT><<<g, AP_THREADS, 0, c->stream>>>(
-        c->frames, frame_stride(c), c->Nj, f.ni, f.nj, TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
-        c->prm.reference_quirks, x, b, bc, k.ni, k.nj, active, c->pp);
+    k_stream_resrestrict0<VT, VT, CVT><<<g, AP_THREADS, 0, c->stream>>>(ap_args(c, TI, active), x, b, bc, k.ni, k.nj);
 }
 
 // stored level l >= 1, straight after ONE forward Gauss-Seidel sweep x_old -> x_new (x_old == nullptr: from zero): the coarse

@@ -1122,8 +1122,12 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// Block sums of up to three values into slots 0 .. nslots_used - 1 of partials[pair][slot][blk]: wave sums, one word per wave
+// in LDS, thread 0 adds the waves in order.  c1 / c2 scale the finished sums of slots 1 / 2.  Every caller of one kernel shares
+// the scratch `s`: a barrier between two calls.
 __device__ __forceinline__ void block_store_partials(double v0, double v1, double v2, double* __restrict__ partials,
-                                                     int nslots_used, int nblk, int pair, int blk) {
+                                                     int nslots_used, int nblk, int pair, int blk, double c1 = 1.0,
+                                                     double c2 = 1.0) {
     __shared__ double s[3][RBLK / 64];
     v0 = wave_sum(v0);
     if (nslots_used > 1) v1 = wave_sum(v1);
@@ -1136,8 +1140,8 @@ __device__ __forceinline__ void block_store_partials(double v0, double v1, doubl
         for (int i = 0; i < RBLK / 64; ++i) { t0 += s[0][i]; t1 += s[1][i]; t2 += s[2][i]; }
         double* pp = partials + ((size_t)pair * 3) * nblk + blk;
         pp[0] = t0;
-        if (nslots_used > 1) pp[nblk] = t1;
-        if (nslots_used > 2) pp[2 * (size_t)nblk] = t2;
+        if (nslots_used > 1) pp[nblk] = c1 * t1;
+        if (nslots_used > 2) pp[2 * (size_t)nblk] = c2 * t2;
     }
 }
 
@@ -3243,446 +3247,6 @@ __global__ __launch_bounds__(128 * NS) void k_sweep0m(
             pp[0] = q0;
             if (tr.dotvec && tr.want_vv) pp[nblk] = q1;
         }
-    }
-}
-
-// ==========================================================================================
-// k_stream_apply0: level-0 operator application y = A x (MODE 0) or y = b - A x (MODE 1), matrix-free,
-// streaming over rows through an LDS ring (every array is read once, coalesced; the 9-point neighbourhood and
-// the 3x3 image neighbourhood come from LDS).  A block owns a 128-column aligned strip (+1 halo column each
-// side) and a band of TI rows; per step the two wave pairs compute two rows.  Optional fused reductions:
-// slot 0 = sum y * dotvec (or y * y if dotvec == nullptr and want_yy), slot 1 = sum y * y (dotvec && want_yy);
-// per-block partials are written at index blockIdx.y * gridDim.x + blockIdx.x (deterministic two-stage sum).
-// ==========================================================================================
-constexpr int AP_OUT = 128, AP_W = 132, AP_THREADS = 256;
-// Ring depth: a step loads rows r + 3, r + 4 while rows r - 1 .. r + 2 are read, i.e. six live rows (the fused
-// residual + restriction kernel likewise keeps residual rows 2s - 4 .. 2s + 1).  Six slots instead of the next power of
-// two keep that kernel at 43.8 KB of LDS = 3 workgroups per CU (8 slots: 58 KB = 2 per CU, 2.9 TB/s).
-constexpr int AP_RING = 6;
-__device__ __forceinline__ int ap_slot(int row) { return (row + 64 * AP_RING) % AP_RING; }   // row >= -64 * AP_RING
-
-// The two ends of a batch run the same ring (MODE 2 and 3, float64 vectors; their extra arguments travel in ApEnds):
-//   MODE 2, prologue of a batch that does not start from zero: the right-hand side b (the expressions of k_rhs_norm, the second
-//     frame through a ring of its own), the initial guess x0 (the saved solution src[pair] of `saved`, or the constants where
-//     src[pair] < 0 or src == nullptr, as k_gather_guess / k_fill write it), r0 = b - A x0 and its copy, with the block partials of
-//     (b, b) in slot 0 and of (r0, r0) in slot 1: frames and guess in, b, x0, r0, r^ out (136 B per pixel instead of 192).
-//   MODE 3, epilogue: the norm of b - A x (slot 0, no residual vector) and, from the same rows of x, what k_finalize_functionals
-//     computes: the four outputs on the full grid with the mirror fix-up (the owner of interior row / column 1 and n - 2 also
-//     writes the border that mirrors it) and the block partials of the three functionals in `fpartials` (96 B instead of 128).
-struct ApEnds {
-    const double* saved; const int* src; double c0, c1, c2;   // MODE 2: the guess
-    double* xo; double* bo;                                   // MODE 2: x0 and b (written)
-    double vscale; double *vx, *vy, *gm, *speed;              // MODE 3: outputs (speed may be nullptr)
-    double* fpartials;                                        // MODE 3: [pair][3][nblk] for k_sum3
-};
-
-// (MODE 3 carries the outputs and the functionals' sums on top of MODE 1: held to the three waves per SIMD of MODE 1.  For the
-// other modes the attribute says 1, which is the default lower bound of a 256-thread kernel: their code is what it was without it)
-template <int MODE, typename XT, typename BT, typename YT>
-__global__ __launch_bounds__(AP_THREADS) __attribute__((amdgpu_waves_per_eu(MODE == 3 ? 3 : 1))) void k_stream_apply0(
-    const double* __restrict__ frames, size_t frame_stride, int Nj, int ni, int nj, int TI, double alpha, double beta,
-    int quirks, const XT* __restrict__ x, const BT* __restrict__ b, YT* __restrict__ y,
-    const double* __restrict__ dotvec, int want_yy, double* __restrict__ partials, int nblk,
-    const int* __restrict__ active, const PairParam* __restrict__ pp, YT* __restrict__ ycopy, ApEnds e) {
-    // ycopy (or nullptr): a second copy of the result (the shadow residual of a warm-started solve)
-    __shared__ XT xs[AP_RING * 3 * AP_W];
-    __shared__ double im[AP_RING * AP_W];
-    __shared__ double jm[MODE == 2 ? AP_RING * AP_W : 1];   // MODE 2: the pair's second frame, as im
-    __shared__ double red[MODE == 3 ? 5 : 2][AP_THREADS / 64];
-    // what a mode never takes is known when it is compiled (MODE 2 / 3: no dot partner; MODE 3: the norm alone, no vector)
-    const double* const dotv = MODE >= 2 ? nullptr : dotvec;
-    const int wyy = MODE == 3 ? 1 : want_yy;
-    YT* const yo = MODE == 3 ? nullptr : y;
-    YT* const yc = MODE == 3 ? nullptr : ycopy;
-    const int pair = blockIdx.z;
-    if (active && !active[pair]) return;
-    int fidx = pair;
-    if (pp) { alpha = pp[pair].alpha; beta = pp[pair].beta; fidx = pp[pair].frame; }
-    const int tid = threadIdx.x;
-    const int half = __builtin_amdgcn_readfirstlane(tid >> 7);   // which of the two rows of a step
-    const int col = tid & 127;
-    const int q0 = blockIdx.x * AP_OUT, p0 = blockIdx.y * TI;
-    const int q = q0 + col;
-    const bool col_ok = q < nj;
-    const size_t npts = (size_t)ni * nj, off = (size_t)pair * 3 * npts;
-    const XT* xp = x + off;
-    const double* img = frames + (size_t)fidx * frame_stride;
-    if (MODE == 2) {   // the guess: a saved solution, or (xp == nullptr) the constants
-        const int sp = e.src ? e.src[pair] : -1;
-        xp = sp >= 0 ? (const XT*)(e.saved + (size_t)sp * 3 * npts) : nullptr;
-    }
-    const size_t obase = MODE == 3 ? (size_t)(pp ? pp[pair].out : pair) * (size_t)(ni + 2) * Nj : 0;
-    double f0 = 0.0, f1 = 0.0, f2 = 0.0;   // MODE 3: the functionals' sums
-    double jn = 0.0;                        // MODE 3: second frame at this thread's point of the next step
-    // x ring local column of q is col + 1 (local 0 <-> q0 - 1); ghost columns fold onto their mirror
-    const bool oL = q - 1 < 0, oR = q + 1 >= nj;
-    const int cC = col + 1, cL = oL ? col + 2 : col, cR = oR ? col : col + 2;
-    // image ring local column li <-> full-image column q0 + li; point q uses li = col, col+1, col+2
-    double s0 = 0.0, s1 = 0.0;
-    const int nsteps = TI / 2;
-    BT bn0 = (BT)0, bn1 = (BT)0, bn2 = (BT)0;   // b and the dot partner of this thread's point of the NEXT step (loaded a step ahead)
-    double dn0 = 0.0, dn1 = 0.0, dn2 = 0.0;
-    for (int s = -2; s < nsteps; ++s) {
-        const int r = 2 * s;
-        BT bc0 = bn0, bc1 = bn1, bc2 = bn2;
-        const double jc = jn;
-        const double dc0 = dn0, dc1 = dn1, dc2 = dn2;
-        // ---- global loads of relative row r + 3 + half into registers
-        const int rl = r + 3 + half, pl = p0 + rl;
-        const bool row_ld = rl <= TI && pl >= 0 && pl < ni;
-        const bool irow_ld = rl <= TI && pl + 1 >= 0 && pl + 1 <= ni + 1;
-        XT l0 = (XT)0, l1 = (XT)0, l2 = (XT)0, h0 = (XT)0, h1 = (XT)0, h2 = (XT)0;
-        double li0 = 0.0, li1 = 0.0, lj0 = 0.0, lj1 = 0.0;
-        if (row_ld) {
-            // halo columns q0 - 1 (lane 0) and q0 + 128 (lane 127)
-            const int qh = (col == 0) ? q0 - 1 : q0 + AP_OUT;
-            const bool halo = (col == 0 || col == 127) && qh >= 0 && qh < nj;
-            if (MODE == 2 && !xp) {
-                if (col_ok) { l0 = (XT)e.c0; l1 = (XT)e.c1; l2 = (XT)e.c2; }
-                if (halo) { h0 = (XT)e.c0; h1 = (XT)e.c1; h2 = (XT)e.c2; }
-            } else {
-                const XT* xr = xp + (size_t)pl * nj;
-                if (col_ok) { l0 = xr[q]; l1 = xr[npts + q]; l2 = xr[2 * npts + q]; }
-                if (halo) { h0 = xr[qh]; h1 = xr[npts + qh]; h2 = xr[2 * npts + qh]; }
-            }
-            if (MODE == 2 && rl >= 0 && rl < TI && col_ok) {   // x0: the rows and columns this block owns
-                const size_t idl = off + (size_t)pl * nj + q;
-                e.xo[idl] = (double)l0; e.xo[npts + idl] = (double)l1; e.xo[2 * npts + idl] = (double)l2;
-            }
-        }
-        if (irow_ld) {
-            const double* ir = img + (size_t)(pl + 1) * Nj;
-            if (q0 + col <= nj + 1) li0 = ir[q0 + col];
-            if (col < 2 && q0 + 128 + col <= nj + 1) li1 = ir[q0 + 128 + col];
-            if (MODE == 2) {
-                const double* jr = ir + frame_stride;
-                if (q0 + col <= nj + 1) lj0 = jr[q0 + col];
-                if (col < 2 && q0 + 128 + col <= nj + 1) lj1 = jr[q0 + 128 + col];
-            }
-        }
-        {   // b / dot partner of the row this thread computes in the next step
-            const int rcn = r + 2 + half, pn = p0 + rcn;
-            if (s + 1 >= 0 && rcn < TI && pn < ni && col_ok) {
-                const size_t idn = (size_t)pn * nj + q;
-                if (MODE == 1) { bn0 = b[off + idn]; bn1 = b[off + npts + idn]; bn2 = b[off + 2 * npts + idn]; }
-                if (dotv) { dn0 = dotv[off + idn]; dn1 = dotv[off + npts + idn]; dn2 = dotv[off + 2 * npts + idn]; }
-                if (MODE == 3) jn = img[frame_stride + (size_t)(pn + 1) * Nj + q + 1];
-            }
-        }
-        // ---- compute relative row r + half
-        const int rc = r + half, p = p0 + rc;
-        if (s >= 0 && rc < TI && p < ni && col_ok) {
-            const bool oU = p - 1 < 0, oD = p + 1 >= ni;
-            const int sU = ap_slot(rc - 1), sC = ap_slot(rc), sD = ap_slot(rc + 1);
-            const double* i0 = im + sU * AP_W;
-            const double* i1 = im + sC * AP_W;
-            const double* i2 = im + sD * AP_W;
-            double imm = i0[col], im0 = i0[col + 1], imp = i0[col + 2];
-            double i0m = i1[col], i00 = i1[col + 1], i0p = i1[col + 2];
-            double ipm = i2[col], ip0 = i2[col + 1], ipp = i2[col + 2];
-            PixCoef k;
-            k.P = i00;
-            k.Dx = (ip0 - im0) / 2;
-            k.Dy = quirks ? k.Dx : (i0p - i0m) / 2;
-            k.Dxx = ip0 + im0 - 2 * i00;
-            k.Dyy = i0p + i0m - 2 * i00;
-            k.Dxy = (ipp - ipm - imp + imm) / 4;
-            const XT* ru = xs + (oU ? sD : sU) * 3 * AP_W;   // ghost row -1 mirrors row 1, ghost row n mirrors n-2
-            const XT* rcn = xs + sC * 3 * AP_W;
-            const XT* rd = xs + (oD ? sU : sD) * 3 * AP_W;
-            const double sUL = (oU && oL) ? 2.0 : 1.0, sUR = (oU && oR) ? 2.0 : 1.0;
-            const double sDL = (oD && oL) ? 2.0 : 1.0, sDR = (oD && oR) ? 2.0 : 1.0;
-            Nbr n;
-            n.u[0] = sUL * (double)ru[cL]; n.w[0] = sUL * (double)ru[AP_W + cL];
-            n.u[1] = (double)ru[cC];       n.w[1] = (double)ru[AP_W + cC];       n.g[1] = (double)ru[2 * AP_W + cC];
-            n.u[2] = sUR * (double)ru[cR]; n.w[2] = sUR * (double)ru[AP_W + cR];
-            n.u[3] = (double)rcn[cL];      n.w[3] = (double)rcn[AP_W + cL];      n.g[3] = (double)rcn[2 * AP_W + cL];
-            n.u[4] = (double)rcn[cC];      n.w[4] = (double)rcn[AP_W + cC];      n.g[4] = (double)rcn[2 * AP_W + cC];
-            n.u[5] = (double)rcn[cR];      n.w[5] = (double)rcn[AP_W + cR];      n.g[5] = (double)rcn[2 * AP_W + cR];
-            n.u[6] = sDL * (double)rd[cL]; n.w[6] = sDL * (double)rd[AP_W + cL];
-            n.u[7] = (double)rd[cC];       n.w[7] = (double)rd[AP_W + cC];       n.g[7] = (double)rd[2 * AP_W + cC];
-            n.u[8] = sDR * (double)rd[cR]; n.w[8] = sDR * (double)rd[AP_W + cR];
-            double y0, y1, y2;
-            offdiag0(k, alpha, beta, n, y0, y1, y2);
-            const double P = k.P;
-            y0 += (P * (k.Dxx - 2 * P) - 4 * alpha) * n.u[4] + P * k.Dxy * n.w[4];
-            y1 += (P * (k.Dyy - 2 * P) - 4 * alpha) * n.w[4] + P * k.Dxy * n.u[4];
-            y2 += (-1 - 4 * beta) * n.g[4] + k.Dx * n.u[4] + k.Dy * n.w[4];
-            const size_t idx = (size_t)p * nj + q;
-            if (MODE == 2) {   // b as k_rhs_norm forms it (rounded products: no contraction into the residual below)
-                const double* j0 = jm + sU * AP_W;
-                const double* j1 = jm + sC * AP_W;
-                const double* j2 = jm + sD * AP_W;
-                const double dxt = (j2[col + 1] - j0[col + 1] - ip0 + im0) / 2;
-                const double dyt = (j1[col + 2] - j1[col] - i0p + i0m) / 2;
-                const double dt = j1[col + 1] - i00;
-                {
-#pragma clang fp contract(off)
-                    bc0 = -P * dxt; bc1 = -P * dyt; bc2 = -dt;
-                }
-                e.bo[off + idx] = bc0; e.bo[off + npts + idx] = bc1; e.bo[off + 2 * npts + idx] = bc2;
-                s0 += (double)bc0 * bc0 + (double)bc1 * bc1 + (double)bc2 * bc2;
-            }
-            if (MODE == 3) {   // functional terms of this pixel, as in k_finalize_functionals
-                const double u0 = n.u[4], w0 = n.w[4], g0 = n.g[4];
-                const double dt = jc - k.P;
-                const double dux = (n.u[7] - n.u[1]) / 2, dwx = (n.w[7] - n.w[1]) / 2, dgx = (n.g[7] - n.g[1]) / 2;
-                const double duy = quirks ? dux : (n.u[5] - n.u[3]) / 2;
-                const double dwy = quirks ? dwx : (n.w[5] - n.w[3]) / 2;
-                const double dgy = quirks ? dgx : (n.g[5] - n.g[3]) / 2;
-                const double ee = dt + u0 * k.Dx + w0 * k.Dy + k.P * dux + k.P * dwy - g0;
-                f0 += ee * ee;
-                f1 += dux * dux + duy * duy + dwx * dwx + dwy * dwy;
-                f2 += dgx * dgx + dgy * dgy;
-            }
-            if (MODE == 3) { bc0 = b[off + idx]; bc1 = b[off + npts + idx]; bc2 = b[off + 2 * npts + idx]; }
-            if (MODE >= 1) {
-                y0 = (double)bc0 - y0;
-                y1 = (double)bc1 - y1;
-                y2 = (double)bc2 - y2;
-            }
-            if (yo) {   // (nullptr: only the reductions are wanted)
-                yo[off + idx] = (YT)y0;
-                yo[off + npts + idx] = (YT)y1;
-                yo[off + 2 * npts + idx] = (YT)y2;
-            }
-            if (yc) {
-                yc[off + idx] = (YT)y0;
-                yc[off + npts + idx] = (YT)y1;
-                yc[off + 2 * npts + idx] = (YT)y2;
-            }
-            if (MODE == 2) {
-                s1 += y0 * y0 + y1 * y1 + y2 * y2;
-            } else if (dotv) {
-                s0 += y0 * dc0 + y1 * dc1 + y2 * dc2;
-                if (wyy) s1 += y0 * y0 + y1 * y1 + y2 * y2;
-            } else if (wyy) {
-                s0 += y0 * y0 + y1 * y1 + y2 * y2;
-            }
-            if (MODE == 3) {   // outputs of this pixel, as in k_finalize_functionals (last: only x of the pixel is still live)
-                const double u0 = n.u[4], w0 = n.w[4], g0 = n.g[4];
-                const double u = u0 * e.vscale, w = w0 * e.vscale;
-                const double sp = e.speed ? sqrt(u * u + w * w) : 0.0;
-                auto put = [&](int i, int j) {
-                    const size_t t = obase + (size_t)i * Nj + j;
-                    e.vx[t] = u; e.vy[t] = w; e.gm[t] = g0;
-                    if (e.speed) e.speed[t] = sp;
-                };
-                // border rows / columns mirror interior row / column 1 and n - 2 (fold): their owner writes them along
-                const int iA = p == 1 ? 0 : -1, iB = p == ni - 2 ? ni + 1 : -1;
-                const int jA = q == 1 ? 0 : -1, jB = q == nj - 2 ? nj + 1 : -1;
-                put(p + 1, q + 1);
-                if ((iA & iB & jA & jB) >= 0) {
-                    const int ri[3] = {p + 1, iA, iB}, cj[3] = {q + 1, jA, jB};
-#pragma unroll
-                    for (int a = 0; a < 3; ++a)
-#pragma unroll
-                        for (int c2 = 0; c2 < 3; ++c2)
-                            if (a + c2 > 0 && ri[a] >= 0 && cj[c2] >= 0) put(ri[a], cj[c2]);
-                }
-            }
-        }
-        // ---- loaded row -> LDS ring
-        if (rl <= TI) {
-            const int sl = ap_slot(rl);
-            XT* xr = xs + sl * 3 * AP_W;
-            xr[col + 1] = l0; xr[AP_W + col + 1] = l1; xr[2 * AP_W + col + 1] = l2;
-            if (col == 0 || col == 127) {
-                const int ch = (col == 0) ? 0 : AP_OUT + 1;
-                xr[ch] = h0; xr[AP_W + ch] = h1; xr[2 * AP_W + ch] = h2;
-            }
-            double* ir = im + sl * AP_W;
-            ir[col] = li0;
-            if (col < 2) ir[128 + col] = li1;
-            if (MODE == 2) {
-                double* jr = jm + sl * AP_W;
-                jr[col] = lj0;
-                if (col < 2) jr[128 + col] = lj1;
-            }
-        }
-        __syncthreads();
-    }
-    if (partials && (dotv || wyy || MODE == 2)) {
-        s0 = wave_sum(s0);
-        s1 = wave_sum(s1);
-        const int lane = tid & 63, wv = tid >> 6;
-        if (lane == 0) { red[0][wv] = s0; red[1][wv] = s1; }
-        if (MODE == 3) {
-            f0 = wave_sum(f0); f1 = wave_sum(f1); f2 = wave_sum(f2);
-            if (lane == 0) { red[2][wv] = f0; red[3][wv] = f1; red[4][wv] = f2; }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double t0 = 0, t1 = 0;
-            for (int i = 0; i < AP_THREADS / 64; ++i) { t0 += red[0][i]; t1 += red[1][i]; }
-            const int blk = blockIdx.y * gridDim.x + blockIdx.x;
-            double* pp = partials + ((size_t)pair * 3) * nblk + blk;
-            pp[0] = t0;
-            if ((dotv && wyy) || MODE == 2) pp[nblk] = t1;
-            if (MODE == 3) {
-                double g0 = 0, g1 = 0, g2 = 0;
-                for (int i = 0; i < AP_THREADS / 64; ++i) { g0 += red[2][i]; g1 += red[3][i]; g2 += red[4][i]; }
-                double* fp = e.fpartials + ((size_t)pair * 3) * nblk + blk;
-                fp[0] = g0; fp[nblk] = alpha * g1; fp[2 * (size_t)nblk] = beta * g2;
-            }
-        }
-    }
-}
-
-// ==========================================================================================
-// k_stream_resrestrict0: coarse right-hand side  b_c = R (b - A x)  of level 0 in one pass: the fine residual
-// rows are produced exactly as in k_stream_apply0<1> but kept in a small LDS ring and immediately restricted
-// (full weighting, R = P^T / 4), so the fine residual is never written to / re-read from HBM
-// (I + x(3) + b(3) in, 3/4 out per fine pixel = 62 B instead of 80 + 30).
-// A block owns 63 coarse columns x TI/2 coarse rows: fine columns [126 bx - 1, 126 bx + 127), fine rows
-// [p0 - 1, p0 + TI) with p0 = by * TI (even).
-// ==========================================================================================
-constexpr int RR_CO = 63;   // coarse columns per strip (fine stride 126)
-
-template <typename XT, typename BT, typename CT2>
-__global__ __launch_bounds__(AP_THREADS) void k_stream_resrestrict0(
-    const double* __restrict__ frames, size_t frame_stride, int Nj, int ni, int nj, int TI, double alpha, double beta,
-    int quirks, const XT* __restrict__ x, const BT* __restrict__ b, CT2* __restrict__ bc, int nci, int ncj,
-    const int* __restrict__ active, const PairParam* __restrict__ pp) {
-    __shared__ XT xs[AP_RING * 3 * AP_W];
-    __shared__ double im[AP_RING * AP_W];
-    __shared__ double rs[AP_RING * 3 * 128];     // residual ring [row][field][fine column of the strip]
-    const int pair = blockIdx.z;
-    if (active && !active[pair]) return;
-    int fidx = pair;
-    if (pp) { alpha = pp[pair].alpha; beta = pp[pair].beta; fidx = pp[pair].frame; }
-    const int tid = threadIdx.x;
-    const int half = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int col = tid & 127;
-    const int q0 = blockIdx.x * (2 * RR_CO) - 1;        // first fine column whose residual the strip computes
-    const int p0 = blockIdx.y * TI - 1;                 // first fine row
-    const int q = q0 + col;
-    const bool col_ok = q >= 0 && q < nj;
-    const size_t npts = (size_t)ni * nj, off = (size_t)pair * 3 * npts;
-    const XT* xp = x + off;
-    const double* img = frames + (size_t)fidx * frame_stride;
-    const bool oL = q - 1 < 0, oR = q + 1 >= nj;
-    const int cC = col + 1, cL = oL ? col + 2 : col, cR = oR ? col : col + 2;
-    // restriction phase: thread <-> (field, coarse column of the strip)
-    const int ef = tid / RR_CO, em = tid % RR_CO;
-    const int ecq = blockIdx.x * RR_CO + em;
-    const bool e_on = tid < 3 * RR_CO && ecq < ncj;
-    const size_t ncpts = (size_t)nci * ncj;
-    const int nsteps = TI / 2 + 1;                      // fine rows p0 .. p0 + TI (relative 0 .. TI)
-    BT bn0 = (BT)0, bn1 = (BT)0, bn2 = (BT)0;           // b of this thread's point of the NEXT step (loaded a step ahead: used
-                                                        // at the point of use, its latency was exposed in every step)
-    for (int s = -2; s <= nsteps + 1; ++s) {
-        const int r = 2 * s;
-        const BT bc0 = bn0, bc1 = bn1, bc2 = bn2;
-        // ---- restriction of coarse row k = s - 2 (fine relative rows 2k, 2k+1, 2k+2), computed in earlier steps
-        {
-            const int k = s - 2;
-            const int cp = blockIdx.y * (TI / 2) + k;
-            if (k >= 0 && k < TI / 2 && cp < nci && e_on) {
-                double acc = 0.0;
-#pragma unroll
-                for (int di = -1; di <= 1; ++di) {
-                    const int fp = 2 * cp + di;
-                    if (fp < 0 || fp >= ni) continue;
-                    const double wi = pweight(fp, cp, nci);
-                    const double* row = rs + (ap_slot(2 * k + 1 + di) * 3 + ef) * 128;
-#pragma unroll
-                    for (int dj = -1; dj <= 1; ++dj) {
-                        const int fq = 2 * ecq + dj;
-                        if (fq < 0 || fq >= nj) continue;
-                        acc += wi * pweight(fq, ecq, ncj) * row[2 * em + 1 + dj];
-                    }
-                }
-                bc[(size_t)pair * 3 * ncpts + (size_t)ef * ncpts + (size_t)cp * ncj + ecq] = (CT2)(0.25 * acc);
-            }
-        }
-        // ---- global loads of relative row r + 3 + half into registers
-        const int rl = r + 3 + half, pl = p0 + rl;
-        const bool need = rl <= TI + 1;
-        const bool row_ld = need && pl >= 0 && pl < ni;
-        const bool irow_ld = need && pl + 1 >= 0 && pl + 1 <= ni + 1;
-        XT l0 = (XT)0, l1 = (XT)0, l2 = (XT)0, h0 = (XT)0, h1 = (XT)0, h2 = (XT)0;
-        double li0 = 0.0, li1 = 0.0;
-        if (row_ld) {
-            const XT* xr = xp + (size_t)pl * nj;
-            if (col_ok) { l0 = xr[q]; l1 = xr[npts + q]; l2 = xr[2 * npts + q]; }
-            const int qh = (col == 0) ? q0 - 1 : q0 + 128;
-            if ((col == 0 || col == 127) && qh >= 0 && qh < nj) { h0 = xr[qh]; h1 = xr[npts + qh]; h2 = xr[2 * npts + qh]; }
-        }
-        if (irow_ld) {
-            const double* ir = img + (size_t)(pl + 1) * Nj;
-            const int fc0 = q0 + col, fc1 = q0 + 128 + col;
-            if (fc0 >= 0 && fc0 <= nj + 1) li0 = ir[fc0];
-            if (col < 2 && fc1 >= 0 && fc1 <= nj + 1) li1 = ir[fc1];
-        }
-        {   // b of the row this thread computes in the next step
-            const int rcn = r + 2 + half, pn = p0 + rcn;
-            if (s + 1 >= 0 && rcn <= TI && pn >= 0 && pn < ni && col_ok) {
-                const size_t idn = (size_t)pn * nj + q;
-                bn0 = b[off + idn]; bn1 = b[off + npts + idn]; bn2 = b[off + 2 * npts + idn];
-            }
-        }
-        // ---- fine residual of relative row r + half -> LDS residual ring
-        const int rc = r + half, p = p0 + rc;
-        if (s >= 0 && rc <= TI) {
-            double y0 = 0.0, y1 = 0.0, y2 = 0.0;
-            if (p >= 0 && p < ni && col_ok) {
-                const bool oU = p - 1 < 0, oD = p + 1 >= ni;
-                const int sU = ap_slot(rc - 1), sC = ap_slot(rc), sD = ap_slot(rc + 1);
-                const double* i0 = im + sU * AP_W;
-                const double* i1 = im + sC * AP_W;
-                const double* i2 = im + sD * AP_W;
-                double imm = i0[col], im0 = i0[col + 1], imp = i0[col + 2];
-                double i0m = i1[col], i00 = i1[col + 1], i0p = i1[col + 2];
-                double ipm = i2[col], ip0 = i2[col + 1], ipp = i2[col + 2];
-                PixCoef k;
-                k.P = i00;
-                k.Dx = (ip0 - im0) / 2;
-                k.Dy = quirks ? k.Dx : (i0p - i0m) / 2;
-                k.Dxx = ip0 + im0 - 2 * i00;
-                k.Dyy = i0p + i0m - 2 * i00;
-                k.Dxy = (ipp - ipm - imp + imm) / 4;
-                const XT* ru = xs + (oU ? sD : sU) * 3 * AP_W;
-                const XT* rcn = xs + sC * 3 * AP_W;
-                const XT* rd = xs + (oD ? sU : sD) * 3 * AP_W;
-                const double sUL = (oU && oL) ? 2.0 : 1.0, sUR = (oU && oR) ? 2.0 : 1.0;
-                const double sDL = (oD && oL) ? 2.0 : 1.0, sDR = (oD && oR) ? 2.0 : 1.0;
-                Nbr n;
-                n.u[0] = sUL * (double)ru[cL]; n.w[0] = sUL * (double)ru[AP_W + cL];
-                n.u[1] = (double)ru[cC];       n.w[1] = (double)ru[AP_W + cC];       n.g[1] = (double)ru[2 * AP_W + cC];
-                n.u[2] = sUR * (double)ru[cR]; n.w[2] = sUR * (double)ru[AP_W + cR];
-                n.u[3] = (double)rcn[cL];      n.w[3] = (double)rcn[AP_W + cL];      n.g[3] = (double)rcn[2 * AP_W + cL];
-                n.u[4] = (double)rcn[cC];      n.w[4] = (double)rcn[AP_W + cC];      n.g[4] = (double)rcn[2 * AP_W + cC];
-                n.u[5] = (double)rcn[cR];      n.w[5] = (double)rcn[AP_W + cR];      n.g[5] = (double)rcn[2 * AP_W + cR];
-                n.u[6] = sDL * (double)rd[cL]; n.w[6] = sDL * (double)rd[AP_W + cL];
-                n.u[7] = (double)rd[cC];       n.w[7] = (double)rd[AP_W + cC];       n.g[7] = (double)rd[2 * AP_W + cC];
-                n.u[8] = sDR * (double)rd[cR]; n.w[8] = sDR * (double)rd[AP_W + cR];
-                offdiag0(k, alpha, beta, n, y0, y1, y2);
-                const double P = k.P;
-                y0 += (P * (k.Dxx - 2 * P) - 4 * alpha) * n.u[4] + P * k.Dxy * n.w[4];
-                y1 += (P * (k.Dyy - 2 * P) - 4 * alpha) * n.w[4] + P * k.Dxy * n.u[4];
-                y2 += (-1 - 4 * beta) * n.g[4] + k.Dx * n.u[4] + k.Dy * n.w[4];
-                y0 = (double)bc0 - y0;
-                y1 = (double)bc1 - y1;
-                y2 = (double)bc2 - y2;
-            }
-            double* rr = rs + (ap_slot(rc) * 3) * 128 + col;
-            rr[0] = y0; rr[128] = y1; rr[256] = y2;
-        }
-        // ---- loaded row -> LDS ring
-        if (need) {
-            const int sl = ap_slot(rl);
-            XT* xr = xs + sl * 3 * AP_W;
-            xr[col + 1] = l0; xr[AP_W + col + 1] = l1; xr[2 * AP_W + col + 1] = l2;
-            if (col == 0 || col == 127) {
-                const int ch = (col == 0) ? 0 : AP_OUT + 1;
-                xr[ch] = h0; xr[AP_W + ch] = h1; xr[2 * AP_W + ch] = h2;
-            }
-            double* ir = im + sl * AP_W;
-            ir[col] = li0;
-            if (col < 2) ir[128 + col] = li1;
-        }
-        __syncthreads();
     }
 }
 
