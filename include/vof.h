@@ -343,6 +343,69 @@ int vof_vary_blursize_host(vof_ctx* ctx, const double* movie, int n_frames, cons
                            const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats,
                            double* v_x, double* v_y, double* speed, double* net_remodelling);
 
+/* Summary of one channel of compare_channel_flows. */
+typedef struct vof_compare_stats {
+    double speed_mean, speed_variance;             /* np.mean / np.var of the channel's speed stack; NaN propagates as in numpy */
+    double remodelling_mean, remodelling_variance; /* ... of net_remodelling; 0 without include_remodelling */
+    int64_t nonfinite_count;                       /* NaN / Inf values in the speed stack */
+    int32_t channel;                               /* 0 = a, 1 = b, echoed */
+    int32_t reserved;
+} vof_compare_stats;
+
+/* The comparison of two channels of one movie the reference's scripts run around conduct_optical_flow
+ * (compare_rho_and_actin.py:616-767): what vof_box_flow_* computes for box_size from movie_a and from movie_b (the same
+ * n_frames and image size; the kernels and the fused / general choice of vof_box_flow_dev, same bits), the per-channel
+ * statistics of vof_vary_blursize_* and the joint statistics of the two velocity fields, in one call.  A channel's frames are
+ * blurred first if its blur_weights != NULL (taps as for vof_blur_stack_*).  Pairs are processed in chunks sized as in
+ * vof_vary_boxsize_*; per chunk the box flow runs once per channel, then one pass reads v_x, v_y and speed of both channels
+ * (48 bytes per pixel and pair) and writes nothing of field size.
+ * stats: 2 records (a, b), host memory, required.  Every per-channel array below has a leading axis of length 2, a first.
+ * histogram_edges / histogram_bins / histograms (2 x histogram_bins int64), angle_bins (0, or 1 .. 64) / angle_histograms /
+ *   weighted_angle_histograms (2 x angle_bins): as for vof_vary_blursize_*.
+ * Joint, per sample of all n_frames - 1 pairs, float64, every operation explicit and in this order:
+ *   dot = v_x_a * v_x_b + v_y_a * v_y_b;  w = speed_a * speed_b;  cos = dot / w;  theta = acos(cos) / pi.
+ *   A sample takes part only if both speeds are finite; the others are counted in joint_counts[0].  With reference_quirks cos is
+ *   not clipped, as in the script: a rounding excess over 1 gives a NaN theta; without, cos is clipped to [-1, 1] first (a NaN
+ *   stays one).  Samples whose theta is NaN are in no bin and counted in joint_counts[1].
+ * relative_angle_bins: 1 .. 64.  relative_angle_histogram (host, int64) receives np.histogram(theta, bins, (0, 1))[0] and
+ *   weighted_relative_angle_histogram (host, float64) np.histogram(theta, bins, (0, 1), weights=w)[0]: a fixed-shape reduction
+ *   per pair whose shape depends on the image size only, the pairs added in pair order on the host; no floating-point atomics,
+ *   so the sums are bit-identical from call to call and for every number of pairs in flight.
+ * joint_speed_edges_a / _b: both NULL, or the joint_speed_bins_a + 1 and joint_speed_bins_b + 1 edges of np.linspace in host
+ *   memory (1 .. 1024 bins per axis); joint_speed_histogram (host, bins_a x bins_b int64) then receives
+ *   np.histogram2d(speed_a[m], speed_b[m], (bins_a, bins_b), ranges)[0] with m = speed_b > *joint_speed_min_b (all samples
+ *   with joint_speed_min_b == NULL).
+ * joint_counts: host, 2 x int64, required.
+ * v_x_a .. net_remodelling_b: NULL (stats only: no full-size stack exists anywhere beyond the pairs in flight), or
+ *   (n_frames - 1, n_i, n_j) float64, v_x, v_y and speed of both channels together; the two net_remodelling may be NULL also
+ *   then (required with include_remodelling).
+ * _dev: the movies and the eight field stacks are device pointers; _host: host pointers, staged through the context's pinned
+ * bounce buffer.  Everything else is host memory in both. */
+int vof_compare_flows_dev(vof_ctx* ctx, const double* movie_a, const double* movie_b, int n_frames,
+                          const double* blur_weights_a, int blur_radius_a, const double* blur_weights_b, int blur_radius_b,
+                          int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                          const double* histogram_edges, int histogram_bins, int64_t* histograms,
+                          int angle_bins, int64_t* angle_histograms, double* weighted_angle_histograms,
+                          int relative_angle_bins, int64_t* relative_angle_histogram, double* weighted_relative_angle_histogram,
+                          const double* joint_speed_edges_a, int joint_speed_bins_a,
+                          const double* joint_speed_edges_b, int joint_speed_bins_b,
+                          const double* joint_speed_min_b, int64_t* joint_speed_histogram,
+                          int64_t* joint_counts, vof_compare_stats* stats,
+                          double* v_x_a, double* v_y_a, double* speed_a, double* net_remodelling_a,
+                          double* v_x_b, double* v_y_b, double* speed_b, double* net_remodelling_b);
+int vof_compare_flows_host(vof_ctx* ctx, const double* movie_a, const double* movie_b, int n_frames,
+                           const double* blur_weights_a, int blur_radius_a, const double* blur_weights_b, int blur_radius_b,
+                           int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
+                           const double* histogram_edges, int histogram_bins, int64_t* histograms,
+                           int angle_bins, int64_t* angle_histograms, double* weighted_angle_histograms,
+                           int relative_angle_bins, int64_t* relative_angle_histogram, double* weighted_relative_angle_histogram,
+                           const double* joint_speed_edges_a, int joint_speed_bins_a,
+                           const double* joint_speed_edges_b, int joint_speed_bins_b,
+                           const double* joint_speed_min_b, int64_t* joint_speed_histogram,
+                           int64_t* joint_counts, vof_compare_stats* stats,
+                           double* v_x_a, double* v_y_a, double* speed_a, double* net_remodelling_a,
+                           double* v_x_b, double* v_y_b, double* speed_b, double* net_remodelling_b);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

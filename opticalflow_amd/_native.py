@@ -60,6 +60,11 @@ BLURSIZE_DTYPE = np.dtype([("speed_mean", np.float64), ("speed_variance", np.flo
                            ("reserved", np.int32)])
 assert BLURSIZE_DTYPE.itemsize == 48      # sizeof(vof_blursize_stats)
 
+COMPARE_DTYPE = np.dtype([("speed_mean", np.float64), ("speed_variance", np.float64), ("remodelling_mean", np.float64),
+                          ("remodelling_variance", np.float64), ("nonfinite_count", np.int64), ("channel", np.int32),
+                          ("reserved", np.int32)])
+assert COMPARE_DTYPE.itemsize == 48       # sizeof(vof_compare_stats)
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
@@ -95,6 +100,12 @@ SIGNATURES = {
                                         C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vof_vary_blursize_host": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp,
                                          C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vof_compare_flows_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                        _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vof_compare_flows_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                         _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -468,6 +479,63 @@ class Solver:
         return self._vary_blursize("vof_vary_blursize_dev", movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling,
                                    reference_quirks, histogram_edges, angle_bins, intensity_edges, probe_locations,
                                    [v_x, v_y, speed, net_remodelling])
+
+    def _compare_flows(self, fn, movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
+                       weights_a, weights_b, histogram_edges, angle_bins, relative_angle_bins, joint_speed_edges, joint_speed_min_b,
+                       fields_a, fields_b):
+        w = [None if t is None else np.ascontiguousarray(t, dtype=np.float64).ravel() for t in (weights_a, weights_b)]
+        edges, bins, hist = _edges_and_counts(histogram_edges, 2)
+        abins, tbins = int(angle_bins or 0), int(relative_angle_bins)
+        ahist = np.zeros((2, abins), dtype=np.int64) if abins else None
+        awhist = np.zeros((2, abins)) if abins else None
+        thist, twhist = np.zeros(max(tbins, 0), dtype=np.int64), np.zeros(max(tbins, 0))
+        jedges, jhist = [None, None], None
+        if joint_speed_edges is not None:
+            jedges = [np.ascontiguousarray(e, dtype=np.float64).ravel() for e in joint_speed_edges]
+            jhist = np.zeros((jedges[0].size - 1, jedges[1].size - 1), dtype=np.int64)
+        jmin = None if joint_speed_min_b is None else np.array([joint_speed_min_b], dtype=np.float64)
+        jcounts = np.zeros(2, dtype=np.int64)
+        stats = np.zeros(2, dtype=COMPARE_DTYPE)
+        rc = getattr(self.lib, fn)(self.h, _ptr(movie_a), _ptr(movie_b), int(n_frames), _ptr(w[0]), 0 if w[0] is None else w[0].size // 2,
+                                   _ptr(w[1]), 0 if w[1] is None else w[1].size // 2, int(box_size), float(delta_x), float(delta_t),
+                                   int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(edges), bins, _ptr(hist), abins,
+                                   _ptr(ahist), _ptr(awhist), tbins, _ptr(thist), _ptr(twhist), _ptr(jedges[0]),
+                                   0 if jedges[0] is None else jedges[0].size - 1, _ptr(jedges[1]),
+                                   0 if jedges[1] is None else jedges[1].size - 1, _ptr(jmin), _ptr(jhist), _ptr(jcounts), _ptr(stats),
+                                   *[_ptr(f) for f in fields_a], *[_ptr(f) for f in fields_b])
+        self._check(rc, fn)
+        return stats, hist, ahist, awhist, thist, twhist, jhist, jcounts
+
+    def compare_flows_host(self, movie_a: np.ndarray, movie_b: np.ndarray, box_size, delta_x=1.0, delta_t=1.0, include_remodelling=False,
+                           reference_quirks=True, weights_a=None, weights_b=None, histogram_edges=None, angle_bins=None,
+                           relative_angle_bins=50, joint_speed_edges=None, joint_speed_min_b=None, return_fields=False):
+        """The box flows of two host movies of one shape and their joint statistics in one native call; ``weights_a`` /
+        ``weights_b`` are the blur taps of a channel or None, ``joint_speed_edges`` a pair of edge vectors or None.  Returns
+        ``(stats, histograms, angle_histograms, weighted_angle_histograms, relative_angle_histogram,
+        weighted_relative_angle_histogram, joint_speed_histogram, joint_counts, fields)``: a COMPARE_DTYPE record per channel,
+        the per-channel histograms ``(2, bins)`` or None where not asked for, the two histograms of the angle between the
+        flows, the ``(bins_a, bins_b)`` counts or None, ``(joint non-finite, theta dropped)``, and None or a pair of
+        ``(v_x, v_y, speed, net_remodelling)`` of shape ``(T - 1, n_i, n_j)`` (``net_remodelling`` is None without
+        ``include_remodelling``)."""
+        movie_a = np.ascontiguousarray(movie_a, dtype=np.float64)
+        movie_b = np.ascontiguousarray(movie_b, dtype=np.float64)
+        assert movie_a.ndim == 3 and movie_a.shape[1:] == (self.n_i, self.n_j) and movie_b.shape == movie_a.shape
+        T = movie_a.shape[0]
+        fields = [[f if f is None else f[0] for f in self._sweep_fields(1, T, include_remodelling, return_fields)] for _ in range(2)]
+        out = self._compare_flows("vof_compare_flows_host", movie_a, movie_b, T, box_size, delta_x, delta_t, include_remodelling,
+                                  reference_quirks, weights_a, weights_b, histogram_edges, angle_bins, relative_angle_bins,
+                                  joint_speed_edges, joint_speed_min_b, fields[0], fields[1])
+        return (*out, (tuple(fields[0]), tuple(fields[1])) if return_fields else None)
+
+    def compare_flows_dev(self, movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
+                          weights_a=None, weights_b=None, histogram_edges=None, angle_bins=None, relative_angle_bins=50,
+                          joint_speed_edges=None, joint_speed_min_b=None, fields_a=None, fields_b=None):
+        """The same on device memory (torch tensors or raw pointers): the movies and the optional field stacks
+        ``(v_x, v_y, speed, net_remodelling)`` of a channel, ``(n_frames - 1, n_i, n_j)`` each; returns the eight summaries as
+        host arrays."""
+        return self._compare_flows("vof_compare_flows_dev", movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling,
+                                   reference_quirks, weights_a, weights_b, histogram_edges, angle_bins, relative_angle_bins,
+                                   joint_speed_edges, joint_speed_min_b, fields_a or [None] * 4, fields_b or [None] * 4)
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

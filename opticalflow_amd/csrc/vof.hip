@@ -14,6 +14,7 @@
 #include "vof_boxflow.hpp"
 #include "vof_boxsweep.hpp"
 #include "vof_blursweep.hpp"
+#include "vof_compare.hpp"
 #include "vof_liushen.hpp"
 #include "../../include/vof.h"
 
@@ -110,7 +111,7 @@ struct vof_ctx {
     double* st_movie2 = nullptr;                                 // second frame buffer (upload of the next batch under the solve)
     double *blur_tmp = nullptr, *blur_w = nullptr, *blur_io = nullptr;   // Gaussian blur scratch (lazy)
     double* bf_scratch = nullptr;                                        // box flow, general path: derived planes + row sums (lazy)
-    double* sw_scratch = nullptr;                                        // box-size and blur sweep: the planes of the one in progress (lazy; sweep_scratch)
+    double* sw_scratch = nullptr;                                        // box-size / blur sweep, channel comparison: the planes of the one in progress (lazy; sweep_scratch)
     size_t sw_planes = 0;                                                // planes of sw_scratch
     bool sw_by_budget = false;                                           // sw_scratch was sized by the free memory, not by the request
     char* sw_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
@@ -4037,6 +4038,188 @@ int vof_vary_blursize_host(vof_ctx* c, const double* movie, int n_frames, const 
                                               blur_weights, blur_radii, n_sigmas, box_size, angle_bins, angle_histograms,
                                               weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, stats});
 }
+
+// ---- two channels of one movie: their box flows and the joint statistics (compare_channel_flows; vof_compare.hpp) --------
+struct CompareReq : SweepBase {           // movie, outs: channel a; the tail's two entries are the channels
+    const double* movie_b;
+    const double* taps[2]; int radius[2];
+    int box_size;
+    int abins; int64_t* ahist; double* awhist;                  // per-channel flow direction
+    int tbins; int64_t* thist; double* twhist;                  // angle between the two flows
+    const double* jedges[2]; int jbins[2]; const double* jmin; int64_t* jhist;     // the two speeds
+    int64_t* jcounts;
+    double* outs_b[4];
+    vof_compare_stats* stats;
+};
+
+// np.linspace(lo, hi, bins + 1) for hi - lo exactly representable: i * step + lo, the last one the stop itself
+static std::vector<double> linspace_edges(double lo, double hi, int bins) {
+    std::vector<double> e((size_t)bins + 1);
+    const volatile double step = (hi - lo) / (double)bins;
+    for (int i = 0; i < bins; ++i) { const volatile double t = (double)i * step; e[i] = t + lo; }
+    e[bins] = hi;
+    return e;
+}
+
+static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
+    if (!c) return -1;
+    if (int rc = sweep_check(c, r, r.stats)) return rc;
+    if (!r.movie_b) { c->err = "movie_b is NULL"; return -1; }
+    for (int f = 0; f < 4; ++f)
+        if ((r.outs[f] != nullptr) != (r.outs_b[f] != nullptr)) { c->err = "the field stacks of both channels must be given together"; return -1; }
+    for (int ch = 0; ch < 2; ++ch)
+        if (r.taps[ch] && (r.radius[ch] < 0 || r.radius[ch] > 4096)) { c->err = "bad blur_radius"; return -1; }
+    if (r.box_size < 1) { c->err = "box_size must be >= 1"; return -1; }
+    if (r.abins < 0 || r.abins > CP_MAX_THETA_BINS) { c->err = "angle_bins must be 0 .. " + std::to_string(CP_MAX_THETA_BINS); return -1; }
+    if (r.abins && (!r.ahist || !r.awhist)) { c->err = "angle_bins needs angle_histograms and weighted_angle_histograms"; return -1; }
+    if (r.tbins < 1 || r.tbins > CP_MAX_THETA_BINS) { c->err = "relative_angle_bins must be 1 .. " + std::to_string(CP_MAX_THETA_BINS); return -1; }
+    if (!r.thist || !r.twhist || !r.jcounts) { c->err = "relative_angle_histogram, weighted_relative_angle_histogram and joint_counts are required"; return -1; }
+    const bool joint = r.jedges[0] || r.jedges[1];
+    if (joint) {
+        if (!r.jedges[0] || !r.jedges[1] || !r.jhist) { c->err = "joint_speed_edges_a, joint_speed_edges_b and joint_speed_histogram go together"; return -1; }
+        for (int ch = 0; ch < 2; ++ch) {
+            if (r.jbins[ch] < 1 || r.jbins[ch] > CP_MAX_SPEED_BINS) { c->err = "joint_speed_bins must be 1 .. " + std::to_string(CP_MAX_SPEED_BINS) + " per axis"; return -1; }
+            if (!(r.jedges[ch][r.jbins[ch]] > r.jedges[ch][0])) { c->err = "joint_speed_edges must increase"; return -1; }
+        }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const int P = r.n_frames - 1;
+    const int ba = joint ? r.jbins[0] : 0, bb = joint ? r.jbins[1] : 0;
+    // scratch planes: cap + 1 frames of the channel in progress and four chunk outputs per channel and pair in flight
+    const int cap = sweep_scratch(c, 1, 1 + 8, sweep_want(c, r), "channel comparison", " for one pair");
+    if (cap < 0) return cap;
+    double* frames = c->sw_scratch;
+    double* chunk_out[2][4];
+    for (int ch = 0; ch < 2; ++ch)
+        for (int f = 0; f < 4; ++f) chunk_out[ch][f] = frames + ((size_t)(cap + 1) + (size_t)(4 * ch + f) * cap) * fs;
+    if (r.taps[0] || r.taps[1]) if (int rc = blur_alloc(c)) return rc;
+
+    // what the comparison's own kernels read and write, behind the tail's
+    const size_t n_taps[2] = {r.taps[0] ? 2 * (size_t)r.radius[0] + 1 : 0, r.taps[1] ? 2 * (size_t)r.radius[1] + 1 : 0};
+    const size_t n_ahist = 2 * (size_t)r.abins, n_awsum = 2 * (size_t)P * r.abins, n_twsum = (size_t)P * r.tbins, n_jhist = (size_t)ba * bb;
+    const int ang_blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));   // as the blur sweep
+    const int cp_blk = cp_blocks(fs);
+    Take doubles, counts;
+    const size_t at_taps[2] = {doubles(n_taps[0]), doubles(n_taps[1])};
+    const size_t at_aedges = doubles(r.abins ? r.abins + 1 : 0), at_tedges = doubles((size_t)r.tbins + 1),
+                 at_jedges[2] = {doubles(joint ? (size_t)ba + 1 : 0), doubles(joint ? (size_t)bb + 1 : 0)},
+                 at_awsum = doubles(n_awsum), at_apart = doubles((size_t)cap * ang_blk * r.abins), at_twsum = doubles(n_twsum),
+                 at_tpart = doubles((size_t)cap * cp_blk * r.tbins);
+    const size_t at_ahist = counts(n_ahist), at_thist = counts(r.tbins), at_jhist = counts(n_jhist), at_jc = counts(2);
+    SweepTail tail;
+    if (int rc = sweep_tail_begin(c, tail, r, "channel comparison", 2, cap, doubles.items, counts.items)) return rc;
+    double* const ad = tail.own_doubles;
+    unsigned long long* const au = tail.own_counters;
+    for (int ch = 0; ch < 2; ++ch) {
+        if (r.taps[ch]) if (int rc = h2d_bounced(c, ad + at_taps[ch], r.taps[ch], n_taps[ch] * 8)) return rc;
+        if (joint) if (int rc = h2d_bounced(c, ad + at_jedges[ch], r.jedges[ch], ((size_t)r.jbins[ch] + 1) * 8)) return rc;
+    }
+    if (r.abins) {
+        const std::vector<double> e = linspace_edges(-1.0, 1.0, r.abins);
+        if (int rc = h2d_bounced(c, ad + at_aedges, e.data(), e.size() * 8)) return rc;
+    }
+    {
+        const std::vector<double> e = linspace_edges(0.0, 1.0, r.tbins);
+        if (int rc = h2d_bounced(c, ad + at_tedges, e.data(), e.size() * 8)) return rc;
+    }
+    SweepBase chan[2] = {r, r};            // a channel as a sweep of one entry: where its fields go
+    chan[1].movie = r.movie_b;
+    for (int f = 0; f < 4; ++f) chan[1].outs[f] = r.outs_b[f];
+
+    for (int k0 = 0; k0 < P; k0 += cap) {
+        const int np = std::min(cap, P - k0);
+        SweepDst d[2];
+        for (int ch = 0; ch < 2; ++ch) {
+            const double* src = chan[ch].movie + (size_t)k0 * fs;
+            if (r.host) {
+                if (int rc = h2d_bounced(c, frames, src, (size_t)(np + 1) * fb)) return rc;
+                src = frames;
+            }
+            if (r.taps[ch]) {
+                if (int rc = blur_frames(c, src, frames, np + 1, r.radius[ch], ad + at_taps[ch])) return rc;
+                src = frames;
+            }
+            d[ch] = sweep_dst(chan[ch], chunk_out[ch], fs, 0, k0);
+            // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
+            if (int rc = box_flow_pairs(c, src, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d[ch].f[0], d[ch].f[1],
+                                        d[ch].f[2], d[ch].keep_g ? d[ch].f[3] : nullptr)) return rc;
+            sweep_tail_speed(c, tail, ch, k0, np, d[ch].f[2]);
+            if (r.abins) {
+                Prof prof(c, VOF_K_REDUCE, 0);
+                k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
+                    d[ch].f[0], d[ch].f[1], d[ch].f[2], fs, ad + at_aedges, r.abins, au + at_ahist + (size_t)ch * r.abins, ad + at_apart);
+                const int nt = np * r.abins;
+                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_apart, ang_blk, r.abins, np,
+                                                                        ad + at_awsum + ((size_t)ch * P + k0) * r.abins);
+            }
+            if (int rc = sweep_tail_moments(c, tail, ch, k0, np, d[ch].f[2], d[ch].f[3])) return rc;
+        }
+        {
+            CompareArgs a{};
+            a.vxa = d[0].f[0]; a.vya = d[0].f[1]; a.spa = d[0].f[2];
+            a.vxb = d[1].f[0]; a.vyb = d[1].f[1]; a.spb = d[1].f[2];
+            a.fs = fs;
+            a.tedges = ad + at_tedges; a.tbins = r.tbins;
+            a.ea = ad + at_jedges[0]; a.eb = ad + at_jedges[1]; a.ba = ba; a.bb = bb;
+            a.has_min = r.jmin ? 1 : 0; a.min_b = r.jmin ? *r.jmin : 0.0;
+            a.clip = r.quirks ? 0 : 1;
+            a.thist = au + at_thist; a.jhist = au + at_jhist; a.counters = au + at_jc;
+            a.partials = ad + at_tpart;
+            c->cur_units = np;
+            Prof prof(c, VOF_K_REDUCE, 0, 48.0 * fs);
+            k_cp_joint<<<dim3(cp_blk, np), 64, cp_lds(r.tbins, ba, bb), c->stream>>>(a);
+            const int nt = np * r.tbins;
+            k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_tpart, cp_blk, r.tbins, np, ad + at_twsum + (size_t)k0 * r.tbins);
+        }
+        if (hipGetLastError() != hipSuccess) { c->err = "channel comparison: launch failed"; return -2; }
+        for (int ch = 0; ch < 2; ++ch)
+            if (int rc = sweep_copy_out(c, chan[ch], d[ch], fs, np)) return rc;
+    }
+    if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
+    std::vector<double> sums(n_awsum + n_twsum);
+    if (n_awsum) if (int rc = d2h_bounced(c, sums.data(), ad + at_awsum, n_awsum * 8)) return rc;
+    if (int rc = d2h_bounced(c, sums.data() + n_awsum, ad + at_twsum, n_twsum * 8)) return rc;
+    const unsigned long long* own = tail.counters.data() + (tail.n_counters - counts.items);
+    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)own[at_ahist + t];
+    for (int b = 0; b < r.tbins; ++b) r.thist[b] = (int64_t)own[at_thist + b];
+    for (size_t t = 0; t < n_jhist; ++t) r.jhist[t] = (int64_t)own[at_jhist + t];
+    r.jcounts[0] = (int64_t)own[at_jc]; r.jcounts[1] = (int64_t)own[at_jc + 1];
+    for (int ch = 0; ch < 2; ++ch) {
+        for (int b = 0; b < r.abins; ++b) {                  // the pairs' sums in pair order
+            double w = 0.0;
+            for (int k = 0; k < P; ++k) w += sums[((size_t)ch * P + k) * r.abins + b];
+            r.awhist[(size_t)ch * r.abins + b] = w;
+        }
+        r.stats[ch].channel = ch;
+    }
+    for (int b = 0; b < r.tbins; ++b) {
+        double w = 0.0;
+        for (int k = 0; k < P; ++k) w += sums[n_awsum + (size_t)k * r.tbins + b];
+        r.twhist[b] = w;
+    }
+    return 0;
+}
+
+#define VOF_COMPARE_ARGS                                                                                                              \
+    vof_ctx *c, const double *movie_a, const double *movie_b, int n_frames, const double *blur_weights_a, int blur_radius_a,          \
+        const double *blur_weights_b, int blur_radius_b, int box_size, double delta_x, double delta_t, int include_remodelling,       \
+        int reference_quirks, const double *histogram_edges, int histogram_bins, int64_t *histograms, int angle_bins,                 \
+        int64_t *angle_histograms, double *weighted_angle_histograms, int relative_angle_bins, int64_t *relative_angle_histogram,     \
+        double *weighted_relative_angle_histogram, const double *joint_speed_edges_a, int joint_speed_bins_a,                         \
+        const double *joint_speed_edges_b, int joint_speed_bins_b, const double *joint_speed_min_b, int64_t *joint_speed_histogram,   \
+        int64_t *joint_counts, vof_compare_stats *stats, double *v_x_a, double *v_y_a, double *speed_a, double *net_remodelling_a,    \
+        double *v_x_b, double *v_y_b, double *speed_b, double *net_remodelling_b
+#define VOF_COMPARE_REQ(host)                                                                                                         \
+    CompareReq{{movie_a, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges, histogram_bins,          \
+                histograms, nullptr, 0, nullptr, {v_x_a, v_y_a, speed_a, net_remodelling_a}, host},                                   \
+               movie_b, {blur_weights_a, blur_weights_b}, {blur_radius_a, blur_radius_b}, box_size, angle_bins, angle_histograms,     \
+               weighted_angle_histograms, relative_angle_bins, relative_angle_histogram, weighted_relative_angle_histogram,           \
+               {joint_speed_edges_a, joint_speed_edges_b}, {joint_speed_bins_a, joint_speed_bins_b}, joint_speed_min_b,               \
+               joint_speed_histogram, joint_counts, {v_x_b, v_y_b, speed_b, net_remodelling_b}, stats}
+
+int vof_compare_flows_dev(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(false)); }
+int vof_compare_flows_host(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(true)); }
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------
 constexpr int LS_CHUNK = 16384;           // pairs per launch (grid z)

@@ -64,7 +64,7 @@ def release_device_memory(_locked=False):
 atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
-           "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "make_fake_data_frame", "blur_movie",
+           "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -721,6 +721,155 @@ def vary_blursize(movie, blursizes=np.arange(0.5, 15, 0.1), boxsize=21, delta_x=
         own["intensity_histograms"] = summaries[4]
         own["intensity_edges"] = intensity_edges
     return _sweep_result({"blursizes": sigmas}, summaries, fields, own, edges, include_remodelling, delta_x, delta_t, filename)
+
+
+COMPARE_MAX_ANGLE_BINS = 64          # CP_MAX_THETA_BINS of csrc/vof_compare.hpp: angle_bins and relative_angle_bins
+COMPARE_MAX_SPEED_BINS = 1024        # CP_MAX_SPEED_BINS: per axis of joint_speed_bins
+
+
+def _channel_pair(name, value):
+    """``(a, b)`` of an argument that is a scalar or None (both channels) or a pair."""
+    if isinstance(value, (tuple, list)) or (isinstance(value, np.ndarray) and value.ndim > 0):
+        if len(value) != 2:
+            raise ValueError(f"{name} must be a scalar or a pair (a, b)")
+        return value[0], value[1]
+    return value, value
+
+
+def _compare_arguments(movie_a, movie_b, boxsize, smoothing_sigma, background, histogram_bins, histogram_range, angle_bins,
+                       relative_angle_bins, joint_speed_bins, joint_speed_ranges, output):
+    """The argument checks of ``compare_channel_flows``, all before the library is touched; returns the shape, the per-channel
+    sigmas and backgrounds, the speed edges and the pair of joint speed edges (or None)."""
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    shape = _sweep_shape(movie_a)
+    if tuple(movie_b.shape if hasattr(movie_b, "shape") else np.asarray(movie_b).shape) != shape:
+        raise ValueError("movie_a and movie_b must have the same shape (frames, x, y)")
+    if int(boxsize) < 1:
+        raise ValueError("boxsize must be >= 1")
+    sigmas = _channel_pair("smoothing_sigma", smoothing_sigma)
+    for s in sigmas:
+        if s is not None and not (np.isfinite(float(s)) and float(s) > 0):
+            raise ValueError("smoothing_sigma must be finite and > 0")
+    backgrounds = _channel_pair("background", background)
+    edges = _sweep_edges("histogram", histogram_bins, histogram_range)
+    if angle_bins is not None and not 1 <= int(angle_bins) <= COMPARE_MAX_ANGLE_BINS:
+        raise ValueError(f"angle_bins must be 1 .. {COMPARE_MAX_ANGLE_BINS}")
+    if relative_angle_bins is None or not 1 <= int(relative_angle_bins) <= COMPARE_MAX_ANGLE_BINS:
+        raise ValueError(f"relative_angle_bins must be 1 .. {COMPARE_MAX_ANGLE_BINS}")
+    joint_edges = None
+    if joint_speed_bins is not None:
+        if np.ndim(joint_speed_bins) != 1 or len(joint_speed_bins) != 2:
+            raise ValueError("joint_speed_bins must be a pair (bins_a, bins_b)")
+        if joint_speed_ranges is None:
+            raise ValueError("joint_speed_bins needs joint_speed_ranges")
+        if len(joint_speed_ranges) != 2 or any(np.ndim(r) != 1 or len(r) != 2 for r in joint_speed_ranges):
+            raise ValueError("joint_speed_ranges must be a pair ((lo, hi), (lo, hi))")
+        if not all(1 <= int(b) <= COMPARE_MAX_SPEED_BINS for b in joint_speed_bins):
+            raise ValueError(f"joint_speed_bins must be 1 .. {COMPARE_MAX_SPEED_BINS} per axis")
+        joint_edges = tuple(_sweep_edges("joint_speed", b, r) for b, r in zip(joint_speed_bins, joint_speed_ranges))
+    return shape, sigmas, backgrounds, edges, joint_edges
+
+
+def compare_channel_flows(movie_a, movie_b, boxsize=31, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, background=None,
+                          include_remodelling=False, filename=None, *, histogram_bins=50, histogram_range=None, angle_bins=50,
+                          relative_angle_bins=50, joint_speed_bins=None, joint_speed_ranges=None, joint_speed_min_b=None,
+                          return_fields=False, reference_quirks=True, device=0, output="numpy"):
+    """The comparison of two channels of one movie the reference's scripts run around ``conduct_optical_flow``
+    (compare_rho_and_actin.py:616-767: Rho and actin, box 31, sigma 3) as one native call (``vof_compare_flows_*``): the box
+    flow of both channels, their per-channel statistics and the joint statistics of the two velocity fields; only the
+    summaries come back.
+
+    ``movie_a`` and ``movie_b`` have the same shape ``(T, N_i, N_j)``, ``T >= 2``.  ``smoothing_sigma`` and ``background`` are a
+    scalar (both channels) or a pair ``(a, b)``.  Each channel is treated as ``conduct_optical_flow(movie, boxsize, delta_x,
+    delta_t, smoothing_sigma, background, include_remodelling, reference_quirks=...)`` treats it, bit for bit.
+
+    Returns a dict of numpy summaries.  Per channel, leading axis of length 2, a first: ``speed_means``, ``speed_stds``
+    (``np.mean`` / ``np.std`` of the channel's speed stack; NaN propagates), ``nonfinite_counts`` and
+    with ``include_remodelling``: ``remodelling_means``, ``remodelling_stds``;
+    with ``histogram_bins`` (``histogram_range=(lo, hi)`` is then required; pass ``histogram_bins=None`` for none):
+    ``speed_histograms``, int64 ``(2, bins)``, equal to ``np.histogram(speed.ravel(), bins, range)[0]``, and ``histogram_edges``;
+    with ``angle_bins`` (None, or 1 .. 64): ``angle_histograms``, ``weighted_angle_histograms`` and ``angle_edges`` as
+    ``vary_blursize`` defines them, the direction ``np.arccos(v_y / speed) * np.sign(v_x) / np.pi`` on (-1, 1), weighted by ``speed``.
+
+    Joint, over all ``T - 1`` pairs and all pixels, per sample in float64 and in this order: ``dot = v_x_a * v_x_b + v_y_a *
+    v_y_b``, ``w = speed_a * speed_b``, ``cos = dot / w``, ``theta = np.arccos(cos) / np.pi``.  A sample takes part only if both
+    speeds are finite; the others are counted in ``joint_nonfinite_count``.  With ``reference_quirks=True`` ``cos`` is not
+    clipped, as in the script, so a rounding excess over 1 (about a third of the pixels when both channels are the same 8-bit
+    movie) gives a NaN ``theta``; ``reference_quirks=False`` clips ``cos`` to [-1, 1] first.  A sample whose ``theta`` is NaN
+    (also: a zero speed) is in no bin and counted in ``relative_angle_dropped``.
+    ``relative_angle_histogram``: int64, ``np.histogram(theta, relative_angle_bins, (0, 1))[0]`` (1 .. 64 bins);
+    ``weighted_relative_angle_histogram``: float64, the same with ``weights=w``, bit-identical from call to call and for every
+    number of pairs in flight; ``weighted_relative_angle_density``: what ``density=True`` makes of it, ``sums /
+    np.diff(edges) / sums.sum()``; ``relative_angle_edges``.
+    With ``joint_speed_bins=(ba, bb)`` (1 .. 1024 each; ``joint_speed_ranges=((lo, hi), (lo, hi))`` is then required):
+    ``joint_speed_histogram``, int64 ``(ba, bb)``, equal to ``np.histogram2d(speed_a[m], speed_b[m], bins, range)[0]`` with ``m =
+    speed_b > joint_speed_min_b`` (``None``: all samples), ``joint_speed_edges_a`` and ``joint_speed_edges_b``.
+    ``delta_x`` and ``delta_t`` are returned.  With ``return_fields``: ``a`` and ``b``, dicts as ``conduct_optical_flow`` returns
+    them; without it no full-size field stack exists on either side beyond the pairs in flight.
+    ``filename``: the dict is saved with ``np.save``.  ``output="torch"``: the movies may be device tensors and the arrays of ``a``
+    and ``b`` stay on the device as float64 tensors; the summaries are numpy arrays in both modes."""
+    (T, N_i, N_j), sigmas, backgrounds, edges, joint_edges = _compare_arguments(
+        movie_a, movie_b, boxsize, smoothing_sigma, background, histogram_bins, histogram_range, angle_bins, relative_angle_bins,
+        joint_speed_bins, joint_speed_ranges, output)
+    taps = [None if s is None else gaussian_taps(s) for s in sigmas]
+    args = (int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks, taps[0], taps[1], edges, angle_bins,
+            int(relative_angle_bins), joint_edges, joint_speed_min_b)
+    movies, analysed, blurred, fields = (movie_a, movie_b), [None, None], [None, None], None
+    if output == "numpy":
+        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
+            for ch in range(2):
+                source = np.asarray(movies[ch])
+                analysed[ch] = source if backgrounds[ch] is None else _subtract_background(source, backgrounds[ch], device, solver)
+            *summaries, fields = solver.compare_flows_host(analysed[0], analysed[1], *args, return_fields)
+            if return_fields:
+                blurred = [analysed[ch] if taps[ch] is None else solver.blur_host(analysed[ch], taps[ch]) for ch in range(2)]
+    else:
+        import torch
+        dev = torch.device("cuda", int(device))
+        with _box_flow_context(N_i, N_j, 1, device) as solver:
+            for ch in range(2):
+                frames = torch.as_tensor(movies[ch]).to(device=dev, dtype=torch.float64).contiguous()
+                analysed[ch] = frames if backgrounds[ch] is None else _subtract_background_device(frames, backgrounds[ch], solver)
+            if return_fields:
+                fields = [[torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4 if include_remodelling else 3)]
+                          for _ in range(2)]
+                for ch in range(2):
+                    blurred[ch] = analysed[ch]
+                    if taps[ch] is not None:
+                        blurred[ch] = torch.empty_like(analysed[ch])
+                        torch.cuda.synchronize(dev)
+                        solver.blur_dev(analysed[ch], blurred[ch], T, taps[ch])
+            torch.cuda.synchronize(dev)                                    # the library launches on its own stream
+            padded = [None if fields is None else fields[ch] + [None] * (4 - len(fields[ch])) for ch in range(2)]
+            summaries = solver.compare_flows_dev(analysed[0], analysed[1], T, *args, padded[0], padded[1])
+    rec, hist, angle_hist, weighted_angle_hist, theta_hist, weighted_theta_hist, joint_hist, joint_counts = summaries
+    own = dict()
+    if angle_bins is not None:
+        own["angle_histograms"], own["weighted_angle_histograms"] = angle_hist, weighted_angle_hist
+        own["angle_edges"] = np.linspace(-1.0, 1.0, int(angle_bins) + 1, endpoint=True, dtype=np.float64)
+    theta_edges = np.linspace(0.0, 1.0, int(relative_angle_bins) + 1, endpoint=True, dtype=np.float64)
+    own["joint_nonfinite_count"], own["relative_angle_dropped"] = int(joint_counts[0]), int(joint_counts[1])
+    own["relative_angle_histogram"] = theta_hist
+    own["weighted_relative_angle_histogram"] = weighted_theta_hist
+    with np.errstate(invalid="ignore", divide="ignore"):                  # np.histogram(..., density=True): nothing in range gives NaN
+        own["weighted_relative_angle_density"] = weighted_theta_hist / np.diff(theta_edges) / weighted_theta_hist.sum()
+    own["relative_angle_edges"] = theta_edges
+    if joint_edges is not None:
+        own["joint_speed_histogram"] = joint_hist
+        own["joint_speed_edges_a"], own["joint_speed_edges_b"] = joint_edges
+    result = _sweep_result({}, (rec, hist, None), None, own, edges, include_remodelling, delta_x, delta_t, None)
+    if return_fields:
+        for ch, key in enumerate("ab"):
+            one = dict(v_x=fields[ch][0], v_y=fields[ch][1], speed=fields[ch][2], original_data=movies[ch], delta_x=delta_x,
+                       delta_t=delta_t,
+                       blurred_data=movies[ch] if (backgrounds[ch] is None and taps[ch] is None) else blurred[ch])
+            if include_remodelling:
+                one["net_remodelling"] = fields[ch][3]
+            result[key] = one
+    if filename is not None:
+        np.save(filename, result)
+    return result
 
 
 # ---------------------------------------------------------------------------------------------------------
