@@ -123,6 +123,9 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *                              of inside the first pre-smoothing pass of the cycle that consumes them (same bits)
  *   VOF_FUSE_RR=0              level 0: the coarse right-hand side R (b - A x) by the stand-alone residual + restriction kernel instead
  *                              of as the trailing stage of the pre-smoothing pass
+ *   VOF_ACTIVE_LIST=0          every launch of a Krylov round covers all pair slots of the batch, and the blocks of finished pairs
+ *                              read their flag and leave (default: after each count of the active pairs the launches take the
+ *                              list of their slots and cover those alone; same bits, tests/test_gpu_active_list.py)
  *   VOF_FOLD_STORED=1          stored levels: coarse-grid correction interpolated inside the first post-sweep
  *   VOF_TRACE=1                direct preconditioner: progress lines on stderr
  * Read at every vof_solve_stack_dev call (speed only; per pair the same arithmetic, partial sums may add in another order):

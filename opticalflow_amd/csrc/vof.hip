@@ -93,11 +93,15 @@ struct vof_ctx {
     int nblk = 0;
     PairScalars* sc = nullptr;
     int* active = nullptr;
+    int* alist = nullptr;        // slots of the pairs that were active at the host's last count, ascending (post_active_list)
+    int alist_n = 0;             // ... and how many: the pair dimension of a launch that takes the list
+    bool use_alist = true;       // VOF_ACTIVE_LIST=0: every launch covers all slots of the batch (no list)
     double* func3 = nullptr;
     double *W = nullptr, *invT = nullptr;
     int nd = 0;
     // host mirrors (pinned)
     int* h_active = nullptr;
+    int* h_alist = nullptr;
     PairScalars* h_sc = nullptr;
     double* h_func3 = nullptr;
     char* h_bounce = nullptr;        // pinned bounce buffer of the debug / test entry points (lazy)
@@ -430,6 +434,14 @@ int dbg_check_canaries(vof_ctx* c, std::string* report) {
     return bad;
 }
 
+// ---- which pairs a launch covers (ActiveSet, vof_device.hpp)
+const ActiveSet ALL_PAIRS{nullptr, nullptr};   // every slot of the batch, no flags: set-up, epilogue, debug entry points
+// `flags` with the context's list.  Only for flags that are on for no pair outside the list: c->active after post_active_list,
+// and the GMRES cycle flags between two of its restarts (gmres_phase)
+inline ActiveSet listed(const vof_ctx* c, const int* flags) { return ActiveSet{flags, c->use_alist ? c->alist : nullptr}; }
+// entries of the pair dimension of a launch that is given `a`
+inline int pair_slots(const vof_ctx* c, const ActiveSet& a, int np) { return a.list ? c->alist_n : np; }
+
 inline dim3 grid2d(int ni, int nj, int z) { return dim3((nj + BX - 1) / BX, (ni + BY - 1) / BY, z); }
 inline dim3 grid2d_colour(int ni, int nj, int colour, int z) {
     int cp = colour >> 1, cq = colour & 1;
@@ -468,9 +480,9 @@ template <typename T> struct TypeTag { typedef T type; };
 inline double coef_bytes(const vof_ctx* c, int l) { const int f = l > 0 ? c->cfmt : 0; return f == 3 ? 30.0 * 4 : (f == 2 ? 45.0 * 4 : (f == 1 ? 81.0 * 4 : 81.0 * 8)); }
 
 // one colour, in place, one launch per colour: the simple reference smoother (double vectors only)
-void gs_colour(vof_ctx* c, int l, double* x, const double* b, int colour, int np, const int* active) {
+void gs_colour(vof_ctx* c, int l, double* x, const double* b, int colour, int np, ActiveSet active) {
     Level& lv = c->L[l];
-    dim3 g = grid2d_colour(lv.ni, lv.nj, colour, np);
+    dim3 g = grid2d_colour(lv.ni, lv.nj, colour, pair_slots(c, active, np));
     if (l == 0 && c->L.size() > 1) {
         Prof p(c, VOF_K_GS0, 0, 20.0 * lv.npts);
         k_gs0<<<g, blk2d, 0, c->stream>>>(c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, c->prm.speed_alpha,
@@ -506,7 +518,7 @@ ApplyGrid apply_grid(const vof_ctx* c, int np) {
     return g;
 }
 // What both streaming level-0 kernels are given first: frames, level-0 grid, band height TI, model parameters, pair tables.
-ApArgs ap_args(const vof_ctx* c, int TI, const int* active) {
+ApArgs ap_args(const vof_ctx* c, int TI, ActiveSet active) {
     const Level& lv = c->L[0];
     return ApArgs{c->frames, frame_stride(c), c->Nj, lv.ni, lv.nj, TI, c->prm.speed_alpha, c->prm.remodelling_alpha,
                   c->prm.reference_quirks, active, c->pp};
@@ -516,13 +528,13 @@ ApArgs ap_args(const vof_ctx* c, int TI, const int* active) {
 // c->partials (slot 0: y.dotvec, or y.y when dotvec == nullptr; slot 1: y.y when both are asked for); the
 // number of per-pair partials is apply_grid().nblk.
 template <typename XT, typename BT, typename YT>
-void apply_fine_t(vof_ctx* c, const XT* x, const BT* b, YT* y, int mode, int np, const int* active,
+void apply_fine_t(vof_ctx* c, const XT* x, const BT* b, YT* y, int mode, int np, ActiveSet active,
                   const double* dotvec = nullptr, int want_yy = 0, YT* ycopy = nullptr) {
     Level& lv = c->L[0];
     const double bytes = (8.0 + 3.0 * sizeof(XT) + ((y ? 3.0 : 0.0) + (ycopy ? 3.0 : 0.0)) * sizeof(YT) + (mode ? 3.0 * sizeof(BT) : 0.0) +
                           (dotvec ? 24.0 : 0.0)) * lv.npts;
     Prof p(c, VOF_K_APPLY0, 0, bytes);
-    ApplyGrid ag = apply_grid(c, np);
+    ApplyGrid ag = apply_grid(c, pair_slots(c, active, np));
     double* part = (dotvec || want_yy) ? c->partials : nullptr;
     const ApArgs a = ap_args(c, ag.TI, active);
     if (mode)
@@ -532,9 +544,9 @@ void apply_fine_t(vof_ctx* c, const XT* x, const BT* b, YT* y, int mode, int np,
 }
 
 template <typename VT>
-void apply_stored_t(vof_ctx* c, int l, const VT* x, const VT* b, VT* y, int mode, int np, const int* active) {
+void apply_stored_t(vof_ctx* c, int l, const VT* x, const VT* b, VT* y, int mode, int np, ActiveSet active) {
     Level& lv = c->L[l];
-    dim3 g = grid2d(lv.ni, lv.nj, np);
+    dim3 g = grid2d(lv.ni, lv.nj, pair_slots(c, active, np));
     Prof p(c, VOF_K_RESIDUAL, l, (coef_bytes(c, l) + (mode ? 9.0 : 6.0) * sizeof(VT)) * lv.npts);
     if (mode) CDISPATCH(c, l, (k_apply<CT, 1, VT><<<g, blk2d, 0, c->stream>>>((const CW*)lv.C, lv.ni, lv.nj, x, b, y, active)));
     else CDISPATCH(c, l, (k_apply<CT, 0, VT><<<g, blk2d, 0, c->stream>>>((const CW*)lv.C, lv.ni, lv.nj, x, b, y, active)));
@@ -542,7 +554,7 @@ void apply_stored_t(vof_ctx* c, int l, const VT* x, const VT* b, VT* y, int mode
 
 // V-cycle internal operator application on level l (all vectors VT)
 template <typename VT>
-void apply_level_t(vof_ctx* c, int l, const VT* x, const VT* b, VT* y, int mode, int np, const int* active) {
+void apply_level_t(vof_ctx* c, int l, const VT* x, const VT* b, VT* y, int mode, int np, ActiveSet active) {
     if (l == 0 && c->L[0].C == nullptr) apply_fine_t<VT, VT, VT>(c, x, b, y, mode, np, active);
     else apply_stored_t<VT>(c, l, x, b, y, mode, np, active);
 }
@@ -550,7 +562,7 @@ void apply_level_t(vof_ctx* c, int l, const VT* x, const VT* b, VT* y, int mode,
 // Krylov-level products on level 0 with FP64 results: out = A y (y V-typed) and out = b - A x (all double).
 // On the matrix-free level 0 the reductions asked for (out.dotvec and/or out.out) are fused into the operator kernel
 // and the function returns the number of per-pair partials it wrote; otherwise 0 (the caller then launches k_dot2).
-int krylov_apply(vof_ctx* c, const void* y, double* out, int np, const int* active, const double* dotvec = nullptr,
+int krylov_apply(vof_ctx* c, const void* y, double* out, int np, ActiveSet active, const double* dotvec = nullptr,
                  int want_yy = 0) {
     if (c->L[0].C) { apply_stored_t<double>(c, 0, (const double*)y, nullptr, out, 0, np, active); return 0; }
     if (c->vfloat || c->h32) apply_fine_t<float, double, double>(c, (const float*)y, nullptr, out, 0, np, active, dotvec, want_yy);
@@ -561,7 +573,7 @@ int krylov_apply(vof_ctx* c, const void* y, double* out, int np, const int* acti
 // not possible, and the caller falls back to a residual vector)
 // out2 (streaming kernel only, see residual_copy_ok): a second copy of the residual
 inline bool residual_copy_ok(const vof_ctx* c) { return !c->L[0].C; }
-int residual_d(vof_ctx* c, const double* x, const double* b, double* out, int np, const int* active, int want_norm = 0,
+int residual_d(vof_ctx* c, const double* x, const double* b, double* out, int np, ActiveSet active, int want_norm = 0,
                double* out2 = nullptr) {
     if (!out && !(want_norm && !c->L[0].C)) return 0;
     if (c->L[0].C) { apply_stored_t<double>(c, 0, x, b, out, 1, np, active); return 0; }
@@ -581,7 +593,7 @@ int fused_prologue(vof_ctx* c, const int* src, double c0, double c1, double c2, 
     ApEnds e{};
     e.saved = c->warm_x; e.src = src; e.c0 = c0; e.c1 = c1; e.c2 = c2; e.xo = c->kx; e.bo = c->kb;
     k_stream_apply0<2, double, double, double><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-        ap_args(c, ag.TI, nullptr), nullptr, nullptr, c->kr, nullptr, 0, c->partials, ag.nblk, c->krh, e);
+        ap_args(c, ag.TI, ALL_PAIRS), nullptr, nullptr, c->kr, nullptr, 0, c->partials, ag.nblk, c->krh, e);
     return ag.nblk;
 }
 // Epilogue: the norm of the independent residual b - A x (slot 0 of c->partials) and, from the same rows of x, the outputs and
@@ -595,23 +607,23 @@ int fused_epilogue(vof_ctx* c, double* vx, double* vy, double* gm, double* speed
     ApEnds e{};
     e.vscale = c->prm.delta_x / c->prm.delta_t; e.vx = vx; e.vy = vy; e.gm = gm; e.speed = speed; e.fpartials = fpart;
     k_stream_apply0<3, double, double, double><<<ag.grid, AP_THREADS, 0, c->stream>>>(
-        ap_args(c, ag.TI, nullptr), c->kx, c->kb, nullptr, nullptr, 1, c->partials, ag.nblk, nullptr, e);
+        ap_args(c, ag.TI, ALL_PAIRS), c->kx, c->kb, nullptr, nullptr, 1, c->partials, ag.nblk, nullptr, e);
     return ag.nblk;
 }
 
 template <typename VT>
-void restrict_level_t(vof_ctx* c, int l, const VT* fine, VT* coarse, int np, const int* active) {
+void restrict_level_t(vof_ctx* c, int l, const VT* fine, VT* coarse, int np, ActiveSet active) {
     Level &f = c->L[l], &k = c->L[l + 1];
     Prof p(c, VOF_K_RESTRICT, l, 3.0 * sizeof(VT) * (f.npts + k.npts));
-    k_restrict<VT><<<grid2d(k.ni, k.nj, np), blk2d, 0, c->stream>>>(fine, f.ni, f.nj, coarse, k.ni, k.nj, active);
+    k_restrict<VT><<<grid2d(k.ni, k.nj, pair_slots(c, active, np)), blk2d, 0, c->stream>>>(fine, f.ni, f.nj, coarse, k.ni, k.nj, active);
 }
 
 // level 0, matrix-free: coarse right-hand side b_1 = R (b - A x) in one pass (no fine residual in HBM)
 template <typename VT, typename CVT = VT>
-void resrestrict_fine_t(vof_ctx* c, const VT* x, const VT* b, CVT* bc, int np, const int* active) {
+void resrestrict_fine_t(vof_ctx* c, const VT* x, const VT* b, CVT* bc, int np, ActiveSet active) {
     Level &f = c->L[0], &k = c->L[1];
     int TI = pick_band_height(f.ni, (k.nj + RR_CO - 1) / RR_CO, c->cur_units);
-    dim3 g((k.nj + RR_CO - 1) / RR_CO, (k.ni + TI / 2 - 1) / (TI / 2), np);
+    dim3 g((k.nj + RR_CO - 1) / RR_CO, (k.ni + TI / 2 - 1) / (TI / 2), pair_slots(c, active, np));
     Prof p(c, VOF_K_APPLY0, 0, (8.0 + 6.0 * sizeof(VT)) * f.npts + 3.0 * sizeof(CVT) * k.npts);
     k_stream_resrestrict0<VT, VT, CVT><<<g, AP_THREADS, 0, c->stream>>>(ap_args(c, TI, active), x, b, bc, k.ni, k.nj);
 }
@@ -623,14 +635,14 @@ inline double resu_coef_bytes(const vof_ctx* c) {   // average per fine point: 8
     return c->cfmt == 3 ? 12.0 * 4 : (c->cfmt == 2 ? 18.5 * 4 : (c->cfmt == 1 ? 36.0 * 4 : 36.0 * 8));
 }
 template <typename VT>
-void resrestrict_u_t(vof_ctx* c, int l, const VT* x_new, const VT* x_old, VT* bc, int np, const int* active) {
+void resrestrict_u_t(vof_ctx* c, int l, const VT* x_new, const VT* x_old, VT* bc, int np, ActiveSet active) {
     Level &f = c->L[l], &k = c->L[l + 1];
     const double vs = sizeof(VT);
     // algorithmic: the residual and the restriction it performs (as apply_stored_t + restrict_level_t count them)
     const double algo = (coef_bytes(c, l) + 9.0 * vs) * f.npts + 3.0 * vs * (f.npts + k.npts);
     const double moved = (resu_coef_bytes(c) + (x_old ? 6.0 : 3.0) * vs) * f.npts + 3.0 * vs * k.npts;
     Prof p(c, VOF_K_RESIDUAL, l, algo, moved);
-    dim3 g(1, (k.ni + BY - 1) / BY, np);
+    dim3 g(1, (k.ni + BY - 1) / BY, pair_slots(c, active, np));
     CDISPATCH(c, l, {
         if (x_old) k_resrestrict_u<CT, VT, true><<<g, blk2d, 0, c->stream>>>((const CW*)f.C, f.ni, f.nj, x_new, x_old, bc, k.ni, k.nj, active);
         else k_resrestrict_u<CT, VT, false><<<g, blk2d, 0, c->stream>>>((const CW*)f.C, f.ni, f.nj, x_new, x_old, bc, k.ni, k.nj, active);
@@ -638,16 +650,16 @@ void resrestrict_u_t(vof_ctx* c, int l, const VT* x_new, const VT* x_old, VT* bc
 }
 
 template <typename VT>
-void prolong_add_level_t(vof_ctx* c, int l, VT* fine, const VT* coarse, int np, const int* active) {
+void prolong_add_level_t(vof_ctx* c, int l, VT* fine, const VT* coarse, int np, ActiveSet active) {
     Level &f = c->L[l], &k = c->L[l + 1];
     Prof p(c, VOF_K_PROLONG, l, 3.0 * sizeof(VT) * (2 * f.npts + k.npts));
-    k_prolong_add<VT><<<grid2d(f.ni, f.nj, np), blk2d, 0, c->stream>>>(fine, f.ni, f.nj, coarse, k.ni, k.nj, active);
+    k_prolong_add<VT><<<grid2d(f.ni, f.nj, pair_slots(c, active, np)), blk2d, 0, c->stream>>>(fine, f.ni, f.nj, coarse, k.ni, k.nj, active);
 }
 
 template <typename VT>
-void coarse_solve_t(vof_ctx* c, const VT* r, VT* e, int np, const int* active) {
+void coarse_solve_t(vof_ctx* c, const VT* r, VT* e, int np, ActiveSet active) {
     Prof p(c, VOF_K_COARSE_SOLVE, (int)c->L.size() - 1);
-    k_coarse_solve<VT><<<np, 256, c->nd * sizeof(double), c->stream>>>(c->invT, c->nd, r, e, active);
+    k_coarse_solve<VT><<<pair_slots(c, active, np), 256, c->nd * sizeof(double), c->stream>>>(c->invT, c->nd, r, e, active);
 }
 
 // k_sweep0m (merged colours, 16-byte accesses, up to two sweeps per pass) needs float64 vectors and an even row length
@@ -874,88 +886,88 @@ inline bool handoff32_ok(const vof_ctx* c) {
 //   k_sweep0p   12   <NS 1|2, EC, FROM_ZERO, PO 0|1>, (EC, FROM_ZERO) = (1,0) (0,1) (0,0)
 //   k_sweep0     6   <VT double|float, EC, FROM_ZERO>, (EC, FROM_ZERO) = (1,0) (0,1) (0,0)
 struct L0Ptrs {
-    const void* x_in; void* x_out; const void* b; const int* active; const void* ecoarse;
+    const void* x_in; void* x_out; const void* b; ActiveSet active; const void* ecoarse;
     S0Trail tr; S0BSrc bsrc;
 };
 template <int V> using IntTag = std::integral_constant<int, V>;
 template <typename T> constexpr bool is_f32() { return std::is_same<T, float>::value; }
 
 template <int NS, bool EC, bool FZ, int TR, typename ET, int PO, int BF = 0, typename XT = double>
-bool s0r_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+bool s0r_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
     if (p.NS != NS || p.EC != EC || p.FROM_ZERO != FZ || p.TRAIL != TR || p.ET32 != is_f32<ET>() || p.PO != PO || p.BF != BF || p.XT32 != is_f32<XT>()) return false;
-    k_sweep0r<NS, EC, FZ, TR, ET, PO, 1, BF, XT><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
-        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, np, (const XT*)a.x_in, (XT*)a.x_out, (const double*)a.b, a.active,
+    k_sweep0r<NS, EC, FZ, TR, ET, PO, 1, BF, XT><<<dim3(p.blocks * nslots), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, nslots, (const XT*)a.x_in, (XT*)a.x_out, (const double*)a.b, a.active,
         (const ET*)a.ecoarse, p.nci, p.ncj, a.tr, 0, 0, a.bsrc);
     return true;
 }
-bool launch_s0r(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+bool launch_s0r(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
     auto shapes = [&](auto ns, auto po) {
         constexpr int NS = decltype(ns)::value, PO = decltype(po)::value;
-        return s0r_row<NS, true, false, 1, float, PO>(c, p, f0, np, a) || s0r_row<NS, true, false, 0, float, PO>(c, p, f0, np, a) ||
-               s0r_row<NS, true, false, 1, double, PO>(c, p, f0, np, a) || s0r_row<NS, false, false, 1, double, PO>(c, p, f0, np, a) ||
-               s0r_row<NS, true, false, 0, double, PO>(c, p, f0, np, a) ||
-               s0r_row<NS, false, true, 0, double, PO, s0r_bf_from_zero(NS)>(c, p, f0, np, a) ||
-               s0r_row<NS, false, false, 0, double, PO>(c, p, f0, np, a);
+        return s0r_row<NS, true, false, 1, float, PO>(c, p, f0, nslots, a) || s0r_row<NS, true, false, 0, float, PO>(c, p, f0, nslots, a) ||
+               s0r_row<NS, true, false, 1, double, PO>(c, p, f0, nslots, a) || s0r_row<NS, false, false, 1, double, PO>(c, p, f0, nslots, a) ||
+               s0r_row<NS, true, false, 0, double, PO>(c, p, f0, nslots, a) ||
+               s0r_row<NS, false, true, 0, double, PO, s0r_bf_from_zero(NS)>(c, p, f0, nslots, a) ||
+               s0r_row<NS, false, false, 0, double, PO>(c, p, f0, nslots, a);
     };
     auto from_zero = [&](auto bf) {   // the two-sweep pass from zero with the coarse right-hand side and / or the vector update
         constexpr int BF = decltype(bf)::value;
-        return s0r_row<2, false, true, 2, float, 0, BF, float>(c, p, f0, np, a) || s0r_row<2, false, true, 2, float, 0, BF, double>(c, p, f0, np, a) ||
-               s0r_row<2, false, true, 2, double, 0, BF, double>(c, p, f0, np, a);
+        return s0r_row<2, false, true, 2, float, 0, BF, float>(c, p, f0, nslots, a) || s0r_row<2, false, true, 2, float, 0, BF, double>(c, p, f0, nslots, a) ||
+               s0r_row<2, false, true, 2, double, 0, BF, double>(c, p, f0, nslots, a);
     };
     return from_zero(IntTag<3>{}) || from_zero(IntTag<1>{}) || from_zero(IntTag<2>{}) ||
-           s0r_row<2, false, true, 0, double, 0, 1, double>(c, p, f0, np, a) || s0r_row<2, false, true, 0, double, 0, 2, double>(c, p, f0, np, a) ||
-           s0r_row<2, true, false, 1, float, 1, 0, float>(c, p, f0, np, a) || s0r_row<2, true, false, 1, double, 1, 0, float>(c, p, f0, np, a) ||
-           s0r_row<2, true, false, 0, float, 1, 0, float>(c, p, f0, np, a) || s0r_row<2, true, false, 0, double, 1, 0, float>(c, p, f0, np, a) ||
+           s0r_row<2, false, true, 0, double, 0, 1, double>(c, p, f0, nslots, a) || s0r_row<2, false, true, 0, double, 0, 2, double>(c, p, f0, nslots, a) ||
+           s0r_row<2, true, false, 1, float, 1, 0, float>(c, p, f0, nslots, a) || s0r_row<2, true, false, 1, double, 1, 0, float>(c, p, f0, nslots, a) ||
+           s0r_row<2, true, false, 0, float, 1, 0, float>(c, p, f0, nslots, a) || s0r_row<2, true, false, 0, double, 1, 0, float>(c, p, f0, nslots, a) ||
            shapes(IntTag<2>{}, IntTag<0>{}) || shapes(IntTag<2>{}, IntTag<1>{}) || shapes(IntTag<1>{}, IntTag<0>{}) || shapes(IntTag<1>{}, IntTag<1>{});
 }
 
 template <int NS, bool EC, bool FZ, int TR, typename ET = double>
-bool s0m_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+bool s0m_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
     if (p.NS != NS || p.EC != EC || p.FROM_ZERO != FZ || p.TRAIL != TR || p.ET32 != is_f32<ET>()) return false;
-    k_sweep0m<NS, EC, FZ, TR, ET><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
-        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, np, (const double*)a.x_in, (double*)a.x_out, (const double*)a.b, a.active,
+    k_sweep0m<NS, EC, FZ, TR, ET><<<dim3(p.blocks * nslots), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, nslots, (const double*)a.x_in, (double*)a.x_out, (const double*)a.b, a.active,
         (const ET*)a.ecoarse, p.nci, p.ncj, a.tr);
     return true;
 }
-bool launch_s0m(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+bool launch_s0m(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
     auto shapes = [&](auto ns) {
         constexpr int NS = decltype(ns)::value;
-        return s0m_row<NS, true, false, 1, float>(c, p, f0, np, a) || s0m_row<NS, true, false, 0, float>(c, p, f0, np, a) ||
-               s0m_row<NS, true, false, 1>(c, p, f0, np, a) || s0m_row<NS, false, false, 1>(c, p, f0, np, a) ||
-               s0m_row<NS, true, false, 0>(c, p, f0, np, a) || s0m_row<NS, false, true, 0>(c, p, f0, np, a) ||
-               s0m_row<NS, false, false, 0>(c, p, f0, np, a);
+        return s0m_row<NS, true, false, 1, float>(c, p, f0, nslots, a) || s0m_row<NS, true, false, 0, float>(c, p, f0, nslots, a) ||
+               s0m_row<NS, true, false, 1>(c, p, f0, nslots, a) || s0m_row<NS, false, false, 1>(c, p, f0, nslots, a) ||
+               s0m_row<NS, true, false, 0>(c, p, f0, nslots, a) || s0m_row<NS, false, true, 0>(c, p, f0, nslots, a) ||
+               s0m_row<NS, false, false, 0>(c, p, f0, nslots, a);
     };
     return shapes(IntTag<2>{}) || shapes(IntTag<1>{});
 }
 
 template <int NS, bool EC, bool FZ, int PO>
-bool s0p_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+bool s0p_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
     if (p.NS != NS || p.EC != EC || p.FROM_ZERO != FZ || p.PO != PO) return false;
-    k_sweep0p<NS, EC, FZ, PO><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
-        f0, c->L[0].ni, c->L[0].nj, p.TI, p.nx, p.nxp, p.ny, np, (const float*)a.x_in, (float*)a.x_out, (const float*)a.b, a.active,
+    k_sweep0p<NS, EC, FZ, PO><<<dim3(p.blocks * nslots), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.nx, p.nxp, p.ny, nslots, (const float*)a.x_in, (float*)a.x_out, (const float*)a.b, a.active,
         (const float*)a.ecoarse, p.nci, p.ncj);
     return true;
 }
-bool launch_s0p(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+bool launch_s0p(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
     auto shapes = [&](auto ns, auto po) {
         constexpr int NS = decltype(ns)::value, PO = decltype(po)::value;
-        return s0p_row<NS, true, false, PO>(c, p, f0, np, a) || s0p_row<NS, false, true, PO>(c, p, f0, np, a) ||
-               s0p_row<NS, false, false, PO>(c, p, f0, np, a);
+        return s0p_row<NS, true, false, PO>(c, p, f0, nslots, a) || s0p_row<NS, false, true, PO>(c, p, f0, nslots, a) ||
+               s0p_row<NS, false, false, PO>(c, p, f0, nslots, a);
     };
     return shapes(IntTag<2>{}, IntTag<0>{}) || shapes(IntTag<2>{}, IntTag<1>{}) || shapes(IntTag<1>{}, IntTag<0>{}) || shapes(IntTag<1>{}, IntTag<1>{});
 }
 
 template <typename VT, bool EC, bool FZ>
-bool s0_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
+bool s0_row(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
     if (p.EC != EC || p.FROM_ZERO != FZ) return false;
-    k_sweep0<VT, EC, FZ><<<dim3(p.blocks * np), p.block, p.lds, c->stream>>>(
-        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, np, (const VT*)a.x_in, (VT*)a.x_out, (const VT*)a.b, a.active,
+    k_sweep0<VT, EC, FZ><<<dim3(p.blocks * nslots), p.block, p.lds, c->stream>>>(
+        f0, c->L[0].ni, c->L[0].nj, p.TI, p.PO, p.nx, p.ny, nslots, (const VT*)a.x_in, (VT*)a.x_out, (const VT*)a.b, a.active,
         (const VT*)a.ecoarse, p.nci, p.ncj);
     return true;
 }
 template <typename VT>
-bool launch_s0(vof_ctx* c, const L0Pass& p, const Fine0& f0, int np, const L0Ptrs& a) {
-    return s0_row<VT, true, false>(c, p, f0, np, a) || s0_row<VT, false, true>(c, p, f0, np, a) || s0_row<VT, false, false>(c, p, f0, np, a);
+bool launch_s0(vof_ctx* c, const L0Pass& p, const Fine0& f0, int nslots, const L0Ptrs& a) {
+    return s0_row<VT, true, false>(c, p, f0, nslots, a) || s0_row<VT, false, true>(c, p, f0, nslots, a) || s0_row<VT, false, false>(c, p, f0, nslots, a);
 }
 
 // The folded s update (BF = 1) is followed, in stream order, by what follows the stand-alone k_update_s: (s, s) and the stopping
@@ -988,7 +1000,7 @@ struct SmoothArgs {
 
 // One pass x_in -> x_out (x_in == nullptr: zero initial guess): a.nsweeps full 4-colour sweeps.
 template <typename VT>
-void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, int np, const int* active, const SmoothArgs<VT>& a,
+void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, int np, ActiveSet active, const SmoothArgs<VT>& a,
                    CycleIO& io) {
     Level& lv = c->L[l];
     const VT* ecoarse = a.ecoarse;
@@ -1012,11 +1024,12 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, in
         bool launched = false;
         {
             Prof pr(c, VOF_K_GS0, 0, p.algo, p.moved);
+            const int nslots = pair_slots(c, active, np);
             switch (p.fam) {
-                case L0_SWEEP0R: launched = launch_s0r(c, p, f0, np, ptrs); break;
-                case L0_SWEEP0M: launched = launch_s0m(c, p, f0, np, ptrs); break;
-                case L0_SWEEP0P: launched = launch_s0p(c, p, f0, np, ptrs); break;
-                case L0_SWEEP0: launched = launch_s0<VT>(c, p, f0, np, ptrs); break;
+                case L0_SWEEP0R: launched = launch_s0r(c, p, f0, nslots, ptrs); break;
+                case L0_SWEEP0M: launched = launch_s0m(c, p, f0, nslots, ptrs); break;
+                case L0_SWEEP0P: launched = launch_s0p(c, p, f0, nslots, ptrs); break;
+                case L0_SWEEP0: launched = launch_s0<VT>(c, p, f0, nslots, ptrs); break;
             }
         }
         if (!launched) { c->err = "internal: the library holds no kernel for the planned level-0 pass"; io.failed = true; return; }
@@ -1031,7 +1044,8 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, in
     const int nx = (lv.nj + GeoB::OUT - 1) / GeoB::OUT;
     const int TI = pick_band_height(rows, nx, c->cur_units);
     const int ny = (rows + TI - 1) / TI;
-    dim3 g((unsigned)nx * ny * np, 1, 1);
+    const int nslots = pair_slots(c, active, np);
+    dim3 g((unsigned)nx * ny * nslots, 1, 1);
     const double vs = sizeof(VT);
     int nci = 0, ncj = 0;
     double ebytes = 0.0;
@@ -1044,12 +1058,12 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, in
         using PCT = typename decltype(ct_tag)::type;
         if (ecoarse) {   // the sweep starts from x_in + P ecoarse (coarse rows through a 3-row LDS ring)
             const size_t lds_e = lds + (size_t)9 * (W / 2 + 2) * sizeof(VT);
-            if (a.out64) k_sweep_st<PCT, VT, double, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, (double*)x_out, b, active, ecoarse, nci, ncj, 0);
-            else k_sweep_st<PCT, VT, VT, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj, 0);
+            if (a.out64) k_sweep_st<PCT, VT, double, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, nslots, x_in, (double*)x_out, b, active, ecoarse, nci, ncj, 0);
+            else k_sweep_st<PCT, VT, VT, true><<<g, GeoB::THREADS, lds_e, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, nslots, x_in, x_out, b, active, ecoarse, nci, ncj, 0);
         } else {
             const int sk = (a.skip0 && x_in && !a.reverse) ? 1 : 0;
-            if (a.out64) k_sweep_st<PCT, VT, double><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, (double*)x_out, b, active, nullptr, 0, 0, sk);
-            else k_sweep_st<PCT, VT><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, nullptr, 0, 0, sk);
+            if (a.out64) k_sweep_st<PCT, VT, double><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, nslots, x_in, (double*)x_out, b, active, nullptr, 0, 0, sk);
+            else k_sweep_st<PCT, VT><<<g, GeoB::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, po, nx, ny, nslots, x_in, x_out, b, active, nullptr, 0, 0, sk);
         }
         };
         if (c->cfmt == 3) launch(TypeTag<CoefF8>{}); else launch(TypeTag<CoefB16>{});
@@ -1057,7 +1071,7 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, in
     }
     CDISPATCH(c, l, {
         SweepStored<CT> pol; pol.C = (const CW*)lv.C; pol.plane = CLay(lv.ni, lv.nj).plane;
-        k_sweep<SweepStored<CT>, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, np, x_in, x_out, b, active, ecoarse, nci, ncj);
+        k_sweep<SweepStored<CT>, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, nslots, x_in, x_out, b, active, ecoarse, nci, ncj);
     });
 }
 
@@ -1066,7 +1080,7 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, in
 // a.ecoarse: on the matrix-free level 0 it is folded into the first sweep (coarse rows streamed through LDS); otherwise the
 // prolongation kernel runs first.
 template <typename VT>
-VT* smooth_level_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int nu, int np, const int* active, SmoothArgs<VT> a, CycleIO& io) {
+VT* smooth_level_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int nu, int np, ActiveSet active, SmoothArgs<VT> a, CycleIO& io) {
     const size_t bytes = (size_t)np * 3 * c->L[l].npts * sizeof(VT);
     const bool fine0 = l == 0 && c->L[0].C == nullptr;
     const bool fold = a.ecoarse && nu > 0 && c->fused && !a.from_zero && (fine0 || (sweep_st_usable(c, l) && c->fold_stored));
@@ -1149,7 +1163,7 @@ bool tail_prepare(vof_ctx* c) {
 }
 
 template <typename VT>
-void tail_cycle_t(vof_ctx* c, VT* x, const VT* b, int np, const int* active, bool from_zero) {
+void tail_cycle_t(vof_ctx* c, VT* x, const VT* b, int np, ActiveSet active, bool from_zero) {
     TailArgs A = c->tail;
     const int l0 = c->tail_first, last = (int)c->L.size() - 1;
     for (int l = l0; l <= last; ++l) A.L[l - l0].C = c->L[l].C;
@@ -1157,7 +1171,7 @@ void tail_cycle_t(vof_ctx* c, VT* x, const VT* b, int np, const int* active, boo
     if (!from_zero) A.op_arg[0] &= ~1;   // the first operation is the pre-smoothing of the top tail level
     const Level& top = c->L[l0];
     Prof p(c, VOF_K_COARSE_TAIL, l0, (from_zero ? 6.0 : 9.0) * sizeof(VT) * top.npts);   // b in, x (in and) out; stencils stay in cache
-    CDISPATCH(c, l0, (k_tail_cycle<CT, VT><<<np, TAIL_THREADS, c->tail_lds, c->stream>>>(A, b, x, from_zero ? 1 : 0, active)));
+    CDISPATCH(c, l0, (k_tail_cycle<CT, VT><<<pair_slots(c, active, np), TAIL_THREADS, c->tail_lds, c->stream>>>(A, b, x, from_zero ? 1 : 0, active)));
 }
 
 // One multigrid cycle on level l for A_l x = b, starting from a zero guess (from_zero) or from the contents of x.
@@ -1167,7 +1181,7 @@ void tail_cycle_t(vof_ctx* c, VT* x, const VT* b, int np, const int* active, boo
 template <typename VT>
 // after_post: x holds the result of a previous visit of this level with the same b, i.e. of its reverse post-smoothing sweep
 // emit64 (level 1 under a float64 level 0, vcycle_precision 3): the last post-smoothing sweep writes the result as float64
-VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, const int* active, CycleIO& io, bool from_zero = true,
+VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, ActiveSet active, CycleIO& io, bool from_zero = true,
              bool after_post = false, bool emit64 = false) {
     int last = (int)c->L.size() - 1;
     if (l == last) { coarse_solve_t<VT>(c, b, x, np, active); return x; }
@@ -1250,7 +1264,7 @@ template <typename VT> int direct_apply_t(vof_ctx* c, VT* z, const VT* r, int np
 
 // One cycle M b -> *xslot (c->ky or c->kz).  The out-of-place sweeps may leave the result in the level-0 ping-pong partner
 // instead (an odd number of passes); the two buffers then trade places - a pointer swap instead of a copy of the vector.
-void vcycle(vof_ctx* c, double** xslot, const void* b, int np, const int* active, CycleIO& io) {
+void vcycle(vof_ctx* c, double** xslot, const void* b, int np, ActiveSet active, CycleIO& io) {
     if (c->direct_on) {   // the direct preconditioner takes the place of the cycle (every pair of the batch, active or not)
         VDISPATCH(c, direct_apply_t<VT>(c, (VT*)*xslot, (const VT*)b, np));
         return;
@@ -1346,13 +1360,28 @@ int setup_batch(vof_ctx* c, const double* frames_dev, int np) {
 }
 
 inline dim3 rgrid(const vof_ctx* c, int np) { return dim3(c->nblk, np, 1); }
+inline dim3 rgrid(const vof_ctx* c, int np, const ActiveSet& a) { return rgrid(c, pair_slots(c, a, np)); }
 
-// Number of active pairs (copies the flags to the host; synchronises the stream).
-int count_active(vof_ctx* c, int np) {
+// The active list from the flags in c->h_active, which the caller has just copied and waited for: the slots that are on, in
+// ascending order, into the pinned mirror, and its copy queued on the context's stream.  The wait that precedes the next call
+// (the next count) also ends that copy, so the one mirror is never rewritten under a copy in flight.
+int post_active_list(vof_ctx* c, int np) {
+    if (!c->use_alist) return 0;
+    int n = 0;
+    for (int k = 0; k < np; ++k) if (c->h_active[k]) c->h_alist[n++] = k;
+    c->alist_n = n;
+    if (n) HIPCHK(hipMemcpyAsync(c->alist, c->h_alist, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// Number of active pairs (copies the flags to the host; synchronises the stream); the active list is renewed along unless the
+// caller still launches over the pairs of the list in place (renew_list == false).
+int count_active(vof_ctx* c, int np, bool renew_list = true) {
     if (hipMemcpyAsync(c->h_active, c->active, np * sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
     int n = 0;
     for (int k = 0; k < np; ++k) n += c->h_active[k] != 0;
+    if (renew_list && post_active_list(c, np)) return -1;
     return n;
 }
 
@@ -1426,22 +1455,26 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
     c->vcoarse32 = false;
     double* V = c->gm_V;
     double* w = c->kt;
-    const dim3 rg = rgrid(c, np);
     const int coef_c = (int)(offsetof(GmresState, c) / sizeof(double)), coef_y = (int)(offsetof(GmresState, y) / sizeof(double));
     for (;;) {
         c->cur_units = nact;
-        int nb = residual_d(c, c->kx, c->kb, V, np, c->gm_cycle, 1);      // V_0 = b - A x and its norm
-        if (!nb) { Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rg, RBLK, 0, s>>>(V, V, nullptr, nullptr, len, c->partials, c->gm_cycle); nb = c->nblk; }
+        // The active list holds the pairs of the cycle from one k_gm_init to the next: k_gm_begin and k_gm_init leave active ==
+        // cycle, and the list is taken at the count that follows them.  The counts inside a cycle do not renew it - the cycle's
+        // last launches go by the cycle flags again -, so a pair that drops out in between keeps its blocks, which leave at once.
+        const ActiveSet cyc = listed(c, c->gm_cycle);
+        int nb = residual_d(c, c->kx, c->kb, V, np, cyc, 1);      // V_0 = b - A x and its norm
+        if (!nb) { Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rgrid(c, np, cyc), RBLK, 0, s>>>(V, V, nullptr, nullptr, len, c->partials, cyc); nb = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0);
           k_gm_init<<<np, 64, 0, s>>>(c->gm_state, c->sc, c->partials, nb, c->active, c->gm_cycle, P.max_iterations); }
         nact = count_active(c, np);
         if (nact < 0) { c->err = "stream synchronize failed"; return -2; }
         if (nact == 0) break;
         c->cur_units = nact;
-        { Prof p(c, VOF_K_VECTOR, 0, 16.0 * len); k_gm_scale<<<rg, RBLK, 0, s>>>(V, V, len, c->gm_state, c->active); }
+        const ActiveSet act = listed(c, c->active);
+        const dim3 rg = rgrid(c, np, act);   // (the same for the cycle flags: one list)
+        { Prof p(c, VOF_K_VECTOR, 0, 16.0 * len); k_gm_scale<<<rg, RBLK, 0, s>>>(V, V, len, c->gm_state, act); }
         int jdone = 0;
         for (int j = 0; j < m; ++j) {
-            const int* act = c->active;
             CycleIO io;
             vcycle(c, &c->ky, V + (size_t)j * vstride, np, act, io);         // z = M v_j
             if (io.failed) return -1;
@@ -1451,7 +1484,7 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
                     int cnt = std::min(GM_NV, j + 1 - i0);
                     Prof p(c, VOF_K_REDUCE, 0, 8.0 * len * (cnt + 1));
                     k_gm_multidot<<<rg, RBLK, 0, s>>>(V + (size_t)i0 * vstride, vstride, cnt, w, len, c->gm_partials, act);
-                    k_gm_hcoef<<<np, 64, 0, s>>>(c->gm_state, c->gm_partials, c->nblk, i0, cnt, pass, act);
+                    k_gm_hcoef<<<np, 64, 0, s>>>(c->gm_state, c->gm_partials, c->nblk, i0, cnt, pass, c->active);
                 }
                 for (int i0 = 0; i0 <= j; i0 += GM_NV) {
                     int cnt = std::min(GM_NV, j + 1 - i0);
@@ -1464,9 +1497,9 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
             }
             { Prof p(c, VOF_K_VECTOR, 0, 16.0 * len);
               k_gm_givens<<<np, 64, 0, s>>>(c->gm_state, c->sc, c->gm_partials, c->nblk, j, c->active, P.max_iterations);
-              k_gm_scale<<<rg, RBLK, 0, s>>>(V + (size_t)(j + 1) * vstride, V + (size_t)(j + 1) * vstride, len, c->gm_state, c->active); }
+              k_gm_scale<<<rg, RBLK, 0, s>>>(V + (size_t)(j + 1) * vstride, V + (size_t)(j + 1) * vstride, len, c->gm_state, act); }
             jdone = j + 1;
-            nact = count_active(c, np);
+            nact = count_active(c, np, /*renew_list=*/false);
             if (nact < 0) { c->err = "stream synchronize failed"; return -2; }
             if (nact == 0) break;
             c->cur_units = nact;
@@ -1477,12 +1510,12 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
             int cnt = std::min(GM_NV, jdone - i0);
             Prof p(c, VOF_K_VECTOR, 0, 8.0 * len * (cnt + 2));
             k_gm_axpy<<<rg, RBLK, 0, s>>>(V + (size_t)i0 * vstride, vstride, i0, cnt, c->gm_state, coef_y, 1.0,
-                                          i0 ? c->kp : nullptr, c->kp, len, c->gm_cycle, 1, nullptr);
+                                          i0 ? c->kp : nullptr, c->kp, len, cyc, 1, nullptr);
         }
         CycleIO io;
-        vcycle(c, &c->ky, c->kp, np, c->gm_cycle, io);
+        vcycle(c, &c->ky, c->kp, np, cyc, io);
         if (io.failed) return -1;
-        { Prof p(c, VOF_K_VECTOR, 0, 24.0 * len); k_gm_xpy<<<rg, RBLK, 0, s>>>(c->kx, c->ky, len, c->gm_cycle); }
+        { Prof p(c, VOF_K_VECTOR, 0, 24.0 * len); k_gm_xpy<<<rg, RBLK, 0, s>>>(c->kx, c->ky, len, cyc); }
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipGetLastError());
@@ -1708,11 +1741,11 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         }
         // r0 = b - A x0 with the partial sums of (r0, r0) and, where the streaming kernel runs, the copy r^ from the same pass
         const bool two = residual_copy_ok(c);
-        nb0 = residual_d(c, c->kx, c->kb, c->kr, np, nullptr, 1, two ? c->krh : nullptr);
+        nb0 = residual_d(c, c->kx, c->kb, c->kr, np, ALL_PAIRS, 1, two ? c->krh : nullptr);
         if (!two) HIPCHK(hipMemcpyAsync(c->krh, c->kr, (size_t)np * len * sizeof(double), hipMemcpyDeviceToDevice, s));
         // (p and v need no initialisation: the first iteration after a (re)start sets p = r without reading either)
         if (!nb0) {   // the operator kernel in use does not fuse the norm
-            Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kr, c->kr, nullptr, nullptr, len, c->partials, nullptr);
+            Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kr, c->kr, nullptr, nullptr, len, c->partials, ALL_PAIRS);
             nb0 = c->nblk;
         }
     }
@@ -1730,13 +1763,14 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         int nact = 0;
         for (int k = 0; k < np; ++k) nact += c->h_active[k] != 0;
         if (nact == 0) break;
+        if (int rc = post_active_list(c, np)) return rc;
         // vcycle_precision 2 ("auto"): float32 V-cycle vectors for the first iterations, float64 for stragglers
         // (in the slowly converging regimes float32 storage costs iterations)
         if (it_total == AUTO_F64_AFTER) { if (P.vcycle_precision == 2) c->vfloat = false; c->vcoarse32 = false; }
         c->cur_units = nact;
         // float32 level-0 hand-off vectors under the same rule (y and z of one iteration have the same type)
         c->h32 = handoff32_ok(c);
-        const int* act = c->active;
+        const ActiveSet act = listed(c, c->active);   // the launches of this iteration cover the nact listed pairs
         void* vrhs_p = c->vfloat ? (void*)c->b32 : (void*)c->kp;   // V-cycle right-hand sides (V-typed)
         void* vrhs_s = c->vfloat ? (void*)c->b32 : (void*)c->kr;
         const double vsz = (c->vfloat || c->h32) ? 4.0 : 8.0;
@@ -1764,7 +1798,7 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         } else {
             Prof p(c, VOF_K_VECTOR, 0, 8.0 * len * (it == 0 ? 2 : 4) + (c->vfloat ? 4.0 * len : 0.0));
             const double* p_old = (it == 1 && ran_on_r) ? rh : c->kp;
-            VDISPATCH(c, (k_update_p<VT><<<rgrid(c, np), RBLK, 0, s>>>(c->kp, p_old, c->kr, c->kv, len, c->sc, act,
+            VDISPATCH(c, (k_update_p<VT><<<rgrid(c, np, act), RBLK, 0, s>>>(c->kp, p_old, c->kr, c->kv, len, c->sc, act,
                                                                      c->vfloat ? (VT*)c->b32 : (VT*)nullptr, it == 0 ? 1 : 0)));
         }
         if (it == 0) ran_on_r = on_r;
@@ -1773,7 +1807,7 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         vcycle(c, &c->ky, vrhs_p, np, act, io_p);
         if (!cycle_ok(io_p, "p")) return -1;
         int nb1 = io_p.trail_nblk ? io_p.trail_nblk : krylov_apply(c, c->ky, c->kv, np, act, rh, 0);
-        if (!nb1) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(rh, c->kv, nullptr, nullptr, len, c->partials, act); nb1 = c->nblk; }
+        if (!nb1) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np, act), RBLK, 0, s>>>(rh, c->kv, nullptr, nullptr, len, c->partials, act); nb1 = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_ALPHA><<<np, 64, 0, s>>>(c->sc, c->partials, nb1, c->active, P.rtol, P.max_iterations); }
         if (fold_b) {
             // s = r - alpha v, (s, s), the half-step test and its x += alpha y: in / right after the first pass of the cycle on s
@@ -1784,7 +1818,7 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
             vrhs_s = (void*)c->kr;
         } else {
         { Prof p(c, VOF_K_VECTOR, 0, 8.0 * len * 3 + (c->vfloat ? 4.0 * len : 0.0));   // s = r - alpha v, (s, s)
-          VDISPATCH(c, (k_update_s<VT><<<rgrid(c, np), RBLK, 0, s>>>(c->kr, c->kv, len, c->sc, c->partials, act, c->vfloat ? (VT*)c->b32 : (VT*)nullptr))); }
+          VDISPATCH(c, (k_update_s<VT><<<rgrid(c, np, act), RBLK, 0, s>>>(c->kr, c->kv, len, c->sc, c->partials, act, c->vfloat ? (VT*)c->b32 : (VT*)nullptr))); }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_S><<<np, 64, 0, s>>>(c->sc, c->partials, c->nblk, c->active, P.rtol, P.max_iterations); }
         { Prof p(c, VOF_K_VECTOR, 0);                                  // pairs done at the half step: x += alpha y
           YDISPATCH(c, (k_fix_half<VT><<<dim3(64, np), RBLK, 0, s>>>(c->kx, (const VT*)c->ky, len, c->sc)));
@@ -1795,10 +1829,10 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
         vcycle(c, &c->kz, vrhs_s, np, act, io_s);
         if (!cycle_ok(io_s, "s")) return -1;
         int nb2 = io_s.trail_nblk ? io_s.trail_nblk : krylov_apply(c, c->kz, c->kt, np, act, c->kr, 1);
-        if (!nb2) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kt, c->kr, c->kt, c->kt, len, c->partials, act); nb2 = c->nblk; }
+        if (!nb2) { Prof p(c, VOF_K_REDUCE, 0, 16.0 * len); k_dot2<<<rgrid(c, np, act), RBLK, 0, s>>>(c->kt, c->kr, c->kt, c->kt, len, c->partials, act); nb2 = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_OMEGA><<<np, 64, 0, s>>>(c->sc, c->partials, nb2, c->active, P.rtol, P.max_iterations); }
         { Prof p(c, VOF_K_VECTOR, 0, 8.0 * len * 6 + 2.0 * vsz * len);   // x += alpha y + omega z; r = s - omega t; (r,r), (r^,r)
-          YDISPATCH(c, (k_update_xr<VT><<<rgrid(c, np), RBLK, 0, s>>>(c->kx, (const VT*)c->ky, (const VT*)c->kz, c->kr, c->kt, rh, len, c->sc, c->partials, act))); }
+          YDISPATCH(c, (k_update_xr<VT><<<rgrid(c, np, act), RBLK, 0, s>>>(c->kx, (const VT*)c->ky, (const VT*)c->kz, c->kr, c->kt, rh, len, c->sc, c->partials, act))); }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_R><<<np, 64, 0, s>>>(c->sc, c->partials, c->nblk, c->active, P.rtol, P.max_iterations); }
     }
     c->h32 = false;   // (the other users of the cycle - GMRES, the debug entry points - decide for themselves)
@@ -1809,9 +1843,9 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
     // (keep == false: only the norm, no residual vector - it is needed again only if a pair has to be restarted)
     auto independent_residual = [&](bool keep) -> int {
         c->cur_units = np;
-        int nb3 = keep ? 0 : residual_d(c, c->kx, c->kb, nullptr, np, nullptr, 1);
-        if (!nb3) nb3 = residual_d(c, c->kx, c->kb, c->kt, np, nullptr, 1);
-        if (!nb3) { Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kt, c->kt, nullptr, nullptr, len, c->partials, nullptr); nb3 = c->nblk; }
+        int nb3 = keep ? 0 : residual_d(c, c->kx, c->kb, nullptr, np, ALL_PAIRS, 1);
+        if (!nb3) nb3 = residual_d(c, c->kx, c->kb, c->kt, np, ALL_PAIRS, 1);
+        if (!nb3) { Prof p(c, VOF_K_REDUCE, 0); k_dot2<<<rgrid(c, np), RBLK, 0, s>>>(c->kt, c->kt, nullptr, nullptr, len, c->partials, ALL_PAIRS); nb3 = c->nblk; }
         { Prof p(c, VOF_K_VECTOR, 0); k_scalar<S_FINAL><<<np, 64, 0, s>>>(c->sc, c->partials, nb3, c->active, P.rtol, P.max_iterations); }
         HIPCHK(hipGetLastError());
         return 0;
@@ -1843,7 +1877,8 @@ int solve_batch(vof_ctx* c, const BatchReq& rq) {
             c->cur_units = nact;
             rh = c->krh;   // (the restarting pairs get their new r^ written; the others are done and no longer read theirs)
             { Prof p(c, VOF_K_VECTOR, 0, 8.0 * len * 3);
-              k_restart_vectors<<<rgrid(c, np), RBLK, 0, s>>>(c->kr, rh, c->kt, len, c->active); }
+              const ActiveSet act = listed(c, c->active);
+              k_restart_vectors<<<rgrid(c, np, act), RBLK, 0, s>>>(c->kr, rh, c->kt, len, act); }
             if (int rc = bicg_loop(std::min(bicg_limit, 8))) return rc;
             if (int rc = independent_residual(false)) return rc;
         }
@@ -2020,6 +2055,7 @@ void vof_destroy(vof_ctx* c) {
     for (auto e : c->free_events) hipEventDestroy(e);
     for (const auto& a : c->allocs) hipFree(a.raw);
     if (c->h_active) hipHostFree(c->h_active);
+    if (c->h_alist) hipHostFree(c->h_alist);
     if (c->h_sc) hipHostFree(c->h_sc);
     if (c->h_func3) hipHostFree(c->h_func3);
     if (c->h_bounce) hipHostFree(c->h_bounce);
@@ -2066,6 +2102,7 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     if (const char* e = getenv("VOF_FOLD_STORED")) c->fold_stored = e[0] != '0';
     if (const char* e = getenv("VOF_L0_HANDOFF")) c->l0_handoff = e[0] != '0';
     if (const char* e = getenv("VOF_SWEEP0R_MIN_BLOCKS")) c->sweep0r_min_blocks = atol(e);
+    if (const char* e = getenv("VOF_ACTIVE_LIST")) c->use_alist = e[0] != '0';
     if (const char* e = getenv("VOF_FUSE_B")) c->fuse_b = e[0] != '0';
     if (const char* e = getenv("VOF_FUSE_RR")) c->fuse_rr = e[0] != '0';
     if (const char* e = getenv("VOF_FUSED_ENDS")) { const int v = atoi(e); if (v >= 0 && v <= 3) c->fused_ends = v; }
@@ -2156,8 +2193,10 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     }
     if (int rc = dev_alloc(c, &c->sc, (size_t)B)) return rc;
     if (int rc = dev_alloc(c, &c->active, (size_t)B)) return rc;
+    if (int rc = dev_alloc(c, &c->alist, (size_t)B)) return rc;
     if (int rc = dev_alloc(c, &c->func3, (size_t)B * 3)) return rc;
     HIPCHK(hipHostMalloc((void**)&c->h_active, B * sizeof(int)));
+    HIPCHK(hipHostMalloc((void**)&c->h_alist, B * sizeof(int)));
     HIPCHK(hipHostMalloc((void**)&c->h_sc, B * sizeof(PairScalars)));
     HIPCHK(hipHostMalloc((void**)&c->h_func3, B * 3 * sizeof(double)));
     for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreate(&c->ev_batch[i]));
@@ -2310,6 +2349,7 @@ int make_lane(vof_ctx* c, int i, int n, vof_ctx* L) {
     L->partials += lo * c->part_per_pair;
     L->sc += lo; L->h_sc += lo;
     L->active += lo; L->h_active += lo;
+    L->alist += lo; L->h_alist += lo;
     L->func3 += 3 * lo; L->h_func3 += 3 * lo;
     if (L->pp_buf) L->pp_buf += lo;
     if (L->warm_src) L->warm_src += lo;
@@ -3090,11 +3130,11 @@ int vof_bench_sweeps_dev(vof_ctx* c, const double* movie, int n_pairs, const vof
         k_convert<double, float><<<1024, 256, 0, c->stream>>>(c->kb, (float*)c->b32, n);
         SmoothArgs<float> a;
         a.from_zero = true;
-        smooth_level_t<float>(c, 0, (float*)c->ky, (float*)f.x2, (const float*)c->b32, n_sweeps, n_pairs, nullptr, a, io);
+        smooth_level_t<float>(c, 0, (float*)c->ky, (float*)f.x2, (const float*)c->b32, n_sweeps, n_pairs, ALL_PAIRS, a, io);
     } else {
         SmoothArgs<double> a;
         a.from_zero = true;
-        smooth_level_t<double>(c, 0, c->kx, (double*)f.x2, c->kb, n_sweeps, n_pairs, nullptr, a, io);
+        smooth_level_t<double>(c, 0, c->kx, (double*)f.x2, c->kb, n_sweeps, n_pairs, ALL_PAIRS, a, io);
     }
     if (io.failed) return -1;
     HIPCHK(hipGetLastError());
@@ -3244,10 +3284,10 @@ int vof_debug_apply(vof_ctx* c, int level, const double* x_host, double* y_host)
     size_t n = nbytes / sizeof(double);
     if (int rc = dbg_up(c, c->kp, x_host, n)) return rc;
     if (level == 0) {   // the Krylov product: V-typed x, FP64 result
-        krylov_apply(c, c->kp, c->kv, c->npairs, nullptr);
+        krylov_apply(c, c->kp, c->kv, c->npairs, ALL_PAIRS);
         return d2h_bounced(c, y_host, c->kv, nbytes);
     }
-    VDISPATCH(c, apply_level_t<VT>(c, level, (const VT*)c->kp, (const VT*)nullptr, (VT*)c->kv, 0, c->npairs, nullptr));
+    VDISPATCH(c, apply_level_t<VT>(c, level, (const VT*)c->kp, (const VT*)nullptr, (VT*)c->kv, 0, c->npairs, ALL_PAIRS));
     return dbg_down(c, y_host, c->kv, n);
 }
 
@@ -3257,7 +3297,7 @@ int vof_debug_gs(vof_ctx* c, int level, double* x_host, const double* b_host, in
     if (c->vfloat) { c->err = "the per-colour reference smoother works on float64 vectors only"; return -1; }
     if (int rc = h2d_bounced(c, c->kp, x_host, nbytes)) return rc;
     if (int rc = h2d_bounced(c, c->kv, b_host, nbytes)) return rc;
-    gs_colour(c, level, c->kp, c->kv, colour, c->npairs, nullptr);
+    gs_colour(c, level, c->kp, c->kv, colour, c->npairs, ALL_PAIRS);
     return d2h_bounced(c, x_host, c->kp, nbytes);
 }
 
@@ -3271,7 +3311,7 @@ int vof_debug_sweep(vof_ctx* c, int level, double* x_host, const double* b_host,
     VDISPATCH(c, {
         SmoothArgs<VT> a;
         a.reverse = reverse != 0;
-        sweep_level_t<VT>(c, level, from_zero ? (const VT*)nullptr : (const VT*)c->kp, (VT*)c->kt, (const VT*)c->kv, c->npairs, nullptr, a, io);
+        sweep_level_t<VT>(c, level, from_zero ? (const VT*)nullptr : (const VT*)c->kp, (VT*)c->kt, (const VT*)c->kv, c->npairs, ALL_PAIRS, a, io);
     });
     return io.failed ? -1 : dbg_down(c, x_host, c->kt, n);
 }
@@ -3288,7 +3328,7 @@ int vof_debug_smooth(vof_ctx* c, int level, double* x_host, const double* b_host
         SmoothArgs<VT> a;
         a.from_zero = from_zero != 0;
         a.reverse = reverse != 0;
-        smooth_level_t<VT>(c, level, (VT*)c->kp, (VT*)c->kt, (const VT*)c->kv, nu, c->npairs, nullptr, a, io);
+        smooth_level_t<VT>(c, level, (VT*)c->kp, (VT*)c->kt, (const VT*)c->kv, nu, c->npairs, ALL_PAIRS, a, io);
     });
     return io.failed ? -1 : dbg_down(c, x_host, c->kp, n);
 }
@@ -3305,7 +3345,7 @@ int vof_debug_restrict(vof_ctx* c, int level, const double* fine_host, double* c
     if (level + 1 >= (int)c->L.size()) { c->err = "no coarser level"; return -1; }
     Level& k = c->L[level + 1];
     if (int rc = dbg_up(c, c->kp, fine_host, nbytes / sizeof(double))) return rc;
-    VDISPATCH(c, restrict_level_t<VT>(c, level, (const VT*)c->kp, (VT*)c->kv, c->npairs, nullptr));
+    VDISPATCH(c, restrict_level_t<VT>(c, level, (const VT*)c->kp, (VT*)c->kv, c->npairs, ALL_PAIRS));
     return dbg_down(c, coarse_host, c->kv, (size_t)c->npairs * 3 * k.npts);
 }
 
@@ -3316,7 +3356,7 @@ int vof_debug_resrestrict_u(vof_ctx* c, int level, const double* x_new_host, con
     if (int rc = dbg_up(c, c->kp, x_new_host, nbytes / sizeof(double))) return rc;
     if (x_old_host)
         if (int rc = dbg_up(c, c->kt, x_old_host, nbytes / sizeof(double))) return rc;
-    VDISPATCH(c, resrestrict_u_t<VT>(c, level, (const VT*)c->kp, x_old_host ? (const VT*)c->kt : (const VT*)nullptr, (VT*)c->kv, c->npairs, nullptr));
+    VDISPATCH(c, resrestrict_u_t<VT>(c, level, (const VT*)c->kp, x_old_host ? (const VT*)c->kt : (const VT*)nullptr, (VT*)c->kv, c->npairs, ALL_PAIRS));
     return dbg_down(c, coarse_host, c->kv, (size_t)c->npairs * 3 * k.npts);
 }
 
@@ -3326,7 +3366,7 @@ int vof_debug_prolong_add(vof_ctx* c, int level, double* fine_host, const double
     Level& k = c->L[level + 1];
     if (int rc = dbg_up(c, c->kp, fine_host, nbytes / sizeof(double))) return rc;
     if (int rc = dbg_up(c, c->kv, coarse_host, (size_t)c->npairs * 3 * k.npts)) return rc;
-    VDISPATCH(c, prolong_add_level_t<VT>(c, level, (VT*)c->kp, (const VT*)c->kv, c->npairs, nullptr));
+    VDISPATCH(c, prolong_add_level_t<VT>(c, level, (VT*)c->kp, (const VT*)c->kv, c->npairs, ALL_PAIRS));
     return dbg_down(c, fine_host, c->kp, nbytes / sizeof(double));
 }
 
@@ -3396,7 +3436,7 @@ int vof_debug_vcycle(vof_ctx* c, const double* r_host, double* e_host) {
     if (int rc = dbg_up(c, c->kp, r_host, n)) return rc;
     c->h32 = handoff32_ok(c);   // the cycle as the BiCGStab loop's first iterations run it
     CycleIO io;
-    vcycle(c, &c->ky, c->kp, c->npairs, nullptr, io);
+    vcycle(c, &c->ky, c->kp, c->npairs, ALL_PAIRS, io);
     const int rc = io.failed ? -1 : dbg_down(c, e_host, c->ky, n);
     c->h32 = false;
     return rc;
@@ -3414,9 +3454,9 @@ int vof_debug_vcycle_apply(vof_ctx* c, const double* r_host, double* y_host, dou
     CycleIO io;
     io.trail = S0Trail{c->kv, c->krh, 1, c->partials};
     c->h32 = handoff32_ok(c);
-    vcycle(c, &c->ky, c->kp, np, nullptr, io);
+    vcycle(c, &c->ky, c->kp, np, ALL_PAIRS, io);
     if (io.failed) { c->h32 = false; return -1; }
-    int nb = io.trail_nblk ? io.trail_nblk : krylov_apply(c, c->ky, c->kv, np, nullptr, c->krh, 1);
+    int nb = io.trail_nblk ? io.trail_nblk : krylov_apply(c, c->ky, c->kv, np, ALL_PAIRS, c->krh, 1);
     if (fused) *fused = io.trail_nblk ? 1 : 0;
     if (!nb) { c->h32 = false; c->err = "the operator kernel did not fuse the dot products"; return -1; }
     const int rcd = dbg_down(c, y_host, c->ky, n);
@@ -3439,7 +3479,7 @@ int vof_debug_coarse_solve(vof_ctx* c, const double* r_host, double* e_host) {
     DBG_LEVEL(last)
     size_t n = nbytes / sizeof(double);
     if (int rc = dbg_up(c, c->kp, r_host, n)) return rc;
-    VDISPATCH(c, coarse_solve_t<VT>(c, (const VT*)c->kp, (VT*)c->kv, c->npairs, nullptr));
+    VDISPATCH(c, coarse_solve_t<VT>(c, (const VT*)c->kp, (VT*)c->kv, c->npairs, ALL_PAIRS));
     return dbg_down(c, e_host, c->kv, n);
 }
 

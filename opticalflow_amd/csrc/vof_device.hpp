@@ -39,6 +39,17 @@ struct PairParam {
     int out;     // index of the pair's slot in the output stacks
 };
 
+// The pairs a launch serves.  flags[pair] != 0: the pair is still being solved (nullptr: every pair is).  list: the slots of the
+// pairs that were active when the host last counted them, ascending; the grid dimension that runs over the pairs then holds one
+// entry per listed pair instead of one per slot of the batch (nullptr: one per slot).  A block takes its pair from the list and
+// still checks the flag: pairs are switched off on the device between two counts (k_scalar), and those blocks leave as before.
+struct ActiveSet {
+    const int* flags;
+    const int* list;
+    __device__ __forceinline__ int pair(int slot) const { return list ? list[slot] : slot; }
+    __device__ __forceinline__ bool on(int pair) const { return !flags || flags[pair]; }
+};
+
 __device__ __forceinline__ int fold(int t, int n) { return t < 0 ? 1 : (t >= n ? n - 2 : t); }
 
 // weight of fine point f in the prolongation column of coarse point c (1-D), nc = #coarse points.
@@ -439,9 +450,9 @@ __global__ __launch_bounds__(NT) void k_rhs(const double* __restrict__ frames, s
 __global__ __launch_bounds__(NT) void k_gs0(const double* __restrict__ frames, size_t frame_stride, int Nj, int ni,
                                             int nj, double alpha, double beta, int quirks, double* __restrict__ x,
                                             const double* __restrict__ b, int colour,
-                                            const int* __restrict__ active, const PairParam* __restrict__ pp) {
-    int pair = blockIdx.z;
-    if (active && !active[pair]) return;
+                                            const ActiveSet act, const PairParam* __restrict__ pp) {
+    int pair = act.pair(blockIdx.z);
+    if (!act.on(pair)) return;
     int q = 2 * (blockIdx.x * BX + threadIdx.x) + (colour & 1);
     int p = 2 * (blockIdx.y * BY + threadIdx.y) + (colour >> 1);
     if (p >= ni || q >= nj) return;
@@ -504,9 +515,9 @@ __device__ __forceinline__ void stencil_offdiag(const CoefSet<CT>& cs, size_t np
 template <typename CT, int MODE, typename VT>
 __global__ __launch_bounds__(NT) void k_apply(const typename CoefFmt<CT>::word_t* __restrict__ C, int ni, int nj,
                                               const VT* __restrict__ x, const VT* __restrict__ b, VT* __restrict__ y,
-                                              const int* __restrict__ active) {
-    int q = blockIdx.x * BX + threadIdx.x, p = blockIdx.y * BY + threadIdx.y, pair = blockIdx.z;
-    if (active && !active[pair]) return;
+                                              const ActiveSet act) {
+    int q = blockIdx.x * BX + threadIdx.x, p = blockIdx.y * BY + threadIdx.y, pair = act.pair(blockIdx.z);
+    if (!act.on(pair)) return;
     if (p >= ni || q >= nj) return;
     size_t npts = (size_t)ni * nj, idx = (size_t)p * nj + q, off = (size_t)pair * 3 * npts;
     const CLay L(ni, nj);
@@ -537,9 +548,9 @@ __device__ __forceinline__ void solve3(const double* D, double r0, double r1, do
 template <typename CT>
 __global__ __launch_bounds__(NT) void k_gs(const typename CoefFmt<CT>::word_t* __restrict__ C, int ni, int nj,
                                            double* __restrict__ x, const double* __restrict__ b, int colour,
-                                           const int* __restrict__ active) {
-    int pair = blockIdx.z;
-    if (active && !active[pair]) return;
+                                           const ActiveSet act) {
+    int pair = act.pair(blockIdx.z);
+    if (!act.on(pair)) return;
     int q = 2 * (blockIdx.x * BX + threadIdx.x) + (colour & 1);
     int p = 2 * (blockIdx.y * BY + threadIdx.y) + (colour >> 1);
     if (p >= ni || q >= nj) return;
@@ -565,9 +576,9 @@ __global__ __launch_bounds__(NT) void k_gs(const typename CoefFmt<CT>::word_t* _
 template <typename VT>
 __global__ __launch_bounds__(NT) void k_restrict(const VT* __restrict__ fine, int nfi, int nfj,
                                                  VT* __restrict__ coarse, int nci, int ncj,
-                                                 const int* __restrict__ active) {
-    int cq = blockIdx.x * BX + threadIdx.x, cp = blockIdx.y * BY + threadIdx.y, pair = blockIdx.z;
-    if (active && !active[pair]) return;
+                                                 const ActiveSet act) {
+    int cq = blockIdx.x * BX + threadIdx.x, cp = blockIdx.y * BY + threadIdx.y, pair = act.pair(blockIdx.z);
+    if (!act.on(pair)) return;
     if (cp >= nci || cq >= ncj) return;
     size_t nf = (size_t)nfi * nfj, nc = (size_t)nci * ncj;
     const VT* f = fine + (size_t)pair * 3 * nf;
@@ -598,9 +609,9 @@ __global__ __launch_bounds__(NT) void k_restrict(const VT* __restrict__ fine, in
 template <typename VT>
 __global__ __launch_bounds__(NT) void k_prolong_add(VT* __restrict__ fine, int nfi, int nfj,
                                                     const VT* __restrict__ coarse, int nci, int ncj,
-                                                    const int* __restrict__ active) {
-    int fq = blockIdx.x * BX + threadIdx.x, fp = blockIdx.y * BY + threadIdx.y, pair = blockIdx.z;
-    if (active && !active[pair]) return;
+                                                    const ActiveSet act) {
+    int fq = blockIdx.x * BX + threadIdx.x, fp = blockIdx.y * BY + threadIdx.y, pair = act.pair(blockIdx.z);
+    if (!act.on(pair)) return;
     if (fp >= nfi || fq >= nfj) return;
     size_t nf = (size_t)nfi * nfj, nc = (size_t)nci * ncj;
     const VT* c = coarse + (size_t)pair * 3 * nc;
@@ -702,10 +713,10 @@ template <typename CT, typename VT, bool HAS_OLD> struct ResuBudget {
 template <typename CT, typename VT, bool HAS_OLD>
 __global__ __launch_bounds__(NT, (ResuBudget<CT, VT, HAS_OLD>::kMinWaves)) void k_resrestrict_u(const typename CoefFmt<CT>::word_t* __restrict__ C, int ni, int nj,
                                                       const VT* __restrict__ x_new, const VT* __restrict__ x_old,
-                                                      VT* __restrict__ bc, int nci, int ncj, const int* __restrict__ active) {
+                                                      VT* __restrict__ bc, int nci, int ncj, const ActiveSet act) {
     typedef typename CoefFmt<CT>::word_t word_t;
-    const int pair = blockIdx.z;
-    if (active && !active[pair]) return;
+    const int pair = act.pair(blockIdx.z);
+    if (!act.on(pair)) return;
     const int cp = blockIdx.y * BY + __builtin_amdgcn_readfirstlane(threadIdx.y);     // one wave per coarse row (wave-uniform)
     if (cp >= nci) return;
     const int lane = threadIdx.x;
@@ -1096,9 +1107,9 @@ __global__ __launch_bounds__(1024) void k_coarse_invert(double* __restrict__ W, 
 
 template <typename VT>
 __global__ void k_coarse_solve(const double* __restrict__ invT, int nd, const VT* __restrict__ r,
-                               VT* __restrict__ e, const int* __restrict__ active) {
-    int pair = blockIdx.x;
-    if (active && !active[pair]) return;
+                               VT* __restrict__ e, const ActiveSet act) {
+    int pair = act.pair(blockIdx.x);
+    if (!act.on(pair)) return;
     extern __shared__ double s_r[];
     for (int j = threadIdx.x; j < nd; j += blockDim.x) s_r[j] = (double)r[(size_t)pair * nd + j];
     __syncthreads();
@@ -1149,9 +1160,9 @@ __device__ __forceinline__ void block_store_partials(double v0, double v1, doubl
 __global__ __launch_bounds__(RBLK) void k_dot2(const double* __restrict__ a1, const double* __restrict__ b1,
                                                const double* __restrict__ a2, const double* __restrict__ b2,
                                                size_t len, double* __restrict__ partials,
-                                               const int* __restrict__ active) {
-    int pair = blockIdx.y;
-    if (active && !active[pair]) return;
+                                               const ActiveSet act) {
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     size_t off = (size_t)pair * len;
     double s0 = 0, s1 = 0;
     for (size_t i = (size_t)blockIdx.x * RBLK + threadIdx.x; i < len; i += (size_t)gridDim.x * RBLK) {
@@ -1270,12 +1281,12 @@ template <typename VT>
 __global__ __launch_bounds__(RBLK) void k_update_p(double* p, const double* p_old, const double* __restrict__ r,
                                                    const double* __restrict__ v, size_t len,
                                                    const PairScalars* __restrict__ sc,
-                                                   const int* __restrict__ active, VT* __restrict__ pcopy, int first) {
+                                                   const ActiveSet act, VT* __restrict__ pcopy, int first) {
     // first: the iteration that follows a (re)start, p = r (p and v are neither read nor need to be initialised).
     // p_old: the previous search direction - p itself, or r^ = r0 in the second iteration when the first one ran the cycle
     // straight on r (the solver then never wrote p = r0)
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     double beta = sc[pair].beta, omega = sc[pair].omega;
     size_t off = (size_t)pair * len;
     if ((len & 1) == 0) {
@@ -1310,9 +1321,9 @@ __global__ __launch_bounds__(RBLK) void k_update_p(double* p, const double* p_ol
 template <typename VT>
 __global__ __launch_bounds__(RBLK) void k_update_s(double* __restrict__ r, const double* __restrict__ v, size_t len,
                                                    const PairScalars* __restrict__ sc, double* __restrict__ partials,
-                                                   const int* __restrict__ active, VT* __restrict__ scopy) {
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+                                                   const ActiveSet act, VT* __restrict__ scopy) {
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     double alpha = sc[pair].alpha;
     size_t off = (size_t)pair * len;
     double ss = 0;
@@ -1346,9 +1357,9 @@ __global__ __launch_bounds__(RBLK) void k_update_xr(double* __restrict__ x, cons
                                                     const VT* __restrict__ z, double* __restrict__ r,
                                                     const double* __restrict__ t, const double* __restrict__ rh,
                                                     size_t len, const PairScalars* __restrict__ sc,
-                                                    double* __restrict__ partials, const int* __restrict__ active) {
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+                                                    double* __restrict__ partials, const ActiveSet act) {
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     double alpha = sc[pair].alpha, omega = sc[pair].omega;
     size_t off = (size_t)pair * len;
     double rr = 0, rho = 0;
@@ -1556,9 +1567,9 @@ __global__ void k_gm_init(GmresState* __restrict__ st, PairScalars* __restrict__
 
 // dst = src * state.scale
 __global__ __launch_bounds__(RBLK) void k_gm_scale(double* __restrict__ dst, const double* __restrict__ src, size_t len,
-                                                   const GmresState* __restrict__ st, const int* __restrict__ active) {
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+                                                   const GmresState* __restrict__ st, const ActiveSet act) {
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     const double f = st[pair].scale;
     size_t off = (size_t)pair * len;
     for (size_t i = (size_t)blockIdx.x * RBLK + threadIdx.x; i < len; i += (size_t)gridDim.x * RBLK) dst[off + i] = src[off + i] * f;
@@ -1567,9 +1578,9 @@ __global__ __launch_bounds__(RBLK) void k_gm_scale(double* __restrict__ dst, con
 // partials[pair][k][blk] = (V_k, w) for k < cnt, slot GM_NV = (w, w); V_k = V + k * vstride
 __global__ __launch_bounds__(RBLK) void k_gm_multidot(const double* __restrict__ V, size_t vstride, int cnt,
                                                       const double* __restrict__ w, size_t len,
-                                                      double* __restrict__ partials, const int* __restrict__ active) {
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+                                                      double* __restrict__ partials, const ActiveSet act) {
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     const double* wp = w + (size_t)pair * len;
     const double* vp = V + (size_t)pair * len;
     double acc[GM_NV + 1];
@@ -1617,10 +1628,10 @@ __global__ void k_gm_hcoef(GmresState* __restrict__ st, const double* __restrict
 __global__ __launch_bounds__(RBLK) void k_gm_axpy(const double* __restrict__ V, size_t vstride, int i0, int cnt,
                                                   const GmresState* __restrict__ st, int coef_offset, double sign,
                                                   const double* w_in, double* w_out, size_t len,
-                                                  const int* __restrict__ active, int limit_by_k,
+                                                  const ActiveSet act, int limit_by_k,
                                                   double* __restrict__ norm_partials) {
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     const double* coef = reinterpret_cast<const double*>(st + pair) + coef_offset + i0;
     int n = cnt;
     if (limit_by_k) n = min(cnt, st[pair].k - i0);
@@ -1732,9 +1743,9 @@ __global__ void k_bicg_restart(PairScalars* __restrict__ sc, int* __restrict__ a
 // r = r^ = t (the independent residual), p = v = 0 for the restarted pairs
 __global__ __launch_bounds__(RBLK) void k_restart_vectors(double* __restrict__ r, double* __restrict__ rh,
                                                           const double* __restrict__ t, size_t len,
-                                                          const int* __restrict__ active) {
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+                                                          const ActiveSet act) {
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     size_t off = (size_t)pair * len;
     for (size_t i = (size_t)blockIdx.x * RBLK + threadIdx.x; i < len; i += (size_t)gridDim.x * RBLK) {
         const double a = t[off + i];
@@ -1744,9 +1755,9 @@ __global__ __launch_bounds__(RBLK) void k_restart_vectors(double* __restrict__ r
 
 // x += z (z V-cycle output, float64)
 __global__ __launch_bounds__(RBLK) void k_gm_xpy(double* __restrict__ x, const double* __restrict__ z, size_t len,
-                                                 const int* __restrict__ active) {
-    int pair = blockIdx.y;
-    if (!active[pair]) return;
+                                                 const ActiveSet act) {
+    int pair = act.pair(blockIdx.y);
+    if (!act.on(pair)) return;
     size_t off = (size_t)pair * len;
     for (size_t i = (size_t)blockIdx.x * RBLK + threadIdx.x; i < len; i += (size_t)gridDim.x * RBLK) x[off + i] += z[off + i];
 }
@@ -1925,7 +1936,7 @@ __device__ __forceinline__ SweepRows sweep_rows(const SweepGeom& g, int rr, int 
 template <class Pol, class G, typename VT>
 __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, int ni, int nj, int TI, int po, int nx, int ny, int nz,
                                                const VT* __restrict__ x_in, VT* __restrict__ x_out,
-                                               const VT* __restrict__ b, const int* __restrict__ active,
+                                               const VT* __restrict__ b, const ActiveSet act,
                                                const VT* __restrict__ ecoarse, int nci, int ncj) {
     // (ecoarse, nci, ncj are not read: on these levels the correction is added by k_prolong_add before the sweep)
     constexpr int W = G::W, OUT = G::OUT, THREADS = G::THREADS;
@@ -1935,8 +1946,8 @@ __global__ __launch_bounds__(G::THREADS, Pol::kMinWaves) void k_sweep(Pol pol, i
     unsigned lb = blockIdx.x;
     if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // bijective when nblocks % 8 == 0
     const int bx = lb % nx, by = (lb / nx) % ny;
-    const int pair = lb / (nx * ny);
-    if (active && !active[pair]) return;
+    const int pair = act.pair(lb / (nx * ny));
+    if (!act.on(pair)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: keeps the stage's row arithmetic scalar
     SweepGeom g;
@@ -2119,7 +2130,7 @@ template <typename CT, typename VT, typename OT = VT, bool EC = false>
 __global__ __launch_bounds__(GeoB::THREADS, SweepStBudget<CT>::kMinWaves) void k_sweep_st(const typename CoefFmt<CT>::word_t* __restrict__ C, int ni, int nj, int TI,
                                                                int po, int nx, int ny, int nz, const VT* __restrict__ x_in,
                                                                OT* __restrict__ x_out, const VT* __restrict__ b,
-                                                               const int* __restrict__ active, const VT* __restrict__ ecoarse, int nci,
+                                                               const ActiveSet act, const VT* __restrict__ ecoarse, int nci,
                                                                int ncj, int skip0) {
     // skip0: x_in comes straight from a sweep in REVERSE colour order with the same b (the post-smoothing of the previous
     // visit of a W-cycle): colour 0 was updated last there and none of its neighbours has changed since - updating it again
@@ -2135,8 +2146,8 @@ __global__ __launch_bounds__(GeoB::THREADS, SweepStBudget<CT>::kMinWaves) void k
     unsigned lb = blockIdx.x;
     if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
     const int bx = lb % nx, by = (lb / nx) % ny;
-    const int pair = lb / (nx * ny);
-    if (active && !active[pair]) return;
+    const int pair = act.pair(lb / (nx * ny));
+    if (!act.on(pair)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int p0 = by * TI - po;
@@ -2503,7 +2514,7 @@ __host__ __device__ constexpr int s0_row_bytes(int vt_bytes) { return 3 * S0_W *
 template <typename VT, bool EC, bool FROM_ZERO>
 __global__ __launch_bounds__(S0_THREADS) void k_sweep0(Fine0 pol, int ni, int nj, int TI, int po, int nx, int ny, int nz,
                                                        const VT* __restrict__ x_in, VT* __restrict__ x_out,
-                                                       const VT* __restrict__ b, const int* __restrict__ active,
+                                                       const VT* __restrict__ b, const ActiveSet act,
                                                        const VT* __restrict__ ecoarse, int nci, int ncj) {
     constexpr int W = S0_W, IW = S0_IW, OUT = S0_OUT;
     constexpr int VB = (int)sizeof(VT);
@@ -2519,8 +2530,8 @@ __global__ __launch_bounds__(S0_THREADS) void k_sweep0(Fine0 pol, int ni, int nj
     unsigned lb = blockIdx.x;
     if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
     const int bx = lb % nx, by = (lb / nx) % ny;
-    const int pair = lb / (nx * ny);
-    if (active && !active[pair]) return;
+    const int pair = act.pair(lb / (nx * ny));
+    if (!act.on(pair)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int p0 = by * TI - po;                 // true row of relative row 0
@@ -2852,7 +2863,7 @@ struct S0BSrc {
 template <int NS, bool EC, bool FROM_ZERO, int TRAIL = 0, typename ET = double>
 __global__ __launch_bounds__(128 * NS) void k_sweep0m(
     Fine0 pol, int ni, int nj, int TI, int po, int nx, int ny, int nz, const double* __restrict__ x_in,
-    double* __restrict__ x_out, const double* __restrict__ b, const int* __restrict__ active,
+    double* __restrict__ x_out, const double* __restrict__ b, const ActiveSet act,
     const ET* __restrict__ ecoarse, int nci, int ncj, S0Trail tr) {
     typedef S0M<NS, TRAIL> G;
     constexpr int W = S0_W, IW = S0_IW, NW = G::NW, R = G::R, RSB = G::RSB, RINGB = R * RSB, CRW = G::CRW;
@@ -2865,8 +2876,8 @@ __global__ __launch_bounds__(128 * NS) void k_sweep0m(
     unsigned lb = blockIdx.x;
     if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
     const int bx = lb % nx, by = (lb / nx) % ny;
-    const int pair = lb / (nx * ny);
-    if (active && !active[pair]) return;
+    const int pair = act.pair(lb / (nx * ny));
+    if (!act.on(pair)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p0 = by * TI - po;                 // true row of relative row 0 (reverse order: rows shifted by one)
@@ -3368,11 +3379,11 @@ __device__ __forceinline__ void tail_colour(const TailLevel& lv, const CoefSet<C
 
 template <typename CT, typename VT>
 __global__ __launch_bounds__(TAIL_THREADS) void k_tail_cycle(TailArgs A, const VT* __restrict__ b_top, VT* __restrict__ x_top,
-                                                             int from_zero, const int* __restrict__ active) {
+                                                             int from_zero, const ActiveSet act) {
     extern __shared__ double tl_lds[];
     double* lds = tl_lds;
-    const int pair = blockIdx.x;
-    if (active && !active[pair]) return;
+    const int pair = act.pair(blockIdx.x);
+    if (!act.on(pair)) return;
     const int tid = threadIdx.x;
     // ---- load: b of the top tail level, x (or zeros), zero halos of every level
     {

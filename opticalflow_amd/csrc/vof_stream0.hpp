@@ -25,7 +25,7 @@ static_assert(AP_THREADS == RBLK, "block_store_partials sums the waves of an RBL
 // (ni x nj interior points of an image with Nj columns), the band height, the model parameters and the per-pair tables.
 struct ApArgs {
     const double* frames; size_t frame_stride; int Nj, ni, nj, TI; double alpha, beta; int quirks;
-    const int* active; const PairParam* pp;
+    ActiveSet act; const PairParam* pp;
 };
 
 // ------------------------------------------------------------------------------------------ the ring
@@ -165,8 +165,8 @@ __global__ __launch_bounds__(AP_THREADS) __attribute__((amdgpu_waves_per_eu(MODE
     const int wyy = MODE == 3 ? 1 : want_yy;
     YT* const yo = MODE == 3 ? nullptr : y;
     YT* const yc = MODE == 3 ? nullptr : ycopy;
-    const int pair = blockIdx.z;
-    if (a.active && !a.active[pair]) return;
+    const int pair = a.act.pair(blockIdx.z);
+    if (!a.act.on(pair)) return;
     const size_t frame_stride = a.frame_stride;
     const int Nj = a.Nj, ni = a.ni, nj = a.nj, TI = a.TI, quirks = a.quirks;
     double alpha = a.alpha, beta = a.beta;
@@ -344,8 +344,8 @@ __global__ __launch_bounds__(AP_THREADS) void k_stream_resrestrict0(ApArgs a, co
     __shared__ XT xs[AP_RING * 3 * AP_W];
     __shared__ double im[AP_RING * AP_W];
     __shared__ double rs[AP_RING * 3 * 128];     // residual ring [row][field][fine column of the strip]
-    const int pair = blockIdx.z;
-    if (a.active && !a.active[pair]) return;
+    const int pair = a.act.pair(blockIdx.z);
+    if (!a.act.on(pair)) return;
     const int Nj = a.Nj, ni = a.ni, nj = a.nj, TI = a.TI;
     double alpha = a.alpha, beta = a.beta;
     int fidx = pair;

@@ -84,7 +84,7 @@ struct S0PRow { f2 ux, uy, wx, wy, gx, gy; };   // one x row of the two strips: 
 template <int NS, bool EC, bool FROM_ZERO, int PO>
 __global__ __launch_bounds__(64) void k_sweep0p(
     Fine0 pol, int ni, int nj, int TI, int nx, int nxp, int ny, int nz, const float* __restrict__ x_in,
-    float* __restrict__ x_out, const float* __restrict__ b, const int* __restrict__ active,
+    float* __restrict__ x_out, const float* __restrict__ b, const ActiveSet act,
     const float* __restrict__ ecoarse, int nci, int ncj) {
     typedef S0R<NS, 0> G;
     constexpr int W = S0_W, LO = G::LO, NRW = G::NRW, NRI = G::NRI, IRB = G::IRB, IHB = G::IPW * 8;
@@ -95,8 +95,8 @@ __global__ __launch_bounds__(64) void k_sweep0p(
     unsigned lb = blockIdx.x;
     if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
     const int bxp = lb % nxp, by = (lb / nxp) % ny;
-    const int pair = lb / (nxp * ny);
-    if (active && !active[pair]) return;
+    const int pair = act.pair(lb / (nxp * ny));
+    if (!act.on(pair)) return;
     const int lane = threadIdx.x;
     const int p0 = by * TI - po;
     const int qsA = (2 * bxp) * G::OUT - G::HALO, qsB = qsA + G::OUT;

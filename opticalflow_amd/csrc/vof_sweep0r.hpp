@@ -114,7 +114,7 @@ __device__ __forceinline__ S0RRow round_row32(const S0RRow& s) {
 template <int NS, bool EC, bool FROM_ZERO, int TRAIL, typename ET, int PO, int QK = 1, int BF = 0, typename XT = double>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO && (BF == 0 || BF == 3) && TRAIL != 2) ? VOF_S0R_FZ_WAVES : 1, (FROM_ZERO && (BF == 0 || BF == 3) && TRAIL != 2) ? VOF_S0R_FZ_WAVES : 1))) void k_sweep0r(
     Fine0 pol, int ni, int nj, int TI, int /*po*/, int nx, int ny, int nz, const XT* __restrict__ x_in,
-    XT* __restrict__ x_out, const double* __restrict__ b, const int* __restrict__ active,
+    XT* __restrict__ x_out, const double* __restrict__ b, const ActiveSet act,
     const ET* __restrict__ ecoarse, int nci, int ncj, S0Trail tr, int skip_first = 0, int skip_count = 0,
     S0BSrc bsrc = S0BSrc{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) {
     static_assert(BF == 0 || NS == 2, "b is handed from the first sweep's stages to the second's");
@@ -144,8 +144,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
     if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
     const int bxl = lb % nx, by = (lb / nx) % ny;
     const int bx = bxl < skip_first ? bxl : bxl + skip_count;
-    const int pair = lb / (nx * ny);
-    if (active && !active[pair]) return;
+    const int pair = act.pair(lb / (nx * ny));
+    if (!act.on(pair)) return;
     const int lane = threadIdx.x;
     const int p0 = by * TI - po;                 // true row of relative row 0 (reverse order: rows shifted by one)
     const int qs = bx * G::OUT - G::HALO;        // true column of local column 0 (even: 16-byte aligned pairs)

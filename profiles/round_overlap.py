@@ -3,7 +3,7 @@
 iteration of a batch: two multigrid cycles plus the vector kernels) at its k_update_xr launches, and how much of the
 under-filled rounds another queue's dense rounds cover (profiles/r06_lane_groups_summary.md).
 
-    python profiles/round_overlap.py <kernel_trace.csv> [--steps N] [--straggler 0.10] [--quiet]
+    python profiles/round_overlap.py <kernel_trace.csv> [--steps N] [--straggler 0.10] [--quiet] [--launches]
 
 A round is the kernels of a queue after one k_update_xr up to and including the next (the first round of a batch also
 holds the hierarchy set-up and the epilogue of the batch before it; what follows a queue's last k_update_xr is listed as
@@ -12,27 +12,31 @@ queue's longest is a proxy for the share of pairs the round serves.  A round bel
 round.  Its wall span counts as covered where a round that is not a straggler is under way on another queue.
 
 Only the solver's kernels (vof::) count, without the synthetic stack's generator (k_texture_*).  --steps divides the
-per-step totals (a bench run with --warmup 1 --steps 1 holds two steps).
+per-step totals (a bench run with --warmup 1 --steps 1 holds two steps).  --launches adds the launches of the straggler rounds
+per (kernel, grid in threads): count and minimum / median / maximum duration (profiles/r16_active_list_summary.md).
 """
 import argparse
 import csv
+import re
+import statistics
 from collections import defaultdict
 
 
 def rounds_of(kernels):
     """kernels: (start, end, name) sorted by start.  -> list of dicts, one per round."""
     out, cur = [], []
-    for s, e, name in kernels:
-        cur.append((s, e))
+    for k in kernels:
+        s, e, name = k[:3]
+        cur.append(k)
         if "k_update_xr" in name:
             out.append({"iv": cur, "upd": e - s})
             cur = []
     if cur:
         out.append({"iv": cur, "upd": None})
     for r in out:
-        r["start"] = min(s for s, _ in r["iv"])
-        r["end"] = max(e for _, e in r["iv"])
-        r["sum"] = sum(e - s for s, e in r["iv"])
+        r["start"] = min(k[0] for k in r["iv"])
+        r["end"] = max(k[1] for k in r["iv"])
+        r["sum"] = sum(k[1] - k[0] for k in r["iv"])
     return out
 
 
@@ -56,6 +60,7 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--straggler", type=float, default=0.10)
     ap.add_argument("--quiet", action="store_true", help="totals only, no per-round table")
+    ap.add_argument("--launches", action="store_true", help="the straggler rounds' launches per (kernel, grid)")
     a = ap.parse_args()
     per_queue = defaultdict(list)
     with open(a.trace) as f:
@@ -63,7 +68,8 @@ def main():
             name = r["Kernel_Name"]
             if "vof::" not in name or "k_texture" in name:
                 continue
-            per_queue[r.get("Queue_Id", "?")].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name))
+            grid = "x".join(r.get("Grid_Size_" + d, "?") for d in "XYZ")
+            per_queue[r.get("Queue_Id", "?")].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name, grid))
     t0 = min(k[0] for ks in per_queue.values() for k in ks)
     rounds = {}
     for q, ks in per_queue.items():
@@ -94,7 +100,7 @@ def main():
                 tail = f"yes | {cov / 1e6:.2f}" if r["straggler"] else " | "
                 print(f"| {q} | {i} | {(r['start'] - t0) / 1e6:.1f} | {span / 1e6:.2f} | {r['sum'] / 1e6:.2f} | {len(r['iv'])} | {upd} | {share} | {tail} |")
     k = a.steps
-    all_iv = [(s, e) for ks in per_queue.values() for s, e, _ in ks]
+    all_iv = [(x[0], x[1]) for ks in per_queue.values() for x in ks]
     span_all = max(e for _, e in all_iv) - min(s for s, _ in all_iv)
     print(f"\n| per step ({k} steps in the trace) | |\n|---|---:|")
     print(f"| queues with solver kernels | {len(rounds)} |")
@@ -105,6 +111,17 @@ def main():
     print(f"| of the wall span: covered by a dense round of another queue, ms | {tot_cov / 1e6 / k:.2f} |")
     print(f"| of the wall span: not covered, ms | {(tot_span - tot_cov) / 1e6 / k:.2f} |")
     print(f"| first to last solver kernel, ms (all steps, with the gaps between them) | {span_all / 1e6:.1f} |")
+    if a.launches:
+        by = defaultdict(list)
+        for rs in rounds.values():
+            for r in rs:
+                if r["straggler"]:
+                    for s, e, name, grid in r["iv"]:
+                        by[(re.sub(r"\(.*", "", name).replace("void ", "").replace("vof::", "").strip()[:70], grid)].append(e - s)
+        print("\n| kernel (straggler rounds) | grid (threads) | launches | total ms | min us | median us | max us |")
+        print("|---|---|---:|---:|---:|---:|---:|")
+        for (name, grid), d in sorted(by.items(), key=lambda kv: -sum(kv[1])):
+            print(f"| `{name}` | {grid} | {len(d)} | {sum(d) / 1e6:.3f} | {min(d) / 1e3:.1f} | {statistics.median(d) / 1e3:.1f} | {max(d) / 1e3:.1f} |")
 
 
 if __name__ == "__main__":
