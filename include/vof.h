@@ -126,6 +126,9 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *   VOF_ACTIVE_LIST=0          every launch of a Krylov round covers all pair slots of the batch, and the blocks of finished pairs
  *                              read their flag and leave (default: after each count of the active pairs the launches take the
  *                              list of their slots and cover those alone; same bits, tests/test_gpu_active_list.py)
+ *   VOF_FUSE_REVISIT=0         W-cycle: between two visits of the revisited stored level, the post-smoothing sweep of one visit and the
+ *                              pre-smoothing sweep of the next as two launches (default: one pass over the level, k_sweep_st2; same bits,
+ *                              tests/test_gpu_revisit_fusion.py)
  *   VOF_FOLD_STORED=1          stored levels: coarse-grid correction interpolated inside the first post-sweep
  *   VOF_TRACE=1                direct preconditioner: progress lines on stderr
  * Read at every vof_solve_stack_dev call (speed only; per pair the same arithmetic, partial sums may add in another order):

@@ -147,6 +147,8 @@ struct vof_ctx {
     bool fold_stored = false;   // stored levels, packed stencils (k_sweep_st): the coarse-grid correction interpolated inside the first
                                 // post-sweep (VOF_FOLD_STORED=1; measured: the sweep gets slower by what the stand-alone prolongation
                                 // kernel costs, so that one stays)
+    bool fuse_revisit = true;   // VOF_FUSE_REVISIT=0: between two visits of the W-cycle's revisited level, the post-smoothing sweep of one
+                                // visit and the pre-smoothing sweep of the next as two k_sweep_st launches instead of one k_sweep_st2 pass
     // direct preconditioner (block-tridiagonal LU by image rows, vof_direct.hpp); buffers allocated on first use
     bool direct_on = false;          // the batch in solve_batch is preconditioned by the direct solver instead of the multigrid cycle
                                      // (BatchReq::direct; written by solve_batch alone)
@@ -677,6 +679,18 @@ inline bool sweep_st_usable(const vof_ctx* c, int l) {
     return l > 0 && c->L[l].C != nullptr && c->cfmt >= 2;
 }
 
+// k_sweep_st2: the post-smoothing of one visit of level l and the pre-smoothing of the next in one pass.  A regular stored level
+// (packed stencils, neither the coarsest level nor the top of the coarse tail) that smooths once before and once after its
+// coarse-grid correction.  (With VOF_FOLD_STORED the first post-sweep interpolates the correction, which k_sweep_st2 does not.)
+bool tail_prepare(vof_ctx* c);
+inline bool revisit_fusable(vof_ctx* c, int l) {
+    if (!c->fused || !c->fuse_revisit || c->fold_stored || !sweep_st_usable(c, l) || l >= (int)c->L.size() - 1) return false;
+    if (l == c->tail_first && tail_prepare(c)) return false;
+    const int nu1 = c->prm.nu_pre_coarse > 0 ? c->prm.nu_pre_coarse : c->prm.nu_pre;
+    const int nu2 = c->prm.nu_post_coarse > 0 ? c->prm.nu_post_coarse : c->prm.nu_post;
+    return nu1 == 1 && nu2 == 1;
+}
+
 // vcycle_precision 3 applies when level 0 runs the kernels in which the two storage types meet: the residual + restriction
 // (float64 in, float32 out) and the k_sweep0m / k_sweep0r pass with the interpolated correction (float32 in); anything else
 // keeps float64 everywhere
@@ -1075,6 +1089,25 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, in
     });
 }
 
+// Stored level l between two visits (revisit_fusable): a reverse sweep x_in -> x_mid and a forward sweep x_mid -> x_out, which
+// leaves colour 0 alone, in one pass (k_sweep_st2).  The bands are those of the forward sweep.
+template <typename VT>
+void sweep2_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_mid, VT* x_out, const VT* b, int np, ActiveSet active) {
+    Level& lv = c->L[l];
+    const int nx = (lv.nj + GeoR::OUT - 1) / GeoR::OUT;
+    const int TI = pick_band_height(lv.ni, nx, c->cur_units);
+    const int ny = (lv.ni + TI - 1) / TI;
+    const int nslots = pair_slots(c, active, np);
+    dim3 g((unsigned)nx * ny * nslots, 1, 1);
+    const double vs = sizeof(VT);
+    // algorithmic: the two sweeps as sweep_level_t counts them; moved: C once + b(3) + x(3) in, x(6) out
+    Prof p(c, VOF_K_GS, l, 2.0 * (coef_bytes(c, l) + 9.0 * vs) * lv.npts, (coef_bytes(c, l) + 12.0 * vs) * lv.npts);
+    const size_t lds = (size_t)(GeoR::RING * 3 * GeoR::W) * sizeof(VT);
+    const uint32_t* Cw = (const uint32_t*)lv.C;
+    if (c->cfmt == 3) k_sweep_st2<CoefF8, VT><<<g, GeoR::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, nx, ny, nslots, x_in, x_mid, x_out, b, active);
+    else k_sweep_st2<CoefB16, VT><<<g, GeoR::THREADS, lds, c->stream>>>(Cw, lv.ni, lv.nj, TI, nx, ny, nslots, x_in, x_mid, x_out, b, active);
+}
+
 // nu sweeps (from a zero guess if a.from_zero, else from x); the result is guaranteed to end in `x`, or - with a.allow_swap - in
 // the buffer returned: `x`, or `tmp` when the last out-of-place sweep ended there (saves a device-to-device copy on the coarse levels).
 // a.ecoarse: on the matrix-free level 0 it is folded into the first sweep (coarse rows streamed through LDS); otherwise the
@@ -1181,8 +1214,11 @@ void tail_cycle_t(vof_ctx* c, VT* x, const VT* b, int np, ActiveSet active, bool
 template <typename VT>
 // after_post: x holds the result of a previous visit of this level with the same b, i.e. of its reverse post-smoothing sweep
 // emit64 (level 1 under a float64 level 0, vcycle_precision 3): the last post-smoothing sweep writes the result as float64
+// defer_post (revisit_fusable(c, l), another visit follows): the visit ends with x + P e and leaves its post-smoothing sweep to the
+// next visit, which is told so by post_pending and performs it together with its own pre-smoothing sweep (k_sweep_st2).  That
+// pass writes two vectors, so the level's third buffer (r) joins the ping-pong pair; the caller only reads what is returned.
 VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, ActiveSet active, CycleIO& io, bool from_zero = true,
-             bool after_post = false, bool emit64 = false) {
+             bool after_post = false, bool emit64 = false, bool defer_post = false, bool post_pending = false) {
     int last = (int)c->L.size() - 1;
     if (l == last) { coarse_solve_t<VT>(c, b, x, np, active); return x; }
     if (l == c->tail_first && l > 0 && tail_prepare(c)) { tail_cycle_t<VT>(c, x, b, np, active, from_zero); return x; }
@@ -1204,7 +1240,13 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, ActiveSet a
         pre.allow_swap = true;
         pre.skip0 = after_post && !from_zero && nu2 >= 1;
     }
-    if (smooth_level_t<VT>(c, l, x, tmp, b, nu1, np, active, pre, io) != x) std::swap(x, tmp);
+    if (post_pending) {   // x -> tmp (the previous visit's result, x_old of k_resrestrict_u) -> the third buffer
+        VT* third = (VT*)lv.x;
+        if (third == x || third == tmp) third = (VT*)lv.x2;
+        if (third == x || third == tmp) third = (VT*)lv.r;
+        sweep2_level_t<VT>(c, l, x, tmp, third, b, np, active);
+        x = third;
+    } else if (smooth_level_t<VT>(c, l, x, tmp, b, nu1, np, active, pre, io) != x) std::swap(x, tmp);
     if (io.failed) return x;
     const bool rr_fused = l == 0 && io.rr_done;   // ... and it did (k_sweep0r, TRAIL = 2)
     if constexpr (std::is_same<VT, double>::value) {
@@ -1221,10 +1263,12 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, ActiveSet a
             const int nu2c = c->prm.nu_post_coarse > 0 ? c->prm.nu_post_coarse : c->prm.nu_post;
             const bool can64 = 1 < last && !(c->tail_first == 1 && tail_prepare(c)) && sweep_st_usable(c, 1) && nu2c > 0;
             const int visits = (c->prm.w_cycle_level == 0 && 1 < last) ? (c->prm.w_cycle_visits > 0 ? c->prm.w_cycle_visits : 2) : 1;
-            float* fe = vcycle_t<float>(c, 1, fx, ft, (const float*)nx.b, np, active, io, true, false, /*emit64=*/can64 && visits == 1);
+            const bool fr = visits > 1 && revisit_fusable(c, 1);
+            float* fe = vcycle_t<float>(c, 1, fx, ft, (const float*)nx.b, np, active, io, true, false, /*emit64=*/can64 && visits == 1, /*defer_post=*/fr);
             for (int v = 1; v < visits; ++v) {
                 float* other = (fe == fx) ? ft : fx;
-                fe = vcycle_t<float>(c, 1, fe, other, (const float*)nx.b, np, active, io, false, false, /*emit64=*/can64 && v == visits - 1);
+                fe = vcycle_t<float>(c, 1, fe, other, (const float*)nx.b, np, active, io, false, false, /*emit64=*/can64 && v == visits - 1,
+                                     /*defer_post=*/fr && v < visits - 1, /*post_pending=*/fr);
             }
             SmoothArgs<double> post;
             post.reverse = post.allow_swap = post.final_smooth = true;
@@ -1244,19 +1288,23 @@ VT* vcycle_t(vof_ctx* c, int l, VT* x, VT* tmp, const VT* b, int np, ActiveSet a
     }
     VT* cx = (VT*)nx.x;
     VT* ct = (VT*)nx.x2;
-    VT* ec = vcycle_t<VT>(c, l + 1, cx, ct, (const VT*)nx.b, np, active, io, true);
-    if (c->prm.w_cycle_level == l && l + 1 < last) {
-        const int visits = c->prm.w_cycle_visits > 0 ? c->prm.w_cycle_visits : 2;
-        for (int v = 1; v < visits; ++v) {
-            VT* other = (ec == cx) ? ct : cx;
-            ec = vcycle_t<VT>(c, l + 1, ec, other, (const VT*)nx.b, np, active, io, false, /*after_post=*/true);
-        }
+    const int visits = (c->prm.w_cycle_level == l && l + 1 < last) ? (c->prm.w_cycle_visits > 0 ? c->prm.w_cycle_visits : 2) : 1;
+    const bool fr = visits > 1 && revisit_fusable(c, l + 1);
+    VT* ec = vcycle_t<VT>(c, l + 1, cx, ct, (const VT*)nx.b, np, active, io, true, false, false, /*defer_post=*/fr);
+    for (int v = 1; v < visits; ++v) {
+        VT* other = (ec == cx) ? ct : cx;
+        ec = vcycle_t<VT>(c, l + 1, ec, other, (const VT*)nx.b, np, active, io, false, /*after_post=*/true, false,
+                          /*defer_post=*/fr && v < visits - 1, /*post_pending=*/fr);
     }
     SmoothArgs<VT> post;
     post.reverse = post.allow_swap = true;
     post.final_smooth = l == 0;
     post.ecoarse = ec;
     post.out64 = emit64 && l == 1 && std::is_same<VT, float>::value && nu2 > 0;
+    if (defer_post) {
+        prolong_add_level_t<VT>(c, l, x, ec, np, active);
+        return x;
+    }
     return smooth_level_t<VT>(c, l, x, tmp, b, nu2, np, active, post, io);
 }
 
@@ -2100,6 +2148,7 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
     if (c->dbg_sync)
         if (const char* e = getenv("VOF_DEBUG_SYNC_FILE")) c->dbg_fd = open(e, O_WRONLY | O_CREAT, 0644);
     if (const char* e = getenv("VOF_FOLD_STORED")) c->fold_stored = e[0] != '0';
+    if (const char* e = getenv("VOF_FUSE_REVISIT")) c->fuse_revisit = e[0] != '0';
     if (const char* e = getenv("VOF_L0_HANDOFF")) c->l0_handoff = e[0] != '0';
     if (const char* e = getenv("VOF_SWEEP0R_MIN_BLOCKS")) c->sweep0r_min_blocks = atol(e);
     if (const char* e = getenv("VOF_ACTIVE_LIST")) c->use_alist = e[0] != '0';
@@ -2182,6 +2231,11 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
         HIPCHK(hipFuncSetAttribute((const void*)k_sweep0m<2, false, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIPCHK(hipFuncSetAttribute((const void*)k_sweep0m<1, true, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIPCHK(hipFuncSetAttribute((const void*)k_sweep0m<1, false, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
+    {   // ... and so does the 22-row ring of the two-sweep pass of the stored levels with float64 vectors (74 KB; float32: 37 KB)
+        const int lds = GeoR::RING * 3 * GeoR::W * (int)sizeof(double);
+        HIPCHK(hipFuncSetAttribute((const void*)k_sweep_st2<CoefB16, double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute((const void*)k_sweep_st2<CoefF8, double>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     c->nblk = (int)std::min<size_t>(256, std::max<size_t>(1, (len0 + 4 * RBLK - 1) / (4 * RBLK)));
     {

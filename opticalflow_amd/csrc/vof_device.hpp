@@ -2487,6 +2487,275 @@ __global__ __launch_bounds__(GeoB::THREADS, SweepStBudget<CT>::kMinWaves) void k
     }
 }
 
+// ==========================================================================================
+// k_sweep_st2: TWO sweeps of a stored level in one march down the band - a sweep in reverse colour order (3,2,1,0) followed by a
+// forward sweep that leaves colour 0 alone (k_sweep_st's skip0) - for the revisits of a W-cycle, where the post-smoothing of
+// one visit and the pre-smoothing of the next run back to back with the same b.  x_mid receives the result of the reverse
+// sweep (the x_old of k_resrestrict_u), x_out the final one.  Same point update, same order per point, same bits as the two
+// k_sweep_st launches; the x rows are read once and the stencil words of a row are requested a second time 9 - 11 rows after
+// their first use, while they are still on the die.
+//  * Rows are counted in the frame of the reverse sweep: relative row 0 is the row ABOVE the forward band of TI rows, and
+//    the reverse sweep covers TI + 4 rows, so that its result is final on every row the forward sweep reads (relative rows
+//    0 .. TI + 2).  Seven stage waves: 0-3 the reverse sweep's colours on rows e, e-2, e-5, e-7 as in k_sweep_st; 4-6 the
+//    forward colours 1, 2, 3 on rows e-11, e-14, e-16.  Row e-9 of the reverse sweep is final after step e-2 and written
+//    to x_mid at the start of step e, so the first forward stage may touch it from step e+2 on; the later forward stages
+//    trail by the three / two rows the colour order asks for.  Rows e-20, e-19 leave the ring (22 rows) for x_out.
+//  * Columns: the forward sweep reads the reverse sweep's result two columns to the left and three to the right of the
+//    owned 128, so the reverse sweep owns those five columns too and its own halo triangle moves out by as much: 8 halo
+//    columns each side, and an eighth wave that updates the 21 halo points of a step (18 reverse, 3 forward).
+//  * Every stage wave keeps its two sets of off-diagonal words and requests b with the diagonal block, as in k_sweep_st.
+// ==========================================================================================
+struct GeoR {
+    static constexpr int OUT = 128, HALO = 8, W = 144, THREADS = 512, RING = 22;
+};
+template <typename CT, typename VT>
+__global__ __launch_bounds__(GeoR::THREADS, SweepStBudget<CT>::kMinWaves) void k_sweep_st2(const typename CoefFmt<CT>::word_t* __restrict__ C, int ni, int nj, int TI,
+                                                               int nx, int ny, int nz, const VT* __restrict__ x_in,
+                                                               VT* __restrict__ x_mid, VT* __restrict__ x_out,
+                                                               const VT* __restrict__ b, const ActiveSet act) {
+    typedef GeoR G;
+    typedef typename CoefFmt<CT>::word_t word_t;
+    constexpr int W = G::W, OUT = G::OUT, HALO = G::HALO, RING = G::RING, PLANES = CoefFmt<CT>::PLANES;
+    extern __shared__ double sw_lds[];
+    VT* xs = reinterpret_cast<VT*>(sw_lds);                                                     // [RING][3][W]
+    const unsigned nblocks = (unsigned)nx * ny * nz;
+    unsigned lb = blockIdx.x;
+    if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
+    const int bx = lb % nx, by = (lb / nx) % ny;
+    const int pair = act.pair(lb / (nx * ny));
+    if (!act.on(pair)) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int H = TI + 4;                 // rows of the reverse sweep
+    const int p0 = by * TI - 1;           // true row of relative row 0
+    const int qs = bx * OUT - HALO;
+    const size_t npts = (size_t)ni * nj, off = (size_t)pair * 3 * npts;
+    const VT* xin = x_in + off;
+    VT* xmid = x_mid + off;
+    VT* xout = x_out + off;
+    const VT* bp = b + off;
+    const CLay L(ni, nj);
+    const word_t* Cp = C + (size_t)pair * PLANES * L.plane;
+
+    // ---- stage of this lane.  Waves 0-6: stage = wave; wave 7 updates the halo points.  Stages 0-3 have the column parities
+    // of a sweep with po = 1, stages 4-6 those of the colours 1-3 of a sweep with po = 0: (stage & 1) ^ 1 in both cases.
+    int stage = wave, lc;
+    bool lane_on = true;
+    lc = HALO + 2 * lane + ((wave & 1) ^ 1);
+    if (wave == 7) {
+        constexpr int NH = 21;
+        const int hs[NH] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5};
+        const int hl[NH] = {3, 5, 7, HALO + OUT + 1, HALO + OUT + 3, HALO + OUT + 5, 4, 6, HALO + OUT, HALO + OUT + 2, HALO + OUT + 4,
+                            5, 7, HALO + OUT + 1, HALO + OUT + 3, 6, HALO + OUT, HALO + OUT + 2, 7, HALO + OUT + 1, HALO + OUT};
+        lane_on = lane < NH;
+        stage = hs[lane_on ? lane : 0];
+        lc = hl[lane_on ? lane : 0];
+    }
+    const int q = qs + lc;
+    const bool col_ok = lane_on && (q >= 0) && (q < nj);
+    const int qc = col_ok ? q : 0, lcc = col_ok ? lc : 2;
+    const int cC = sw_cs<G>(lcc), uL = sw_cs<G>(lcc - 1), uR = sw_cs<G>(lcc + 1);
+    const unsigned ccq = (unsigned)((size_t)(qc & 1) * L.sub + (size_t)(qc >> 1));   // column part of the stencil index
+    const unsigned bcol = (unsigned)qc;
+    // cooperative load-in / write-out of 2 rows x 3 fields x W columns per step; recomputed where used, see k_sweep_st
+    auto opaque_tid = [&]() { int t = tid; asm volatile("" : "+v"(t)); return t; };
+    struct XMap { int row, col, q, lds; unsigned g; bool on, ld, st; };
+    auto xmap = [&](const int t) {
+        XMap m;
+        m.row = t >= W ? 1 : 0; m.col = t - m.row * W;
+        m.on = t < 2 * W;
+        m.q = qs + m.col;
+        m.ld = m.on && m.q >= 0 && m.q < nj;
+        m.st = m.ld && m.col >= HALO && m.col < HALO + OUT;
+        m.g = m.ld ? (unsigned)m.q : 0u;
+        m.lds = sw_cs<G>(m.on ? m.col : 0);
+        return m;
+    };
+    auto wrap = [](int t) { return t >= RING ? t - RING : t; };   // t in [0, 2 RING)
+    const int sro = (stage == 0) ? 0 : (stage == 1) ? -2 : (stage == 2) ? -5 : (stage == 3) ? -7 : (stage == 4) ? -11 : (stage == 5) ? -14 : -16;
+    const int rr_lo = (stage < 2) ? 0 : (stage < 5) ? 1 : 2;
+    const int rr_hi = (stage < 2) ? H : (stage < 4) ? H - 1 : (stage == 4) ? TI + 1 : TI;
+    const bool uni = wave < 7;                           // stage waves: the stage's row is wave-uniform
+
+    constexpr int ND = CoefFmt<CT>::ND;
+    constexpr bool F8 = std::is_same<CT, CoefF8>::value;
+    static_assert(CoefPacked<CT>::value, "k_sweep_st2 is written for the packed stencil formats");
+    word_t cw[2][ND], dg[PLANES - ND];
+    VT bq[3];                                            // b of the stage's point: requested with the diagonal block
+#pragma unroll
+    for (int k = 0; k < ND; ++k) cw[0][k] = cw[1][k] = 0;
+#pragma unroll
+    for (int k = 0; k < PLANES - ND; ++k) dg[k] = 0;
+    bq[0] = bq[1] = bq[2] = (VT)0;
+    auto offd = [](const word_t* w, int j) {   // off-diagonal coefficient j (0..71) of a set (CoefF8: in the units of its row)
+        if constexpr (F8) {
+            return (double)f8_decode(w[j >> 2], j & 3);
+        } else {
+            const uint32_t v = w[j >> 1];
+            return (double)__uint_as_float((j & 1) ? (v & 0xFFFF0000u) : (v << 16));
+        }
+    };
+    auto point_base = [&](const int pn, const word_t*& base, unsigned& idx, const bool fast) {
+        if (fast && uni) {
+            const int pnu = __builtin_amdgcn_readfirstlane(pn);
+            base = Cp + (size_t)((pnu & 1) << 1) * L.sub + (size_t)(pnu >> 1) * L.hj;
+            idx = ccq;
+        } else {
+            base = Cp;
+            idx = (unsigned)((size_t)((pn & 1) << 1) * L.sub + (size_t)(pn >> 1) * L.hj) + ccq;
+        }
+    };
+    auto fetch_point = [&](auto fast_tag, auto jtag, const int eN) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        constexpr int J = decltype(jtag)::value;
+        const int rrn = eN + sro, pn = p0 + rrn;
+        if (FAST || (col_ok && rrn >= rr_lo && rrn <= rr_hi && pn >= 0 && pn < ni)) {
+            const word_t* base; unsigned idx;
+            point_base(pn, base, idx, FAST);
+#pragma unroll
+            for (int k = 0; k < ND; ++k) cw[J][k] = (base + (size_t)k * L.plane)[idx];
+        }
+    };
+    auto fetch_diag = [&](auto fast_tag, const int eN) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        const int rrn = eN + sro, pn = p0 + rrn;
+        if (FAST || (col_ok && rrn >= rr_lo && rrn <= rr_hi && pn >= 0 && pn < ni)) {
+            const word_t* base; unsigned idx;
+            point_base(pn, base, idx, FAST);
+#pragma unroll
+            for (int k = 0; k < PLANES - ND; ++k) dg[k] = (base + (size_t)(ND + k) * L.plane)[idx];
+            const VT* brow = bp + (size_t)pn * nj + bcol;
+            bq[0] = brow[0]; bq[1] = brow[npts]; bq[2] = brow[2 * npts];
+        }
+    };
+
+    int slotA = (2 * RING - 2) % RING;   // ring slot of relative row e + 2 (even), advanced by 2 per step
+    auto step = [&](auto fast_tag, auto jtag, const int e) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        constexpr int JC = decltype(jtag)::value;
+        const bool do_load = FAST ? true : (e + 2 <= H + 1);
+        const XMap m1 = xmap(opaque_tid());
+        // (1) write-out: rows e - 10, e - 9 of the reverse sweep's result, rows e - 20, e - 19 of the final one (the slots the rows
+        // loaded in this step take over).  Both only for the TI rows of the forward band, relative rows 1 .. TI.
+        {
+            const int rr = e - 10 + m1.row, p = p0 + rr;
+            if (m1.st && (FAST || (rr >= 1 && rr <= TI && p >= 0 && p < ni))) {
+                VT* orow = xmid + (size_t)p * nj + m1.g;
+                const VT* lrow = xs + (wrap(slotA + RING - 12) + m1.row) * 3 * W + m1.lds;
+                orow[0] = lrow[0]; orow[npts] = lrow[W]; orow[2 * npts] = lrow[2 * W];
+            }
+        }
+        {
+            const int rr = e - 20 + m1.row, p = p0 + rr;
+            if (m1.st && (FAST || (rr >= 1 && rr <= TI && p >= 0 && p < ni))) {
+                VT* orow = xout + (size_t)p * nj + m1.g;
+                const VT* lrow = xs + (slotA + m1.row) * 3 * W + m1.lds;
+                orow[0] = lrow[0]; orow[npts] = lrow[W]; orow[2 * npts] = lrow[2 * W];
+            }
+        }
+        // (2) rows e + 2, e + 3 -> registers (moved into the ring in (5)), then the next step's point
+        VT lx[3] = {(VT)0, (VT)0, (VT)0};
+        {
+            const int pR = p0 + e + 2 + m1.row;
+            if (FAST) {   // (columns outside the grid: a clamped address, see k_sweep_st)
+                const VT* irow = xin + (size_t)pR * nj + m1.g;
+                lx[0] = irow[0]; lx[1] = irow[npts]; lx[2] = irow[2 * npts];
+            } else if (m1.ld && do_load && pR >= 0 && pR < ni) {
+                const VT* irow = xin + (size_t)pR * nj + m1.g;
+                lx[0] = irow[0]; lx[1] = irow[npts]; lx[2] = irow[2 * npts];
+            }
+        }
+        fetch_point(fast_tag, std::integral_constant<int, 1 - JC>{}, e + 2);
+        // (4) the stage of this lane: block Gauss-Seidel update of its point, neighbours read row by row (as in k_sweep_st)
+        {
+            const int rr = e + sro, p = p0 + rr;
+            if (col_ok && (FAST || (rr >= rr_lo && rr <= rr_hi && p >= 0 && p < ni))) {
+                // rows rr - 1, rr, rr + 1 are (e + 2) + (sro - 3), (sro - 2), (sro - 1); sro - 3 >= -19 > -RING
+                const int sU = wrap(slotA + RING + sro - 3), sC = wrap(slotA + RING + sro - 2), sD = wrap(slotA + RING + sro - 1);
+                const int rowo[3] = {sU * 3 * W, sC * 3 * W, sD * 3 * W};
+                const int colo[3] = {uL, cC, uR};
+                const word_t* c_ = cw[JC];
+                double y0 = 0, y1 = 0, y2 = 0;
+                typedef double AT;
+                AT yp[F8 ? 9 : 1];
+                if constexpr (F8) {
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) yp[t] = 0;
+                }
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const VT* row = xs + rowo[a];
+#pragma unroll
+                    for (int bb = 0; bb < 3; ++bb) {
+                        if (a == 1 && bb == 1) continue;
+                        double xu = (double)row[colo[bb]], xw = (double)row[W + colo[bb]], xg = (double)row[2 * W + colo[bb]];
+                        const int d = a * 3 + bb, t0 = (d < 4 ? d : d - 1) * 9;
+                        if constexpr (F8) {
+                            const AT au = (AT)row[colo[bb]], aw = (AT)row[W + colo[bb]], ag = (AT)row[2 * W + colo[bb]];
+#pragma unroll
+                            for (int r = 0; r < 3; ++r) {
+                                yp[3 * r + 0] += (AT)f8_decode(c_[(t0 + 3 * r + 0) >> 2], (t0 + 3 * r + 0) & 3) * au;
+                                yp[3 * r + 1] += (AT)f8_decode(c_[(t0 + 3 * r + 1) >> 2], (t0 + 3 * r + 1) & 3) * aw;
+                                yp[3 * r + 2] += (AT)f8_decode(c_[(t0 + 3 * r + 2) >> 2], (t0 + 3 * r + 2) & 3) * ag;
+                            }
+                        } else {
+                            y0 += offd(c_, t0 + 0) * xu + offd(c_, t0 + 1) * xw + offd(c_, t0 + 2) * xg;
+                            y1 += offd(c_, t0 + 3) * xu + offd(c_, t0 + 4) * xw + offd(c_, t0 + 5) * xg;
+                            y2 += offd(c_, t0 + 6) * xu + offd(c_, t0 + 7) * xw + offd(c_, t0 + 8) * xg;
+                        }
+                    }
+                    asm volatile("" ::: "memory");   // keep the LDS reads of the next row behind this row's arithmetic
+                }
+                double Dm[9];
+#pragma unroll
+                for (int t = 0; t < 9; ++t) Dm[t] = (double)__uint_as_float(dg[t]);
+                if constexpr (F8) {
+                    y0 = (double)yp[0] * (double)f8_unit(dg[9], 0) + (double)yp[1] * (double)f8_unit(dg[9], 1) + (double)yp[2] * (double)f8_unit(dg[9], 2);
+                    y1 = (double)yp[3] * (double)f8_unit(dg[10], 0) + (double)yp[4] * (double)f8_unit(dg[10], 1) + (double)yp[5] * (double)f8_unit(dg[10], 2);
+                    y2 = (double)yp[6] * (double)f8_unit(dg[11], 0) + (double)yp[7] * (double)f8_unit(dg[11], 1) + (double)yp[8] * (double)f8_unit(dg[11], 2);
+                }
+                double u, w, gm;
+                solve3(Dm, (double)bq[0] - y0, (double)bq[1] - y1, (double)bq[2] - y2, u, w, gm);
+                VT* row = xs + rowo[1] + cC;
+                row[0] = (VT)u; row[W] = (VT)w; row[2 * W] = (VT)gm;
+            }
+        }
+        fetch_diag(fast_tag, e + 2);   // the diagonal block and b of the next step's point (the registers are free now)
+        // (5) loaded rows -> LDS ring (the slots freed by the second write-out, same thread <-> element mapping)
+        const XMap m5 = xmap(opaque_tid());
+        if (do_load && m5.on) {
+            VT* lrow = xs + (slotA + m5.row) * 3 * W + m5.lds;
+            lrow[0] = lx[0]; lrow[W] = lx[1]; lrow[2 * W] = lx[2];
+        }
+        slotA = wrap(slotA + 2);
+        __syncthreads();
+    };
+
+    // Steps s = -2 .. TI / 2 + 10 (e = 2 s); step n = s + 2 uses set n & 1.  A step is FAST when every row it touches - written out
+    // (e - 20 .. e - 9, inside 1 .. TI), loaded (e + 2, e + 3), updated (e .. e - 16, inside their stage's range) - and every row the
+    // NEXT step updates exists.
+    const int s_end = TI / 2 + 10;
+    const int e_lo = max(22, 20 - p0);                 // row e - 20 >= 2 and inside the grid
+    const int e_hi = min(TI + 2, ni - 4 - p0);         // loaded row e + 3 <= H + 1 and inside the grid, next step's row e + 2 <= H
+    auto pair_fast = [&](const int s) { return 2 * s >= e_lo && 2 * (s + 1) <= e_hi; };
+    int s = -2;
+    for (int part = 0; part < 2; ++part) {
+        while (s <= s_end && (part == 1 || !pair_fast(s))) {
+            step(std::false_type{}, std::integral_constant<int, 0>{}, 2 * s);
+            if (s + 1 <= s_end) step(std::false_type{}, std::integral_constant<int, 1>{}, 2 * (s + 1));
+            s += 2;
+        }
+        if (part == 0 && s <= s_end) {
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): nothing requested by the predicated steps is still in flight
+            while (pair_fast(s)) {
+                step(std::true_type{}, std::integral_constant<int, 0>{}, 2 * s);
+                step(std::true_type{}, std::integral_constant<int, 1>{}, 2 * (s + 1));
+                s += 2;
+            }
+        }
+    }
+}
+
 // k_sweep0: the fused 4-colour sweep of level 0 (matrix-free), the north-star kernel.  Same schedule, strip geometry
 // (120 owned + 2 x 4 halo columns, 4 colour waves, 12-row ring, bands of TI rows) and results as the first-generation
 // level-0 instantiation of the generic k_sweep above (retired) - bit for bit - but the row loop is rebuilt around its
