@@ -104,7 +104,7 @@ typedef struct vof_pair_stats {
 enum vof_kernel_id {
     VOF_K_RHS = 0, VOF_K_APPLY0, VOF_K_GS0, VOF_K_GS, VOF_K_RESIDUAL, VOF_K_RESTRICT, VOF_K_PROLONG,
     VOF_K_GALERKIN0, VOF_K_GALERKIN, VOF_K_COARSE_SETUP, VOF_K_COARSE_SOLVE, VOF_K_VECTOR, VOF_K_REDUCE,
-    VOF_K_FINALIZE, VOF_K_FUNCTIONALS, VOF_K_COARSE_TAIL, VOF_K_COUNT
+    VOF_K_FINALIZE, VOF_K_FUNCTIONALS, VOF_K_COARSE_TAIL, VOF_K_PREPROCESS, VOF_K_COUNT
 };
 
 int vof_version(void);
@@ -411,6 +411,33 @@ int vof_compare_flows_host(vof_ctx* ctx, const double* movie_a, const double* mo
                            int64_t* joint_counts, vof_compare_stats* stats,
                            double* v_x_a, double* v_y_a, double* speed_a, double* net_remodelling_a,
                            double* v_x_b, double* v_y_b, double* speed_b, double* net_remodelling_b);
+
+/* The two per-frame preprocessing steps the reference's scripts run around every estimator (OF.py:308-374), OpenCV 4's
+ * arithmetic restated in integer / float32 operations (DESIGN.md section 14 has the specification; parity with the real cv2 is
+ * not tested in this repository).  Both first reduce the whole stack to (max, min of the finite values, non-finite count),
+ * written to range[3] (host, may be NULL), and return 1 - nothing else computed, vof_last_error says why - where the
+ * reference's integer cast would be platform-dependent or wrap:
+ *   threshold: a non-finite value, min < 0 or max <= 0;   CLAHE: a non-finite value, min < 0 or max >= 65536.
+ * Frames are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most); the scratch memory
+ * (threshold: 4 bytes per pixel and frame in flight; CLAHE: 65536 x 6 bytes per tile and frame in flight; _host: the staged
+ * frames) is allocated on first use, kept, and freed by vof_destroy.  Results do not depend on frames_in_flight.
+ * Profiler: class VOF_K_PREPROCESS, the `level` is the stage: 0 range, 1 row sums, 2 threshold, 3 histograms, 4 tables, 5 blend.
+ *
+ * vof_adaptive_threshold_*: cv2.adaptiveThreshold(u, 1, ADAPTIVE_THRESH_MEAN_C, THRESH_BINARY, window_size, threshold) == 1 of
+ *   u = (uint8) trunc((x / max) * 255.0) per frame: mask = (u - mean) > -ceil(threshold), mean = the sum of u over the
+ *   window_size x window_size window (indices clamped to the image) divided by window_size^2, rounded to nearest.
+ *   window_size: odd, 3 .. 4095 (every window sum then fits 32 bits); n_j <= 15360.  mask: n_frames x n_i x n_j bytes, 0 / 1.
+ * vof_clahe_*: cv2.createCLAHE(clip_limit, (tiles_x, tiles_y)).apply of v = (uint16) trunc(x) per frame, as float64.
+ *   tiles_x runs along n_j (1 .. n_j - 1), tiles_y along n_i (1 .. n_i - 1); clip_limit <= 0: no clipping.
+ * _dev: movie and the result are device pointers; _host: host pointers, staged through the context's pinned bounce buffer. */
+int vof_adaptive_threshold_dev(vof_ctx* ctx, const double* movie, int n_frames, int window_size, double threshold,
+                               int frames_in_flight, uint8_t* mask, double* range);
+int vof_adaptive_threshold_host(vof_ctx* ctx, const double* movie, int n_frames, int window_size, double threshold,
+                                int frames_in_flight, uint8_t* mask, double* range);
+int vof_clahe_dev(vof_ctx* ctx, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y,
+                  int frames_in_flight, double* out, double* range);
+int vof_clahe_host(vof_ctx* ctx, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y,
+                   int frames_in_flight, double* out, double* range);
 
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);

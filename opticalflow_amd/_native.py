@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VOF_LIB") or os.path.join(HERE, "csrc", "libvof.so")
 
 K_NAMES = ["rhs", "apply0", "gs0", "gs", "residual", "restrict", "prolong", "galerkin0", "galerkin",
-           "coarse_setup", "coarse_solve", "vector", "reduce", "finalize", "functionals", "coarse_tail"]
+           "coarse_setup", "coarse_solve", "vector", "reduce", "finalize", "functionals", "coarse_tail", "preprocess"]
 
 
 class VofParams(C.Structure):
@@ -106,6 +106,10 @@ SIGNATURES = {
     "vof_compare_flows_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                          _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vof_adaptive_threshold_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _dp]),
+    "vof_adaptive_threshold_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _dp]),
+    "vof_clahe_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _dp]),
+    "vof_clahe_host": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _dp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -536,6 +540,40 @@ class Solver:
         return self._compare_flows("vof_compare_flows_dev", movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling,
                                    reference_quirks, weights_a, weights_b, histogram_edges, angle_bins, relative_angle_bins,
                                    joint_speed_edges, joint_speed_min_b, fields_a or [None] * 4, fields_b or [None] * 4)
+
+    def _preprocess(self, fn, movie, n_frames, args, frames_in_flight, out):
+        """One of the four preprocessing entry points; their return code 1 (the stack holds values the reference's integer
+        cast would wrap or leave to the platform) is a ValueError."""
+        rng = (C.c_double * 3)()
+        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), *args, int(frames_in_flight), _ptr(out), rng)
+        if rc == 1:
+            raise ValueError(self.lib.vof_last_error(self.h).decode() + f" (max {rng[0]}, min {rng[1]}, non-finite {int(rng[2])})")
+        self._check(rc, fn)
+
+    def adaptive_threshold_host(self, movie: np.ndarray, window_size=51, threshold=0.0, frames_in_flight=0):
+        """``apply_adaptive_threshold`` of a host movie (read as float64): bool ``(T, n_i, n_j)``.  ``frames_in_flight=0``
+        leaves the chunk size to the library."""
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        mask = np.empty(movie.shape, dtype=np.uint8)
+        self._preprocess("vof_adaptive_threshold_host", movie, movie.shape[0], (int(window_size), float(threshold)), frames_in_flight, mask)
+        return mask.view(np.bool_)
+
+    def adaptive_threshold_dev(self, movie, mask, n_frames, window_size=51, threshold=0.0, frames_in_flight=0):
+        """The same on device memory (torch tensors or raw pointers): float64 frames in, one byte (0 / 1) per pixel out."""
+        self._preprocess("vof_adaptive_threshold_dev", movie, n_frames, (int(window_size), float(threshold)), frames_in_flight, mask)
+
+    def clahe_host(self, movie: np.ndarray, clip_limit, tiles_x, tiles_y, frames_in_flight=0):
+        """``apply_clahe`` of a host movie for the tile grid ``tiles_x`` (along n_j) by ``tiles_y``: float64 ``(T, n_i, n_j)``."""
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        out = np.empty(movie.shape, dtype=np.float64)
+        self._preprocess("vof_clahe_host", movie, movie.shape[0], (float(clip_limit), int(tiles_x), int(tiles_y)), frames_in_flight, out)
+        return out
+
+    def clahe_dev(self, movie, out, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight=0):
+        """The same on device memory: float64 frames in and out (``out`` must not alias ``movie``)."""
+        self._preprocess("vof_clahe_dev", movie, n_frames, (float(clip_limit), int(tiles_x), int(tiles_y)), frames_in_flight, out)
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

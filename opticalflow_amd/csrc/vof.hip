@@ -16,6 +16,7 @@
 #include "vof_blursweep.hpp"
 #include "vof_compare.hpp"
 #include "vof_liushen.hpp"
+#include "vof_preprocess.hpp"
 #include "../../include/vof.h"
 
 #include <fcntl.h>
@@ -120,6 +121,8 @@ struct vof_ctx {
     bool sw_by_budget = false;                                           // sw_scratch was sized by the free memory, not by the request
     char* sw_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
     size_t sw_aux_bytes = 0;
+    char* pre_buf = nullptr;                                             // adaptive threshold / CLAHE: partials, row sums or histograms and tables, staged frames (lazy; pre_plan)
+    size_t pre_bytes = 0;
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
     bool bl_lds_set = false;                                             // tiled blur: dynamic LDS limit raised
     bool ls_lds_set = false;                                             // Liu-Shen flow, fused kernel: dynamic LDS limit raised
@@ -2082,7 +2085,7 @@ int vof_device_memory(int device_id, size_t* free_bytes, size_t* total_bytes) {
 const char* vof_kernel_name(int k) {
     static const char* names[VOF_K_COUNT] = {"rhs", "apply0", "gs0", "gs", "residual", "restrict", "prolong",
                                              "galerkin0", "galerkin", "coarse_setup", "coarse_solve", "vector",
-                                             "reduce", "finalize", "functionals", "coarse_tail"};
+                                             "reduce", "finalize", "functionals", "coarse_tail", "preprocess"};
     return (k >= 0 && k < VOF_K_COUNT) ? names[k] : "?";
 }
 
@@ -4314,6 +4317,218 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
 
 int vof_compare_flows_dev(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(false)); }
 int vof_compare_flows_host(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(true)); }
+
+// ---- preprocessing: adaptive threshold and CLAHE (apply_adaptive_threshold, apply_clahe; vof_preprocess.hpp) ---------------
+constexpr int PRE_MAX_FLIGHT = 16;        // frames in flight when the caller leaves the number to the library
+constexpr int PRE_MAX_WANT = 4096;        // ... and at most when it does not (grid z)
+
+struct PrePlan {
+    int cap;                 // frames in flight
+    PpRange *part, *rng;     // the range reduction's partial records and its result
+    char *work_a, *work_b;   // cap x (bytes_a, bytes_b): row sums | histograms, tables
+    double* in;              // _host: the staged frames
+    char* out;               // _host: the staged results
+};
+
+static inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The scratch buffer of the two calls, grown (never shrunk) to what `cap` frames in flight need; cap is `want`, or sized so that
+// the buffer takes a quarter of the free device memory at most (an existing larger buffer is used in full).
+static int pre_plan(vof_ctx* c, int n_frames, int want, size_t bytes_a, size_t bytes_b, size_t out_bytes, bool host, const char* what, PrePlan* p) {
+    const size_t fb = frame_stride(c) * sizeof(double);
+    const size_t fixed = up256((PP_RANGE_BLOCKS + 1) * sizeof(PpRange)) + 4 * 256;
+    const size_t per = bytes_a + bytes_b + (host ? fb + out_bytes : 0);
+    int cap = std::min(want, PRE_MAX_WANT);
+    if (cap <= 0) {
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        const size_t budget = std::max(fr / 4, c->pre_bytes);
+        cap = (int)std::min<size_t>(PRE_MAX_FLIGHT, budget > fixed ? (budget - fixed) / per : 0);
+    }
+    cap = std::max(1, std::min(cap, n_frames));
+    const size_t need = fixed + up256(cap * bytes_a) + up256(cap * bytes_b) + (host ? up256(cap * fb) + up256(cap * out_bytes) : 0);
+    if (need > c->pre_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (int rc = dev_free(c, c->pre_buf)) return rc;
+        c->pre_buf = nullptr; c->pre_bytes = 0;
+        if (int rc = dev_alloc(c, &c->pre_buf, need)) {
+            (void)hipGetLastError();
+            c->err = std::string(what) + ": no device memory for " + std::to_string(need >> 20) + " MiB of scratch (" + std::to_string(cap) +
+                     " frame(s) in flight): " + c->err;
+            return rc;
+        }
+        c->pre_bytes = need;
+    }
+    char* q = c->pre_buf;
+    p->cap = cap;
+    p->part = (PpRange*)q; p->rng = p->part + PP_RANGE_BLOCKS; q += up256((PP_RANGE_BLOCKS + 1) * sizeof(PpRange));
+    p->work_a = q; q += up256(cap * bytes_a);
+    p->work_b = q; q += up256(cap * bytes_b);
+    p->in = (double*)q; q += host ? up256(cap * fb) : 0;
+    p->out = q;
+    return 0;
+}
+
+// (max, min of the finite values, non-finite count) of the whole stack; _host: chunk by chunk through the staged frames (the
+// last chunk stays there: a stack of one chunk is not uploaded again)
+static int pre_range(vof_ctx* c, const PrePlan& p, const double* movie, int n_frames, bool host, double out[3]) {
+    const size_t fs = frame_stride(c);
+    PpRange acc{-INFINITY, INFINITY, 0};
+    const int chunk = host ? p.cap : n_frames;
+    for (int k0 = 0; k0 < n_frames; k0 += chunk) {
+        const int nf = std::min(chunk, n_frames - k0);
+        const double* src = movie + (size_t)k0 * fs;
+        if (host) {
+            if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fs * sizeof(double))) return rc;
+            src = p.in;
+        }
+        const size_t n = (size_t)nf * fs;
+        const int nb = (int)std::min<size_t>(PP_RANGE_BLOCKS, (n + 8 * PP_BLOCK - 1) / (8 * PP_BLOCK));
+        c->cur_units = nf;
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_RANGE, 8.0 * fs);
+            k_pp_range<<<nb, PP_BLOCK, 0, c->stream>>>(src, n, p.part);
+            k_pp_range_final<<<1, 64, 0, c->stream>>>(p.part, nb, p.rng);
+        }
+        HIPCHK(hipGetLastError());
+        PpRange r;
+        if (int rc = d2h_bounced(c, &r, p.rng, sizeof r)) return rc;
+        acc.vmax = std::max(acc.vmax, r.vmax); acc.vmin = std::min(acc.vmin, r.vmin); acc.bad += r.bad;
+    }
+    out[0] = acc.vmax; out[1] = acc.vmin; out[2] = (double)acc.bad;
+    return 0;
+}
+
+static int adaptive_threshold_impl(vof_ctx* c, const double* movie, int n_frames, int window, double threshold, int flight, uint8_t* mask,
+                                   double* range, bool host) {
+    if (!c) return -1;
+    if (!movie || !mask) { c->err = "NULL pointer"; return -1; }
+    if (n_frames < 1) { c->err = "n_frames must be >= 1"; return -1; }
+    if (window < 3 || window % 2 == 0 || window > PP_MAX_WINDOW) { c->err = "window_size must be odd and 3 .. " + std::to_string(PP_MAX_WINDOW); return -1; }
+    if (c->Nj > PP_MAX_ROW) { c->err = "adaptive threshold: n_j must be <= " + std::to_string(PP_MAX_ROW); return -1; }
+    if (c->Ni > 65535 * PP_COL_ROWS) { c->err = "adaptive threshold: n_i too large"; return -1; }
+    if (std::isnan(threshold)) { c->err = "threshold is NaN"; return -1; }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t fs = frame_stride(c);
+    PrePlan p;
+    if (int rc = pre_plan(c, n_frames, flight, fs * sizeof(unsigned int), 0, fs, host, "adaptive threshold", &p)) return rc;
+    double rg[3];
+    if (int rc = pre_range(c, p, movie, n_frames, host, rg)) return rc;
+    if (range) memcpy(range, rg, sizeof rg);
+    if (rg[2] > 0) { c->err = "adaptive threshold: the movie holds non-finite values"; return 1; }
+    if (rg[1] < 0) { c->err = "adaptive threshold: the movie holds negative values"; return 1; }
+    if (!(rg[0] > 0)) { c->err = "adaptive threshold: the movie's maximum is not positive"; return 1; }
+    const double m = rg[0];
+    const int r = window / 2;
+    const int idelta = (int)std::max(-1024.0, std::min(1024.0, std::ceil(threshold)));   // u - mean lies in [-255, 255]
+    unsigned int* H = (unsigned int*)p.work_a;
+    for (int k0 = 0; k0 < n_frames; k0 += p.cap) {
+        const int nf = std::min(p.cap, n_frames - k0);
+        const double* src = movie + (size_t)k0 * fs;
+        if (host) {
+            if (n_frames > p.cap) if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fs * sizeof(double))) return rc;
+            src = p.in;
+        }
+        uint8_t* dst = host ? (uint8_t*)p.out : mask + (size_t)k0 * fs;
+        c->cur_units = nf;
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_ROWSUM, 12.0 * fs);
+            k_pp_rowsum<<<dim3(c->Ni, nf), PP_BLOCK, (size_t)c->Nj * sizeof(unsigned int), c->stream>>>(src, c->Ni, c->Nj, m, r, H);
+        }
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_THRESHOLD, 13.0 * fs);
+            k_pp_threshold<<<dim3((c->Nj + PP_BLOCK - 1) / PP_BLOCK, (c->Ni + PP_COL_ROWS - 1) / PP_COL_ROWS, nf), PP_BLOCK, 0, c->stream>>>(src, H, c->Ni, c->Nj, m, r,
+                                                                                                                  idelta, dst);
+        }
+        HIPCHK(hipGetLastError());
+        if (host) if (int rc = d2h_bounced(c, mask + (size_t)k0 * fs, dst, (size_t)nf * fs)) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vof_adaptive_threshold_dev(vof_ctx* c, const double* movie, int n_frames, int window_size, double threshold, int frames_in_flight,
+                               uint8_t* mask, double* range) {
+    return adaptive_threshold_impl(c, movie, n_frames, window_size, threshold, frames_in_flight, mask, range, false);
+}
+int vof_adaptive_threshold_host(vof_ctx* c, const double* movie, int n_frames, int window_size, double threshold, int frames_in_flight,
+                                uint8_t* mask, double* range) {
+    return adaptive_threshold_impl(c, movie, n_frames, window_size, threshold, frames_in_flight, mask, range, true);
+}
+
+static int clahe_impl(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int flight, double* out,
+                      double* range, bool host) {
+    if (!c) return -1;
+    if (!movie || !out) { c->err = "NULL pointer"; return -1; }
+    if (n_frames < 1) { c->err = "n_frames must be >= 1"; return -1; }
+    if (tiles_x < 1 || tiles_x > c->Nj - 1 || tiles_y < 1 || tiles_y > c->Ni - 1) {
+        c->err = "CLAHE: the tile grid must be 1 .. n_j - 1 by 1 .. n_i - 1"; return -1;
+    }
+    if (std::isnan(clip_limit)) { c->err = "clip_limit is NaN"; return -1; }
+    ClaheGeom g{};
+    g.ni = c->Ni; g.nj = c->Nj; g.tx = tiles_x; g.ty = tiles_y;
+    const bool pad = g.nj % g.tx != 0 || g.ni % g.ty != 0;          // one axis not dividing pads both, a dividing one by a full grid
+    g.pj = pad ? g.nj + (g.tx - g.nj % g.tx) : g.nj;
+    g.pi = pad ? g.ni + (g.ty - g.ni % g.ty) : g.ni;
+    g.tw = g.pj / g.tx; g.th = g.pi / g.ty;
+    const long long area = (long long)g.tw * g.th;
+    if (g.pi > 65535 || area > 0x7FFFFFFFLL) { c->err = "CLAHE: image too large"; return -1; }
+    if (clip_limit > 0) {
+        const double cl = clip_limit * (double)area / (double)PP_BINS;
+        g.clip = std::max(cl >= 2147483647.0 ? 2147483647 : (int)cl, 1);
+    }
+    g.lut_scale = (float)(PP_BINS - 1) / (float)area;
+    g.inv_tw = 1.0f / (float)g.tw; g.inv_th = 1.0f / (float)g.th;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const size_t ntiles = (size_t)g.tx * g.ty, hist_bytes = ntiles * PP_BINS * sizeof(unsigned int), lut_bytes = ntiles * PP_BINS * sizeof(uint16_t);
+    PrePlan p;
+    if (int rc = pre_plan(c, n_frames, flight, hist_bytes, lut_bytes, fb, host, "CLAHE", &p)) return rc;
+    double rg[3];
+    if (int rc = pre_range(c, p, movie, n_frames, host, rg)) return rc;
+    if (range) memcpy(range, rg, sizeof rg);
+    if (rg[2] > 0) { c->err = "CLAHE: the movie holds non-finite values"; return 1; }
+    if (rg[1] < 0 || rg[0] >= 65536.0) { c->err = "CLAHE: the movie holds values outside [0, 65536)"; return 1; }
+    unsigned int* hist = (unsigned int*)p.work_a;
+    uint16_t* lut = (uint16_t*)p.work_b;
+    const double padded = (double)g.pi * g.pj;
+    for (int k0 = 0; k0 < n_frames; k0 += p.cap) {
+        const int nf = std::min(p.cap, n_frames - k0);
+        const double* src = movie + (size_t)k0 * fs;
+        if (host) {
+            if (n_frames > p.cap) if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fb)) return rc;
+            src = p.in;
+        }
+        double* dst = host ? (double*)p.out : out + (size_t)k0 * fs;
+        c->cur_units = nf;
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_HIST, 8.0 * padded + 2.0 * hist_bytes);   // the zero fill and the counters read back
+            HIPCHK(hipMemsetAsync(hist, 0, (size_t)nf * hist_bytes, c->stream));
+            k_pp_hist<<<dim3((g.pj + PP_BLOCK - 1) / PP_BLOCK, g.pi, nf), PP_BLOCK, 0, c->stream>>>(src, g, hist);
+        }
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_LUT, (g.clip > 0 ? 2.0 : 1.0) * hist_bytes + lut_bytes, (double)hist_bytes + lut_bytes);
+            k_pp_lut<<<dim3((unsigned)ntiles, nf), PP_BLOCK, 0, c->stream>>>(hist, g, lut);
+        }
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_BLEND, 24.0 * fs, 16.0 * fs);             // 4 table entries of 2 bytes from the cache
+            k_pp_blend<<<dim3((g.nj + PP_BLOCK - 1) / PP_BLOCK, g.ni, nf), PP_BLOCK, 0, c->stream>>>(src, g, lut, dst);
+        }
+        HIPCHK(hipGetLastError());
+        if (host) if (int rc = d2h_bounced(c, out + (size_t)k0 * fs, dst, (size_t)nf * fb)) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vof_clahe_dev(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int frames_in_flight,
+                  double* out, double* range) {
+    return clahe_impl(c, movie, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight, out, range, false);
+}
+int vof_clahe_host(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int frames_in_flight,
+                   double* out, double* range) {
+    return clahe_impl(c, movie, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight, out, range, true);
+}
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------
 constexpr int LS_CHUNK = 16384;           // pairs per launch (grid z)

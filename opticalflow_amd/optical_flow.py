@@ -65,6 +65,7 @@ atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
+           "apply_adaptive_threshold", "apply_clahe",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -109,6 +110,116 @@ def blur_movie(movie, smoothing_sigma, device=0, _solver=None):
         if (solver.n_i, solver.n_j) != movie.shape[1:]:
             raise ValueError("frames must be at least 4x4")
         return solver.blur_host(frames, taps)
+
+
+THRESHOLD_MAX_WINDOW = 4095          # PP_MAX_WINDOW of csrc/vof_preprocess.hpp: 255 * w^2 < 2^32, every window sum fits 32 bits
+THRESHOLD_MAX_ROW = 15360            # PP_MAX_ROW: a row's prefix sums live in LDS
+
+
+def _preprocess_shape(movie, output):
+    """``(T, N_i, N_j)`` of a movie the two preprocessing calls accept; the checks the two share, before the library is touched."""
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
+    if len(shape) != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    if shape[0] < 1 or shape[1] < 4 or shape[2] < 4:
+        raise ValueError("movie needs at least one frame of at least 4x4 pixels")
+    return shape
+
+
+def _run_preprocess(movie, shape, device, output, result_dtype, host_call, dev_call):
+    """The frames as float64 on the side ``output`` names, through the cached context, to one of the native calls."""
+    T, N_i, N_j = shape
+    if output == "numpy":
+        frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
+        with _device_context(N_i, N_j, 1, device) as solver:
+            return host_call(solver, frames)
+    import torch
+    dev = torch.device("cuda", int(device))
+    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
+    out = torch.empty(shape, dtype=result_dtype(torch), device=dev)
+    with _device_context(N_i, N_j, 1, device) as solver:
+        torch.cuda.synchronize(dev)                  # the library launches on its own stream
+        dev_call(solver, frames, out, T)
+    return out
+
+
+def apply_adaptive_threshold(movie, window_size=51, threshold=0.0, *, device=0, output="numpy"):
+    """OpenCV's adaptive mean threshold of every frame on the GPU; positional arguments and the bool ``(T, N_i, N_j)`` result
+    as OF.py:308-338, which calls ``cv2.adaptiveThreshold(frame, 1.0, cv2.ADAPTIVE_THRESH_MEAN_C, cv2.THRESH_BINARY,
+    window_size, threshold)`` on ``np.array(movie / np.max(movie) * 255.0, dtype='uint8')`` and compares with 1.
+
+    The movie is read as float64 (a float32 movie is therefore computed in float64).  With ``m`` the maximum of the whole stack:
+    ``u = (uint8) trunc((x / m) * 255.0)``; ``S`` the sum of ``u`` over the ``window_size`` x ``window_size`` window centred on the
+    pixel, indices outside the image clamped to the edge (BORDER_REPLICATE; the window may be larger than the image);
+    ``mean = floor((2 * S + w**2) / (2 * w**2))``, ``S / w**2`` rounded to nearest (``w`` is odd: no tie); result
+    ``(u - mean) > -ceil(threshold)``.  All of it is integer arithmetic, restated from OpenCV 4's source; parity with an
+    installed ``cv2`` is tested only where one can be imported (tests/test_preprocess_cv2_cpu.py).
+
+    ``window_size`` must be odd and 3 .. 4095 (every window sum then fits 32 bits) and ``N_j <= 15360``: ``ValueError``
+    otherwise.  Two deviations from the reference: a stack with a NaN / Inf, a negative value or a maximum ``<= 0`` raises
+    ``ValueError`` - the reference's ``uint8`` cast of such values is platform-dependent; and frames smaller than 4 x 4 pixels
+    raise ``ValueError`` - the device context serves no smaller image.
+    ``output="torch"``: ``movie`` may be a device tensor and the result is a ``torch.bool`` tensor on the device."""
+    shape = _preprocess_shape(movie, output)
+    if int(window_size) != window_size or int(window_size) % 2 == 0 or int(window_size) <= 1:
+        raise ValueError("window_size must be an odd integer > 1")
+    if int(window_size) > THRESHOLD_MAX_WINDOW:
+        raise ValueError(f"window_size must be <= {THRESHOLD_MAX_WINDOW}")
+    if shape[2] > THRESHOLD_MAX_ROW:
+        raise ValueError(f"frames may have {THRESHOLD_MAX_ROW} columns at most")
+    if np.isnan(float(threshold)):
+        raise ValueError("threshold is NaN")
+    w, t = int(window_size), float(threshold)
+    return _run_preprocess(movie, shape, device, output, lambda torch: torch.bool,
+                           lambda solver, frames: solver.adaptive_threshold_host(frames, w, t),
+                           lambda solver, frames, out, T: solver.adaptive_threshold_dev(frames, out, T, w, t))
+
+
+def clahe_tile_grid(shape, tile_number):
+    """``(tilesX, tilesY)`` the reference hands to ``cv2.createCLAHE`` for a ``(T, N_i, N_j)`` movie (OF.py:365-366):
+    ``tilesX = tile_number`` runs along ``N_j`` - OpenCV's ``Size(width, height)`` - and ``tilesY = round(tile_number * N_j /
+    N_i)`` along ``N_i``; the mix-up of the axes is the reference's and is kept.  ``ValueError`` unless ``1 <= tilesX <= N_j - 1``
+    and ``1 <= tilesY <= N_i - 1`` (the reflected padding needs it)."""
+    _T, N_i, N_j = shape
+    if int(tile_number) != tile_number:
+        raise ValueError("tile_number must be an integer")
+    tiles_x = int(tile_number)
+    tiles_y = round(tile_number * (N_j / N_i))
+    if not (1 <= tiles_x <= N_j - 1 and 1 <= tiles_y <= N_i - 1):
+        raise ValueError(f"tile grid {tiles_x} x {tiles_y} does not fit frames of {N_i} x {N_j} pixels: "
+                         "1 <= tilesX <= N_j - 1 and 1 <= tilesY <= N_i - 1 are required")
+    return tiles_x, tiles_y
+
+
+def apply_clahe(movie, clipLimit=50000, tile_number=10, *, device=0, output="numpy"):
+    """OpenCV's contrast-limited adaptive histogram equalisation of every frame on the GPU; positional arguments and the
+    float64 ``(T, N_i, N_j)`` result as OF.py:340-374, which calls ``cv2.createCLAHE(clipLimit, (tile_number,
+    round(tile_number * N_j / N_i))).apply`` on ``movie.astype(np.uint16)``.  The reference's ``print(np.max(...))`` is not
+    reproduced.
+
+    Per frame, restated from OpenCV 4's ``clahe.cpp`` for 16-bit input (65536 bins): ``v = (uint16) trunc(x)``; the tile grid of
+    ``clahe_tile_grid``; if either axis does not divide by its grid, the right side is extended by ``tilesX - N_j % tilesX``
+    columns and the bottom by ``tilesY - N_i % tilesY`` rows (BORDER_REFLECT_101) - a dividing axis then receives a full
+    ``tiles`` of padding, as in OpenCV; ``clip = max(int(clipLimit * area / 65536), 1)`` for ``clipLimit > 0``, no clipping
+    otherwise; per tile the histogram is clipped, the excess is redistributed (``excess // 65536`` to every bin, the rest
+    one each to every ``max(65536 // rest, 1)``-th bin) and summed into a uint16 table ``rint(float32(sum) * float32(65535) /
+    float32(area))``; every pixel blends the tables of its four neighbouring tiles bilinearly in float32.  Integer up to the
+    table, so bit-reproducible; parity with an installed ``cv2`` is tested only where one can be imported.
+
+    ``ValueError`` for a tile grid that does not fit and - the deviations from the reference - for a stack with a NaN / Inf
+    or a value outside ``[0, 65536)``, which the reference wraps, and for frames smaller than 4 x 4 pixels, which the device
+    context does not serve.  Device memory: ``65536 * 6`` bytes per tile and frame in flight.
+    ``output="torch"``: ``movie`` may be a device tensor and the result is a float64 tensor on the device."""
+    shape = _preprocess_shape(movie, output)
+    tiles_x, tiles_y = clahe_tile_grid(shape, tile_number)
+    if np.isnan(float(clipLimit)):
+        raise ValueError("clipLimit is NaN")
+    clip = float(clipLimit)
+    return _run_preprocess(movie, shape, device, output, lambda torch: torch.float64,
+                           lambda solver, frames: solver.clahe_host(frames, clip, tiles_x, tiles_y),
+                           lambda solver, frames, out, T: solver.clahe_dev(frames, out, T, clip, tiles_x, tiles_y))
 
 
 def format_elapsed_time(time_difference):
