@@ -439,6 +439,26 @@ int vof_clahe_dev(vof_ctx* ctx, const double* movie, int n_frames, double clip_l
 int vof_clahe_host(vof_ctx* ctx, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y,
                    int frames_in_flight, double* out, double* range);
 
+/* The resize of the reference's small-grid experiments, cv2.resize(frame, dsize=(out_j, out_i), interpolation=cv2.INTER_AREA)
+ * of every frame of a one-channel stack when neither axis is enlarged (1 <= out_i <= n_i, 1 <= out_j <= n_j), OpenCV 4's
+ * arithmetic restated operation by operation (DESIGN.md section 15 has the specification; parity with the real cv2 is not
+ * tested in this repository).  Frames arrive as float64 whatever the arithmetic; the result is float64, n_frames x out_i x out_j.
+ *   VOF_RESIZE_U8:  the arithmetic OpenCV applies to uint8 frames - float32 sums where a scale is fractional, integer block
+ *     sums where both are integers, the result rounded to 0 .. 255 (half to even; half up on the 2 x 2 path).  The stack is
+ *     first reduced as in the calls above: a non-finite value, min < 0 or max > 255 returns 1, nothing else computed,
+ *     vof_last_error says why.  That every value is an integer is the caller's contract and is not checked.
+ *   VOF_RESIZE_F64: the arithmetic of float64 frames - float64 sums with float32 weights; NaN and Inf propagate.
+ * Frames are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most); the two axis tables
+ * are built on the host and live, with the staged frames of _host, in the scratch buffer of the calls above.  Results do not
+ * depend on frames_in_flight.  Profiler: class VOF_K_PREPROCESS, `level` 6.
+ * _dev: movie and out are device pointers (out must not alias movie); _host: host pointers, staged through the context's
+ * pinned bounce buffer. */
+enum vof_resize_arithmetic { VOF_RESIZE_U8 = 0, VOF_RESIZE_F64 = 1 };
+int vof_resize_area_dev(vof_ctx* ctx, const double* movie, int n_frames, int out_i, int out_j, int arithmetic,
+                        int frames_in_flight, double* out);
+int vof_resize_area_host(vof_ctx* ctx, const double* movie, int n_frames, int out_i, int out_j, int arithmetic,
+                         int frames_in_flight, double* out);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

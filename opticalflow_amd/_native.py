@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("VOF_LIB") or os.path.join(HERE, "csrc", "libvof.so")
 
 K_NAMES = ["rhs", "apply0", "gs0", "gs", "residual", "restrict", "prolong", "galerkin0", "galerkin",
            "coarse_setup", "coarse_solve", "vector", "reduce", "finalize", "functionals", "coarse_tail", "preprocess"]
+RESIZE_U8, RESIZE_F64 = 0, 1         # enum vof_resize_arithmetic
 
 
 class VofParams(C.Structure):
@@ -110,6 +111,8 @@ SIGNATURES = {
     "vof_adaptive_threshold_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _dp]),
     "vof_clahe_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _dp]),
     "vof_clahe_host": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _dp]),
+    "vof_resize_area_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "vof_resize_area_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -574,6 +577,26 @@ class Solver:
     def clahe_dev(self, movie, out, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight=0):
         """The same on device memory: float64 frames in and out (``out`` must not alias ``movie``)."""
         self._preprocess("vof_clahe_dev", movie, n_frames, (float(clip_limit), int(tiles_x), int(tiles_y)), frames_in_flight, out)
+
+    def _resize_area(self, fn, movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out):
+        """``vof_resize_area_*``; return code 1 (uint8 arithmetic asked for a stack that holds other values) is a ValueError."""
+        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), int(out_i), int(out_j), int(arithmetic), int(frames_in_flight), _ptr(out))
+        if rc == 1:
+            raise ValueError(self.lib.vof_last_error(self.h).decode())
+        self._check(rc, fn)
+
+    def resize_area_host(self, movie: np.ndarray, out_i, out_j, arithmetic, frames_in_flight=0):
+        """``cv2.resize(frame, (out_j, out_i), interpolation=cv2.INTER_AREA)`` of every frame of a host movie (read as float64)
+        in the arithmetic OpenCV applies to uint8 (``RESIZE_U8``) or float64 (``RESIZE_F64``) frames: float64 ``(T, out_i, out_j)``."""
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        out = np.empty((movie.shape[0], int(out_i), int(out_j)), dtype=np.float64)
+        self._resize_area("vof_resize_area_host", movie, movie.shape[0], out_i, out_j, arithmetic, frames_in_flight, out)
+        return out
+
+    def resize_area_dev(self, movie, out, n_frames, out_i, out_j, arithmetic, frames_in_flight=0):
+        """The same on device memory: float64 frames in, float64 ``(n_frames, out_i, out_j)`` out (``out`` must not alias ``movie``)."""
+        self._resize_area("vof_resize_area_dev", movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out)
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

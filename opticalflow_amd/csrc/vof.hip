@@ -17,6 +17,7 @@
 #include "vof_compare.hpp"
 #include "vof_liushen.hpp"
 #include "vof_preprocess.hpp"
+#include "vof_resize.hpp"
 #include "../../include/vof.h"
 
 #include <fcntl.h>
@@ -24,6 +25,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -121,7 +123,7 @@ struct vof_ctx {
     bool sw_by_budget = false;                                           // sw_scratch was sized by the free memory, not by the request
     char* sw_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
     size_t sw_aux_bytes = 0;
-    char* pre_buf = nullptr;                                             // adaptive threshold / CLAHE: partials, row sums or histograms and tables, staged frames (lazy; pre_plan)
+    char* pre_buf = nullptr;                                             // adaptive threshold / CLAHE / resize: partials, row sums | histograms and tables | axis tables, staged frames (lazy; pre_plan)
     size_t pre_bytes = 0;
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
     bool bl_lds_set = false;                                             // tiled blur: dynamic LDS limit raised
@@ -4528,6 +4530,140 @@ int vof_clahe_dev(vof_ctx* c, const double* movie, int n_frames, double clip_lim
 int vof_clahe_host(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int frames_in_flight,
                    double* out, double* range) {
     return clahe_impl(c, movie, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight, out, range, true);
+}
+
+// ---- INTER_AREA downsampling (downsample_movie; vof_resize.hpp) --------------------------------------------------------------
+// One axis of cv2.resize's INTER_AREA: the two roundings of the scale, and computeResizeAreaTab in C++ double exactly as OpenCV
+// writes it; the entries of an output index are consecutive source indices, so (first index, count, weights) holds them.
+struct ResizeAxis {
+    double scale = 1.0;
+    int iscale = 1, kmax = 0;
+    std::vector<int> start, count;
+    std::vector<float> w;                  // [d * kmax + k]
+};
+
+static void resize_axis_scale(int ssize, int dsize, ResizeAxis* t) {
+    const double inv = (double)dsize / (double)ssize;
+    t->scale = 1.0 / inv;
+    t->iscale = (int)t->scale;
+}
+
+static bool resize_axis_table(int ssize, int dsize, ResizeAxis* t) {
+#pragma clang fp contract(off)
+    const double scale = t->scale;
+    std::vector<std::vector<float>> ws((size_t)dsize);
+    t->start.assign((size_t)dsize, 0);
+    t->count.assign((size_t)dsize, 0);
+    t->kmax = 0;
+    int prev_start = 0, prev_end = 0;
+    for (int d = 0; d < dsize; ++d) {
+        const double f1 = d * scale;
+        const double f2 = f1 + scale;
+        const double cw = std::min(scale, ssize - f1);
+        int s1 = (int)std::ceil(f1);
+        const int s2 = std::min((int)std::floor(f2), ssize - 1);
+        s1 = std::min(s1, s2);
+        std::vector<float>& w = ws[(size_t)d];
+        int first = s1;
+        if (s1 - f1 > 1e-3) { first = s1 - 1; w.push_back((float)((s1 - f1) / cw)); }
+        for (int s = s1; s < s2; ++s) w.push_back((float)(1.0 / cw));
+        if (f2 - s2 > 1e-3) {
+            if (w.empty()) first = s2;
+            w.push_back((float)(std::min(std::min(f2 - s2, 1.0), cw) / cw));
+        }
+        const int n = (int)w.size(), end = first + n;
+        // what the kernel's staging relies on: a non-empty run inside the row, runs that move right with d
+        if (n < 1 || first < 0 || end > ssize || first < prev_start || end < prev_end) return false;
+        prev_start = first; prev_end = end;
+        t->start[(size_t)d] = first; t->count[(size_t)d] = n;
+        t->kmax = std::max(t->kmax, n);
+    }
+    t->w.assign((size_t)dsize * t->kmax, 0.0f);
+    for (int d = 0; d < dsize; ++d) std::copy(ws[(size_t)d].begin(), ws[(size_t)d].end(), t->w.begin() + (size_t)d * t->kmax);
+    return true;
+}
+
+static int resize_area_impl(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int flight, double* out,
+                            bool host) {
+    if (!c) return -1;
+    if (!movie || !out) { c->err = "NULL pointer"; return -1; }
+    if (n_frames < 1) { c->err = "n_frames must be >= 1"; return -1; }
+    if (arithmetic != VOF_RESIZE_U8 && arithmetic != VOF_RESIZE_F64) { c->err = "resize: arithmetic must be VOF_RESIZE_U8 or VOF_RESIZE_F64"; return -1; }
+    if (out_i < 1 || out_i > c->Ni || out_j < 1 || out_j > c->Nj) {
+        c->err = "resize: 1 <= out_i <= n_i and 1 <= out_j <= n_j are required (downsampling only)"; return -1;
+    }
+    if (out_i > 65535) { c->err = "resize: out_i must be <= 65535"; return -1; }
+    const bool u8 = arithmetic == VOF_RESIZE_U8;
+    ResizeAxis ty, tx;
+    resize_axis_scale(c->Ni, out_i, &ty);
+    resize_axis_scale(c->Nj, out_j, &tx);
+    const bool fast = std::fabs(tx.scale - tx.iscale) < DBL_EPSILON && std::fabs(ty.scale - ty.iscale) < DBL_EPSILON;
+    std::vector<uint32_t> tab;                                          // start_y, count_y, start_x, count_x, w_y, w_x
+    if (fast) {
+        if ((long long)ty.iscale * out_i != c->Ni || (long long)tx.iscale * out_j != c->Nj) { c->err = "internal: resize scales"; return -1; }
+        if ((long long)ty.iscale * tx.iscale > 0x7FFFFFFFLL / 255) { c->err = "resize: more than 2^23 source pixels per output pixel"; return -1; }
+    } else {
+        if (!resize_axis_table(c->Ni, out_i, &ty) || !resize_axis_table(c->Nj, out_j, &tx)) { c->err = "internal: resize table"; return -1; }
+        tab.resize(2 * (size_t)out_i + 2 * (size_t)out_j + ty.w.size() + tx.w.size());
+        uint32_t* q = tab.data();
+        for (const ResizeAxis* t : {&ty, &tx}) {
+            memcpy(q, t->start.data(), t->start.size() * 4); q += t->start.size();
+            memcpy(q, t->count.data(), t->count.size() * 4); q += t->count.size();
+        }
+        memcpy(q, ty.w.data(), ty.w.size() * 4); q += ty.w.size();
+        memcpy(q, tx.w.data(), tx.w.size() * 4);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const size_t os = (size_t)out_i * out_j, ob = os * sizeof(double);
+    PrePlan p;
+    if (int rc = pre_plan(c, n_frames, flight, up256(tab.size() * 4 + 4), 0, ob, host, "resize", &p)) return rc;
+    if (u8) {
+        double rg[3];
+        if (int rc = pre_range(c, p, movie, n_frames, host, rg)) return rc;
+        if (rg[2] > 0) { c->err = "resize: the movie holds non-finite values (uint8 arithmetic)"; return 1; }
+        if (rg[1] < 0 || rg[0] > 255.0) { c->err = "resize: the movie holds values outside 0 .. 255 (uint8 arithmetic)"; return 1; }
+    }
+    RsAxis ay{}, ax{};
+    if (!fast) {
+        if (int rc = h2d_bounced(c, p.work_a, tab.data(), tab.size() * 4)) return rc;
+        const int* q = (const int*)p.work_a;
+        ay.start = q; ay.count = q + out_i; ax.start = q + 2 * (size_t)out_i; ax.count = ax.start + out_j;
+        ay.w = (const float*)(ax.count + out_j); ax.w = ay.w + ty.w.size();
+        ay.kmax = ty.kmax; ax.kmax = tx.kmax;
+    }
+    const float scale_f = 1.0f / (float)(tx.iscale * ty.iscale);
+    const int half_up = tx.iscale == 2 && ty.iscale == 2;
+    for (int k0 = 0; k0 < n_frames; k0 += p.cap) {
+        const int nf = std::min(p.cap, n_frames - k0);
+        const double* src = movie + (size_t)k0 * fs;
+        if (host) {
+            // U8: the range reduction has left its last chunk staged - the whole stack if it is one chunk
+            if (!u8 || n_frames > p.cap) if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fb)) return rc;
+            src = p.in;
+        }
+        double* dst = host ? (double*)p.out : out + (size_t)k0 * os;
+        c->cur_units = nf;
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_RESIZE, 8.0 * fs + 8.0 * os);
+            const dim3 grid((out_j + RS_BLOCK - 1) / RS_BLOCK, out_i, nf);
+            if (fast && u8) k_rs_fast<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, half_up, dst);
+            else if (fast) k_rs_fast<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, 0, dst);
+            else if (u8) k_rs_area<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
+            else k_rs_area<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
+        }
+        HIPCHK(hipGetLastError());
+        if (host) if (int rc = d2h_bounced(c, out + (size_t)k0 * os, dst, (size_t)nf * ob)) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vof_resize_area_dev(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int frames_in_flight, double* out) {
+    return resize_area_impl(c, movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out, false);
+}
+int vof_resize_area_host(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int frames_in_flight, double* out) {
+    return resize_area_impl(c, movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out, true);
 }
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------

@@ -18,7 +18,7 @@ constexpr int PP_BINS = 65536;            // CLAHE: histSize of a 16-bit image
 constexpr int PP_LUT_STEP = 4 * PP_BLOCK; // bins a workgroup of k_pp_lut takes per iteration (4 per lane)
 
 // profiler stages of VOF_K_PREPROCESS (the `level` of vof_profile_get)
-enum { PP_ST_RANGE = 0, PP_ST_ROWSUM, PP_ST_THRESHOLD, PP_ST_HIST, PP_ST_LUT, PP_ST_BLEND };
+enum { PP_ST_RANGE = 0, PP_ST_ROWSUM, PP_ST_THRESHOLD, PP_ST_HIST, PP_ST_LUT, PP_ST_BLEND, PP_ST_RESIZE };
 
 struct PpRange { double vmax, vmin; unsigned long long bad; };   // of the finite values; bad: NaN / Inf count
 

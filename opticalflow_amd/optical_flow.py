@@ -65,7 +65,7 @@ atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
-           "apply_adaptive_threshold", "apply_clahe",
+           "apply_adaptive_threshold", "apply_clahe", "downsample_movie",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -128,8 +128,9 @@ def _preprocess_shape(movie, output):
     return shape
 
 
-def _run_preprocess(movie, shape, device, output, result_dtype, host_call, dev_call):
-    """The frames as float64 on the side ``output`` names, through the cached context, to one of the native calls."""
+def _run_preprocess(movie, shape, device, output, result_dtype, host_call, dev_call, out_shape=None):
+    """The frames as float64 on the side ``output`` names, through the cached context, to one of the native calls; the result
+    has the movie's shape unless ``out_shape`` names another."""
     T, N_i, N_j = shape
     if output == "numpy":
         frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
@@ -138,7 +139,7 @@ def _run_preprocess(movie, shape, device, output, result_dtype, host_call, dev_c
     import torch
     dev = torch.device("cuda", int(device))
     frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
-    out = torch.empty(shape, dtype=result_dtype(torch), device=dev)
+    out = torch.empty(out_shape or shape, dtype=result_dtype(torch), device=dev)
     with _device_context(N_i, N_j, 1, device) as solver:
         torch.cuda.synchronize(dev)                  # the library launches on its own stream
         dev_call(solver, frames, out, T)
@@ -220,6 +221,54 @@ def apply_clahe(movie, clipLimit=50000, tile_number=10, *, device=0, output="num
     return _run_preprocess(movie, shape, device, output, lambda torch: torch.float64,
                            lambda solver, frames: solver.clahe_host(frames, clip, tiles_x, tiles_y),
                            lambda solver, frames, out, T: solver.clahe_dev(frames, out, T, clip, tiles_x, tiles_y))
+
+
+def _movie_dtype_name(movie):
+    """'uint8', 'float64', ... of a numpy array, a torch tensor or anything ``np.asarray`` takes."""
+    dtype = movie.dtype if hasattr(movie, "dtype") else np.asarray(movie).dtype
+    return str(dtype).replace("torch.", "")
+
+
+def downsample_movie(movie, resolution, *, device=0, output="numpy"):
+    """OpenCV's area resize of every frame on the GPU: the loop of the reference's small-grid experiments
+    (analyse_variational_optical_flow.py:534-539, 625-630; analyse_short_timeinterval_data.py:754-759),
+
+        for k, frame in enumerate(movie):
+            downsampled[k] = cv2.resize(frame, dsize=(resolution, resolution), interpolation=cv2.INTER_AREA)
+
+    with ``downsampled`` a float64 array.  ``movie`` is ``(T, N_i, N_j)``; ``resolution`` is an int ``r`` - the result is
+    ``(T, r, r)`` whatever the aspect ratio, as in the scripts - or a pair ``(n_i, n_j)`` of output rows and columns.  The result
+    is float64 ``(T, n_i, n_j)``.
+
+    OpenCV's arithmetic depends on the depth of the frame, so the dtype of ``movie`` selects it and only the two depths the
+    scripts use are served: **uint8** (float32 sums, or integer block sums where both scales are integers, rounded to
+    0 .. 255) and **float64**.  Any other dtype raises ``ValueError``: cast the movie to the depth whose arithmetic is meant.
+    Restated from OpenCV 4's ``resize.cpp`` (``resizeArea_`` with the tables of ``computeResizeAreaTab``; ``resizeAreaFast_``
+    where ``N / n`` is an integer on both axes, with its half-up rounding of uint8 2 x 2 blocks and its unrolled float64
+    sums); DESIGN.md section 15 has every operation.  Parity with an installed ``cv2`` is tested only where one can be
+    imported (tests/test_resize_cv2_cpu.py).  A NaN or Inf of a float64 movie propagates as it does in OpenCV.
+
+    ``ValueError`` unless ``1 <= n_i <= N_i`` and ``1 <= n_j <= N_j`` - OpenCV takes another code path as soon as one axis is
+    enlarged, and that path is not built - and for frames smaller than 4 x 4 pixels, which the device context does not serve.
+    ``output="torch"``: ``movie`` may be a device tensor and the result is a float64 tensor on the device, ready for
+    ``variational_optical_flow(..., output="torch")``."""
+    shape = _preprocess_shape(movie, output)
+    name = _movie_dtype_name(movie)
+    if name not in ("uint8", "float64"):
+        raise ValueError(f"downsample_movie serves uint8 and float64 movies only (OpenCV's arithmetic differs by depth), not {name}: "
+                         "cast the movie to the depth whose arithmetic is meant")
+    pair = resolution if isinstance(resolution, (tuple, list)) else (resolution, resolution)
+    if len(pair) != 2 or any(isinstance(r, bool) or int(r) != r for r in pair):
+        raise ValueError("resolution must be an integer or a pair (n_i, n_j) of integers")
+    n_i, n_j = int(pair[0]), int(pair[1])
+    if not (1 <= n_i <= shape[1] and 1 <= n_j <= shape[2]):
+        raise ValueError(f"resolution {n_i} x {n_j} does not downsample frames of {shape[1]} x {shape[2]} pixels: "
+                         "1 <= n_i <= N_i and 1 <= n_j <= N_j are required")
+    arithmetic = _native.RESIZE_U8 if name == "uint8" else _native.RESIZE_F64
+    return _run_preprocess(movie, shape, device, output, lambda torch: torch.float64,
+                           lambda solver, frames: solver.resize_area_host(frames, n_i, n_j, arithmetic),
+                           lambda solver, frames, out, T: solver.resize_area_dev(frames, out, T, n_i, n_j, arithmetic),
+                           out_shape=(shape[0], n_i, n_j))
 
 
 def format_elapsed_time(time_difference):
