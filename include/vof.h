@@ -129,6 +129,15 @@ int vof_default_params(vof_params* p, size_t struct_size);
  *   VOF_FUSE_REVISIT=0         W-cycle: between two visits of the revisited stored level, the post-smoothing sweep of one visit and the
  *                              pre-smoothing sweep of the next as two launches (default: one pass over the level, k_sweep_st2; same bits,
  *                              tests/test_gpu_revisit_fusion.py)
+ *   VOF_GALERKIN_FAST=n        batch set-up, level-0 Galerkin product (k_galerkin); a bit mask, default 1.  0: one generic kernel (existence
+ *                              tests, ghost folds and weights at run time) for every coarse point.  bit 0: the coarse points away
+ *                              from the border by a kernel of their own (compile-time weights, raw blocks: the arithmetic these
+ *                              points had before) and the border frame by the generic kernel on a compact grid.  bit 1 (with
+ *                              bit 0, i.e. 3): that kernel evaluates the product in closed form (the image fields times
+ *                              compile-time coefficients).  Off by default: it takes a tenth off that kernel (0.4 ms of a 173 ms
+ *                              step) and moves the last bits of the level-1 stencils, with which an ill-conditioned regime's
+ *                              iteration counts shift by one (profiles/r20_galerkin_setup_summary.md section 5;
+ *                              tests/test_gpu_galerkin_setup.py checks both settings)
  *   VOF_FOLD_STORED=1          stored levels: coarse-grid correction interpolated inside the first post-sweep
  *   VOF_TRACE=1                direct preconditioner: progress lines on stderr
  * Read at every vof_solve_stack_dev call (speed only; per pair the same arithmetic, partial sums may add in another order):

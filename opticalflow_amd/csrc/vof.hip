@@ -154,6 +154,9 @@ struct vof_ctx {
                                 // kernel costs, so that one stays)
     bool fuse_revisit = true;   // VOF_FUSE_REVISIT=0: between two visits of the W-cycle's revisited level, the post-smoothing sweep of one
                                 // visit and the pre-smoothing sweep of the next as two k_sweep_st launches instead of one k_sweep_st2 pass
+    int galerkin_fast = 1;      // VOF_GALERKIN_FAST, level-0 Galerkin product.  bit 0: a kernel of its own for the coarse points away from
+                                // the border; bit 1 (with bit 0): that kernel evaluates the closed form (last bits differ; off by
+                                // default).  0: the generic kernel for every point
     // direct preconditioner (block-tridiagonal LU by image rows, vof_direct.hpp); buffers allocated on first use
     bool direct_on = false;          // the batch in solve_batch is preconditioned by the direct solver instead of the multigrid cycle
                                      // (BatchReq::direct; written by solve_batch alone)
@@ -1337,16 +1340,29 @@ int build_hierarchy(vof_ctx* c, int np) {
     int nl = (int)c->L.size();
     for (int l = 0; l + 1 < nl; ++l) {
         Level &f = c->L[l], &k = c->L[l + 1];
-        dim3 g = grid2d(k.ni, k.nj, np);
+        const dim3 g = grid2d(k.ni, k.nj, np);
         if (l == 0) {
             Prof p(c, VOF_K_GALERKIN0, 0);
-            CDISPATCH(c, 1, (k_galerkin<double, CT, true><<<g, blk2d, 0, c->stream>>>(
+            // the points away from the border by the interior kernel and the border frame by the generic one on a compact grid,
+            // or every point by the generic kernel (switched off, or no such point)
+            const GalerkinFrame frame(f.ni, f.nj, k.ni, k.nj);
+            const bool split = frame.any_interior() && (c->galerkin_fast & 1);
+            const dim3 gb = split ? dim3((frame.border_points(k.ni, k.nj) + NT - 1) / NT, 1, np) : g;
+            if (split && (c->galerkin_fast & 2))
+                CDISPATCH(c, 1, (k_galerkin<double, CT, true, true, true><<<g, blk2d, 0, c->stream>>>(
+                                     c->frames, frame_stride(c), c->Nj, P.speed_alpha, P.remodelling_alpha, P.reference_quirks,
+                                     nullptr, f.ni, f.nj, (CW*)k.C, k.ni, k.nj, c->pp, 0)));
+            else if (split)
+                CDISPATCH(c, 1, (k_galerkin<double, CT, true, true><<<g, blk2d, 0, c->stream>>>(
+                                     c->frames, frame_stride(c), c->Nj, P.speed_alpha, P.remodelling_alpha, P.reference_quirks,
+                                     nullptr, f.ni, f.nj, (CW*)k.C, k.ni, k.nj, c->pp, 0)));
+            CDISPATCH(c, 1, (k_galerkin<double, CT, true, false><<<gb, blk2d, 0, c->stream>>>(
                                  c->frames, frame_stride(c), c->Nj, P.speed_alpha, P.remodelling_alpha, P.reference_quirks,
-                                 nullptr, f.ni, f.nj, (CW*)k.C, k.ni, k.nj, c->pp)));
+                                 nullptr, f.ni, f.nj, (CW*)k.C, k.ni, k.nj, c->pp, split ? 1 : 0)));
         } else {
             Prof p(c, VOF_K_GALERKIN, l);
-            CDISPATCH(c, 1, (k_galerkin<CT, CT, false><<<g, blk2d, 0, c->stream>>>(
-                                 nullptr, 0, 0, 0.0, 0.0, 0, (const CW*)f.C, f.ni, f.nj, (CW*)k.C, k.ni, k.nj, nullptr)));
+            CDISPATCH(c, 1, (k_galerkin<CT, CT, false, false><<<g, blk2d, 0, c->stream>>>(
+                                 nullptr, 0, 0, 0.0, 0.0, 0, (const CW*)f.C, f.ni, f.nj, (CW*)k.C, k.ni, k.nj, nullptr, 0)));
         }
     }
     return 0;
@@ -2154,6 +2170,7 @@ static int create_impl(vof_ctx* c, int device_id, int n_i, int n_j, int B, void*
         if (const char* e = getenv("VOF_DEBUG_SYNC_FILE")) c->dbg_fd = open(e, O_WRONLY | O_CREAT, 0644);
     if (const char* e = getenv("VOF_FOLD_STORED")) c->fold_stored = e[0] != '0';
     if (const char* e = getenv("VOF_FUSE_REVISIT")) c->fuse_revisit = e[0] != '0';
+    if (const char* e = getenv("VOF_GALERKIN_FAST")) c->galerkin_fast = atoi(e) & 3;
     if (const char* e = getenv("VOF_L0_HANDOFF")) c->l0_handoff = e[0] != '0';
     if (const char* e = getenv("VOF_SWEEP0R_MIN_BLOCKS")) c->sweep0r_min_blocks = atol(e);
     if (const char* e = getenv("VOF_ACTIVE_LIST")) c->use_alist = e[0] != '0';

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include <utility>
 
 namespace vof {
 
@@ -219,8 +220,9 @@ __device__ __forceinline__ PixCoef pix_coef(const double* __restrict__ I, int Nj
 
 // blk[r*3+c] += scale * (raw 3x3 block of offset (oi, oj)), OF.py:843-960.
 // (T = double, or float with a PixCoefF: the level-0 Galerkin product of the 32-bit stencil formats)
+// (constexpr: the closed form of the level-0 Galerkin product below is checked against it at compile time)
 template <typename T, typename KT>
-__device__ __forceinline__ void add_raw_block(const KT& k, T alpha, T beta, int oi, int oj, T scale, T* blk) {
+__host__ __device__ __forceinline__ constexpr void add_raw_block(const KT& k, T alpha, T beta, int oi, int oj, T scale, T* blk) {
     const T P = k.P;
     if (oi == 0 && oj == 0) {
         blk[0] += scale * (P * (k.Dxx + -2 * P) - 4 * alpha);
@@ -262,6 +264,112 @@ __host__ __device__ constexpr unsigned raw_block_mask(int oi, int oj) {
          : (oi == 0)            ? 0x1BBu                 // {0, 1, 3, 4, 5, 7, 8}
                                 : 0x00Au;                // {1, 3}
 }
+
+// ------------------------------------------------------------------------------------------
+// The raw blocks as a linear form.  Every entry of a raw block is linear in nine per-pixel fields and the constants alpha, beta
+// and 1: raw_block_coef(m, oi, oj, t) is the coefficient of field m in entry t of the raw block of offset (oi, oj).  With it the
+// level-0 Galerkin product at a coarse point C away from the border (weights 1 and 1/2 only, no ghost folds) has the closed form
+//   4 A_c(C, C + (a, b))[t] = sum over f in 2C + {-1,0,1}^2 and fields m of  K[m][fi][fj][a][b][t] * phi_m(f),
+//   K[m][fi][fj][a][b][t]   = w(fi) w(fj) sum over (oi, oj) of raw_block_coef(m, oi, oj, t) w(fi + oi - 2a) w(fj + oj - 2b),
+// w(0) = 1, w(+-1) = 1/2, w = 0 elsewhere: the sum over g is done by the compiler.  552 of the 9 x 9 x 81 image terms are
+// non-zero (the +-s terms of the first derivatives cancel under equal weights; raw_block_mask); the alpha / beta / 1 part does
+// not depend on the image at all (36 coefficients on 27 of the 81 entries).  tests/test_galerkin_closed_form_cpu.py restates
+// this in numpy.
+// ------------------------------------------------------------------------------------------
+enum RawField { RF_PP, RF_PDX, RF_PDY, RF_PDXX, RF_PDYY, RF_PDXY, RF_P, RF_DX, RF_DY, RF_IMAGE /* = 9 image fields */,
+                RF_ALPHA = RF_IMAGE, RF_BETA, RF_ONE, RF_ALL };
+__host__ __device__ constexpr double raw_block_coef(int m, int oi, int oj, int t) {
+    if (oi == 0 && oj == 0) {
+        if (t == 0) return m == RF_PDXX ? 1 : m == RF_PP ? -2 : m == RF_ALPHA ? -4 : 0;
+        if (t == 1 || t == 3) return m == RF_PDXY ? 1 : 0;
+        if (t == 4) return m == RF_PDYY ? 1 : m == RF_PP ? -2 : m == RF_ALPHA ? -4 : 0;
+        if (t == 6) return m == RF_DX ? 1 : 0;
+        if (t == 7) return m == RF_DY ? 1 : 0;
+        if (t == 8) return m == RF_ONE ? -1 : m == RF_BETA ? -4 : 0;
+    } else if (oj == 0) {  // (+-1, 0)
+        const double s = oi;
+        if (t == 0) return m == RF_PDX ? s : (m == RF_PP || m == RF_ALPHA) ? 1 : 0;
+        if (t == 1 || t == 3) return m == RF_PDY ? s / 2 : 0;
+        if (t == 2) return m == RF_P ? -s / 2 : 0;
+        if (t == 4) return m == RF_ALPHA ? 1 : 0;
+        if (t == 6) return m == RF_P ? s / 2 : 0;
+        if (t == 8) return m == RF_BETA ? 1 : 0;
+    } else if (oi == 0) {  // (0, +-1)
+        const double s = oj;
+        if (t == 0) return m == RF_ALPHA ? 1 : 0;
+        if (t == 1 || t == 3) return m == RF_PDX ? s / 2 : 0;
+        if (t == 4) return m == RF_PDY ? s : (m == RF_PP || m == RF_ALPHA) ? 1 : 0;
+        if (t == 5) return m == RF_P ? -s / 2 : 0;
+        if (t == 7) return m == RF_P ? s / 2 : 0;
+        if (t == 8) return m == RF_BETA ? 1 : 0;
+    } else {               // diagonals
+        if (t == 1 || t == 3) return m == RF_PP ? (double)(oi * oj) / 4 : 0;
+    }
+    return 0;
+}
+// the fields of one pixel, in the order of RawField
+template <typename T, typename KT>
+__host__ __device__ __forceinline__ constexpr void raw_fields(const KT& k, T* phi) {
+    const T P = k.P;
+    phi[RF_PP] = P * P; phi[RF_PDX] = P * k.Dx; phi[RF_PDY] = P * k.Dy; phi[RF_PDXX] = P * k.Dxx; phi[RF_PDYY] = P * k.Dyy;
+    phi[RF_PDXY] = P * k.Dxy; phi[RF_P] = P; phi[RF_DX] = k.Dx; phi[RF_DY] = k.Dy;
+}
+// raw_block_coef against add_raw_block at one set of values (small integers: every product and sum is exact)
+__host__ __device__ constexpr bool raw_block_coef_matches(const PixCoef& k, double alpha, double beta) {
+    double phi[RF_ALL] = {};
+    raw_fields(k, phi);
+    phi[RF_ALPHA] = alpha; phi[RF_BETA] = beta; phi[RF_ONE] = 1;
+    for (int oi = -1; oi <= 1; ++oi)
+        for (int oj = -1; oj <= 1; ++oj) {
+            double blk[9] = {};
+            add_raw_block(k, alpha, beta, oi, oj, 1.0, blk);
+            for (int t = 0; t < 9; ++t) {
+                double v = 0;
+                bool any = false;
+                for (int m = 0; m < RF_ALL; ++m) {
+                    const double s = raw_block_coef(m, oi, oj, t);
+                    any = any || s != 0;
+                    v += s * phi[m];
+                }
+                if (v != blk[t]) return false;
+                if (any != (((raw_block_mask(oi, oj) >> t) & 1u) != 0)) return false;   // the pattern is raw_block_mask
+            }
+        }
+    return true;
+}
+static_assert(raw_block_coef_matches(PixCoef{3, 5, 7, 11, 13, 17}, 19, 23), "raw_block_coef is not add_raw_block");
+static_assert(raw_block_coef_matches(PixCoef{0, 0, 0, 0, 0, 0}, 19, 23), "constant terms of raw_block_coef are not those of add_raw_block");
+static_assert(raw_block_coef_matches(PixCoef{0, 0, 0, 0, 0, 0}, 0, 0), "the 1 part of raw_block_coef is not that of add_raw_block");
+
+struct GalerkinClosedForm {
+    double k[RF_ALL][3][3][9][9];   // [m][fi + 1][fj + 1][d = (a + 1) * 3 + (b + 1)][t]
+    double c[3][9][9];              // alpha / beta / 1 part of an interior point: the sum of k over the nine fine points
+};
+__host__ __device__ constexpr double galerkin_w(int d) { return d == 0 ? 1.0 : ((d == 1 || d == -1) ? 0.5 : 0.0); }
+__host__ __device__ constexpr GalerkinClosedForm make_galerkin_closed_form() {
+    GalerkinClosedForm K = {};
+    for (int oi = -1; oi <= 1; ++oi)
+        for (int oj = -1; oj <= 1; ++oj)
+            for (int t = 0; t < 9; ++t)
+                for (int m = 0; m < RF_ALL; ++m) {
+                    const double s = raw_block_coef(m, oi, oj, t);
+                    if (s == 0) continue;
+                    for (int fi = -1; fi <= 1; ++fi)
+                        for (int fj = -1; fj <= 1; ++fj)
+                            for (int a = -1; a <= 1; ++a)
+                                for (int b = -1; b <= 1; ++b) {
+                                    const double w = galerkin_w(fi) * galerkin_w(fj) * galerkin_w(fi + oi - 2 * a) * galerkin_w(fj + oj - 2 * b);
+                                    K.k[m][fi + 1][fj + 1][(a + 1) * 3 + (b + 1)][t] += w * s;
+                                    if (m >= RF_IMAGE) K.c[m - RF_IMAGE][(a + 1) * 3 + (b + 1)][t] += w * s;
+                                }
+                }
+    return K;
+}
+// compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // Folded block of offset (oi, oj) at interior point (p, q): the ghost couplings are added onto the
 // interior point they mirror to.  The target (p+oi, q+oj) must be inside the grid.
@@ -840,16 +948,62 @@ __global__ __launch_bounds__(NT, (ResuBudget<CT, VT, HAS_OLD>::kMinWaves)) void 
 // <= 4 coarse neighbours whose prolongation column contains g; the 81 x 9 accumulators live in registers (all
 // loops are fully unrolled, so their indices are compile-time).  With the colour-split plane layout the lanes
 // of a wave (consecutive coarse columns) read consecutive elements of one fine colour sub-plane.
+// Coarse points away from the border (all but a frame of one or two points) have no existence test, ghost fold or orphan
+// weight to make: every prolongation weight is a compile-time 1 or 1/2.  On level 0 they have a kernel of their own (FAST):
+// the generic loops with constant weights and raw blocks, in the generic order.  Or (CLOSED, an instantiation of its own: both
+// in one kernel take 227 registers, two waves per SIMD instead of three) the closed form (GalerkinClosedForm above) - the nine
+// fields of each of the nine fine points times compile-time coefficients, on accumulators that start at the alpha / beta / 1
+// part.  No blocks are formed; the terms of an entry are added in another order than by the loops, so the last bits of the
+// accumulator type differ.
+// The generic kernel (FAST = false) then serves the border frame alone, on a compact 1-D grid (border_only != 0), or every
+// point on the 2-D grid (VOF_GALERKIN_FAST=0, and the stored levels).  Two kernels instead of two paths in one: with both in
+// one kernel a quarter of the waves (those with a lane in the first or last column) ran through both, and the code of the two
+// did not fit the instruction cache together.
 // ------------------------------------------------------------------------------------------
-template <typename CTF, typename CTC, bool LEVEL0>
+inline constexpr GalerkinClosedForm kGalerkinClosedForm = make_galerkin_closed_form();
+// The interior coarse points are 1 <= cp <= pi, 1 <= cq <= qi (none if either bound is < 1); the border frame is what is left.
+struct GalerkinFrame {
+    int pi, qi;
+    __host__ __device__ GalerkinFrame(int nfi, int nfj, int nci, int ncj) {
+        const int a = nfi >= 3 ? (nfi - 3) / 2 : 0, b = nfj >= 3 ? (nfj - 3) / 2 : 0;
+        pi = nci - 2 < a ? nci - 2 : a;
+        qi = ncj - 2 < b ? ncj - 2 : b;
+        if (pi < 1 || qi < 1) pi = qi = 0;
+    }
+    __host__ __device__ bool any_interior() const { return pi >= 1; }
+    __host__ __device__ bool interior(int cp, int cq) const { return cp >= 1 && cp <= pi && cq >= 1 && cq <= qi; }
+    // border points: the rows 0 and pi + 1 .. nci - 1 in full, then the columns 0 and qi + 1 .. ncj - 1 of the rows 1 .. pi
+    __host__ __device__ int border_points(int nci, int ncj) const { return (nci - pi) * ncj + pi * (ncj - qi); }
+    __host__ __device__ void border_point(int t, int nci, int ncj, int& cp, int& cq) const {
+        const int rows = (nci - pi) * ncj;
+        if (t < rows) {
+            const int r = t / ncj;
+            cq = t - r * ncj;
+            cp = r == 0 ? 0 : pi + r;
+        } else {
+            const int cols = ncj - qi, u = t - rows, r = u / cols, c = u - r * cols;
+            cp = 1 + r;
+            cq = c == 0 ? 0 : qi + c;
+        }
+    }
+};
+template <typename CTF, typename CTC, bool LEVEL0, bool FAST, bool CLOSED = false>
 __global__ __launch_bounds__(NT) void k_galerkin(const double* __restrict__ frames, size_t frame_stride, int Nj,
                                                  double alpha, double beta, int quirks,
                                                  const typename CoefFmt<CTF>::word_t* __restrict__ Cf, int nfi, int nfj,
                                                  typename CoefFmt<CTC>::word_t* __restrict__ Cc, int nci, int ncj,
-                                                 const PairParam* __restrict__ pp) {
+                                                 const PairParam* __restrict__ pp, const int border_only) {
+    static_assert((LEVEL0 || !FAST) && (FAST || !CLOSED), "the interior kernel exists for level 0 only, the closed form in it only");
     int cq = blockIdx.x * BX + threadIdx.x, cp = blockIdx.y * BY + threadIdx.y;
     int pair = blockIdx.z;
+    const GalerkinFrame frame(nfi, nfj, nci, ncj);
+    if (!FAST && border_only) {
+        const int t = blockIdx.x * NT + threadIdx.y * BX + threadIdx.x;
+        if (t >= frame.border_points(nci, ncj)) return;
+        frame.border_point(t, nci, ncj, cp, cq);
+    }
     if (cp >= nci || cq >= ncj) return;
+    if (FAST && !frame.interior(cp, cq)) return;
     int fidx = pair;
     if (LEVEL0 && pp) { alpha = pp[pair].alpha; beta = pp[pair].beta; fidx = pp[pair].frame; }
     const CLay Lf(nfi, nfj), Lc(nci, ncj);
@@ -864,10 +1018,7 @@ __global__ __launch_bounds__(NT) void k_galerkin(const double* __restrict__ fram
     for (int d = 0; d < 9; ++d)
 #pragma unroll
         for (int t = 0; t < 9; ++t) acc[d][t] = (AT)0;
-    // Coarse points away from the border (all but a frame of one or two points) take a path without any of the existence
-    // tests, ghost folds and orphan weights: every prolongation weight is then a compile-time constant (1 or 1/2 per
-    // direction), every loop bound is static and the fine blocks are the raw ones.
-    const bool interior = cp >= 1 && cp + 1 < nci && 2 * cp + 1 <= nfi - 2 && cq >= 1 && cq + 1 < ncj && 2 * cq + 1 <= nfj - 2;
+    // IN (the interior kernel of level 0): constant weights, no tests, raw blocks
     auto accumulate = [&](auto interior_tag) {
         constexpr bool IN = decltype(interior_tag)::value;
 #pragma unroll
@@ -937,10 +1088,29 @@ __global__ __launch_bounds__(NT) void k_galerkin(const double* __restrict__ fram
             }
         }
     };
-    // (level 0 only: on the stored levels the compiler hoists the stencil loads of all nine fine points out of the straight-line
-    // path - 256 registers + spills)
-    if constexpr (LEVEL0) {
-        if (interior) accumulate(std::true_type{}); else accumulate(std::false_type{});
+    // level 0, interior: the closed form.  The image derivatives are float64 as in pix_coef; the fields and the sums follow AT.
+    auto closed_form = [&](auto) {   // (generic: instantiated by the CLOSED kernels alone)
+        const AT al = (AT)alpha, be = (AT)beta;
+        static_for<81>([&](auto E) {
+            constexpr int e = decltype(E)::value;
+            constexpr double ka = kGalerkinClosedForm.c[0][e / 9][e % 9], kb = kGalerkinClosedForm.c[1][e / 9][e % 9], k1 = kGalerkinClosedForm.c[2][e / 9][e % 9];
+            if constexpr (ka != 0.0 || kb != 0.0 || k1 != 0.0) acc[e / 9][e % 9] = al * (AT)ka + be * (AT)kb + (AT)k1;
+        });
+        static_for<9>([&](auto F) {
+            constexpr int fi = decltype(F)::value / 3, fj = decltype(F)::value % 3;
+            const PixCoef k = pix_coef(frames + (size_t)fidx * frame_stride, Nj, 2 * cp + fi - 1, 2 * cq + fj - 1, quirks);
+            AT phi[RF_IMAGE];
+            if constexpr (std::is_same<AT, float>::value) raw_fields(PixCoefF(k), phi);
+            else raw_fields(k, phi);
+            static_for<81 * RF_IMAGE>([&](auto X) {
+                constexpr int m = decltype(X)::value % RF_IMAGE, e = decltype(X)::value / RF_IMAGE;
+                constexpr double kv = kGalerkinClosedForm.k[m][decltype(F)::value / 3][decltype(F)::value % 3][e / 9][e % 9];
+                if constexpr (kv != 0.0) acc[e / 9][e % 9] += (AT)kv * phi[m];
+            });
+        });
+    };
+    if constexpr (FAST) {
+        if constexpr (CLOSED) closed_form(0); else accumulate(std::true_type{});
     } else {
         accumulate(std::false_type{});
     }
