@@ -468,6 +468,37 @@ int vof_resize_area_dev(vof_ctx* ctx, const double* movie, int n_frames, int out
 int vof_resize_area_host(vof_ctx* ctx, const double* movie, int n_frames, int out_i, int out_j, int arithmetic,
                          int frames_in_flight, double* out);
 
+/* Farnebaeck's dense flow of n_pairs frame pairs, cv2.calcOpticalFlowFarneback(first[k], second[k], None, pyr_scale, levels,
+ * winsize, iterations, poly_n, poly_sigma, OPTFLOW_FARNEBACK_GAUSSIAN) without an initial flow, OpenCV 4's arithmetic restated
+ * operation by operation in float32 and, where OpenCV uses it, double (DESIGN.md section 16 has the specification; parity
+ * with the real cv2 is not tested in this repository).  first and second are two stacks of n_pairs frames of n_i x n_j
+ * float64 each and may be two views of one movie (second = first + n_i * n_j).  Everything that needs an exp is planned by the
+ * caller (farneback_plan of the Python package) and arrives as host arrays:
+ *   n_levels, level_sizes[2 * n_levels]   (height, width) of the pyramid's images, finest first; level 0 is (n_i, n_j)
+ *   ksizes[n_levels], presmooth_taps      the odd tap counts of the blur that precedes the resize to a level, and the taps of
+ *                                         all levels one after the other (float32)
+ *   poly_n, poly_tables, poly_ig          1 .. 10; g | xg | xxg, 2 poly_n + 1 float32 each (offsets -poly_n .. poly_n); the
+ *                                         four entries (1,1), (0,3), (3,3), (5,5) of the inverse moment matrix
+ *   winsize, window_taps                  1 .. 129; the winsize / 2 + 1 float32 taps k[0 ..] of the Gaussian window
+ *   iterations, flow_scale                >= 0; float32(1 / pyr_scale), applied to the flow carried to the next finer level
+ *   velocity_scale                        delta_x / delta_t
+ * Results: v_x = channel 0 of OpenCV's flow (along n_j), v_y = channel 1 (along n_i), promoted to float64 and multiplied by
+ * velocity_scale, and speed = sqrt(v_x^2 + v_y^2); n_pairs x n_i x n_j each.  Both stacks are first reduced as in the
+ * preprocessing calls above: a non-finite value returns 1, nothing else computed, vof_last_error says why.
+ * Pairs are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most; 108 bytes of scratch per
+ * pixel and pair in flight, in the scratch buffer of the calls above).  Results do not depend on frames_in_flight.
+ * Frames of at least 16 x 16.  Profiler: class VOF_K_PREPROCESS, `level` 7 level images, 8 polynomial expansion, 9 flow carried
+ * to a level, 10 matrices, 11 window rows (vertical pass), 12 window columns + solve + update, 13 results.
+ * _dev: the stacks and the results are device pointers; _host: host pointers, staged through the pinned bounce buffer. */
+int vof_farneback_dev(vof_ctx* ctx, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes,
+                      const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
+                      int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale,
+                      int frames_in_flight, double* v_x, double* v_y, double* speed);
+int vof_farneback_host(vof_ctx* ctx, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes,
+                       const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
+                       int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale,
+                       int frames_in_flight, double* v_x, double* v_y, double* speed);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

@@ -18,6 +18,7 @@
 #include "vof_liushen.hpp"
 #include "vof_preprocess.hpp"
 #include "vof_resize.hpp"
+#include "vof_farneback.hpp"
 #include "../../include/vof.h"
 
 #include <fcntl.h>
@@ -4681,6 +4682,156 @@ int vof_resize_area_dev(vof_ctx* c, const double* movie, int n_frames, int out_i
 }
 int vof_resize_area_host(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int frames_in_flight, double* out) {
     return resize_area_impl(c, movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out, true);
+}
+
+// ---- Farnebaeck's dense flow (conduct_opencv_flow; vof_farneback.hpp) ---------------------------------------------------------
+// The float32 planes of one pair in flight, each n_i * n_j floats long whatever the level (a level's planes are compact at
+// the start of their slots): FB_PLANES in all.
+struct FbPair {
+    float *tmp_a, *tmp_b, *image, *R[2], *M, *V, *flow[2];
+    explicit FbPair(float* q, size_t fs) {
+        tmp_a = q; tmp_b = q + fs; image = q + 2 * fs; R[0] = q + 3 * fs; R[1] = q + 8 * fs; M = q + 13 * fs; V = q + 18 * fs;
+        flow[0] = q + 23 * fs; flow[1] = q + 25 * fs;
+    }
+};
+
+static int farneback_impl(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes,
+                          const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
+                          int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale, int flight,
+                          double* v_x, double* v_y, double* speed, bool host) {
+    if (!c) return -1;
+    if (!first || !second || !v_x || !v_y || !speed || !level_sizes || !ksizes || !presmooth_taps || !poly_tables || !poly_ig || !window_taps) {
+        c->err = "NULL pointer"; return -1;
+    }
+    if (n_pairs < 1) { c->err = "n_pairs must be >= 1"; return -1; }
+    if (c->Ni < 16 || c->Nj < 16) { c->err = "Farneback flow: frames must be at least 16 x 16"; return -1; }
+    if (n_levels < 1 || n_levels > 64) { c->err = "Farneback flow: 1 .. 64 pyramid images"; return -1; }
+    if (poly_n < 1 || poly_n > FB_MAX_POLY_N) { c->err = "Farneback flow: poly_n must be 1 .. " + std::to_string(FB_MAX_POLY_N); return -1; }
+    if (winsize < 1 || winsize > FB_MAX_WINSIZE) { c->err = "Farneback flow: winsize must be 1 .. " + std::to_string(FB_MAX_WINSIZE); return -1; }
+    if (iterations < 0) { c->err = "Farneback flow: iterations must be >= 0"; return -1; }
+    if (level_sizes[0] != c->Ni || level_sizes[1] != c->Nj) { c->err = "Farneback flow: level 0 must have the frame's size"; return -1; }
+    size_t n_taps = 0;
+    std::vector<size_t> tap_at((size_t)n_levels);
+    for (int k = 0; k < n_levels; ++k) {
+        const int h = level_sizes[2 * k], w = level_sizes[2 * k + 1];
+        if (h < 1 || w < 1 || h > c->Ni || w > c->Nj || h > 65535) { c->err = "Farneback flow: a level's size must be 1 .. the frame's (65535 rows at most)"; return -1; }
+        if (ksizes[k] < 1 || ksizes[k] % 2 == 0 || ksizes[k] > 65535) { c->err = "Farneback flow: a level's tap count must be odd"; return -1; }
+        tap_at[(size_t)k] = n_taps;
+        n_taps += (size_t)ksizes[k];
+    }
+    const int m = winsize / 2, poly_len = 3 * (2 * poly_n + 1);
+    std::vector<float> tab(n_taps + (size_t)poly_len + (size_t)m + 1);       // pre-smoothing taps | g, xg, xxg | window taps
+    memcpy(tab.data(), presmooth_taps, n_taps * sizeof(float));
+    memcpy(tab.data() + n_taps, poly_tables, (size_t)poly_len * sizeof(float));
+    memcpy(tab.data() + n_taps + poly_len, window_taps, ((size_t)m + 1) * sizeof(float));
+    const FbInvG ig{poly_ig[0], poly_ig[1], poly_ig[2], poly_ig[3]};
+    HIPCHK(hipSetDevice(c->device));
+    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const size_t pair_floats = (size_t)FB_PLANES * fs;
+    PrePlan p;
+    // work_a: the planes of the pairs in flight and, _host, the staged second images (the first ones are staged in p.in);
+    // work_b: the tables (a copy per pair in flight is reserved, one is used)
+    if (int rc = pre_plan(c, n_pairs, flight, up256(pair_floats * sizeof(float)) + (host ? up256(fb) : 0), up256(tab.size() * sizeof(float)), 3 * fb, host,
+                          "Farneback flow", &p)) return rc;
+    for (const double* stack : {first, second}) {
+        double rg[3];
+        if (int rc = pre_range(c, p, stack, n_pairs, host, rg)) return rc;
+        if (rg[2] > 0) { c->err = "Farneback flow: the movie holds non-finite values"; return 1; }
+    }
+    if (int rc = h2d_bounced(c, p.work_b, tab.data(), tab.size() * sizeof(float))) return rc;
+    const float* d_tab = (const float*)p.work_b;
+    const float *d_poly = d_tab + n_taps, *d_win = d_poly + poly_len;
+    float* planes = (float*)p.work_a;
+    double* stage2 = (double*)(p.work_a + (size_t)p.cap * up256(pair_floats * sizeof(float)));
+    const FbPair q(planes, fs);
+    const size_t ps = up256(pair_floats * sizeof(float)) / sizeof(float);      // floats from a pair's planes to the next pair's
+    const size_t vblur_lds = (size_t)(FB_VB_ROWS + 2 * m) * FB_VB_COLS * sizeof(float);
+    for (int k0 = 0; k0 < n_pairs; k0 += p.cap) {
+        const int nf = std::min(p.cap, n_pairs - k0);
+        const double* src[2] = {first + (size_t)k0 * fs, second + (size_t)k0 * fs};
+        if (host) {
+            if (int rc = h2d_bounced(c, p.in, src[0], (size_t)nf * fb)) return rc;
+            if (int rc = h2d_bounced(c, stage2, src[1], (size_t)nf * fb)) return rc;
+            src[0] = p.in; src[1] = stage2;
+        }
+        c->cur_units = nf;
+        int cur = 0;                                                            // q.flow[cur]: the flow of the level in progress
+        for (int lv = n_levels - 1; lv >= 0; --lv) {
+            const int h = level_sizes[2 * lv], w = level_sizes[2 * lv + 1], r = ksizes[lv] / 2;
+            const size_t hw = (size_t)h * w;
+            const float* d_w = d_tab + tap_at[(size_t)lv];
+            const dim3 full((c->Nj + FB_BLOCK - 1) / FB_BLOCK, c->Ni, nf), rows((w + FB_BLOCK - 1) / FB_BLOCK, h, nf);
+            for (int role = 0; role < 2; ++role) {
+                {
+                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_LEVEL, 8.0 * fs + 12.0 * fs + 4.0 * hw);
+                    k_fb_smooth<double, true><<<full, FB_BLOCK, 0, c->stream>>>(src[role], fs, c->Ni, c->Nj, d_w, r, q.tmp_a, ps);
+                    k_fb_smooth<float, false><<<full, FB_BLOCK, 0, c->stream>>>(q.tmp_a, ps, c->Ni, c->Nj, d_w, r, q.tmp_b, ps);
+                    k_fb_resize<false><<<rows, FB_BLOCK, 0, c->stream>>>(q.tmp_b, ps, c->Ni, c->Nj, q.image, ps, h, w, 1.0 / ((double)h / c->Ni),
+                                                                         1.0 / ((double)w / c->Nj), 1, 1.0f);
+                }
+                {
+                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_POLY, 24.0 * hw);
+                    k_fb_polyexp<<<rows, FB_BLOCK, 0, c->stream>>>(q.image, ps, h, w, poly_n, d_poly, ig, q.R[role], ps);
+                }
+            }
+            {
+                Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_FLOW, 8.0 * hw);
+                if (lv == n_levels - 1) {
+                    for (int k = 0; k < nf; ++k) HIPCHK(hipMemsetAsync(q.flow[cur] + (size_t)k * ps, 0, 2 * hw * sizeof(float), c->stream));
+                } else {
+                    const int sh = level_sizes[2 * lv + 2], sw = level_sizes[2 * lv + 3];
+                    k_fb_resize<true><<<dim3(rows.x, h, 2 * nf), FB_BLOCK, 0, c->stream>>>(q.flow[cur ^ 1], ps, sh, sw, q.flow[cur], ps, h, w,
+                                                                                         1.0 / ((double)h / sh), 1.0 / ((double)w / sw), 2, flow_scale);
+                }
+            }
+            if (iterations > 0) {
+                Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_MATRICES, 68.0 * hw);
+                k_fb_matrices<<<rows, FB_BLOCK, 0, c->stream>>>(q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w);
+            }
+            for (int it = 0; it < iterations; ++it) {
+                {
+                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_VBLUR, 40.0 * hw);
+                    k_fb_vblur<<<dim3((w + FB_VB_COLS - 1) / FB_VB_COLS, (h + FB_VB_ROWS - 1) / FB_VB_ROWS, 5 * nf), FB_BLOCK, vblur_lds, c->stream>>>(
+                        q.M, q.V, ps, h, w, m, d_win);
+                }
+                {
+                    const bool rebuild = it < iterations - 1;
+                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_UPDATE, (rebuild ? 88.0 : 28.0) * hw);
+                    k_fb_update<<<rows, FB_BLOCK, 0, c->stream>>>(q.V, q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w, m, d_win, rebuild ? 1 : 0);
+                }
+            }
+            HIPCHK(hipGetLastError());
+            cur ^= 1;
+        }
+        cur ^= 1;                                                               // the finished level 0
+        double* dst[3] = {v_x + (size_t)k0 * fs, v_y + (size_t)k0 * fs, speed + (size_t)k0 * fs};
+        if (host) for (int a = 0; a < 3; ++a) dst[a] = (double*)p.out + (size_t)a * p.cap * fs;
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_OUT, 32.0 * fs);
+            k_fb_output<<<dim3((unsigned)((fs + FB_BLOCK - 1) / FB_BLOCK), 1, nf), FB_BLOCK, 0, c->stream>>>(q.flow[cur], ps, fs, velocity_scale, dst[0], dst[1],
+                                                                                                            dst[2]);
+        }
+        HIPCHK(hipGetLastError());
+        if (host) {
+            double* res[3] = {v_x, v_y, speed};
+            for (int a = 0; a < 3; ++a) if (int rc = d2h_bounced(c, res[a] + (size_t)k0 * fs, dst[a], (size_t)nf * fb)) return rc;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vof_farneback_dev(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
+                      const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, const float* window_taps,
+                      int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
+    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, winsize, window_taps,
+                          iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, false);
+}
+int vof_farneback_host(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
+                       const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, const float* window_taps,
+                       int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
+    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, winsize, window_taps,
+                          iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, true);
 }
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------

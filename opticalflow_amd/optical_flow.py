@@ -65,7 +65,7 @@ atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
-           "apply_adaptive_threshold", "apply_clahe", "downsample_movie",
+           "apply_adaptive_threshold", "apply_clahe", "downsample_movie", "conduct_opencv_flow", "farneback_plan",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -92,6 +92,207 @@ def gaussian_taps(sigma, truncate=4.0):
     x = np.arange(-radius, radius + 1)
     phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
     return phi / phi.sum()
+
+
+FARNEBACK_ARGUMENTS = ("pyr_scale", "levels", "winsize", "iterations", "poly_n", "poly_sigma")
+FARNEBACK_MIN_SIDE = 16
+FARNEBACK_MAX_WINSIZE = 129          # FB_MAX_WINSIZE of csrc/vof_farneback.hpp: a row segment and its two margins live in LDS
+FARNEBACK_MAX_POLY_N = 10            # FB_MAX_POLY_N
+
+
+def _f32(value):
+    """A Python float rounded to float32 (and back: every float32 is a float)."""
+    return float(np.float32(value))
+
+
+def _left_to_right_sum(values):
+    total = 0.0
+    for v in values:
+        total += v
+    return total
+
+
+def _half_even(value):
+    """OpenCV's cvRound: to the nearest integer, ties to the even one - Python's round."""
+    return int(round(value))
+
+
+def farneback_plan(N_i, N_j, pyr_scale, levels, winsize, poly_n, poly_sigma):
+    """Everything ``cv2.calcOpticalFlowFarneback(..., flags=OPTFLOW_FARNEBACK_GAUSSIAN)`` derives from its arguments before it
+    touches a pixel, for frames of ``N_i`` x ``N_j``.  The native call takes these tables as arrays and
+    evaluates no ``exp`` itself; here every ``exp`` is ``math.exp`` of a Python float.  A dict:
+
+    ``sizes``           ``(height, width)`` of the pyramid's images, finest first: ``scale`` is multiplied by ``pyr_scale`` up to
+                        ``levels`` times and the loop stops as soon as a side times ``scale`` falls below 32; the ``k`` it has
+                        reached is the coarsest image, so ``levels`` scalings that all fit give ``levels + 1`` images
+    ``ksizes``, ``presmooth_taps``   per image the tap count ``max(cvRound(5 sigma) | 1, 3)`` with ``sigma = (1 / scale_k - 1) / 2``
+                        and the float32 taps of the Gaussian blur applied to the frame before it is resized to that image
+                        (``[0.25, 0.5, 0.25]`` at level 0)
+    ``g, xg, xxg``      the float32 tables of the polynomial expansion for the offsets ``-poly_n .. poly_n`` (``sigma = 0.3 poly_n``
+                        where ``poly_sigma < FLT_EPSILON``); ``G``, ``invG`` the 6 x 6 moment matrix and its inverse in float64,
+                        ``ig11, ig03, ig33, ig55`` the four entries of the inverse that are used
+    ``window_taps``     the ``winsize // 2 + 1`` float32 taps ``k[0 ..]`` of the Gaussian window (``sigma = 0.3 (winsize // 2)``)
+    ``flow_scale``      ``float32(1 / pyr_scale)``, applied to the flow carried from an image to the next finer one
+    and ``winsize``, ``poly_n`` as given."""
+    import math
+    pyr_scale, poly_sigma = float(pyr_scale), float(poly_sigma)
+    scale, coarsest = 1.0, 0
+    while coarsest < levels:
+        scale *= pyr_scale
+        if N_j * scale < 32 or N_i * scale < 32:
+            break
+        coarsest += 1
+    sizes, ksizes, presmooth = [], [], []
+    for k in range(coarsest + 1):
+        scale = 1.0
+        for _ in range(k):
+            scale *= pyr_scale
+        sigma = (1.0 / scale - 1) * 0.5
+        ksize = max(_half_even(sigma * 5) | 1, 3)
+        if ksize == 3 and sigma <= 0:
+            taps = [0.25, 0.5, 0.25]
+        else:
+            scale2x = -0.5 / (sigma * sigma)
+            raw = []
+            for i in range(ksize):
+                x = i - (ksize - 1) * 0.5
+                raw.append(math.exp(scale2x * x * x))
+            norm = 1.0 / _left_to_right_sum(raw)
+            taps = [t * norm for t in raw]
+        sizes.append((_half_even(N_i * scale), _half_even(N_j * scale)))
+        ksizes.append(ksize)
+        presmooth.append(np.array(taps, dtype=np.float64).astype(np.float32))
+    n = int(poly_n)
+    sigma = n * 0.3 if poly_sigma < float(np.finfo(np.float32).eps) else poly_sigma
+    offsets = list(range(-n, n + 1))
+    g = [_f32(math.exp(-x * x / (2 * sigma * sigma))) for x in offsets]
+    norm = 1.0 / _left_to_right_sum(g)
+    g = [_f32(v * norm) for v in g]
+    xg = [_f32(x * v) for x, v in zip(offsets, g)]
+    xxg = [_f32(x * x * v) for x, v in zip(offsets, g)]
+    G00 = G11 = G33 = G55 = 0.0
+    for y, gy in zip(offsets, g):
+        for x, gx in zip(offsets, g):
+            gg = gy * gx
+            G00 += gg
+            G11 += gg * x * x
+            G33 += gg * x * x * x * x
+            G55 += gg * x * x * y * y
+    G = np.zeros((6, 6), dtype=np.float64)
+    G[0, 0] = G00
+    for at in ((1, 1), (2, 2), (0, 3), (0, 4), (3, 0), (4, 0)):
+        G[at] = G11
+    G[3, 3] = G[4, 4] = G33
+    G[3, 4] = G[4, 3] = G[5, 5] = G55
+    invG = np.linalg.inv(G)
+    m = int(winsize) // 2
+    sigma = m * 0.3
+    window = [1.0] + [_f32(math.exp(-i * i / (2 * sigma * sigma))) for i in range(1, m + 1)]
+    total = 1.0
+    for v in window[1:]:
+        total += v * 2
+    norm = 1.0 / total
+    window = [v * norm for v in window]
+    as_f32 = lambda values: np.array(values, dtype=np.float64).astype(np.float32)
+    return dict(sizes=sizes, ksizes=ksizes, presmooth_taps=presmooth, g=as_f32(g), xg=as_f32(xg), xxg=as_f32(xxg), G=G, invG=invG,
+                ig11=float(invG[1, 1]), ig03=float(invG[0, 3]), ig33=float(invG[3, 3]), ig55=float(invG[5, 5]),
+                window_taps=as_f32(window), flow_scale=np.float32(1.0 / pyr_scale), winsize=int(winsize), poly_n=n)
+
+
+def _farneback_arguments(shape, kwargs):
+    """The six OpenCV arguments of ``conduct_opencv_flow`` checked as ``cv2`` checks their names (``TypeError``) and against the
+    limits of this build (``ValueError``), before the library is touched."""
+    if "flags" in kwargs:
+        raise TypeError("conduct_opencv_flow() passes flags=cv2.OPTFLOW_FARNEBACK_GAUSSIAN itself, as the reference does: "
+                        "got multiple values for argument 'flags'")
+    unknown = sorted(set(kwargs) - set(FARNEBACK_ARGUMENTS))
+    if unknown:
+        raise TypeError(f"conduct_opencv_flow() got an unexpected keyword argument {unknown[0]!r}")
+    missing = [name for name in FARNEBACK_ARGUMENTS if name not in kwargs]
+    if missing:
+        raise TypeError(f"conduct_opencv_flow() missing required argument {missing[0]!r} of cv2.calcOpticalFlowFarneback")
+    for name in ("levels", "winsize", "iterations", "poly_n"):
+        if isinstance(kwargs[name], bool) or int(kwargs[name]) != kwargs[name]:
+            raise TypeError(f"{name} must be an integer")
+    a = dict(pyr_scale=float(kwargs["pyr_scale"]), levels=int(kwargs["levels"]), winsize=int(kwargs["winsize"]),
+             iterations=int(kwargs["iterations"]), poly_n=int(kwargs["poly_n"]), poly_sigma=float(kwargs["poly_sigma"]))
+    if shape[1] < FARNEBACK_MIN_SIDE or shape[2] < FARNEBACK_MIN_SIDE:
+        raise ValueError(f"frames must be at least {FARNEBACK_MIN_SIDE} x {FARNEBACK_MIN_SIDE} pixels")
+    if not 0.0 < a["pyr_scale"] < 1.0:
+        raise ValueError("0 < pyr_scale < 1 is required")
+    if a["levels"] < 0:
+        raise ValueError("levels must be >= 0")
+    if not 1 <= a["winsize"] <= FARNEBACK_MAX_WINSIZE:
+        raise ValueError(f"winsize must be 1 .. {FARNEBACK_MAX_WINSIZE}")
+    if a["iterations"] < 0:
+        raise ValueError("iterations must be >= 0")
+    if not 1 <= a["poly_n"] <= FARNEBACK_MAX_POLY_N:
+        raise ValueError(f"poly_n must be 1 .. {FARNEBACK_MAX_POLY_N}")
+    if not np.isfinite(a["poly_sigma"]) or a["poly_sigma"] < 0:
+        raise ValueError("poly_sigma must be finite and >= 0")
+    return a
+
+
+def conduct_opencv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *, device=0, output="numpy", **kwargs):
+    """Farnebaeck's dense flow of every frame pair on the GPU; positional arguments and the result dict as
+    source/optical_flow.py:220-279, which calls ``cv2.calcOpticalFlowFarneback(blurred[k], movie[k + 1], ..., flags=
+    cv2.OPTFLOW_FARNEBACK_GAUSSIAN, **kwargs)`` per pair.
+
+    ``kwargs`` are OpenCV's names ``pyr_scale, levels, winsize, iterations, poly_n, poly_sigma``; all six are required, and a
+    missing one, an unknown one or ``flags`` is a ``TypeError`` as with ``cv2``.  The reference never asks for
+    ``OPTFLOW_USE_INITIAL_FLOW`` - the flow it passes on is an output buffer only - so the pairs are independent and run as one batch.
+
+    Returns ``v_x``, ``v_y``, ``speed`` (float64 ``(T-1, N_i, N_j)``), ``original_data``, ``delta_x`` and ``delta_t``.  The
+    reference's quirks are kept: ``v_x`` is OpenCV's channel 0, the displacement **along axis 2** (columns), and ``v_y`` channel 1,
+    along axis 1 - unlike every other estimator of the module; with ``smoothing_sigma`` pair ``k`` takes its first image from the
+    blurred movie and its second from the unblurred ``movie[k + 1]``, and ``original_data`` is the blurred movie; there is no
+    ``blurred_data`` key.  The fields are the float32 flow promoted to float64 and multiplied by ``delta_x / delta_t``;
+    ``speed = sqrt(v_x**2 + v_y**2)`` in float64.
+
+    OpenCV's arithmetic is restated operation by operation from OpenCV 4's ``optflowgf.cpp`` (DESIGN.md section 16 has all of
+    it and names the points where a real ``cv2`` may differ); parity with an installed ``cv2`` is tested only where one can be
+    imported (tests/test_farneback_cv2_cpu.py).  OpenCV converts a frame to float32 first, and that conversion depends on the
+    depth, so only the two depths the scripts use are served: **uint8** and **float64** movies; another dtype raises
+    ``ValueError``: cast the movie.  ``ValueError`` also for a NaN or Inf in the movie, for frames smaller than 16 x 16 and
+    outside ``0 < pyr_scale < 1``, ``levels >= 0``, ``1 <= winsize <= 129``, ``iterations >= 0``, ``1 <= poly_n <= 10``.
+    ``output="torch"``: ``movie`` may be a device tensor and every array of the result stays on the device (float64 tensors)."""
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
+    if len(shape) != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    a = _farneback_arguments(shape, kwargs)
+    if shape[0] < 2:
+        raise ValueError("movie needs at least two frames")
+    name = _movie_dtype_name(movie)
+    if name not in ("uint8", "float64"):
+        raise ValueError(f"conduct_opencv_flow serves uint8 and float64 movies only (OpenCV converts each depth to float32 in its own way), "
+                         f"not {name}: cast the movie")
+    T, N_i, N_j = shape
+    plan = farneback_plan(N_i, N_j, a["pyr_scale"], a["levels"], a["winsize"], a["poly_n"], a["poly_sigma"])
+    velocity_scale = delta_x / delta_t
+    if output == "numpy":
+        source = np.asarray(movie)
+        frames = np.ascontiguousarray(source, dtype=np.float64)
+        with _device_context(N_i, N_j, 1, device) as solver:
+            first = frames if smoothing_sigma is None else blur_movie(frames, smoothing_sigma=smoothing_sigma, device=device, _solver=solver)
+            v_x, v_y, speed = solver.farneback_host(first[:-1], frames[1:], plan, a["iterations"], velocity_scale)
+        analysed = movie if smoothing_sigma is None else first
+    else:
+        import torch
+        dev = torch.device("cuda", int(device))
+        frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
+        v_x, v_y, speed = (torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(3))
+        with _device_context(N_i, N_j, 1, device) as solver:
+            first = frames
+            if smoothing_sigma is not None:
+                first = torch.empty_like(frames)
+                torch.cuda.synchronize(dev)
+                solver.blur_dev(frames, first, T, gaussian_taps(smoothing_sigma))
+            torch.cuda.synchronize(dev)                  # the library launches on its own stream
+            solver.farneback_dev(first[:-1], frames[1:], T - 1, plan, a["iterations"], velocity_scale, v_x, v_y, speed)
+        analysed = movie if smoothing_sigma is None else first
+    return dict(v_x=v_x, v_y=v_y, speed=speed, original_data=analysed, delta_x=delta_x, delta_t=delta_t)
 
 
 def blur_movie(movie, smoothing_sigma, device=0, _solver=None):
