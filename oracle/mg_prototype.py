@@ -205,6 +205,14 @@ class Hierarchy:
     def shapes(self):
         return [c.shape[-2:] for c in self.levels]
 
+    @staticmethod
+    def level_shapes(n_i, n_j, coarsest_max=COARSEST_MAX):
+        """The level sizes of an ``n_i x n_j`` interior grid (what ``shapes()`` gives, without building the stencils)."""
+        out = [(n_i, n_j)]
+        while max(out[-1]) > coarsest_max:
+            out.append((coarse_size(out[-1][0]), coarse_size(out[-1][1])))
+        return out
+
     def apply(self, x):
         return apply_stencil(self.levels[0], x)
 
@@ -216,6 +224,26 @@ class Hierarchy:
         smooth(C, x, b, nu1)
         r = b - apply_stencil(C, x)
         ec = self.vcycle(restrict(r), nu1, nu2, level + 1)
+        x += prolong(ec, *x.shape[-2:])
+        smooth(C, x, b, nu2, reverse=True)
+        return x
+
+    def cycle(self, b, sweeps=(2, 2, 0, 0), w_cycle_level=-1, visits=2, level=0, x0=None):
+        """The cycle with the solver's shape options: ``sweeps = (nu_pre, nu_post, nu_pre_coarse, nu_post_coarse)`` (the levels
+        below 0 take the coarse counts; 0 there: the counts of level 0), and level ``w_cycle_level`` visits the next level
+        ``visits`` times (0: twice) unless that level is the coarsest, each visit continuing from the last one's result (``x0``)."""
+        C = self.levels[level]
+        if level == len(self.levels) - 1:
+            return (self.coarse_inv @ b.ravel()).reshape(b.shape)
+        nu1 = sweeps[2] if level > 0 and sweeps[2] > 0 else sweeps[0]
+        nu2 = sweeps[3] if level > 0 and sweeps[3] > 0 else sweeps[1]
+        x = np.zeros_like(b) if x0 is None else x0.copy()
+        smooth(C, x, b, nu1)
+        rc = restrict(b - apply_stencil(C, x))
+        ec = self.cycle(rc, sweeps, w_cycle_level, visits, level + 1)
+        if level == w_cycle_level and level + 1 < len(self.levels) - 1:
+            for _ in range((visits if visits > 0 else 2) - 1):
+                ec = self.cycle(rc, sweeps, w_cycle_level, visits, level + 1, x0=ec)
         x += prolong(ec, *x.shape[-2:])
         smooth(C, x, b, nu2, reverse=True)
         return x
