@@ -427,9 +427,11 @@ int vof_compare_flows_host(vof_ctx* ctx, const double* movie_a, const double* mo
  * written to range[3] (host, may be NULL), and return 1 - nothing else computed, vof_last_error says why - where the
  * reference's integer cast would be platform-dependent or wrap:
  *   threshold: a non-finite value, min < 0 or max <= 0;   CLAHE: a non-finite value, min < 0 or max >= 65536.
- * Frames are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most); the scratch memory
- * (threshold: 4 bytes per pixel and frame in flight; CLAHE: 65536 x 6 bytes per tile and frame in flight; _host: the staged
- * frames) is allocated on first use, kept, and freed by vof_destroy.  Results do not depend on frames_in_flight.
+ * Frames are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most).  The scratch memory,
+ * one buffer that this group, the resize and Farnebaeck's flow below share, holds per frame in flight: threshold 4 bytes per
+ * pixel, CLAHE 65536 x 6 bytes per tile, _host the staged frame and its result; once per call: the records of the range
+ * reduction (and the tables of the calls below).  It is allocated on first use, grown on demand, kept, and freed by
+ * vof_destroy; nothing in it is kept from one call to the next.  Results do not depend on frames_in_flight.
  * Profiler: class VOF_K_PREPROCESS, the `level` is the stage: 0 range, 1 row sums, 2 threshold, 3 histograms, 4 tables, 5 blend.
  *
  * vof_adaptive_threshold_*: cv2.adaptiveThreshold(u, 1, ADAPTIVE_THRESH_MEAN_C, THRESH_BINARY, window_size, threshold) == 1 of
@@ -457,9 +459,9 @@ int vof_clahe_host(vof_ctx* ctx, const double* movie, int n_frames, double clip_
  *     first reduced as in the calls above: a non-finite value, min < 0 or max > 255 returns 1, nothing else computed,
  *     vof_last_error says why.  That every value is an integer is the caller's contract and is not checked.
  *   VOF_RESIZE_F64: the arithmetic of float64 frames - float64 sums with float32 weights; NaN and Inf propagate.
- * Frames are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most); the two axis tables
- * are built on the host and live, with the staged frames of _host, in the scratch buffer of the calls above.  Results do not
- * depend on frames_in_flight.  Profiler: class VOF_K_PREPROCESS, `level` 6.
+ * Frames are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most).  In the scratch
+ * buffer of the calls above: once per call the two axis tables, built on the host; per frame in flight, _host only, the staged
+ * frame and its result.  Results do not depend on frames_in_flight.  Profiler: class VOF_K_PREPROCESS, `level` 6.
  * _dev: movie and out are device pointers (out must not alias movie); _host: host pointers, staged through the context's
  * pinned bounce buffer. */
 enum vof_resize_arithmetic { VOF_RESIZE_U8 = 0, VOF_RESIZE_F64 = 1 };
@@ -485,8 +487,9 @@ int vof_resize_area_host(vof_ctx* ctx, const double* movie, int n_frames, int ou
  * Results: v_x = channel 0 of OpenCV's flow (along n_j), v_y = channel 1 (along n_i), promoted to float64 and multiplied by
  * velocity_scale, and speed = sqrt(v_x^2 + v_y^2); n_pairs x n_i x n_j each.  Both stacks are first reduced as in the
  * preprocessing calls above: a non-finite value returns 1, nothing else computed, vof_last_error says why.
- * Pairs are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most; 108 bytes of scratch per
- * pixel and pair in flight, in the scratch buffer of the calls above).  Results do not depend on frames_in_flight.
+ * Pairs are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most).  In the scratch buffer
+ * of the calls above: once per call the tap tables; per pair in flight 108 bytes per pixel of planes and, _host only, the two
+ * staged frames and the three results.  Results do not depend on frames_in_flight.
  * Frames of at least 16 x 16.  Profiler: class VOF_K_PREPROCESS, `level` 7 level images, 8 polynomial expansion, 9 flow carried
  * to a level, 10 matrices, 11 window rows (vertical pass), 12 window columns + solve + update, 13 results.
  * _dev: the stacks and the results are device pointers; _host: host pointers, staged through the pinned bounce buffer. */

@@ -124,7 +124,7 @@ struct vof_ctx {
     bool sw_by_budget = false;                                           // sw_scratch was sized by the free memory, not by the request
     char* sw_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
     size_t sw_aux_bytes = 0;
-    char* pre_buf = nullptr;                                             // adaptive threshold / CLAHE / resize: partials, row sums | histograms and tables | axis tables, staged frames (lazy; pre_plan)
+    char* pre_buf = nullptr;                                             // frame-wise calls: range records, tables once per call; work regions and staged frames per frame in flight (lazy; FrameChunks carves it anew in every call)
     size_t pre_bytes = 0;
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
     bool bl_lds_set = false;                                             // tiled blur: dynamic LDS limit raised
@@ -4338,133 +4338,190 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
 int vof_compare_flows_dev(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(false)); }
 int vof_compare_flows_host(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(true)); }
 
-// ---- preprocessing: adaptive threshold and CLAHE (apply_adaptive_threshold, apply_clahe; vof_preprocess.hpp) ---------------
-constexpr int PRE_MAX_FLIGHT = 16;        // frames in flight when the caller leaves the number to the library
+// ---- frame chunks: the walk of the frame-wise calls through c->pre_buf ------------------------------
+constexpr int PRE_MAX_FLIGHT = 16;        // units in flight when the caller leaves the number to the library
 constexpr int PRE_MAX_WANT = 4096;        // ... and at most when it does not (grid z)
 
-struct PrePlan {
-    int cap;                 // frames in flight
-    PpRange *part, *rng;     // the range reduction's partial records and its result
-    char *work_a, *work_b;   // cap x (bytes_a, bytes_b): row sums | histograms, tables
-    double* in;              // _host: the staged frames
-    char* out;               // _host: the staged results
-};
+// One call of the adaptive threshold, CLAHE, the resize or Farnebaeck's flow over a stack of `n` units (frames or pairs), on the
+// stack of that call: the call declares its regions of the scratch buffer, plan() sizes the chunk and carves the buffer, range()
+// reduces a stack, run() walks the chunks.  What a staged input holds is recorded here alone: nothing staged outlives the call.
+extern "C++" {
+struct FrameChunks {
+    struct Region { void* ptr; size_t bytes; bool per_unit; };     // ptr: where the carve stores the region's address
+    struct In { const double* stack; double* slot; int k0, nf; };  // _host: slot holds units [k0, k0 + nf) of stack (nf 0: nothing)
+    struct Out { char* caller; size_t bytes; char* slot; };        // bytes per unit
+    vof_ctx* const c; const char* const what;                      // what: the call, for messages
+    const int n, want; const bool host;                            // units; the caller's frames_in_flight
+    const size_t fs;                                               // doubles per unit of an input stack
+    int cap = 0;                                                   // units in flight (plan)
+    PpRange* part = nullptr;                                       // the range reduction's partial records, then its result
+    double rg[3] = {};                                             // ... and what range() found
+    std::vector<Region> regions;
+    In in[2] = {}; Out out[3] = {}; int n_in = 0, n_out = 0;
 
-static inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// The scratch buffer of the two calls, grown (never shrunk) to what `cap` frames in flight need; cap is `want`, or sized so that
-// the buffer takes a quarter of the free device memory at most (an existing larger buffer is used in full).
-static int pre_plan(vof_ctx* c, int n_frames, int want, size_t bytes_a, size_t bytes_b, size_t out_bytes, bool host, const char* what, PrePlan* p) {
-    const size_t fb = frame_stride(c) * sizeof(double);
-    const size_t fixed = up256((PP_RANGE_BLOCKS + 1) * sizeof(PpRange)) + 4 * 256;
-    const size_t per = bytes_a + bytes_b + (host ? fb + out_bytes : 0);
-    int cap = std::min(want, PRE_MAX_WANT);
-    if (cap <= 0) {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        const size_t budget = std::max(fr / 4, c->pre_bytes);
-        cap = (int)std::min<size_t>(PRE_MAX_FLIGHT, budget > fixed ? (budget - fixed) / per : 0);
+    FrameChunks(vof_ctx* c_, const char* what_, int n_, int want_, bool host_) : c(c_), what(what_), n(n_), want(want_), host(host_), fs(frame_stride(c_)) {
+        once(&part, (PP_RANGE_BLOCKS + 1) * sizeof(PpRange));
     }
-    cap = std::max(1, std::min(cap, n_frames));
-    const size_t need = fixed + up256(cap * bytes_a) + up256(cap * bytes_b) + (host ? up256(cap * fb) + up256(cap * out_bytes) : 0);
-    if (need > c->pre_bytes) {
+    FrameChunks(const FrameChunks&) = delete;                      // the regions point into the object
+
+    // what every frame-wise entry point checks first
+    static int check(vof_ctx* c, std::initializer_list<const void*> pointers, int n, const char* n_name) {
+        if (!c) return -1;
+        for (const void* p : pointers) if (!p) { c->err = "NULL pointer"; return -1; }
+        if (n < 1) { c->err = std::string(n_name) + " must be >= 1"; return -1; }
+        return 0;
+    }
+
+    // The request.  *ptr (a pointer of any type) is the region's address after plan(): `bytes` once per call, or per unit in
+    // flight, unit after unit - align_units: each at a multiple of 256 bytes; per_unit returns the stride.
+    static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+    void once(void* ptr, size_t bytes) { regions.push_back({ptr, bytes, false}); }
+    size_t per_unit(void* ptr, size_t bytes, bool align_units = false) {
+        regions.push_back({ptr, align_units ? up256(bytes) : bytes, true});
+        return regions.back().bytes;
+    }
+    void input(const double* stack) {                              // fs doubles per unit; _host: staged
+        if (host) per_unit(&in[n_in].slot, fs * sizeof(double));
+        in[n_in++].stack = stack;
+    }
+    void output(void* caller, size_t unit_bytes) {                 // _host: staged, then copied to `caller`
+        if (host) per_unit(&out[n_out].slot, unit_bytes);
+        out[n_out].caller = (char*)caller; out[n_out++].bytes = unit_bytes;
+    }
+
+    // The layout, stated once: region after region, each at a multiple of 256 bytes.  Returns the bytes `units` in flight take;
+    // a null base only measures.
+    size_t carve(char* base, int units) {
+        size_t at = 0;
+        for (const Region& r : regions) {
+            if (base) { char* q = base + at; memcpy(r.ptr, &q, sizeof q); }
+            at += up256(r.per_unit ? (size_t)units * r.bytes : r.bytes);
+        }
+        return at;
+    }
+
+    // The chunk size - `want`, or as many units as a quarter of the free device memory holds (an existing larger buffer is used
+    // in full) - and the buffer, grown (never shrunk) to it.
+    int plan() {
+        HIPCHK(hipSetDevice(c->device));
+        cap = std::min(want > 0 ? std::min(want, PRE_MAX_WANT) : PRE_MAX_FLIGHT, n);
+        if (want <= 0) {
+            size_t fr = 0, tot = 0;
+            HIPCHK(hipMemGetInfo(&fr, &tot));
+            const size_t budget = std::max(fr / 4, c->pre_bytes);
+            while (cap > 1 && carve(nullptr, cap) > budget) --cap;
+        }
+        const size_t need = carve(nullptr, cap);
+        if (need > c->pre_bytes) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            if (int rc = dev_free(c, c->pre_buf)) return rc;
+            c->pre_buf = nullptr; c->pre_bytes = 0;
+            if (int rc = dev_alloc(c, &c->pre_buf, need)) {
+                (void)hipGetLastError();
+                c->err = std::string(what) + ": no device memory for " + std::to_string(need >> 20) + " MiB of scratch (" + std::to_string(cap) +
+                         " frame(s) in flight): " + c->err;
+                return rc;
+            }
+            c->pre_bytes = need;
+        }
+        carve(c->pre_buf, cap);
+        return 0;
+    }
+
+    // Units [k0, k0 + nf) of input s on the device: the caller's own memory, or the slot - uploaded unless it holds exactly these
+    int staged(int s, int k0, int nf, const double** p) {
+        In& i = in[s];
+        *p = host ? i.slot : i.stack + (size_t)k0 * fs;
+        if (!host || (i.nf == nf && i.k0 == k0)) return 0;
+        if (int rc = h2d_bounced(c, i.slot, i.stack + (size_t)k0 * fs, (size_t)nf * fs * sizeof(double))) return rc;
+        i.k0 = k0; i.nf = nf;
+        return 0;
+    }
+
+    // rg = (max, min of the finite values, non-finite count) of the whole of input s (_host: chunk by chunk through its slot), to
+    // `report` too if there is one; then return code 1 and the message if anything is non-finite or outside the permitted [lo, hi]
+    int range(int s, double lo, double hi, const char* outside, const char* note = "", double* report = nullptr) {
+        PpRange* const rng = part + PP_RANGE_BLOCKS;
+        PpRange acc{-INFINITY, INFINITY, 0};
+        const int chunk = host ? cap : n;
+        for (int k0 = 0; k0 < n; k0 += chunk) {
+            const int nf = std::min(chunk, n - k0);
+            const double* src;
+            if (int rc = staged(s, k0, nf, &src)) return rc;
+            const size_t m = (size_t)nf * fs;
+            const int nb = (int)std::min<size_t>(PP_RANGE_BLOCKS, (m + 8 * PP_BLOCK - 1) / (8 * PP_BLOCK));
+            c->cur_units = nf;
+            {
+                Prof prof(c, VOF_K_PREPROCESS, PP_ST_RANGE, 8.0 * fs);
+                k_pp_range<<<nb, PP_BLOCK, 0, c->stream>>>(src, m, part);
+                k_pp_range_final<<<1, 64, 0, c->stream>>>(part, nb, rng);
+            }
+            HIPCHK(hipGetLastError());
+            PpRange r;
+            if (int rc = d2h_bounced(c, &r, rng, sizeof r)) return rc;
+            acc.vmax = std::max(acc.vmax, r.vmax); acc.vmin = std::min(acc.vmin, r.vmin); acc.bad += r.bad;
+        }
+        rg[0] = acc.vmax; rg[1] = acc.vmin; rg[2] = (double)acc.bad;
+        if (report) memcpy(report, rg, sizeof rg);
+        const char* found = rg[2] > 0 ? "non-finite values" : (rg[1] < lo || rg[0] > hi ? outside : nullptr);
+        if (!found) return 0;
+        c->err = std::string(what) + ": the movie holds " + found + note;
+        return 1;
+    }
+
+    // The chunks in turn: body(k0, nf, inputs, outputs) enqueues the kernels of units [k0, k0 + nf) - device pointers, one per
+    // declared input and output - and returns 0; _host: the outputs are then copied to the caller's arrays.
+    template <class Body>
+    int run(Body&& body) {
+        for (int k0 = 0; k0 < n; k0 += cap) {
+            const int nf = std::min(cap, n - k0);
+            const double* src[2] = {}; void* dst[3] = {};
+            for (int s = 0; s < n_in; ++s) if (int rc = staged(s, k0, nf, &src[s])) return rc;
+            for (int a = 0; a < n_out; ++a) dst[a] = host ? out[a].slot : out[a].caller + (size_t)k0 * out[a].bytes;
+            c->cur_units = nf;
+            if (int rc = body(k0, nf, src, dst)) return rc;
+            HIPCHK(hipGetLastError());
+            for (int a = 0; host && a < n_out; ++a)
+                if (int rc = d2h_bounced(c, out[a].caller + (size_t)k0 * out[a].bytes, dst[a], (size_t)nf * out[a].bytes)) return rc;
+        }
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (int rc = dev_free(c, c->pre_buf)) return rc;
-        c->pre_buf = nullptr; c->pre_bytes = 0;
-        if (int rc = dev_alloc(c, &c->pre_buf, need)) {
-            (void)hipGetLastError();
-            c->err = std::string(what) + ": no device memory for " + std::to_string(need >> 20) + " MiB of scratch (" + std::to_string(cap) +
-                     " frame(s) in flight): " + c->err;
-            return rc;
-        }
-        c->pre_bytes = need;
+        return 0;
     }
-    char* q = c->pre_buf;
-    p->cap = cap;
-    p->part = (PpRange*)q; p->rng = p->part + PP_RANGE_BLOCKS; q += up256((PP_RANGE_BLOCKS + 1) * sizeof(PpRange));
-    p->work_a = q; q += up256(cap * bytes_a);
-    p->work_b = q; q += up256(cap * bytes_b);
-    p->in = (double*)q; q += host ? up256(cap * fb) : 0;
-    p->out = q;
-    return 0;
-}
+};
+}  // extern "C++"
 
-// (max, min of the finite values, non-finite count) of the whole stack; _host: chunk by chunk through the staged frames (the
-// last chunk stays there: a stack of one chunk is not uploaded again)
-static int pre_range(vof_ctx* c, const PrePlan& p, const double* movie, int n_frames, bool host, double out[3]) {
-    const size_t fs = frame_stride(c);
-    PpRange acc{-INFINITY, INFINITY, 0};
-    const int chunk = host ? p.cap : n_frames;
-    for (int k0 = 0; k0 < n_frames; k0 += chunk) {
-        const int nf = std::min(chunk, n_frames - k0);
-        const double* src = movie + (size_t)k0 * fs;
-        if (host) {
-            if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fs * sizeof(double))) return rc;
-            src = p.in;
-        }
-        const size_t n = (size_t)nf * fs;
-        const int nb = (int)std::min<size_t>(PP_RANGE_BLOCKS, (n + 8 * PP_BLOCK - 1) / (8 * PP_BLOCK));
-        c->cur_units = nf;
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_RANGE, 8.0 * fs);
-            k_pp_range<<<nb, PP_BLOCK, 0, c->stream>>>(src, n, p.part);
-            k_pp_range_final<<<1, 64, 0, c->stream>>>(p.part, nb, p.rng);
-        }
-        HIPCHK(hipGetLastError());
-        PpRange r;
-        if (int rc = d2h_bounced(c, &r, p.rng, sizeof r)) return rc;
-        acc.vmax = std::max(acc.vmax, r.vmax); acc.vmin = std::min(acc.vmin, r.vmin); acc.bad += r.bad;
-    }
-    out[0] = acc.vmax; out[1] = acc.vmin; out[2] = (double)acc.bad;
-    return 0;
-}
-
+// ---- preprocessing: adaptive threshold and CLAHE (apply_adaptive_threshold, apply_clahe; vof_preprocess.hpp) ---------------
 static int adaptive_threshold_impl(vof_ctx* c, const double* movie, int n_frames, int window, double threshold, int flight, uint8_t* mask,
                                    double* range, bool host) {
-    if (!c) return -1;
-    if (!movie || !mask) { c->err = "NULL pointer"; return -1; }
-    if (n_frames < 1) { c->err = "n_frames must be >= 1"; return -1; }
+    if (int rc = FrameChunks::check(c, {movie, mask}, n_frames, "n_frames")) return rc;
     if (window < 3 || window % 2 == 0 || window > PP_MAX_WINDOW) { c->err = "window_size must be odd and 3 .. " + std::to_string(PP_MAX_WINDOW); return -1; }
     if (c->Nj > PP_MAX_ROW) { c->err = "adaptive threshold: n_j must be <= " + std::to_string(PP_MAX_ROW); return -1; }
     if (c->Ni > 65535 * PP_COL_ROWS) { c->err = "adaptive threshold: n_i too large"; return -1; }
     if (std::isnan(threshold)) { c->err = "threshold is NaN"; return -1; }
-    HIPCHK(hipSetDevice(c->device));
     const size_t fs = frame_stride(c);
-    PrePlan p;
-    if (int rc = pre_plan(c, n_frames, flight, fs * sizeof(unsigned int), 0, fs, host, "adaptive threshold", &p)) return rc;
-    double rg[3];
-    if (int rc = pre_range(c, p, movie, n_frames, host, rg)) return rc;
-    if (range) memcpy(range, rg, sizeof rg);
-    if (rg[2] > 0) { c->err = "adaptive threshold: the movie holds non-finite values"; return 1; }
-    if (rg[1] < 0) { c->err = "adaptive threshold: the movie holds negative values"; return 1; }
-    if (!(rg[0] > 0)) { c->err = "adaptive threshold: the movie's maximum is not positive"; return 1; }
-    const double m = rg[0];
+    FrameChunks fc(c, "adaptive threshold", n_frames, flight, host);
+    unsigned int* H;                                                                     // row sums
+    fc.per_unit(&H, fs * sizeof(unsigned int));
+    fc.input(movie);
+    fc.output(mask, fs);
+    if (int rc = fc.plan()) return rc;
+    if (int rc = fc.range(0, 0.0, INFINITY, "negative values", "", range)) return rc;
+    const double m = fc.rg[0];
+    if (!(m > 0)) { c->err = "adaptive threshold: the movie's maximum is not positive"; return 1; }
     const int r = window / 2;
     const int idelta = (int)std::max(-1024.0, std::min(1024.0, std::ceil(threshold)));   // u - mean lies in [-255, 255]
-    unsigned int* H = (unsigned int*)p.work_a;
-    for (int k0 = 0; k0 < n_frames; k0 += p.cap) {
-        const int nf = std::min(p.cap, n_frames - k0);
-        const double* src = movie + (size_t)k0 * fs;
-        if (host) {
-            if (n_frames > p.cap) if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fs * sizeof(double))) return rc;
-            src = p.in;
-        }
-        uint8_t* dst = host ? (uint8_t*)p.out : mask + (size_t)k0 * fs;
-        c->cur_units = nf;
+    return fc.run([&](int, int nf, const double* const* in, void* const* out) {
         {
             Prof prof(c, VOF_K_PREPROCESS, PP_ST_ROWSUM, 12.0 * fs);
-            k_pp_rowsum<<<dim3(c->Ni, nf), PP_BLOCK, (size_t)c->Nj * sizeof(unsigned int), c->stream>>>(src, c->Ni, c->Nj, m, r, H);
+            k_pp_rowsum<<<dim3(c->Ni, nf), PP_BLOCK, (size_t)c->Nj * sizeof(unsigned int), c->stream>>>(in[0], c->Ni, c->Nj, m, r, H);
         }
         {
             Prof prof(c, VOF_K_PREPROCESS, PP_ST_THRESHOLD, 13.0 * fs);
-            k_pp_threshold<<<dim3((c->Nj + PP_BLOCK - 1) / PP_BLOCK, (c->Ni + PP_COL_ROWS - 1) / PP_COL_ROWS, nf), PP_BLOCK, 0, c->stream>>>(src, H, c->Ni, c->Nj, m, r,
-                                                                                                                  idelta, dst);
+            k_pp_threshold<<<dim3((c->Nj + PP_BLOCK - 1) / PP_BLOCK, (c->Ni + PP_COL_ROWS - 1) / PP_COL_ROWS, nf), PP_BLOCK, 0, c->stream>>>(
+                in[0], H, c->Ni, c->Nj, m, r, idelta, (uint8_t*)out[0]);
         }
-        HIPCHK(hipGetLastError());
-        if (host) if (int rc = d2h_bounced(c, mask + (size_t)k0 * fs, dst, (size_t)nf * fs)) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+        return 0;
+    });
 }
 
 int vof_adaptive_threshold_dev(vof_ctx* c, const double* movie, int n_frames, int window_size, double threshold, int frames_in_flight,
@@ -4478,9 +4535,7 @@ int vof_adaptive_threshold_host(vof_ctx* c, const double* movie, int n_frames, i
 
 static int clahe_impl(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int flight, double* out,
                       double* range, bool host) {
-    if (!c) return -1;
-    if (!movie || !out) { c->err = "NULL pointer"; return -1; }
-    if (n_frames < 1) { c->err = "n_frames must be >= 1"; return -1; }
+    if (int rc = FrameChunks::check(c, {movie, out}, n_frames, "n_frames")) return rc;
     if (tiles_x < 1 || tiles_x > c->Nj - 1 || tiles_y < 1 || tiles_y > c->Ni - 1) {
         c->err = "CLAHE: the tile grid must be 1 .. n_j - 1 by 1 .. n_i - 1"; return -1;
     }
@@ -4499,32 +4554,23 @@ static int clahe_impl(vof_ctx* c, const double* movie, int n_frames, double clip
     }
     g.lut_scale = (float)(PP_BINS - 1) / (float)area;
     g.inv_tw = 1.0f / (float)g.tw; g.inv_th = 1.0f / (float)g.th;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const size_t fs = frame_stride(c);
     const size_t ntiles = (size_t)g.tx * g.ty, hist_bytes = ntiles * PP_BINS * sizeof(unsigned int), lut_bytes = ntiles * PP_BINS * sizeof(uint16_t);
-    PrePlan p;
-    if (int rc = pre_plan(c, n_frames, flight, hist_bytes, lut_bytes, fb, host, "CLAHE", &p)) return rc;
-    double rg[3];
-    if (int rc = pre_range(c, p, movie, n_frames, host, rg)) return rc;
-    if (range) memcpy(range, rg, sizeof rg);
-    if (rg[2] > 0) { c->err = "CLAHE: the movie holds non-finite values"; return 1; }
-    if (rg[1] < 0 || rg[0] >= 65536.0) { c->err = "CLAHE: the movie holds values outside [0, 65536)"; return 1; }
-    unsigned int* hist = (unsigned int*)p.work_a;
-    uint16_t* lut = (uint16_t*)p.work_b;
+    FrameChunks fc(c, "CLAHE", n_frames, flight, host);
+    unsigned int* hist;
+    uint16_t* lut;
+    fc.per_unit(&hist, hist_bytes);
+    fc.per_unit(&lut, lut_bytes);
+    fc.input(movie);
+    fc.output(out, fs * sizeof(double));
+    if (int rc = fc.plan()) return rc;
+    if (int rc = fc.range(0, 0.0, std::nextafter(65536.0, 0.0), "values outside [0, 65536)", "", range)) return rc;   // hi: the last double below 65536
     const double padded = (double)g.pi * g.pj;
-    for (int k0 = 0; k0 < n_frames; k0 += p.cap) {
-        const int nf = std::min(p.cap, n_frames - k0);
-        const double* src = movie + (size_t)k0 * fs;
-        if (host) {
-            if (n_frames > p.cap) if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fb)) return rc;
-            src = p.in;
-        }
-        double* dst = host ? (double*)p.out : out + (size_t)k0 * fs;
-        c->cur_units = nf;
+    return fc.run([&](int, int nf, const double* const* in, void* const* dst) -> int {
         {
             Prof prof(c, VOF_K_PREPROCESS, PP_ST_HIST, 8.0 * padded + 2.0 * hist_bytes);   // the zero fill and the counters read back
             HIPCHK(hipMemsetAsync(hist, 0, (size_t)nf * hist_bytes, c->stream));
-            k_pp_hist<<<dim3((g.pj + PP_BLOCK - 1) / PP_BLOCK, g.pi, nf), PP_BLOCK, 0, c->stream>>>(src, g, hist);
+            k_pp_hist<<<dim3((g.pj + PP_BLOCK - 1) / PP_BLOCK, g.pi, nf), PP_BLOCK, 0, c->stream>>>(in[0], g, hist);
         }
         {
             Prof prof(c, VOF_K_PREPROCESS, PP_ST_LUT, (g.clip > 0 ? 2.0 : 1.0) * hist_bytes + lut_bytes, (double)hist_bytes + lut_bytes);
@@ -4532,13 +4578,10 @@ static int clahe_impl(vof_ctx* c, const double* movie, int n_frames, double clip
         }
         {
             Prof prof(c, VOF_K_PREPROCESS, PP_ST_BLEND, 24.0 * fs, 16.0 * fs);             // 4 table entries of 2 bytes from the cache
-            k_pp_blend<<<dim3((g.nj + PP_BLOCK - 1) / PP_BLOCK, g.ni, nf), PP_BLOCK, 0, c->stream>>>(src, g, lut, dst);
+            k_pp_blend<<<dim3((g.nj + PP_BLOCK - 1) / PP_BLOCK, g.ni, nf), PP_BLOCK, 0, c->stream>>>(in[0], g, lut, (double*)dst[0]);
         }
-        HIPCHK(hipGetLastError());
-        if (host) if (int rc = d2h_bounced(c, out + (size_t)k0 * fs, dst, (size_t)nf * fb)) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+        return 0;
+    });
 }
 
 int vof_clahe_dev(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int frames_in_flight,
@@ -4603,9 +4646,7 @@ static bool resize_axis_table(int ssize, int dsize, ResizeAxis* t) {
 
 static int resize_area_impl(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int flight, double* out,
                             bool host) {
-    if (!c) return -1;
-    if (!movie || !out) { c->err = "NULL pointer"; return -1; }
-    if (n_frames < 1) { c->err = "n_frames must be >= 1"; return -1; }
+    if (int rc = FrameChunks::check(c, {movie, out}, n_frames, "n_frames")) return rc;
     if (arithmetic != VOF_RESIZE_U8 && arithmetic != VOF_RESIZE_F64) { c->err = "resize: arithmetic must be VOF_RESIZE_U8 or VOF_RESIZE_F64"; return -1; }
     if (out_i < 1 || out_i > c->Ni || out_j < 1 || out_j > c->Nj) {
         c->err = "resize: 1 <= out_i <= n_i and 1 <= out_j <= n_j are required (downsampling only)"; return -1;
@@ -4631,50 +4672,34 @@ static int resize_area_impl(vof_ctx* c, const double* movie, int n_frames, int o
         memcpy(q, ty.w.data(), ty.w.size() * 4); q += ty.w.size();
         memcpy(q, tx.w.data(), tx.w.size() * 4);
     }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
-    const size_t os = (size_t)out_i * out_j, ob = os * sizeof(double);
-    PrePlan p;
-    if (int rc = pre_plan(c, n_frames, flight, up256(tab.size() * 4 + 4), 0, ob, host, "resize", &p)) return rc;
-    if (u8) {
-        double rg[3];
-        if (int rc = pre_range(c, p, movie, n_frames, host, rg)) return rc;
-        if (rg[2] > 0) { c->err = "resize: the movie holds non-finite values (uint8 arithmetic)"; return 1; }
-        if (rg[1] < 0 || rg[0] > 255.0) { c->err = "resize: the movie holds values outside 0 .. 255 (uint8 arithmetic)"; return 1; }
-    }
+    const size_t fs = frame_stride(c), os = (size_t)out_i * out_j;
+    FrameChunks fc(c, "resize", n_frames, flight, host);
+    int* q;                                                             // the axis tables on the device
+    fc.once(&q, tab.size() * 4);
+    fc.input(movie);
+    fc.output(out, os * sizeof(double));
+    if (int rc = fc.plan()) return rc;
+    if (u8) if (int rc = fc.range(0, 0.0, 255.0, "values outside 0 .. 255", " (uint8 arithmetic)")) return rc;
     RsAxis ay{}, ax{};
     if (!fast) {
-        if (int rc = h2d_bounced(c, p.work_a, tab.data(), tab.size() * 4)) return rc;
-        const int* q = (const int*)p.work_a;
+        if (int rc = h2d_bounced(c, q, tab.data(), tab.size() * 4)) return rc;
         ay.start = q; ay.count = q + out_i; ax.start = q + 2 * (size_t)out_i; ax.count = ax.start + out_j;
         ay.w = (const float*)(ax.count + out_j); ax.w = ay.w + ty.w.size();
         ay.kmax = ty.kmax; ax.kmax = tx.kmax;
     }
     const float scale_f = 1.0f / (float)(tx.iscale * ty.iscale);
     const int half_up = tx.iscale == 2 && ty.iscale == 2;
-    for (int k0 = 0; k0 < n_frames; k0 += p.cap) {
-        const int nf = std::min(p.cap, n_frames - k0);
-        const double* src = movie + (size_t)k0 * fs;
-        if (host) {
-            // U8: the range reduction has left its last chunk staged - the whole stack if it is one chunk
-            if (!u8 || n_frames > p.cap) if (int rc = h2d_bounced(c, p.in, src, (size_t)nf * fb)) return rc;
-            src = p.in;
-        }
-        double* dst = host ? (double*)p.out : out + (size_t)k0 * os;
-        c->cur_units = nf;
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_RESIZE, 8.0 * fs + 8.0 * os);
-            const dim3 grid((out_j + RS_BLOCK - 1) / RS_BLOCK, out_i, nf);
-            if (fast && u8) k_rs_fast<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, half_up, dst);
-            else if (fast) k_rs_fast<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, 0, dst);
-            else if (u8) k_rs_area<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
-            else k_rs_area<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
-        }
-        HIPCHK(hipGetLastError());
-        if (host) if (int rc = d2h_bounced(c, out + (size_t)k0 * os, dst, (size_t)nf * ob)) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return fc.run([&](int, int nf, const double* const* in, void* const* out_dev) {
+        const double* src = in[0];
+        double* dst = (double*)out_dev[0];
+        Prof prof(c, VOF_K_PREPROCESS, PP_ST_RESIZE, 8.0 * fs + 8.0 * os);
+        const dim3 grid((out_j + RS_BLOCK - 1) / RS_BLOCK, out_i, nf);
+        if (fast && u8) k_rs_fast<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, half_up, dst);
+        else if (fast) k_rs_fast<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, 0, dst);
+        else if (u8) k_rs_area<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
+        else k_rs_area<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
+        return 0;
+    });
 }
 
 int vof_resize_area_dev(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int frames_in_flight, double* out) {
@@ -4699,11 +4724,8 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
                           const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
                           int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale, int flight,
                           double* v_x, double* v_y, double* speed, bool host) {
-    if (!c) return -1;
-    if (!first || !second || !v_x || !v_y || !speed || !level_sizes || !ksizes || !presmooth_taps || !poly_tables || !poly_ig || !window_taps) {
-        c->err = "NULL pointer"; return -1;
-    }
-    if (n_pairs < 1) { c->err = "n_pairs must be >= 1"; return -1; }
+    if (int rc = FrameChunks::check(c, {first, second, v_x, v_y, speed, level_sizes, ksizes, presmooth_taps, poly_tables, poly_ig, window_taps}, n_pairs,
+                                    "n_pairs")) return rc;
     if (c->Ni < 16 || c->Nj < 16) { c->err = "Farneback flow: frames must be at least 16 x 16"; return -1; }
     if (n_levels < 1 || n_levels > 64) { c->err = "Farneback flow: 1 .. 64 pyramid images"; return -1; }
     if (poly_n < 1 || poly_n > FB_MAX_POLY_N) { c->err = "Farneback flow: poly_n must be 1 .. " + std::to_string(FB_MAX_POLY_N); return -1; }
@@ -4725,36 +4747,21 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
     memcpy(tab.data() + n_taps, poly_tables, (size_t)poly_len * sizeof(float));
     memcpy(tab.data() + n_taps + poly_len, window_taps, ((size_t)m + 1) * sizeof(float));
     const FbInvG ig{poly_ig[0], poly_ig[1], poly_ig[2], poly_ig[3]};
-    HIPCHK(hipSetDevice(c->device));
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
-    const size_t pair_floats = (size_t)FB_PLANES * fs;
-    PrePlan p;
-    // work_a: the planes of the pairs in flight and, _host, the staged second images (the first ones are staged in p.in);
-    // work_b: the tables (a copy per pair in flight is reserved, one is used)
-    if (int rc = pre_plan(c, n_pairs, flight, up256(pair_floats * sizeof(float)) + (host ? up256(fb) : 0), up256(tab.size() * sizeof(float)), 3 * fb, host,
-                          "Farneback flow", &p)) return rc;
-    for (const double* stack : {first, second}) {
-        double rg[3];
-        if (int rc = pre_range(c, p, stack, n_pairs, host, rg)) return rc;
-        if (rg[2] > 0) { c->err = "Farneback flow: the movie holds non-finite values"; return 1; }
-    }
-    if (int rc = h2d_bounced(c, p.work_b, tab.data(), tab.size() * sizeof(float))) return rc;
-    const float* d_tab = (const float*)p.work_b;
+    const size_t fs = frame_stride(c);
+    FrameChunks fc(c, "Farneback flow", n_pairs, flight, host);
+    float *planes, *d_tab;
+    const size_t ps = fc.per_unit(&planes, (size_t)FB_PLANES * fs * sizeof(float), true) / sizeof(float);   // floats from a pair's planes to the next pair's
+    fc.once(&d_tab, tab.size() * sizeof(float));
+    fc.input(first);
+    fc.input(second);
+    for (double* field : {v_x, v_y, speed}) fc.output(field, fs * sizeof(double));
+    if (int rc = fc.plan()) return rc;
+    for (int s = 0; s < 2; ++s) if (int rc = fc.range(s, -INFINITY, INFINITY, "")) return rc;
+    if (int rc = h2d_bounced(c, d_tab, tab.data(), tab.size() * sizeof(float))) return rc;
     const float *d_poly = d_tab + n_taps, *d_win = d_poly + poly_len;
-    float* planes = (float*)p.work_a;
-    double* stage2 = (double*)(p.work_a + (size_t)p.cap * up256(pair_floats * sizeof(float)));
     const FbPair q(planes, fs);
-    const size_t ps = up256(pair_floats * sizeof(float)) / sizeof(float);      // floats from a pair's planes to the next pair's
     const size_t vblur_lds = (size_t)(FB_VB_ROWS + 2 * m) * FB_VB_COLS * sizeof(float);
-    for (int k0 = 0; k0 < n_pairs; k0 += p.cap) {
-        const int nf = std::min(p.cap, n_pairs - k0);
-        const double* src[2] = {first + (size_t)k0 * fs, second + (size_t)k0 * fs};
-        if (host) {
-            if (int rc = h2d_bounced(c, p.in, src[0], (size_t)nf * fb)) return rc;
-            if (int rc = h2d_bounced(c, stage2, src[1], (size_t)nf * fb)) return rc;
-            src[0] = p.in; src[1] = stage2;
-        }
-        c->cur_units = nf;
+    return fc.run([&](int, int nf, const double* const* src, void* const* dst) -> int {
         int cur = 0;                                                            // q.flow[cur]: the flow of the level in progress
         for (int lv = n_levels - 1; lv >= 0; --lv) {
             const int h = level_sizes[2 * lv], w = level_sizes[2 * lv + 1], r = ksizes[lv] / 2;
@@ -4804,21 +4811,11 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
             cur ^= 1;
         }
         cur ^= 1;                                                               // the finished level 0
-        double* dst[3] = {v_x + (size_t)k0 * fs, v_y + (size_t)k0 * fs, speed + (size_t)k0 * fs};
-        if (host) for (int a = 0; a < 3; ++a) dst[a] = (double*)p.out + (size_t)a * p.cap * fs;
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_OUT, 32.0 * fs);
-            k_fb_output<<<dim3((unsigned)((fs + FB_BLOCK - 1) / FB_BLOCK), 1, nf), FB_BLOCK, 0, c->stream>>>(q.flow[cur], ps, fs, velocity_scale, dst[0], dst[1],
-                                                                                                            dst[2]);
-        }
-        HIPCHK(hipGetLastError());
-        if (host) {
-            double* res[3] = {v_x, v_y, speed};
-            for (int a = 0; a < 3; ++a) if (int rc = d2h_bounced(c, res[a] + (size_t)k0 * fs, dst[a], (size_t)nf * fb)) return rc;
-        }
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+        Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_OUT, 32.0 * fs);
+        k_fb_output<<<dim3((unsigned)((fs + FB_BLOCK - 1) / FB_BLOCK), 1, nf), FB_BLOCK, 0, c->stream>>>(q.flow[cur], ps, fs, velocity_scale, (double*)dst[0],
+                                                                                                        (double*)dst[1], (double*)dst[2]);
+        return 0;
+    });
 }
 
 int vof_farneback_dev(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,

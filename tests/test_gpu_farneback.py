@@ -178,6 +178,136 @@ def test_cross_checks():
         same(dict(zip(FIELDS, got)), want)
 
 
+def plan_of(name, N_i, N_j):
+    return of().farneback_plan(N_i, N_j, **{k: v for k, v in case_arguments(name).items() if k != "iterations"})
+
+
+@functools.lru_cache(maxsize=None)
+def reversed_reference():
+    """"smallest" with its frames in reverse order."""
+    out = R.conduct_opencv_flow(np.ascontiguousarray(case_input("smallest")[::-1]), **case_arguments("smallest"))
+    return {k: out[k] for k in FIELDS}
+
+
+def test_nothing_staged_survives_a_call():
+    """One context, two views of one host array at one address: both stacks are staged whole (frames_in_flight=0), the array is
+    overwritten in place (the frames in reverse order, so both stacks change), and the second call sees the new frames."""
+    from opticalflow_amd import _native
+    name = "smallest"
+    iterations = case_arguments(name)["iterations"]
+    frames = case_input(name).astype(np.float64)
+    with _native.Solver(40, 52, 1) as solver:
+        first = solver.farneback_host(frames[:-1], frames[1:], plan_of(name, 40, 52), iterations, frames_in_flight=0)
+        frames[...] = frames[::-1].copy()
+        second = solver.farneback_host(frames[:-1], frames[1:], plan_of(name, 40, 52), iterations, frames_in_flight=0)
+    same(dict(zip(FIELDS, first)), reference(name)[0])
+    same(dict(zip(FIELDS, second)), reversed_reference())
+    assert not np.array_equal(second[0], first[0])
+
+
+def test_range_is_accumulated_over_chunks_and_stacks():
+    """One pair in flight; a NaN in the last frame of the movie is in `second` alone, one in frame 0 is in the first chunk of
+    `first` alone - not in the chunk its range reduction leaves staged."""
+    from opticalflow_amd import _native
+    name = "smallest"
+    iterations = case_arguments(name)["iterations"]
+    movie = case_input(name).astype(np.float64)
+    with _native.Solver(40, 52, 1) as solver:
+        for frame in (2, 0):
+            frames = movie.copy()
+            frames[frame, 7, 9] = np.nan
+            with pytest.raises(ValueError, match="non-finite"):
+                solver.farneback_host(frames[:-1], frames[1:], plan_of(name, 40, 52), iterations, frames_in_flight=1)
+        got = solver.farneback_host(movie[:-1], movie[1:], plan_of(name, 40, 52), iterations, frames_in_flight=1)
+    same(dict(zip(FIELDS, got)), reference(name)[0])
+
+
+# ---- one context, every owner of the frame-chunk scratch buffer in turn -----------------------------------------------------
+# 41 x 53, the shape of the resize case "mixed_counts"; the other inputs are committed cases padded to it by repeating their
+# last row / column: "smallest" (40 x 52) for the flow, "blurred" (37 x 53) for the threshold, "A" (37 x 53) for CLAHE.
+def padded(movie):
+    return np.pad(movie, ((0, 0), (0, 41 - movie.shape[1]), (0, 53 - movie.shape[2])), mode="edge")
+
+
+@functools.lru_cache(maxsize=None)
+def sequence_inputs():
+    from preprocess_cases import clahe_input, threshold_input
+    from resize_cases import case_input as resize_input
+    return {"flow": padded(case_input("smallest")).astype(np.float64), "resize": resize_input("mixed_counts", "u8").astype(np.float64),
+            "threshold": padded(threshold_input("blurred")), "clahe": padded(clahe_input("A"))}
+
+
+@functools.lru_cache(maxsize=None)
+def sequence_references():
+    import preprocess_restatement
+    import resize_restatement
+    inputs = sequence_inputs()
+    flow = R.conduct_opencv_flow(inputs["flow"].astype(np.uint8), **case_arguments("smallest"))
+    rec = {}
+    clahe = preprocess_restatement.clahe(inputs["clahe"], 50000, 4, rec)
+    return {"flow": {k: flow[k] for k in FIELDS}, "resize": resize_restatement.resize_area(inputs["resize"].astype(np.uint8), 8, 10),
+            "threshold": preprocess_restatement.adaptive_threshold(inputs["threshold"], 11, 2.5), "clahe": clahe,
+            "tiles": (rec["tilesX"], rec["tilesY"])}
+
+
+def run_sequence(after_each_call=lambda solver: None):
+    """Farnebaeck _host (the largest request), uint8 resize _host with two frames in flight, threshold _host, CLAHE _dev,
+    Farnebaeck _dev on one context; every result is checked against its restatement."""
+    import torch
+    from opticalflow_amd import _native
+    inputs, want = sequence_inputs(), sequence_references()
+    iterations = case_arguments("smallest")["iterations"]
+    plan = plan_of("smallest", 41, 53)
+    flow = inputs["flow"]
+    results = []
+    with _native.Solver(41, 53, 1) as solver:
+        def done(got, key):
+            after_each_call(solver)
+            if key == "flow":
+                same(dict(zip(FIELDS, got)), want[key])
+            else:
+                assert np.array_equal(got, want[key]), key
+            assert all(np.isfinite(g).all() for g in (got if key == "flow" else [got])), key
+            results.append(got)
+
+        done(solver.farneback_host(flow[:-1], flow[1:], plan, iterations), "flow")
+        done(solver.resize_area_host(inputs["resize"], 8, 10, _native.RESIZE_U8, frames_in_flight=2), "resize")
+        done(solver.adaptive_threshold_host(inputs["threshold"], 11, 2.5), "threshold")
+        frames = torch.as_tensor(inputs["clahe"]).cuda()
+        out = torch.zeros(frames.shape, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        solver.clahe_dev(frames, out, frames.shape[0], 50000, *want["tiles"])
+        done(out.cpu().numpy(), "clahe")
+        d = torch.as_tensor(flow).cuda()
+        fields = [torch.zeros((2, 41, 53), dtype=torch.float64, device="cuda") for _ in range(3)]
+        torch.cuda.synchronize()
+        solver.farneback_dev(d[:-1], d[1:], 2, plan, iterations, 1.0, *fields)
+        done(tuple(f.cpu().numpy() for f in fields), "flow")
+    return results
+
+
+@functools.lru_cache(maxsize=None)
+def plain_sequence():
+    return run_sequence()
+
+
+def test_one_context_serves_every_owner_of_the_scratch_buffer():
+    """A smaller request is carved anew inside the buffer a larger one left behind."""
+    assert len(plain_sequence()) == 5
+
+
+def test_scratch_buffer_under_guard_regions_and_poison(monkeypatch):
+    """The same sequence with guard regions around every device buffer and poisoned (0xFF: NaN) allocations: no guard region is
+    touched by any call, and the results are those of the plain run (finite: run_sequence asserts it)."""
+    plain = plain_sequence()
+    monkeypatch.setenv("VOF_DEBUG_CANARY", "1")
+    monkeypatch.setenv("VOF_DEBUG_POISON", "1")
+    guarded = run_sequence(lambda solver: solver.check_canaries())
+    for got, want in zip(guarded, plain):
+        for g, w in zip(got, want) if isinstance(got, tuple) else [(got, want)]:
+            assert np.array_equal(g, w)
+
+
 def test_errors_leave_the_context_usable():
     name = "smallest"
     movie, args = case_input(name), case_arguments(name)

@@ -95,6 +95,32 @@ def test_threshold_cross_checks():
             assert np.array_equal(mask.cpu().numpy(), want), flight
 
 
+def test_threshold_nothing_staged_survives_a_call():
+    """One context, one host array at one address: the whole stack is staged (frames_in_flight=0), the array is overwritten in
+    place, and the second call sees the new frames."""
+    from opticalflow_amd import _native
+    m = threshold_input("blurred").copy()
+    with _native.Solver(37, 53, 1) as solver:
+        first = solver.adaptive_threshold_host(m, 11, 2.5, frames_in_flight=0)
+        m[...] = threshold_input("raw")
+        second = solver.adaptive_threshold_host(m, 11, 2.5, frames_in_flight=0)
+    assert np.array_equal(first, threshold_reference("blurred", 11, 2.5)[0])
+    assert np.array_equal(second, threshold_reference("raw", 11, 2.5)[0]) and not np.array_equal(second, first)
+
+
+def test_threshold_range_is_accumulated_over_chunks():
+    """One frame in flight, the offending value in frame 0 only: it is not in the chunk the range reduction leaves staged."""
+    from opticalflow_amd import _native
+    movie = threshold_input("raw")
+    with _native.Solver(37, 53, 1) as solver:
+        for bad, message in ((np.nan, "non-finite"), (-1.0, "negative")):
+            m = movie.copy()
+            m[0, 3, 5] = bad
+            with pytest.raises(ValueError, match=message):
+                solver.adaptive_threshold_host(m, 11, 2.5, frames_in_flight=1)
+        assert np.array_equal(solver.adaptive_threshold_host(movie, 11, 2.5, frames_in_flight=1), threshold_reference("raw", 11, 2.5)[0])
+
+
 def test_threshold_value_errors():
     import torch
     movie = threshold_input("raw").copy()
@@ -185,6 +211,33 @@ def test_clahe_cross_checks():
             torch.cuda.synchronize()
             solver.clahe_dev(frames, out, 2, clip_limit, rec["tilesX"], rec["tilesY"], frames_in_flight=flight)
             assert np.array_equal(out.cpu().numpy(), want), flight
+
+
+def test_clahe_nothing_staged_survives_a_call():
+    """As test_threshold_nothing_staged_survives_a_call; the second movie is the first with its two frames exchanged."""
+    from opticalflow_amd import _native
+    name, clip_limit, _ = CLAHE_CASES["A"]
+    want, rec = clahe_reference("A")
+    assert want.shape[0] == 2 and not np.array_equal(want[0], want[1])
+    m = clahe_input(name).copy()
+    with _native.Solver(37, 53, 1) as solver:
+        first = solver.clahe_host(m, clip_limit, rec["tilesX"], rec["tilesY"], frames_in_flight=0)
+        m[...] = clahe_input(name)[::-1]
+        second = solver.clahe_host(m, clip_limit, rec["tilesX"], rec["tilesY"], frames_in_flight=0)
+    assert np.array_equal(first, want)
+    assert np.array_equal(second, want[::-1]) and not np.array_equal(second, first)
+
+
+def test_clahe_range_is_accumulated_over_chunks():
+    from opticalflow_amd import _native
+    name, clip_limit, _ = CLAHE_CASES["A"]
+    want, rec = clahe_reference("A")
+    m = clahe_input(name).copy()
+    m[0, 3, 5] = 65536.0                                                                        # frame 0 of 2, one frame in flight
+    with _native.Solver(37, 53, 1) as solver:
+        with pytest.raises(ValueError, match="65536"):
+            solver.clahe_host(m, clip_limit, rec["tilesX"], rec["tilesY"], frames_in_flight=1)
+        assert np.array_equal(solver.clahe_host(clahe_input(name), clip_limit, rec["tilesX"], rec["tilesY"], frames_in_flight=1), want)
 
 
 def test_clahe_value_errors():

@@ -183,6 +183,32 @@ def test_cross_checks():
         assert np.array_equal(solver.resize_area_host(case_input("mixed_counts", "u8"), 8, 10, _native.RESIZE_U8), reference("mixed_counts", "u8")[0])
 
 
+def test_nothing_staged_survives_a_call():
+    """uint8 arithmetic, one context, one host array at one address: the whole stack is staged for the range reduction
+    (frames_in_flight=0), the array is overwritten in place (the frames in reverse order), and the second call sees the new frames."""
+    from opticalflow_amd import _native
+    want, _ = reference("mixed_counts", "u8")
+    m = case_input("mixed_counts", "u8").astype(np.float64)
+    with _native.Solver(41, 53, 1) as solver:
+        first = solver.resize_area_host(m, 8, 10, _native.RESIZE_U8, frames_in_flight=0)
+        m[...] = m[::-1].copy()
+        second = solver.resize_area_host(m, 8, 10, _native.RESIZE_U8, frames_in_flight=0)
+    assert np.array_equal(first, want)
+    assert np.array_equal(second, want[::-1]) and not np.array_equal(second, first)
+
+
+def test_range_is_accumulated_over_chunks():
+    """One frame in flight, 256 in frame 0 only: it is not in the chunk the range reduction leaves staged."""
+    from opticalflow_amd import _native
+    movie = case_input("mixed_counts", "u8")
+    m = movie.astype(np.float64)
+    m[0, 3, 5] = 256.0
+    with _native.Solver(41, 53, 1) as solver:
+        with pytest.raises(ValueError, match="0 .. 255"):
+            solver.resize_area_host(m, 8, 10, _native.RESIZE_U8, frames_in_flight=1)
+        assert np.array_equal(solver.resize_area_host(movie, 8, 10, _native.RESIZE_U8, frames_in_flight=1), reference("mixed_counts", "u8")[0])
+
+
 def test_value_errors_leave_the_context_usable():
     movie = case_input("mixed_counts", "f64")
     want, _ = reference("mixed_counts", "f64")
