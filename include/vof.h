@@ -502,6 +502,25 @@ int vof_farneback_host(vof_ctx* ctx, const double* first, const double* second, 
                        int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale,
                        int frames_in_flight, double* v_x, double* v_y, double* speed);
 
+/* The same with OpenCV's default window (flags without OPTFLOW_FARNEBACK_GAUSSIAN): the box window of 2 (winsize / 2) + 1 rows and
+ * columns, which OpenCV keeps as two running sums in double - down the columns, then along the rows - and divides by winsize^2;
+ * the sums are formed in OpenCV's order of additions ("Iteration, box window").  The arguments are those
+ * of vof_farneback_* without window_taps; everything else - levels, level images, expansion, matrices, results, the range
+ * reduction and its return code 1, chunking - is shared with them.  winsize: 2 .. 129; at winsize 1 OpenCV's start values count
+ * row 0 and column 0 once too often, which is not restated: -1.
+ * Scratch per pair in flight: 128 bytes per pixel of planes instead of 108 - 32 float32 planes, of which the window's vertical
+ * running sums take ten as five double planes - and, _host only, the staged frames and results; the same buffer, re-carved by
+ * either variant.  Profiler: class VOF_K_PREPROCESS, `level` 7 - 10 and 13 as above, 14 window rows (the vertical running sum),
+ * 15 window columns (the horizontal running sum) + solve + update; 11 and 12 stay the Gaussian window's. */
+int vof_farneback_box_dev(vof_ctx* ctx, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes,
+                          const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
+                          int winsize, int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x,
+                          double* v_y, double* speed);
+int vof_farneback_box_host(vof_ctx* ctx, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes,
+                           const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
+                           int winsize, int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x,
+                           double* v_y, double* speed);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

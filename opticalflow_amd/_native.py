@@ -117,6 +117,10 @@ SIGNATURES = {
                                     C.c_double, C.c_int, _vp, _vp, _vp]),
     "vof_farneback_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
                                      C.c_double, C.c_int, _vp, _vp, _vp]),
+    "vof_farneback_box_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
+                                        C.c_double, C.c_int, _vp, _vp, _vp]),
+    "vof_farneback_box_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
+                                         C.c_double, C.c_int, _vp, _vp, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -602,8 +606,9 @@ class Solver:
         """The same on device memory: float64 frames in, float64 ``(n_frames, out_i, out_j)`` out (``out`` must not alias ``movie``)."""
         self._resize_area("vof_resize_area_dev", movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out)
 
-    def _farneback(self, fn, first, second, n_pairs, plan, iterations, velocity_scale, frames_in_flight, v_x, v_y, speed):
-        """``vof_farneback_*`` with the tables of ``optical_flow.farneback_plan``; return code 1 (a non-finite frame) is a ValueError."""
+    def _farneback(self, fn, first, second, n_pairs, plan, iterations, velocity_scale, frames_in_flight, v_x, v_y, speed, box=False):
+        """``vof_farneback_*`` (``box``: ``vof_farneback_box_*``, which take no window taps) with the tables of
+        ``optical_flow.farneback_plan``; return code 1 (a non-finite frame) is a ValueError."""
         sizes = np.ascontiguousarray(plan["sizes"], dtype=np.int32).reshape(-1, 2)
         ksizes = np.ascontiguousarray(plan["ksizes"], dtype=np.int32)
         taps = np.ascontiguousarray(np.concatenate(plan["presmooth_taps"]), dtype=np.float32)
@@ -612,27 +617,31 @@ class Solver:
         window = np.ascontiguousarray(plan["window_taps"], dtype=np.float32)
         assert ksizes.size == sizes.shape[0] and taps.size == int(ksizes.sum()) and poly.size == 3 * (2 * int(plan["poly_n"]) + 1)
         assert window.size == int(plan["winsize"]) // 2 + 1
+        if box:
+            fn = fn.replace("vof_farneback_", "vof_farneback_box_")
         rc = getattr(self.lib, fn)(self.h, _ptr(first), _ptr(second), int(n_pairs), sizes.shape[0], _ptr(sizes), _ptr(ksizes), _ptr(taps),
-                                   int(plan["poly_n"]), _ptr(poly), _ptr(ig), int(plan["winsize"]), _ptr(window), int(iterations),
-                                   float(plan["flow_scale"]), float(velocity_scale), int(frames_in_flight), _ptr(v_x), _ptr(v_y), _ptr(speed))
+                                   int(plan["poly_n"]), _ptr(poly), _ptr(ig), int(plan["winsize"]), *(() if box else (_ptr(window),)),
+                                   int(iterations), float(plan["flow_scale"]), float(velocity_scale), int(frames_in_flight), _ptr(v_x), _ptr(v_y),
+                                   _ptr(speed))
         if rc == 1:
             raise ValueError(self.lib.vof_last_error(self.h).decode())
         self._check(rc, fn)
 
-    def farneback_host(self, first: np.ndarray, second: np.ndarray, plan, iterations, velocity_scale=1.0, frames_in_flight=0):
+    def farneback_host(self, first: np.ndarray, second: np.ndarray, plan, iterations, velocity_scale=1.0, frames_in_flight=0, box=False):
         """Farnebaeck's flow of the pairs ``(first[k], second[k])`` of two host stacks (read as float64; they may be two views of
-        one movie): ``(v_x, v_y, speed)``, float64 ``(n_pairs, n_i, n_j)`` each.  ``plan``: ``optical_flow.farneback_plan``."""
+        one movie): ``(v_x, v_y, speed)``, float64 ``(n_pairs, n_i, n_j)`` each.  ``plan``: ``optical_flow.farneback_plan``.
+        ``box``: OpenCV's default box window of ``plan["winsize"]`` in place of the Gaussian one (the plan's window taps are unused)."""
         first = np.ascontiguousarray(first, dtype=np.float64)
         second = np.ascontiguousarray(second, dtype=np.float64)
         assert first.ndim == 3 and first.shape[1:] == (self.n_i, self.n_j) and second.shape == first.shape
         out = [np.empty(first.shape, dtype=np.float64) for _ in range(3)]
-        self._farneback("vof_farneback_host", first, second, first.shape[0], plan, iterations, velocity_scale, frames_in_flight, *out)
+        self._farneback("vof_farneback_host", first, second, first.shape[0], plan, iterations, velocity_scale, frames_in_flight, *out, box=box)
         return tuple(out)
 
-    def farneback_dev(self, first, second, n_pairs, plan, iterations, velocity_scale, v_x, v_y, speed, frames_in_flight=0):
+    def farneback_dev(self, first, second, n_pairs, plan, iterations, velocity_scale, v_x, v_y, speed, frames_in_flight=0, box=False):
         """The same on device memory: two float64 stacks of ``n_pairs`` frames in, three float64 ``(n_pairs, n_i, n_j)`` arrays out
         (none of them may alias a stack)."""
-        self._farneback("vof_farneback_dev", first, second, n_pairs, plan, iterations, velocity_scale, frames_in_flight, v_x, v_y, speed)
+        self._farneback("vof_farneback_dev", first, second, n_pairs, plan, iterations, velocity_scale, frames_in_flight, v_x, v_y, speed, box=box)
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

@@ -4711,25 +4711,32 @@ int vof_resize_area_host(vof_ctx* c, const double* movie, int n_frames, int out_
 
 // ---- Farnebaeck's dense flow (conduct_opencv_flow; vof_farneback.hpp) ---------------------------------------------------------
 // The float32 planes of one pair in flight, each n_i * n_j floats long whatever the level (a level's planes are compact at
-// the start of their slots): FB_PLANES in all.
+// the start of their slots): FB_PLANES in all with the Gaussian window; FB_BOX_PLANES with the box window, whose V is five
+// double planes (the slot of ten float32 ones; a pair's planes start at a multiple of 256 bytes, so V is aligned).
+enum FbWindow { FB_GAUSSIAN, FB_BOX };
 struct FbPair {
     float *tmp_a, *tmp_b, *image, *R[2], *M, *V, *flow[2];
-    explicit FbPair(float* q, size_t fs) {
+    explicit FbPair(float* q, size_t fs, FbWindow window) {
         tmp_a = q; tmp_b = q + fs; image = q + 2 * fs; R[0] = q + 3 * fs; R[1] = q + 8 * fs; M = q + 13 * fs; V = q + 18 * fs;
-        flow[0] = q + 23 * fs; flow[1] = q + 25 * fs;
+        flow[0] = V + (window == FB_BOX ? 10 : 5) * fs; flow[1] = flow[0] + 2 * fs;
     }
 };
 
 static int farneback_impl(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes,
                           const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
-                          int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale, int flight,
-                          double* v_x, double* v_y, double* speed, bool host) {
-    if (int rc = FrameChunks::check(c, {first, second, v_x, v_y, speed, level_sizes, ksizes, presmooth_taps, poly_tables, poly_ig, window_taps}, n_pairs,
-                                    "n_pairs")) return rc;
+                          FbWindow window, int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale,
+                          int flight, double* v_x, double* v_y, double* speed, bool host) {
+    const bool box = window == FB_BOX;                                          // no taps: the window is two running sums
+    if (int rc = FrameChunks::check(c, {first, second, v_x, v_y, speed, level_sizes, ksizes, presmooth_taps, poly_tables, poly_ig,
+                                        box ? (const void*)first : window_taps}, n_pairs, "n_pairs")) return rc;
     if (c->Ni < 16 || c->Nj < 16) { c->err = "Farneback flow: frames must be at least 16 x 16"; return -1; }
     if (n_levels < 1 || n_levels > 64) { c->err = "Farneback flow: 1 .. 64 pyramid images"; return -1; }
     if (poly_n < 1 || poly_n > FB_MAX_POLY_N) { c->err = "Farneback flow: poly_n must be 1 .. " + std::to_string(FB_MAX_POLY_N); return -1; }
     if (winsize < 1 || winsize > FB_MAX_WINSIZE) { c->err = "Farneback flow: winsize must be 1 .. " + std::to_string(FB_MAX_WINSIZE); return -1; }
+    if (box && winsize < 2) {
+        c->err = "Farneback flow: the box window needs winsize >= 2 (at winsize 1 OpenCV's running sums start with row 0 and column 0 counted once too often)";
+        return -1;
+    }
     if (iterations < 0) { c->err = "Farneback flow: iterations must be >= 0"; return -1; }
     if (level_sizes[0] != c->Ni || level_sizes[1] != c->Nj) { c->err = "Farneback flow: level 0 must have the frame's size"; return -1; }
     size_t n_taps = 0;
@@ -4742,15 +4749,15 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
         n_taps += (size_t)ksizes[k];
     }
     const int m = winsize / 2, poly_len = 3 * (2 * poly_n + 1);
-    std::vector<float> tab(n_taps + (size_t)poly_len + (size_t)m + 1);       // pre-smoothing taps | g, xg, xxg | window taps
+    std::vector<float> tab(n_taps + (size_t)poly_len + (box ? 0 : (size_t)m + 1));   // pre-smoothing taps | g, xg, xxg | Gaussian window taps
     memcpy(tab.data(), presmooth_taps, n_taps * sizeof(float));
     memcpy(tab.data() + n_taps, poly_tables, (size_t)poly_len * sizeof(float));
-    memcpy(tab.data() + n_taps + poly_len, window_taps, ((size_t)m + 1) * sizeof(float));
+    if (!box) memcpy(tab.data() + n_taps + poly_len, window_taps, ((size_t)m + 1) * sizeof(float));
     const FbInvG ig{poly_ig[0], poly_ig[1], poly_ig[2], poly_ig[3]};
     const size_t fs = frame_stride(c);
     FrameChunks fc(c, "Farneback flow", n_pairs, flight, host);
     float *planes, *d_tab;
-    const size_t ps = fc.per_unit(&planes, (size_t)FB_PLANES * fs * sizeof(float), true) / sizeof(float);   // floats from a pair's planes to the next pair's
+    const size_t ps = fc.per_unit(&planes, (size_t)(box ? FB_BOX_PLANES : FB_PLANES) * fs * sizeof(float), true) / sizeof(float);   // floats from a pair's planes to the next pair's
     fc.once(&d_tab, tab.size() * sizeof(float));
     fc.input(first);
     fc.input(second);
@@ -4759,7 +4766,8 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
     for (int s = 0; s < 2; ++s) if (int rc = fc.range(s, -INFINITY, INFINITY, "")) return rc;
     if (int rc = h2d_bounced(c, d_tab, tab.data(), tab.size() * sizeof(float))) return rc;
     const float *d_poly = d_tab + n_taps, *d_win = d_poly + poly_len;
-    const FbPair q(planes, fs);
+    const FbPair q(planes, fs, window);
+    const double box_scale = 1.0 / (double)(winsize * winsize);
     const size_t vblur_lds = (size_t)(FB_VB_ROWS + 2 * m) * FB_VB_COLS * sizeof(float);
     return fc.run([&](int, int nf, const double* const* src, void* const* dst) -> int {
         int cur = 0;                                                            // q.flow[cur]: the flow of the level in progress
@@ -4796,13 +4804,24 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
                 k_fb_matrices<<<rows, FB_BLOCK, 0, c->stream>>>(q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w);
             }
             for (int it = 0; it < iterations; ++it) {
+                const bool rebuild = it < iterations - 1;
+                if (box) {
+                    {
+                        Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_BOX_ROWS, 80.0 * hw, 60.0 * hw);     // the row leaving the window is re-read from the caches
+                        k_fb_box_rows<FB_BR_LOOK><<<dim3((w + FB_BR_BLOCK - 1) / FB_BR_BLOCK, 1, 5 * nf), FB_BR_BLOCK, 0, c->stream>>>(
+                            q.M, ps, (double*)q.V, ps / 2, h, w, m);
+                    }
+                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_BOX_UPDATE, (rebuild ? 148.0 : 88.0) * hw, (rebuild ? 108.0 : 48.0) * hw);   // likewise the column
+                    k_fb_box_update<<<dim3((h + FB_BU_ROWS - 1) / FB_BU_ROWS, 1, nf), FB_BLOCK, 0, c->stream>>>(
+                        (const double*)q.V, ps / 2, q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w, m, box_scale, rebuild ? 1 : 0);
+                    continue;
+                }
                 {
                     Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_VBLUR, 40.0 * hw);
                     k_fb_vblur<<<dim3((w + FB_VB_COLS - 1) / FB_VB_COLS, (h + FB_VB_ROWS - 1) / FB_VB_ROWS, 5 * nf), FB_BLOCK, vblur_lds, c->stream>>>(
                         q.M, q.V, ps, h, w, m, d_win);
                 }
                 {
-                    const bool rebuild = it < iterations - 1;
                     Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_UPDATE, (rebuild ? 88.0 : 28.0) * hw);
                     k_fb_update<<<rows, FB_BLOCK, 0, c->stream>>>(q.V, q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w, m, d_win, rebuild ? 1 : 0);
                 }
@@ -4821,13 +4840,25 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
 int vof_farneback_dev(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
                       const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, const float* window_taps,
                       int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
-    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, winsize, window_taps,
-                          iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, false);
+    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_GAUSSIAN, winsize,
+                          window_taps, iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, false);
 }
 int vof_farneback_host(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
                        const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, const float* window_taps,
                        int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
-    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, winsize, window_taps,
+    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_GAUSSIAN, winsize,
+                          window_taps, iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, true);
+}
+int vof_farneback_box_dev(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
+                          const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, int iterations,
+                          float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
+    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_BOX, winsize, nullptr,
+                          iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, false);
+}
+int vof_farneback_box_host(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
+                           const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, int iterations,
+                           float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
+    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_BOX, winsize, nullptr,
                           iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, true);
 }
 

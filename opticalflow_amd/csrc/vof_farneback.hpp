@@ -9,6 +9,7 @@
 // An iteration is two launches: k_fb_vblur (M -> V, an LDS tile of 32 + 2 m rows by 64 columns per workgroup and plane) and
 // k_fb_update (V -> window sum along the row out of LDS, the 2 x 2 solve, the flow, and M rebuilt from the pixel's own new flow).
 // With V between them M needs no second copy: the first launch only reads M, the second only writes it.
+// The box window (OpenCV's default, flags = 0) has the same two launches, k_fb_box_rows and k_fb_box_update, with V in double.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -22,10 +23,17 @@ constexpr int FB_MAX_WINSIZE = 129;      // m = winsize / 2 <= 64
 constexpr int FB_VB_COLS = 64;           // k_fb_vblur: columns of a tile, two per lane
 constexpr int FB_VB_ROWS = 32;           // ... and its output rows
 constexpr int FB_VB_PER = FB_VB_ROWS / (FB_BLOCK / (FB_VB_COLS / 2));   // output rows of a lane: 4
-constexpr int FB_PLANES = 27;            // float32 planes of scratch per pair in flight (FbPair)
+constexpr int FB_PLANES = 27;            // float32 planes of scratch per pair in flight (FbPair), Gaussian window
+constexpr int FB_BOX_PLANES = 32;        // ... box window: V is five double planes
+constexpr int FB_BR_BLOCK = 64;          // k_fb_box_rows: lanes of a workgroup (a column of a plane each)
+constexpr int FB_BR_LOOK = 16;           // ... steps whose rows of M a lane loads ahead (DESIGN.md section 16.4 has the ones dropped)
+constexpr int FB_BU_ROWS = 8;            // k_fb_box_update: rows of a workgroup's band
+constexpr int FB_BU_COLS = 32;           // ... columns of a tile
+constexpr int FB_BU_PITCH = FB_BU_COLS + 1;   // ... doubles from one (row, plane) line in LDS to the next: odd
 
 // profiler stages of VOF_K_PREPROCESS, after those of vof_preprocess.hpp
-enum { PP_ST_FB_LEVEL = PP_ST_RESIZE + 1, PP_ST_FB_POLY, PP_ST_FB_FLOW, PP_ST_FB_MATRICES, PP_ST_FB_VBLUR, PP_ST_FB_UPDATE, PP_ST_FB_OUT };
+enum { PP_ST_FB_LEVEL = PP_ST_RESIZE + 1, PP_ST_FB_POLY, PP_ST_FB_FLOW, PP_ST_FB_MATRICES, PP_ST_FB_VBLUR, PP_ST_FB_UPDATE, PP_ST_FB_OUT,
+       PP_ST_FB_BOX_ROWS, PP_ST_FB_BOX_UPDATE };
 
 __device__ inline int fb_reflect101(int i, int n) {
     while (i < 0 || i >= n) {
@@ -155,8 +163,8 @@ __global__ __launch_bounds__(FB_BLOCK) void k_fb_polyexp(const float* __restrict
 
 // FarnebackUpdateMatrices at one pixel: M[0 .. 4] from R0 at the pixel, R1 gathered bilinearly at (x + dx, y + dy) and the pixel's flow.
 // A position whose floor is not inside [0, w - 1) x [0, h - 1) - NaN and what fits no int included - takes the outside branch.
-__device__ inline void fb_matrix(const float* __restrict__ R0, const float* __restrict__ R1, int h, int w, int x, int y, float dx, float dy,
-                                 float* __restrict__ M) {
+__device__ inline void fb_matrix_values(const float* __restrict__ R0, const float* __restrict__ R1, int h, int w, int x, int y, float dx, float dy,
+                                        float* __restrict__ out) {
 #pragma clang fp contract(off)
     const size_t hw = (size_t)h * w, at = (size_t)y * w + x;
     float fx = (float)x + dx, fy = (float)y + dy;
@@ -199,11 +207,19 @@ __device__ inline void fb_matrix(const float* __restrict__ R0, const float* __re
     }
     const float r44 = r4 * r4, r66 = r6 * r6, r55 = r5 * r5;
     const float r42 = r4 * r2, r63 = r6 * r3, r62 = r6 * r2, r53 = r5 * r3;
-    M[at] = r44 + r66;
-    M[at + hw] = (r4 + r5) * r6;
-    M[at + 2 * hw] = r55 + r66;
-    M[at + 3 * hw] = r42 + r63;
-    M[at + 4 * hw] = r62 + r53;
+    out[0] = r44 + r66;
+    out[1] = (r4 + r5) * r6;
+    out[2] = r55 + r66;
+    out[3] = r42 + r63;
+    out[4] = r62 + r53;
+}
+
+__device__ inline void fb_matrix(const float* __restrict__ R0, const float* __restrict__ R1, int h, int w, int x, int y, float dx, float dy,
+                                 float* __restrict__ M) {
+    float v[5];
+    fb_matrix_values(R0, R1, h, w, x, y, dx, dy, v);
+    const size_t hw = (size_t)h * w, at = (size_t)y * w + x;
+    for (int c = 0; c < 5; ++c) M[at + c * hw] = v[c];
 }
 
 // M of a whole level from its start flow.  Grid (ceil(w / FB_BLOCK), h, pairs); every array with its stride per pair.
@@ -299,6 +315,152 @@ __global__ __launch_bounds__(FB_BLOCK) void k_fb_update(const float* __restrict_
     flow[o + px] = dx;
     flow[o + hw + px] = dy;
     if (rebuild) fb_matrix(R0 + o, R1 + o, h, w, x, y, dx, dy, M + o);
+}
+
+// ---- the box window (flags without OPTFLOW_FARNEBACK_GAUSSIAN; DESIGN.md section 16.1, "Iteration, box window") ------------------
+// OpenCV keeps the window as two running sums in double, so every value depends on the order of the additions: both kernels add
+// in that order, one double addition per element; everything else (the differences, the solve, fb_matrix) is pixel-parallel.
+//
+// The vertical running sum of one column of one plane per lane, lanes along x (coalesced without staging):
+//   v = double(float32(M[0] * float32(m + 2))); v += double(M[min(y, h - 1)]) for y = 1 .. m - 1; then for y = 0 .. h - 1
+//   v += double(float32(M[min(y + m, h - 1)] - M[max(y - m - 1, 0)])), V[y] = v (double planes).
+// A lane's addresses are known ahead, so it holds the two rows of M of the next FB_BR_LOOK steps in registers while it adds the
+// current ones: at 1024^2 x 16 pairs there are 1.25 waves per SIMD and only loads in flight hide the memory latency.  Row indices
+// past the last step are clamped, loaded and not used.  Grid (ceil(w / FB_BR_BLOCK), 1, pairs * 5).
+template <int LOOK>
+__global__ __launch_bounds__(FB_BR_BLOCK) void k_fb_box_rows(const float* __restrict__ M, size_t stride, double* __restrict__ V, size_t v_stride, int h, int w,
+                                                             int m) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x * FB_BR_BLOCK + threadIdx.x;
+    if (x >= w) return;
+    const int pair = blockIdx.z / 5, plane = blockIdx.z % 5;
+    const size_t hw = (size_t)h * w;
+    const float* Mc = M + (size_t)pair * stride + (size_t)plane * hw + x;
+    double* Vc = V + (size_t)pair * v_stride + (size_t)plane * hw + x;
+    double v = (double)(Mc[0] * (float)(m + 2));
+    for (int y0 = 1; y0 < m; y0 += LOOK) {
+        float a[LOOK];
+#pragma unroll
+        for (int j = 0; j < LOOK; ++j) a[j] = Mc[(size_t)min(y0 + j, h - 1) * w];
+#pragma unroll
+        for (int j = 0; j < LOOK; ++j) if (y0 + j < m) v = v + (double)a[j];
+    }
+    float a[LOOK], b[LOOK];
+#pragma unroll
+    for (int j = 0; j < LOOK; ++j) {
+        a[j] = Mc[(size_t)min(j + m, h - 1) * w];
+        b[j] = Mc[(size_t)max(min(j, h - 1) - m - 1, 0) * w];
+    }
+    for (int y0 = 0; y0 < h; y0 += LOOK) {
+        float na[LOOK], nb[LOOK];
+#pragma unroll
+        for (int j = 0; j < LOOK; ++j) {
+            const int y = min(y0 + LOOK + j, h - 1);
+            na[j] = Mc[(size_t)min(y + m, h - 1) * w];
+            nb[j] = Mc[(size_t)max(y - m - 1, 0) * w];
+        }
+#pragma unroll
+        for (int j = 0; j < LOOK; ++j) {
+            if (y0 + j < h) {
+                const float d = a[j] - b[j];
+                v = v + (double)d;
+                Vc[(size_t)(y0 + j) * w] = v;
+            }
+            a[j] = na[j]; b[j] = nb[j];
+        }
+    }
+}
+
+// The rest of a box iteration.  The horizontal running sum of a row and plane, columns clamped, in double:
+//   a = V[0] * double(m + 2); a += V[x] for x = 1 .. m - 1; then for x = 0 .. w - 1: a += (V[x + m] - V[x - m - 1]), g[x] = a
+// then g * scale (1 / winsize^2), the solve of k_fb_update, the flow, and M rebuilt from it.  The chains run along x, so a workgroup
+// owns a band of FB_BU_ROWS rows and sweeps x in tiles of FB_BU_COLS columns, three steps per tile:
+//   (a) all lanes read V[x + m] and V[x - m - 1] (coalesced, 32 columns of a row and plane per half wave), form the difference in
+//       double and store it in LDS, one line of FB_BU_PITCH doubles per (row, plane);
+//   (b) one lane per (row, plane), 5 FB_BU_ROWS of the 256, adds its line in order into the running sum it keeps in a register and
+//       overwrites the line with the sums;
+//   (c) all lanes: FB_BU_ROWS / 8 pixels each (lanes along x), the solve, the flow and fb_matrix.
+// A tile costs a workgroup two dependent trips to memory, (a)'s reads and (c)'s gather at the new flow, so (a)'s reads are requested
+// a tile ahead, before (c), and only the gather's latency is left on the path.
+// FB_BU_PITCH is odd: in (b) the 32 lanes of a half wave read 8 bytes at 66 L + 2 t dwords, 32 different bank pairs of the 64; (a)
+// and (c) touch consecutive doubles.  Rows past the band's end inside the last band are clamped, computed and not written.
+// Grid (ceil(h / FB_BU_ROWS), 1, pairs); 5 FB_BU_ROWS FB_BU_PITCH doubles of LDS.
+__global__ __launch_bounds__(FB_BLOCK) void k_fb_box_update(const double* __restrict__ V, size_t v_stride, const float* __restrict__ R0,
+                                                            const float* __restrict__ R1, float* __restrict__ flow, float* __restrict__ M, size_t stride,
+                                                            int h, int w, int m, double scale, int rebuild) {
+#pragma clang fp contract(off)
+    constexpr int LINES = FB_BU_ROWS * 5, LOOK = 8;
+    __shared__ double line[LINES * FB_BU_PITCH];
+    const int y0 = blockIdx.x * FB_BU_ROWS, tid = threadIdx.x;
+    const size_t o = (size_t)blockIdx.z * stride, hw = (size_t)h * w;
+    const double* Vp = V + (size_t)blockIdx.z * v_stride;
+    double a = 0.0;                                                      // (b): the running sum of line tid = row * 5 + plane
+    if (tid < LINES) {
+        const double* row = Vp + (size_t)(tid % 5) * hw + (size_t)min(y0 + tid / 5, h - 1) * w;
+        a = row[0] * (double)(m + 2);
+        for (int x0 = 1; x0 < m; x0 += LOOK) {
+            double s[LOOK];
+#pragma unroll
+            for (int j = 0; j < LOOK; ++j) s[j] = row[min(x0 + j, w - 1)];
+#pragma unroll
+            for (int j = 0; j < LOOK; ++j) if (x0 + j < m) a = a + s[j];
+        }
+    }
+    static_assert(LINES * FB_BU_COLS % FB_BLOCK == 0 && FB_BU_ROWS * FB_BU_COLS % FB_BLOCK == 0, "whole rounds of the workgroup");
+    constexpr int ROUNDS = LINES * FB_BU_COLS / FB_BLOCK;
+    double enter[ROUNDS], leave[ROUNDS];                                 // (a): V[x + m] and V[x - m - 1] of the tile at x0, requested a tile ahead
+    const auto request = [&](int x0) {
+#pragma unroll
+        for (int i = 0; i < ROUNDS; ++i) {
+            const int e = i * FB_BLOCK + tid, t = e % FB_BU_COLS, l = e / FB_BU_COLS;
+            const double* row = Vp + (size_t)(l % 5) * hw + (size_t)min(y0 + l / 5, h - 1) * w;
+            enter[i] = row[min(x0 + t + m, w - 1)];
+            leave[i] = row[max(min(x0 + t, w - 1) - m - 1, 0)];
+        }
+    };
+    request(0);
+    for (int x0 = 0; x0 < w; x0 += FB_BU_COLS) {
+#pragma unroll
+        for (int i = 0; i < ROUNDS; ++i) {
+            const int e = i * FB_BLOCK + tid;
+            line[e / FB_BU_COLS * FB_BU_PITCH + e % FB_BU_COLS] = enter[i] - leave[i];
+        }
+        __syncthreads();
+        if (tid < LINES) {
+            double* d = line + tid * FB_BU_PITCH;
+#pragma unroll
+            for (int t = 0; t < FB_BU_COLS; ++t) {
+                a = a + d[t];
+                d[t] = a;
+            }
+        }
+        __syncthreads();
+        request(x0 + FB_BU_COLS);                                        // in flight during (c); past the last tile: the last column again, unused
+        // a lane's pixels are computed side by side - the loads of all of them in flight together - at coordinates clamped into the
+        // image; only the stores ask whether the pixel exists
+#pragma unroll
+        for (int i = 0; i < FB_BU_ROWS * FB_BU_COLS / FB_BLOCK; ++i) {
+            const int e = i * FB_BLOCK + tid;
+            const bool inside = x0 + e % FB_BU_COLS < w && y0 + e / FB_BU_COLS < h;
+            const int x = min(x0 + e % FB_BU_COLS, w - 1), y = min(y0 + e / FB_BU_COLS, h - 1);
+            const double* g = line + (e / FB_BU_COLS) * 5 * FB_BU_PITCH + e % FB_BU_COLS;
+            const double g11 = g[0] * scale, g12 = g[FB_BU_PITCH] * scale, g22 = g[2 * FB_BU_PITCH] * scale, h1 = g[3 * FB_BU_PITCH] * scale,
+                         h2 = g[4 * FB_BU_PITCH] * scale;
+            const double p0 = g11 * g22, p1 = g12 * g12;
+            const double idet = 1.0 / ((p0 - p1) + 1e-3);
+            const double a0 = g11 * h2, a1 = g12 * h1, c0 = g22 * h1, c1 = g12 * h2;
+            const float dx = (float)((a0 - a1) * idet), dy = (float)((c0 - c1) * idet);
+            const size_t px = (size_t)y * w + x;
+            float v[5];
+            if (rebuild) fb_matrix_values(R0 + o, R1 + o, h, w, x, y, dx, dy, v);
+            if (inside) {
+                flow[o + px] = dx;
+                flow[o + hw + px] = dy;
+                if (rebuild) for (int c = 0; c < 5; ++c) M[o + c * hw + px] = v[c];
+            }
+        }
+        __syncthreads();                                                 // the next tile's (a) overwrites the lines
+    }
 }
 
 // The results: the float32 flow promoted to double and multiplied by delta_x / delta_t; speed = sqrt(v_x * v_x + v_y * v_y) in double.

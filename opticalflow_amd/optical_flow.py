@@ -66,6 +66,7 @@ atexit.register(release_device_memory)
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
            "apply_adaptive_threshold", "apply_clahe", "downsample_movie", "conduct_opencv_flow", "farneback_plan",
+           "calcOpticalFlowFarneback", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_FARNEBACK_GAUSSIAN",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
            "subsample_velocities_for_visualisation", "costum_imshow", "make_velocity_overlay_movie",
            "make_joint_overlay_movie", "release_device_memory"]
@@ -98,6 +99,9 @@ FARNEBACK_ARGUMENTS = ("pyr_scale", "levels", "winsize", "iterations", "poly_n",
 FARNEBACK_MIN_SIDE = 16
 FARNEBACK_MAX_WINSIZE = 129          # FB_MAX_WINSIZE of csrc/vof_farneback.hpp: a row segment and its two margins live in LDS
 FARNEBACK_MAX_POLY_N = 10            # FB_MAX_POLY_N
+FARNEBACK_WINDOWS = ("gaussian", "box")
+OPTFLOW_USE_INITIAL_FLOW = 4         # cv2's flag bits
+OPTFLOW_FARNEBACK_GAUSSIAN = 256
 
 
 def _f32(value):
@@ -233,7 +237,17 @@ def _farneback_arguments(shape, kwargs):
     return a
 
 
-def conduct_opencv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *, device=0, output="numpy", **kwargs):
+def _farneback_window(window, winsize):
+    """``window`` checked; True for the box window, whose limits on ``winsize`` are checked too."""
+    if window not in FARNEBACK_WINDOWS:
+        raise ValueError(f"window must be one of {FARNEBACK_WINDOWS}, not {window!r}")
+    if window == "box" and winsize < 2:
+        raise ValueError("the box window needs winsize >= 2: at winsize=1 OpenCV's running sums start with row 0 and column 0 counted "
+                         "once too often and never lose the surplus, which this build does not restate")
+    return window == "box"
+
+
+def conduct_opencv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *, device=0, output="numpy", window="gaussian", **kwargs):
     """Farnebaeck's dense flow of every frame pair on the GPU; positional arguments and the result dict as
     source/optical_flow.py:220-279, which calls ``cv2.calcOpticalFlowFarneback(blurred[k], movie[k + 1], ..., flags=
     cv2.OPTFLOW_FARNEBACK_GAUSSIAN, **kwargs)`` per pair.
@@ -255,13 +269,18 @@ def conduct_opencv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *
     depth, so only the two depths the scripts use are served: **uint8** and **float64** movies; another dtype raises
     ``ValueError``: cast the movie.  ``ValueError`` also for a NaN or Inf in the movie, for frames smaller than 16 x 16 and
     outside ``0 < pyr_scale < 1``, ``levels >= 0``, ``1 <= winsize <= 129``, ``iterations >= 0``, ``1 <= poly_n <= 10``.
-    ``output="torch"``: ``movie`` may be a device tensor and every array of the result stays on the device (float64 tensors)."""
+    ``output="torch"``: ``movie`` may be a device tensor and every array of the result stays on the device (float64 tensors).
+
+    ``window="box"`` (not in the reference's signature) runs OpenCV's default window instead, the one ``flags=0`` selects: the
+    ``2 (winsize // 2) + 1`` box, summed as OpenCV sums it - two running sums in double - and divided by ``winsize**2``;
+    it needs ``winsize >= 2``.  Any other value than ``"gaussian"`` or ``"box"`` is a ``ValueError``; ``flags`` stays a ``TypeError``."""
     if output not in ("numpy", "torch"):
         raise ValueError("output must be 'numpy' or 'torch'")
     shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
     if len(shape) != 3:
         raise ValueError("movie must be a 3-D array (frames, x, y)")
     a = _farneback_arguments(shape, kwargs)
+    box = _farneback_window(window, a["winsize"])
     if shape[0] < 2:
         raise ValueError("movie needs at least two frames")
     name = _movie_dtype_name(movie)
@@ -276,7 +295,7 @@ def conduct_opencv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *
         frames = np.ascontiguousarray(source, dtype=np.float64)
         with _device_context(N_i, N_j, 1, device) as solver:
             first = frames if smoothing_sigma is None else blur_movie(frames, smoothing_sigma=smoothing_sigma, device=device, _solver=solver)
-            v_x, v_y, speed = solver.farneback_host(first[:-1], frames[1:], plan, a["iterations"], velocity_scale)
+            v_x, v_y, speed = solver.farneback_host(first[:-1], frames[1:], plan, a["iterations"], velocity_scale, box=box)
         analysed = movie if smoothing_sigma is None else first
     else:
         import torch
@@ -290,9 +309,57 @@ def conduct_opencv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *
                 torch.cuda.synchronize(dev)
                 solver.blur_dev(frames, first, T, gaussian_taps(smoothing_sigma))
             torch.cuda.synchronize(dev)                  # the library launches on its own stream
-            solver.farneback_dev(first[:-1], frames[1:], T - 1, plan, a["iterations"], velocity_scale, v_x, v_y, speed)
+            solver.farneback_dev(first[:-1], frames[1:], T - 1, plan, a["iterations"], velocity_scale, v_x, v_y, speed, box=box)
         analysed = movie if smoothing_sigma is None else first
     return dict(v_x=v_x, v_y=v_y, speed=speed, original_data=analysed, delta_x=delta_x, delta_t=delta_t)
+
+
+def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, *, device=0, output="numpy"):
+    """``cv2.calcOpticalFlowFarneback`` of one frame pair on the GPU, with ``cv2``'s positional signature: the float32 flow
+    ``(N_i, N_j, 2)`` in OpenCV's channel order (channel 0 along the columns, channel 1 along the rows).
+
+    ``flags=0`` is OpenCV's default, the box window (``conduct_opencv_flow(..., window="box")``); ``flags=
+    OPTFLOW_FARNEBACK_GAUSSIAN`` (256) is the Gaussian window, the same bits as ``conduct_opencv_flow`` gives.  ``flow`` is
+    accepted and ignored: without ``OPTFLOW_USE_INITIAL_FLOW`` it is an output buffer in ``cv2``.  ``OPTFLOW_USE_INITIAL_FLOW`` (4)
+    is not built - the reference never passes it - and it or any other bit is a ``ValueError``.
+
+    ``prev`` and ``next`` are 2-D, of equal shape, both uint8 or both float64 (as ``conduct_opencv_flow``: OpenCV converts each
+    depth to float32 in its own way).  Limits and error types are those of ``conduct_opencv_flow``; in addition the box window
+    needs ``winsize >= 2``.  ``output="torch"``: the frames may be device tensors and the result stays on the device."""
+    if output not in ("numpy", "torch"):
+        raise ValueError("output must be 'numpy' or 'torch'")
+    if isinstance(flags, bool) or int(flags) != flags:
+        raise TypeError("flags must be an integer")
+    flags = int(flags)
+    if flags & OPTFLOW_USE_INITIAL_FLOW:
+        raise ValueError("OPTFLOW_USE_INITIAL_FLOW is not built: the reference never passes an initial flow")
+    if flags & ~OPTFLOW_FARNEBACK_GAUSSIAN:
+        raise ValueError(f"flags={flags}: only 0 (the box window) and OPTFLOW_FARNEBACK_GAUSSIAN = 256 are built")
+    shapes = [tuple(f.shape) if hasattr(f, "shape") else np.asarray(f).shape for f in (prev, next)]
+    if len(shapes[0]) != 2 or shapes[0] != shapes[1]:
+        raise ValueError(f"prev and next must be 2-D images of one shape, not {shapes[0]} and {shapes[1]}")
+    names = [_movie_dtype_name(f) for f in (prev, next)]
+    if names[0] != names[1] or names[0] not in ("uint8", "float64"):
+        raise ValueError(f"calcOpticalFlowFarneback serves two uint8 or two float64 frames only (OpenCV converts each depth to float32 "
+                         f"in its own way), not {names[0]} and {names[1]}: cast the frames")
+    N_i, N_j = shapes[0]
+    a = _farneback_arguments((1, N_i, N_j), dict(pyr_scale=pyr_scale, levels=levels, winsize=winsize, iterations=iterations, poly_n=poly_n,
+                                                 poly_sigma=poly_sigma))
+    box = _farneback_window("gaussian" if flags & OPTFLOW_FARNEBACK_GAUSSIAN else "box", a["winsize"])
+    plan = farneback_plan(N_i, N_j, a["pyr_scale"], a["levels"], a["winsize"], a["poly_n"], a["poly_sigma"])
+    if output == "numpy":
+        first, second = (np.ascontiguousarray(np.asarray(f)[None], dtype=np.float64) for f in (prev, next))
+        with _device_context(N_i, N_j, 1, device) as solver:
+            v_x, v_y, _ = solver.farneback_host(first, second, plan, a["iterations"], 1.0, box=box)
+        return np.stack([v_x[0], v_y[0]], axis=2).astype(np.float32)         # exact: float32 values promoted, times 1.0
+    import torch
+    dev = torch.device("cuda", int(device))
+    first, second = (torch.as_tensor(f).to(device=dev, dtype=torch.float64).contiguous()[None] for f in (prev, next))
+    v_x, v_y, speed = (torch.empty((1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(3))
+    with _device_context(N_i, N_j, 1, device) as solver:
+        torch.cuda.synchronize(dev)                      # the library launches on its own stream
+        solver.farneback_dev(first, second, 1, plan, a["iterations"], 1.0, v_x, v_y, speed, box=box)
+    return torch.stack([v_x[0], v_y[0]], dim=2).to(torch.float32)
 
 
 def blur_movie(movie, smoothing_sigma, device=0, _solver=None):
