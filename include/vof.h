@@ -216,7 +216,10 @@ int vof_solve_stack_dev(vof_ctx* ctx, const double* movie, int n_frames, const v
 
 /* Replaces blur_movie (OF.py:282-306): per-frame Gaussian blur, scipy.ndimage.gaussian_filter semantics
  * (mode='nearest'); weights = the 2*radius+1 normalised taps in host memory (radius = int(4*sigma + 0.5) for the
- * reference's skimage call).  The context fixes the frame size; any number of frames. */
+ * reference's skimage call).  The context fixes the frame size; any number of frames.
+ * Scratch: the blur, the general path of the box flow, the sweeps, the channel comparison and the frame-wise calls below take
+ * their device scratch from one buffer of the context, allocated on first use, grown on demand to the largest request served
+ * (not their sum), kept, and freed by vof_destroy; every call lays it out anew and nothing in it survives the call. */
 int vof_blur_stack_dev(vof_ctx* ctx, const double* in_dev, double* out_dev, int n_frames, const double* weights, int radius);
 int vof_blur_stack_host(vof_ctx* ctx, const double* in_host, double* out_host, int n_frames, const double* weights, int radius);
 
@@ -229,7 +232,8 @@ int vof_blur_stack_host(vof_ctx* ctx, const double* in_host, double* out_host, i
  * all zero and zeros at the pixels whose determinant is 0.0; 0: n = pixels in the window, speed filled, such pixels NaN.
  * movie: (n_frames, n_i, n_j) float64; outputs (n_frames - 1, n_i, n_j) float64, caller allocated, every element written;
  * net_remodelling may be NULL without include_remodelling (zeros are written otherwise).  Box sizes up to 31 run in one fused
- * kernel, larger ones through scratch planes of the context.  _dev: device pointers; _host: host pointers, staged by the library. */
+ * kernel, larger ones through scratch planes (the context's scratch buffer, above).  _dev: device pointers; _host: host
+ * pointers, staged by the library. */
 int vof_box_flow_dev(vof_ctx* ctx, const double* movie, int n_frames, int box_size, double delta_x, double delta_t,
                      int include_remodelling, int reference_quirks,
                      double* v_x, double* v_y, double* speed, double* net_remodelling);
@@ -293,7 +297,7 @@ typedef struct vof_boxsize_stats {
  * half width 0 to max int(box / 2), only ever adding terms to float64 accumulators, so a box costs O(1) per pixel; the fields
  * of a box do not depend on the other boxes of the list.  The frames are blurred first if blur_weights != NULL (taps as for
  * vof_blur_stack_*).  Pairs are processed in chunks sized by the free device memory (_host: at most the context's
- * max_pairs_in_flight at a time); scratch planes are kept on the context.
+ * max_pairs_in_flight at a time); the scratch planes are the context's one scratch buffer (vof_blur_stack_*).
  * stats: n_boxes records, host memory, required.  Mean / variance are two-pass reductions on the device.
  * histogram_edges: NULL, or the histogram_bins + 1 edges of np.linspace(lo, hi, bins + 1) in host memory; histograms (host,
  *   n_boxes x histogram_bins int64) then receives np.histogram(speed, bins, (lo, hi))[0] of every box exactly.
@@ -329,9 +333,9 @@ typedef struct vof_blursize_stats {
  * intensity histogram): for each of the n_sigmas >= 1 tap vectors (blur_weights: 2 * blur_radii[s] + 1 taps as for
  * vof_blur_stack_*, concatenated in list order; any order, duplicates allowed) the movie is blurred and what vof_box_flow_*
  * computes for box_size from the blurred frames is reduced, in one call.  The movie is uploaded once; per entry all frames are
- * blurred into a scratch stack of the context, the box flow runs with the kernels and the fused / general choice of
- * vof_box_flow_dev (same bits), for pairs in chunks sized as in vof_vary_boxsize_*.  The results of an entry do not depend on
- * the other entries of the list.
+ * blurred into a scratch stack (the context's scratch buffer), the box flow runs with the kernels and the fused / general
+ * choice of vof_box_flow_dev (same bits), for pairs in chunks sized as in vof_vary_boxsize_*.  The results of an entry do not
+ * depend on the other entries of the list.
  * stats: n_sigmas records, host memory, required.  Mean / variance are two-pass reductions on the device.
  * histogram_edges / histogram_bins / histograms: as for vof_vary_boxsize_* (n_sigmas x histogram_bins int64).
  * angle_bins: 0, or 1 .. 128 bins of the flow direction a = acos(v_y / speed) * sign(v_x) / pi (float64, sign(0) = 0) on (-1, 1):
@@ -428,9 +432,9 @@ int vof_compare_flows_host(vof_ctx* ctx, const double* movie_a, const double* mo
  * reference's integer cast would be platform-dependent or wrap:
  *   threshold: a non-finite value, min < 0 or max <= 0;   CLAHE: a non-finite value, min < 0 or max >= 65536.
  * Frames are processed in chunks of frames_in_flight (0: sized from the free device memory, 16 at most).  The scratch memory,
- * one buffer that this group, the resize and Farnebaeck's flow below share, holds per frame in flight: threshold 4 bytes per
- * pixel, CLAHE 65536 x 6 bytes per tile, _host the staged frame and its result; once per call: the records of the range
- * reduction (and the tables of the calls below).  It is allocated on first use, grown on demand, kept, and freed by
+ * the context's one scratch buffer (vof_blur_stack_*), holds per frame in flight: threshold 4 bytes per pixel, CLAHE
+ * 65536 x 6 bytes per tile, _host the staged frame and its result; once per call: the records of the range reduction (and the
+ * tables of the calls below).  It is allocated on first use, grown on demand, kept, and freed by
  * vof_destroy; nothing in it is kept from one call to the next.  Results do not depend on frames_in_flight.
  * Profiler: class VOF_K_PREPROCESS, the `level` is the stage: 0 range, 1 row sums, 2 threshold, 3 histograms, 4 tables, 5 blend.
  *

@@ -117,15 +117,8 @@ struct vof_ctx {
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_solved[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr}, ev_uploaded[2] = {nullptr, nullptr};
     double* st_movie2 = nullptr;                                 // second frame buffer (upload of the next batch under the solve)
-    double *blur_tmp = nullptr, *blur_w = nullptr, *blur_io = nullptr;   // Gaussian blur scratch (lazy)
-    double* bf_scratch = nullptr;                                        // box flow, general path: derived planes + row sums (lazy)
-    double* sw_scratch = nullptr;                                        // box-size / blur sweep, channel comparison: the planes of the one in progress (lazy; sweep_scratch)
-    size_t sw_planes = 0;                                                // planes of sw_scratch
-    bool sw_by_budget = false;                                           // sw_scratch was sized by the free memory, not by the request
-    char* sw_aux = nullptr;                                              // box-size and blur sweep: edges, probe indices, counters, probe values (lazy)
-    size_t sw_aux_bytes = 0;
-    char* pre_buf = nullptr;                                             // frame-wise calls: range records, tables once per call; work regions and staged frames per frame in flight (lazy; FrameChunks carves it anew in every call)
-    size_t pre_bytes = 0;
+    char* scratch = nullptr;                                             // the one scratch buffer of the blur, the box flow's general path, the sweeps, the comparison and the frame-wise calls (lazy, grown on demand; the Scratch of the call in progress carves it anew)
+    size_t scratch_bytes = 0;
     bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
     bool bl_lds_set = false;                                             // tiled blur: dynamic LDS limit raised
     bool ls_lds_set = false;                                             // Liu-Shen flow, fused kernel: dynamic LDS limit raised
@@ -302,8 +295,8 @@ void prof_collect(vof_ctx* c) {
     } while (0)
 
 // Caller host memory (pageable) <-> device through a pinned bounce buffer on the context's stream: no null stream, and nothing
-// for the runtime to pin on the fly.  Every copy of the debug entry points and of the box / Liu-Shen
-// host variants; the caller's memory is free again on return.
+// for the runtime to pin on the fly.  Every copy of the debug entry points, the box flow and Liu-Shen host
+// variants, the sweeps, the comparison, the frame-wise calls and the blur's taps - not the frames of vof_blur_stack_host (blur_stack).
 constexpr size_t BOUNCE_BYTES = (size_t)8 << 20;
 int d2h_bounced(vof_ctx* c, void* host, const void* dev, size_t bytes) {
     if (!c->h_bounce) HIPCHK(hipHostMalloc((void**)&c->h_bounce, BOUNCE_BYTES));
@@ -2517,6 +2510,396 @@ std::vector<HostRegion> plan_output_regions(double* const* outs, const std::vect
     return regions;
 }
 
+// ---- the scratch arena of one ABI call -----------------------------------------------------------
+// The blur, the box flow's general path, the sweeps, the channel comparison and the frame-wise calls take their device scratch
+// from the context's one buffer through a Scratch on the stack of the call: the call declares typed regions, plan() picks the
+// units in flight, grows the buffer and stores the addresses.  One walk measures and carves, so size and layout cannot disagree.
+// The rule: an arena is planned exactly once per ABI call, and every address taken from it is dead when the call returns.  A
+// helper that needs scratch declares it into its caller's arena (blur_regions, box_flow_regions, sweep_tail_regions) and never
+// plans one; no entry point that plans an arena calls another that does.
+struct Scratch {
+    struct Region { void* ptr; size_t fixed, unit; };              // ptr: where the carve stores the region's address; bytes: fixed + units * unit
+    vof_ctx* const c;
+    std::vector<Region> regions;
+    int units = 0; size_t bytes = 0;                               // what plan() settled on
+    explicit Scratch(vof_ctx* c_) : c(c_) {}
+    Scratch(const Scratch&) = delete;                              // the regions point at the caller's pointers
+    // The request.  *p is the region's address after plan(): `count` elements once per call, per unit in flight (align_units:
+    // each at a multiple of 256 bytes; returns the stride in elements), or per unit and once more (the frames of n pairs: n + 1).
+    static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+    template <class T> void once(T** p, size_t count) { regions.push_back({p, count * sizeof(T), 0}); }
+    template <class T> size_t per_unit(T** p, size_t count, bool align_units = false) {
+        regions.push_back({p, 0, align_units ? up256(count * sizeof(T)) : count * sizeof(T)});
+        return regions.back().unit / sizeof(T);
+    }
+    template <class T> void per_unit_plus_one(T** p, size_t count) { regions.push_back({p, count * sizeof(T), count * sizeof(T)}); }
+
+    // The layout, stated once: region after region, each at a multiple of 256 bytes.  Returns the bytes `n` units in flight
+    // take; a null base only measures.
+    size_t carve(char* base, int n) const {
+        size_t at = 0;
+        for (const Region& r : regions) {
+            if (base) { char* q = base + at; memcpy(r.ptr, &q, sizeof q); }
+            at += up256(r.fixed + (size_t)n * r.unit);
+        }
+        return at;
+    }
+
+    // The units in flight - min(want, at_most), or the largest count (one at least) that needs no more than the buffer or `share`
+    // of the memory that is free or the arena's - and the buffer.  Returns the count, or < 0 (out_of_memory(): the allocation failed).
+    int plan(int want, int at_most, double share) {
+        HIPCHK(hipSetDevice(c->device));
+        size_t budget = c->scratch_bytes, fr = 0, tot = 0;
+        units = std::max(1, std::min(want, at_most));
+        if (carve(nullptr, units) > budget) {
+            HIPCHK(hipMemGetInfo(&fr, &tot));
+            budget = std::max(budget, (size_t)(share * (double)(fr + budget)));
+        }
+        while (units > 1 && carve(nullptr, units) > budget) --units;
+        bytes = carve(nullptr, units);
+        if (bytes > c->scratch_bytes) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            if (int rc = dev_free(c, c->scratch)) return rc;
+            c->scratch = nullptr; c->scratch_bytes = 0;
+            if (int rc = dev_alloc(c, &c->scratch, bytes)) { (void)hipGetLastError(); return rc; }
+            c->scratch_bytes = bytes;
+        }
+        carve(c->scratch, units);
+        return units;
+    }
+    bool out_of_memory() const { return bytes > c->scratch_bytes; }   // the buffer does not hold the planned layout
+};
+
+// ---- frame chunks: the walk of the frame-wise calls through the scratch arena -----------------------
+constexpr int PRE_MAX_FLIGHT = 16;        // units in flight when the caller leaves the number to the library
+constexpr int PRE_MAX_WANT = 4096;        // ... and at most when it does not (grid z)
+
+// One call of the adaptive threshold, CLAHE, the resize or Farnebaeck's flow over a stack of `n` units (frames or
+// pairs), on the stack of that call: the call declares its regions into the arena sc, plan() sizes the chunk and carves the
+// buffer, range() reduces a stack, run() walks the chunks.  What a staged input holds is recorded here alone: nothing staged
+// outlives the call.
+struct FrameChunks {
+    struct In { const double* stack; double* slot; int k0, nf; };  // _host: slot holds units [k0, k0 + nf) of stack (nf 0: nothing)
+    struct Out { char* caller; size_t bytes; char* slot; };        // bytes per unit
+    vof_ctx* const c; const char* const what;                      // what: the call, for messages
+    const int n, want; const bool host;                            // units; the caller's frames_in_flight
+    const size_t fs;                                               // doubles per unit of an input stack
+    Scratch sc;
+    int cap = 0;                                                   // units in flight (plan)
+    PpRange* part = nullptr;                                       // the range reduction's partial records, then its result
+    double rg[3] = {};                                             // ... and what range() found
+    In in[2] = {}; Out out[3] = {}; int n_in = 0, n_out = 0;
+
+    FrameChunks(vof_ctx* c_, const char* what_, int n_, int want_, bool host_) : c(c_), what(what_), n(n_), want(want_), host(host_), fs(frame_stride(c_)), sc(c_) {
+        sc.once(&part, (size_t)PP_RANGE_BLOCKS + 1);
+    }
+
+    // what every frame-wise entry point checks first
+    static int check(vof_ctx* c, std::initializer_list<const void*> pointers, int n, const char* n_name) {
+        if (!c) return -1;
+        for (const void* p : pointers) if (!p) { c->err = "NULL pointer"; return -1; }
+        if (n < 1) { c->err = std::string(n_name) + " must be >= 1"; return -1; }
+        return 0;
+    }
+
+    void input(const double* stack) {                              // fs doubles per unit; _host: staged
+        if (host) sc.per_unit(&in[n_in].slot, fs);
+        in[n_in++].stack = stack;
+    }
+    void output(void* caller, size_t unit_bytes) {                 // _host: staged, then copied to `caller`
+        if (host) sc.per_unit(&out[n_out].slot, unit_bytes);
+        out[n_out].caller = (char*)caller; out[n_out++].bytes = unit_bytes;
+    }
+
+    // the chunk size - `want`, or 16 where that is left to the library, within a quarter of the free device memory - and the arena
+    int plan() {
+        const int rc = sc.plan(want > 0 ? want : PRE_MAX_FLIGHT, std::min(PRE_MAX_WANT, n), 0.25);
+        if (rc < 0 && sc.out_of_memory())
+            c->err = std::string(what) + ": no device memory for " + std::to_string(sc.bytes >> 20) + " MiB of scratch (" +
+                     std::to_string(sc.units) + " frame(s) in flight): " + c->err;
+        cap = rc;
+        return rc < 0 ? rc : 0;
+    }
+
+    // Units [k0, k0 + nf) of input s on the device: the caller's own memory, or the slot - uploaded unless it holds exactly these
+    int staged(int s, int k0, int nf, const double** p) {
+        In& i = in[s];
+        *p = host ? i.slot : i.stack + (size_t)k0 * fs;
+        if (!host || (i.nf == nf && i.k0 == k0)) return 0;
+        if (int rc = h2d_bounced(c, i.slot, i.stack + (size_t)k0 * fs, (size_t)nf * fs * sizeof(double))) return rc;
+        i.k0 = k0; i.nf = nf;
+        return 0;
+    }
+
+    // rg = (max, min of the finite values, non-finite count) of the whole of input s (_host: chunk by chunk through its slot), to
+    // `report` too if there is one; then return code 1 and the message if anything is non-finite or outside the permitted [lo, hi]
+    int range(int s, double lo, double hi, const char* outside, const char* note = "", double* report = nullptr) {
+        PpRange* const rng = part + PP_RANGE_BLOCKS;
+        PpRange acc{-INFINITY, INFINITY, 0};
+        const int chunk = host ? cap : n;
+        for (int k0 = 0; k0 < n; k0 += chunk) {
+            const int nf = std::min(chunk, n - k0);
+            const double* src;
+            if (int rc = staged(s, k0, nf, &src)) return rc;
+            const size_t m = (size_t)nf * fs;
+            const int nb = (int)std::min<size_t>(PP_RANGE_BLOCKS, (m + 8 * PP_BLOCK - 1) / (8 * PP_BLOCK));
+            c->cur_units = nf;
+            {
+                Prof prof(c, VOF_K_PREPROCESS, PP_ST_RANGE, 8.0 * fs);
+                k_pp_range<<<nb, PP_BLOCK, 0, c->stream>>>(src, m, part);
+                k_pp_range_final<<<1, 64, 0, c->stream>>>(part, nb, rng);
+            }
+            HIPCHK(hipGetLastError());
+            PpRange r;
+            if (int rc = d2h_bounced(c, &r, rng, sizeof r)) return rc;
+            acc.vmax = std::max(acc.vmax, r.vmax); acc.vmin = std::min(acc.vmin, r.vmin); acc.bad += r.bad;
+        }
+        rg[0] = acc.vmax; rg[1] = acc.vmin; rg[2] = (double)acc.bad;
+        if (report) memcpy(report, rg, sizeof rg);
+        const char* found = rg[2] > 0 ? "non-finite values" : (rg[1] < lo || rg[0] > hi ? outside : nullptr);
+        if (!found) return 0;
+        c->err = std::string(what) + ": the movie holds " + found + note;
+        return 1;
+    }
+
+    // The chunks in turn: body(k0, nf, inputs, outputs) enqueues the kernels of units [k0, k0 + nf) - device pointers, one per
+    // declared input and output - and returns 0; _host: the outputs are then copied to the caller's arrays.
+    template <class Body>
+    int run(Body&& body) {
+        for (int k0 = 0; k0 < n; k0 += cap) {
+            const int nf = std::min(cap, n - k0);
+            const double* src[2] = {}; void* dst[3] = {};
+            for (int s = 0; s < n_in; ++s) if (int rc = staged(s, k0, nf, &src[s])) return rc;
+            for (int a = 0; a < n_out; ++a) dst[a] = host ? out[a].slot : out[a].caller + (size_t)k0 * out[a].bytes;
+            c->cur_units = nf;
+            if (int rc = body(k0, nf, src, dst)) return rc;
+            HIPCHK(hipGetLastError());
+            for (int a = 0; host && a < n_out; ++a)
+                if (int rc = d2h_bounced(c, out[a].caller + (size_t)k0 * out[a].bytes, dst[a], (size_t)nf * out[a].bytes)) return rc;
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+};
+
+// (count, mean, M2 = sum (x - mean)^2) of one chunk, exact two-pass; chunks are merged with Chan's formula
+struct Moments {
+    double n = 0, mean = 0, m2 = 0;
+    void merge(double nb, double meanb, double m2b) {
+        if (nb == 0) return;
+        double nt = n + nb, d = meanb - mean;
+        m2 += m2b + d * d * n * nb / nt;
+        mean += d * nb / nt;
+        n = nt;
+    }
+};
+
+// ---- sweeps of the box flow: what vary_boxsize and vary_blursize share --------------------------------------------
+constexpr int BS_MAX_CHUNK = 32;          // pairs per launch (grid z) at most; more adds nothing once the chip is full
+
+// Mean and variance of a field per list entry, shared by the box-size and the blur sweep: the two-pass reduction of
+// vof_field_moments_dev per pair on the device, sums [field][pass][entry][pair][3]; a pair is the unit the host merges.
+struct PairMoments {
+    double* d_mom; double* d_part;        // device: the sums; the partials of one chunk
+    size_t n_mom;                         // n_entries * P * 3
+    int n_entries, P, mom_blk;
+};
+
+inline int pair_moments_blocks(size_t fs) { return (int)std::min<size_t>(256, std::max<size_t>(1, (fs + 4 * RBLK - 1) / (4 * RBLK))); }
+
+// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote x: no host round trip in a sweep
+static void pair_moments_enqueue(vof_ctx* c, const PairMoments& m, const double* x, size_t fs, int field, int b, int k0, int np) {
+    const dim3 gm(m.mom_blk, np);
+    double* first = m.d_mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P + k0) * 3;
+    double* second = first + m.n_mom;
+    Prof prof(c, VOF_K_REDUCE, 0, 16.0 * fs);
+    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, nullptr, m.d_part);
+    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, first);
+    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, first, m.d_part);
+    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, second);
+}
+
+// mom: the host copy of d_mom.  Pairs merged in order with Chan's formula; per pair the arithmetic of chunk_moments
+static Moments pair_moments_merged(const PairMoments& m, const double* mom, size_t fs, int field, int b) {
+    Moments acc;
+    const double* first = mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P) * 3;
+    const double* second = first + m.n_mom;
+    const double n = (double)fs;
+    for (int k = 0; k < m.P; ++k) {
+        double mean = first[3 * k] / n;
+        const double s0 = second[3 * k], s1 = second[3 * k + 1];
+        mean += s0 / n;                                         // first-order correction of the rounded mean
+        acc.merge(n, mean, s1 - s0 * s0 / n);
+    }
+    return acc;
+}
+
+// what every sweep is asked for besides its list
+struct SweepBase {
+    const double* movie; int n_frames;
+    double delta_x, delta_t; int remodel, quirks;
+    const double* edges; int bins; int64_t* hist;               // speed
+    const int32_t* probe_ij; int n_probes; double* probe_out;
+    double* outs[4];                      // v_x, v_y, speed, net_remodelling: all NULL = stats only
+    bool host;                            // movie and outs are host memory
+};
+
+static int sweep_check(vof_ctx* c, const SweepBase& r, const void* stats) {
+    if (!r.movie) { c->err = "movie is NULL"; return -1; }
+    if (!stats) { c->err = "stats is NULL"; return -1; }
+    if (r.n_frames < 2) { c->err = "need at least two frames"; return -1; }
+    if (r.delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
+    if (r.edges && (r.bins < 1 || !r.hist)) { c->err = "histogram_edges needs histogram_bins >= 1 and histograms"; return -1; }
+    if (r.edges && !(r.edges[r.bins] > r.edges[0])) { c->err = "histogram_edges must increase"; return -1; }
+    if (r.probe_ij) {
+        if (r.n_probes < 1 || !r.probe_out) { c->err = "probe_ij needs n_probes >= 1 and probe_speeds"; return -1; }
+        for (int l = 0; l < r.n_probes; ++l)
+            if (r.probe_ij[2 * l] < 0 || r.probe_ij[2 * l] >= c->Ni || r.probe_ij[2 * l + 1] < 0 || r.probe_ij[2 * l + 1] >= c->Nj) {
+                c->err = "probe outside the image"; return -1;
+            }
+    }
+    const bool any = r.outs[0] || r.outs[1] || r.outs[2] || r.outs[3];
+    if (any && (!r.outs[0] || !r.outs[1] || !r.outs[2])) { c->err = "v_x, v_y and speed must be given together (or all NULL)"; return -1; }
+    if (any && r.remodel && !r.outs[3]) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
+    return 0;
+}
+
+// pairs a sweep keeps in flight at most: a _host sweep stages no more than the context's slots
+inline int sweep_want(const vof_ctx* c, const SweepBase& r) {
+    return std::min(std::min(r.n_frames - 1, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
+}
+
+// where the fields of pairs k0 .. of entry b go on the device: the caller's stacks (_dev with fields) or the chunk planes
+struct SweepDst {
+    double* f[4];
+    size_t oo;                            // offset of the chunk in the caller's stacks
+    bool keep_v, keep_g;                  // v_x / v_y and net_remodelling are wanted (speed always is)
+};
+
+static SweepDst sweep_dst(const SweepBase& r, double* const chunk_out[4], size_t fs, int b, int k0) {
+    SweepDst d;
+    const bool fields = r.outs[0] != nullptr;
+    d.oo = ((size_t)b * (r.n_frames - 1) + k0) * fs;
+    for (int f = 0; f < 4; ++f) d.f[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + d.oo : chunk_out[f];
+    d.keep_v = fields;
+    d.keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
+    return d;
+}
+
+// _host with fields: np pairs from the chunk planes into the caller's stacks; net_remodelling is zero where it was not computed
+static int sweep_copy_out(vof_ctx* c, const SweepBase& r, const SweepDst& d, size_t fs, int np) {
+    if (!r.host) return 0;
+    const size_t bytes = (size_t)np * fs * sizeof(double);
+    for (int f = 0; f < 4; ++f) {
+        if (!r.outs[f]) continue;
+        if (f == 3 && !r.remodel) memset(r.outs[f] + d.oo, 0, bytes);
+        else if (int rc = d2h_bounced(c, r.outs[f] + d.oo, d.f[f], bytes)) return rc;
+    }
+    return 0;
+}
+
+// The statistics every sweep keeps per list entry: histogram and non-finite count of the speed, the speed at the probes, mean
+// and variance of speed and net_remodelling.  What the kernels read and write are regions of the sweep's arena.  The counters
+// - the tail's, then the sweep's own - are the last regions the sweep declares: one span from d_bad to the arena's end, zeroed
+// by one memset and brought back by one copy.
+struct SweepTail {
+    const SweepBase* r; const char* name;
+    int n; size_t fs;
+    PairMoments pm;
+    size_t n_hist, n_probe, n_mom_all;
+    double *d_edges, *d_probe;
+    unsigned long long *d_bad, *d_hist;
+    int32_t* d_pij;
+    std::vector<unsigned long long> counters;     // host copy of the span (sweep_tail_finish)
+    const unsigned long long* host(const unsigned long long* dev) const { return counters.data() + (dev - d_bad); }
+};
+
+// declares the tail's regions, the counters last: the sweep's own counters follow, everything else of the sweep comes before
+static void sweep_tail_regions(Scratch& sc, SweepTail& t, const SweepBase& r, const char* name, int n) {
+    const int P = r.n_frames - 1;
+    t.r = &r; t.name = name; t.n = n; t.fs = frame_stride(sc.c);
+    t.n_hist = r.edges ? (size_t)n * r.bins : 0;
+    t.n_probe = r.probe_ij ? (size_t)n * P * r.n_probes : 0;
+    // moments: per field (speed, net_remodelling), pass, entry and pair the three sums of k_sum3; then the partials of a chunk
+    const size_t n_mom = (size_t)n * P * 3;
+    t.n_mom_all = 2 * (r.remodel ? 2 : 1) * n_mom;
+    t.pm = PairMoments{nullptr, nullptr, n_mom, n, P, pair_moments_blocks(t.fs)};
+    sc.once(&t.d_edges, r.edges ? (size_t)r.bins + 1 : 0);
+    sc.once(&t.d_probe, t.n_probe);
+    sc.once(&t.pm.d_mom, t.n_mom_all);
+    sc.per_unit(&t.pm.d_part, (size_t)3 * t.pm.mom_blk);
+    sc.once(&t.d_pij, r.probe_ij ? (size_t)2 * r.n_probes : 0);
+    sc.once(&t.d_bad, (size_t)n);
+    sc.once(&t.d_hist, t.n_hist);
+}
+
+// Plans the sweep's arena, zeroes the counters and uploads edges and probes.  Returns the pairs in flight (1 .. sweep_want) or
+// an error code (< 0); `unit`: what the planes of the message are counted for.
+static int sweep_tail_begin(Scratch& sc, SweepTail& t, const char* unit) {
+    vof_ctx* const c = sc.c;
+    const SweepBase& r = *t.r;
+    const int cap = sc.plan(sweep_want(c, r), r.n_frames - 1, 0.8);
+    if (cap < 0 && sc.units == 1 && sc.out_of_memory()) {       // not even one pair fits; a failed allocation of more stays what it is
+        c->err = std::string("the ") + t.name + " does not fit into the free device memory (" +
+                 std::to_string(sc.bytes / (t.fs * sizeof(double))) + " planes of n_i x n_j doubles" + unit + ")";
+        return -3;
+    }
+    if (cap < 0) return cap;
+    t.counters.resize((size_t)(c->scratch + sc.bytes - (char*)t.d_bad) / 8);
+    if (hipMemsetAsync(t.d_bad, 0, t.counters.size() * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
+    if (r.edges) if (int rc = h2d_bounced(c, t.d_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
+    if (r.probe_ij) if (int rc = h2d_bounced(c, t.d_pij, r.probe_ij, (size_t)2 * r.n_probes * sizeof(int32_t))) return rc;
+    return cap;
+}
+
+// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote them: first the counts and the probes of the speed ...
+static void sweep_tail_speed(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed) {
+    const SweepBase& r = *t.r;
+    Prof prof(c, VOF_K_REDUCE, 0);
+    const size_t m = (size_t)np * t.fs;
+    const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
+    k_bs_counts<<<nb, 256, 0, c->stream>>>(speed, m, t.d_edges, r.edges ? r.bins : 0, r.edges ? t.d_hist + (size_t)b * r.bins : nullptr,
+                                           t.d_bad + b);
+    if (r.probe_ij) {
+        const int nt = np * r.n_probes;
+        k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(speed, t.fs, c->Nj, np, t.d_pij, r.n_probes,
+                                                            t.d_probe + ((size_t)b * t.pm.P + k0) * r.n_probes);
+    }
+}
+
+// ... then, behind whatever the sweep adds on the same fields, the moments; asks for the error of the chunk's launches
+static int sweep_tail_moments(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed, const double* gamma) {
+    const SweepBase& r = *t.r;
+    pair_moments_enqueue(c, t.pm, speed, t.fs, 0, b, k0, np);
+    if (r.remodel) pair_moments_enqueue(c, t.pm, gamma, t.fs, 1, b, k0, np);
+    if (hipGetLastError() != hipSuccess) { c->err = std::string(t.name) + ": launch failed"; return -2; }
+    return 0;
+}
+
+// waits for the sweep, brings the statistics back and fills the fields the two stats records share
+template <class Stats>
+static int sweep_tail_finish(vof_ctx* c, SweepTail& t, Stats* stats) {
+    const SweepBase& r = *t.r;
+    if (int rc = d2h_bounced(c, t.counters.data(), t.d_bad, t.counters.size() * 8)) return rc;
+    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, t.d_probe, t.n_probe * 8)) return rc;
+    std::vector<double> mom(t.n_mom_all);
+    if (int rc = d2h_bounced(c, mom.data(), t.pm.d_mom, mom.size() * 8)) return rc;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
+    for (size_t i = 0; i < t.n_hist; ++i) r.hist[i] = (int64_t)t.host(t.d_hist)[i];
+    for (int b = 0; b < t.n; ++b) {
+        Stats& o = stats[b];
+        memset(&o, 0, sizeof o);
+        const Moments ms = pair_moments_merged(t.pm, mom.data(), t.fs, 0, b);
+        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
+        if (r.remodel) {
+            const Moments mr = pair_moments_merged(t.pm, mom.data(), t.fs, 1, b);
+            o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n;
+        }
+        o.nonfinite_count = (int64_t)t.host(t.d_bad)[b];
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2927,20 +3310,19 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
     return rc_all;
 }
 
-// workspace of the blur: one chunk of row-filtered frames and the taps
-static int blur_alloc(vof_ctx* c) {
-    if (!c->blur_tmp) {
-        if (int rc = dev_alloc(c, &c->blur_tmp, (size_t)16 * frame_stride(c))) return rc;
-        if (int rc = dev_alloc(c, &c->blur_w, (size_t)2 * 4096 + 1)) return rc;
-    }
-    return 0;
+// workspace of the blur of up to `frames` frames per blur_frames call, declared into the caller's arena: one chunk of
+// row-filtered frames, and room for the taps of `radius` where the caller does not bring its own (w null)
+constexpr int BLUR_CHUNK = 16;
+static void blur_regions(Scratch& sc, int frames, double** tmp, double** w = nullptr, int radius = 0) {
+    sc.once(tmp, (size_t)std::min(frames, BLUR_CHUNK) * frame_stride(sc.c));
+    if (w) sc.once(w, (size_t)2 * radius + 1);
 }
 
-// n_frames device-resident frames with the taps already on the device at w (c->blur_w, or the sweep's own copy), enqueued on
-// the context's stream (out may alias in).  Radii BL_RMIN .. BL_RMAX take the LDS-tiled kernels, same bits as k_blur1d.
-static int blur_frames(vof_ctx* c, const double* in, double* out, int n_frames, int radius, const double* w) {
+// n_frames device-resident frames with the taps already on the device at w and the row-filtered chunk at tmp (blur_regions),
+// enqueued on the context's stream (out may alias in).  Radii BL_RMIN .. BL_RMAX take the LDS-tiled kernels, same bits as k_blur1d.
+static int blur_frames(vof_ctx* c, const double* in, double* out, int n_frames, int radius, double* tmp, const double* w) {
     size_t fs = frame_stride(c);
-    const int chunk = std::min(n_frames, 16);
+    const int chunk = std::min(n_frames, BLUR_CHUNK);
     bool tiled = radius >= BL_RMIN && radius <= BL_RMAX;
     if (const char* e = getenv("VOF_BLUR_TILED")) tiled = tiled && e[0] != '0';
     if (tiled && !c->bl_lds_set) {
@@ -2952,44 +3334,51 @@ static int blur_frames(vof_ctx* c, const double* in, double* out, int n_frames, 
         Prof p(c, VOF_K_RHS, 0);
         if (tiled) {
             const dim3 g0((c->Nj + BX - 1) / BX, (c->Ni + BL_TI - 1) / BL_TI, nf), g1(g0.x, (c->Ni + BL_TR - 1) / BL_TR, nf);
-            k_blur1d_tiled<0><<<g0, blk2d, blur_tiled_lds(0, radius), c->stream>>>(in + (size_t)f0 * fs, c->blur_tmp, c->Ni, c->Nj, w, radius);
-            k_blur1d_tiled<1><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(c->blur_tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
+            k_blur1d_tiled<0><<<g0, blk2d, blur_tiled_lds(0, radius), c->stream>>>(in + (size_t)f0 * fs, tmp, c->Ni, c->Nj, w, radius);
+            k_blur1d_tiled<1><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
         } else {
             dim3 g = grid2d(c->Ni, c->Nj, nf);
-            k_blur1d<0><<<g, blk2d, 0, c->stream>>>(in + (size_t)f0 * fs, c->blur_tmp, c->Ni, c->Nj, w, radius);
-            k_blur1d<1><<<g, blk2d, 0, c->stream>>>(c->blur_tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
+            k_blur1d<0><<<g, blk2d, 0, c->stream>>>(in + (size_t)f0 * fs, tmp, c->Ni, c->Nj, w, radius);
+            k_blur1d<1><<<g, blk2d, 0, c->stream>>>(tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
         }
     }
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-int vof_blur_stack_dev(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius) {
+// The body of both blur entry points.  _dev: the frames where they lie.  _host: a chunk at a time up into a region of the arena,
+// blurred in place, down - as pageable asynchronous copies, as they always were: through the bounce buffer the call measured half
+// as slow again (profiles/r22_scratch_arena_summary.md).  The taps take the bounce buffer.
+static int blur_stack(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius, bool host) {
     if (!c) return -1;
     if (!in || !out || !weights) { c->err = "NULL pointer"; return -1; }
+    if (host && n_frames < 1) return 0;
     if (n_frames < 1 || radius < 0 || radius > 4096) { c->err = "bad n_frames / radius"; return -1; }
-    HIPCHK(hipSetDevice(c->device));
-    if (int rc = blur_alloc(c)) return rc;
-    HIPCHK(hipMemcpyAsync(c->blur_w, weights, (size_t)(2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (int rc = blur_frames(c, in, out, n_frames, radius, c->blur_w)) return rc;
+    const size_t fs = frame_stride(c);
+    Scratch sc(c);
+    double *io = nullptr, *tmp, *w;
+    if (host) sc.once(&io, (size_t)std::min(n_frames, BLUR_CHUNK) * fs);
+    blur_regions(sc, n_frames, &tmp, &w, radius);
+    if (int rc = sc.plan(1, 1, 0.8); rc < 0) return rc;
+    if (int rc = h2d_bounced(c, w, weights, (size_t)(2 * radius + 1) * sizeof(double))) return rc;
+    if (host) {
+        for (int f0 = 0; f0 < n_frames; f0 += BLUR_CHUNK) {
+            const int nf = std::min(BLUR_CHUNK, n_frames - f0);
+            HIPCHK(hipMemcpyAsync(io, in + (size_t)f0 * fs, (size_t)nf * fs * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            if (int rc = blur_frames(c, io, io, nf, radius, tmp, w)) return rc;
+            HIPCHK(hipMemcpyAsync(out + (size_t)f0 * fs, io, (size_t)nf * fs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+    } else if (int rc = blur_frames(c, in, out, n_frames, radius, tmp, w)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
+int vof_blur_stack_dev(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius) {
+    return blur_stack(c, in, out, n_frames, weights, radius, false);
+}
 int vof_blur_stack_host(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius) {
-    if (!c) return -1;
-    if (!in || !out || !weights) { c->err = "NULL pointer"; return -1; }
-    HIPCHK(hipSetDevice(c->device));
-    size_t fs = frame_stride(c);
-    if (!c->blur_io) { if (int rc = dev_alloc(c, &c->blur_io, (size_t)2 * 16 * fs)) return rc; }
-    for (int f0 = 0; f0 < n_frames; f0 += 16) {
-        int nf = std::min(16, n_frames - f0);
-        HIPCHK(hipMemcpyAsync(c->blur_io, in + (size_t)f0 * fs, (size_t)nf * fs * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (int rc = vof_blur_stack_dev(c, c->blur_io, c->blur_io + (size_t)16 * fs, nf, weights, radius)) return rc;
-        HIPCHK(hipMemcpyAsync(out + (size_t)f0 * fs, c->blur_io + (size_t)16 * fs, (size_t)nf * fs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return blur_stack(c, in, out, n_frames, weights, radius, true);
 }
 
 // sum (x - shift), sum (x - shift)^2 over n device doubles -> out2 (host); uses ctx->partials / func3 as scratch
@@ -3005,18 +3394,6 @@ static int moments_pass(vof_ctx* c, const double* x, size_t n, double shift, dou
     out2[1] = c->h_func3[1];
     return 0;
 }
-
-// (count, mean, M2 = sum (x - mean)^2) of one chunk, exact two-pass; chunks are merged with Chan's formula
-struct Moments {
-    double n = 0, mean = 0, m2 = 0;
-    void merge(double nb, double meanb, double m2b) {
-        if (nb == 0) return;
-        double nt = n + nb, d = meanb - mean;
-        m2 += m2b + d * d * n * nb / nt;
-        mean += d * nb / nt;
-        n = nt;
-    }
-};
 
 static int chunk_moments(vof_ctx* c, const double* x, size_t n, Moments* acc) {
     double s[2];
@@ -3574,9 +3951,18 @@ static int box_flow_check(vof_ctx* c, const double* movie, int n_frames, int box
     return 0;
 }
 
-// P pairs of a device-resident movie into device-resident outputs, enqueued on the context's stream.
-static int box_flow_pairs(vof_ctx* c, const double* movie, int P, int box_size, double delta_x, double delta_t, int include_remodelling,
-                          int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
+static bool box_flow_fused(int box_size) {                 // the fused kernel, or the general path: three kernels through scratch planes
+    const char* e = getenv("VOF_BOXFLOW_FUSED");
+    return box_size / 2 <= BF_HMAX && !(e && e[0] == '0');
+}
+// the planes of the general path, declared into the caller's arena where box_flow_pairs will take that path (none otherwise)
+static void box_flow_regions(Scratch& sc, int box_size, double** planes) {
+    sc.once(planes, box_flow_fused(box_size) ? 0 : (size_t)BF_GENERAL_CHUNK * 11 * frame_stride(sc.c));
+}
+
+// P pairs of a device-resident movie into device-resident outputs, enqueued on the context's stream; planes: box_flow_regions.
+static int box_flow_pairs(vof_ctx* c, double* planes, const double* movie, int P, int box_size, double delta_x, double delta_t,
+                          int include_remodelling, int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
     const size_t fs = frame_stride(c);
     BoxArgs a{};
     a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj; a.h = box_size / 2;
@@ -3584,14 +3970,12 @@ static int box_flow_pairs(vof_ctx* c, const double* movie, int P, int box_size, 
     a.quirks = reference_quirks ? 1 : 0;
     a.n_box = (double)box_size * (double)box_size;
     a.scale = delta_x / delta_t;
-    bool fused = a.h <= BF_HMAX;
-    if (const char* e = getenv("VOF_BOXFLOW_FUSED")) fused = fused && e[0] != '0';
     auto at = [&](int k0) {
         a.movie = movie + (size_t)k0 * fs;
         a.vx = v_x + (size_t)k0 * fs; a.vy = v_y + (size_t)k0 * fs; a.speed = speed + (size_t)k0 * fs;
         a.gamma = net_remodelling ? net_remodelling + (size_t)k0 * fs : nullptr;
     };
-    if (fused) {
+    if (box_flow_fused(box_size)) {
         if (!c->bf_lds_set) {
             const int lds = (int)bf_fused_lds(BF_HMAX);
             HIPCHK(hipFuncSetAttribute((const void*)k_boxflow_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -3609,9 +3993,8 @@ static int box_flow_pairs(vof_ctx* c, const double* movie, int P, int box_size, 
             else k_boxflow_fused<false><<<g, BF_THREADS, lds, c->stream>>>(a);
         }
     } else {
-        if (!c->bf_scratch) { if (int rc = dev_alloc(c, &c->bf_scratch, (size_t)BF_GENERAL_CHUNK * 11 * fs)) return rc; }
-        double* der = c->bf_scratch;
-        double* rows = c->bf_scratch + (size_t)BF_GENERAL_CHUNK * 3 * fs;
+        double* der = planes;
+        double* rows = planes + (size_t)BF_GENERAL_CHUNK * 3 * fs;
         for (int k0 = 0; k0 < P; k0 += BF_GENERAL_CHUNK) {
             const int np = std::min(BF_GENERAL_CHUNK, P - k0);
             at(k0);
@@ -3636,8 +4019,11 @@ int vof_box_flow_dev(vof_ctx* c, const double* movie, int n_frames, int box_size
                      int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
     if (!c) return -1;
     if (int rc = box_flow_check(c, movie, n_frames, box_size, delta_t, include_remodelling, v_x, v_y, speed, net_remodelling)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    if (int rc = box_flow_pairs(c, movie, n_frames - 1, box_size, delta_x, delta_t, include_remodelling, reference_quirks, v_x, v_y, speed,
+    Scratch sc(c);
+    double* planes = nullptr;
+    box_flow_regions(sc, box_size, &planes);
+    if (int rc = sc.plan(1, 1, 0.8); rc < 0) return rc;
+    if (int rc = box_flow_pairs(c, planes, movie, n_frames - 1, box_size, delta_x, delta_t, include_remodelling, reference_quirks, v_x, v_y, speed,
                                 net_remodelling)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -3647,7 +4033,10 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
                       int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
     if (!c) return -1;
     if (int rc = box_flow_check(c, movie, n_frames, box_size, delta_t, include_remodelling, v_x, v_y, speed, net_remodelling)) return rc;
-    HIPCHK(hipSetDevice(c->device));
+    Scratch sc(c);
+    double* planes = nullptr;
+    box_flow_regions(sc, box_size, &planes);
+    if (int rc = sc.plan(1, 1, 0.8); rc < 0) return rc;
     if (int rc = ensure_staging(c, false)) return rc;
     const size_t fs = frame_stride(c), fb = fs * sizeof(double);
     const int P = n_frames - 1;
@@ -3655,7 +4044,7 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
     for (int k0 = 0; k0 < P; k0 += c->B) {
         const int np = std::min(c->B, P - k0);
         if (int rc = h2d_bounced(c, c->st_movie, movie + (size_t)k0 * fs, (size_t)(np + 1) * fb)) return rc;
-        if (int rc = box_flow_pairs(c, c->st_movie, np, box_size, delta_x, delta_t, include_remodelling, reference_quirks, c->st_out[0],
+        if (int rc = box_flow_pairs(c, planes, c->st_movie, np, box_size, delta_x, delta_t, include_remodelling, reference_quirks, c->st_out[0],
                                     c->st_out[1], c->st_out[2], include_remodelling ? c->st_out[3] : nullptr)) return rc;
         for (int f = 0; f < 4; ++f)
             if (outs[f])
@@ -3664,239 +4053,6 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
     if (!include_remodelling && net_remodelling) memset(net_remodelling, 0, (size_t)P * fb);
     return 0;
 }
-
-// ---- sweeps of the box flow: what vary_boxsize and vary_blursize share --------------------------------------------
-constexpr int BS_MAX_CHUNK = 32;          // pairs per launch (grid z) at most; more adds nothing once the chip is full
-
-// Mean and variance of a field per list entry, shared by the box-size and the blur sweep: the two-pass reduction of
-// vof_field_moments_dev per pair on the device, sums [field][pass][entry][pair][3]; a pair is the unit the host merges.
-struct PairMoments {
-    double* d_mom; double* d_part;        // device: the sums; the partials of one chunk
-    size_t n_mom;                         // n_entries * P * 3
-    int n_entries, P, mom_blk;
-};
-
-inline int pair_moments_blocks(size_t fs) { return (int)std::min<size_t>(256, std::max<size_t>(1, (fs + 4 * RBLK - 1) / (4 * RBLK))); }
-
-// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote x: no host round trip in a sweep
-static void pair_moments_enqueue(vof_ctx* c, const PairMoments& m, const double* x, size_t fs, int field, int b, int k0, int np) {
-    const dim3 gm(m.mom_blk, np);
-    double* first = m.d_mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P + k0) * 3;
-    double* second = first + m.n_mom;
-    Prof prof(c, VOF_K_REDUCE, 0, 16.0 * fs);
-    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, nullptr, m.d_part);
-    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, first);
-    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, first, m.d_part);
-    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, second);
-}
-
-// mom: the host copy of d_mom.  Pairs merged in order with Chan's formula; per pair the arithmetic of chunk_moments
-static Moments pair_moments_merged(const PairMoments& m, const double* mom, size_t fs, int field, int b) {
-    Moments acc;
-    const double* first = mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P) * 3;
-    const double* second = first + m.n_mom;
-    const double n = (double)fs;
-    for (int k = 0; k < m.P; ++k) {
-        double mean = first[3 * k] / n;
-        const double s0 = second[3 * k], s1 = second[3 * k + 1];
-        mean += s0 / n;                                         // first-order correction of the rounded mean
-        acc.merge(n, mean, s1 - s0 * s0 / n);
-    }
-    return acc;
-}
-
-// what every sweep is asked for besides its list
-struct SweepBase {
-    const double* movie; int n_frames;
-    double delta_x, delta_t; int remodel, quirks;
-    const double* edges; int bins; int64_t* hist;               // speed
-    const int32_t* probe_ij; int n_probes; double* probe_out;
-    double* outs[4];                      // v_x, v_y, speed, net_remodelling: all NULL = stats only
-    bool host;                            // movie and outs are host memory
-};
-
-static int sweep_check(vof_ctx* c, const SweepBase& r, const void* stats) {
-    if (!r.movie) { c->err = "movie is NULL"; return -1; }
-    if (!stats) { c->err = "stats is NULL"; return -1; }
-    if (r.n_frames < 2) { c->err = "need at least two frames"; return -1; }
-    if (r.delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
-    if (r.edges && (r.bins < 1 || !r.hist)) { c->err = "histogram_edges needs histogram_bins >= 1 and histograms"; return -1; }
-    if (r.edges && !(r.edges[r.bins] > r.edges[0])) { c->err = "histogram_edges must increase"; return -1; }
-    if (r.probe_ij) {
-        if (r.n_probes < 1 || !r.probe_out) { c->err = "probe_ij needs n_probes >= 1 and probe_speeds"; return -1; }
-        for (int l = 0; l < r.n_probes; ++l)
-            if (r.probe_ij[2 * l] < 0 || r.probe_ij[2 * l] >= c->Ni || r.probe_ij[2 * l + 1] < 0 || r.probe_ij[2 * l + 1] >= c->Nj) {
-                c->err = "probe outside the image"; return -1;
-            }
-    }
-    const bool any = r.outs[0] || r.outs[1] || r.outs[2] || r.outs[3];
-    if (any && (!r.outs[0] || !r.outs[1] || !r.outs[2])) { c->err = "v_x, v_y and speed must be given together (or all NULL)"; return -1; }
-    if (any && r.remodel && !r.outs[3]) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
-    return 0;
-}
-
-// pairs a sweep keeps in flight at most: a _host sweep stages no more than the context's slots
-inline int sweep_want(const vof_ctx* c, const SweepBase& r) {
-    return std::min(std::min(r.n_frames - 1, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
-}
-
-// The scratch planes of a sweep (one buffer on the context, lazy): `fixed` planes and `per_pair` for every pair in flight, `want`
-// pairs if the free memory allows.  Returns the pairs the buffer holds (1 .. want) or an error code (< 0).  A buffer the free
-// memory sized is kept as long as it holds one pair: asking again would free and re-allocate it at every call.
-static int sweep_scratch(vof_ctx* c, size_t fixed, size_t per_pair, int want, const char* name, const char* unit) {
-    const size_t fs = frame_stride(c);
-    int cap = c->sw_planes > fixed ? (int)std::min<size_t>((c->sw_planes - fixed) / per_pair, (size_t)want) : 0;
-    if (cap >= want || (c->sw_by_budget && cap >= 1)) return cap;
-    if (int rc = dev_free(c, c->sw_scratch)) return rc;
-    c->sw_scratch = nullptr; c->sw_planes = 0;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = (size_t)(0.8 * (double)free_b) / (fs * sizeof(double));
-    cap = budget > fixed ? (int)std::min<size_t>((budget - fixed) / per_pair, (size_t)want) : 0;
-    if (cap < 1) {
-        c->err = std::string("the ") + name + " does not fit into the free device memory (" + std::to_string(fixed + per_pair) +
-                 " planes of n_i x n_j doubles" + unit + ")";
-        return -3;
-    }
-    if (int rc = dev_alloc(c, &c->sw_scratch, (fixed + per_pair * cap) * fs)) return rc;
-    c->sw_planes = fixed + per_pair * cap;
-    c->sw_by_budget = cap < want;
-    return cap;
-}
-
-// where the fields of pairs k0 .. of entry b go on the device: the caller's stacks (_dev with fields) or the chunk planes
-struct SweepDst {
-    double* f[4];
-    size_t oo;                            // offset of the chunk in the caller's stacks
-    bool keep_v, keep_g;                  // v_x / v_y and net_remodelling are wanted (speed always is)
-};
-
-static SweepDst sweep_dst(const SweepBase& r, double* const chunk_out[4], size_t fs, int b, int k0) {
-    SweepDst d;
-    const bool fields = r.outs[0] != nullptr;
-    d.oo = ((size_t)b * (r.n_frames - 1) + k0) * fs;
-    for (int f = 0; f < 4; ++f) d.f[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + d.oo : chunk_out[f];
-    d.keep_v = fields;
-    d.keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
-    return d;
-}
-
-// _host with fields: np pairs from the chunk planes into the caller's stacks; net_remodelling is zero where it was not computed
-static int sweep_copy_out(vof_ctx* c, const SweepBase& r, const SweepDst& d, size_t fs, int np) {
-    if (!r.host) return 0;
-    const size_t bytes = (size_t)np * fs * sizeof(double);
-    for (int f = 0; f < 4; ++f) {
-        if (!r.outs[f]) continue;
-        if (f == 3 && !r.remodel) memset(r.outs[f] + d.oo, 0, bytes);
-        else if (int rc = d2h_bounced(c, r.outs[f] + d.oo, d.f[f], bytes)) return rc;
-    }
-    return 0;
-}
-
-struct Take {                             // lays items out one after the other
-    size_t items = 0;
-    size_t operator()(size_t k) { const size_t at = items; items += k; return at; }
-};
-
-// The statistics every sweep keeps per list entry: histogram and non-finite count of the speed, the speed at the probes, mean
-// and variance of speed and net_remodelling.  What the kernels read and write lives in one buffer on the context, grown on
-// demand: 8-byte items - the tail's, then `own_doubles` of the sweep, then the counters (zeroed; the tail's, then `own_counters`
-// of the sweep) - and the probe indices.
-struct SweepTail {
-    const SweepBase* r; const char* name;
-    int n; size_t fs;
-    PairMoments pm;
-    size_t n_hist, n_probe, n_mom_all, n_counters;
-    double *d_edges, *d_probe, *own_doubles;
-    unsigned long long *d_bad, *d_hist, *own_counters;
-    int32_t* d_pij;
-    std::vector<unsigned long long> counters;     // host copy (sweep_tail_finish): n non-finite counts, the histograms, the sweep's own
-};
-
-static int sweep_tail_begin(vof_ctx* c, SweepTail& t, const SweepBase& r, const char* name, int n, int cap, size_t own_doubles,
-                            size_t own_counters) {
-    const int P = r.n_frames - 1;
-    t.r = &r; t.name = name; t.n = n; t.fs = frame_stride(c);
-    t.n_hist = r.edges ? (size_t)n * r.bins : 0;
-    t.n_probe = r.probe_ij ? (size_t)n * P * r.n_probes : 0;
-    // moments: per field (speed, net_remodelling), pass, entry and pair the three sums of k_sum3; then the partials of a chunk
-    const size_t n_mom = (size_t)n * P * 3;
-    const int mom_blk = pair_moments_blocks(t.fs);
-    t.n_mom_all = 2 * (r.remodel ? 2 : 1) * n_mom;
-    Take take;
-    const size_t at_edges = take(r.edges ? r.bins + 1 : 0), at_probe = take(t.n_probe), at_mom = take(t.n_mom_all),
-                 at_part = take((size_t)cap * 3 * mom_blk), at_own = take(own_doubles);
-    const size_t at_bad = take(n), at_hist = take(t.n_hist), at_own_counters = take(own_counters);
-    t.n_counters = take.items - at_bad;
-    const size_t pij_bytes = r.probe_ij ? (size_t)2 * r.n_probes * sizeof(int32_t) : 0, aux_bytes = take.items * 8 + pij_bytes;
-    if (c->sw_aux_bytes < aux_bytes) {
-        if (int rc = dev_free(c, c->sw_aux)) return rc;
-        c->sw_aux = nullptr; c->sw_aux_bytes = 0;
-        if (int rc = dev_alloc(c, &c->sw_aux, aux_bytes)) return rc;
-        c->sw_aux_bytes = aux_bytes;
-    }
-    double* const ad = (double*)c->sw_aux;
-    unsigned long long* const au = (unsigned long long*)c->sw_aux;
-    t.d_edges = ad + at_edges; t.d_probe = ad + at_probe; t.own_doubles = ad + at_own;
-    t.d_bad = au + at_bad; t.d_hist = au + at_hist; t.own_counters = au + at_own_counters;
-    t.d_pij = (int32_t*)(ad + take.items);
-    t.pm = PairMoments{ad + at_mom, ad + at_part, n_mom, n, P, mom_blk};
-    if (hipMemsetAsync(t.d_bad, 0, t.n_counters * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
-    if (r.edges) if (int rc = h2d_bounced(c, t.d_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
-    if (r.probe_ij) if (int rc = h2d_bounced(c, t.d_pij, r.probe_ij, pij_bytes)) return rc;
-    return 0;
-}
-
-// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote them: first the counts and the probes of the speed ...
-static void sweep_tail_speed(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed) {
-    const SweepBase& r = *t.r;
-    Prof prof(c, VOF_K_REDUCE, 0);
-    const size_t m = (size_t)np * t.fs;
-    const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
-    k_bs_counts<<<nb, 256, 0, c->stream>>>(speed, m, t.d_edges, r.edges ? r.bins : 0, r.edges ? t.d_hist + (size_t)b * r.bins : nullptr,
-                                           t.d_bad + b);
-    if (r.probe_ij) {
-        const int nt = np * r.n_probes;
-        k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(speed, t.fs, c->Nj, np, t.d_pij, r.n_probes,
-                                                            t.d_probe + ((size_t)b * t.pm.P + k0) * r.n_probes);
-    }
-}
-
-// ... then, behind whatever the sweep adds on the same fields, the moments; asks for the error of the chunk's launches
-static int sweep_tail_moments(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed, const double* gamma) {
-    const SweepBase& r = *t.r;
-    pair_moments_enqueue(c, t.pm, speed, t.fs, 0, b, k0, np);
-    if (r.remodel) pair_moments_enqueue(c, t.pm, gamma, t.fs, 1, b, k0, np);
-    if (hipGetLastError() != hipSuccess) { c->err = std::string(t.name) + ": launch failed"; return -2; }
-    return 0;
-}
-
-// waits for the sweep, brings the statistics back and fills the fields the two stats records share
-extern "C++" {
-template <class Stats>
-static int sweep_tail_finish(vof_ctx* c, SweepTail& t, Stats* stats) {
-    const SweepBase& r = *t.r;
-    t.counters.resize(t.n_counters);
-    if (int rc = d2h_bounced(c, t.counters.data(), t.d_bad, t.n_counters * 8)) return rc;
-    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, t.d_probe, t.n_probe * 8)) return rc;
-    std::vector<double> mom(t.n_mom_all);
-    if (int rc = d2h_bounced(c, mom.data(), t.pm.d_mom, mom.size() * 8)) return rc;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
-    for (size_t i = 0; i < t.n_hist; ++i) r.hist[i] = (int64_t)t.counters[(size_t)t.n + i];
-    for (int b = 0; b < t.n; ++b) {
-        Stats& o = stats[b];
-        memset(&o, 0, sizeof o);
-        const Moments ms = pair_moments_merged(t.pm, mom.data(), t.fs, 0, b);
-        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
-        if (r.remodel) {
-            const Moments mr = pair_moments_merged(t.pm, mom.data(), t.fs, 1, b);
-            o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n;
-        }
-        o.nonfinite_count = (int64_t)t.counters[b];
-    }
-    return 0;
-}
-}  // extern "C++"
 
 // ---- box-size sweep of the box flow (vary_boxsize; vof_boxsweep.hpp) ---------------------------------------------
 struct SweepReq : SweepBase {
@@ -3912,27 +4068,24 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     for (int b = 0; b < r.n_boxes; ++b)
         if (r.boxes[b] < 1) { c->err = "every box size must be >= 1"; return -1; }
     if (r.blur_w && (r.blur_r < 0 || r.blur_r > 4096)) { c->err = "bad blur_radius"; return -1; }
-    HIPCHK(hipSetDevice(c->device));
     const size_t fs = frame_stride(c), fb = fs * sizeof(double);
     const int P = r.n_frames - 1, NQ = r.remodel ? 8 : 5;
-    // scratch planes: cap + 1 frames, and per pair 3 derived planes, R / C / W of every quantity and 4 chunk outputs
-    const int cap = sweep_scratch(c, 1, 1 + 3 + 3 * (size_t)NQ + 4, sweep_want(c, r), "box-size sweep", " for one pair");
-    if (cap < 0) return cap;
-    double* frames = c->sw_scratch;
-    double* der = frames + (size_t)(cap + 1) * fs;
+    // the arena: cap + 1 frames, and per pair 3 derived planes, R / C / W of every quantity and 4 chunk outputs
+    Scratch sc(c);
+    double *frames, *der, *chunk_out[4], *blur_tmp = nullptr, *blur_w = nullptr;
     SweepArgs s{};
-    s.der = der; s.fs = fs; s.Ni = c->Ni; s.Nj = c->Nj;
-    s.R = der + (size_t)cap * 3 * fs;
-    s.C = s.R + (size_t)cap * NQ * fs;
-    s.W = s.C + (size_t)cap * NQ * fs;
-    double* chunk_out[4];
-    for (int f = 0; f < 4; ++f) chunk_out[f] = s.W + (size_t)cap * NQ * fs + (size_t)f * cap * fs;
+    s.fs = fs; s.Ni = c->Ni; s.Nj = c->Nj;
+    sc.per_unit_plus_one(&frames, fs);
+    sc.per_unit(&der, 3 * fs);
+    for (double** q : {&s.R, &s.C, &s.W}) sc.per_unit(q, (size_t)NQ * fs);
+    for (double*& q : chunk_out) sc.per_unit(&q, fs);
+    if (r.blur_w) blur_regions(sc, sweep_want(c, r) + 1, &blur_tmp, &blur_w, r.blur_r);
     SweepTail tail;
-    if (int rc = sweep_tail_begin(c, tail, r, "box-size sweep", r.n_boxes, cap, 0, 0)) return rc;
-    if (r.blur_w) {
-        if (int rc = blur_alloc(c)) return rc;
-        if (int rc = h2d_bounced(c, c->blur_w, r.blur_w, (size_t)(2 * r.blur_r + 1) * sizeof(double))) return rc;
-    }
+    sweep_tail_regions(sc, tail, r, "box-size sweep", r.n_boxes);
+    const int cap = sweep_tail_begin(sc, tail, " for one pair");
+    if (cap < 0) return cap;
+    s.der = der;
+    if (r.blur_w) if (int rc = h2d_bounced(c, blur_w, r.blur_w, (size_t)(2 * r.blur_r + 1) * sizeof(double))) return rc;
 
     // the steps: a half width past the longer image side adds only zeros, so the chain ends there
     const int h_stop = std::max(c->Ni, c->Nj);
@@ -3958,7 +4111,7 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
             chunk_frames = frames;
         }
         if (r.blur_w) {
-            if (int rc = blur_frames(c, chunk_frames, frames, np + 1, r.blur_r, c->blur_w)) return rc;
+            if (int rc = blur_frames(c, chunk_frames, frames, np + 1, r.blur_r, blur_tmp, blur_w)) return rc;
             chunk_frames = frames;
         }
         c->cur_units = np;
@@ -4034,6 +4187,15 @@ struct BlurSweepReq : SweepBase {
     vof_blursize_stats* stats;
 };
 
+// np.linspace(lo, hi, bins + 1) for hi - lo exactly representable: i * step + lo, the last one the stop itself
+static std::vector<double> linspace_edges(double lo, double hi, int bins) {
+    std::vector<double> e((size_t)bins + 1);
+    const volatile double step = (hi - lo) / (double)bins;
+    for (int i = 0; i < bins; ++i) { const volatile double t = (double)i * step; e[i] = t + lo; }
+    e[bins] = hi;
+    return e;
+}
+
 static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     if (!c) return -1;
     if (int rc = sweep_check(c, r, r.stats)) return rc;
@@ -4045,69 +4207,66 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     if (r.iedges && !(r.iedges[r.ibins] > r.iedges[0])) { c->err = "intensity_edges must increase"; return -1; }
     if (r.abins < 0 || r.abins > BZ_MAX_ANGLE_BINS) { c->err = "angle_bins must be 0 .. " + std::to_string(BZ_MAX_ANGLE_BINS); return -1; }
     if (r.abins && (!r.ahist || !r.awhist)) { c->err = "angle_bins needs angle_histograms and weighted_angle_histograms"; return -1; }
-    HIPCHK(hipSetDevice(c->device));
     const size_t fs = frame_stride(c), fb = fs * sizeof(double);
     const int T = r.n_frames, P = T - 1, n = r.n_sigmas;
-    // scratch planes: the blurred stack, four chunk outputs per pair in flight and the movie (_host)
-    const int cap = sweep_scratch(c, (size_t)(r.host ? 2 : 1) * T, 4, sweep_want(c, r), "blur sweep", "");
-    if (cap < 0) return cap;
-    double* blurred = c->sw_scratch;
-    double* chunk_out[4];
-    for (int f = 0; f < 4; ++f) chunk_out[f] = blurred + ((size_t)T + (size_t)f * cap) * fs;
-    const double* movie = r.movie;
-    if (r.host) {                                            // the movie goes up once
-        double* up = blurred + ((size_t)T + 4 * (size_t)cap) * fs;
-        if (int rc = h2d_bounced(c, up, r.movie, (size_t)T * fb)) return rc;
-        movie = up;
-    }
-    if (int rc = blur_alloc(c)) return rc;
-
-    // what the sweep's own kernels read and write, behind the tail's: taps, direction and intensity edges, direction sums and counts
     std::vector<size_t> tap_at(n);
     size_t n_taps = 0;
     for (int s = 0; s < n; ++s) { tap_at[s] = n_taps; n_taps += 2 * (size_t)r.radii[s] + 1; }
     const size_t n_ahist = (size_t)n * r.abins, n_ihist = r.iedges ? (size_t)n * r.ibins : 0, n_awsum = (size_t)n * P * r.abins;
     const int ang_blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));   // by the plane size only
-    Take doubles, counts;
-    const size_t at_taps = doubles(n_taps), at_aedges = doubles(r.abins ? r.abins + 1 : 0), at_iedges = doubles(r.iedges ? r.ibins + 1 : 0),
-                 at_awsum = doubles(n_awsum), at_apart = doubles((size_t)cap * ang_blk * r.abins);
-    const size_t at_ahist = counts(n_ahist), at_ihist = counts(n_ihist), at_ibad = counts(1);
+    // the arena: the blurred stack, the movie (_host) and four chunk outputs per pair in flight; what the sweep's own kernels
+    // read and write: taps, direction and intensity edges, direction sums and their partials; the tail's; the sweep's counters
+    Scratch sc(c);
+    double *blurred, *up = nullptr, *chunk_out[4], *blur_tmp, *bf_planes = nullptr, *d_taps, *d_aedges, *d_iedges, *d_awsum, *d_apart;
+    unsigned long long *d_ahist, *d_ihist, *d_ibad;
+    sc.once(&blurred, (size_t)T * fs);
+    if (r.host) sc.once(&up, (size_t)T * fs);
+    for (double*& q : chunk_out) sc.per_unit(&q, fs);
+    blur_regions(sc, T, &blur_tmp);
+    box_flow_regions(sc, r.box_size, &bf_planes);
+    sc.once(&d_taps, n_taps);
+    sc.once(&d_aedges, r.abins ? (size_t)r.abins + 1 : 0);
+    sc.once(&d_iedges, r.iedges ? (size_t)r.ibins + 1 : 0);
+    sc.once(&d_awsum, n_awsum);
+    sc.per_unit(&d_apart, (size_t)ang_blk * r.abins);
     SweepTail tail;
-    if (int rc = sweep_tail_begin(c, tail, r, "blur sweep", n, cap, doubles.items, counts.items)) return rc;
-    double* const ad = tail.own_doubles;
-    unsigned long long* const au = tail.own_counters;
-    if (int rc = h2d_bounced(c, ad + at_taps, r.taps, n_taps * 8)) return rc;
-    if (r.iedges) if (int rc = h2d_bounced(c, ad + at_iedges, r.iedges, (size_t)(r.ibins + 1) * 8)) return rc;
-    if (r.abins) {                         // np.linspace(-1, 1, bins + 1): i * step + start, the last one the stop itself
-        std::vector<double> e((size_t)r.abins + 1);
-        const volatile double step = 2.0 / (double)r.abins;
-        for (int i = 0; i < r.abins; ++i) { const volatile double t = (double)i * step; e[i] = t + -1.0; }
-        e[r.abins] = 1.0;
-        if (int rc = h2d_bounced(c, ad + at_aedges, e.data(), e.size() * 8)) return rc;
+    sweep_tail_regions(sc, tail, r, "blur sweep", n);
+    sc.once(&d_ahist, n_ahist);
+    sc.once(&d_ihist, n_ihist);
+    sc.once(&d_ibad, 1);
+    const int cap = sweep_tail_begin(sc, tail, "");
+    if (cap < 0) return cap;
+    if (r.host) if (int rc = h2d_bounced(c, up, r.movie, (size_t)T * fb)) return rc;     // the movie goes up once
+    const double* movie = r.host ? up : r.movie;
+    if (int rc = h2d_bounced(c, d_taps, r.taps, n_taps * 8)) return rc;
+    if (r.iedges) if (int rc = h2d_bounced(c, d_iedges, r.iedges, (size_t)(r.ibins + 1) * 8)) return rc;
+    if (r.abins) {
+        const std::vector<double> e = linspace_edges(-1.0, 1.0, r.abins);
+        if (int rc = h2d_bounced(c, d_aedges, e.data(), e.size() * 8)) return rc;
     }
 
     for (int s = 0; s < n; ++s) {
-        if (int rc = blur_frames(c, movie, blurred, T, r.radii[s], ad + at_taps + tap_at[s])) return rc;
+        if (int rc = blur_frames(c, movie, blurred, T, r.radii[s], blur_tmp, d_taps + tap_at[s])) return rc;
         if (r.iedges) {
             const size_t m = (size_t)T * fs;
             const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
             Prof prof(c, VOF_K_REDUCE, 0);
-            k_bs_counts<<<nb, 256, 0, c->stream>>>(blurred, m, ad + at_iedges, r.ibins, au + at_ihist + (size_t)s * r.ibins, au + at_ibad);
+            k_bs_counts<<<nb, 256, 0, c->stream>>>(blurred, m, d_iedges, r.ibins, d_ihist + (size_t)s * r.ibins, d_ibad);
         }
         for (int k0 = 0; k0 < P; k0 += cap) {
             const int np = std::min(cap, P - k0);
             const SweepDst d = sweep_dst(r, chunk_out, fs, s, k0);
             // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
-            if (int rc = box_flow_pairs(c, blurred + (size_t)k0 * fs, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d.f[0], d.f[1],
+            if (int rc = box_flow_pairs(c, bf_planes, blurred + (size_t)k0 * fs, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d.f[0], d.f[1],
                                         d.f[2], d.keep_g ? d.f[3] : nullptr)) return rc;
             sweep_tail_speed(c, tail, s, k0, np, d.f[2]);
             if (r.abins) {
                 Prof prof(c, VOF_K_REDUCE, 0);
                 k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
-                    d.f[0], d.f[1], d.f[2], fs, ad + at_aedges, r.abins, au + at_ahist + (size_t)s * r.abins, ad + at_apart);
+                    d.f[0], d.f[1], d.f[2], fs, d_aedges, r.abins, d_ahist + (size_t)s * r.abins, d_apart);
                 const int nt = np * r.abins;
-                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_apart, ang_blk, r.abins, np,
-                                                                        ad + at_awsum + ((size_t)s * P + k0) * r.abins);
+                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_apart, ang_blk, r.abins, np,
+                                                                        d_awsum + ((size_t)s * P + k0) * r.abins);
             }
             if (int rc = sweep_tail_moments(c, tail, s, k0, np, d.f[2], d.f[3])) return rc;
             if (int rc = sweep_copy_out(c, r, d, fs, np)) return rc;
@@ -4115,10 +4274,9 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     }
     if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
     std::vector<double> awsum(n_awsum);
-    if (n_awsum) if (int rc = d2h_bounced(c, awsum.data(), ad + at_awsum, n_awsum * 8)) return rc;
-    const unsigned long long* own = tail.counters.data() + (tail.n_counters - counts.items);
-    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)own[at_ahist + t];
-    for (size_t t = 0; t < n_ihist; ++t) r.ihist[t] = (int64_t)own[at_ihist + t];
+    if (n_awsum) if (int rc = d2h_bounced(c, awsum.data(), d_awsum, n_awsum * 8)) return rc;
+    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)tail.host(d_ahist)[t];
+    for (size_t t = 0; t < n_ihist; ++t) r.ihist[t] = (int64_t)tail.host(d_ihist)[t];
     for (int s = 0; s < n; ++s) {
         for (int b = 0; b < r.abins; ++b) {                  // the pairs' sums in pair order
             double w = 0.0;
@@ -4169,15 +4327,6 @@ struct CompareReq : SweepBase {           // movie, outs: channel a; the tail's 
     vof_compare_stats* stats;
 };
 
-// np.linspace(lo, hi, bins + 1) for hi - lo exactly representable: i * step + lo, the last one the stop itself
-static std::vector<double> linspace_edges(double lo, double hi, int bins) {
-    std::vector<double> e((size_t)bins + 1);
-    const volatile double step = (hi - lo) / (double)bins;
-    for (int i = 0; i < bins; ++i) { const volatile double t = (double)i * step; e[i] = t + lo; }
-    e[bins] = hi;
-    return e;
-}
-
 static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
     if (!c) return -1;
     if (int rc = sweep_check(c, r, r.stats)) return rc;
@@ -4199,46 +4348,49 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
             if (!(r.jedges[ch][r.jbins[ch]] > r.jedges[ch][0])) { c->err = "joint_speed_edges must increase"; return -1; }
         }
     }
-    HIPCHK(hipSetDevice(c->device));
     const size_t fs = frame_stride(c), fb = fs * sizeof(double);
     const int P = r.n_frames - 1;
     const int ba = joint ? r.jbins[0] : 0, bb = joint ? r.jbins[1] : 0;
-    // scratch planes: cap + 1 frames of the channel in progress and four chunk outputs per channel and pair in flight
-    const int cap = sweep_scratch(c, 1, 1 + 8, sweep_want(c, r), "channel comparison", " for one pair");
-    if (cap < 0) return cap;
-    double* frames = c->sw_scratch;
-    double* chunk_out[2][4];
-    for (int ch = 0; ch < 2; ++ch)
-        for (int f = 0; f < 4; ++f) chunk_out[ch][f] = frames + ((size_t)(cap + 1) + (size_t)(4 * ch + f) * cap) * fs;
-    if (r.taps[0] || r.taps[1]) if (int rc = blur_alloc(c)) return rc;
-
-    // what the comparison's own kernels read and write, behind the tail's
     const size_t n_taps[2] = {r.taps[0] ? 2 * (size_t)r.radius[0] + 1 : 0, r.taps[1] ? 2 * (size_t)r.radius[1] + 1 : 0};
     const size_t n_ahist = 2 * (size_t)r.abins, n_awsum = 2 * (size_t)P * r.abins, n_twsum = (size_t)P * r.tbins, n_jhist = (size_t)ba * bb;
     const int ang_blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));   // as the blur sweep
     const int cp_blk = cp_blocks(fs);
-    Take doubles, counts;
-    const size_t at_taps[2] = {doubles(n_taps[0]), doubles(n_taps[1])};
-    const size_t at_aedges = doubles(r.abins ? r.abins + 1 : 0), at_tedges = doubles((size_t)r.tbins + 1),
-                 at_jedges[2] = {doubles(joint ? (size_t)ba + 1 : 0), doubles(joint ? (size_t)bb + 1 : 0)},
-                 at_awsum = doubles(n_awsum), at_apart = doubles((size_t)cap * ang_blk * r.abins), at_twsum = doubles(n_twsum),
-                 at_tpart = doubles((size_t)cap * cp_blk * r.tbins);
-    const size_t at_ahist = counts(n_ahist), at_thist = counts(r.tbins), at_jhist = counts(n_jhist), at_jc = counts(2);
+    // the arena: cap + 1 frames of the channel in progress and four chunk outputs per channel and pair in flight; what the
+    // comparison's own kernels read and write; the tail's; the comparison's counters
+    Scratch sc(c);
+    double *frames, *chunk_out[2][4], *blur_tmp = nullptr, *bf_planes = nullptr, *d_taps[2], *d_aedges, *d_tedges, *d_jedges[2], *d_awsum, *d_apart,
+           *d_twsum, *d_tpart;
+    unsigned long long *d_ahist, *d_thist, *d_jhist, *d_jc;
+    sc.per_unit_plus_one(&frames, fs);
+    for (auto& ch : chunk_out) for (double*& q : ch) sc.per_unit(&q, fs);
+    if (r.taps[0] || r.taps[1]) blur_regions(sc, sweep_want(c, r) + 1, &blur_tmp);
+    box_flow_regions(sc, r.box_size, &bf_planes);
+    for (int ch = 0; ch < 2; ++ch) { sc.once(&d_taps[ch], n_taps[ch]); sc.once(&d_jedges[ch], joint ? (size_t)r.jbins[ch] + 1 : 0); }
+    sc.once(&d_aedges, r.abins ? (size_t)r.abins + 1 : 0);
+    sc.once(&d_tedges, (size_t)r.tbins + 1);
+    sc.once(&d_awsum, n_awsum);
+    sc.per_unit(&d_apart, (size_t)ang_blk * r.abins);
+    sc.once(&d_twsum, n_twsum);
+    sc.per_unit(&d_tpart, (size_t)cp_blk * r.tbins);
     SweepTail tail;
-    if (int rc = sweep_tail_begin(c, tail, r, "channel comparison", 2, cap, doubles.items, counts.items)) return rc;
-    double* const ad = tail.own_doubles;
-    unsigned long long* const au = tail.own_counters;
+    sweep_tail_regions(sc, tail, r, "channel comparison", 2);
+    sc.once(&d_ahist, n_ahist);
+    sc.once(&d_thist, (size_t)r.tbins);
+    sc.once(&d_jhist, n_jhist);
+    sc.once(&d_jc, 2);
+    const int cap = sweep_tail_begin(sc, tail, " for one pair");
+    if (cap < 0) return cap;
     for (int ch = 0; ch < 2; ++ch) {
-        if (r.taps[ch]) if (int rc = h2d_bounced(c, ad + at_taps[ch], r.taps[ch], n_taps[ch] * 8)) return rc;
-        if (joint) if (int rc = h2d_bounced(c, ad + at_jedges[ch], r.jedges[ch], ((size_t)r.jbins[ch] + 1) * 8)) return rc;
+        if (r.taps[ch]) if (int rc = h2d_bounced(c, d_taps[ch], r.taps[ch], n_taps[ch] * 8)) return rc;
+        if (joint) if (int rc = h2d_bounced(c, d_jedges[ch], r.jedges[ch], ((size_t)r.jbins[ch] + 1) * 8)) return rc;
     }
     if (r.abins) {
         const std::vector<double> e = linspace_edges(-1.0, 1.0, r.abins);
-        if (int rc = h2d_bounced(c, ad + at_aedges, e.data(), e.size() * 8)) return rc;
+        if (int rc = h2d_bounced(c, d_aedges, e.data(), e.size() * 8)) return rc;
     }
     {
         const std::vector<double> e = linspace_edges(0.0, 1.0, r.tbins);
-        if (int rc = h2d_bounced(c, ad + at_tedges, e.data(), e.size() * 8)) return rc;
+        if (int rc = h2d_bounced(c, d_tedges, e.data(), e.size() * 8)) return rc;
     }
     SweepBase chan[2] = {r, r};            // a channel as a sweep of one entry: where its fields go
     chan[1].movie = r.movie_b;
@@ -4254,21 +4406,21 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
                 src = frames;
             }
             if (r.taps[ch]) {
-                if (int rc = blur_frames(c, src, frames, np + 1, r.radius[ch], ad + at_taps[ch])) return rc;
+                if (int rc = blur_frames(c, src, frames, np + 1, r.radius[ch], blur_tmp, d_taps[ch])) return rc;
                 src = frames;
             }
             d[ch] = sweep_dst(chan[ch], chunk_out[ch], fs, 0, k0);
             // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
-            if (int rc = box_flow_pairs(c, src, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d[ch].f[0], d[ch].f[1],
+            if (int rc = box_flow_pairs(c, bf_planes, src, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d[ch].f[0], d[ch].f[1],
                                         d[ch].f[2], d[ch].keep_g ? d[ch].f[3] : nullptr)) return rc;
             sweep_tail_speed(c, tail, ch, k0, np, d[ch].f[2]);
             if (r.abins) {
                 Prof prof(c, VOF_K_REDUCE, 0);
                 k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
-                    d[ch].f[0], d[ch].f[1], d[ch].f[2], fs, ad + at_aedges, r.abins, au + at_ahist + (size_t)ch * r.abins, ad + at_apart);
+                    d[ch].f[0], d[ch].f[1], d[ch].f[2], fs, d_aedges, r.abins, d_ahist + (size_t)ch * r.abins, d_apart);
                 const int nt = np * r.abins;
-                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_apart, ang_blk, r.abins, np,
-                                                                        ad + at_awsum + ((size_t)ch * P + k0) * r.abins);
+                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_apart, ang_blk, r.abins, np,
+                                                                        d_awsum + ((size_t)ch * P + k0) * r.abins);
             }
             if (int rc = sweep_tail_moments(c, tail, ch, k0, np, d[ch].f[2], d[ch].f[3])) return rc;
         }
@@ -4277,17 +4429,17 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
             a.vxa = d[0].f[0]; a.vya = d[0].f[1]; a.spa = d[0].f[2];
             a.vxb = d[1].f[0]; a.vyb = d[1].f[1]; a.spb = d[1].f[2];
             a.fs = fs;
-            a.tedges = ad + at_tedges; a.tbins = r.tbins;
-            a.ea = ad + at_jedges[0]; a.eb = ad + at_jedges[1]; a.ba = ba; a.bb = bb;
+            a.tedges = d_tedges; a.tbins = r.tbins;
+            a.ea = d_jedges[0]; a.eb = d_jedges[1]; a.ba = ba; a.bb = bb;
             a.has_min = r.jmin ? 1 : 0; a.min_b = r.jmin ? *r.jmin : 0.0;
             a.clip = r.quirks ? 0 : 1;
-            a.thist = au + at_thist; a.jhist = au + at_jhist; a.counters = au + at_jc;
-            a.partials = ad + at_tpart;
+            a.thist = d_thist; a.jhist = d_jhist; a.counters = d_jc;
+            a.partials = d_tpart;
             c->cur_units = np;
             Prof prof(c, VOF_K_REDUCE, 0, 48.0 * fs);
             k_cp_joint<<<dim3(cp_blk, np), 64, cp_lds(r.tbins, ba, bb), c->stream>>>(a);
             const int nt = np * r.tbins;
-            k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(ad + at_tpart, cp_blk, r.tbins, np, ad + at_twsum + (size_t)k0 * r.tbins);
+            k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_tpart, cp_blk, r.tbins, np, d_twsum + (size_t)k0 * r.tbins);
         }
         if (hipGetLastError() != hipSuccess) { c->err = "channel comparison: launch failed"; return -2; }
         for (int ch = 0; ch < 2; ++ch)
@@ -4295,13 +4447,12 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
     }
     if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
     std::vector<double> sums(n_awsum + n_twsum);
-    if (n_awsum) if (int rc = d2h_bounced(c, sums.data(), ad + at_awsum, n_awsum * 8)) return rc;
-    if (int rc = d2h_bounced(c, sums.data() + n_awsum, ad + at_twsum, n_twsum * 8)) return rc;
-    const unsigned long long* own = tail.counters.data() + (tail.n_counters - counts.items);
-    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)own[at_ahist + t];
-    for (int b = 0; b < r.tbins; ++b) r.thist[b] = (int64_t)own[at_thist + b];
-    for (size_t t = 0; t < n_jhist; ++t) r.jhist[t] = (int64_t)own[at_jhist + t];
-    r.jcounts[0] = (int64_t)own[at_jc]; r.jcounts[1] = (int64_t)own[at_jc + 1];
+    if (n_awsum) if (int rc = d2h_bounced(c, sums.data(), d_awsum, n_awsum * 8)) return rc;
+    if (int rc = d2h_bounced(c, sums.data() + n_awsum, d_twsum, n_twsum * 8)) return rc;
+    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)tail.host(d_ahist)[t];
+    for (int b = 0; b < r.tbins; ++b) r.thist[b] = (int64_t)tail.host(d_thist)[b];
+    for (size_t t = 0; t < n_jhist; ++t) r.jhist[t] = (int64_t)tail.host(d_jhist)[t];
+    r.jcounts[0] = (int64_t)tail.host(d_jc)[0]; r.jcounts[1] = (int64_t)tail.host(d_jc)[1];
     for (int ch = 0; ch < 2; ++ch) {
         for (int b = 0; b < r.abins; ++b) {                  // the pairs' sums in pair order
             double w = 0.0;
@@ -4338,158 +4489,6 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
 int vof_compare_flows_dev(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(false)); }
 int vof_compare_flows_host(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(true)); }
 
-// ---- frame chunks: the walk of the frame-wise calls through c->pre_buf ------------------------------
-constexpr int PRE_MAX_FLIGHT = 16;        // units in flight when the caller leaves the number to the library
-constexpr int PRE_MAX_WANT = 4096;        // ... and at most when it does not (grid z)
-
-// One call of the adaptive threshold, CLAHE, the resize or Farnebaeck's flow over a stack of `n` units (frames or pairs), on the
-// stack of that call: the call declares its regions of the scratch buffer, plan() sizes the chunk and carves the buffer, range()
-// reduces a stack, run() walks the chunks.  What a staged input holds is recorded here alone: nothing staged outlives the call.
-extern "C++" {
-struct FrameChunks {
-    struct Region { void* ptr; size_t bytes; bool per_unit; };     // ptr: where the carve stores the region's address
-    struct In { const double* stack; double* slot; int k0, nf; };  // _host: slot holds units [k0, k0 + nf) of stack (nf 0: nothing)
-    struct Out { char* caller; size_t bytes; char* slot; };        // bytes per unit
-    vof_ctx* const c; const char* const what;                      // what: the call, for messages
-    const int n, want; const bool host;                            // units; the caller's frames_in_flight
-    const size_t fs;                                               // doubles per unit of an input stack
-    int cap = 0;                                                   // units in flight (plan)
-    PpRange* part = nullptr;                                       // the range reduction's partial records, then its result
-    double rg[3] = {};                                             // ... and what range() found
-    std::vector<Region> regions;
-    In in[2] = {}; Out out[3] = {}; int n_in = 0, n_out = 0;
-
-    FrameChunks(vof_ctx* c_, const char* what_, int n_, int want_, bool host_) : c(c_), what(what_), n(n_), want(want_), host(host_), fs(frame_stride(c_)) {
-        once(&part, (PP_RANGE_BLOCKS + 1) * sizeof(PpRange));
-    }
-    FrameChunks(const FrameChunks&) = delete;                      // the regions point into the object
-
-    // what every frame-wise entry point checks first
-    static int check(vof_ctx* c, std::initializer_list<const void*> pointers, int n, const char* n_name) {
-        if (!c) return -1;
-        for (const void* p : pointers) if (!p) { c->err = "NULL pointer"; return -1; }
-        if (n < 1) { c->err = std::string(n_name) + " must be >= 1"; return -1; }
-        return 0;
-    }
-
-    // The request.  *ptr (a pointer of any type) is the region's address after plan(): `bytes` once per call, or per unit in
-    // flight, unit after unit - align_units: each at a multiple of 256 bytes; per_unit returns the stride.
-    static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-    void once(void* ptr, size_t bytes) { regions.push_back({ptr, bytes, false}); }
-    size_t per_unit(void* ptr, size_t bytes, bool align_units = false) {
-        regions.push_back({ptr, align_units ? up256(bytes) : bytes, true});
-        return regions.back().bytes;
-    }
-    void input(const double* stack) {                              // fs doubles per unit; _host: staged
-        if (host) per_unit(&in[n_in].slot, fs * sizeof(double));
-        in[n_in++].stack = stack;
-    }
-    void output(void* caller, size_t unit_bytes) {                 // _host: staged, then copied to `caller`
-        if (host) per_unit(&out[n_out].slot, unit_bytes);
-        out[n_out].caller = (char*)caller; out[n_out++].bytes = unit_bytes;
-    }
-
-    // The layout, stated once: region after region, each at a multiple of 256 bytes.  Returns the bytes `units` in flight take;
-    // a null base only measures.
-    size_t carve(char* base, int units) {
-        size_t at = 0;
-        for (const Region& r : regions) {
-            if (base) { char* q = base + at; memcpy(r.ptr, &q, sizeof q); }
-            at += up256(r.per_unit ? (size_t)units * r.bytes : r.bytes);
-        }
-        return at;
-    }
-
-    // The chunk size - `want`, or as many units as a quarter of the free device memory holds (an existing larger buffer is used
-    // in full) - and the buffer, grown (never shrunk) to it.
-    int plan() {
-        HIPCHK(hipSetDevice(c->device));
-        cap = std::min(want > 0 ? std::min(want, PRE_MAX_WANT) : PRE_MAX_FLIGHT, n);
-        if (want <= 0) {
-            size_t fr = 0, tot = 0;
-            HIPCHK(hipMemGetInfo(&fr, &tot));
-            const size_t budget = std::max(fr / 4, c->pre_bytes);
-            while (cap > 1 && carve(nullptr, cap) > budget) --cap;
-        }
-        const size_t need = carve(nullptr, cap);
-        if (need > c->pre_bytes) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (int rc = dev_free(c, c->pre_buf)) return rc;
-            c->pre_buf = nullptr; c->pre_bytes = 0;
-            if (int rc = dev_alloc(c, &c->pre_buf, need)) {
-                (void)hipGetLastError();
-                c->err = std::string(what) + ": no device memory for " + std::to_string(need >> 20) + " MiB of scratch (" + std::to_string(cap) +
-                         " frame(s) in flight): " + c->err;
-                return rc;
-            }
-            c->pre_bytes = need;
-        }
-        carve(c->pre_buf, cap);
-        return 0;
-    }
-
-    // Units [k0, k0 + nf) of input s on the device: the caller's own memory, or the slot - uploaded unless it holds exactly these
-    int staged(int s, int k0, int nf, const double** p) {
-        In& i = in[s];
-        *p = host ? i.slot : i.stack + (size_t)k0 * fs;
-        if (!host || (i.nf == nf && i.k0 == k0)) return 0;
-        if (int rc = h2d_bounced(c, i.slot, i.stack + (size_t)k0 * fs, (size_t)nf * fs * sizeof(double))) return rc;
-        i.k0 = k0; i.nf = nf;
-        return 0;
-    }
-
-    // rg = (max, min of the finite values, non-finite count) of the whole of input s (_host: chunk by chunk through its slot), to
-    // `report` too if there is one; then return code 1 and the message if anything is non-finite or outside the permitted [lo, hi]
-    int range(int s, double lo, double hi, const char* outside, const char* note = "", double* report = nullptr) {
-        PpRange* const rng = part + PP_RANGE_BLOCKS;
-        PpRange acc{-INFINITY, INFINITY, 0};
-        const int chunk = host ? cap : n;
-        for (int k0 = 0; k0 < n; k0 += chunk) {
-            const int nf = std::min(chunk, n - k0);
-            const double* src;
-            if (int rc = staged(s, k0, nf, &src)) return rc;
-            const size_t m = (size_t)nf * fs;
-            const int nb = (int)std::min<size_t>(PP_RANGE_BLOCKS, (m + 8 * PP_BLOCK - 1) / (8 * PP_BLOCK));
-            c->cur_units = nf;
-            {
-                Prof prof(c, VOF_K_PREPROCESS, PP_ST_RANGE, 8.0 * fs);
-                k_pp_range<<<nb, PP_BLOCK, 0, c->stream>>>(src, m, part);
-                k_pp_range_final<<<1, 64, 0, c->stream>>>(part, nb, rng);
-            }
-            HIPCHK(hipGetLastError());
-            PpRange r;
-            if (int rc = d2h_bounced(c, &r, rng, sizeof r)) return rc;
-            acc.vmax = std::max(acc.vmax, r.vmax); acc.vmin = std::min(acc.vmin, r.vmin); acc.bad += r.bad;
-        }
-        rg[0] = acc.vmax; rg[1] = acc.vmin; rg[2] = (double)acc.bad;
-        if (report) memcpy(report, rg, sizeof rg);
-        const char* found = rg[2] > 0 ? "non-finite values" : (rg[1] < lo || rg[0] > hi ? outside : nullptr);
-        if (!found) return 0;
-        c->err = std::string(what) + ": the movie holds " + found + note;
-        return 1;
-    }
-
-    // The chunks in turn: body(k0, nf, inputs, outputs) enqueues the kernels of units [k0, k0 + nf) - device pointers, one per
-    // declared input and output - and returns 0; _host: the outputs are then copied to the caller's arrays.
-    template <class Body>
-    int run(Body&& body) {
-        for (int k0 = 0; k0 < n; k0 += cap) {
-            const int nf = std::min(cap, n - k0);
-            const double* src[2] = {}; void* dst[3] = {};
-            for (int s = 0; s < n_in; ++s) if (int rc = staged(s, k0, nf, &src[s])) return rc;
-            for (int a = 0; a < n_out; ++a) dst[a] = host ? out[a].slot : out[a].caller + (size_t)k0 * out[a].bytes;
-            c->cur_units = nf;
-            if (int rc = body(k0, nf, src, dst)) return rc;
-            HIPCHK(hipGetLastError());
-            for (int a = 0; host && a < n_out; ++a)
-                if (int rc = d2h_bounced(c, out[a].caller + (size_t)k0 * out[a].bytes, dst[a], (size_t)nf * out[a].bytes)) return rc;
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return 0;
-    }
-};
-}  // extern "C++"
-
 // ---- preprocessing: adaptive threshold and CLAHE (apply_adaptive_threshold, apply_clahe; vof_preprocess.hpp) ---------------
 static int adaptive_threshold_impl(vof_ctx* c, const double* movie, int n_frames, int window, double threshold, int flight, uint8_t* mask,
                                    double* range, bool host) {
@@ -4501,7 +4500,7 @@ static int adaptive_threshold_impl(vof_ctx* c, const double* movie, int n_frames
     const size_t fs = frame_stride(c);
     FrameChunks fc(c, "adaptive threshold", n_frames, flight, host);
     unsigned int* H;                                                                     // row sums
-    fc.per_unit(&H, fs * sizeof(unsigned int));
+    fc.sc.per_unit(&H, fs);
     fc.input(movie);
     fc.output(mask, fs);
     if (int rc = fc.plan()) return rc;
@@ -4559,8 +4558,8 @@ static int clahe_impl(vof_ctx* c, const double* movie, int n_frames, double clip
     FrameChunks fc(c, "CLAHE", n_frames, flight, host);
     unsigned int* hist;
     uint16_t* lut;
-    fc.per_unit(&hist, hist_bytes);
-    fc.per_unit(&lut, lut_bytes);
+    fc.sc.per_unit(&hist, ntiles * PP_BINS);
+    fc.sc.per_unit(&lut, ntiles * PP_BINS);
     fc.input(movie);
     fc.output(out, fs * sizeof(double));
     if (int rc = fc.plan()) return rc;
@@ -4675,7 +4674,7 @@ static int resize_area_impl(vof_ctx* c, const double* movie, int n_frames, int o
     const size_t fs = frame_stride(c), os = (size_t)out_i * out_j;
     FrameChunks fc(c, "resize", n_frames, flight, host);
     int* q;                                                             // the axis tables on the device
-    fc.once(&q, tab.size() * 4);
+    fc.sc.once(&q, tab.size());
     fc.input(movie);
     fc.output(out, os * sizeof(double));
     if (int rc = fc.plan()) return rc;
@@ -4757,8 +4756,8 @@ static int farneback_impl(vof_ctx* c, const double* first, const double* second,
     const size_t fs = frame_stride(c);
     FrameChunks fc(c, "Farneback flow", n_pairs, flight, host);
     float *planes, *d_tab;
-    const size_t ps = fc.per_unit(&planes, (size_t)(box ? FB_BOX_PLANES : FB_PLANES) * fs * sizeof(float), true) / sizeof(float);   // floats from a pair's planes to the next pair's
-    fc.once(&d_tab, tab.size() * sizeof(float));
+    const size_t ps = fc.sc.per_unit(&planes, (size_t)(box ? FB_BOX_PLANES : FB_PLANES) * fs, true);   // floats from a pair's planes to the next pair's
+    fc.sc.once(&d_tab, tab.size());
     fc.input(first);
     fc.input(second);
     for (double* field : {v_x, v_y, speed}) fc.output(field, fs * sizeof(double));

@@ -252,7 +252,8 @@ def sequence_references():
 
 def run_sequence(after_each_call=lambda solver: None):
     """Farnebaeck _host (the largest request), uint8 resize _host with two frames in flight, threshold _host, CLAHE _dev,
-    Farnebaeck _dev on one context; every result is checked against its restatement."""
+    Farnebaeck _dev on one context; every result is checked against its restatement.  Between them a blur _host and a box-size
+    sweep _host, checked against fresh contexts."""
     import torch
     from opticalflow_amd import _native
     inputs, want = sequence_inputs(), sequence_references()
@@ -270,8 +271,20 @@ def run_sequence(after_each_call=lambda solver: None):
             assert all(np.isfinite(g).all() for g in (got if key == "flow" else [got])), key
             results.append(got)
 
+        def as_on_a_fresh_context(call):
+            """The blur and the box-size sweep take their scratch from the same buffer: each equals its run on a context of its own."""
+            got = call(solver)
+            after_each_call(solver)
+            with _native.Solver(41, 53, 1) as fresh:
+                want_fresh = call(fresh)
+            for g, w in zip(got, want_fresh):
+                assert g.dtype == w.dtype and g.shape == w.shape and (g.tobytes() == w.tobytes() or np.array_equal(g, w, equal_nan=True))
+
         done(solver.farneback_host(flow[:-1], flow[1:], plan, iterations), "flow")
+        as_on_a_fresh_context(lambda s: (s.blur_host(flow, of().gaussian_taps(1.5)),))
         done(solver.resize_area_host(inputs["resize"], 8, 10, _native.RESIZE_U8, frames_in_flight=2), "resize")
+        as_on_a_fresh_context(lambda s: (lambda r: (r[0], r[1], *r[3]))(s.vary_boxsize_host(
+            flow, (5, 12), include_remodelling=True, histogram_edges=np.linspace(0.0, 4.0, 9), return_fields=True)))
         done(solver.adaptive_threshold_host(inputs["threshold"], 11, 2.5), "threshold")
         frames = torch.as_tensor(inputs["clahe"]).cuda()
         out = torch.zeros(frames.shape, dtype=torch.float64, device="cuda")
