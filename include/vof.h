@@ -525,6 +525,65 @@ int vof_farneback_box_host(vof_ctx* ctx, const double* first, const double* seco
                            int winsize, int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x,
                            double* v_y, double* speed);
 
+/* The reference's filter of a finished flow result, optical_flow.filter_PIV_flow_result (OF.py:2232-2250), in place on the
+ * n_pairs x n_i x n_j float64 stacks v_x, v_y and speed.  movie: the first n_pairs frames of the result's original data, float64.
+ * Per chunk of frames_in_flight frames (0: sized from the free device memory, 16 at most) the frames are blurred into the
+ * scratch buffer with the kernels of vof_blur_stack_* (blur_weights: 2 * blur_radius + 1 taps; same bits) and one kernel
+ * applies, per sample: low = blurred < intensity_threshold; fast = speed > speed_threshold on the incoming speed; v_x and v_y
+ * become 0.0 where low or fast; speed becomes 0.0 where fast, and where low too with zero_speed_under_low != 0 (the reference
+ * leaves it).  NaN compares false and is kept; +inf > speed_threshold is true.  The blurred movie never exists at stack size.
+ * counts (host, 2 x int64): the samples with low, the samples with fast.  A NaN threshold returns -1.
+ * Profiler: class VOF_K_REDUCE, `level` 1 (the mask kernel; the blur is VOF_K_RHS).
+ * _dev: movie and the three stacks are device pointers; _host: host pointers, staged through the pinned bounce buffer. */
+int vof_flow_filter_dev(vof_ctx* ctx, const double* movie, int n_pairs, const double* blur_weights, int blur_radius,
+                        double intensity_threshold, double speed_threshold, int zero_speed_under_low, int frames_in_flight,
+                        double* v_x, double* v_y, double* speed, int64_t* counts);
+int vof_flow_filter_host(vof_ctx* ctx, const double* movie, int n_pairs, const double* blur_weights, int blur_radius,
+                         double intensity_threshold, double speed_threshold, int zero_speed_under_low, int frames_in_flight,
+                         double* v_x, double* v_y, double* speed, int64_t* counts);
+
+/* The comparison of two finished flow results the reference's scripts make (analyse_short_timeinterval_data.py:697-745): six
+ * n_pairs x n_i x n_j float64 stacks, v_x, v_y and speed of result a and of result b, read in chunks of frames_in_flight pairs
+ * (as above); 48 bytes per sample and pass, nothing of field size is written and the stacks are never modified.
+ * Per sample, float64, every operation explicit and in this order:
+ *   sa, sb = the speeds with NaN replaced by 0;  a sample whose sa or sb is +-inf takes no part below;
+ *   m1 = sa > speed_threshold and sb > speed_threshold;
+ *   dot = v_x_b * v_x_a + v_y_b * v_y_a;  w = sb * sa;  cos = dot / w;  theta = acos(cos), radians;
+ *   m2 = sa > angle_threshold and sb > angle_threshold.
+ * With reference_quirks cos is not clipped (a rounding excess over 1 is a NaN theta); without, it is clipped to [-1, 1] first
+ * (NaN stays NaN).
+ * vof_flow_extremes_*: the first pass.  extremes (host, 6 doubles): min and max of sa over the m1 samples, of sb over the m1
+ *   samples, and of cos over the m2 samples whose theta is not NaN; +inf and -inf where there is no such sample.  Exact and
+ *   order independent: block partials and a final reduction, no floating-point atomics.
+ * vof_flow_compare_*: the second pass.  joint_speed_histogram (host, bins_a x bins_b int64) receives
+ *   np.histogram2d(sa[m1], sb[m1], bins, ranges)[0] for the np.linspace edges given (joint_speed_bins: 1 .. 1024 bins per axis),
+ *   angle_histogram (host, angle_bins int64; angle_bins: 1 .. 64) np.histogram(theta[m2], angle_bins, range)[0] without the NaN.
+ *   clamp_angle != 0 (a range chosen from the extremes of these stacks): a theta outside the edges is counted in the first or
+ *   the last bin; 0 (an explicit range): it is dropped, as numpy drops it.  Edges are host memory and must increase.
+ *   counts (host, 6 x int64): NaN speeds of a, of b; samples with an infinite speed; m1 samples; m2 samples whose theta is not
+ *   NaN; m2 samples whose theta is NaN (in no bin).  Counters live in LDS first (2-D histograms of more than 4096 bins in global
+ *   memory); integer atomics only, so every result is bit-identical from call to call and for every frames_in_flight.
+ * Profiler: class VOF_K_REDUCE, `level` 2 (extremes) and 3 (histograms).
+ * _dev: the six stacks are device pointers; _host: host pointers, staged through the pinned bounce buffer. */
+int vof_flow_extremes_dev(vof_ctx* ctx, const double* v_x_a, const double* v_y_a, const double* speed_a, const double* v_x_b,
+                          const double* v_y_b, const double* speed_b, int n_pairs, double speed_threshold, double angle_threshold,
+                          int reference_quirks, int frames_in_flight, double* extremes);
+int vof_flow_extremes_host(vof_ctx* ctx, const double* v_x_a, const double* v_y_a, const double* speed_a, const double* v_x_b,
+                           const double* v_y_b, const double* speed_b, int n_pairs, double speed_threshold, double angle_threshold,
+                           int reference_quirks, int frames_in_flight, double* extremes);
+int vof_flow_compare_dev(vof_ctx* ctx, const double* v_x_a, const double* v_y_a, const double* speed_a, const double* v_x_b,
+                         const double* v_y_b, const double* speed_b, int n_pairs, double speed_threshold, double angle_threshold,
+                         int reference_quirks, const double* joint_speed_edges_a, int joint_speed_bins_a,
+                         const double* joint_speed_edges_b, int joint_speed_bins_b, const double* angle_edges, int angle_bins,
+                         int clamp_angle, int frames_in_flight, int64_t* joint_speed_histogram, int64_t* angle_histogram,
+                         int64_t* counts);
+int vof_flow_compare_host(vof_ctx* ctx, const double* v_x_a, const double* v_y_a, const double* speed_a, const double* v_x_b,
+                          const double* v_y_b, const double* speed_b, int n_pairs, double speed_threshold, double angle_threshold,
+                          int reference_quirks, const double* joint_speed_edges_a, int joint_speed_bins_a,
+                          const double* joint_speed_edges_b, int joint_speed_bins_b, const double* angle_edges, int angle_bins,
+                          int clamp_angle, int frames_in_flight, int64_t* joint_speed_histogram, int64_t* angle_histogram,
+                          int64_t* counts);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

@@ -121,6 +121,14 @@ SIGNATURES = {
                                         C.c_double, C.c_int, _vp, _vp, _vp]),
     "vof_farneback_box_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
                                          C.c_double, C.c_int, _vp, _vp, _vp]),
+    "vof_flow_filter_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "vof_flow_filter_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "vof_flow_extremes_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp]),
+    "vof_flow_extremes_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp]),
+    "vof_flow_compare_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                       _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "vof_flow_compare_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                        _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -642,6 +650,52 @@ class Solver:
         """The same on device memory: two float64 stacks of ``n_pairs`` frames in, three float64 ``(n_pairs, n_i, n_j)`` arrays out
         (none of them may alias a stack)."""
         self._farneback("vof_farneback_dev", first, second, n_pairs, plan, iterations, velocity_scale, frames_in_flight, v_x, v_y, speed, box=box)
+
+    # -- two finished flow results (vof_flowcompare.hpp): numpy arrays take the _host twin, device memory the _dev twin
+    @staticmethod
+    def _twin(name, arrays):
+        host = [isinstance(a, np.ndarray) for a in arrays if a is not None]
+        assert all(host) or not any(host), "host arrays and device memory do not mix in one call"
+        return name + ("_host" if host and host[0] else "_dev")
+
+    def flow_filter(self, movie, weights, n_pairs, intensity_threshold, speed_threshold, zero_speed_under_low, v_x, v_y, speed,
+                    frames_in_flight=0):
+        """``vof_flow_filter_*``: the reference's result filter in place on ``v_x``, ``v_y`` and ``speed`` (float64, ``(n_pairs, n_i,
+        n_j)``), ``movie`` the first ``n_pairs`` float64 frames, ``weights`` the blur taps.  Returns ``(low, fast)`` sample counts."""
+        weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        counts = np.zeros(2, dtype=np.int64)
+        fn = self._twin("vof_flow_filter", (movie, v_x, v_y, speed))
+        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_pairs), _ptr(weights), weights.size // 2, float(intensity_threshold),
+                                   float(speed_threshold), int(bool(zero_speed_under_low)), int(frames_in_flight), _ptr(v_x), _ptr(v_y),
+                                   _ptr(speed), _ptr(counts))
+        self._check(rc, fn)
+        return counts
+
+    def flow_extremes(self, stacks, n_pairs, speed_threshold, angle_threshold, reference_quirks=True, frames_in_flight=0):
+        """``vof_flow_extremes_*`` of the six stacks ``(v_x_a, v_y_a, speed_a, v_x_b, v_y_b, speed_b)``: float64 ``(3, 2)``, the
+        (min, max) of speed a, of speed b and of cos over the samples that take part (+inf, -inf where none does)."""
+        out = np.zeros((3, 2), dtype=np.float64)
+        fn = self._twin("vof_flow_extremes", stacks)
+        rc = getattr(self.lib, fn)(self.h, *[_ptr(s) for s in stacks], int(n_pairs), float(speed_threshold), float(angle_threshold),
+                                   int(bool(reference_quirks)), int(frames_in_flight), _ptr(out))
+        self._check(rc, fn)
+        return out
+
+    def flow_compare(self, stacks, n_pairs, speed_threshold, angle_threshold, reference_quirks, edges_a, edges_b, angle_edges, clamp_angle,
+                     frames_in_flight=0):
+        """``vof_flow_compare_*`` of the six stacks against the three edge vectors: ``(joint_speed_histogram, angle_histogram,
+        counts)``, int64 ``(bins_a, bins_b)``, ``(angle_bins,)`` and the six counters of include/vof.h."""
+        edges = [np.ascontiguousarray(e, dtype=np.float64).ravel() for e in (edges_a, edges_b, angle_edges)]
+        jhist = np.zeros((edges[0].size - 1, edges[1].size - 1), dtype=np.int64)
+        thist = np.zeros(edges[2].size - 1, dtype=np.int64)
+        counts = np.zeros(6, dtype=np.int64)
+        fn = self._twin("vof_flow_compare", stacks)
+        rc = getattr(self.lib, fn)(self.h, *[_ptr(s) for s in stacks], int(n_pairs), float(speed_threshold), float(angle_threshold),
+                                   int(bool(reference_quirks)), _ptr(edges[0]), edges[0].size - 1, _ptr(edges[1]), edges[1].size - 1,
+                                   _ptr(edges[2]), edges[2].size - 1, int(bool(clamp_angle)), int(frames_in_flight), _ptr(jhist), _ptr(thist),
+                                   _ptr(counts))
+        self._check(rc, fn)
+        return jhist, thist, counts
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

@@ -15,6 +15,7 @@
 #include "vof_boxsweep.hpp"
 #include "vof_blursweep.hpp"
 #include "vof_compare.hpp"
+#include "vof_flowcompare.hpp"
 #include "vof_liushen.hpp"
 #include "vof_preprocess.hpp"
 #include "vof_resize.hpp"
@@ -2574,8 +2575,8 @@ struct Scratch {
 constexpr int PRE_MAX_FLIGHT = 16;        // units in flight when the caller leaves the number to the library
 constexpr int PRE_MAX_WANT = 4096;        // ... and at most when it does not (grid z)
 
-// One call of the adaptive threshold, CLAHE, the resize or Farnebaeck's flow over a stack of `n` units (frames or
-// pairs), on the stack of that call: the call declares its regions into the arena sc, plan() sizes the chunk and carves the
+// One call of the adaptive threshold, CLAHE, the resize, Farnebaeck's flow, the result filter or the comparison of two results
+// over a stack of `n` units (frames or pairs), on the stack of that call: the call declares its regions into the arena sc, plan() sizes the chunk and carves the
 // buffer, range() reduces a stack, run() walks the chunks.  What a staged input holds is recorded here alone: nothing staged
 // outlives the call.
 struct FrameChunks {
@@ -2588,7 +2589,8 @@ struct FrameChunks {
     int cap = 0;                                                   // units in flight (plan)
     PpRange* part = nullptr;                                       // the range reduction's partial records, then its result
     double rg[3] = {};                                             // ... and what range() found
-    In in[2] = {}; Out out[3] = {}; int n_in = 0, n_out = 0;
+    static constexpr int MAX_IN = 6, MAX_OUT = 3;                  // the comparison of two results reads six stacks
+    In in[MAX_IN] = {}; Out out[MAX_OUT] = {}; int n_in = 0, n_out = 0;
 
     FrameChunks(vof_ctx* c_, const char* what_, int n_, int want_, bool host_) : c(c_), what(what_), n(n_), want(want_), host(host_), fs(frame_stride(c_)), sc(c_) {
         sc.once(&part, (size_t)PP_RANGE_BLOCKS + 1);
@@ -2668,7 +2670,7 @@ struct FrameChunks {
     int run(Body&& body) {
         for (int k0 = 0; k0 < n; k0 += cap) {
             const int nf = std::min(cap, n - k0);
-            const double* src[2] = {}; void* dst[3] = {};
+            const double* src[MAX_IN] = {}; void* dst[MAX_OUT] = {};
             for (int s = 0; s < n_in; ++s) if (int rc = staged(s, k0, nf, &src[s])) return rc;
             for (int a = 0; a < n_out; ++a) dst[a] = host ? out[a].slot : out[a].caller + (size_t)k0 * out[a].bytes;
             c->cur_units = nf;
@@ -4860,6 +4862,169 @@ int vof_farneback_box_host(vof_ctx* c, const double* first, const double* second
     return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_BOX, winsize, nullptr,
                           iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, true);
 }
+
+// ---- two finished flow results: the result filter and the comparison (filter_PIV_flow_result, compare_flow_results;
+// vof_flowcompare.hpp) ------------------------------------------------------------------------------
+static int flow_filter_impl(vof_ctx* c, const double* movie, int n_pairs, const double* weights, int radius, double intensity, double limit,
+                            int zero_low, int flight, double* v_x, double* v_y, double* speed, int64_t* counts, bool host) {
+    if (int rc = FrameChunks::check(c, {movie, weights, v_x, v_y, speed, counts}, n_pairs, "n_pairs")) return rc;
+    if (radius < 0 || radius > 4096) { c->err = "bad blur_radius"; return -1; }
+    if (std::isnan(intensity) || std::isnan(limit)) { c->err = "flow filter: a threshold is NaN"; return -1; }
+    const size_t fs = frame_stride(c);
+    FrameChunks fc(c, "flow filter", n_pairs, flight, host);
+    double *blurred, *tmp, *w;                                      // the blurred frames of one chunk: never a stack
+    unsigned long long* d_counts;
+    fc.sc.per_unit(&blurred, fs);
+    blur_regions(fc.sc, n_pairs, &tmp, &w, radius);
+    fc.sc.once(&d_counts, 2);
+    fc.input(movie); fc.input(v_x); fc.input(v_y); fc.input(speed);
+    fc.output(v_x, fs * sizeof(double)); fc.output(v_y, fs * sizeof(double)); fc.output(speed, fs * sizeof(double));
+    if (int rc = fc.plan()) return rc;
+    if (int rc = h2d_bounced(c, w, weights, (size_t)(2 * radius + 1) * sizeof(double))) return rc;
+    HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    if (int rc = fc.run([&](int, int nf, const double* const* in, void* const* out) -> int {
+            if (int rc = blur_frames(c, in[0], blurred, nf, radius, tmp, w)) return rc;
+            const size_t n = (size_t)nf * fs;
+            const int blocks = (int)std::min<size_t>(2048, (n + 8 * FC_BLOCK - 1) / (8 * FC_BLOCK));
+            Prof prof(c, VOF_K_REDUCE, FC_ST_MASK, 56.0 * fs);
+            k_fc_mask<<<blocks, FC_BLOCK, 0, c->stream>>>(blurred, in[1], in[2], in[3], n, intensity, limit, zero_low, (double*)out[0],
+                                                          (double*)out[1], (double*)out[2], d_counts);
+            return 0;
+        })) return rc;
+    unsigned long long h[2];
+    if (int rc = d2h_bounced(c, h, d_counts, sizeof h)) return rc;
+    counts[0] = (int64_t)h[0]; counts[1] = (int64_t)h[1];
+    return 0;
+}
+
+int vof_flow_filter_dev(vof_ctx* c, const double* movie, int n_pairs, const double* blur_weights, int blur_radius, double intensity_threshold,
+                        double speed_threshold, int zero_speed_under_low, int frames_in_flight, double* v_x, double* v_y, double* speed,
+                        int64_t* counts) {
+    return flow_filter_impl(c, movie, n_pairs, blur_weights, blur_radius, intensity_threshold, speed_threshold, zero_speed_under_low,
+                            frames_in_flight, v_x, v_y, speed, counts, false);
+}
+int vof_flow_filter_host(vof_ctx* c, const double* movie, int n_pairs, const double* blur_weights, int blur_radius, double intensity_threshold,
+                         double speed_threshold, int zero_speed_under_low, int frames_in_flight, double* v_x, double* v_y, double* speed,
+                         int64_t* counts) {
+    return flow_filter_impl(c, movie, n_pairs, blur_weights, blur_radius, intensity_threshold, speed_threshold, zero_speed_under_low,
+                            frames_in_flight, v_x, v_y, speed, counts, true);
+}
+
+// the six stacks of two results as inputs of a frame-chunk walk, and those of one chunk as the kernels take them
+struct FlowStacks { const double *vxa, *vya, *spa, *vxb, *vyb, *spb; };
+static int flow_stacks_check(vof_ctx* c, const FlowStacks& s, int n_pairs, double speed_min, double angle_min) {
+    if (int rc = FrameChunks::check(c, {s.vxa, s.vya, s.spa, s.vxb, s.vyb, s.spb}, n_pairs, "n_pairs")) return rc;
+    if (std::isnan(speed_min) || std::isnan(angle_min)) { c->err = "flow comparison: a threshold is NaN"; return -1; }
+    return 0;
+}
+static void flow_stacks_inputs(FrameChunks& fc, const FlowStacks& s) {
+    for (const double* p : {s.vxa, s.vya, s.spa, s.vxb, s.vyb, s.spb}) fc.input(p);
+}
+static FlowPlanes flow_planes(const double* const* in, size_t fs) { return FlowPlanes{in[0], in[1], in[2], in[3], in[4], in[5], fs}; }
+
+static int flow_extremes_impl(vof_ctx* c, const FlowStacks& s, int n_pairs, double speed_min, double angle_min, int quirks, int flight,
+                              double* extremes, bool host) {
+    if (int rc = flow_stacks_check(c, s, n_pairs, speed_min, angle_min)) return rc;
+    if (!extremes) { c->err = "NULL pointer"; return -1; }
+    const size_t fs = frame_stride(c);
+    const int blk = fc_blocks(fs);
+    FrameChunks fc(c, "flow extremes", n_pairs, flight, host);
+    FcExtremes *part, *acc;
+    fc.sc.per_unit(&part, (size_t)blk);
+    fc.sc.once(&acc, 1);
+    flow_stacks_inputs(fc, s);
+    if (int rc = fc.plan()) return rc;
+    const FcExtremes none{INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+    if (int rc = h2d_bounced(c, acc, &none, sizeof none)) return rc;
+    if (int rc = fc.run([&](int, int nf, const double* const* in, void* const*) -> int {
+            Prof prof(c, VOF_K_REDUCE, FC_ST_EXTREMES, 48.0 * fs);
+            k_fc_extremes<<<dim3(blk, nf), FC_BLOCK, 0, c->stream>>>(flow_planes(in, fs), speed_min, angle_min, quirks ? 0 : 1, part);
+            k_fc_extremes_fold<<<1, 64, 0, c->stream>>>(part, blk * nf, acc);
+            return 0;
+        })) return rc;
+    static_assert(sizeof(FcExtremes) == 6 * sizeof(double), "extremes: six doubles");
+    return d2h_bounced(c, extremes, acc, sizeof(FcExtremes));
+}
+
+#define VOF_FLOW_STACKS_ARGS const double *v_x_a, const double *v_y_a, const double *speed_a, const double *v_x_b, const double *v_y_b, const double *speed_b
+#define VOF_FLOW_STACKS FlowStacks{v_x_a, v_y_a, speed_a, v_x_b, v_y_b, speed_b}
+
+int vof_flow_extremes_dev(vof_ctx* c, VOF_FLOW_STACKS_ARGS, int n_pairs, double speed_threshold, double angle_threshold, int reference_quirks,
+                          int frames_in_flight, double* extremes) {
+    return flow_extremes_impl(c, VOF_FLOW_STACKS, n_pairs, speed_threshold, angle_threshold, reference_quirks, frames_in_flight, extremes, false);
+}
+int vof_flow_extremes_host(vof_ctx* c, VOF_FLOW_STACKS_ARGS, int n_pairs, double speed_threshold, double angle_threshold, int reference_quirks,
+                           int frames_in_flight, double* extremes) {
+    return flow_extremes_impl(c, VOF_FLOW_STACKS, n_pairs, speed_threshold, angle_threshold, reference_quirks, frames_in_flight, extremes, true);
+}
+
+struct FlowCompareReq {
+    FlowStacks s; int n_pairs; double speed_min, angle_min; int quirks;
+    const double* edges[3]; int bins[3];                      // speed of a, speed of b, theta
+    int clamp_theta, flight;
+    int64_t *jhist, *thist, *counts;
+    bool host;
+};
+
+static int flow_compare_impl(vof_ctx* c, const FlowCompareReq& r) {
+    if (int rc = flow_stacks_check(c, r.s, r.n_pairs, r.speed_min, r.angle_min)) return rc;
+    if (!r.edges[0] || !r.edges[1] || !r.edges[2] || !r.jhist || !r.thist || !r.counts) { c->err = "NULL pointer"; return -1; }
+    for (int e = 0; e < 3; ++e) {
+        const int most = e < 2 ? CP_MAX_SPEED_BINS : CP_MAX_THETA_BINS;
+        if (r.bins[e] < 1 || r.bins[e] > most) {
+            c->err = std::string(e < 2 ? "joint_speed_bins must be 1 .. " : "angle_bins must be 1 .. ") + std::to_string(most) + (e < 2 ? " per axis" : "");
+            return -1;
+        }
+        bool rising = r.edges[e][r.bins[e]] > r.edges[e][0];
+        for (int b = 0; b < r.bins[e]; ++b) rising = rising && r.edges[e][b + 1] >= r.edges[e][b];
+        if (!rising) { c->err = e < 2 ? "joint_speed_edges must increase" : "angle_edges must increase"; return -1; }
+    }
+    const size_t fs = frame_stride(c);
+    const int blk = fc_blocks(fs);
+    const size_t nj = (size_t)r.bins[0] * r.bins[1];
+    FrameChunks fc(c, "flow comparison", r.n_pairs, r.flight, r.host);
+    double* d_edges[3];
+    unsigned long long *d_jhist, *d_thist, *d_counters;
+    for (int e = 0; e < 3; ++e) fc.sc.once(&d_edges[e], (size_t)r.bins[e] + 1);
+    fc.sc.once(&d_jhist, nj);
+    fc.sc.once(&d_thist, (size_t)r.bins[2]);
+    fc.sc.once(&d_counters, (size_t)FC_COUNTERS);
+    flow_stacks_inputs(fc, r.s);
+    if (int rc = fc.plan()) return rc;
+    for (int e = 0; e < 3; ++e)
+        if (int rc = h2d_bounced(c, d_edges[e], r.edges[e], ((size_t)r.bins[e] + 1) * sizeof(double))) return rc;
+    HIPCHK(hipMemsetAsync(d_jhist, 0, nj * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(d_thist, 0, (size_t)r.bins[2] * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(d_counters, 0, FC_COUNTERS * sizeof(unsigned long long), c->stream));
+    if (int rc = fc.run([&](int, int nf, const double* const* in, void* const*) -> int {
+            FcHistArgs a{};
+            a.p = flow_planes(in, fs);
+            a.speed_min = r.speed_min; a.angle_min = r.angle_min; a.clip = r.quirks ? 0 : 1; a.clamp_theta = r.clamp_theta ? 1 : 0;
+            a.ea = d_edges[0]; a.ba = r.bins[0]; a.eb = d_edges[1]; a.bb = r.bins[1];
+            a.tedges = d_edges[2]; a.tbins = r.bins[2];
+            a.jhist = d_jhist; a.thist = d_thist; a.counters = d_counters;
+            Prof prof(c, VOF_K_REDUCE, FC_ST_HISTOGRAMS, 48.0 * fs);
+            k_fc_histograms<<<dim3(blk, nf), FC_BLOCK, 0, c->stream>>>(a);
+            return 0;
+        })) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counters are copied as they are");
+    if (int rc = d2h_bounced(c, r.jhist, d_jhist, nj * sizeof(int64_t))) return rc;
+    if (int rc = d2h_bounced(c, r.thist, d_thist, (size_t)r.bins[2] * sizeof(int64_t))) return rc;
+    return d2h_bounced(c, r.counts, d_counters, FC_COUNTERS * sizeof(int64_t));
+}
+
+#define VOF_FLOW_COMPARE_ARGS                                                                                                          \
+    vof_ctx *c, VOF_FLOW_STACKS_ARGS, int n_pairs, double speed_threshold, double angle_threshold, int reference_quirks,               \
+        const double *joint_speed_edges_a, int joint_speed_bins_a, const double *joint_speed_edges_b, int joint_speed_bins_b,          \
+        const double *angle_edges, int angle_bins, int clamp_angle, int frames_in_flight, int64_t *joint_speed_histogram,              \
+        int64_t *angle_histogram, int64_t *counts
+#define VOF_FLOW_COMPARE_REQ(host)                                                                                                     \
+    FlowCompareReq{VOF_FLOW_STACKS, n_pairs, speed_threshold, angle_threshold, reference_quirks,                                       \
+                   {joint_speed_edges_a, joint_speed_edges_b, angle_edges}, {joint_speed_bins_a, joint_speed_bins_b, angle_bins},     \
+                   clamp_angle, frames_in_flight, joint_speed_histogram, angle_histogram, counts, host}
+
+int vof_flow_compare_dev(VOF_FLOW_COMPARE_ARGS) { return flow_compare_impl(c, VOF_FLOW_COMPARE_REQ(false)); }
+int vof_flow_compare_host(VOF_FLOW_COMPARE_ARGS) { return flow_compare_impl(c, VOF_FLOW_COMPARE_REQ(true)); }
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------
 constexpr int LS_CHUNK = 16384;           // pairs per launch (grid z)

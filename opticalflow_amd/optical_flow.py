@@ -65,6 +65,7 @@ atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
+           "compare_flow_results", "filter_PIV_flow_result",
            "apply_adaptive_threshold", "apply_clahe", "downsample_movie", "conduct_opencv_flow", "farneback_plan",
            "calcOpticalFlowFarneback", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_FARNEBACK_GAUSSIAN",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
@@ -1297,6 +1298,247 @@ def compare_channel_flows(movie_a, movie_b, boxsize=31, delta_x=1.0, delta_t=1.0
             result[key] = one
     if filename is not None:
         np.save(filename, result)
+    return result
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Two finished flow results: the reference's result filter (OF.py:2232-2250) and the comparison its scripts make of
+# PIVlab's and Farnebäck's flow (analyse_short_timeinterval_data.py:640-745).  DESIGN.md section 17.
+# ---------------------------------------------------------------------------------------------------------
+FILTER_BLUR_SIGMA = 3                # OF.py:2242
+FILTER_SPEED_LIMIT = 7               # OF.py:2247-2250 compare with 7 whatever speed_threshold says
+
+
+def _is_device_tensor(a):
+    return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+
+def _flow_fields(name, result):
+    """``(v_x, v_y, speed)`` of a flow-result dict as the native calls take them - all numpy arrays or all device tensors,
+    float64, C-contiguous, one shape ``(P, N_i, N_j)`` with frames of at least 4 x 4 pixels; ``ValueError`` otherwise, before the
+    library is touched."""
+    fields = []
+    for key in ("v_x", "v_y", "speed"):
+        try:
+            f = result[key]
+        except (KeyError, TypeError, IndexError):
+            raise ValueError(f"{name} must be a flow-result dict with 'v_x', 'v_y' and 'speed'") from None
+        if not (isinstance(f, np.ndarray) or _is_device_tensor(f)):
+            raise ValueError(f"{name}[{key!r}] must be a numpy array or a device tensor")
+        if _movie_dtype_name(f) != "float64":
+            raise ValueError(f"{name}[{key!r}] is {_movie_dtype_name(f)}, not float64: cast it")
+        if _is_device_tensor(f) and not f.is_cuda:
+            raise ValueError(f"{name}[{key!r}] is a tensor in host memory: pass a numpy array or a device tensor")
+        if not (f.flags["C_CONTIGUOUS"] if isinstance(f, np.ndarray) else f.is_contiguous()):
+            raise ValueError(f"{name}[{key!r}] must be contiguous")
+        fields.append(f)
+    shape = tuple(fields[0].shape)
+    if len(shape) != 3 or any(tuple(f.shape) != shape for f in fields):
+        raise ValueError(f"'v_x', 'v_y' and 'speed' of {name} must have one common shape (pairs, x, y)")
+    if shape[0] < 1 or shape[1] < 4 or shape[2] < 4:
+        raise ValueError(f"{name} needs at least one pair of at least 4x4 pixels")
+    if len({_is_device_tensor(f) for f in fields}) != 1:
+        raise ValueError(f"the fields of {name} must be all numpy arrays or all device tensors")
+    return fields
+
+
+def _tensor_device(fields, device):
+    """The torch device the tensors of a call share (``ValueError`` if they do not), synchronised: the library launches on its own
+    stream."""
+    import torch
+    devices = {f.device for f in fields}
+    if len(devices) != 1:
+        raise ValueError("the tensors must lie on one device")
+    dev = devices.pop()
+    torch.cuda.synchronize(dev)
+    return dev, int(device) if dev.index is None else dev.index
+
+
+def filter_PIV_flow_result(flow_result, intensity_threshold=10, speed_threshold=7, *, device=0, reference_quirks=True):
+    """The reference's filter of a flow result converted from PIV (OF.py:2232-2250) on the GPU, in place like the reference;
+    returns ``None``.
+
+    ``flow_result`` holds ``v_x``, ``v_y`` and ``speed`` of shape ``(T - 1, N_i, N_j)`` and ``original_data`` with ``T`` or ``T - 1``
+    frames of any real dtype; the four are all numpy arrays - which keep their identity and are overwritten - or all device
+    tensors, modified in place.  A field that is not float64 or not contiguous is a ``ValueError`` (cast it: a silent copy would
+    not be filtered in place).
+
+    Per sample: ``blurred`` is ``blur_movie(original_data, 3)`` restricted to the first ``T - 1`` frames, the same bits, blurred a
+    chunk of frames at a time in device scratch (the last frame is not blurred at all, and no blurred stack exists);
+    ``low = blurred < intensity_threshold``; ``fast = speed > S`` on the incoming ``speed``; ``v_x`` and ``v_y`` become ``0.0``
+    where ``low or fast``, ``speed`` where ``fast``.  NaN compares false everywhere and is kept; ``+inf > S`` is true.
+    With ``reference_quirks=True`` (the default) ``S`` is 7 whatever ``speed_threshold`` says and ``speed`` stays where only
+    ``low`` holds, as in the reference; ``reference_quirks=False`` uses ``speed_threshold`` and zeroes ``speed`` under ``low`` too."""
+    fields = _flow_fields("flow_result", flow_result)
+    P, N_i, N_j = fields[0].shape
+    try:
+        movie = flow_result["original_data"]
+    except KeyError:
+        raise ValueError("flow_result has no 'original_data'") from None
+    on_device = _is_device_tensor(fields[0])
+    if _is_device_tensor(movie) != on_device or not (on_device or isinstance(movie, np.ndarray)):
+        raise ValueError("'original_data' and the fields of flow_result must be all numpy arrays or all device tensors")
+    if len(movie.shape) != 3 or tuple(movie.shape[1:]) != (N_i, N_j) or movie.shape[0] not in (P, P + 1):
+        raise ValueError(f"'original_data' must have {P} or {P + 1} frames of {N_i} x {N_j} pixels")
+    name = _movie_dtype_name(movie)
+    if not name.startswith(("uint", "int", "float", "bfloat")):
+        raise ValueError(f"'original_data' is {name}, not a real dtype")
+    if np.isnan(float(intensity_threshold)) or np.isnan(float(speed_threshold)):
+        raise ValueError("a threshold is NaN")
+    limit = float(FILTER_SPEED_LIMIT if reference_quirks else speed_threshold)
+    taps = gaussian_taps(FILTER_BLUR_SIGMA)
+    if on_device:
+        import torch
+        dev, index = _tensor_device(fields + [movie], device)
+        frames = movie[:P].to(dtype=torch.float64).contiguous()
+        torch.cuda.synchronize(dev)
+    else:
+        index, frames = device, np.ascontiguousarray(movie[:P], dtype=np.float64)
+    with _device_context(N_i, N_j, 1, index) as solver:
+        solver.flow_filter(frames, taps, P, float(intensity_threshold), limit, not reference_quirks, *fields)
+
+
+def _explicit_edges(name, bins, value_range):
+    """numpy's own edges of ``bins`` equal bins over an explicit ``(lo, hi)``, its widening of ``lo == hi`` included."""
+    if np.ndim(value_range) != 1 or len(value_range) != 2:
+        raise ValueError(f"{name} must be None or a pair (lo, hi)")
+    lo, hi = float(value_range[0]), float(value_range[1])
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+        raise ValueError(f"{name} must be finite with lo <= hi")
+    return np.histogram_bin_edges(np.zeros(0), bins, range=(lo, hi))
+
+
+def _automatic_edges(bins, lo, hi):
+    """The edges ``plt.hist`` / ``plt.hist2d`` choose for samples whose extremes are ``lo`` and ``hi``: numpy's own, from the two
+    values alone; an empty selection (``lo > hi``, or NaN) takes numpy's range (0, 1)."""
+    if not lo <= hi:
+        return np.histogram_bin_edges(np.zeros(0), bins)
+    return np.histogram_bin_edges(np.array([lo, hi]), bins)
+
+
+def _ground_truth_points(ground_truth, shape):
+    """``(frame, start, end)`` with ``start`` and ``end`` int64 ``(n, 2)`` arrays of (x, y) inside the stack; ``ValueError`` otherwise."""
+    if not isinstance(ground_truth, (tuple, list)) or len(ground_truth) != 3:
+        raise ValueError("ground_truth must be (frame, start, end)")
+    frame, start, end = ground_truth
+    if isinstance(frame, bool) or int(frame) != frame or not 0 <= int(frame) < shape[0]:
+        raise ValueError(f"ground_truth: frame must be an integer 0 .. {shape[0] - 1}")
+    points = []
+    for label, p in (("start", start), ("end", end)):
+        p = np.asarray(p)
+        if p.ndim != 2 or p.shape[1] != 2 or not np.issubdtype(p.dtype, np.integer):
+            raise ValueError(f"ground_truth: {label} must be an integer (n, 2) array of (x, y) pixel positions")
+        if p.size and (p.min() < 0 or p[:, 0].max() >= shape[1] or p[:, 1].max() >= shape[2]):
+            raise ValueError(f"ground_truth: {label} holds a position outside the {shape[1]} x {shape[2]} image")
+        points.append(p.astype(np.int64))
+    if points[0].shape != points[1].shape:
+        raise ValueError("ground_truth: start and end must have the same shape")
+    return int(frame), points[0], points[1]
+
+
+def _gather_points(field, frame, points):
+    """``field[frame, x, y]`` of the ``n`` points as a host float64 vector; only the ``n`` values leave the device."""
+    if isinstance(field, np.ndarray):
+        return field[frame, points[:, 0], points[:, 1]]
+    import torch
+    index = torch.as_tensor(points, device=field.device)
+    return field[frame, index[:, 0], index[:, 1]].cpu().numpy()
+
+
+def compare_flow_results(flow_a, flow_b, *, speed_threshold=0.1, angle_threshold=0.5, joint_speed_bins=(50, 50),
+                         joint_speed_ranges=None, angle_bins=20, angle_range=None, ground_truth=None, reference_quirks=True,
+                         device=0, frames_in_flight=0):
+    """What the reference's scripts do with two finished flow results, PIVlab's and Farnebäck's
+    (analyse_short_timeinterval_data.py:640-745), for any two results on the GPU: the field stacks stay where they are, are
+    never modified (the script overwrites the NaN speeds in its dicts) and only the summaries come back, as host numpy.
+
+    ``flow_a`` and ``flow_b`` hold ``v_x``, ``v_y`` and ``speed`` of one common shape ``(P, N_i, N_j)``, float64 and contiguous, all
+    six numpy arrays or all device tensors (``device`` names the GPU for numpy arrays).  Anything else is a ``ValueError``
+    raised before the library is touched.
+
+    Per sample, in float64, every operation explicit and in this order: ``sa``, ``sb``: the speeds with NaN replaced by 0
+    (``nan_speed_counts`` of them); a sample whose ``sa`` or ``sb`` is infinite takes no part anywhere (``infinite_count``; numpy's
+    automatic range would raise there); ``m1 = sa > speed_threshold and sb > speed_threshold`` - those ``joint_count`` samples go
+    into ``joint_speed_histogram``, ``np.histogram2d(sa[m1], sb[m1], joint_speed_bins, joint_speed_ranges)[0]``; ``dot = v_x_b *
+    v_x_a + v_y_b * v_y_a``, ``w = sb * sa``, ``cos = dot / w``, ``theta = arccos(cos)`` in radians; ``m2 = sa > angle_threshold and
+    sb > angle_threshold`` - those samples go into ``angle_histogram``, ``np.histogram(theta[m2], angle_bins, angle_range)[0]``,
+    except that a NaN ``theta`` is in no bin and counted in ``angle_dropped`` (numpy would raise); ``angle_count`` are the others.
+    With ``reference_quirks=False`` ``cos`` is clipped to [-1, 1] first (NaN stays NaN), so a rounding excess over 1 is an angle
+    of 0 instead of a dropped sample.
+
+    A range that is ``None`` (also one axis of ``joint_speed_ranges``) is the minimum and maximum of the samples that take part,
+    as ``plt.hist2d`` and ``plt.hist`` choose it: a first device pass returns the exact extremes - ``speed_extremes``, ``(2, 2)``:
+    (min, max) of ``sa[m1]`` and of ``sb[m1]``; ``cos_extremes``: of ``cos`` over the ``m2`` samples with a ``theta`` - and the edges are
+    numpy's own, ``np.histogram_bin_edges(np.array([lo, hi]), bins)``, for the angle with ``lo = np.arccos(cos_max)`` and ``hi =
+    np.arccos(cos_min)``; no such sample: numpy's range (0, 1) and NaN extremes.  On an automatic angle range a ``theta`` outside
+    the edges is counted in the first or last bin - every kept sample lies inside by construction, only the last bits of the
+    device's ``acos`` could say otherwise; on an explicit one it is dropped as numpy drops it.  With every range explicit the
+    first pass is skipped and the extremes are NaN.  ``joint_speed_bins``: 1 .. 1024 per axis; ``angle_bins``: 1 .. 64.
+
+    ``ground_truth=(frame, start, end)``: integer ``(n, 2)`` arrays of (x, y) positions inside the image (no negative wrap:
+    ``ValueError``); the ``v_x`` and ``v_y`` of both results at ``[frame, start[:, 0], start[:, 1]]`` are gathered and
+    ``relative_errors``, ``(2, n)``, is ``sqrt((dy - v_y)**2 + (dx - v_x)**2) / sqrt(dy**2 + dx**2)`` with ``(dx, dy) = end - start``,
+    formed on the host (analyse_short_timeinterval_data.py:658-666).
+
+    Returns ``joint_speed_histogram`` (int64), ``joint_speed_edges_a``, ``joint_speed_edges_b``, ``angle_histogram`` (int64),
+    ``angle_edges``, ``nan_speed_counts`` (2), ``infinite_count``, ``joint_count``, ``angle_count``, ``angle_dropped``,
+    ``speed_extremes``, ``cos_extremes`` and, with ``ground_truth``, ``relative_errors``.  Integer atomics and exact extremes only:
+    every summary is bit-identical from call to call and for any ``frames_in_flight`` (pairs read per launch; 0: the library's choice)."""
+    a, b = _flow_fields("flow_a", flow_a), _flow_fields("flow_b", flow_b)
+    shape = tuple(a[0].shape)
+    if tuple(b[0].shape) != shape:
+        raise ValueError("flow_a and flow_b must have the same shape (pairs, x, y)")
+    stacks = a + b
+    on_device = _is_device_tensor(stacks[0])
+    if any(_is_device_tensor(s) != on_device for s in stacks):
+        raise ValueError("flow_a and flow_b must be both numpy arrays or both device tensors")
+    if np.isnan(float(speed_threshold)) or np.isnan(float(angle_threshold)):
+        raise ValueError("a threshold is NaN")
+    if np.ndim(joint_speed_bins) != 1 or len(joint_speed_bins) != 2:
+        raise ValueError("joint_speed_bins must be a pair (bins_a, bins_b)")
+    if not all(int(n) == n and 1 <= int(n) <= COMPARE_MAX_SPEED_BINS for n in joint_speed_bins):
+        raise ValueError(f"joint_speed_bins must be 1 .. {COMPARE_MAX_SPEED_BINS} per axis")
+    if angle_bins is None or int(angle_bins) != angle_bins or not 1 <= int(angle_bins) <= COMPARE_MAX_ANGLE_BINS:
+        raise ValueError(f"angle_bins must be 1 .. {COMPARE_MAX_ANGLE_BINS}")
+    if isinstance(frames_in_flight, bool) or int(frames_in_flight) != frames_in_flight or int(frames_in_flight) < 0:
+        raise ValueError("frames_in_flight must be an integer >= 0")
+    bins = [int(joint_speed_bins[0]), int(joint_speed_bins[1]), int(angle_bins)]
+    if joint_speed_ranges is None:
+        joint_speed_ranges = (None, None)
+    if len(joint_speed_ranges) != 2:
+        raise ValueError("joint_speed_ranges must be None or a pair of (lo, hi) or None")
+    edges = [None if r is None else _explicit_edges("joint_speed_ranges", n, r) for n, r in zip(bins, joint_speed_ranges)]
+    edges.append(None if angle_range is None else _explicit_edges("angle_range", bins[2], angle_range))
+    truth = None if ground_truth is None else _ground_truth_points(ground_truth, shape)
+    index = _tensor_device(stacks, device)[1] if on_device else device
+    P, N_i, N_j = shape
+    extremes = np.full((3, 2), np.nan)
+    st, at, flight = float(speed_threshold), float(angle_threshold), int(frames_in_flight)
+    with _device_context(N_i, N_j, 1, index) as solver:
+        if any(e is None for e in edges):
+            found = solver.flow_extremes(stacks, P, st, at, reference_quirks, flight)
+            extremes = np.where(found[:, :1] <= found[:, 1:], found, np.nan)
+            for axis in range(2):
+                if edges[axis] is None:
+                    edges[axis] = _automatic_edges(bins[axis], *found[axis])
+            if edges[2] is None:
+                with np.errstate(invalid="ignore"):                       # no sample: arccos of an infinity is NaN
+                    edges[2] = _automatic_edges(bins[2], np.arccos(found[2, 1]), np.arccos(found[2, 0]))
+        joint, angles, counts = solver.flow_compare(stacks, P, st, at, reference_quirks, edges[0], edges[1], edges[2],
+                                                    angle_range is None, flight)
+    result = dict(joint_speed_histogram=joint, joint_speed_edges_a=edges[0], joint_speed_edges_b=edges[1], angle_histogram=angles,
+                  angle_edges=edges[2], nan_speed_counts=counts[:2].copy(), infinite_count=int(counts[2]), joint_count=int(counts[3]),
+                  angle_count=int(counts[4]), angle_dropped=int(counts[5]), speed_extremes=extremes[:2].copy(),
+                  cos_extremes=extremes[2].copy())
+    if truth is not None:
+        frame, start, end = truth
+        d = (end - start).astype(np.float64)
+        errors = np.empty((2, start.shape[0]), dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for r, fields in enumerate((a, b)):
+                v_x, v_y = _gather_points(fields[0], frame, start), _gather_points(fields[1], frame, start)
+                errors[r] = np.sqrt((d[:, 1] - v_y) ** 2 + (d[:, 0] - v_x) ** 2) / np.sqrt(d[:, 1] ** 2 + d[:, 0] ** 2)
+        result["relative_errors"] = errors
     return result
 
 

@@ -9,6 +9,7 @@ from opticalflow_amd.optical_flow import *  # noqa: F401,F403,E402
 from opticalflow_amd.optical_flow import (variational_optical_flow, conduct_optical_flow, conduct_optical_flow_jit, liu_shen_optical_flow_jit,
                                           conduct_variational_optical_flow_deprecated, vary_regularisation, vary_boxsize, vary_blursize, compare_channel_flows, make_fake_data_frame, blur_movie,  # noqa: F401,E402
                                           apply_adaptive_threshold, apply_clahe, downsample_movie,
+                                          compare_flow_results, filter_PIV_flow_result,
                                           format_elapsed_time, apply_constant_boundary_condition,
                                           subsample_velocities_for_visualisation, costum_imshow,
                                           make_velocity_overlay_movie, make_joint_overlay_movie)
