@@ -2571,16 +2571,17 @@ struct Scratch {
     bool out_of_memory() const { return bytes > c->scratch_bytes; }   // the buffer does not hold the planned layout
 };
 
-// ---- frame chunks: the walk of the frame-wise calls through the scratch arena -----------------------
+// ---- stack chunks: the walk of the frame-wise and pair-wise calls through the scratch arena --------
 constexpr int PRE_MAX_FLIGHT = 16;        // units in flight when the caller leaves the number to the library
 constexpr int PRE_MAX_WANT = 4096;        // ... and at most when it does not (grid z)
 
-// One call of the adaptive threshold, CLAHE, the resize, Farnebaeck's flow, the result filter or the comparison of two results
-// over a stack of `n` units (frames or pairs), on the stack of that call: the call declares its regions into the arena sc, plan() sizes the chunk and carves the
-// buffer, range() reduces a stack, run() walks the chunks.  What a staged input holds is recorded here alone: nothing staged
-// outlives the call.
+// One call of the adaptive threshold, CLAHE, the resize, Farnebaeck's flow, the result filter, the comparison of two results
+// or the Liu-Shen flow over a stack of `n` units (frames or pairs), on the stack of that call: the call declares
+// its regions into the arena sc, plan() sizes the chunk and carves the buffer, range() reduces a stack, run() walks the chunks.
+// An input holds one frame per unit, or - a pair stack - one more: pair k reads frames k and k + 1, so a chunk of nf pairs reads
+// nf + 1.  What a staged input holds is recorded here alone: nothing staged outlives the call.
 struct FrameChunks {
-    struct In { const double* stack; double* slot; int k0, nf; };  // _host: slot holds units [k0, k0 + nf) of stack (nf 0: nothing)
+    struct In { const double* stack; double* slot; int extra, k0, nf; };   // _host: slot holds frames [k0, k0 + nf + extra) of stack (nf 0: nothing)
     struct Out { char* caller; size_t bytes; char* slot; };        // bytes per unit
     vof_ctx* const c; const char* const what;                      // what: the call, for messages
     const int n, want; const bool host;                            // units; the caller's frames_in_flight
@@ -2604,8 +2605,10 @@ struct FrameChunks {
         return 0;
     }
 
-    void input(const double* stack) {                              // fs doubles per unit; _host: staged
-        if (host) sc.per_unit(&in[n_in].slot, fs);
+    void input(const double* stack, bool pairs = false) {          // fs doubles per frame; pairs: a pair stack; _host: staged
+        if (host && pairs) sc.per_unit_plus_one(&in[n_in].slot, fs);
+        else if (host) sc.per_unit(&in[n_in].slot, fs);
+        in[n_in].extra = pairs ? 1 : 0;
         in[n_in++].stack = stack;
     }
     void output(void* caller, size_t unit_bytes) {                 // _host: staged, then copied to `caller`
@@ -2628,7 +2631,7 @@ struct FrameChunks {
         In& i = in[s];
         *p = host ? i.slot : i.stack + (size_t)k0 * fs;
         if (!host || (i.nf == nf && i.k0 == k0)) return 0;
-        if (int rc = h2d_bounced(c, i.slot, i.stack + (size_t)k0 * fs, (size_t)nf * fs * sizeof(double))) return rc;
+        if (int rc = h2d_bounced(c, i.slot, i.stack + (size_t)k0 * fs, (size_t)(nf + i.extra) * fs * sizeof(double))) return rc;
         i.k0 = k0; i.nf = nf;
         return 0;
     }
@@ -3133,7 +3136,9 @@ int vof_solve_stack_dev(vof_ctx* c, const double* movie, int n_frames, const vof
 }
 
 // Device staging of the host API: frames of one batch (+1) and TWO sets of output buffers, so that the device-to-host
-// copies of batch k (copy stream) overlap the solve of batch k+1 (main stream).
+// copies of batch k (copy stream) overlap the solve of batch k+1 (main stream).  st_* serve vof_solve_stack_host,
+// vof_vary_regularisation_host, vof_debug_setup and - its chunks are the context's pairs - vof_box_flow_host; every other call
+// stages through its arena.
 static int ensure_staging(vof_ctx* c, bool double_buffer) {
     const size_t fs = frame_stride(c);
     if (!c->st_movie) {
@@ -4056,6 +4061,23 @@ int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_siz
     return 0;
 }
 
+// Frames k0 .. k0 + np of a pair chunk of sweep r on the device, *p: the caller's own (_dev), or `frames` - a per_unit_plus_one
+// region - where they are uploaded (_host) and, with device taps, blurred in place (tmp: blur_regions)
+static int pair_chunk_frames(vof_ctx* c, const SweepBase& r, int k0, int np, double* frames, const double* taps, int radius, double* tmp,
+                             const double** p) {
+    const size_t fs = frame_stride(c);
+    *p = r.movie + (size_t)k0 * fs;
+    if (r.host) {
+        if (int rc = h2d_bounced(c, frames, *p, (size_t)(np + 1) * fs * sizeof(double))) return rc;
+        *p = frames;
+    }
+    if (taps) {
+        if (int rc = blur_frames(c, *p, frames, np + 1, radius, tmp, taps)) return rc;
+        *p = frames;
+    }
+    return 0;
+}
+
 // ---- box-size sweep of the box flow (vary_boxsize; vof_boxsweep.hpp) ---------------------------------------------
 struct SweepReq : SweepBase {
     const int32_t* boxes; int n_boxes;
@@ -4070,7 +4092,7 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     for (int b = 0; b < r.n_boxes; ++b)
         if (r.boxes[b] < 1) { c->err = "every box size must be >= 1"; return -1; }
     if (r.blur_w && (r.blur_r < 0 || r.blur_r > 4096)) { c->err = "bad blur_radius"; return -1; }
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const size_t fs = frame_stride(c);
     const int P = r.n_frames - 1, NQ = r.remodel ? 8 : 5;
     // the arena: cap + 1 frames, and per pair 3 derived planes, R / C / W of every quantity and 4 chunk outputs
     Scratch sc(c);
@@ -4107,17 +4129,8 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     for (int k0 = 0; k0 < P; k0 += cap) {
         const int np = std::min(cap, P - k0);
         const dim3 g = grid2d(c->Ni, c->Nj, np);
-        const double* chunk_frames = r.movie + (size_t)k0 * fs;
-        if (r.host) {
-            if (int rc = h2d_bounced(c, frames, chunk_frames, (size_t)(np + 1) * fb)) return rc;
-            chunk_frames = frames;
-        }
-        if (r.blur_w) {
-            if (int rc = blur_frames(c, chunk_frames, frames, np + 1, r.blur_r, blur_tmp, blur_w)) return rc;
-            chunk_frames = frames;
-        }
+        if (int rc = pair_chunk_frames(c, r, k0, np, frames, blur_w, r.blur_r, blur_tmp, &a.movie)) return rc;
         c->cur_units = np;
-        a.movie = chunk_frames;
         { Prof prof(c, VOF_K_RHS, 0);
           k_bf_derived<<<g, blk2d, 0, c->stream>>>(a, der);
           if (r.remodel) k_bs_init<true><<<g, blk2d, 0, c->stream>>>(s);
@@ -4198,6 +4211,54 @@ static std::vector<double> linspace_edges(double lo, double hi, int bins) {
     return e;
 }
 
+// sum P per-pair partial histograms of `bins` bins, part[pair][bin], in pair order
+static void sum_pair_histograms(const double* part, int P, int bins, double* out) {
+    for (int b = 0; b < bins; ++b) {
+        double w = 0.0;
+        for (int k = 0; k < P; ++k) w += part[(size_t)k * bins + b];
+        out[b] = w;
+    }
+}
+
+// The flow-direction histogram per list entry of a sweep - the sigmas of the blur sweep, the two channels of the comparison -:
+// counts and speed-weighted sums over `bins` bins of [-1, 1] (0: none).  Its integer counters belong to the span behind the
+// tail's d_bad (SweepTail), so the sweep calls regions() before sweep_tail_regions and counters() after it.
+struct DirectionHist {
+    int bins, n, P, blk; size_t fs;       // blk: blocks per pair, by the plane size only
+    double *d_edges, *d_wsum, *d_part;    // the sums [entry][pair][bin]; the partials of one chunk
+    unsigned long long* d_hist;
+    void regions(Scratch& sc, int bins_, int n_, int P_) {
+        bins = bins_; n = n_; P = P_; fs = frame_stride(sc.c);
+        blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));
+        sc.once(&d_edges, bins ? (size_t)bins + 1 : 0);
+        sc.once(&d_wsum, (size_t)n * P * bins);
+        sc.per_unit(&d_part, (size_t)blk * bins);
+    }
+    void counters(Scratch& sc) { sc.once(&d_hist, (size_t)n * bins); }
+    int upload_edges(vof_ctx* c) const {                           // once the arena is planned
+        if (!bins) return 0;
+        const std::vector<double> e = linspace_edges(-1.0, 1.0, bins);
+        return h2d_bounced(c, d_edges, e.data(), e.size() * 8);
+    }
+    // pairs k0 .. k0 + np of entry e, enqueued behind the kernels that wrote the fields
+    void enqueue(vof_ctx* c, int e, int k0, int np, const double* vx, const double* vy, const double* speed) const {
+        if (!bins) return;
+        Prof prof(c, VOF_K_REDUCE, 0);
+        k_bz_angles<<<dim3(blk, np), 64, (size_t)bins * 64 * sizeof(double), c->stream>>>(vx, vy, speed, fs, d_edges, bins,
+                                                                                          d_hist + (size_t)e * bins, d_part);
+        const int nt = np * bins;
+        k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_part, blk, bins, np, d_wsum + ((size_t)e * P + k0) * bins);
+    }
+    // behind sweep_tail_finish: the counts from the tail's host copy, the weighted sums summed over the pairs in pair order
+    int finish(vof_ctx* c, const SweepTail& t, int64_t* hist, double* whist) const {
+        std::vector<double> wsum((size_t)n * P * bins);
+        if (bins) if (int rc = d2h_bounced(c, wsum.data(), d_wsum, wsum.size() * 8)) return rc;
+        for (size_t i = 0; i < (size_t)n * bins; ++i) hist[i] = (int64_t)t.host(d_hist)[i];
+        for (int e = 0; e < n; ++e) sum_pair_histograms(wsum.data() + (size_t)e * P * bins, P, bins, whist + (size_t)e * bins);
+        return 0;
+    }
+};
+
 static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     if (!c) return -1;
     if (int rc = sweep_check(c, r, r.stats)) return rc;
@@ -4214,26 +4275,24 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     std::vector<size_t> tap_at(n);
     size_t n_taps = 0;
     for (int s = 0; s < n; ++s) { tap_at[s] = n_taps; n_taps += 2 * (size_t)r.radii[s] + 1; }
-    const size_t n_ahist = (size_t)n * r.abins, n_ihist = r.iedges ? (size_t)n * r.ibins : 0, n_awsum = (size_t)n * P * r.abins;
-    const int ang_blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));   // by the plane size only
+    const size_t n_ihist = r.iedges ? (size_t)n * r.ibins : 0;
     // the arena: the blurred stack, the movie (_host) and four chunk outputs per pair in flight; what the sweep's own kernels
-    // read and write: taps, direction and intensity edges, direction sums and their partials; the tail's; the sweep's counters
+    // read and write: taps, intensity edges, the direction histogram's; the tail's; the sweep's counters
     Scratch sc(c);
-    double *blurred, *up = nullptr, *chunk_out[4], *blur_tmp, *bf_planes = nullptr, *d_taps, *d_aedges, *d_iedges, *d_awsum, *d_apart;
-    unsigned long long *d_ahist, *d_ihist, *d_ibad;
+    double *blurred, *up = nullptr, *chunk_out[4], *blur_tmp, *bf_planes = nullptr, *d_taps, *d_iedges;
+    unsigned long long *d_ihist, *d_ibad;
+    DirectionHist dir;
     sc.once(&blurred, (size_t)T * fs);
     if (r.host) sc.once(&up, (size_t)T * fs);
     for (double*& q : chunk_out) sc.per_unit(&q, fs);
     blur_regions(sc, T, &blur_tmp);
     box_flow_regions(sc, r.box_size, &bf_planes);
     sc.once(&d_taps, n_taps);
-    sc.once(&d_aedges, r.abins ? (size_t)r.abins + 1 : 0);
     sc.once(&d_iedges, r.iedges ? (size_t)r.ibins + 1 : 0);
-    sc.once(&d_awsum, n_awsum);
-    sc.per_unit(&d_apart, (size_t)ang_blk * r.abins);
+    dir.regions(sc, r.abins, n, P);
     SweepTail tail;
     sweep_tail_regions(sc, tail, r, "blur sweep", n);
-    sc.once(&d_ahist, n_ahist);
+    dir.counters(sc);
     sc.once(&d_ihist, n_ihist);
     sc.once(&d_ibad, 1);
     const int cap = sweep_tail_begin(sc, tail, "");
@@ -4242,10 +4301,7 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     const double* movie = r.host ? up : r.movie;
     if (int rc = h2d_bounced(c, d_taps, r.taps, n_taps * 8)) return rc;
     if (r.iedges) if (int rc = h2d_bounced(c, d_iedges, r.iedges, (size_t)(r.ibins + 1) * 8)) return rc;
-    if (r.abins) {
-        const std::vector<double> e = linspace_edges(-1.0, 1.0, r.abins);
-        if (int rc = h2d_bounced(c, d_aedges, e.data(), e.size() * 8)) return rc;
-    }
+    if (int rc = dir.upload_edges(c)) return rc;
 
     for (int s = 0; s < n; ++s) {
         if (int rc = blur_frames(c, movie, blurred, T, r.radii[s], blur_tmp, d_taps + tap_at[s])) return rc;
@@ -4262,31 +4318,15 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
             if (int rc = box_flow_pairs(c, bf_planes, blurred + (size_t)k0 * fs, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d.f[0], d.f[1],
                                         d.f[2], d.keep_g ? d.f[3] : nullptr)) return rc;
             sweep_tail_speed(c, tail, s, k0, np, d.f[2]);
-            if (r.abins) {
-                Prof prof(c, VOF_K_REDUCE, 0);
-                k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
-                    d.f[0], d.f[1], d.f[2], fs, d_aedges, r.abins, d_ahist + (size_t)s * r.abins, d_apart);
-                const int nt = np * r.abins;
-                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_apart, ang_blk, r.abins, np,
-                                                                        d_awsum + ((size_t)s * P + k0) * r.abins);
-            }
+            dir.enqueue(c, s, k0, np, d.f[0], d.f[1], d.f[2]);
             if (int rc = sweep_tail_moments(c, tail, s, k0, np, d.f[2], d.f[3])) return rc;
             if (int rc = sweep_copy_out(c, r, d, fs, np)) return rc;
         }
     }
     if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
-    std::vector<double> awsum(n_awsum);
-    if (n_awsum) if (int rc = d2h_bounced(c, awsum.data(), d_awsum, n_awsum * 8)) return rc;
-    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)tail.host(d_ahist)[t];
+    if (int rc = dir.finish(c, tail, r.ahist, r.awhist)) return rc;
     for (size_t t = 0; t < n_ihist; ++t) r.ihist[t] = (int64_t)tail.host(d_ihist)[t];
-    for (int s = 0; s < n; ++s) {
-        for (int b = 0; b < r.abins; ++b) {                  // the pairs' sums in pair order
-            double w = 0.0;
-            for (int k = 0; k < P; ++k) w += awsum[((size_t)s * P + k) * r.abins + b];
-            r.awhist[(size_t)s * r.abins + b] = w;
-        }
-        r.stats[s].sigma_index = s;
-    }
+    for (int s = 0; s < n; ++s) r.stats[s].sigma_index = s;
     return 0;
 }
 
@@ -4350,33 +4390,30 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
             if (!(r.jedges[ch][r.jbins[ch]] > r.jedges[ch][0])) { c->err = "joint_speed_edges must increase"; return -1; }
         }
     }
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
+    const size_t fs = frame_stride(c);
     const int P = r.n_frames - 1;
     const int ba = joint ? r.jbins[0] : 0, bb = joint ? r.jbins[1] : 0;
     const size_t n_taps[2] = {r.taps[0] ? 2 * (size_t)r.radius[0] + 1 : 0, r.taps[1] ? 2 * (size_t)r.radius[1] + 1 : 0};
-    const size_t n_ahist = 2 * (size_t)r.abins, n_awsum = 2 * (size_t)P * r.abins, n_twsum = (size_t)P * r.tbins, n_jhist = (size_t)ba * bb;
-    const int ang_blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));   // as the blur sweep
+    const size_t n_twsum = (size_t)P * r.tbins, n_jhist = (size_t)ba * bb;
     const int cp_blk = cp_blocks(fs);
     // the arena: cap + 1 frames of the channel in progress and four chunk outputs per channel and pair in flight; what the
     // comparison's own kernels read and write; the tail's; the comparison's counters
     Scratch sc(c);
-    double *frames, *chunk_out[2][4], *blur_tmp = nullptr, *bf_planes = nullptr, *d_taps[2], *d_aedges, *d_tedges, *d_jedges[2], *d_awsum, *d_apart,
-           *d_twsum, *d_tpart;
-    unsigned long long *d_ahist, *d_thist, *d_jhist, *d_jc;
+    double *frames, *chunk_out[2][4], *blur_tmp = nullptr, *bf_planes = nullptr, *d_taps[2], *d_tedges, *d_jedges[2], *d_twsum, *d_tpart;
+    unsigned long long *d_thist, *d_jhist, *d_jc;
+    DirectionHist dir;
     sc.per_unit_plus_one(&frames, fs);
     for (auto& ch : chunk_out) for (double*& q : ch) sc.per_unit(&q, fs);
     if (r.taps[0] || r.taps[1]) blur_regions(sc, sweep_want(c, r) + 1, &blur_tmp);
     box_flow_regions(sc, r.box_size, &bf_planes);
     for (int ch = 0; ch < 2; ++ch) { sc.once(&d_taps[ch], n_taps[ch]); sc.once(&d_jedges[ch], joint ? (size_t)r.jbins[ch] + 1 : 0); }
-    sc.once(&d_aedges, r.abins ? (size_t)r.abins + 1 : 0);
+    dir.regions(sc, r.abins, 2, P);
     sc.once(&d_tedges, (size_t)r.tbins + 1);
-    sc.once(&d_awsum, n_awsum);
-    sc.per_unit(&d_apart, (size_t)ang_blk * r.abins);
     sc.once(&d_twsum, n_twsum);
     sc.per_unit(&d_tpart, (size_t)cp_blk * r.tbins);
     SweepTail tail;
     sweep_tail_regions(sc, tail, r, "channel comparison", 2);
-    sc.once(&d_ahist, n_ahist);
+    dir.counters(sc);
     sc.once(&d_thist, (size_t)r.tbins);
     sc.once(&d_jhist, n_jhist);
     sc.once(&d_jc, 2);
@@ -4386,10 +4423,7 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
         if (r.taps[ch]) if (int rc = h2d_bounced(c, d_taps[ch], r.taps[ch], n_taps[ch] * 8)) return rc;
         if (joint) if (int rc = h2d_bounced(c, d_jedges[ch], r.jedges[ch], ((size_t)r.jbins[ch] + 1) * 8)) return rc;
     }
-    if (r.abins) {
-        const std::vector<double> e = linspace_edges(-1.0, 1.0, r.abins);
-        if (int rc = h2d_bounced(c, d_aedges, e.data(), e.size() * 8)) return rc;
-    }
+    if (int rc = dir.upload_edges(c)) return rc;
     {
         const std::vector<double> e = linspace_edges(0.0, 1.0, r.tbins);
         if (int rc = h2d_bounced(c, d_tedges, e.data(), e.size() * 8)) return rc;
@@ -4402,28 +4436,14 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
         const int np = std::min(cap, P - k0);
         SweepDst d[2];
         for (int ch = 0; ch < 2; ++ch) {
-            const double* src = chan[ch].movie + (size_t)k0 * fs;
-            if (r.host) {
-                if (int rc = h2d_bounced(c, frames, src, (size_t)(np + 1) * fb)) return rc;
-                src = frames;
-            }
-            if (r.taps[ch]) {
-                if (int rc = blur_frames(c, src, frames, np + 1, r.radius[ch], blur_tmp, d_taps[ch])) return rc;
-                src = frames;
-            }
+            const double* src;
+            if (int rc = pair_chunk_frames(c, chan[ch], k0, np, frames, r.taps[ch] ? d_taps[ch] : nullptr, r.radius[ch], blur_tmp, &src)) return rc;
             d[ch] = sweep_dst(chan[ch], chunk_out[ch], fs, 0, k0);
             // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
             if (int rc = box_flow_pairs(c, bf_planes, src, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d[ch].f[0], d[ch].f[1],
                                         d[ch].f[2], d[ch].keep_g ? d[ch].f[3] : nullptr)) return rc;
             sweep_tail_speed(c, tail, ch, k0, np, d[ch].f[2]);
-            if (r.abins) {
-                Prof prof(c, VOF_K_REDUCE, 0);
-                k_bz_angles<<<dim3(ang_blk, np), 64, (size_t)r.abins * 64 * sizeof(double), c->stream>>>(
-                    d[ch].f[0], d[ch].f[1], d[ch].f[2], fs, d_aedges, r.abins, d_ahist + (size_t)ch * r.abins, d_apart);
-                const int nt = np * r.abins;
-                k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_apart, ang_blk, r.abins, np,
-                                                                        d_awsum + ((size_t)ch * P + k0) * r.abins);
-            }
+            dir.enqueue(c, ch, k0, np, d[ch].f[0], d[ch].f[1], d[ch].f[2]);
             if (int rc = sweep_tail_moments(c, tail, ch, k0, np, d[ch].f[2], d[ch].f[3])) return rc;
         }
         {
@@ -4448,26 +4468,14 @@ static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
             if (int rc = sweep_copy_out(c, chan[ch], d[ch], fs, np)) return rc;
     }
     if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
-    std::vector<double> sums(n_awsum + n_twsum);
-    if (n_awsum) if (int rc = d2h_bounced(c, sums.data(), d_awsum, n_awsum * 8)) return rc;
-    if (int rc = d2h_bounced(c, sums.data() + n_awsum, d_twsum, n_twsum * 8)) return rc;
-    for (size_t t = 0; t < n_ahist; ++t) r.ahist[t] = (int64_t)tail.host(d_ahist)[t];
+    if (int rc = dir.finish(c, tail, r.ahist, r.awhist)) return rc;
+    std::vector<double> twsum(n_twsum);
+    if (int rc = d2h_bounced(c, twsum.data(), d_twsum, n_twsum * 8)) return rc;
     for (int b = 0; b < r.tbins; ++b) r.thist[b] = (int64_t)tail.host(d_thist)[b];
     for (size_t t = 0; t < n_jhist; ++t) r.jhist[t] = (int64_t)tail.host(d_jhist)[t];
     r.jcounts[0] = (int64_t)tail.host(d_jc)[0]; r.jcounts[1] = (int64_t)tail.host(d_jc)[1];
-    for (int ch = 0; ch < 2; ++ch) {
-        for (int b = 0; b < r.abins; ++b) {                  // the pairs' sums in pair order
-            double w = 0.0;
-            for (int k = 0; k < P; ++k) w += sums[((size_t)ch * P + k) * r.abins + b];
-            r.awhist[(size_t)ch * r.abins + b] = w;
-        }
-        r.stats[ch].channel = ch;
-    }
-    for (int b = 0; b < r.tbins; ++b) {
-        double w = 0.0;
-        for (int k = 0; k < P; ++k) w += sums[n_awsum + (size_t)k * r.tbins + b];
-        r.twhist[b] = w;
-    }
+    sum_pair_histograms(twsum.data(), P, r.tbins, r.twhist);
+    for (int ch = 0; ch < 2; ++ch) r.stats[ch].channel = ch;
     return 0;
 }
 
@@ -5027,7 +5035,7 @@ int vof_flow_compare_dev(VOF_FLOW_COMPARE_ARGS) { return flow_compare_impl(c, VO
 int vof_flow_compare_host(VOF_FLOW_COMPARE_ARGS) { return flow_compare_impl(c, VOF_FLOW_COMPARE_REQ(true)); }
 
 // ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------
-constexpr int LS_CHUNK = 16384;           // pairs per launch (grid z)
+constexpr int LS_HOST_CHUNK = 8;          // pairs per chunk of vof_liu_shen_host
 
 static int liu_shen_check(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, const double* ix, const double* iy,
                           const double* ir, int initial_kind, int max_iterations, const double* v_x, const double* v_y,
@@ -5051,9 +5059,9 @@ static int liu_shen_depth(vof_ctx* c, int* depth) {
     return 0;
 }
 
-// P pairs of a device-resident movie into device-resident outputs, enqueued on the context's stream.  The iterates
-// ping-pong between (v_x, v_y) and (speed, remodelling); ix / iy / ir are device arrays of initial_kind 1 / 2 (ix, iy may be
-// any of the four outputs), sx / sy / sr the scalars of kind 0.  write_remodelling false leaves remodelling as scratch.
+// P pairs (at most 4096: a chunk of the walk) of a device-resident movie into device-resident outputs, enqueued on the context's
+// stream.  The iterates ping-pong between (v_x, v_y) and (speed, remodelling); ix / iy / ir are device arrays of initial_kind 1 / 2
+// (ix, iy may be any of the four outputs), sx / sy / sr the scalars of kind 0.  write_remodelling false leaves remodelling as scratch.
 static int liu_shen_pairs(vof_ctx* c, const double* movie, int P, double delta_x, double delta_t, double alpha, const double* ix,
                           const double* iy, const double* ir, double sx, double sy, double sr, int kind, int iterations, int depth,
                           double* v_x, double* v_y, double* speed, double* remodelling, bool write_remodelling) {
@@ -5062,96 +5070,86 @@ static int liu_shen_pairs(vof_ctx* c, const double* movie, int P, double delta_x
         HIPCHK(hipFuncSetAttribute((const void*)k_ls_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls_fused_lds(LS_KMAX)));
         c->ls_lds_set = true;
     }
-    for (int k0 = 0; k0 < P; k0 += LS_CHUNK) {
-        const int np = std::min(LS_CHUNK, P - k0);
-        const size_t off = (size_t)k0 * fs, n = (size_t)np * fs;
-        const unsigned nb = (unsigned)((n + 255) / 256);
-        double* buf[2][2] = {{v_x + off, v_y + off}, {speed + off, remodelling + off}};
-        const size_t ioff = kind == 2 ? off : 0;
-        c->cur_units = np;
-        Prof prof(c, VOF_K_RHS, 0);
-        k_ls_init<<<nb, 256, 0, c->stream>>>(buf[0][0], buf[0][1], kind ? ix + ioff : nullptr, kind ? iy + ioff : nullptr, sx, sy, kind,
-                                             fs, n, delta_t, delta_x);
-        LsArgs a{};
-        a.movie = movie + off; a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj; a.alpha = alpha;
-        int cur = 0;
-        for (int done = 0; done < iterations;) {
-            const int k = std::min(depth, iterations - done);
-            a.k = k;
-            a.sx = buf[cur][0]; a.sy = buf[cur][1]; a.dx = buf[cur ^ 1][0]; a.dy = buf[cur ^ 1][1];
-            if (depth == 1) {
-                k_ls_step<<<grid2d(c->Ni, c->Nj, np), blk2d, 0, c->stream>>>(a);
-            } else {
-                const dim3 g((c->Nj + LS_TJ - 1) / LS_TJ, (c->Ni + LS_TI - 1) / LS_TI, np);
-                k_ls_fused<<<g, LS_THREADS, ls_fused_lds(k), c->stream>>>(a);
-            }
-            done += k;
-            cur ^= 1;
+    const size_t n = (size_t)P * fs;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    double* buf[2][2] = {{v_x, v_y}, {speed, remodelling}};
+    c->cur_units = P;
+    Prof prof(c, VOF_K_RHS, 0);
+    k_ls_init<<<nb, 256, 0, c->stream>>>(buf[0][0], buf[0][1], kind ? ix : nullptr, kind ? iy : nullptr, sx, sy, kind, fs, n, delta_t, delta_x);
+    LsArgs a{};
+    a.movie = movie; a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj; a.alpha = alpha;
+    int cur = 0;
+    for (int done = 0; done < iterations;) {
+        const int k = std::min(depth, iterations - done);
+        a.k = k;
+        a.sx = buf[cur][0]; a.sy = buf[cur][1]; a.dx = buf[cur ^ 1][0]; a.dy = buf[cur ^ 1][1];
+        if (depth == 1) {
+            k_ls_step<<<grid2d(c->Ni, c->Nj, P), blk2d, 0, c->stream>>>(a);
+        } else {
+            const dim3 g((c->Nj + LS_TJ - 1) / LS_TJ, (c->Ni + LS_TI - 1) / LS_TI, P);
+            k_ls_fused<<<g, LS_THREADS, ls_fused_lds(k), c->stream>>>(a);
         }
-        k_ls_finish<<<nb, 256, 0, c->stream>>>(buf[cur][0], buf[cur][1], buf[0][0], buf[0][1], buf[1][0],
-                                               write_remodelling ? buf[1][1] : nullptr, kind ? ir + ioff : nullptr, sr, kind, fs, n,
-                                               delta_x / delta_t);
+        done += k;
+        cur ^= 1;
     }
+    k_ls_finish<<<nb, 256, 0, c->stream>>>(buf[cur][0], buf[cur][1], buf[0][0], buf[0][1], buf[1][0], write_remodelling ? buf[1][1] : nullptr,
+                                           kind ? ir : nullptr, sr, kind, fs, n, delta_x / delta_t);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-int vof_liu_shen_dev(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
-                     const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
-                     int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling) {
+// The pairs in chunks: all of them for device-resident arrays, LS_HOST_CHUNK staged at a time for host arrays.  _host keeps the
+// fourth iterate buffer in the arena and never uploads initial_remodelling: remodelling is filled on the host.
+static int liu_shen_impl(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
+                         const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
+                         int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling, bool host) {
     if (!c) return -1;
     if (int rc = liu_shen_check(c, movie, n_frames, delta_x, delta_t, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
                                 max_iterations, v_x, v_y, speed, remodelling)) return rc;
-    if (initial_kind && (initial_remodelling == remodelling || initial_remodelling == speed || initial_remodelling == v_x ||
-                         initial_remodelling == v_y)) { c->err = "initial_remodelling must not be an output array"; return -1; }
+    if (!host && initial_kind && (initial_remodelling == remodelling || initial_remodelling == speed || initial_remodelling == v_x ||
+                                  initial_remodelling == v_y)) { c->err = "initial_remodelling must not be an output array"; return -1; }
     int depth;
     if (int rc = liu_shen_depth(c, &depth)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const bool s = initial_kind == 0;
-    if (int rc = liu_shen_pairs(c, movie, n_frames - 1, delta_x, delta_t, alpha, initial_v_x, initial_v_y, initial_remodelling,
-                                s ? *initial_v_x : 0.0, s ? *initial_v_y : 0.0, s ? *initial_remodelling : 0.0, initial_kind,
-                                max_iterations, depth, v_x, v_y, speed, remodelling, true)) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int vof_liu_shen_host(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
-                      const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
-                      int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling) {
-    if (!c) return -1;
-    if (int rc = liu_shen_check(c, movie, n_frames, delta_x, delta_t, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
-                                max_iterations, v_x, v_y, speed, remodelling)) return rc;
-    int depth;
-    if (int rc = liu_shen_depth(c, &depth)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    if (int rc = ensure_staging(c, false)) return rc;
     const size_t fs = frame_stride(c), fb = fs * sizeof(double);
     const int P = n_frames - 1;
     const bool s = initial_kind == 0;
-    double* outs[3] = {v_x, v_y, speed};
-    for (int k0 = 0; k0 < P; k0 += c->B) {
-        const int np = std::min(c->B, P - k0);
-        if (int rc = h2d_bounced(c, c->st_movie, movie + (size_t)k0 * fs, (size_t)(np + 1) * fb)) return rc;
-        // the initial fields travel through the second pair of iterate buffers, which the first iteration overwrites
-        if (initial_kind) {
-            const size_t io = initial_kind == 2 ? (size_t)k0 * fs : 0, ib = (initial_kind == 2 ? (size_t)np : 1) * fb;
-            if (int rc = h2d_bounced(c, c->st_out[2], initial_v_x + io, ib)) return rc;
-            if (int rc = h2d_bounced(c, c->st_out[3], initial_v_y + io, ib)) return rc;
-        }
-        if (int rc = liu_shen_pairs(c, c->st_movie, np, delta_x, delta_t, alpha, c->st_out[2], c->st_out[3], nullptr,
-                                    s ? *initial_v_x : 0.0, s ? *initial_v_y : 0.0, 0.0, initial_kind, max_iterations, depth,
-                                    c->st_out[0], c->st_out[1], c->st_out[2], c->st_out[3], false)) return rc;
-        for (int f = 0; f < 3; ++f)
-            if (int rc = d2h_bounced(c, outs[f] + (size_t)k0 * fs, c->st_out[f], (size_t)np * fb)) return rc;
-    }
+    FrameChunks fc(c, "Liu-Shen flow", P, host ? LS_HOST_CHUNK : P, host);
+    double *fourth = nullptr, *plane_x = nullptr, *plane_y = nullptr;          // _host: the fourth iterate buffer, the planes of kind 1
+    fc.input(movie, true);
+    if (initial_kind == 2) { fc.input(initial_v_x); fc.input(initial_v_y); if (!host) fc.input(initial_remodelling); }
+    if (initial_kind == 1 && host) { fc.sc.once(&plane_x, fs); fc.sc.once(&plane_y, fs); }
+    if (host) fc.sc.per_unit(&fourth, fs);
+    for (double* o : {v_x, v_y, speed}) fc.output(o, fb);
+    if (int rc = fc.plan()) return rc;
+    if (plane_x) if (int rc = h2d_bounced(c, plane_x, initial_v_x, fb)) return rc;
+    if (plane_y) if (int rc = h2d_bounced(c, plane_y, initial_v_y, fb)) return rc;
+    if (int rc = fc.run([&](int k0, int np, const double* const* in, void* const* out) -> int {
+            const bool stack = initial_kind == 2;
+            return liu_shen_pairs(c, in[0], np, delta_x, delta_t, alpha, stack ? in[1] : host ? plane_x : initial_v_x,
+                                  stack ? in[2] : host ? plane_y : initial_v_y, stack ? in[3] : host ? nullptr : initial_remodelling,
+                                  s ? *initial_v_x : 0.0, s ? *initial_v_y : 0.0, s && !host ? *initial_remodelling : 0.0, initial_kind,
+                                  max_iterations, depth, (double*)out[0], (double*)out[1], (double*)out[2],
+                                  host ? fourth : remodelling + (size_t)k0 * fs, !host);
+        })) return rc;
     // OF.py:507, 668: the initial remodelling comes back untouched
-    for (int k = 0; k < P; ++k) {
+    for (int k = 0; host && k < P; ++k) {
         double* r = remodelling + (size_t)k * fs;
+        const double* ir = initial_remodelling + (initial_kind == 2 ? (size_t)k * fs : 0);
         if (initial_kind == 0) std::fill(r, r + fs, *initial_remodelling);
-        else if (initial_remodelling + (initial_kind == 2 ? (size_t)k * fs : 0) != r)
-            memcpy(r, initial_remodelling + (initial_kind == 2 ? (size_t)k * fs : 0), fb);
+        else if (ir != r) memcpy(r, ir, fb);
     }
     return 0;
 }
+
+#define VOF_LIU_SHEN_ARGS                                                                                                             \
+    vof_ctx *c, const double *movie, int n_frames, double delta_x, double delta_t, double alpha, const double *initial_v_x,           \
+        const double *initial_v_y, const double *initial_remodelling, int initial_kind, int max_iterations, double *v_x, double *v_y, \
+        double *speed, double *remodelling
+#define VOF_LIU_SHEN_CALL(host)                                                                                                       \
+    liu_shen_impl(c, movie, n_frames, delta_x, delta_t, alpha, initial_v_x, initial_v_y, initial_remodelling, initial_kind,           \
+                  max_iterations, v_x, v_y, speed, remodelling, host)
+
+int vof_liu_shen_dev(VOF_LIU_SHEN_ARGS) { return VOF_LIU_SHEN_CALL(false); }
+int vof_liu_shen_host(VOF_LIU_SHEN_ARGS) { return VOF_LIU_SHEN_CALL(true); }
 
 }  // extern "C"

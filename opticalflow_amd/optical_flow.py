@@ -841,7 +841,8 @@ def _variational_optical_flow_device(movie, smoothing_sigma, device, max_pairs_i
 # Box least-squares flow (Vig et al. 2016): the reference's other estimator, OF.py:24-218.
 # ---------------------------------------------------------------------------------------------------------
 def _box_flow_context(n_i, n_j, n_pairs, device):
-    # the host entry point stages one batch of the context's pairs at a time; the kernels need no per-pair workspace
+    # for the box flow, the sweeps and compare_channel_flows: on host arrays they stage at most the context's pairs at a time
+    # (at most 8 here); the kernels need no per-pair workspace.  The Liu-Shen flow chunks on its own and asks for one pair.
     return _device_context(n_i, n_j, max(1, min(int(n_pairs), 8)), device)
 
 
@@ -1585,7 +1586,7 @@ def liu_shen_optical_flow_jit(movie, delta_x=1.0, delta_t=1.0, alpha=100, remode
     initial = (initial_v_x, initial_v_y, initial_remodelling)
     if output == "numpy":
         frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
-        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
+        with _device_context(N_i, N_j, 1, device) as solver:
             out = solver.liu_shen_host(frames, delta_x, delta_t, alpha, *initial, int(max_iterations))
         return out + (int(max_iterations) - 1,)
     import torch

@@ -125,26 +125,41 @@ def test_invalid_fusion_depth_is_an_error(monkeypatch):
             of.liu_shen_optical_flow_jit(texture(16, 16), max_iterations=2)
 
 
-@pytest.mark.parametrize("kind", ["scalar", "plane", "stack"])
-def test_torch_output_is_bit_equal_to_the_host_path(kind):
+def torch_output_against_the_host_path(kind, n_i, n_j, frames, iterations):
     import torch
     from opticalflow_amd import optical_flow as of
-    movie = texture(70, 90, frames=4, seed=2)
+    movie = texture(n_i, n_j, frames=frames, seed=2)
     rng = np.random.default_rng(8)
-    shape = {"scalar": (), "plane": (70, 90), "stack": (3, 70, 90)}[kind]
+    pairs = (frames - 1, n_i, n_j)
+    shape = {"scalar": (), "plane": pairs[1:], "stack": pairs}[kind]
     init = [0.2 * rng.standard_normal(shape) for _ in range(3)]
     if kind == "scalar":
         init = [float(f) for f in init]
-    host = of.liu_shen_optical_flow_jit(movie, 0.3, 0.7, 0.2, 1.0, *init, 11)
+    host = of.liu_shen_optical_flow_jit(movie, 0.3, 0.7, 0.2, 1.0, *init, iterations)
     dev_init = init if kind == "scalar" else [torch.as_tensor(f).cuda() for f in init]
-    dev = of.liu_shen_optical_flow_jit(torch.as_tensor(movie).cuda(), 0.3, 0.7, 0.2, 1.0, *dev_init, 11, output="torch")
-    assert host[4] == dev[4] == 10
+    dev = of.liu_shen_optical_flow_jit(torch.as_tensor(movie).cuda(), 0.3, 0.7, 0.2, 1.0, *dev_init, iterations, output="torch")
+    assert host[4] == dev[4] == iterations - 1
+    assert np.isfinite(host[0]).all() and host[0].any()
     for f in range(4):
         assert np.array_equal(host[f], dev[f].cpu().numpy()), (kind, f)
-    assert np.array_equal(host[3], np.broadcast_to(init[2], (3, 70, 90)))
+    assert np.array_equal(host[3], np.broadcast_to(init[2], pairs))
     # mixed forms are passed in the widest one
-    mixed = of.liu_shen_optical_flow_jit(movie, 0.3, 0.7, 0.2, 1.0, init[0], init[1], 0.25, 11)
+    mixed = of.liu_shen_optical_flow_jit(movie, 0.3, 0.7, 0.2, 1.0, init[0], init[1], 0.25, iterations)
     assert np.array_equal(mixed[0], host[0]) and np.all(mixed[3] == 0.25)
+
+
+@pytest.mark.parametrize("kind", ["scalar", "plane", "stack"])
+def test_torch_output_is_bit_equal_to_the_host_path(kind):
+    torch_output_against_the_host_path(kind, 70, 90, 4, 11)
+
+
+@pytest.mark.parametrize("depth", [None, 1])
+@pytest.mark.parametrize("kind", ["scalar", "plane", "stack"])
+def test_torch_output_is_bit_equal_to_the_host_path_of_two_chunks(kind, depth, monkeypatch):
+    """11 frames of 12 x 20: host arrays go through the library as chunks of 8 and 2 pairs, with the initial stacks offset
+    by the chunk, the device tensors as one chunk of 10."""
+    set_depth(monkeypatch, depth)
+    torch_output_against_the_host_path(kind, 12, 20, 11, 7)
 
 
 @pytest.mark.parametrize("output", ["numpy", "torch"])

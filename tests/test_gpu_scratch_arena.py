@@ -1,6 +1,6 @@
-"""GPU tests of the call-scoped scratch arena: the blur, the box flow's general path, the sweeps, the
-channel comparison and the frame-wise calls carve one buffer of the context anew in every call.  What a call computes inside a
-buffer that another owner filled is compared bit for bit with the same call on a fresh context."""
+"""GPU tests of the call-scoped scratch arena: the blur, the box flow's general path, the Liu-Shen flow, the sweeps,
+the channel comparison and the frame-wise calls carve one buffer of the context anew in every call.  What a call computes inside
+a buffer that another owner filled is compared bit for bit with the same call on a fresh context."""
 import functools
 
 import numpy as np
@@ -52,6 +52,8 @@ def calls():
     assert taps(0.8).size == 7 and taps(1.6).size == 13                      # two radii
     boxsize = lambda s: summaries_and_fields(s.vary_boxsize_host(                                                  # noqa: E731
         a, (3, 8, 21), include_remodelling=True, weights=taps(1.0), histogram_edges=SPEED_EDGES, probe_locations=PROBES, return_fields=True))
+    rng = np.random.default_rng(6)
+    initial = [0.2 * rng.standard_normal((a.shape[0] - 1,) + SHAPE) for _ in range(3)]
     return [
         ("blur of one frame", lambda s: (s.blur_host(a[:1], taps(1.0)), None)),
         ("blur sweep", lambda s: summaries_and_fields(s.vary_blursize_host(
@@ -59,10 +61,12 @@ def calls():
             probe_locations=PROBES, return_fields=True))),
         ("box flow, general path, box wider than the image", lambda s: box_flow_dev(s, a, 33)),
         ("box-size sweep", boxsize),
+        ("box flow on host arrays, box 33", lambda s: (None, s.box_flow_host(a, 33))),
         ("threshold", lambda s: (s.adaptive_threshold_host(a, 11, 2.5, frames_in_flight=2), None)),
         ("comparison", lambda s: summaries_and_fields(s.compare_flows_host(
             a, b, 7, weights_a=taps(0.8), weights_b=taps(1.6), histogram_edges=SPEED_EDGES, angle_bins=8, relative_angle_bins=10,
             joint_speed_edges=(np.linspace(0.0, 4.0, 6), np.linspace(0.0, 4.0, 5)), return_fields=True))),
+        ("Liu-Shen on host arrays, stack initial fields", lambda s: (None, s.liu_shen_host(a, 0.5, 2.0, 10.0, *initial, 5))),
         ("blur of six frames", lambda s: (s.blur_host(a, taps(1.6)), None)),
         ("box-size sweep again", boxsize),
     ]
@@ -115,7 +119,12 @@ def test_every_owner_in_turn_on_one_context():
             assert_same(got, call(fresh), name)
     fields = arrays(plain_sequence()[3][1])
     assert len(fields) == 4 and all(f.shape == (3, 5) + SHAPE for f in fields)                     # the sweep did return its fields
-    assert plain_sequence()[4][0].any() and not plain_sequence()[4][0].all()                       # the mask is no constant
+    assert calls()[5][0] == "threshold"
+    assert plain_sequence()[5][0].any() and not plain_sequence()[5][0].all()                       # the mask is no constant
+    for at, name in ((4, "box flow on host arrays, box 33"), (7, "Liu-Shen on host arrays, stack initial fields")):
+        assert calls()[at][0] == name
+        v_x = plain_sequence()[at][1][0]
+        assert np.isfinite(v_x).any() and np.unique(v_x[np.isfinite(v_x)]).size > 1, name            # the flow is no constant
 
 
 def test_the_sequence_under_guard_regions_and_poison(monkeypatch):
@@ -157,3 +166,38 @@ def test_the_context_holds_one_buffer_not_a_sum():
         assert s.workspace_bytes - before == max(growth.values())
         A(s)
         assert s.workspace_bytes - before == max(growth.values())
+
+
+def texture11():
+    from oracle import vof_oracle as orc
+    return np.ascontiguousarray(orc.make_texture_stack(20, 11, seed=4)[:, :16, :20])
+
+
+def test_pair_chunks_do_not_depend_on_the_context():
+    """The Liu-Shen flow on host arrays stages its own chunks of 8 pairs (here 8 + 2) in the arena, whatever the solver's batch
+    capacity: contexts of 1 and of 8 pairs give the same bytes and grow by the same number of bytes.  (The box flow on host
+    arrays still chunks by the context's pairs: profiles/pair_chunks_summary.md.)"""
+    from opticalflow_amd import _native
+    movie = texture11()
+    rng = np.random.default_rng(12)
+    initial = [0.2 * rng.standard_normal((10, 16, 20)) for _ in range(3)]
+    results, growth = {}, {}
+    for slots in (1, 8):
+        with _native.Solver(16, 20, slots) as s:
+            before = s.workspace_bytes
+            fields = list(s.liu_shen_host(movie, 0.3, 0.7, 0.2, *initial, 7))
+            results[slots], growth[slots] = fields, s.workspace_bytes - before
+    assert len(results[1]) == len(results[8]) == 4
+    for i, (one, eight) in enumerate(zip(results[1], results[8])):
+        assert one.shape == (10, 16, 20) and one.tobytes() == eight.tobytes(), i
+    assert all(np.isfinite(pair).all() and pair.any() for pair in results[1][0])                  # every pair holds a flow
+    print("growth of workspace_bytes:", growth)
+    assert growth[1] == growth[8] > 0
+
+
+def test_the_liu_shen_flow_on_host_arrays_asks_for_a_context_of_one_pair():
+    from opticalflow_amd import optical_flow as of
+    of.release_device_memory()
+    out = of.liu_shen_optical_flow_jit(texture11()[:10], 1.0, 1.0, 0.5, 1.0, 0.1, 0.1, 0.0, 3)
+    assert out[0].shape == (9, 16, 20)
+    assert of._cache["solver"].max_pairs == 1
