@@ -75,7 +75,10 @@ __global__ __launch_bounds__(NT) void k_blur1d_tiled(const double* __restrict__ 
 //     of block q adds the samples q * 64 + l, + gridDim.x * 64, ... of its pair in that order into a column of its own,
 //     lw[b][l]; the 64 columns are then added by wave_sum's fixed tree.  gridDim.x depends on the plane size only, and
 //     k_bz_angle_sum adds the blocks of a pair in block order, so a pair's sums do not depend on the launch that held it.
-// No floating-point atomics.  Dynamic LDS: bins * 64 doubles, <= 64 KiB for bins <= BZ_MAX_ANGLE_BINS.
+// No floating-point atomics.  Dynamic LDS: bins * 64 doubles, exactly 64 KiB at bins = BZ_MAX_ANGLE_BINS, next to the 512 B of
+// static counters (lc): 66 048 B per workgroup, more than 64 KiB in all.  Observed on gfx950: the launch is accepted as it is, with
+// no hipFuncSetAttribute for this kernel (the dynamic part alone does not exceed 64 KiB, and a CU has 160 KiB), and the counts and
+// sums of 128 bins are those of numpy (tests/test_gpu_summary_launch_shapes.py).  A larger BZ_MAX_ANGLE_BINS needs the attribute.
 constexpr int BZ_MAX_ANGLE_BINS = 128;
 constexpr int BZ_ANGLE_PER_LANE = 32;    // samples a lane adds at least before a plane gets another block ...
 constexpr int BZ_ANGLE_MAX_BLOCKS = 256; // ... up to this many blocks per pair

@@ -13,7 +13,10 @@ Every comparison prints its figure before it asserts.
 
 Inputs: (A) a 40 x 52 cut of the benchmark texture, N_j > N_i, so the column-clamp quirk leaves empty windows (NaN speeds and
 NaN means); (B) 52 x 40 random 8-bit frames, every speed finite and every direction bin occupied.  Radius 60 (sigma 15) on a
-40-pixel side is among the sigmas of (A)."""
+40-pixel side is among the sigmas of (A).
+Planes of 2080 samples are one-block launches of k_bz_angles (and at most three blocks of k_bs_moments): several blocks per pair,
+the block caps, 128 direction bins, histograms past the LDS counters and more pairs than a launch holds are in
+tests/test_gpu_summary_launch_shapes.py."""
 
 import numpy as np
 import pytest

@@ -17,7 +17,9 @@ which do not all hold the same number of samples, and N_j != N_i.  Inputs:
 (A) 40 x 52 cuts of the benchmark texture, seeds 0 and 1: N_j > N_i, so the column-clamp quirk leaves NaN speeds;
 (B) 52 x 40 random 8-bit frames of default_rng(44) and default_rng(45): every theta bin occupied at boxes 7 and 15;
 (C) the first movie of (B) as both channels: cos is 1 up to rounding, the excess over 1 is what the quirk drops;
-(D) the first two frames of (B)'s first movie against the same two in reverse order: v_b = -v_a exactly on integer frames."""
+(D) the first two frames of (B)'s first movie against the same two in reverse order: v_b = -v_a exactly on integer frames.
+With two blocks of k_cp_joint and one of k_bz_angles per pair these are the smallest launches: 21 and 255 blocks, the cap of 256,
+64 angle bins, 64 x 64 and 64 x 65 joint counters and more pairs than a launch holds are in tests/test_gpu_summary_launch_shapes.py."""
 
 import numpy as np
 import pytest

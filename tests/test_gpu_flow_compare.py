@@ -11,7 +11,9 @@ Bounds, none of them taken from what the GPU gives:
 * bit-identical summaries for host arrays and device tensors, from call to call and for 1, 2 and the library's pairs in flight.
 
 Planes are 40 x 52 (2080 samples: one block of the kernels per pair whose lanes do not all hold the same number of samples,
-N_i != N_j), P = 3: the launches hold 1, 2 or 3 pairs.  Inputs: flow_compare_restatement.inputs_a and filter_inputs."""
+N_i != N_j), P = 3: the launches hold 1, 2 or 3 pairs.  Inputs: flow_compare_restatement.inputs_a and filter_inputs.
+These are one-block launches: several blocks per pair, the block caps, more than 64 extremes records, more pairs than a launch
+holds and samples on the bin edges are in tests/test_gpu_summary_launch_shapes.py."""
 import numpy as np
 import pytest
 
