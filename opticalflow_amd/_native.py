@@ -82,53 +82,9 @@ SIGNATURES = {
     "vof_query_workspace_for": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vof_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "vof_num_levels": (C.c_int, [_vp]),
-    "vof_solve_stack_host": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), _vp, _vp, _vp, _vp, _vp]),
-    "vof_solve_stack_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), _vp, _vp, _vp, _vp, _vp]),
     "vof_texture_stack_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_double, C.c_double]),
     "vof_bench_sweeps_dev": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), C.c_int]),
-    "vof_blur_stack_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int]),
-    "vof_blur_stack_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int]),
-    "vof_box_flow_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "vof_box_flow_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "vof_liu_shen_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "vof_liu_shen_host": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "vof_vary_regularisation_host": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(VofParams), _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
-    "vof_vary_boxsize_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
-                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "vof_vary_boxsize_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
-                                        _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "vof_vary_blursize_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp,
-                                        C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "vof_vary_blursize_host": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp,
-                                         C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "vof_compare_flows_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
-                                        _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
-                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "vof_compare_flows_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
-                                         _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "vof_adaptive_threshold_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _dp]),
-    "vof_adaptive_threshold_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _dp]),
-    "vof_clahe_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _dp]),
-    "vof_clahe_host": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _dp]),
-    "vof_resize_area_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
-    "vof_resize_area_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
-    "vof_farneback_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
-                                    C.c_double, C.c_int, _vp, _vp, _vp]),
-    "vof_farneback_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
-                                     C.c_double, C.c_int, _vp, _vp, _vp]),
-    "vof_farneback_box_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
-                                        C.c_double, C.c_int, _vp, _vp, _vp]),
-    "vof_farneback_box_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
-                                         C.c_double, C.c_int, _vp, _vp, _vp]),
-    "vof_flow_filter_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "vof_flow_filter_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
-    "vof_flow_extremes_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp]),
-    "vof_flow_extremes_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp]),
-    "vof_flow_compare_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp, C.c_int,
-                                       _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
-    "vof_flow_compare_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp, C.c_int,
-                                        _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "vof_field_moments_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vof_subsample_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "vof_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -156,6 +112,33 @@ SIGNATURES = {
     "vof_debug_coarse_solve": (C.c_int, [_vp, _vp, _vp]),
     "vof_debug_vcycle_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
 }
+
+# the entries the library has twice, NAME_host on host arrays and NAME_dev on device memory: one argument list for the two
+TWINS = {
+    "vof_solve_stack": [_vp, _vp, C.c_int, C.POINTER(VofParams), _vp, _vp, _vp, _vp, _vp],
+    "vof_blur_stack": [_vp, _vp, _vp, C.c_int, _vp, C.c_int],
+    "vof_box_flow": [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "vof_liu_shen": [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "vof_vary_boxsize": [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                         _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "vof_vary_blursize": [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, C.c_int, _vp,
+                          C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "vof_compare_flows": [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                          _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "vof_adaptive_threshold": [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp, _dp],
+    "vof_clahe": [_vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _dp],
+    "vof_resize_area": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp],
+    "vof_farneback": [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
+                      C.c_double, C.c_int, _vp, _vp, _vp],
+    "vof_farneback_box": [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_float,
+                          C.c_double, C.c_int, _vp, _vp, _vp],
+    "vof_flow_filter": [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "vof_flow_extremes": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp],
+    "vof_flow_compare": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                         _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
+}
+SIGNATURES.update({name + twin: (C.c_int, args) for name, args in TWINS.items() for twin in ("_host", "_dev")})
 
 _lib = None
 
@@ -247,6 +230,21 @@ def _probes_and_speeds(probe_locations, n, n_frames):
     return pij, np.zeros((n, max(int(n_frames) - 1, 0), pij.shape[0]))
 
 
+def liu_shen_initial(fields, pairs_shape):
+    """The three initial fields of the Liu-Shen flow - numpy arrays or device tensors, each a scalar, an ``(n_i, n_j)`` plane or a
+    ``(T - 1, n_i, n_j)`` stack - in the widest of their three forms, as ``Solver.liu_shen`` takes them, and that form's kind: 0 three
+    Python floats, 1 contiguous planes, 2 contiguous stacks.  Any other shape is a ``ValueError``."""
+    forms = ((), tuple(pairs_shape[1:]), tuple(pairs_shape))
+    try:
+        kind = max(forms.index(tuple(f.shape)) for f in fields)
+    except ValueError:
+        raise ValueError(f"initial fields must be scalars, {forms[1]} planes or {forms[2]} stacks") from None
+    if kind == 0:
+        return [float(f) for f in fields], 0
+    return [np.ascontiguousarray(np.broadcast_to(f, forms[kind])) if isinstance(f, np.ndarray) else f.expand(forms[kind]).contiguous()
+            for f in fields], kind
+
+
 class Solver:
     """One context = one device; owns the device workspace for (n_i, n_j) images and a batch of
     ``max_pairs_in_flight`` frame pairs."""
@@ -305,103 +303,108 @@ class Solver:
         self._check(self.lib.vof_debug_level_shape(self.h, level, C.byref(a), C.byref(b)), "level_shape")
         return a.value, b.value
 
-    # -- solves
+    # -- the native twins.  X takes the input stacks, the frame (or pair) count and the output arrays, all numpy arrays or all device
+    # memory (torch tensors or raw pointers), float64 and contiguous, and calls the _host or the _dev twin accordingly; X_host converts
+    # the movie, allocates numpy outputs, calls X and returns them; X_dev is X under the name its callers know.
+    @staticmethod
+    def _twin(name, arrays):
+        host = [isinstance(a, np.ndarray) for a in arrays if a is not None]
+        assert all(host) or not any(host), "host arrays and device memory do not mix in one call"
+        return name + ("_host" if host and host[0] else "_dev")
+
+    def _call(self, name, arrays, *args, refusal=None):
+        """The twin of ``name`` that ``arrays`` select.  ``refusal``: return code 1 (the stack holds values the entry does not serve) is
+        a ValueError of the library's message and the text ``refusal()`` adds."""
+        fn = self._twin(name, arrays)
+        rc = getattr(self.lib, fn)(self.h, *args)
+        if rc == 1 and refusal is not None:
+            raise ValueError(self.lib.vof_last_error(self.h).decode() + refusal())
+        self._check(rc, fn)
+
+    def _host_movie(self, movie):
+        movie = np.ascontiguousarray(movie, dtype=np.float64)
+        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        return movie
+
+    def solve(self, movie, n_frames, params: VofParams, v_x, v_y, remodelling, speed=None, stats=True):
+        """``vof_solve_stack_*``: the variational flow of ``n_frames`` frames into float64 ``(n_frames - 1, n_i, n_j)`` arrays;
+        returns the STATS_DTYPE record of every pair (None without ``stats``)."""
+        st = np.zeros(n_frames - 1, dtype=STATS_DTYPE) if stats else None
+        self._call("vof_solve_stack", (movie, v_x, v_y, remodelling, speed), _ptr(movie), int(n_frames), C.byref(params), _ptr(v_x),
+                   _ptr(v_y), _ptr(remodelling), _ptr(speed), _ptr(st))
+        return st
+
     def solve_host(self, movie: np.ndarray, params: VofParams, want_speed=True):
         movie = np.ascontiguousarray(movie, dtype=np.float64)
         T = movie.shape[0]
         assert movie.shape[1:] == (self.n_i, self.n_j)
         out = [np.empty((T - 1, self.n_i, self.n_j)) for _ in range(4 if want_speed else 3)]
-        stats = np.zeros(T - 1, dtype=STATS_DTYPE)
-        rc = self.lib.vof_solve_stack_host(self.h, _ptr(movie), T, C.byref(params), _ptr(out[0]), _ptr(out[1]),
-                                           _ptr(out[2]), _ptr(out[3]) if want_speed else None, _ptr(stats))
-        self._check(rc, "vof_solve_stack_host")
+        stats = self.solve(movie, T, params, *out)
         return (*out, stats) if want_speed else (*out, None, stats)
 
-    def solve_dev(self, movie, n_frames, params: VofParams, v_x, v_y, remodelling, speed=None, stats=True):
-        """All arrays are device memory (torch tensors or raw pointers)."""
-        st = np.zeros(n_frames - 1, dtype=STATS_DTYPE) if stats else None
-        rc = self.lib.vof_solve_stack_dev(self.h, _ptr(movie), int(n_frames), C.byref(params), _ptr(v_x), _ptr(v_y),
-                                          _ptr(remodelling), _ptr(speed), _ptr(st))
-        self._check(rc, "vof_solve_stack_dev")
-        return st
+    solve_dev = solve
+
+    def blur(self, movie, out, n_frames, weights: np.ndarray):
+        """``vof_blur_stack_*``: Gaussian blur of ``n_frames`` frames with the taps ``weights`` (on device memory ``out`` may alias
+        ``movie``)."""
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        self._call("vof_blur_stack", (movie, out), _ptr(movie), _ptr(out), int(n_frames), _ptr(weights), weights.size // 2)
 
     def blur_host(self, movie: np.ndarray, weights: np.ndarray):
         """Gaussian blur of every frame on the device (host arrays in and out)."""
         movie = np.ascontiguousarray(movie, dtype=np.float64)
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        assert movie.shape[1:] == (self.n_i, self.n_j) and weights.size % 2 == 1
+        assert movie.shape[1:] == (self.n_i, self.n_j) and np.size(weights) % 2 == 1
         out = np.empty_like(movie)
-        self._check(self.lib.vof_blur_stack_host(self.h, _ptr(movie), _ptr(out), movie.shape[0], _ptr(weights),
-                                                 weights.size // 2), "vof_blur_stack_host")
+        self.blur(movie, out, movie.shape[0], weights)
         return out
 
-    def blur_dev(self, movie, out, n_frames, weights: np.ndarray):
-        """Gaussian blur of ``n_frames`` device-resident frames (``out`` may alias ``movie``)."""
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        self._check(self.lib.vof_blur_stack_dev(self.h, _ptr(movie), _ptr(out), int(n_frames), _ptr(weights),
-                                                weights.size // 2), "vof_blur_stack_dev")
+    blur_dev = blur
+
+    def box_flow(self, movie, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks, v_x, v_y, speed,
+                 net_remodelling=None):
+        """``vof_box_flow_*``: box least-squares flow (conduct_optical_flow_jit, OF.py:24-157) of ``n_frames`` frames into float64
+        ``(n_frames - 1, n_i, n_j)`` arrays; every element of the outputs is written."""
+        self._call("vof_box_flow", (movie, v_x, v_y, speed, net_remodelling), _ptr(movie), int(n_frames), int(box_size), float(delta_x),
+                   float(delta_t), int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(v_x), _ptr(v_y), _ptr(speed),
+                   _ptr(net_remodelling))
 
     def box_flow_host(self, movie: np.ndarray, box_size=15, delta_x=1.0, delta_t=1.0, include_remodelling=False,
                       reference_quirks=True):
-        """Box least-squares flow (conduct_optical_flow_jit, OF.py:24-157) of a host movie; returns
-        ``(v_x, v_y, speed, net_remodelling)``, float64 ``(T - 1, n_i, n_j)`` each (``net_remodelling`` all zero without
-        ``include_remodelling``)."""
-        movie = np.ascontiguousarray(movie, dtype=np.float64)
-        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        """The box flow of a host movie; returns ``(v_x, v_y, speed, net_remodelling)``, float64 ``(T - 1, n_i, n_j)`` each
+        (``net_remodelling`` all zero without ``include_remodelling``)."""
+        movie = self._host_movie(movie)
         T = movie.shape[0]
         out = [np.empty((max(T - 1, 0), self.n_i, self.n_j)) for _ in range(4)]
-        rc = self.lib.vof_box_flow_host(self.h, _ptr(movie), T, int(box_size), float(delta_x), float(delta_t),
-                                        int(bool(include_remodelling)), int(bool(reference_quirks)), *[_ptr(o) for o in out])
-        self._check(rc, "vof_box_flow_host")
+        self.box_flow(movie, T, box_size, delta_x, delta_t, include_remodelling, reference_quirks, *out)
         return tuple(out)
 
-    def box_flow_dev(self, movie, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks, v_x, v_y, speed,
-                     net_remodelling=None):
-        """The same on device memory (torch tensors or raw pointers); every element of the outputs is written."""
-        rc = self.lib.vof_box_flow_dev(self.h, _ptr(movie), int(n_frames), int(box_size), float(delta_x), float(delta_t),
-                                       int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(v_x), _ptr(v_y),
-                                       _ptr(speed), _ptr(net_remodelling))
-        self._check(rc, "vof_box_flow_dev")
+    box_flow_dev = box_flow
 
-    @staticmethod
-    def _initial_kind(fields, pairs_shape):
-        """The common kind of the three initial fields of the Liu-Shen flow: 0 scalar, 1 plane, 2 stack."""
-        kinds = {(): 0, tuple(pairs_shape[1:]): 1, tuple(pairs_shape): 2}
-        try:
-            return max(kinds[tuple(f.shape)] for f in fields)
-        except KeyError:
-            raise ValueError(f"initial fields must be scalars, {tuple(pairs_shape[1:])} planes or {tuple(pairs_shape)} stacks") from None
+    def liu_shen(self, movie, n_frames, delta_x, delta_t, alpha, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
+                 max_iterations, v_x, v_y, speed, remodelling):
+        """``vof_liu_shen_*``: Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) of ``n_frames`` frames into float64
+        ``(n_frames - 1, n_i, n_j)`` arrays; every element of the outputs is written.  The initial fields and their kind are what
+        ``liu_shen_initial`` returns: three Python floats (kind 0), or planes / stacks (1 / 2) on the side of the movie."""
+        initial = [initial_v_x, initial_v_y, initial_remodelling]
+        if initial_kind == 0:                # both twins read three host doubles
+            initial = [np.array([float(f)]) for f in initial]
+        self._call("vof_liu_shen", (movie, v_x, v_y, speed, remodelling), _ptr(movie), int(n_frames), float(delta_x), float(delta_t),
+                   float(alpha), *[_ptr(f) for f in initial], int(initial_kind), int(max_iterations), _ptr(v_x), _ptr(v_y), _ptr(speed),
+                   _ptr(remodelling))
 
     def liu_shen_host(self, movie: np.ndarray, delta_x=1.0, delta_t=1.0, alpha=100.0, initial_v_x=0.0, initial_v_y=0.0,
                       initial_remodelling=0.0, max_iterations=10):
-        """Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) of a host movie; returns
-        ``(v_x, v_y, speed, remodelling)``, float64 ``(T - 1, n_i, n_j)`` each.  The initial fields are scalars, ``(n_i, n_j)``
-        planes or ``(T - 1, n_i, n_j)`` stacks; they are passed in the widest of the three forms."""
-        movie = np.ascontiguousarray(movie, dtype=np.float64)
-        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        """The Liu-Shen flow of a host movie; returns ``(v_x, v_y, speed, remodelling)``, float64 ``(T - 1, n_i, n_j)`` each.  The
+        initial fields are scalars, ``(n_i, n_j)`` planes or ``(T - 1, n_i, n_j)`` stacks."""
+        movie = self._host_movie(movie)
         T = movie.shape[0]
         shape = (max(T - 1, 0), self.n_i, self.n_j)
-        init = [np.asarray(f, dtype=np.float64) for f in (initial_v_x, initial_v_y, initial_remodelling)]
-        kind = self._initial_kind(init, shape)
-        init = [np.ascontiguousarray(np.broadcast_to(f, ((), shape[1:], shape)[kind])).reshape(-1) for f in init]
+        initial, kind = liu_shen_initial([np.asarray(f, dtype=np.float64) for f in (initial_v_x, initial_v_y, initial_remodelling)], shape)
         out = [np.empty(shape) for _ in range(4)]
-        rc = self.lib.vof_liu_shen_host(self.h, _ptr(movie), T, float(delta_x), float(delta_t), float(alpha), *[_ptr(f) for f in init],
-                                        kind, int(max_iterations), *[_ptr(o) for o in out])
-        self._check(rc, "vof_liu_shen_host")
+        self.liu_shen(movie, T, delta_x, delta_t, alpha, *initial, kind, max_iterations, *out)
         return tuple(out)
 
-    def liu_shen_dev(self, movie, n_frames, delta_x, delta_t, alpha, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
-                     max_iterations, v_x, v_y, speed, remodelling):
-        """The same on device memory (torch tensors or raw pointers).  ``initial_kind`` 0: the three initial fields are Python
-        floats; 1 / 2: device planes / stacks.  Every element of the outputs is written."""
-        if initial_kind == 0:
-            keep = [np.array([float(f)]) for f in (initial_v_x, initial_v_y, initial_remodelling)]
-        else:
-            keep = [initial_v_x, initial_v_y, initial_remodelling]
-        rc = self.lib.vof_liu_shen_dev(self.h, _ptr(movie), int(n_frames), float(delta_x), float(delta_t), float(alpha),
-                                       *[_ptr(f) for f in keep], int(initial_kind), int(max_iterations), _ptr(v_x), _ptr(v_y),
-                                       _ptr(speed), _ptr(remodelling))
-        self._check(rc, "vof_liu_shen_dev")
+    liu_shen_dev = liu_shen
 
     def vary_regularisation_host(self, movie: np.ndarray, params: VofParams, speed_alphas, remodelling_alphas, weights=None):
         """The whole (speed_alpha, remodelling_alpha) sweep of vary_regularisation on the device; returns a structured
@@ -423,43 +426,44 @@ class Solver:
         wanted = (4 if include_remodelling else 3) if return_fields else 0
         return [np.empty((n, max(n_frames - 1, 0), self.n_i, self.n_j)) if f < wanted else None for f in range(4)]
 
-    def _vary_boxsize(self, fn, movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks, weights,
-                      histogram_edges, probe_locations, fields):
+    def vary_boxsize(self, movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks, weights=None,
+                     histogram_edges=None, probe_locations=None, v_x=None, v_y=None, speed=None, net_remodelling=None):
+        """``vof_vary_boxsize_*``: the box-size sweep of the box flow in one native call, the blur taps ``weights`` (or None) applied
+        first; the optional field stacks are ``(n_boxes, n_frames - 1, n_i, n_j)``.  Returns ``(stats, histograms, probe_speeds)`` as
+        host arrays: a BOXSIZE_DTYPE record per box, int64 ``(n_boxes, bins)`` counts or None, ``(n_boxes, n_frames - 1, n_probes)``
+        speeds or None."""
         boxes = np.ascontiguousarray(box_sizes, dtype=np.int32).ravel()
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
         edges, bins, hist = _edges_and_counts(histogram_edges, boxes.size)
         pij, probes = _probes_and_speeds(probe_locations, boxes.size, n_frames)
         stats = np.zeros(boxes.size, dtype=BOXSIZE_DTYPE)
-        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), _ptr(boxes), boxes.size, float(delta_x), float(delta_t),
-                                   int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(w),
-                                   0 if w is None else w.size // 2, _ptr(edges), bins, _ptr(hist), _ptr(pij),
-                                   0 if pij is None else pij.shape[0], _ptr(probes), _ptr(stats), *[_ptr(f) for f in fields])
-        self._check(rc, fn)
+        fields = (v_x, v_y, speed, net_remodelling)
+        self._call("vof_vary_boxsize", (movie, *fields), _ptr(movie), int(n_frames), _ptr(boxes), boxes.size, float(delta_x),
+                   float(delta_t), int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(w), 0 if w is None else w.size // 2,
+                   _ptr(edges), bins, _ptr(hist), _ptr(pij), 0 if pij is None else pij.shape[0], _ptr(probes), _ptr(stats),
+                   *[_ptr(f) for f in fields])
         return stats, hist, probes
 
     def vary_boxsize_host(self, movie: np.ndarray, box_sizes, delta_x=1.0, delta_t=1.0, include_remodelling=False,
                           reference_quirks=True, weights=None, histogram_edges=None, probe_locations=None, return_fields=False):
-        """The box-size sweep of the box flow of a host movie in one native call; returns ``(stats, histograms, probe_speeds,
-        fields)``: a BOXSIZE_DTYPE record per box, int64 ``(n_boxes, bins)`` counts or None, ``(n_boxes, T - 1, n_probes)``
-        speeds or None, and None or ``(v_x, v_y, speed, net_remodelling)`` of shape ``(n_boxes, T - 1, n_i, n_j)``
-        (``net_remodelling`` is None without ``include_remodelling``)."""
-        movie = np.ascontiguousarray(movie, dtype=np.float64)
-        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        """The sweep of a host movie; returns ``(stats, histograms, probe_speeds, fields)``, ``fields`` None or ``(v_x, v_y, speed,
+        net_remodelling)`` of shape ``(n_boxes, T - 1, n_i, n_j)`` (``net_remodelling`` is None without ``include_remodelling``)."""
+        movie = self._host_movie(movie)
         T = movie.shape[0]
         fields = self._sweep_fields(np.size(box_sizes), T, include_remodelling, return_fields)
-        out = self._vary_boxsize("vof_vary_boxsize_host", movie, T, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks,
-                                 weights, histogram_edges, probe_locations, fields)
+        out = self.vary_boxsize(movie, T, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks, weights, histogram_edges,
+                                probe_locations, *fields)
         return (*out, tuple(fields) if return_fields else None)
 
-    def vary_boxsize_dev(self, movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling, reference_quirks, weights=None,
-                         histogram_edges=None, probe_locations=None, v_x=None, v_y=None, speed=None, net_remodelling=None):
-        """The same on device memory (torch tensors or raw pointers): ``movie`` and the optional field stacks
-        ``(n_boxes, n_frames - 1, n_i, n_j)``; returns ``(stats, histograms, probe_speeds)`` as host arrays."""
-        return self._vary_boxsize("vof_vary_boxsize_dev", movie, n_frames, box_sizes, delta_x, delta_t, include_remodelling,
-                                  reference_quirks, weights, histogram_edges, probe_locations, [v_x, v_y, speed, net_remodelling])
+    vary_boxsize_dev = vary_boxsize
 
-    def _vary_blursize(self, fn, movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
-                       histogram_edges, angle_bins, intensity_edges, probe_locations, fields):
+    def vary_blursize(self, movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
+                      histogram_edges=None, angle_bins=None, intensity_edges=None, probe_locations=None, v_x=None, v_y=None,
+                      speed=None, net_remodelling=None):
+        """``vof_vary_blursize_*``: the blur sweep of the box flow in one native call; ``taps`` is a list of tap vectors (one blur
+        each), the optional field stacks are ``(n, n_frames - 1, n_i, n_j)``.  Returns ``(stats, histograms, angle_histograms,
+        weighted_angle_histograms, intensity_histograms, probe_speeds)`` as host arrays: a BLURSIZE_DTYPE record per blur, the
+        histograms ``(n, bins)`` or None where not asked for, ``(n, n_frames - 1, n_probes)`` speeds or None."""
         taps = [np.ascontiguousarray(t, dtype=np.float64).ravel() for t in taps]
         n = len(taps)
         radii = np.array([t.size // 2 for t in taps], dtype=np.int32)
@@ -471,41 +475,37 @@ class Solver:
         awhist = np.zeros((n, abins)) if abins else None
         pij, probes = _probes_and_speeds(probe_locations, n, n_frames)
         stats = np.zeros(n, dtype=BLURSIZE_DTYPE)
-        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), _ptr(weights), _ptr(radii), n, int(box_size), float(delta_x),
-                                   float(delta_t), int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(edges), bins,
-                                   _ptr(hist), abins, _ptr(ahist), _ptr(awhist), _ptr(iedges), ibins, _ptr(ihist), _ptr(pij),
-                                   0 if pij is None else pij.shape[0], _ptr(probes), _ptr(stats), *[_ptr(f) for f in fields])
-        self._check(rc, fn)
+        fields = (v_x, v_y, speed, net_remodelling)
+        self._call("vof_vary_blursize", (movie, *fields), _ptr(movie), int(n_frames), _ptr(weights), _ptr(radii), n, int(box_size),
+                   float(delta_x), float(delta_t), int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(edges), bins,
+                   _ptr(hist), abins, _ptr(ahist), _ptr(awhist), _ptr(iedges), ibins, _ptr(ihist), _ptr(pij),
+                   0 if pij is None else pij.shape[0], _ptr(probes), _ptr(stats), *[_ptr(f) for f in fields])
         return stats, hist, ahist, awhist, ihist, probes
 
     def vary_blursize_host(self, movie: np.ndarray, taps, box_size, delta_x=1.0, delta_t=1.0, include_remodelling=False,
                            reference_quirks=True, histogram_edges=None, angle_bins=None, intensity_edges=None, probe_locations=None,
                            return_fields=False):
-        """The blur sweep of the box flow of a host movie in one native call; ``taps`` is a list of tap vectors (one blur
-        each).  Returns ``(stats, histograms, angle_histograms, weighted_angle_histograms, intensity_histograms, probe_speeds,
-        fields)``: a BLURSIZE_DTYPE record per blur, the histograms ``(n, bins)`` or None where not asked for,
-        ``(n, T - 1, n_probes)`` speeds or None, and None or ``(v_x, v_y, speed, net_remodelling)`` of shape
+        """The sweep of a host movie; returns the six summaries and ``fields``, None or ``(v_x, v_y, speed, net_remodelling)`` of shape
         ``(n, T - 1, n_i, n_j)`` (``net_remodelling`` is None without ``include_remodelling``)."""
-        movie = np.ascontiguousarray(movie, dtype=np.float64)
-        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        movie = self._host_movie(movie)
         T = movie.shape[0]
         fields = self._sweep_fields(len(taps), T, include_remodelling, return_fields)
-        out = self._vary_blursize("vof_vary_blursize_host", movie, T, taps, box_size, delta_x, delta_t, include_remodelling,
-                                  reference_quirks, histogram_edges, angle_bins, intensity_edges, probe_locations, fields)
+        out = self.vary_blursize(movie, T, taps, box_size, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
+                                 angle_bins, intensity_edges, probe_locations, *fields)
         return (*out, tuple(fields) if return_fields else None)
 
-    def vary_blursize_dev(self, movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
-                          histogram_edges=None, angle_bins=None, intensity_edges=None, probe_locations=None, v_x=None, v_y=None,
-                          speed=None, net_remodelling=None):
-        """The same on device memory (torch tensors or raw pointers): ``movie`` and the optional field stacks
-        ``(n, n_frames - 1, n_i, n_j)``; returns the six summaries as host arrays."""
-        return self._vary_blursize("vof_vary_blursize_dev", movie, n_frames, taps, box_size, delta_x, delta_t, include_remodelling,
-                                   reference_quirks, histogram_edges, angle_bins, intensity_edges, probe_locations,
-                                   [v_x, v_y, speed, net_remodelling])
+    vary_blursize_dev = vary_blursize
 
-    def _compare_flows(self, fn, movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
-                       weights_a, weights_b, histogram_edges, angle_bins, relative_angle_bins, joint_speed_edges, joint_speed_min_b,
-                       fields_a, fields_b):
+    def compare_flows(self, movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
+                      weights_a=None, weights_b=None, histogram_edges=None, angle_bins=None, relative_angle_bins=50,
+                      joint_speed_edges=None, joint_speed_min_b=None, fields_a=None, fields_b=None):
+        """``vof_compare_flows_*``: the box flows of two movies of one shape and their joint statistics in one native call;
+        ``weights_a`` / ``weights_b`` are the blur taps of a channel or None, ``joint_speed_edges`` a pair of edge vectors or None,
+        ``fields_a`` / ``fields_b`` None or the stacks ``(v_x, v_y, speed[, net_remodelling])`` of a channel, ``(n_frames - 1, n_i,
+        n_j)`` each.  Returns ``(stats, histograms, angle_histograms, weighted_angle_histograms, relative_angle_histogram,
+        weighted_relative_angle_histogram, joint_speed_histogram, joint_counts)`` as host arrays: a COMPARE_DTYPE record per channel,
+        the per-channel histograms ``(2, bins)`` or None where not asked for, the two histograms of the angle between the flows, the
+        ``(bins_a, bins_b)`` counts or None, ``(joint non-finite, theta dropped)``."""
         w = [None if t is None else np.ascontiguousarray(t, dtype=np.float64).ravel() for t in (weights_a, weights_b)]
         edges, bins, hist = _edges_and_counts(histogram_edges, 2)
         abins, tbins = int(angle_bins or 0), int(relative_angle_bins)
@@ -519,104 +519,88 @@ class Solver:
         jmin = None if joint_speed_min_b is None else np.array([joint_speed_min_b], dtype=np.float64)
         jcounts = np.zeros(2, dtype=np.int64)
         stats = np.zeros(2, dtype=COMPARE_DTYPE)
-        rc = getattr(self.lib, fn)(self.h, _ptr(movie_a), _ptr(movie_b), int(n_frames), _ptr(w[0]), 0 if w[0] is None else w[0].size // 2,
-                                   _ptr(w[1]), 0 if w[1] is None else w[1].size // 2, int(box_size), float(delta_x), float(delta_t),
-                                   int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(edges), bins, _ptr(hist), abins,
-                                   _ptr(ahist), _ptr(awhist), tbins, _ptr(thist), _ptr(twhist), _ptr(jedges[0]),
-                                   0 if jedges[0] is None else jedges[0].size - 1, _ptr(jedges[1]),
-                                   0 if jedges[1] is None else jedges[1].size - 1, _ptr(jmin), _ptr(jhist), _ptr(jcounts), _ptr(stats),
-                                   *[_ptr(f) for f in fields_a], *[_ptr(f) for f in fields_b])
-        self._check(rc, fn)
+        fields = [(list(f or ()) + [None] * 4)[:4] for f in (fields_a, fields_b)]
+        self._call("vof_compare_flows", (movie_a, movie_b, *fields[0], *fields[1]), _ptr(movie_a), _ptr(movie_b), int(n_frames),
+                   _ptr(w[0]), 0 if w[0] is None else w[0].size // 2, _ptr(w[1]), 0 if w[1] is None else w[1].size // 2, int(box_size),
+                   float(delta_x), float(delta_t), int(bool(include_remodelling)), int(bool(reference_quirks)), _ptr(edges), bins,
+                   _ptr(hist), abins, _ptr(ahist), _ptr(awhist), tbins, _ptr(thist), _ptr(twhist), _ptr(jedges[0]),
+                   0 if jedges[0] is None else jedges[0].size - 1, _ptr(jedges[1]), 0 if jedges[1] is None else jedges[1].size - 1,
+                   _ptr(jmin), _ptr(jhist), _ptr(jcounts), _ptr(stats), *[_ptr(f) for f in fields[0] + fields[1]])
         return stats, hist, ahist, awhist, thist, twhist, jhist, jcounts
 
     def compare_flows_host(self, movie_a: np.ndarray, movie_b: np.ndarray, box_size, delta_x=1.0, delta_t=1.0, include_remodelling=False,
                            reference_quirks=True, weights_a=None, weights_b=None, histogram_edges=None, angle_bins=None,
                            relative_angle_bins=50, joint_speed_edges=None, joint_speed_min_b=None, return_fields=False):
-        """The box flows of two host movies of one shape and their joint statistics in one native call; ``weights_a`` /
-        ``weights_b`` are the blur taps of a channel or None, ``joint_speed_edges`` a pair of edge vectors or None.  Returns
-        ``(stats, histograms, angle_histograms, weighted_angle_histograms, relative_angle_histogram,
-        weighted_relative_angle_histogram, joint_speed_histogram, joint_counts, fields)``: a COMPARE_DTYPE record per channel,
-        the per-channel histograms ``(2, bins)`` or None where not asked for, the two histograms of the angle between the
-        flows, the ``(bins_a, bins_b)`` counts or None, ``(joint non-finite, theta dropped)``, and None or a pair of
-        ``(v_x, v_y, speed, net_remodelling)`` of shape ``(T - 1, n_i, n_j)`` (``net_remodelling`` is None without
-        ``include_remodelling``)."""
-        movie_a = np.ascontiguousarray(movie_a, dtype=np.float64)
-        movie_b = np.ascontiguousarray(movie_b, dtype=np.float64)
-        assert movie_a.ndim == 3 and movie_a.shape[1:] == (self.n_i, self.n_j) and movie_b.shape == movie_a.shape
+        """The comparison of two host movies; returns the eight summaries and ``fields``, None or a pair of ``(v_x, v_y, speed,
+        net_remodelling)`` of shape ``(T - 1, n_i, n_j)`` (``net_remodelling`` is None without ``include_remodelling``)."""
+        movie_a, movie_b = self._host_movie(movie_a), np.ascontiguousarray(movie_b, dtype=np.float64)
+        assert movie_b.shape == movie_a.shape
         T = movie_a.shape[0]
         fields = [[f if f is None else f[0] for f in self._sweep_fields(1, T, include_remodelling, return_fields)] for _ in range(2)]
-        out = self._compare_flows("vof_compare_flows_host", movie_a, movie_b, T, box_size, delta_x, delta_t, include_remodelling,
-                                  reference_quirks, weights_a, weights_b, histogram_edges, angle_bins, relative_angle_bins,
-                                  joint_speed_edges, joint_speed_min_b, fields[0], fields[1])
+        out = self.compare_flows(movie_a, movie_b, T, box_size, delta_x, delta_t, include_remodelling, reference_quirks, weights_a,
+                                 weights_b, histogram_edges, angle_bins, relative_angle_bins, joint_speed_edges, joint_speed_min_b,
+                                 fields[0], fields[1])
         return (*out, (tuple(fields[0]), tuple(fields[1])) if return_fields else None)
 
-    def compare_flows_dev(self, movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling, reference_quirks,
-                          weights_a=None, weights_b=None, histogram_edges=None, angle_bins=None, relative_angle_bins=50,
-                          joint_speed_edges=None, joint_speed_min_b=None, fields_a=None, fields_b=None):
-        """The same on device memory (torch tensors or raw pointers): the movies and the optional field stacks
-        ``(v_x, v_y, speed, net_remodelling)`` of a channel, ``(n_frames - 1, n_i, n_j)`` each; returns the eight summaries as
-        host arrays."""
-        return self._compare_flows("vof_compare_flows_dev", movie_a, movie_b, n_frames, box_size, delta_x, delta_t, include_remodelling,
-                                   reference_quirks, weights_a, weights_b, histogram_edges, angle_bins, relative_angle_bins,
-                                   joint_speed_edges, joint_speed_min_b, fields_a or [None] * 4, fields_b or [None] * 4)
+    compare_flows_dev = compare_flows
 
-    def _preprocess(self, fn, movie, n_frames, args, frames_in_flight, out):
-        """One of the four preprocessing entry points; their return code 1 (the stack holds values the reference's integer
-        cast would wrap or leave to the platform) is a ValueError."""
+    def _preprocess(self, name, movie, n_frames, args, frames_in_flight, out):
+        """``vof_adaptive_threshold_*`` or ``vof_clahe_*``; their return code 1 (the stack holds values the reference's integer cast would
+        wrap or leave to the platform) is a ValueError."""
         rng = (C.c_double * 3)()
-        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), *args, int(frames_in_flight), _ptr(out), rng)
-        if rc == 1:
-            raise ValueError(self.lib.vof_last_error(self.h).decode() + f" (max {rng[0]}, min {rng[1]}, non-finite {int(rng[2])})")
-        self._check(rc, fn)
+        self._call(name, (movie, out), _ptr(movie), int(n_frames), *args, int(frames_in_flight), _ptr(out), rng,
+                   refusal=lambda: f" (max {rng[0]}, min {rng[1]}, non-finite {int(rng[2])})")
+
+    def adaptive_threshold(self, movie, mask, n_frames, window_size=51, threshold=0.0, frames_in_flight=0):
+        """``vof_adaptive_threshold_*``: ``apply_adaptive_threshold`` of ``n_frames`` float64 frames, one byte (0 / 1) per pixel out.
+        ``frames_in_flight=0`` leaves the chunk size to the library."""
+        self._preprocess("vof_adaptive_threshold", movie, n_frames, (int(window_size), float(threshold)), frames_in_flight, mask)
 
     def adaptive_threshold_host(self, movie: np.ndarray, window_size=51, threshold=0.0, frames_in_flight=0):
-        """``apply_adaptive_threshold`` of a host movie (read as float64): bool ``(T, n_i, n_j)``.  ``frames_in_flight=0``
-        leaves the chunk size to the library."""
-        movie = np.ascontiguousarray(movie, dtype=np.float64)
-        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
-        mask = np.empty(movie.shape, dtype=np.uint8)
-        self._preprocess("vof_adaptive_threshold_host", movie, movie.shape[0], (int(window_size), float(threshold)), frames_in_flight, mask)
-        return mask.view(np.bool_)
+        """The same of a host movie (read as float64): bool ``(T, n_i, n_j)``."""
+        movie = self._host_movie(movie)
+        mask = np.empty(movie.shape, dtype=np.bool_)
+        self.adaptive_threshold(movie, mask, movie.shape[0], window_size, threshold, frames_in_flight)
+        return mask
 
-    def adaptive_threshold_dev(self, movie, mask, n_frames, window_size=51, threshold=0.0, frames_in_flight=0):
-        """The same on device memory (torch tensors or raw pointers): float64 frames in, one byte (0 / 1) per pixel out."""
-        self._preprocess("vof_adaptive_threshold_dev", movie, n_frames, (int(window_size), float(threshold)), frames_in_flight, mask)
+    adaptive_threshold_dev = adaptive_threshold
+
+    def clahe(self, movie, out, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight=0):
+        """``vof_clahe_*``: ``apply_clahe`` of ``n_frames`` float64 frames for the tile grid ``tiles_x`` (along n_j) by ``tiles_y``, float64
+        frames out (``out`` must not alias ``movie``)."""
+        self._preprocess("vof_clahe", movie, n_frames, (float(clip_limit), int(tiles_x), int(tiles_y)), frames_in_flight, out)
 
     def clahe_host(self, movie: np.ndarray, clip_limit, tiles_x, tiles_y, frames_in_flight=0):
-        """``apply_clahe`` of a host movie for the tile grid ``tiles_x`` (along n_j) by ``tiles_y``: float64 ``(T, n_i, n_j)``."""
-        movie = np.ascontiguousarray(movie, dtype=np.float64)
-        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        """The same of a host movie: float64 ``(T, n_i, n_j)``."""
+        movie = self._host_movie(movie)
         out = np.empty(movie.shape, dtype=np.float64)
-        self._preprocess("vof_clahe_host", movie, movie.shape[0], (float(clip_limit), int(tiles_x), int(tiles_y)), frames_in_flight, out)
+        self.clahe(movie, out, movie.shape[0], clip_limit, tiles_x, tiles_y, frames_in_flight)
         return out
 
-    def clahe_dev(self, movie, out, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight=0):
-        """The same on device memory: float64 frames in and out (``out`` must not alias ``movie``)."""
-        self._preprocess("vof_clahe_dev", movie, n_frames, (float(clip_limit), int(tiles_x), int(tiles_y)), frames_in_flight, out)
+    clahe_dev = clahe
 
-    def _resize_area(self, fn, movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out):
-        """``vof_resize_area_*``; return code 1 (uint8 arithmetic asked for a stack that holds other values) is a ValueError."""
-        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_frames), int(out_i), int(out_j), int(arithmetic), int(frames_in_flight), _ptr(out))
-        if rc == 1:
-            raise ValueError(self.lib.vof_last_error(self.h).decode())
-        self._check(rc, fn)
+    def resize_area(self, movie, out, n_frames, out_i, out_j, arithmetic, frames_in_flight=0):
+        """``vof_resize_area_*``: ``cv2.resize(frame, (out_j, out_i), interpolation=cv2.INTER_AREA)`` of ``n_frames`` float64 frames in
+        the arithmetic OpenCV applies to uint8 (``RESIZE_U8``) or float64 (``RESIZE_F64``) frames, float64 ``(n_frames, out_i, out_j)``
+        out (``out`` must not alias ``movie``); return code 1 (uint8 arithmetic asked for a stack that holds other values) is a
+        ValueError."""
+        self._call("vof_resize_area", (movie, out), _ptr(movie), int(n_frames), int(out_i), int(out_j), int(arithmetic),
+                   int(frames_in_flight), _ptr(out), refusal=str)
 
     def resize_area_host(self, movie: np.ndarray, out_i, out_j, arithmetic, frames_in_flight=0):
-        """``cv2.resize(frame, (out_j, out_i), interpolation=cv2.INTER_AREA)`` of every frame of a host movie (read as float64)
-        in the arithmetic OpenCV applies to uint8 (``RESIZE_U8``) or float64 (``RESIZE_F64``) frames: float64 ``(T, out_i, out_j)``."""
-        movie = np.ascontiguousarray(movie, dtype=np.float64)
-        assert movie.ndim == 3 and movie.shape[1:] == (self.n_i, self.n_j)
+        """The same of a host movie (read as float64): float64 ``(T, out_i, out_j)``."""
+        movie = self._host_movie(movie)
         out = np.empty((movie.shape[0], int(out_i), int(out_j)), dtype=np.float64)
-        self._resize_area("vof_resize_area_host", movie, movie.shape[0], out_i, out_j, arithmetic, frames_in_flight, out)
+        self.resize_area(movie, out, movie.shape[0], out_i, out_j, arithmetic, frames_in_flight)
         return out
 
-    def resize_area_dev(self, movie, out, n_frames, out_i, out_j, arithmetic, frames_in_flight=0):
-        """The same on device memory: float64 frames in, float64 ``(n_frames, out_i, out_j)`` out (``out`` must not alias ``movie``)."""
-        self._resize_area("vof_resize_area_dev", movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out)
+    resize_area_dev = resize_area
 
-    def _farneback(self, fn, first, second, n_pairs, plan, iterations, velocity_scale, frames_in_flight, v_x, v_y, speed, box=False):
-        """``vof_farneback_*`` (``box``: ``vof_farneback_box_*``, which take no window taps) with the tables of
-        ``optical_flow.farneback_plan``; return code 1 (a non-finite frame) is a ValueError."""
+    def farneback(self, first, second, n_pairs, plan, iterations, velocity_scale, v_x, v_y, speed, frames_in_flight=0, box=False):
+        """``vof_farneback_*`` (``box``: ``vof_farneback_box_*``, OpenCV's default box window of ``plan["winsize"]`` in place of the
+        Gaussian one, which takes no window taps): Farnebaeck's flow of the pairs ``(first[k], second[k])`` of two float64 stacks of
+        ``n_pairs`` frames (they may be two views of one movie) into three float64 ``(n_pairs, n_i, n_j)`` arrays, none of which may
+        alias a stack.  ``plan``: ``optical_flow.farneback_plan``; return code 1 (a non-finite frame) is a ValueError."""
         sizes = np.ascontiguousarray(plan["sizes"], dtype=np.int32).reshape(-1, 2)
         ksizes = np.ascontiguousarray(plan["ksizes"], dtype=np.int32)
         taps = np.ascontiguousarray(np.concatenate(plan["presmooth_taps"]), dtype=np.float32)
@@ -625,60 +609,39 @@ class Solver:
         window = np.ascontiguousarray(plan["window_taps"], dtype=np.float32)
         assert ksizes.size == sizes.shape[0] and taps.size == int(ksizes.sum()) and poly.size == 3 * (2 * int(plan["poly_n"]) + 1)
         assert window.size == int(plan["winsize"]) // 2 + 1
-        if box:
-            fn = fn.replace("vof_farneback_", "vof_farneback_box_")
-        rc = getattr(self.lib, fn)(self.h, _ptr(first), _ptr(second), int(n_pairs), sizes.shape[0], _ptr(sizes), _ptr(ksizes), _ptr(taps),
-                                   int(plan["poly_n"]), _ptr(poly), _ptr(ig), int(plan["winsize"]), *(() if box else (_ptr(window),)),
-                                   int(iterations), float(plan["flow_scale"]), float(velocity_scale), int(frames_in_flight), _ptr(v_x), _ptr(v_y),
-                                   _ptr(speed))
-        if rc == 1:
-            raise ValueError(self.lib.vof_last_error(self.h).decode())
-        self._check(rc, fn)
+        self._call("vof_farneback_box" if box else "vof_farneback", (first, second, v_x, v_y, speed), _ptr(first), _ptr(second),
+                   int(n_pairs), sizes.shape[0], _ptr(sizes), _ptr(ksizes), _ptr(taps), int(plan["poly_n"]), _ptr(poly), _ptr(ig),
+                   int(plan["winsize"]), *(() if box else (_ptr(window),)), int(iterations), float(plan["flow_scale"]),
+                   float(velocity_scale), int(frames_in_flight), _ptr(v_x), _ptr(v_y), _ptr(speed), refusal=str)
 
     def farneback_host(self, first: np.ndarray, second: np.ndarray, plan, iterations, velocity_scale=1.0, frames_in_flight=0, box=False):
-        """Farnebaeck's flow of the pairs ``(first[k], second[k])`` of two host stacks (read as float64; they may be two views of
-        one movie): ``(v_x, v_y, speed)``, float64 ``(n_pairs, n_i, n_j)`` each.  ``plan``: ``optical_flow.farneback_plan``.
-        ``box``: OpenCV's default box window of ``plan["winsize"]`` in place of the Gaussian one (the plan's window taps are unused)."""
-        first = np.ascontiguousarray(first, dtype=np.float64)
-        second = np.ascontiguousarray(second, dtype=np.float64)
-        assert first.ndim == 3 and first.shape[1:] == (self.n_i, self.n_j) and second.shape == first.shape
+        """The same of two host stacks (read as float64): ``(v_x, v_y, speed)``, float64 ``(n_pairs, n_i, n_j)`` each."""
+        first, second = self._host_movie(first), np.ascontiguousarray(second, dtype=np.float64)
+        assert second.shape == first.shape
         out = [np.empty(first.shape, dtype=np.float64) for _ in range(3)]
-        self._farneback("vof_farneback_host", first, second, first.shape[0], plan, iterations, velocity_scale, frames_in_flight, *out, box=box)
+        self.farneback(first, second, first.shape[0], plan, iterations, velocity_scale, *out, frames_in_flight, box)
         return tuple(out)
 
-    def farneback_dev(self, first, second, n_pairs, plan, iterations, velocity_scale, v_x, v_y, speed, frames_in_flight=0, box=False):
-        """The same on device memory: two float64 stacks of ``n_pairs`` frames in, three float64 ``(n_pairs, n_i, n_j)`` arrays out
-        (none of them may alias a stack)."""
-        self._farneback("vof_farneback_dev", first, second, n_pairs, plan, iterations, velocity_scale, frames_in_flight, v_x, v_y, speed, box=box)
+    farneback_dev = farneback
 
-    # -- two finished flow results (vof_flowcompare.hpp): numpy arrays take the _host twin, device memory the _dev twin
-    @staticmethod
-    def _twin(name, arrays):
-        host = [isinstance(a, np.ndarray) for a in arrays if a is not None]
-        assert all(host) or not any(host), "host arrays and device memory do not mix in one call"
-        return name + ("_host" if host and host[0] else "_dev")
-
+    # -- two finished flow results (vof_flowcompare.hpp)
     def flow_filter(self, movie, weights, n_pairs, intensity_threshold, speed_threshold, zero_speed_under_low, v_x, v_y, speed,
                     frames_in_flight=0):
         """``vof_flow_filter_*``: the reference's result filter in place on ``v_x``, ``v_y`` and ``speed`` (float64, ``(n_pairs, n_i,
         n_j)``), ``movie`` the first ``n_pairs`` float64 frames, ``weights`` the blur taps.  Returns ``(low, fast)`` sample counts."""
         weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
         counts = np.zeros(2, dtype=np.int64)
-        fn = self._twin("vof_flow_filter", (movie, v_x, v_y, speed))
-        rc = getattr(self.lib, fn)(self.h, _ptr(movie), int(n_pairs), _ptr(weights), weights.size // 2, float(intensity_threshold),
-                                   float(speed_threshold), int(bool(zero_speed_under_low)), int(frames_in_flight), _ptr(v_x), _ptr(v_y),
-                                   _ptr(speed), _ptr(counts))
-        self._check(rc, fn)
+        self._call("vof_flow_filter", (movie, v_x, v_y, speed), _ptr(movie), int(n_pairs), _ptr(weights), weights.size // 2,
+                   float(intensity_threshold), float(speed_threshold), int(bool(zero_speed_under_low)), int(frames_in_flight), _ptr(v_x),
+                   _ptr(v_y), _ptr(speed), _ptr(counts))
         return counts
 
     def flow_extremes(self, stacks, n_pairs, speed_threshold, angle_threshold, reference_quirks=True, frames_in_flight=0):
         """``vof_flow_extremes_*`` of the six stacks ``(v_x_a, v_y_a, speed_a, v_x_b, v_y_b, speed_b)``: float64 ``(3, 2)``, the
         (min, max) of speed a, of speed b and of cos over the samples that take part (+inf, -inf where none does)."""
         out = np.zeros((3, 2), dtype=np.float64)
-        fn = self._twin("vof_flow_extremes", stacks)
-        rc = getattr(self.lib, fn)(self.h, *[_ptr(s) for s in stacks], int(n_pairs), float(speed_threshold), float(angle_threshold),
-                                   int(bool(reference_quirks)), int(frames_in_flight), _ptr(out))
-        self._check(rc, fn)
+        self._call("vof_flow_extremes", stacks, *[_ptr(s) for s in stacks], int(n_pairs), float(speed_threshold), float(angle_threshold),
+                   int(bool(reference_quirks)), int(frames_in_flight), _ptr(out))
         return out
 
     def flow_compare(self, stacks, n_pairs, speed_threshold, angle_threshold, reference_quirks, edges_a, edges_b, angle_edges, clamp_angle,
@@ -689,13 +652,11 @@ class Solver:
         jhist = np.zeros((edges[0].size - 1, edges[1].size - 1), dtype=np.int64)
         thist = np.zeros(edges[2].size - 1, dtype=np.int64)
         counts = np.zeros(6, dtype=np.int64)
-        fn = self._twin("vof_flow_compare", stacks)
-        rc = getattr(self.lib, fn)(self.h, *[_ptr(s) for s in stacks], int(n_pairs), float(speed_threshold), float(angle_threshold),
-                                   int(bool(reference_quirks)), _ptr(edges[0]), edges[0].size - 1, _ptr(edges[1]), edges[1].size - 1,
-                                   _ptr(edges[2]), edges[2].size - 1, int(bool(clamp_angle)), int(frames_in_flight), _ptr(jhist), _ptr(thist),
-                                   _ptr(counts))
-        self._check(rc, fn)
+        self._call("vof_flow_compare", stacks, *[_ptr(s) for s in stacks], int(n_pairs), float(speed_threshold), float(angle_threshold),
+                   int(bool(reference_quirks)), _ptr(edges[0]), edges[0].size - 1, _ptr(edges[1]), edges[1].size - 1, _ptr(edges[2]),
+                   edges[2].size - 1, int(bool(clamp_angle)), int(frames_in_flight), _ptr(jhist), _ptr(thist), _ptr(counts))
         return jhist, thist, counts
+
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

@@ -4175,23 +4175,18 @@ static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
     return 0;
 }
 
-int vof_vary_boxsize_dev(vof_ctx* c, const double* movie, int n_frames, const int32_t* box_sizes, int n_boxes, double delta_x,
-                         double delta_t, int include_remodelling, int reference_quirks, const double* blur_weights, int blur_radius,
-                         const double* histogram_edges, int histogram_bins, int64_t* histograms, const int32_t* probe_ij, int n_probes,
-                         double* probe_speeds, vof_boxsize_stats* stats, double* v_x, double* v_y, double* speed, double* net_remodelling) {
-    return vary_boxsize_impl(c, SweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
-                                          histogram_bins, histograms, probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, false},
-                                         box_sizes, n_boxes, blur_weights, blur_radius, stats});
-}
+#define VOF_BOXSIZE_ARGS                                                                                                              \
+    vof_ctx *c, const double *movie, int n_frames, const int32_t *box_sizes, int n_boxes, double delta_x, double delta_t,             \
+        int include_remodelling, int reference_quirks, const double *blur_weights, int blur_radius, const double *histogram_edges,    \
+        int histogram_bins, int64_t *histograms, const int32_t *probe_ij, int n_probes, double *probe_speeds,                         \
+        vof_boxsize_stats *stats, double *v_x, double *v_y, double *speed, double *net_remodelling
+#define VOF_BOXSIZE_REQ(host)                                                                                                         \
+    SweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges, histogram_bins, histograms,  \
+              probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, host},                                            \
+             box_sizes, n_boxes, blur_weights, blur_radius, stats}
 
-int vof_vary_boxsize_host(vof_ctx* c, const double* movie, int n_frames, const int32_t* box_sizes, int n_boxes, double delta_x,
-                          double delta_t, int include_remodelling, int reference_quirks, const double* blur_weights, int blur_radius,
-                          const double* histogram_edges, int histogram_bins, int64_t* histograms, const int32_t* probe_ij, int n_probes,
-                          double* probe_speeds, vof_boxsize_stats* stats, double* v_x, double* v_y, double* speed, double* net_remodelling) {
-    return vary_boxsize_impl(c, SweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
-                                          histogram_bins, histograms, probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, true},
-                                         box_sizes, n_boxes, blur_weights, blur_radius, stats});
-}
+int vof_vary_boxsize_dev(VOF_BOXSIZE_ARGS) { return vary_boxsize_impl(c, VOF_BOXSIZE_REQ(false)); }
+int vof_vary_boxsize_host(VOF_BOXSIZE_ARGS) { return vary_boxsize_impl(c, VOF_BOXSIZE_REQ(true)); }
 
 // ---- blur sweep of the box flow (vary_blursize; vof_blursweep.hpp) -------------------------------------------------
 struct BlurSweepReq : SweepBase {
@@ -4330,31 +4325,20 @@ static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
     return 0;
 }
 
-int vof_vary_blursize_dev(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, const int32_t* blur_radii, int n_sigmas,
-                           int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
-                           const double* histogram_edges, int histogram_bins, int64_t* histograms, int angle_bins, int64_t* angle_histograms,
-                           double* weighted_angle_histograms, const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
-                           const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats, double* v_x, double* v_y,
-                           double* speed, double* net_remodelling) {
-    return vary_blursize_impl(c, BlurSweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
-                                               histogram_bins, histograms, probe_ij, n_probes, probe_speeds,
-                                               {v_x, v_y, speed, net_remodelling}, false},
-                                              blur_weights, blur_radii, n_sigmas, box_size, angle_bins, angle_histograms,
-                                              weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, stats});
-}
+#define VOF_BLURSIZE_ARGS                                                                                                             \
+    vof_ctx *c, const double *movie, int n_frames, const double *blur_weights, const int32_t *blur_radii, int n_sigmas, int box_size, \
+        double delta_x, double delta_t, int include_remodelling, int reference_quirks, const double *histogram_edges,                 \
+        int histogram_bins, int64_t *histograms, int angle_bins, int64_t *angle_histograms, double *weighted_angle_histograms,        \
+        const double *intensity_edges, int intensity_bins, int64_t *intensity_histograms, const int32_t *probe_ij, int n_probes,      \
+        double *probe_speeds, vof_blursize_stats *stats, double *v_x, double *v_y, double *speed, double *net_remodelling
+#define VOF_BLURSIZE_REQ(host)                                                                                                        \
+    BlurSweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges, histogram_bins,          \
+                  histograms, probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, host},                            \
+                 blur_weights, blur_radii, n_sigmas, box_size, angle_bins, angle_histograms, weighted_angle_histograms,               \
+                 intensity_edges, intensity_bins, intensity_histograms, stats}
 
-int vof_vary_blursize_host(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, const int32_t* blur_radii, int n_sigmas,
-                            int box_size, double delta_x, double delta_t, int include_remodelling, int reference_quirks,
-                            const double* histogram_edges, int histogram_bins, int64_t* histograms, int angle_bins, int64_t* angle_histograms,
-                            double* weighted_angle_histograms, const double* intensity_edges, int intensity_bins, int64_t* intensity_histograms,
-                            const int32_t* probe_ij, int n_probes, double* probe_speeds, vof_blursize_stats* stats, double* v_x, double* v_y,
-                            double* speed, double* net_remodelling) {
-    return vary_blursize_impl(c, BlurSweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges,
-                                               histogram_bins, histograms, probe_ij, n_probes, probe_speeds,
-                                               {v_x, v_y, speed, net_remodelling}, true},
-                                              blur_weights, blur_radii, n_sigmas, box_size, angle_bins, angle_histograms,
-                                              weighted_angle_histograms, intensity_edges, intensity_bins, intensity_histograms, stats});
-}
+int vof_vary_blursize_dev(VOF_BLURSIZE_ARGS) { return vary_blursize_impl(c, VOF_BLURSIZE_REQ(false)); }
+int vof_vary_blursize_host(VOF_BLURSIZE_ARGS) { return vary_blursize_impl(c, VOF_BLURSIZE_REQ(true)); }
 
 // ---- two channels of one movie: their box flows and the joint statistics (compare_channel_flows; vof_compare.hpp) --------
 struct CompareReq : SweepBase {           // movie, outs: channel a; the tail's two entries are the channels

@@ -96,6 +96,107 @@ def gaussian_taps(sigma, truncate=4.0):
     return phi / phi.sum()
 
 
+# ---------------------------------------------------------------------------------------------------------
+# Where the arrays of a call live.  An entry that takes ``output=`` is written once against it: ``_side(output, device)``, the checks,
+# a ``_device_context`` and one ``Solver`` method, which takes the _host or the _dev twin of the library by what it is handed.
+# ---------------------------------------------------------------------------------------------------------
+class _Side:
+    def blurred(self, stack, taps, solver):
+        """``stack`` (of ``frames``) blurred with ``taps`` through ``solver``, as a new stack."""
+        out = self.empty(stack.shape)
+        self.wait()
+        solver.blur(stack, out, stack.shape[0], taps)
+        return out
+
+    def analysed(self, movie, background, solver):
+        """The float64 stack ``conduct_optical_flow`` analyses: the movie, less ``background`` if one is given."""
+        return self.frames(movie) if background is None else self.subtract_background(movie, background, solver)
+
+
+class _HostSide(_Side):
+    """``output="numpy"``: host arrays, which the library stages."""
+
+    def frames(self, movie):
+        """``movie`` as a float64 contiguous array on this side (itself if it is one)."""
+        return np.require(np.asarray(movie), np.float64, "C")
+
+    def empty(self, shape, dtype="float64"):
+        return np.empty(shape, dtype=dtype)
+
+    def wait(self):
+        """The caller's stream is waited for before a native call reads its arrays: nothing to wait for here."""
+
+    def subtract_background(self, movie, background, solver):
+        """OF.py:195-198: ``movie - background``, taken in the movie's own dtype as the reference takes it, where the movie blurred with
+        sigma 10 exceeds ``background``, zero elsewhere."""
+        source = np.asarray(movie)
+        threshold = self.blurred(self.frames(source), gaussian_taps(10), solver)
+        analysed = np.zeros_like(threshold)
+        mask = threshold > background
+        analysed[mask] = source[mask] - background
+        return analysed
+
+    def untouched(self, movie, frames):
+        """``blurred_data`` of a movie nothing was applied to: the caller's own object, as in the reference."""
+        return movie
+
+    def box_flow_pairs(self, n_pairs):
+        """The pairs a context of the box flow, the sweeps and ``compare_channel_flows`` must hold: the library stages at most the
+        context's pairs at a time (at most 8 here); the kernels need no per-pair workspace."""
+        return max(1, min(int(n_pairs), 8))
+
+
+class _DeviceSide(_Side):
+    """``output="torch"``: float64 tensors on one device, which torch only allocates, converts and masks.  Nothing else imports torch,
+    so a numpy-only call never does."""
+
+    def __init__(self, device):
+        import torch
+        self.torch, self.dev = torch, torch.device("cuda", int(device))
+
+    def frames(self, movie):
+        return self.torch.as_tensor(movie).to(device=self.dev, dtype=self.torch.float64).contiguous()
+
+    def empty(self, shape, dtype="float64"):
+        return self.torch.empty(tuple(shape), dtype=getattr(self.torch, dtype), device=self.dev)
+
+    def wait(self):
+        self.torch.cuda.synchronize(self.dev)            # the library launches on its own stream
+
+    def subtract_background(self, movie, background, solver):
+        """The same on the float64 stack (for an integer movie the subtraction is therefore not the host's)."""
+        frames = self.frames(movie)
+        threshold = self.blurred(frames, gaussian_taps(10), solver)
+        return self.torch.where(threshold > background, frames - background, self.torch.zeros_like(frames))
+
+    def untouched(self, movie, frames):
+        return frames
+
+    def box_flow_pairs(self, n_pairs):
+        return 1
+
+
+def _side(output, device):
+    if output == "numpy":
+        return _HostSide()
+    if output == "torch":
+        return _DeviceSide(device)
+    raise ValueError("output must be 'numpy' or 'torch'")
+
+
+def _movie_shape(movie, min_frames=2, min_side=None):
+    """``(T, N_i, N_j)`` of a movie - an array, a tensor or anything ``np.asarray`` takes - with the checks the entries share, made
+    before the library is touched: three axes, ``min_frames`` frames (0: any number) and, for the preprocessing calls, ``min_side``."""
+    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
+    if len(shape) != 3:
+        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    if min_side is not None and (shape[0] < min_frames or min(shape[1:]) < min_side):
+        raise ValueError(f"movie needs at least one frame of at least {min_side}x{min_side} pixels")
+    if shape[0] < min_frames:
+        raise ValueError("movie needs at least two frames")
+    return shape
+
+
 FARNEBACK_ARGUMENTS = ("pyr_scale", "levels", "winsize", "iterations", "poly_n", "poly_sigma")
 FARNEBACK_MIN_SIDE = 16
 FARNEBACK_MAX_WINSIZE = 129          # FB_MAX_WINSIZE of csrc/vof_farneback.hpp: a row segment and its two margins live in LDS
@@ -275,44 +376,22 @@ def conduct_opencv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *
     ``window="box"`` (not in the reference's signature) runs OpenCV's default window instead, the one ``flags=0`` selects: the
     ``2 (winsize // 2) + 1`` box, summed as OpenCV sums it - two running sums in double - and divided by ``winsize**2``;
     it needs ``winsize >= 2``.  Any other value than ``"gaussian"`` or ``"box"`` is a ``ValueError``; ``flags`` stays a ``TypeError``."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
-    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
-    if len(shape) != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    a = _farneback_arguments(shape, kwargs)
+    side = _side(output, device)
+    a = _farneback_arguments(_movie_shape(movie, 0), kwargs)
     box = _farneback_window(window, a["winsize"])
-    if shape[0] < 2:
-        raise ValueError("movie needs at least two frames")
+    T, N_i, N_j = _movie_shape(movie, 2)
     name = _movie_dtype_name(movie)
     if name not in ("uint8", "float64"):
         raise ValueError(f"conduct_opencv_flow serves uint8 and float64 movies only (OpenCV converts each depth to float32 in its own way), "
                          f"not {name}: cast the movie")
-    T, N_i, N_j = shape
     plan = farneback_plan(N_i, N_j, a["pyr_scale"], a["levels"], a["winsize"], a["poly_n"], a["poly_sigma"])
-    velocity_scale = delta_x / delta_t
-    if output == "numpy":
-        source = np.asarray(movie)
-        frames = np.ascontiguousarray(source, dtype=np.float64)
-        with _device_context(N_i, N_j, 1, device) as solver:
-            first = frames if smoothing_sigma is None else blur_movie(frames, smoothing_sigma=smoothing_sigma, device=device, _solver=solver)
-            v_x, v_y, speed = solver.farneback_host(first[:-1], frames[1:], plan, a["iterations"], velocity_scale, box=box)
-        analysed = movie if smoothing_sigma is None else first
-    else:
-        import torch
-        dev = torch.device("cuda", int(device))
-        frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
-        v_x, v_y, speed = (torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(3))
-        with _device_context(N_i, N_j, 1, device) as solver:
-            first = frames
-            if smoothing_sigma is not None:
-                first = torch.empty_like(frames)
-                torch.cuda.synchronize(dev)
-                solver.blur_dev(frames, first, T, gaussian_taps(smoothing_sigma))
-            torch.cuda.synchronize(dev)                  # the library launches on its own stream
-            solver.farneback_dev(first[:-1], frames[1:], T - 1, plan, a["iterations"], velocity_scale, v_x, v_y, speed, box=box)
-        analysed = movie if smoothing_sigma is None else first
-    return dict(v_x=v_x, v_y=v_y, speed=speed, original_data=analysed, delta_x=delta_x, delta_t=delta_t)
+    frames = side.frames(movie)
+    v_x, v_y, speed = (side.empty((T - 1, N_i, N_j)) for _ in range(3))
+    with _device_context(N_i, N_j, 1, device) as solver:
+        first = frames if smoothing_sigma is None else side.blurred(frames, gaussian_taps(smoothing_sigma), solver)
+        side.wait()
+        solver.farneback(first[:-1], frames[1:], T - 1, plan, a["iterations"], delta_x / delta_t, v_x, v_y, speed, box=box)
+    return dict(v_x=v_x, v_y=v_y, speed=speed, original_data=movie if smoothing_sigma is None else first, delta_x=delta_x, delta_t=delta_t)
 
 
 def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags, *, device=0, output="numpy"):
@@ -327,8 +406,7 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
     ``prev`` and ``next`` are 2-D, of equal shape, both uint8 or both float64 (as ``conduct_opencv_flow``: OpenCV converts each
     depth to float32 in its own way).  Limits and error types are those of ``conduct_opencv_flow``; in addition the box window
     needs ``winsize >= 2``.  ``output="torch"``: the frames may be device tensors and the result stays on the device."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
+    side = _side(output, device)
     if isinstance(flags, bool) or int(flags) != flags:
         raise TypeError("flags must be an integer")
     flags = int(flags)
@@ -348,19 +426,14 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
                                                  poly_sigma=poly_sigma))
     box = _farneback_window("gaussian" if flags & OPTFLOW_FARNEBACK_GAUSSIAN else "box", a["winsize"])
     plan = farneback_plan(N_i, N_j, a["pyr_scale"], a["levels"], a["winsize"], a["poly_n"], a["poly_sigma"])
-    if output == "numpy":
-        first, second = (np.ascontiguousarray(np.asarray(f)[None], dtype=np.float64) for f in (prev, next))
-        with _device_context(N_i, N_j, 1, device) as solver:
-            v_x, v_y, _ = solver.farneback_host(first, second, plan, a["iterations"], 1.0, box=box)
-        return np.stack([v_x[0], v_y[0]], axis=2).astype(np.float32)         # exact: float32 values promoted, times 1.0
-    import torch
-    dev = torch.device("cuda", int(device))
-    first, second = (torch.as_tensor(f).to(device=dev, dtype=torch.float64).contiguous()[None] for f in (prev, next))
-    v_x, v_y, speed = (torch.empty((1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(3))
+    first, second = (side.frames(f)[None] for f in (prev, next))
+    v_x, v_y, speed = (side.empty((1, N_i, N_j)) for _ in range(3))
     with _device_context(N_i, N_j, 1, device) as solver:
-        torch.cuda.synchronize(dev)                      # the library launches on its own stream
-        solver.farneback_dev(first, second, 1, plan, a["iterations"], 1.0, v_x, v_y, speed, box=box)
-    return torch.stack([v_x[0], v_y[0]], dim=2).to(torch.float32)
+        side.wait()
+        solver.farneback(first, second, 1, plan, a["iterations"], 1.0, v_x, v_y, speed, box=box)
+    flow = side.empty((N_i, N_j, 2), "float32")                             # exact: float32 values promoted, times 1.0
+    flow[:, :, 0], flow[:, :, 1] = v_x[0], v_y[0]
+    return flow
 
 
 def blur_movie(movie, smoothing_sigma, device=0, _solver=None):
@@ -369,8 +442,7 @@ def blur_movie(movie, smoothing_sigma, device=0, _solver=None):
     sigma, mode='nearest', truncate=4.0)``: two 1-D correlations (axis 0, then axis 1) with clamped edges; the
     HIP kernel keeps scipy's summation order, so the result agrees with the host filter to rounding."""
     movie = np.asarray(movie)
-    if movie.ndim != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    _movie_shape(movie, 0)
     taps = gaussian_taps(smoothing_sigma)
     frames = np.ascontiguousarray(movie, dtype=np.float64)
     if _solver is not None:
@@ -385,33 +457,14 @@ THRESHOLD_MAX_WINDOW = 4095          # PP_MAX_WINDOW of csrc/vof_preprocess.hpp:
 THRESHOLD_MAX_ROW = 15360            # PP_MAX_ROW: a row's prefix sums live in LDS
 
 
-def _preprocess_shape(movie, output):
-    """``(T, N_i, N_j)`` of a movie the two preprocessing calls accept; the checks the two share, before the library is touched."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
-    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
-    if len(shape) != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    if shape[0] < 1 or shape[1] < 4 or shape[2] < 4:
-        raise ValueError("movie needs at least one frame of at least 4x4 pixels")
-    return shape
-
-
-def _run_preprocess(movie, shape, device, output, result_dtype, host_call, dev_call, out_shape=None):
-    """The frames as float64 on the side ``output`` names, through the cached context, to one of the native calls; the result
-    has the movie's shape unless ``out_shape`` names another."""
-    T, N_i, N_j = shape
-    if output == "numpy":
-        frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
-        with _device_context(N_i, N_j, 1, device) as solver:
-            return host_call(solver, frames)
-    import torch
-    dev = torch.device("cuda", int(device))
-    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
-    out = torch.empty(out_shape or shape, dtype=result_dtype(torch), device=dev)
-    with _device_context(N_i, N_j, 1, device) as solver:
-        torch.cuda.synchronize(dev)                  # the library launches on its own stream
-        dev_call(solver, frames, out, T)
+def _run_preprocess(movie, shape, device, side, call, dtype="float64", out_shape=None):
+    """The frames as float64 on ``side`` and an empty result of ``dtype`` - of the movie's shape unless ``out_shape`` names another -
+    through the cached context to ``call(solver, frames, out, T)``, one of the native calls; returns the result."""
+    frames = side.frames(movie)
+    out = side.empty(out_shape or shape, dtype)
+    with _device_context(shape[1], shape[2], 1, device) as solver:
+        side.wait()
+        call(solver, frames, out, shape[0])
     return out
 
 
@@ -432,7 +485,8 @@ def apply_adaptive_threshold(movie, window_size=51, threshold=0.0, *, device=0, 
     ``ValueError`` - the reference's ``uint8`` cast of such values is platform-dependent; and frames smaller than 4 x 4 pixels
     raise ``ValueError`` - the device context serves no smaller image.
     ``output="torch"``: ``movie`` may be a device tensor and the result is a ``torch.bool`` tensor on the device."""
-    shape = _preprocess_shape(movie, output)
+    side = _side(output, device)
+    shape = _movie_shape(movie, 1, 4)
     if int(window_size) != window_size or int(window_size) % 2 == 0 or int(window_size) <= 1:
         raise ValueError("window_size must be an odd integer > 1")
     if int(window_size) > THRESHOLD_MAX_WINDOW:
@@ -442,9 +496,7 @@ def apply_adaptive_threshold(movie, window_size=51, threshold=0.0, *, device=0, 
     if np.isnan(float(threshold)):
         raise ValueError("threshold is NaN")
     w, t = int(window_size), float(threshold)
-    return _run_preprocess(movie, shape, device, output, lambda torch: torch.bool,
-                           lambda solver, frames: solver.adaptive_threshold_host(frames, w, t),
-                           lambda solver, frames, out, T: solver.adaptive_threshold_dev(frames, out, T, w, t))
+    return _run_preprocess(movie, shape, device, side, lambda solver, frames, out, T: solver.adaptive_threshold(frames, out, T, w, t), "bool")
 
 
 def clahe_tile_grid(shape, tile_number):
@@ -482,14 +534,13 @@ def apply_clahe(movie, clipLimit=50000, tile_number=10, *, device=0, output="num
     or a value outside ``[0, 65536)``, which the reference wraps, and for frames smaller than 4 x 4 pixels, which the device
     context does not serve.  Device memory: ``65536 * 6`` bytes per tile and frame in flight.
     ``output="torch"``: ``movie`` may be a device tensor and the result is a float64 tensor on the device."""
-    shape = _preprocess_shape(movie, output)
+    side = _side(output, device)
+    shape = _movie_shape(movie, 1, 4)
     tiles_x, tiles_y = clahe_tile_grid(shape, tile_number)
     if np.isnan(float(clipLimit)):
         raise ValueError("clipLimit is NaN")
     clip = float(clipLimit)
-    return _run_preprocess(movie, shape, device, output, lambda torch: torch.float64,
-                           lambda solver, frames: solver.clahe_host(frames, clip, tiles_x, tiles_y),
-                           lambda solver, frames, out, T: solver.clahe_dev(frames, out, T, clip, tiles_x, tiles_y))
+    return _run_preprocess(movie, shape, device, side, lambda solver, frames, out, T: solver.clahe(frames, out, T, clip, tiles_x, tiles_y))
 
 
 def _movie_dtype_name(movie):
@@ -521,7 +572,8 @@ def downsample_movie(movie, resolution, *, device=0, output="numpy"):
     enlarged, and that path is not built - and for frames smaller than 4 x 4 pixels, which the device context does not serve.
     ``output="torch"``: ``movie`` may be a device tensor and the result is a float64 tensor on the device, ready for
     ``variational_optical_flow(..., output="torch")``."""
-    shape = _preprocess_shape(movie, output)
+    side = _side(output, device)
+    shape = _movie_shape(movie, 1, 4)
     name = _movie_dtype_name(movie)
     if name not in ("uint8", "float64"):
         raise ValueError(f"downsample_movie serves uint8 and float64 movies only (OpenCV's arithmetic differs by depth), not {name}: "
@@ -534,9 +586,7 @@ def downsample_movie(movie, resolution, *, device=0, output="numpy"):
         raise ValueError(f"resolution {n_i} x {n_j} does not downsample frames of {shape[1]} x {shape[2]} pixels: "
                          "1 <= n_i <= N_i and 1 <= n_j <= N_j are required")
     arithmetic = _native.RESIZE_U8 if name == "uint8" else _native.RESIZE_F64
-    return _run_preprocess(movie, shape, device, output, lambda torch: torch.float64,
-                           lambda solver, frames: solver.resize_area_host(frames, n_i, n_j, arithmetic),
-                           lambda solver, frames, out, T: solver.resize_area_dev(frames, out, T, n_i, n_j, arithmetic),
+    return _run_preprocess(movie, shape, device, side, lambda solver, frames, out, T: solver.resize_area(frames, out, T, n_i, n_j, arithmetic),
                            out_shape=(shape[0], n_i, n_j))
 
 
@@ -710,22 +760,18 @@ def variational_optical_flow(movie,
         torch tensor already on the device and every array of the result stays on the device as a float64 torch
         tensor - blur, solve and epilogue without PCIe traffic, see ``subsample_velocities_for_visualisation``).
     """
+    side = _side(output, device)
+    direct_fallback = bool(use_direct_solver and preconditioner is None)     # not an explicit preconditioner="direct"
     if output == "torch":
-        return _variational_optical_flow_device(movie, smoothing_sigma, device, max_pairs_in_flight, verbose, return_stats,
+        return _variational_optical_flow_device(side, movie, smoothing_sigma, device, max_pairs_in_flight, verbose, return_stats,
                                                 reference_quirks, _solver_params(
                                                     speed_alpha, remodelling_alpha, delta_x, delta_t, initial_v_x, initial_v_y,
                                                     initial_remodelling, use_direct_solver, rtol, max_iterations,
                                                     reference_quirks, coarse_precision, vcycle_precision, multigrid_sweeps,
                                                     w_cycle_level, krylov_method, gmres_restart, warm_start_stride, preconditioner),
-                                                delta_x, delta_t, direct_fallback=bool(use_direct_solver and preconditioner is None))
-    if output != "numpy":
-        raise ValueError("output must be 'numpy' or 'torch'")
+                                                delta_x, delta_t, direct_fallback)
     source = np.asarray(movie)
-    if source.ndim != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = source.shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
+    T, N_i, N_j = _movie_shape(source, 2)
     # OF.py:769: the reference works on (and returns, as 'original_data') a float64 COPY of the movie.  A stack that already is
     # float64 and contiguous is only read by the solver, so the copy the result needs is made WHILE the solve runs (46 ms of a
     # 0.39-s call at 1024 x 1024 x 256); anything else is converted first, as the reference does
@@ -748,16 +794,11 @@ def variational_optical_flow(movie,
         with (contextlib.nullcontext(_solver) if _solver is not None
               else _device_context(N_i, N_j, max_pairs_in_flight, device, exact)) as solver:
             if smoothing_sigma is not None:                                 # OF.py:770-773
-                movie_to_analyse = blur_movie(movie_in, smoothing_sigma=smoothing_sigma, device=device, _solver=solver)
+                movie_to_analyse = side.blurred(side.frames(movie_in), gaussian_taps(smoothing_sigma), solver)
             else:
                 movie_to_analyse = movie_in
-            try:
-                v_x, v_y, remodelling, speed, stats = solver.solve_host(np.ascontiguousarray(movie_to_analyse), params)
-            except _native.VofError as exc:
-                if not (use_direct_solver and preconditioner is None and _direct_unavailable(exc)):
-                    raise
-                params.preconditioner = 2        # too large for the direct preconditioner: multigrid to the same tight tolerance
-                v_x, v_y, remodelling, speed, stats = solver.solve_host(np.ascontiguousarray(movie_to_analyse), params)
+            out = [side.empty((T - 1, N_i, N_j)) for _ in range(4)]
+            stats = _solve(solver, side.frames(movie_to_analyse), params, out, direct_fallback)     # (the copy keeps a Fortran order)
     finally:
         if copy_done is not None:
             copy_done()
@@ -771,116 +812,81 @@ def variational_optical_flow(movie,
                   f"{stats['relative_residual'][k]:.3e}, converged {bool(stats['converged'][k])}")
         if not stats["converged"].all():
             print("the solver has not actually converged, the result will be incorrect or inaccurate")
+    return _variational_result(out, stats, movie, movie_to_analyse, delta_x, delta_t, reference_quirks, return_stats)
 
-    result = dict()
-    result["v_x"] = v_x
-    result["v_y"] = v_y
-    result["speed"] = speed
-    result["remodelling"] = remodelling
-    result["original_data"] = movie
-    result["delta_x"] = delta_x
-    result["delta_t"] = delta_t
-    result["blurred_data"] = movie_to_analyse
-    result["converged"] = bool(stats["converged"][-1])                  # OF.py:1202: last pair only
-    result["L1_functional"] = float(np.sum(stats["L1_functional"]))
-    result["remodelling_functional"] = float(np.sum(stats["remodelling_functional"]))
+
+def _solve(solver, movie, params, out, direct_fallback):
+    """The solve of a float64 stack into the four stacks ``out = [v_x, v_y, remodelling, speed]`` on its side; returns the per-pair
+    records.  ``direct_fallback``: a stack too large for the direct preconditioner is solved by multigrid to the same tight tolerance."""
+    try:
+        return solver.solve(movie, movie.shape[0], params, *out)
+    except _native.VofError as exc:
+        if not (direct_fallback and _direct_unavailable(exc)):
+            raise
+        params.preconditioner = 2
+        return solver.solve(movie, movie.shape[0], params, *out)
+
+
+def _variational_result(out, stats, movie, movie_to_analyse, delta_x, delta_t, reference_quirks, return_stats):
+    """The reference's result dict (OF.py:1193-1205) from the four stacks ``_solve`` filled and its per-pair records."""
+    result = dict(v_x=out[0], v_y=out[1], speed=out[3], remodelling=out[2], original_data=movie, delta_x=delta_x, delta_t=delta_t,
+                  blurred_data=movie_to_analyse, converged=bool(stats["converged"][-1]),                  # OF.py:1202: last pair only
+                  L1_functional=float(np.sum(stats["L1_functional"])),
+                  remodelling_functional=float(np.sum(stats["remodelling_functional"])))
     # OF.py:1205 stores the remodelling sum under 'speed_functional'
-    result["speed_functional"] = (result["remodelling_functional"] if reference_quirks
-                                  else float(np.sum(stats["speed_functional"])))
+    result["speed_functional"] = result["remodelling_functional"] if reference_quirks else float(np.sum(stats["speed_functional"]))
     if return_stats:
         result["stats"] = stats
     return result
 
 
-def _variational_optical_flow_device(movie, smoothing_sigma, device, max_pairs_in_flight, verbose, return_stats,
+def _variational_optical_flow_device(side, movie, smoothing_sigma, device, max_pairs_in_flight, verbose, return_stats,
                                      reference_quirks, params, delta_x, delta_t, direct_fallback=False):
-    """``output="torch"`` branch of ``variational_optical_flow``: torch only allocates the device arrays."""
-    import torch
-    dev = torch.device("cuda", int(device))
-    movie = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()      # OF.py:769
-    if movie.ndim != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = movie.shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
+    """``output="torch"`` branch of ``variational_optical_flow``, which differs from the host branch before the solve: no float64 copy
+    of the caller's movie, a batch sized without staging buffers, and one wait for the caller's stream ahead of blur and solve."""
+    movie = side.frames(movie)                                                            # OF.py:769
+    T, N_i, N_j = _movie_shape(movie, 2)
     exact = max_pairs_in_flight is not None
     if max_pairs_in_flight is None:
         # device-resident call: no staging buffers, and what is free now is free of the caller's tensors already
         max_pairs_in_flight = choose_pairs_in_flight(N_i, N_j, T - 1, int(device), memory_fraction=0.8, params=params, staging=False)
-    out = [torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4)]
-    torch.cuda.synchronize(dev)          # the library launches on its own stream
+    out = [side.empty((T - 1, N_i, N_j)) for _ in range(4)]
+    side.wait()
     with _device_context(N_i, N_j, max_pairs_in_flight, device, exact) as solver:
+        movie_to_analyse = movie
         if smoothing_sigma is not None:                                                  # OF.py:770-773
-            taps = gaussian_taps(smoothing_sigma)
-            movie_to_analyse = torch.empty_like(movie)
-            solver.blur_dev(movie, movie_to_analyse, T, taps)
-        else:
-            movie_to_analyse = movie
-        try:
-            stats = solver.solve_dev(movie_to_analyse, T, params, out[0], out[1], out[2], out[3])
-        except _native.VofError as exc:
-            # same rule as the host path: only use_direct_solver=True (not an explicit preconditioner="direct") may fall back
-            if not (direct_fallback and _direct_unavailable(exc)):
-                raise
-            params.preconditioner = 2
-            stats = solver.solve_dev(movie_to_analyse, T, params, out[0], out[1], out[2], out[3])
+            movie_to_analyse = side.empty(movie.shape)
+            solver.blur(movie, movie_to_analyse, T, gaussian_taps(smoothing_sigma))
+        stats = _solve(solver, movie_to_analyse, params, out, direct_fallback)
     if verbose:
         print(f"iterations {stats['iterations'].tolist()}, converged {stats['converged'].astype(bool).tolist()}")
-    result = dict(v_x=out[0], v_y=out[1], speed=out[3], remodelling=out[2], original_data=movie, delta_x=delta_x,
-                  delta_t=delta_t, blurred_data=movie_to_analyse, converged=bool(stats["converged"][-1]),
-                  L1_functional=float(np.sum(stats["L1_functional"])),
-                  remodelling_functional=float(np.sum(stats["remodelling_functional"])))
-    result["speed_functional"] = (result["remodelling_functional"] if reference_quirks          # OF.py:1205
-                                  else float(np.sum(stats["speed_functional"])))
-    if return_stats:
-        result["stats"] = stats
-    return result
+    return _variational_result(out, stats, movie, movie_to_analyse, delta_x, delta_t, reference_quirks, return_stats)
 
 
 # ---------------------------------------------------------------------------------------------------------
 # Box least-squares flow (Vig et al. 2016): the reference's other estimator, OF.py:24-218.
 # ---------------------------------------------------------------------------------------------------------
-def _box_flow_context(n_i, n_j, n_pairs, device):
-    # for the box flow, the sweeps and compare_channel_flows: on host arrays they stage at most the context's pairs at a time
-    # (at most 8 here); the kernels need no per-pair workspace.  The Liu-Shen flow chunks on its own and asks for one pair.
-    return _device_context(n_i, n_j, max(1, min(int(n_pairs), 8)), device)
-
-
-def _subtract_background(source, background, device, solver):
-    """OF.py:195-198 on host memory: ``source - background`` where the movie blurred with sigma 10 exceeds ``background``, zero
-    elsewhere."""
-    movie_for_thresholding = blur_movie(source, smoothing_sigma=10, device=device, _solver=solver)
-    movie_to_analyse = np.zeros_like(movie_for_thresholding)
-    mask = movie_for_thresholding > background
-    movie_to_analyse[mask] = source[mask] - background
-    return movie_to_analyse
-
-
-def _subtract_background_device(frames, background, solver):
-    """The same on a float64 device tensor."""
-    import torch
-    blurred = torch.empty_like(frames)
-    torch.cuda.synchronize(frames.device)          # the library launches on its own stream
-    solver.blur_dev(frames, blurred, frames.shape[0], gaussian_taps(10))
-    return torch.where(blurred > background, frames - background, torch.zeros_like(frames))
-
-
 def conduct_optical_flow_jit(movie, box_size=15, delta_x=1.0, delta_t=1.0, include_remodelling=False, *,
                              reference_quirks=True, device=0):
     """Windowed least-squares flow of every frame pair on the GPU; arguments and the returned 4-tuple
     ``(v_x, v_y, speed, net_remodelling)`` as OF.py:24-157 (float64 ``(T-1, N_i, N_j)``; ``net_remodelling`` all zero
     without ``include_remodelling``).  Field ``k`` is computed from frames ``k`` and ``k + 1``.  See ``conduct_optical_flow``
     for ``reference_quirks``."""
-    frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
-    if frames.ndim != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = frames.shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
+    side = _HostSide()
+    T, N_i, N_j = _movie_shape(movie, 2)
     if int(box_size) < 1:
         raise ValueError("box_size must be >= 1")
-    with _box_flow_context(N_i, N_j, T - 1, device) as solver:
-        return solver.box_flow_host(frames, int(box_size), delta_x, delta_t, include_remodelling, reference_quirks)
+    with _device_context(N_i, N_j, side.box_flow_pairs(T - 1), device) as solver:
+        return solver.box_flow_host(side.frames(movie), int(box_size), delta_x, delta_t, include_remodelling, reference_quirks)
+
+
+def _box_flow_result(fields, movie, analysed, delta_x, delta_t, include_remodelling):
+    """The result dict of the box flow (OF.py:205-218) from its field stacks ``[v_x, v_y, speed[, net_remodelling]]``."""
+    result = dict(v_x=fields[0], v_y=fields[1], speed=fields[2], original_data=movie, delta_x=delta_x, delta_t=delta_t,
+                  blurred_data=analysed)
+    if include_remodelling:
+        result["net_remodelling"] = fields[3]
+    return result
 
 
 def conduct_optical_flow(movie, boxsize=15, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, background=None,
@@ -905,67 +911,21 @@ def conduct_optical_flow(movie, boxsize=15, delta_x=1.0, delta_t=1.0, smoothing_
     False: the window is clamped with ``N_j``, ``n`` is the number of pixels in the window, ``speed`` is filled and such
     pixels are NaN), ``device``, ``output`` ("numpy", or "torch": ``movie`` may be a device tensor and every array of the
     result stays on the device as a float64 tensor; ``blurred_data`` is then float64 even for an integer movie)."""
-    if output == "torch":
-        return _conduct_optical_flow_device(movie, boxsize, delta_x, delta_t, smoothing_sigma, background,
-                                            include_remodelling, reference_quirks, device)
-    if output != "numpy":
-        raise ValueError("output must be 'numpy' or 'torch'")
-    source = np.asarray(movie)
-    if source.ndim != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = source.shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
+    side = _side(output, device)
+    T, N_i, N_j = _movie_shape(movie, 2)
     if int(boxsize) < 1:
         raise ValueError("boxsize must be >= 1")
-    with _box_flow_context(N_i, N_j, T - 1, device) as solver:
-        movie_to_analyse = source if background is None else _subtract_background(source, background, device, solver)
+    with _device_context(N_i, N_j, side.box_flow_pairs(T - 1), device) as solver:
+        analysed = side.analysed(movie, background, solver)
         if smoothing_sigma is not None:                                     # OF.py:202-203
-            movie_to_analyse = blur_movie(movie_to_analyse, smoothing_sigma=smoothing_sigma, device=device, _solver=solver)
-        v_x, v_y, speed, net_remodelling = solver.box_flow_host(movie_to_analyse, int(boxsize), delta_x, delta_t,
-                                                                include_remodelling, reference_quirks)
-    result = dict()
-    result["v_x"] = v_x
-    result["v_y"] = v_y
-    result["speed"] = speed
-    result["original_data"] = movie
-    result["delta_x"] = delta_x
-    result["delta_t"] = delta_t
-    result["blurred_data"] = movie if (background is None and smoothing_sigma is None) else movie_to_analyse
-    if include_remodelling:
-        result["net_remodelling"] = net_remodelling
-    return result
-
-
-def _conduct_optical_flow_device(movie, boxsize, delta_x, delta_t, smoothing_sigma, background, include_remodelling,
-                                 reference_quirks, device):
-    """``output="torch"`` branch of ``conduct_optical_flow``: torch only allocates and masks the device arrays."""
-    import torch
-    dev = torch.device("cuda", int(device))
-    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
-    if frames.ndim != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = frames.shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
-    if int(boxsize) < 1:
-        raise ValueError("boxsize must be >= 1")
-    out = [torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4 if include_remodelling else 3)]
-    with _box_flow_context(N_i, N_j, 1, device) as solver:
-        movie_to_analyse = frames if background is None else _subtract_background_device(frames, background, solver)
-        if smoothing_sigma is not None:
-            blurred = torch.empty_like(frames)
-            torch.cuda.synchronize(dev)
-            solver.blur_dev(movie_to_analyse, blurred, T, gaussian_taps(smoothing_sigma))
-            movie_to_analyse = blurred
-        torch.cuda.synchronize(dev)
-        solver.box_flow_dev(movie_to_analyse, T, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks,
-                            out[0], out[1], out[2], out[3] if include_remodelling else None)
-    result = dict(v_x=out[0], v_y=out[1], speed=out[2],
-                  original_data=movie, delta_x=delta_x, delta_t=delta_t, blurred_data=movie_to_analyse)
-    if include_remodelling:
-        result["net_remodelling"] = out[3]
-    return result
+            analysed = side.blurred(analysed, gaussian_taps(smoothing_sigma), solver)
+        # without include_remodelling the _dev twin is handed no fourth stack; the _host twin is, and zero-fills it, as it always was
+        fields = [side.empty((T - 1, N_i, N_j)) for _ in range(4 if include_remodelling or output == "numpy" else 3)]
+        side.wait()
+        solver.box_flow(analysed, T, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks, *fields)
+    if background is None and smoothing_sigma is None:
+        analysed = side.untouched(movie, analysed)
+    return _box_flow_result(fields, movie, analysed, delta_x, delta_t, include_remodelling)
 
 
 def _sweep_edges(name, bins, value_range):
@@ -980,15 +940,6 @@ def _sweep_edges(name, bins, value_range):
     return np.linspace(lo, hi, int(bins) + 1, endpoint=True, dtype=np.float64)
 
 
-def _sweep_shape(movie):
-    shape = tuple(movie.shape) if hasattr(movie, "shape") else np.asarray(movie).shape
-    if len(shape) != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    if shape[0] < 2:
-        raise ValueError("movie needs at least two frames")
-    return shape
-
-
 def _sweep_probes(probe_locations, N_i, N_j):
     if probe_locations is None:
         return None
@@ -1001,32 +952,24 @@ def _sweep_probes(probe_locations, N_i, N_j):
     return probes
 
 
-def _run_sweep(name, native, movie, n, background, include_remodelling, probe_locations, return_fields, device, output):
-    """What the sweeps of the box flow share around their native call ``Solver.<name>_host`` / ``_dev``: the movie goes up (torch) or
-    becomes an array, ``background`` is applied as in ``conduct_optical_flow`` and the stacks of the ``n`` entries are allocated.
-    ``native(entry, head, probes, tail)`` calls ``entry`` with the arguments the two entries share between ``head`` and ``tail``.
-    Returns the summaries of the entry and the list of field stacks (None without ``return_fields``)."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
-    T, N_i, N_j = _sweep_shape(movie)
+FIELD_NAMES = ("v_x", "v_y", "speed", "net_remodelling")
+
+
+def _run_sweep(name, args, movie, n, background, include_remodelling, probe_locations, return_fields, device, output):
+    """What the sweeps of the box flow share around their native call ``Solver.<name>``: the movie becomes a float64 stack on the side
+    ``output`` names, ``background`` is applied as in ``conduct_optical_flow`` and the stacks of the ``n`` entries are allocated.
+    ``args`` are the arguments of the call between the frame count and the probe locations.  Returns the summaries of the call and
+    the list of field stacks (None without ``return_fields``)."""
+    side = _side(output, device)
+    T, N_i, N_j = _movie_shape(movie, 2)
     probes = _sweep_probes(probe_locations, N_i, N_j)
-    if output == "numpy":
-        source = np.asarray(movie)
-        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
-            movie_to_analyse = source if background is None else _subtract_background(source, background, device, solver)
-            *summaries, fields = native(getattr(solver, name + "_host"), (movie_to_analyse,), probes, (return_fields,))
-        return summaries, fields
-    import torch
-    dev = torch.device("cuda", int(device))
-    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
     fields = None
-    with _box_flow_context(N_i, N_j, 1, device) as solver:
-        if background is not None:
-            frames = _subtract_background_device(frames, background, solver)
+    with _device_context(N_i, N_j, side.box_flow_pairs(T - 1), device) as solver:
+        analysed = side.analysed(movie, background, solver)
         if return_fields:
-            fields = [torch.empty((n, T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4 if include_remodelling else 3)]
-        torch.cuda.synchronize(dev)
-        summaries = native(getattr(solver, name + "_dev"), (frames, T), probes, fields or ())
+            fields = [side.empty((n, T - 1, N_i, N_j)) for _ in range(4 if include_remodelling else 3)]
+        side.wait()
+        summaries = getattr(solver, name)(analysed, T, *args, probe_locations=probes, **dict(zip(FIELD_NAMES, fields or ())))
     return summaries, fields
 
 
@@ -1086,12 +1029,8 @@ def vary_boxsize(movie, boxsizes=np.arange(5, 150, 2), delta_x=1.0, delta_t=1.0,
         raise ValueError("every box size must be >= 1")
     edges = _sweep_edges("histogram", histogram_bins, histogram_range)
     taps = None if smoothing_sigma is None else gaussian_taps(smoothing_sigma)
-
-    def native(entry, head, probes, tail):
-        return entry(*head, boxes, delta_x, delta_t, include_remodelling, reference_quirks, taps, edges, probes, *tail)
-
-    summaries, fields = _run_sweep("vary_boxsize", native, movie, len(boxes), background, include_remodelling, probe_locations,
-                                   return_fields, device, output)
+    summaries, fields = _run_sweep("vary_boxsize", (boxes, delta_x, delta_t, include_remodelling, reference_quirks, taps, edges), movie,
+                                   len(boxes), background, include_remodelling, probe_locations, return_fields, device, output)
     return _sweep_result({"boxsizes": np.asarray(boxes)}, summaries, fields, {}, edges, include_remodelling, delta_x, delta_t, filename)
 
 
@@ -1136,12 +1075,8 @@ def vary_blursize(movie, blursizes=np.arange(0.5, 15, 0.1), boxsize=21, delta_x=
     if angle_bins is not None and not 1 <= int(angle_bins) <= 128:
         raise ValueError("angle_bins must be 1 .. 128")
     taps = [gaussian_taps(s) for s in sigmas]
-
-    def native(entry, head, probes, tail):
-        return entry(*head, taps, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks, edges, angle_bins,
-                     intensity_edges, probes, *tail)
-
-    summaries, fields = _run_sweep("vary_blursize", native, movie, len(taps), background, include_remodelling, probe_locations,
+    args = (taps, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks, edges, angle_bins, intensity_edges)
+    summaries, fields = _run_sweep("vary_blursize", args, movie, len(taps), background, include_remodelling, probe_locations,
                                    return_fields, device, output)
     own = dict()
     if angle_bins is not None:
@@ -1168,11 +1103,9 @@ def _channel_pair(name, value):
 
 def _compare_arguments(movie_a, movie_b, boxsize, smoothing_sigma, background, histogram_bins, histogram_range, angle_bins,
                        relative_angle_bins, joint_speed_bins, joint_speed_ranges, output):
-    """The argument checks of ``compare_channel_flows``, all before the library is touched; returns the shape, the per-channel
-    sigmas and backgrounds, the speed edges and the pair of joint speed edges (or None)."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
-    shape = _sweep_shape(movie_a)
+    """The argument checks of ``compare_channel_flows`` (``output`` is checked by its ``_side``), all before the library is touched;
+    returns the shape, the per-channel sigmas and backgrounds, the speed edges and the pair of joint speed edges (or None)."""
+    shape = _movie_shape(movie_a, 2)
     if tuple(movie_b.shape if hasattr(movie_b, "shape") else np.asarray(movie_b).shape) != shape:
         raise ValueError("movie_a and movie_b must have the same shape (frames, x, y)")
     if int(boxsize) < 1:
@@ -1239,40 +1172,22 @@ def compare_channel_flows(movie_a, movie_b, boxsize=31, delta_x=1.0, delta_t=1.0
     them; without it no full-size field stack exists on either side beyond the pairs in flight.
     ``filename``: the dict is saved with ``np.save``.  ``output="torch"``: the movies may be device tensors and the arrays of ``a``
     and ``b`` stay on the device as float64 tensors; the summaries are numpy arrays in both modes."""
+    side = _side(output, device)
     (T, N_i, N_j), sigmas, backgrounds, edges, joint_edges = _compare_arguments(
         movie_a, movie_b, boxsize, smoothing_sigma, background, histogram_bins, histogram_range, angle_bins, relative_angle_bins,
         joint_speed_bins, joint_speed_ranges, output)
     taps = [None if s is None else gaussian_taps(s) for s in sigmas]
-    args = (int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks, taps[0], taps[1], edges, angle_bins,
-            int(relative_angle_bins), joint_edges, joint_speed_min_b)
-    movies, analysed, blurred, fields = (movie_a, movie_b), [None, None], [None, None], None
-    if output == "numpy":
-        with _box_flow_context(N_i, N_j, T - 1, device) as solver:
-            for ch in range(2):
-                source = np.asarray(movies[ch])
-                analysed[ch] = source if backgrounds[ch] is None else _subtract_background(source, backgrounds[ch], device, solver)
-            *summaries, fields = solver.compare_flows_host(analysed[0], analysed[1], *args, return_fields)
-            if return_fields:
-                blurred = [analysed[ch] if taps[ch] is None else solver.blur_host(analysed[ch], taps[ch]) for ch in range(2)]
-    else:
-        import torch
-        dev = torch.device("cuda", int(device))
-        with _box_flow_context(N_i, N_j, 1, device) as solver:
-            for ch in range(2):
-                frames = torch.as_tensor(movies[ch]).to(device=dev, dtype=torch.float64).contiguous()
-                analysed[ch] = frames if backgrounds[ch] is None else _subtract_background_device(frames, backgrounds[ch], solver)
-            if return_fields:
-                fields = [[torch.empty((T - 1, N_i, N_j), dtype=torch.float64, device=dev) for _ in range(4 if include_remodelling else 3)]
-                          for _ in range(2)]
-                for ch in range(2):
-                    blurred[ch] = analysed[ch]
-                    if taps[ch] is not None:
-                        blurred[ch] = torch.empty_like(analysed[ch])
-                        torch.cuda.synchronize(dev)
-                        solver.blur_dev(analysed[ch], blurred[ch], T, taps[ch])
-            torch.cuda.synchronize(dev)                                    # the library launches on its own stream
-            padded = [None if fields is None else fields[ch] + [None] * (4 - len(fields[ch])) for ch in range(2)]
-            summaries = solver.compare_flows_dev(analysed[0], analysed[1], T, *args, padded[0], padded[1])
+    movies, fields = (movie_a, movie_b), (None, None)
+    with _device_context(N_i, N_j, side.box_flow_pairs(T - 1), device) as solver:
+        analysed = [side.analysed(movies[ch], backgrounds[ch], solver) for ch in range(2)]
+        if return_fields:
+            fields = [[side.empty((T - 1, N_i, N_j)) for _ in range(4 if include_remodelling else 3)] for _ in range(2)]
+        side.wait()
+        summaries = solver.compare_flows(analysed[0], analysed[1], T, int(boxsize), delta_x, delta_t, include_remodelling, reference_quirks,
+                                         taps[0], taps[1], edges, angle_bins, int(relative_angle_bins), joint_edges, joint_speed_min_b,
+                                         *fields)
+        if return_fields:                                                  # the blurred stacks exist only for the result dicts
+            blurred = [analysed[ch] if taps[ch] is None else side.blurred(analysed[ch], taps[ch], solver) for ch in range(2)]
     rec, hist, angle_hist, weighted_angle_hist, theta_hist, weighted_theta_hist, joint_hist, joint_counts = summaries
     own = dict()
     if angle_bins is not None:
@@ -1291,12 +1206,9 @@ def compare_channel_flows(movie_a, movie_b, boxsize=31, delta_x=1.0, delta_t=1.0
     result = _sweep_result({}, (rec, hist, None), None, own, edges, include_remodelling, delta_x, delta_t, None)
     if return_fields:
         for ch, key in enumerate("ab"):
-            one = dict(v_x=fields[ch][0], v_y=fields[ch][1], speed=fields[ch][2], original_data=movies[ch], delta_x=delta_x,
-                       delta_t=delta_t,
-                       blurred_data=movies[ch] if (backgrounds[ch] is None and taps[ch] is None) else blurred[ch])
-            if include_remodelling:
-                one["net_remodelling"] = fields[ch][3]
-            result[key] = one
+            untouched = backgrounds[ch] is None and taps[ch] is None
+            result[key] = _box_flow_result(fields[ch], movies[ch], movies[ch] if untouched else blurred[ch], delta_x, delta_t,
+                                           include_remodelling)
     if filename is not None:
         np.save(filename, result)
     return result
@@ -1388,14 +1300,11 @@ def filter_PIV_flow_result(flow_result, intensity_threshold=10, speed_threshold=
         raise ValueError("a threshold is NaN")
     limit = float(FILTER_SPEED_LIMIT if reference_quirks else speed_threshold)
     taps = gaussian_taps(FILTER_BLUR_SIGMA)
-    if on_device:
-        import torch
-        dev, index = _tensor_device(fields + [movie], device)
-        frames = movie[:P].to(dtype=torch.float64).contiguous()
-        torch.cuda.synchronize(dev)
-    else:
-        index, frames = device, np.ascontiguousarray(movie[:P], dtype=np.float64)
+    index = _tensor_device(fields + [movie], device)[1] if on_device else device
+    side = _side("torch" if on_device else "numpy", index)
+    frames = side.frames(movie[:P])
     with _device_context(N_i, N_j, 1, index) as solver:
+        side.wait()
         solver.flow_filter(frames, taps, P, float(intensity_threshold), limit, not reference_quirks, *fields)
 
 
@@ -1571,41 +1480,23 @@ def liu_shen_optical_flow_jit(movie, delta_x=1.0, delta_t=1.0, alpha=100, remode
 
     Keyword-only extras: ``device``, ``output`` ("numpy", or "torch": ``movie`` and the initial fields may be device
     tensors and the four arrays come back as float64 device tensors)."""
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
-    shape = tuple(movie.shape)
-    if len(shape) != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
+    side = _side(output, device)
+    T, N_i, N_j = _movie_shape(movie, 2)
     if min(N_i, N_j) < 3:
         raise ValueError("the Liu-Shen flow needs image sides of at least 3")
     if int(max_iterations) < 1:
         raise ValueError("max_iterations must be >= 1")
-    initial = (initial_v_x, initial_v_y, initial_remodelling)
-    if output == "numpy":
-        frames = np.ascontiguousarray(np.asarray(movie), dtype=np.float64)
-        with _device_context(N_i, N_j, 1, device) as solver:
-            out = solver.liu_shen_host(frames, delta_x, delta_t, alpha, *initial, int(max_iterations))
-        return out + (int(max_iterations) - 1,)
-    import torch
-    dev = torch.device("cuda", int(device))
-    frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
     pairs = (T - 1, N_i, N_j)
+    frames = side.frames(movie)
     # a Python float must not pass through torch's default float32
-    fields = [(f if isinstance(f, torch.Tensor) else torch.as_tensor(np.asarray(f, dtype=np.float64))).to(device=dev, dtype=torch.float64)
-              for f in initial]
-    kind = _native.Solver._initial_kind(fields, pairs)
-    if kind == 0:
-        fields = [float(f) for f in fields]
-    else:
-        fields = [f.expand(pairs[1:] if kind == 1 else pairs).contiguous() for f in fields]
-    out = [torch.empty(pairs, dtype=torch.float64, device=dev) for _ in range(4)]
-    with _box_flow_context(N_i, N_j, 1, device) as solver:
-        torch.cuda.synchronize(dev)          # the library launches on its own stream
-        solver.liu_shen_dev(frames, T, delta_x, delta_t, alpha, *fields, kind, int(max_iterations), *out)
-    return tuple(out) + (int(max_iterations) - 1,)
+    initial = [side.frames(f if _is_device_tensor(f) else np.asarray(f, dtype=np.float64))
+               for f in (initial_v_x, initial_v_y, initial_remodelling)]
+    initial, kind = _native.liu_shen_initial(initial, pairs)
+    out = [side.empty(pairs) for _ in range(4)]
+    with _device_context(N_i, N_j, 1, device) as solver:
+        side.wait()
+        solver.liu_shen(frames, T, delta_x, delta_t, alpha, *initial, kind, int(max_iterations), *out)
+    return (*out, int(max_iterations) - 1)
 
 
 def conduct_variational_optical_flow_deprecated(movie, delta_x=1.0, delta_t=1.0, speed_alpha=1.0, remodelling_alpha=1000.0,
@@ -1633,22 +1524,15 @@ def conduct_variational_optical_flow_deprecated(movie, delta_x=1.0, delta_t=1.0,
     Keyword-only extras: ``device``, ``output`` ("numpy", or "torch": every array of the result stays on the device)."""
     if not use_liu_shen:
         raise ValueError("I can currently only really do this for the liu shen jitted method")
-    if output not in ("numpy", "torch"):
-        raise ValueError("output must be 'numpy' or 'torch'")
-    if len(movie.shape) != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
+    side = _side(output, device)
+    _movie_shape(movie, 0)
     if return_iterations and not 1 <= int(iteration_stepsize) <= int(max_iterations):
         raise ValueError("iteration_stepsize must be between 1 and max_iterations")
     movie_to_analyse = movie
     if smoothing_sigma is not None:
         if output == "torch":
-            import torch
-            dev = torch.device("cuda", int(device))
-            frames = torch.as_tensor(movie).to(device=dev, dtype=torch.float64).contiguous()
-            movie_to_analyse = torch.empty_like(frames)
-            with _box_flow_context(frames.shape[1], frames.shape[2], 1, device) as solver:
-                torch.cuda.synchronize(dev)
-                solver.blur_dev(frames, movie_to_analyse, frames.shape[0], gaussian_taps(smoothing_sigma))
+            with _device_context(movie.shape[1], movie.shape[2], 1, device) as solver:
+                movie_to_analyse = side.blurred(side.frames(movie), gaussian_taps(smoothing_sigma), solver)
         else:
             movie_to_analyse = blur_movie(np.asarray(movie), smoothing_sigma=smoothing_sigma, device=device)
     guesses = (float(v_x_guess), float(v_y_guess), float(remodelling_guess))
@@ -1707,11 +1591,7 @@ def vary_regularisation(movie,
     ``result['stats']`` (the native per-combination records: worst residual / iteration count, all-pairs flag).
     """
     movie = np.asarray(movie)
-    if movie.ndim != 3:
-        raise ValueError("movie must be a 3-D array (frames, x, y)")
-    T, N_i, N_j = movie.shape
-    if T < 2:
-        raise ValueError("movie needs at least two frames")
+    T, N_i, N_j = _movie_shape(movie, 2)
     kw = dict(delta_x=1.0, delta_t=1.0, smoothing_sigma=None, initial_v_x=0.0, initial_v_y=0.0, initial_remodelling=0.0,
               use_direct_solver=False, rtol=None, max_iterations=1000, reference_quirks=True, device=0,
               max_pairs_in_flight=None, coarse_precision="float8", vcycle_precision="coarse_float32", multigrid_sweeps=None,
@@ -1789,12 +1669,11 @@ def subsample_velocities_for_visualisation(flow_result, iteration=None, arrow_bo
     n_x, n_y = fields[0].shape[1], fields[1].shape[2]
     nbx, nby = n_x // box, n_y // box
     if hasattr(fields[0], "data_ptr") and fields[0].is_cuda:
-        import torch
-        sub = []
+        side, sub = _DeviceSide(fields[0].device.index), []
         with _device_context(n_x, n_y, 1, fields[0].device.index) as solver:
             for f in fields:
-                out = torch.empty((n_pairs, nbx, nby), dtype=torch.float64, device=f.device)
-                torch.cuda.synchronize(f.device)
+                out = side.empty((n_pairs, nbx, nby))
+                side.wait()
                 solver.subsample_dev(f[:n_pairs].contiguous(), n_pairs, box, offset, out)
                 sub.append(out.cpu().numpy())
     else:
