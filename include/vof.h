@@ -584,6 +584,47 @@ int vof_flow_compare_host(vof_ctx* ctx, const double* v_x_a, const double* v_y_a
                           int clamp_angle, int frames_in_flight, int64_t* joint_speed_histogram, int64_t* angle_histogram,
                           int64_t* counts);
 
+/* The illumination correction of the reference's real-data scripts, optical_flow.correct_intensity_change
+ * (analyse_short_timeinterval_data.py:241-301, 128-145), of n_frames float64 frames.  With G(f, taps) the blur of vof_blur_stack_*
+ * (same kernels or the same arithmetic in the same order: same bits), per frame k, in this order and nothing else:
+ *   B[k] = G(movie[k], smoothing_weights)      (smoothing_weights NULL: B = movie, no first blur; smoothing_radius is then ignored)
+ *   D    = B[k] - B[reference_frame]           (one float64 subtraction per pixel)
+ *   E    = G(D, filter_weights)                (the drift)
+ *   out[k] = Tg[k] - E,  Tg = B for target VOF_INTENSITY_TARGET_BLURRED, the movie for VOF_INTENSITY_TARGET_ORIGINAL.
+ * drift (n_frames frames, may be NULL) receives E.  Weights are host memory, 2 * radius + 1 taps each.  reference_frame:
+ * 0 .. n_frames - 1; its D is +0.0, its drift 0 and its output Tg[reference_frame] bit for bit.  NaN and Inf propagate through
+ * the taps.  out and drift alias neither each other nor movie.
+ * Frames are walked in chunks of frames_in_flight (0: sized from the free device memory, 16 at most).  Scratch: once per call the
+ * blurred reference frame and the taps; per frame in flight the blurred frame (with a first blur) and the row-filtered frame -
+ * D and E never exist as stacks - and, _host only, the staged frames and results.  The difference is formed by the loader of the
+ * second blur's axis-0 pass and the subtraction by the store of its axis-1 pass, so a frame moves 10 planes (4 + 3 + 3), not the 14
+ * of blur, difference, blur, subtraction.  Results do not depend on frames_in_flight nor on the chunk that holds the reference.
+ * Profiler: class VOF_K_PREPROCESS, stage 16 axis-0 pass, 17 axis-1 pass (the first blur is VOF_K_RHS).  The profiler keeps 16
+ * `level` slots per class, so both are summed in slot 15, with stage 15 of vof_farneback_box_* if that ran since the last reset;
+ * VOF_DEBUG_SYNC names the stages apart.
+ * _dev: movie, out and drift are device pointers; _host: host pointers, staged through the pinned bounce buffer. */
+#define VOF_INTENSITY_TARGET_BLURRED 0
+#define VOF_INTENSITY_TARGET_ORIGINAL 1
+int vof_intensity_correct_dev(vof_ctx* ctx, const double* movie, int n_frames, const double* smoothing_weights, int smoothing_radius,
+                              const double* filter_weights, int filter_radius, int reference_frame, int target, int frames_in_flight,
+                              double* out, double* drift);
+int vof_intensity_correct_host(vof_ctx* ctx, const double* movie, int n_frames, const double* smoothing_weights, int smoothing_radius,
+                               const double* filter_weights, int filter_radius, int reference_frame, int target, int frames_in_flight,
+                               double* out, double* drift);
+
+/* np.histogram(F[k].ravel(), bins, range)[0] of every frame, optical_flow.intensity_histograms: F the movie, or with blur_weights
+ * (host, 2 * blur_radius + 1 taps; NULL: none) its blur, taken a chunk of frames_in_flight frames at a time and never a stack.
+ * edges: host, the bins + 1 values of np.linspace(lo, hi, bins + 1), increasing; bins: 1 .. 2^20.  The bin index is corrected
+ * against the edges, the last bin is closed on the right, NaN and values outside [lo, hi] are dropped.
+ * counts (host, n_frames x bins int64) and nonfinite (host, n_frames int64: the NaN / Inf values of F[k]) are overwritten.
+ * Counters live in LDS up to 1024 bins, in global memory above; integer atomics only, so every count is the same from call to
+ * call and for every frames_in_flight.  Profiler: class VOF_K_PREPROCESS, stage 18 (slot 15, as above).
+ * _dev: movie is a device pointer; _host: a host pointer, staged through the pinned bounce buffer. */
+int vof_intensity_hist_dev(vof_ctx* ctx, const double* movie, int n_frames, const double* blur_weights, int blur_radius,
+                           const double* edges, int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite);
+int vof_intensity_hist_host(vof_ctx* ctx, const double* movie, int n_frames, const double* blur_weights, int blur_radius,
+                            const double* edges, int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

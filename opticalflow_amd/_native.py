@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("VOF_LIB") or os.path.join(HERE, "csrc", "libvof.so")
 K_NAMES = ["rhs", "apply0", "gs0", "gs", "residual", "restrict", "prolong", "galerkin0", "galerkin",
            "coarse_setup", "coarse_solve", "vector", "reduce", "finalize", "functionals", "coarse_tail", "preprocess"]
 RESIZE_U8, RESIZE_F64 = 0, 1         # enum vof_resize_arithmetic
+INTENSITY_TARGETS = ("blurred", "original")   # VOF_INTENSITY_TARGET_*: the index is the value
 
 
 class VofParams(C.Structure):
@@ -137,6 +138,8 @@ TWINS = {
     "vof_flow_extremes": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp],
     "vof_flow_compare": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp, C.c_int,
                          _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
+    "vof_intensity_correct": [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "vof_intensity_hist": [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp],
 }
 SIGNATURES.update({name + twin: (C.c_int, args) for name, args in TWINS.items() for twin in ("_host", "_dev")})
 
@@ -656,6 +659,30 @@ class Solver:
                    int(bool(reference_quirks)), _ptr(edges[0]), edges[0].size - 1, _ptr(edges[1]), edges[1].size - 1, _ptr(edges[2]),
                    edges[2].size - 1, int(bool(clamp_angle)), int(frames_in_flight), _ptr(jhist), _ptr(thist), _ptr(counts))
         return jhist, thist, counts
+
+    # -- the illumination correction and the intensity histograms (vof_intensity.hpp)
+    def intensity_correct(self, movie, n_frames, smoothing_weights, filter_weights, reference_frame, target, out, drift=None,
+                          frames_in_flight=0):
+        """``vof_intensity_correct_*``: ``out[k] = Tg[k] - G(B[k] - B[reference_frame], filter_weights)`` of ``n_frames`` float64
+        frames, ``B`` the movie blurred with ``smoothing_weights`` (None: the movie itself), ``Tg`` ``B`` (``target``
+        ``INTENSITY_TARGETS.index("blurred")``) or the movie (``"original"``); ``drift`` (None: not wanted) receives the subtrahend.
+        ``out`` and ``drift`` alias neither each other nor ``movie``."""
+        w1 = None if smoothing_weights is None else np.ascontiguousarray(smoothing_weights, dtype=np.float64).ravel()
+        w2 = np.ascontiguousarray(filter_weights, dtype=np.float64).ravel()
+        self._call("vof_intensity_correct", (movie, out, drift), _ptr(movie), int(n_frames), _ptr(w1), 0 if w1 is None else w1.size // 2,
+                   _ptr(w2), w2.size // 2, int(reference_frame), int(target), int(frames_in_flight), _ptr(out), _ptr(drift))
+
+    def intensity_hist(self, movie, n_frames, edges, blur_weights=None, frames_in_flight=0):
+        """``vof_intensity_hist_*``: ``(counts, nonfinite)``, int64 ``(n_frames, bins)`` and ``(n_frames,)`` host arrays -
+        ``np.histogram`` of every float64 frame (blurred with ``blur_weights`` first, if given) against the ``bins + 1`` increasing
+        ``edges`` of ``np.linspace``, and the NaN / Inf values per frame."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+        w = None if blur_weights is None else np.ascontiguousarray(blur_weights, dtype=np.float64).ravel()
+        counts = np.zeros((int(n_frames), edges.size - 1), dtype=np.int64)
+        nonfinite = np.zeros(int(n_frames), dtype=np.int64)
+        self._call("vof_intensity_hist", (movie,), _ptr(movie), int(n_frames), _ptr(w), 0 if w is None else w.size // 2, _ptr(edges),
+                   edges.size - 1, int(frames_in_flight), _ptr(counts), _ptr(nonfinite))
+        return counts, nonfinite
 
 
     def field_moments_dev(self, field, n):

@@ -20,6 +20,7 @@
 #include "vof_preprocess.hpp"
 #include "vof_resize.hpp"
 #include "vof_farneback.hpp"
+#include "vof_intensity.hpp"
 #include "../../include/vof.h"
 
 #include <fcntl.h>
@@ -4900,6 +4901,127 @@ int vof_flow_filter_host(vof_ctx* c, const double* movie, int n_pairs, const dou
                          int64_t* counts) {
     return flow_filter_impl(c, movie, n_pairs, blur_weights, blur_radius, intensity_threshold, speed_threshold, zero_speed_under_low,
                             frames_in_flight, v_x, v_y, speed, counts, true);
+}
+
+// ---- the illumination correction and the intensity histograms (correct_intensity_change, intensity_histograms;
+// vof_intensity.hpp) ---------------------------------------------------------------------------------
+// The second blur of nf frames of b less the one frame ref, and the subtraction from target: the two fused passes, mid the
+// row-filtered frames between them.  Radii BL_RMIN .. BL_RMAX take the LDS tiles, the others global memory: same bits.
+static bool intensity_tiled(int radius) { return radius >= BL_RMIN && radius <= BL_RMAX; }
+
+static int intensity_passes(vof_ctx* c, const double* b, const double* ref, const double* target, int nf, int radius, const double* w,
+                            double* mid, double* out, double* drift) {
+    const size_t fs = frame_stride(c);
+    const bool tiled = intensity_tiled(radius);
+    const dim3 g0((c->Nj + BX - 1) / BX, (c->Ni + BL_TI - 1) / BL_TI, nf), g1(g0.x, (c->Ni + BL_TR - 1) / BL_TR, nf), g = grid2d(c->Ni, c->Nj, nf);
+    {
+        Prof prof(c, VOF_K_PREPROCESS, PP_ST_IC_AXIS0, 24.0 * fs, 16.0 * fs);       // the reference frame is re-read from the caches
+        if (tiled) k_ic_axis0_tiled<<<g0, blk2d, blur_tiled_lds(0, radius), c->stream>>>(b, ref, mid, c->Ni, c->Nj, w, radius);
+        else k_ic_axis0<<<g, blk2d, 0, c->stream>>>(b, ref, mid, c->Ni, c->Nj, w, radius);
+    }
+    {
+        Prof prof(c, VOF_K_PREPROCESS, PP_ST_IC_AXIS1, (drift ? 32.0 : 24.0) * fs);
+        if (tiled && drift) k_ic_axis1_tiled<true><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
+        else if (tiled) k_ic_axis1_tiled<false><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
+        else if (drift) k_ic_axis1<true><<<g, blk2d, 0, c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
+        else k_ic_axis1<false><<<g, blk2d, 0, c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int intensity_correct_impl(vof_ctx* c, const double* movie, int n_frames, const double* w1_host, int r1, const double* w2_host, int r2,
+                                  int reference_frame, int target, int flight, double* out, double* drift, bool host) {
+    if (int rc = FrameChunks::check(c, {movie, w2_host, out}, n_frames, "n_frames")) return rc;
+    if ((w1_host && (r1 < 0 || r1 > 4096)) || r2 < 0 || r2 > 4096) { c->err = "bad smoothing_radius / filter_radius"; return -1; }
+    if (reference_frame < 0 || reference_frame >= n_frames) { c->err = "intensity correction: reference_frame outside the stack"; return -1; }
+    if (target != VOF_INTENSITY_TARGET_BLURRED && target != VOF_INTENSITY_TARGET_ORIGINAL) { c->err = "intensity correction: unknown target"; return -1; }
+    const size_t fs = frame_stride(c);
+    FrameChunks fc(c, "intensity correction", n_frames, flight, host);
+    // once per call: the (blurred) reference frame and the taps; per frame in flight: the blurred frame and the row-filtered one,
+    // which is the first blur's scratch too (a chunk of at least BLUR_CHUNK frames is blurred BLUR_CHUNK at a time)
+    double *bref = nullptr, *blurred = nullptr, *mid, *w1 = nullptr, *w2;
+    if (w1_host || host) fc.sc.once(&bref, fs);
+    if (w1_host) { fc.sc.per_unit(&blurred, fs); fc.sc.once(&w1, (size_t)2 * r1 + 1); }
+    fc.sc.per_unit(&mid, fs);
+    fc.sc.once(&w2, (size_t)2 * r2 + 1);
+    fc.input(movie);
+    fc.output(out, fs * sizeof(double));
+    if (drift) fc.output(drift, fs * sizeof(double));
+    if (int rc = fc.plan()) return rc;
+    // the axis-0 tile takes up to 80 KiB of dynamic LDS, past the default limit: raised for its kernel before the walk, in every
+    // call that takes the tiles (a host-side setting of a few microseconds; the context keeps no record of it)
+    if (intensity_tiled(r2))
+        HIPCHK(hipFuncSetAttribute((const void*)k_ic_axis0_tiled, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blur_tiled_lds(0, BL_RMAX)));
+    if (w1_host) if (int rc = h2d_bounced(c, w1, w1_host, (size_t)(2 * r1 + 1) * sizeof(double))) return rc;
+    if (int rc = h2d_bounced(c, w2, w2_host, (size_t)(2 * r2 + 1) * sizeof(double))) return rc;
+    const double* ref = movie + (size_t)reference_frame * fs;
+    if (host) { if (int rc = h2d_bounced(c, bref, ref, fs * sizeof(double))) return rc; ref = bref; }
+    c->cur_units = 1;
+    if (w1_host) { if (int rc = blur_frames(c, ref, bref, 1, r1, mid, w1)) return rc; ref = bref; }
+    return fc.run([&](int, int nf, const double* const* in, void* const* dst) -> int {
+        const double* b = in[0];
+        if (w1_host) { if (int rc = blur_frames(c, in[0], blurred, nf, r1, mid, w1)) return rc; b = blurred; }
+        return intensity_passes(c, b, ref, target == VOF_INTENSITY_TARGET_BLURRED ? b : in[0], nf, r2, w2, mid, (double*)dst[0],
+                                drift ? (double*)dst[1] : nullptr);
+    });
+}
+
+int vof_intensity_correct_dev(vof_ctx* c, const double* movie, int n_frames, const double* smoothing_weights, int smoothing_radius,
+                              const double* filter_weights, int filter_radius, int reference_frame, int target, int frames_in_flight,
+                              double* out, double* drift) {
+    return intensity_correct_impl(c, movie, n_frames, smoothing_weights, smoothing_radius, filter_weights, filter_radius, reference_frame, target,
+                                  frames_in_flight, out, drift, false);
+}
+int vof_intensity_correct_host(vof_ctx* c, const double* movie, int n_frames, const double* smoothing_weights, int smoothing_radius,
+                               const double* filter_weights, int filter_radius, int reference_frame, int target, int frames_in_flight,
+                               double* out, double* drift) {
+    return intensity_correct_impl(c, movie, n_frames, smoothing_weights, smoothing_radius, filter_weights, filter_radius, reference_frame, target,
+                                  frames_in_flight, out, drift, true);
+}
+
+static int intensity_hist_impl(vof_ctx* c, const double* movie, int n_frames, const double* w_host, int radius, const double* edges_host, int bins,
+                               int flight, int64_t* counts, int64_t* nonfinite, bool host) {
+    if (int rc = FrameChunks::check(c, {movie, edges_host, counts, nonfinite}, n_frames, "n_frames")) return rc;
+    if (w_host && (radius < 0 || radius > 4096)) { c->err = "bad blur_radius"; return -1; }
+    if (bins < 1 || bins > IH_MAX_BINS) { c->err = "intensity histograms: bins must be 1 .. " + std::to_string(IH_MAX_BINS); return -1; }
+    if (!(edges_host[0] < edges_host[bins])) { c->err = "intensity histograms: the edges must increase"; return -1; }
+    const size_t fs = frame_stride(c);
+    FrameChunks fc(c, "intensity histograms", n_frames, flight, host);
+    double *blurred = nullptr, *tmp = nullptr, *w = nullptr, *edges;
+    unsigned long long *d_hist, *d_bad;                              // [frame in flight][bins], [frame in flight]
+    if (w_host) { fc.sc.per_unit(&blurred, fs); blur_regions(fc.sc, n_frames, &tmp, &w, radius); }
+    fc.sc.once(&edges, (size_t)bins + 1);
+    fc.sc.per_unit(&d_hist, (size_t)bins);
+    fc.sc.per_unit(&d_bad, 1);
+    fc.input(movie);
+    if (int rc = fc.plan()) return rc;
+    if (w_host) if (int rc = h2d_bounced(c, w, w_host, (size_t)(2 * radius + 1) * sizeof(double))) return rc;
+    if (int rc = h2d_bounced(c, edges, edges_host, ((size_t)bins + 1) * sizeof(double))) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are copied out as they are");
+    const int blocks = (int)std::min<size_t>(IH_MAX_BLOCKS, (fs + (size_t)IH_PER_THREAD * IH_BLOCK - 1) / ((size_t)IH_PER_THREAD * IH_BLOCK));
+    return fc.run([&](int k0, int nf, const double* const* in, void* const*) -> int {
+        const double* x = in[0];
+        if (w_host) { if (int rc = blur_frames(c, in[0], blurred, nf, radius, tmp, w)) return rc; x = blurred; }
+        HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)nf * bins * sizeof(unsigned long long), c->stream));
+        HIPCHK(hipMemsetAsync(d_bad, 0, (size_t)nf * sizeof(unsigned long long), c->stream));
+        {
+            Prof prof(c, VOF_K_PREPROCESS, PP_ST_IH_COUNTS, 8.0 * fs);
+            k_ih_counts<<<dim3(blocks, nf), IH_BLOCK, 0, c->stream>>>(x, fs, edges, bins, d_hist, d_bad);
+        }
+        HIPCHK(hipGetLastError());
+        if (int rc = d2h_bounced(c, counts + (size_t)k0 * bins, d_hist, (size_t)nf * bins * sizeof(int64_t))) return rc;
+        return d2h_bounced(c, nonfinite + k0, d_bad, (size_t)nf * sizeof(int64_t));
+    });
+}
+
+int vof_intensity_hist_dev(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, int blur_radius, const double* edges,
+                           int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite) {
+    return intensity_hist_impl(c, movie, n_frames, blur_weights, blur_radius, edges, bins, frames_in_flight, counts, nonfinite, false);
+}
+int vof_intensity_hist_host(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, int blur_radius, const double* edges,
+                            int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite) {
+    return intensity_hist_impl(c, movie, n_frames, blur_weights, blur_radius, edges, bins, frames_in_flight, counts, nonfinite, true);
 }
 
 // the six stacks of two results as inputs of a frame-chunk walk, and those of one chunk as the kernels take them

@@ -65,7 +65,7 @@ atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
-           "compare_flow_results", "filter_PIV_flow_result",
+           "compare_flow_results", "filter_PIV_flow_result", "correct_intensity_change", "intensity_histograms",
            "apply_adaptive_threshold", "apply_clahe", "downsample_movie", "conduct_opencv_flow", "farneback_plan",
            "calcOpticalFlowFarneback", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_FARNEBACK_GAUSSIAN",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
@@ -588,6 +588,106 @@ def downsample_movie(movie, resolution, *, device=0, output="numpy"):
     arithmetic = _native.RESIZE_U8 if name == "uint8" else _native.RESIZE_F64
     return _run_preprocess(movie, shape, device, side, lambda solver, frames, out, T: solver.resize_area(frames, out, T, n_i, n_j, arithmetic),
                            out_shape=(shape[0], n_i, n_j))
+
+
+BLUR_MAX_RADIUS = 4096               # the largest tap radius the native blur takes
+HISTOGRAM_MAX_BINS = 1 << 20         # IH_MAX_BINS of csrc/vof_intensity.hpp
+
+
+def _blur_taps(name, sigma):
+    """``gaussian_taps(sigma)`` of a positive, finite ``sigma`` whose radius the library serves; ``ValueError`` otherwise."""
+    try:
+        sigma = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a positive number") from None
+    if not (np.isfinite(sigma) and sigma > 0.0):
+        raise ValueError(f"{name} must be positive and finite")
+    if int(4.0 * sigma + 0.5) > BLUR_MAX_RADIUS:
+        raise ValueError(f"{name} is too large: the blur's radius int(4 sigma + 0.5) may be {BLUR_MAX_RADIUS} at most")
+    return gaussian_taps(sigma)
+
+
+def correct_intensity_change(movie, smoothing_sigma=3, filter_size=5, *, target="blurred", reference_frame=0, return_drift=False,
+                             device=0, output="numpy"):
+    """The illumination correction of the reference's real-data scripts on the GPU: what ``correct_intensity_change``
+    (analysis/analyse_short_timeinterval_data.py:241-301) and ``visualise_ground_truth_displacement`` (:128-145) do to a movie
+    whose overall brightness drifts between frames, before an estimator sees it.
+
+    ``movie`` is ``(T, N_i, N_j)`` with ``T >= 1``, read as float64 like ``blur_movie``.  With ``G(f, s)`` the filter of ``blur_movie``
+    - ``scipy.ndimage.gaussian_filter(f, s, mode='nearest', truncate=4.0)``, taps from ``gaussian_taps`` - the arithmetic is, per
+    frame ``k``, in this order and nothing else:
+
+    - ``B[k] = G(movie[k], smoothing_sigma)``; with ``smoothing_sigma=None``, ``B = movie``;
+    - ``D[k] = B[k] - B[reference_frame]``, one float64 subtraction per pixel;
+    - ``E[k] = G(D[k], filter_size)``, the drift;
+    - ``out[k] = Tg[k] - E[k]`` with ``Tg = B`` for ``target="blurred"`` and ``Tg = movie`` for ``target="original"``.
+
+    ``target="blurred"`` with the defaults is the reference's ``:250-252`` (sigma 3, filter 5, a two-frame movie);
+    ``target="original"`` with ``filter_size=7.5`` its ``:140-144`` (frame 0 kept, frame 1 corrected).  The result is the float64
+    ``(T, N_i, N_j)`` stack ``out``; with ``return_drift=True`` it is ``(out, E)``.  The reference frame is no special case: its ``D``
+    is ``+0.0`` everywhere and its drift exactly 0, so its output is ``Tg[reference_frame]`` bit for bit.  NaN and Inf propagate through
+    the taps as in ``blur_movie``; there is no range check.  The fused passes give the bits of the chain made of ``blur_movie`` and
+    numpy subtractions.
+
+    ``reference_frame`` is a Python index in ``-T .. T - 1``.  ``ValueError``, before the library is touched, for a
+    ``reference_frame`` outside that, a ``target`` that is neither name, a non-positive or non-finite sigma, a movie that is not
+    3-D, frames under 4 x 4 pixels and an unknown ``output``.
+    ``output="torch"``: ``movie`` may be a device tensor and the results are float64 tensors on the device, ready for
+    ``variational_optical_flow(..., output="torch")``."""
+    side = _side(output, device)
+    shape = _movie_shape(movie, 1, 4)
+    if target not in _native.INTENSITY_TARGETS:
+        raise ValueError(f"target must be one of {_native.INTENSITY_TARGETS}")
+    try:
+        inside = not isinstance(reference_frame, bool) and int(reference_frame) == reference_frame and -shape[0] <= reference_frame < shape[0]
+    except (TypeError, ValueError):
+        inside = False
+    if not inside:
+        raise ValueError(f"reference_frame must be an integer in {-shape[0]} .. {shape[0] - 1}")
+    reference = int(reference_frame) % shape[0]
+    smoothing = None if smoothing_sigma is None else _blur_taps("smoothing_sigma", smoothing_sigma)
+    taps = _blur_taps("filter_size", filter_size)
+    which = _native.INTENSITY_TARGETS.index(target)
+    frames = side.frames(movie)
+    out = side.empty(shape)
+    drift = side.empty(shape) if return_drift else None
+    with _device_context(shape[1], shape[2], 1, device) as solver:
+        side.wait()
+        solver.intensity_correct(frames, shape[0], smoothing, taps, reference, which, out, drift)
+    return (out, drift) if return_drift else out
+
+
+def intensity_histograms(movie, bins=255, value_range=(0, 255), smoothing_sigma=None, *, device=0, output="numpy"):
+    """The per-frame intensity histograms the reference's scripts read their background and intensity thresholds off
+    (``investigate_intensities``, analyse_short_timeinterval_data.py:303-335 and compare_rho_and_actin.py:98-118;
+    ``investigate_intensity_thresholds``, :198-226; ``make_thresholded_movies``, :281-299) on the GPU.
+
+    Returns a dict: ``counts``, int64 ``(T, bins)``; ``edges``, ``np.linspace(lo, hi, bins + 1)``; ``nonfinite``, int64 ``(T,)``,
+    the NaN / Inf values of every frame.  ``counts[k]`` is ``np.histogram(F[k].ravel(), bins, value_range)[0]`` exactly, ``F`` the
+    movie (read as float64) or, with ``smoothing_sigma``, ``blur_movie(movie, smoothing_sigma)`` - the same bits, blurred a chunk
+    of frames at a time in device scratch and never a stack.  The scripts' whole-movie histogram is ``counts.sum(0)``.  As in
+    numpy the bin index is corrected against the edges, the last bin is closed on the right, and NaN and values outside the range
+    are dropped.
+
+    ``ValueError`` for ``bins < 1`` (or above 2**20), a range that is not finite or not increasing, a bad sigma, a movie that is
+    not 3-D and frames under 4 x 4 pixels.  ``output="torch"``: ``movie`` may be a device tensor, which is read where it lies; the
+    three results are small and numpy arrays either way."""
+    side = _side(output, device)
+    shape = _movie_shape(movie, 1, 4)
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= HISTOGRAM_MAX_BINS:
+        raise ValueError(f"bins must be an integer in 1 .. {HISTOGRAM_MAX_BINS}")
+    if np.ndim(value_range) != 1 or len(value_range) != 2:
+        raise ValueError("value_range must be a pair (lo, hi)")
+    lo, hi = float(value_range[0]), float(value_range[1])
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError("value_range must be finite with lo < hi")
+    taps = None if smoothing_sigma is None else _blur_taps("smoothing_sigma", smoothing_sigma)
+    edges = np.linspace(lo, hi, int(bins) + 1)
+    frames = side.frames(movie)
+    with _device_context(shape[1], shape[2], 1, device) as solver:
+        side.wait()
+        counts, nonfinite = solver.intensity_hist(frames, shape[0], edges, taps)
+    return {"counts": counts, "edges": edges, "nonfinite": nonfinite}
 
 
 def format_elapsed_time(time_difference):
