@@ -131,7 +131,8 @@ struct vof_ctx {
     GmresState* gm_state = nullptr;
     double* gm_partials = nullptr;
     int* gm_cycle = nullptr;
-    int gm_m = 0;
+    int gm_m = 0;                // restart length the basis holds
+    int gm_want = 0;             // restart length it was asked for (> gm_m where the free memory cut it)
     long long gmres_pairs = 0;   // pairs handed to the fallback since the context was created
     struct Alloc { void* raw; char* user; size_t bytes; const char* name; int line; };
     std::vector<Alloc> allocs;     // every device buffer of the context (raw != user only with guard regions)
@@ -1450,10 +1451,27 @@ int count_active(vof_ctx* c, int np, bool renew_list = true) {
     return n;
 }
 
+// Restart length a call asks for (0: the default).
+inline int gmres_restart_wanted(const vof_params& P) { return std::min(P.gmres_restart > 0 ? P.gmres_restart : 100, GM_MAXM); }
+
+// A context outlives a call (the Python layer keeps one per image size), and the basis is sized by the first call that reaches
+// the fallback.  A call that asks for a longer restart length than the basis was sized for gives it up here, at the start of the
+// call (check_params) and so before any lane holds a view of it; gmres_phase then allocates one for this call on first use.  A
+// basis the free memory cut below its request is kept: the same request would be cut again.  So is any basis under a call that
+// cannot reach the fallback (krylov_method 0, BiCGStab alone): its restart length asks for nothing.
+int gmres_release_short_basis(vof_ctx* c) {
+    if (!c->gm_V || c->prm.krylov_method == 0 || gmres_restart_wanted(c->prm) <= c->gm_want) return 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (int rc = dev_free(c, c->gm_V)) return rc;
+    c->gm_V = nullptr;
+    c->gm_m = c->gm_want = 0;
+    return 0;
+}
+
 // Buffers of the GMRES fallback: restart length = min(requested, what fits in half of the free device memory).
 int gmres_buffers(vof_ctx* c, int want_m) {
     want_m = std::min(want_m, GM_MAXM);
-    if (c->gm_V) return 0;   // allocated once per context
+    if (c->gm_V) return 0;   // kept between calls (gmres_release_short_basis)
     const size_t vec = (size_t)c->B * 3 * c->L[0].npts * sizeof(double);
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -1463,9 +1481,10 @@ int gmres_buffers(vof_ctx* c, int want_m) {
     int m = std::min(want_m, fit);
     if (m < 4) { c->err = "not enough device memory for the GMRES fallback (lower max_pairs_in_flight)"; return -3; }
     if (int rc = dev_alloc(c, &c->gm_V, (size_t)(m + 1) * c->B * 3 * c->L[0].npts)) return rc;
-    if (int rc = dev_alloc(c, &c->gm_state, (size_t)c->B)) return rc;
-    if (int rc = dev_alloc(c, &c->gm_partials, (size_t)c->B * (GM_NV + 1) * c->nblk)) return rc;
+    if (!c->gm_state) if (int rc = dev_alloc(c, &c->gm_state, (size_t)c->B)) return rc;   // (do not depend on the restart length)
+    if (!c->gm_partials) if (int rc = dev_alloc(c, &c->gm_partials, (size_t)c->B * (GM_NV + 1) * c->nblk)) return rc;
     c->gm_m = m;
+    c->gm_want = want_m;
     return 0;
 }
 
@@ -1509,13 +1528,13 @@ int gmres_phase(vof_ctx* c, int np, int* handed_over) {
     if (nact == 0) return 0;
     *handed_over = nact;
     if (!c->gm_V) {
-        const int want = P.gmres_restart > 0 ? P.gmres_restart : 100;
+        const int want = gmres_restart_wanted(P);
         int rc = c->lane_parent ? lane_gmres_attach(c, true, want) : gmres_buffers(c, want);
         if (rc == -3) { c->err.clear(); return 0; }   // no room: leave the pairs unconverged (reported per pair)
         if (rc) return rc;
     }
     c->gmres_pairs += nact;
-    const int m = std::min(c->gm_m, P.gmres_restart > 0 ? P.gmres_restart : 100);
+    const int m = std::min(c->gm_m, gmres_restart_wanted(P));
     c->vfloat = false;   // float64 cycle vectors: the basis vectors are the cycle's right-hand sides
     c->vcoarse32 = false;
     double* V = c->gm_V;
@@ -2017,6 +2036,7 @@ int check_params(vof_ctx* c, const vof_params* p) {
     // float32 V-cycle vectors need the fused sweeps and a multi-level hierarchy
     c->vfloat = (p->vcycle_precision == 1 || p->vcycle_precision == 2) && c->fused && c->L.size() > 1;
     c->vcoarse32 = false;   // set per batch (solve_batch); the debug entry points run every level in one storage type
+    if (int rc = gmres_release_short_basis(c)) return rc;
     return ensure_storage(c);
 }
 
