@@ -625,6 +625,38 @@ int vof_intensity_hist_dev(vof_ctx* ctx, const double* movie, int n_frames, cons
 int vof_intensity_hist_host(vof_ctx* ctx, const double* movie, int n_frames, const double* blur_weights, int blur_radius,
                             const double* edges, int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite);
 
+/* The dense part of optical_flow.convert_PIV_result (OF.py:2141-2230), optical_flow.upsample_PIV_vectors: the piecewise cubic
+ * of scipy.interpolate.griddata(points, values, targets, method='cubic') - a Clough-Tocher element on every triangle of a
+ * Delaunay triangulation - of the two vector components at every pixel of n_frames frames of n_i x n_j, and its speed.
+ * out[k][i][j] is the value at the target (x = j, y = i).  The triangulation and the gradients are the caller's (scipy's
+ * Delaunay and CloughTocher2DInterpolator(tri, values).grad): host tables of all frames, frame after frame, with
+ * point_offsets and triangle_offsets (n_frames + 1 int32 each, starting at 0) saying where a frame's rows lie:
+ *   points, values: 2 doubles per point (x, y; v_x, v_y);  gradients: 4 (d v_x/dx, d v_x/dy, d v_y/dx, d v_y/dy);
+ *   simplices, neighbours: 3 int32 per triangle, indices local to the frame, neighbour k opposite vertex k, -1 for none;
+ *   transforms: 6 doubles per triangle, tri.transform - the 2 x 2 inverse, row-major, then the offset r.
+ * Every table is checked before anything is uploaded: indices inside their frame, every number finite (-1 otherwise).
+ * Per target q, float64, every operation single and uncontracted, in the order of tests/piv_restatement.py:
+ *   c0 = T00 (qx - rx) + T01 (qy - ry), c1 = T10 (qx - rx) + T11 (qy - ry), c2 = 1 - c0 - c1 in triangle t; t includes q when
+ *   all three lie in [-eps, 1 + eps], eps = 100 DBL_EPSILON; of the triangles that include q the lowest index is taken; the
+ *   19 control values of scipy's element from the three vertices and the centroids of the neighbours; m = min(c),
+ *   b = c - m, b4 = 3 m and the 19 terms summed left to right with powers as products; speed = sqrt(v_x v_x + v_y v_y).
+ * A pixel no triangle includes is NaN in v_x, v_y and speed.  A frame without triangles is the caller's to fill (a frame with a
+ * degenerate simplex, whose transform holds NaN, is refused with triangles): it is written as NaN and counted.
+ * counts (host, 2 x int64): the pixels outside every triangle of the frames that have triangles; the frames without.
+ * Frames are walked in chunks of frames_in_flight (0: sized from the free device memory, 16 at most); scratch per frame in
+ * flight: the tables at the size of the largest frame, 44 doubles per triangle and an int32 map of the frame.  Integer atomics
+ * only: results are the same from call to call and for every frames_in_flight.
+ * Profiler: class VOF_K_REDUCE, `level` 4 control values, 5 the map, 6 evaluation.
+ * _dev: v_x, v_y and speed are device pointers; _host: host pointers, staged through the pinned bounce buffer. */
+int vof_piv_upsample_dev(vof_ctx* ctx, int n_frames, const double* points, const double* values, const double* gradients,
+                         const int32_t* simplices, const int32_t* neighbours, const double* transforms, const int32_t* point_offsets,
+                         const int32_t* triangle_offsets, int frames_in_flight, double* v_x, double* v_y, double* speed,
+                         int64_t* counts);
+int vof_piv_upsample_host(vof_ctx* ctx, int n_frames, const double* points, const double* values, const double* gradients,
+                          const int32_t* simplices, const int32_t* neighbours, const double* transforms, const int32_t* point_offsets,
+                          const int32_t* triangle_offsets, int frames_in_flight, double* v_x, double* v_y, double* speed,
+                          int64_t* counts);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

@@ -140,6 +140,7 @@ TWINS = {
                          _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
     "vof_intensity_correct": [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "vof_intensity_hist": [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp],
+    "vof_piv_upsample": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
 }
 SIGNATURES.update({name + twin: (C.c_int, args) for name, args in TWINS.items() for twin in ("_host", "_dev")})
 
@@ -684,6 +685,29 @@ class Solver:
                    edges.size - 1, int(frames_in_flight), _ptr(counts), _ptr(nonfinite))
         return counts, nonfinite
 
+    # -- the dense part of convert_PIV_result (vof_piv.hpp)
+    def piv_upsample(self, tables, n_frames, v_x, v_y, speed, frames_in_flight=0):
+        """``vof_piv_upsample_*``: the Clough-Tocher interpolant of ``n_frames`` frames at every pixel into ``v_x``, ``v_y`` and ``speed``
+        (float64, ``(n_frames, n_i, n_j)``, numpy arrays or device memory).  ``tables``: the host tables of include/vof.h by name -
+        ``points``, ``values``, ``gradients``, ``transforms`` (float64), ``simplices``, ``neighbours``, ``point_offsets``,
+        ``triangle_offsets`` (int32).  Returns ``counts``: pixels outside every triangle, frames without triangles."""
+        t = {k: np.ascontiguousarray(tables[k], dtype=np.float64).ravel() for k in ("points", "values", "gradients", "transforms")}
+        t.update({k: np.ascontiguousarray(tables[k], dtype=np.int32).ravel()
+                  for k in ("simplices", "neighbours", "point_offsets", "triangle_offsets")})
+        if t["point_offsets"].size != int(n_frames) + 1 or t["triangle_offsets"].size != int(n_frames) + 1:
+            raise ValueError("point_offsets and triangle_offsets hold n_frames + 1 entries")
+        n_points, n_triangles = int(t["point_offsets"][-1]), int(t["triangle_offsets"][-1])
+        for key, per, n in (("points", 2, n_points), ("values", 2, n_points), ("gradients", 4, n_points), ("transforms", 6, n_triangles),
+                            ("simplices", 3, n_triangles), ("neighbours", 3, n_triangles)):
+            if t[key].size != per * n:
+                raise ValueError(f"{key} holds {t[key].size} numbers, the offsets say {per * n}")
+            if t[key].size == 0:
+                t[key] = np.zeros(1, dtype=t[key].dtype)            # never a NULL pointer
+        counts = np.zeros(2, dtype=np.int64)
+        self._call("vof_piv_upsample", (v_x, v_y, speed), int(n_frames), _ptr(t["points"]), _ptr(t["values"]), _ptr(t["gradients"]),
+                   _ptr(t["simplices"]), _ptr(t["neighbours"]), _ptr(t["transforms"]), _ptr(t["point_offsets"]),
+                   _ptr(t["triangle_offsets"]), int(frames_in_flight), _ptr(v_x), _ptr(v_y), _ptr(speed), _ptr(counts))
+        return counts
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

@@ -21,6 +21,7 @@
 #include "vof_resize.hpp"
 #include "vof_farneback.hpp"
 #include "vof_intensity.hpp"
+#include "vof_piv.hpp"
 #include "../../include/vof.h"
 
 #include <fcntl.h>
@@ -5042,6 +5043,117 @@ int vof_intensity_hist_dev(vof_ctx* c, const double* movie, int n_frames, const 
 int vof_intensity_hist_host(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, int blur_radius, const double* edges,
                             int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite) {
     return intensity_hist_impl(c, movie, n_frames, blur_weights, blur_radius, edges, bins, frames_in_flight, counts, nonfinite, true);
+}
+
+// ---- the dense part of convert_PIV_result (upsample_PIV_vectors; vof_piv.hpp) --------------------------------
+// What the kernels index with comes from the caller: every table is checked on the host before anything is uploaded.
+struct PivRequest {
+    int n_frames;
+    const double *points, *values, *grads, *transforms;
+    const int32_t *simplices, *neighbours, *pt_off, *tri_off;
+};
+
+static int piv_check(vof_ctx* c, const PivRequest& r, int* max_points, int* max_triangles) {
+    if (frame_stride(c) >= (size_t)PIV_NONE) { c->err = "PIV upsampling: frames of 2^31 pixels or more are not served"; return -1; }
+    if (r.pt_off[0] != 0 || r.tri_off[0] != 0) { c->err = "PIV upsampling: the offsets must start at 0"; return -1; }
+    *max_points = *max_triangles = 0;
+    for (int f = 0; f < r.n_frames; ++f) {
+        const int np = r.pt_off[f + 1] - r.pt_off[f], nt = r.tri_off[f + 1] - r.tri_off[f];
+        if (np < 0 || nt < 0 || (nt > 0 && np < 3)) { c->err = "PIV upsampling: bad offsets in frame " + std::to_string(f); return -1; }
+        *max_points = std::max(*max_points, np); *max_triangles = std::max(*max_triangles, nt);
+        const double* P = r.points + (size_t)2 * r.pt_off[f];
+        for (int k = 0; k < 2 * np; ++k)
+            if (!std::isfinite(P[k]) || !std::isfinite(r.values[(size_t)2 * r.pt_off[f] + k]) || !std::isfinite(r.grads[(size_t)4 * r.pt_off[f] + 2 * k]) ||
+                !std::isfinite(r.grads[(size_t)4 * r.pt_off[f] + 2 * k + 1])) {
+                c->err = "PIV upsampling: a point, a vector or a gradient of frame " + std::to_string(f) + " is not finite"; return -1;
+            }
+        for (size_t k = (size_t)3 * r.tri_off[f]; k < (size_t)3 * r.tri_off[f + 1]; ++k)
+            if (r.simplices[k] < 0 || r.simplices[k] >= np || r.neighbours[k] < -1 || r.neighbours[k] >= nt) {
+                c->err = "PIV upsampling: a simplex or a neighbour of frame " + std::to_string(f) + " is outside its tables"; return -1;
+            }
+        for (size_t k = (size_t)6 * r.tri_off[f]; k < (size_t)6 * r.tri_off[f + 1]; ++k)
+            if (!std::isfinite(r.transforms[k])) {
+                c->err = "PIV upsampling: frame " + std::to_string(f) + " has a degenerate simplex (its transform is not finite): evaluate it "
+                         "on the host and pass it without triangles";
+                return -1;
+            }
+    }
+    return 0;
+}
+
+static int piv_upsample_impl(vof_ctx* c, const PivRequest& r, int flight, double* v_x, double* v_y, double* speed, int64_t* counts, bool host) {
+    if (int rc = FrameChunks::check(c, {r.points, r.values, r.grads, r.transforms, r.simplices, r.neighbours, r.pt_off, r.tri_off, v_x, v_y, speed, counts},
+                                    r.n_frames, "n_frames")) return rc;
+    int mp = 0, mt = 0;
+    if (int rc = piv_check(c, r, &mp, &mt)) return rc;
+    const size_t fs = frame_stride(c);
+    FrameChunks fc(c, "PIV upsampling", r.n_frames, flight, host);
+    // per frame in flight: its tables at the size of the call's largest frame (a chunk's tables are uploaded frame after frame, so
+    // they fit whatever the frames), the coefficients and the map; once: the offsets and the counter
+    double *d_pts, *d_val, *d_grad, *d_tr, *d_coef;
+    int *d_simp, *d_nb, *d_map, *d_ptoff, *d_trioff;
+    unsigned long long* d_outside;
+    fc.sc.per_unit(&d_pts, (size_t)2 * mp); fc.sc.per_unit(&d_val, (size_t)2 * mp); fc.sc.per_unit(&d_grad, (size_t)4 * mp);
+    fc.sc.per_unit(&d_tr, (size_t)6 * mt); fc.sc.per_unit(&d_coef, (size_t)PIV_COEF * mt);
+    fc.sc.per_unit(&d_simp, (size_t)3 * mt); fc.sc.per_unit(&d_nb, (size_t)3 * mt);
+    fc.sc.per_unit(&d_map, fs);
+    fc.sc.once(&d_ptoff, (size_t)r.n_frames + 1); fc.sc.once(&d_trioff, (size_t)r.n_frames + 1);
+    fc.sc.once(&d_outside, 1);
+    fc.output(v_x, fs * sizeof(double)); fc.output(v_y, fs * sizeof(double)); fc.output(speed, fs * sizeof(double));
+    if (int rc = fc.plan()) return rc;
+    if (int rc = h2d_bounced(c, d_ptoff, r.pt_off, ((size_t)r.n_frames + 1) * sizeof(int32_t))) return rc;
+    if (int rc = h2d_bounced(c, d_trioff, r.tri_off, ((size_t)r.n_frames + 1) * sizeof(int32_t))) return rc;
+    HIPCHK(hipMemsetAsync(d_outside, 0, sizeof(unsigned long long), c->stream));
+    static_assert(PIV_NONE == 0x7f7f7f7f, "the map is filled bytewise");
+    if (int rc = fc.run([&](int k0, int nf, const double* const*, void* const* out) -> int {
+            const size_t p0 = r.pt_off[k0], np = (size_t)r.pt_off[k0 + nf] - p0, t0 = r.tri_off[k0], nt = (size_t)r.tri_off[k0 + nf] - t0;
+            int most = 0;                                           // triangles of the chunk's largest frame
+            for (int f = k0; f < k0 + nf; ++f) most = std::max(most, r.tri_off[f + 1] - r.tri_off[f]);
+            if (np) {
+                if (int rc = h2d_bounced(c, d_pts, r.points + 2 * p0, 2 * np * sizeof(double))) return rc;
+                if (int rc = h2d_bounced(c, d_val, r.values + 2 * p0, 2 * np * sizeof(double))) return rc;
+                if (int rc = h2d_bounced(c, d_grad, r.grads + 4 * p0, 4 * np * sizeof(double))) return rc;
+            }
+            if (nt) {
+                if (int rc = h2d_bounced(c, d_tr, r.transforms + 6 * t0, 6 * nt * sizeof(double))) return rc;
+                if (int rc = h2d_bounced(c, d_simp, r.simplices + 3 * t0, 3 * nt * sizeof(int32_t))) return rc;
+                if (int rc = h2d_bounced(c, d_nb, r.neighbours + 3 * t0, 3 * nt * sizeof(int32_t))) return rc;
+            }
+            const PivTables tb{d_pts, d_val, d_grad, d_tr, d_simp, d_nb, d_ptoff + k0, d_trioff + k0};
+            HIPCHK(hipMemsetAsync(d_map, 0x7f, (size_t)nf * fs * sizeof(int), c->stream));
+            if (most) {
+                {
+                    Prof prof(c, VOF_K_REDUCE, PIV_ST_COEFFS, 8.0 * (PIV_COEF + 20) * (double)nt / nf);
+                    k_piv_coeffs<<<dim3((most + PIV_BLOCK - 1) / PIV_BLOCK, nf), PIV_BLOCK, 0, c->stream>>>(tb, d_coef);
+                }
+                {
+                    Prof prof(c, VOF_K_REDUCE, PIV_ST_LOCATE);
+                    k_piv_locate<<<dim3((most + PIV_TRI_PER_BLOCK - 1) / PIV_TRI_PER_BLOCK, nf), PIV_BLOCK, 0, c->stream>>>(tb, d_coef, d_map, c->Ni, c->Nj);
+                }
+            }
+            Prof prof(c, VOF_K_REDUCE, PIV_ST_EVAL, 28.0 * fs);
+            k_piv_eval<<<dim3((unsigned)((fs + PIV_BLOCK - 1) / PIV_BLOCK), nf), PIV_BLOCK, 0, c->stream>>>(tb, d_coef, d_map, c->Ni, c->Nj, (double*)out[0],
+                                                                                                      (double*)out[1], (double*)out[2], d_outside);
+            return 0;
+        })) return rc;
+    unsigned long long outside;
+    if (int rc = d2h_bounced(c, &outside, d_outside, sizeof outside)) return rc;
+    counts[0] = (int64_t)outside; counts[1] = 0;
+    for (int f = 0; f < r.n_frames; ++f) counts[1] += r.tri_off[f + 1] == r.tri_off[f];
+    return 0;
+}
+
+int vof_piv_upsample_dev(vof_ctx* c, int n_frames, const double* points, const double* values, const double* gradients, const int32_t* simplices,
+                         const int32_t* neighbours, const double* transforms, const int32_t* point_offsets, const int32_t* triangle_offsets,
+                         int frames_in_flight, double* v_x, double* v_y, double* speed, int64_t* counts) {
+    return piv_upsample_impl(c, PivRequest{n_frames, points, values, gradients, transforms, simplices, neighbours, point_offsets, triangle_offsets},
+                             frames_in_flight, v_x, v_y, speed, counts, false);
+}
+int vof_piv_upsample_host(vof_ctx* c, int n_frames, const double* points, const double* values, const double* gradients, const int32_t* simplices,
+                          const int32_t* neighbours, const double* transforms, const int32_t* point_offsets, const int32_t* triangle_offsets,
+                          int frames_in_flight, double* v_x, double* v_y, double* speed, int64_t* counts) {
+    return piv_upsample_impl(c, PivRequest{n_frames, points, values, gradients, transforms, simplices, neighbours, point_offsets, triangle_offsets},
+                             frames_in_flight, v_x, v_y, speed, counts, true);
 }
 
 // the six stacks of two results as inputs of a frame-chunk walk, and those of one chunk as the kernels take them

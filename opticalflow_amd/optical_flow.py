@@ -65,7 +65,7 @@ atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
-           "compare_flow_results", "filter_PIV_flow_result", "correct_intensity_change", "intensity_histograms",
+           "compare_flow_results", "filter_PIV_flow_result", "convert_PIV_result", "upsample_PIV_vectors", "piv_tables", "correct_intensity_change", "intensity_histograms",
            "apply_adaptive_threshold", "apply_clahe", "downsample_movie", "conduct_opencv_flow", "farneback_plan",
            "calcOpticalFlowFarneback", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_FARNEBACK_GAUSSIAN",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
@@ -1312,6 +1312,179 @@ def compare_channel_flows(movie_a, movie_b, boxsize=31, delta_x=1.0, delta_t=1.0
     if filename is not None:
         np.save(filename, result)
     return result
+
+
+# ---------------------------------------------------------------------------------------------------------
+# A PIVlab result as a dense flow result (OF.py:2141-2230): scipy's Delaunay triangulation and gradient estimate per frame
+# on the host, the Clough-Tocher interpolant at every pixel on the device.  DESIGN.md section 19.
+# ---------------------------------------------------------------------------------------------------------
+PIV_KEYS = ("x", "y", "u_original", "v_original")
+
+
+def _piv_frame_on_host(tri):
+    """A triangulation with a degenerate simplex (scipy marks it with NaN in ``tri.transform`` and treats it specially in
+    ``find_simplex``): its frame is evaluated by scipy itself."""
+    return bool(np.isnan(tri.transform).any())
+
+
+def _piv_stacks(x_locations, y_locations, v_x, v_y):
+    """The four inputs as float64 ``(F, R, C)`` arrays of one shape (each an array of that shape or ``F`` separate ``(R, C)`` arrays)."""
+    stacks = []
+    for name, a in zip(("x_locations", "y_locations", "v_x", "v_y"), (x_locations, y_locations, v_x, v_y)):
+        try:
+            a = np.asarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be an (F, R, C) array or F arrays of one shape (R, C)") from None
+        if a.ndim != 3 or a.shape[0] < 1:
+            raise ValueError(f"{name} must be an (F, R, C) array or F arrays of one shape (R, C), with F >= 1")
+        stacks.append(a)
+    if any(a.shape != stacks[0].shape for a in stacks):
+        raise ValueError("x_locations, y_locations, v_x and v_y must have one common shape (F, R, C)")
+    return stacks
+
+
+def piv_tables(x_locations, y_locations, v_x, v_y):
+    """The host part of ``upsample_PIV_vectors``: per frame the valid points (neither ``v_x`` nor ``v_y`` is NaN, OF.py:2195), their
+    ``scipy.spatial.Delaunay`` triangulation (scipy's defaults, what ``griddata`` makes) and the gradients
+    ``CloughTocher2DInterpolator(tri, (v_x, v_y)).grad`` (tol 1e-6, maxiter 400): one triangulation and one estimate for both fields,
+    which equals the reference's two ``griddata`` calls bit for bit.  A frame whose locations and valid mask are those of the frame
+    before keeps its triangulation.  Returns the tables ``Solver.piv_upsample`` takes, by name, and under ``"host_frames"`` a dict
+    ``{frame: interpolant}`` of the frames with a degenerate simplex, which are left without triangles."""
+    from scipy.interpolate import CloughTocher2DInterpolator
+    from scipy.spatial import Delaunay
+    x, y, vx, vy = _piv_stacks(x_locations, y_locations, v_x, v_y)
+    rows = {k: [] for k in ("points", "values", "gradients", "transforms", "simplices", "neighbours")}
+    point_offsets, triangle_offsets, host_frames = [0], [0], {}
+    previous, tri = None, None
+    for k in range(x.shape[0]):
+        valid = np.logical_and(~np.isnan(vx[k]), ~np.isnan(vy[k]))
+        points = np.stack([x[k][valid].ravel(), y[k][valid].ravel()], axis=1)
+        values = np.stack([vx[k][valid].ravel(), vy[k][valid].ravel()], axis=1)
+        key = (points.tobytes(), valid.tobytes())
+        if key != previous:
+            tri, previous = Delaunay(points), key
+        interpolant = CloughTocher2DInterpolator(tri, values)
+        if _piv_frame_on_host(tri):
+            host_frames[k] = interpolant
+        else:
+            rows["points"].append(points.ravel()), rows["values"].append(values.ravel())
+            rows["gradients"].append(np.asarray(interpolant.grad, dtype=np.float64).ravel())
+            rows["transforms"].append(np.asarray(tri.transform, dtype=np.float64).ravel())
+            rows["simplices"].append(tri.simplices.astype(np.int32).ravel()), rows["neighbours"].append(tri.neighbors.astype(np.int32).ravel())
+        here = k not in host_frames
+        point_offsets.append(point_offsets[-1] + (points.shape[0] if here else 0))
+        triangle_offsets.append(triangle_offsets[-1] + (tri.simplices.shape[0] if here else 0))
+    tables = {k: (np.concatenate(v) if v else np.zeros(0, dtype=np.int32 if k in ("simplices", "neighbours") else np.float64))
+              for k, v in rows.items()}
+    tables["point_offsets"] = np.asarray(point_offsets, dtype=np.int32)
+    tables["triangle_offsets"] = np.asarray(triangle_offsets, dtype=np.int32)
+    tables["host_frames"] = host_frames
+    return tables
+
+
+def _upsample_PIV_vectors(x_locations, y_locations, v_x, v_y, shape, device, output):
+    """``upsample_PIV_vectors`` and the counts of the native call: pixels outside every triangle, frames evaluated on the host."""
+    side = _side(output, device)
+    stacks = _piv_stacks(x_locations, y_locations, v_x, v_y)
+    try:
+        N_i, N_j = (int(n) for n in shape)
+        whole = (N_i, N_j) == tuple(shape)
+    except (TypeError, ValueError):
+        whole = False
+    if not whole or min(N_i, N_j) < 4:
+        raise ValueError("shape must be (N_i, N_j), two integers of at least 4")
+    tables = piv_tables(*stacks)
+    F = stacks[0].shape[0]
+    outs = [side.empty((F, N_i, N_j)) for _ in range(3)]
+    with _device_context(N_i, N_j, 1, device) as solver:
+        side.wait()
+        counts = solver.piv_upsample(tables, F, *outs)
+    q_i, q_j = np.meshgrid(np.arange(N_i, dtype=np.float64), np.arange(N_j, dtype=np.float64), indexing="ij")
+    for k, interpolant in tables["host_frames"].items():
+        v = interpolant(q_j, q_i)
+        fields = (v[..., 0], v[..., 1], np.sqrt(v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]))
+        for out, field in zip(outs, fields):
+            if isinstance(out, np.ndarray):
+                out[k] = field
+            else:
+                out[k].copy_(side.torch.as_tensor(np.ascontiguousarray(field)))
+        counts[0] += int(np.isnan(fields[0]).sum())
+    return tuple(outs), counts
+
+
+def upsample_PIV_vectors(x_locations, y_locations, v_x, v_y, shape, *, device=0, output="numpy"):
+    """PIV vectors on their own grid as dense fields: ``scipy.interpolate.griddata(..., method='cubic')`` of ``v_x`` and of ``v_y`` at
+    every pixel of ``F`` frames of ``shape = (N_i, N_j)`` - the dense part of ``convert_PIV_result`` (OF.py:2193-2209), evaluated on the
+    GPU.  Returns ``(v_x, v_y, speed)``, float64 ``(F, N_i, N_j)``.
+
+    The four inputs are ``(F, R, C)`` arrays, or ``F`` separate ``(R, C)`` arrays each, with NaN for a missing vector - what
+    ``analysis/postprocess_PIV.py:convert_PIV_result`` returns.  Per frame the valid points are those where neither ``v_x`` nor
+    ``v_y`` is NaN; scipy triangulates them and estimates the gradients on the host (``piv_tables``), the device evaluates the
+    Clough-Tocher element of every triangle:
+
+    - ``out[k, i, j]`` is the interpolant at the point ``(x = j, y = i)``, which is what the reference's ``np.meshgrid`` gives for the
+      square movies it can handle (for a non-square movie the reference raises a broadcast error; here the same rule serves it);
+    - a pixel outside the convex hull of the frame's valid points is NaN in all three outputs;
+    - ``speed = sqrt(v_x * v_x + v_y * v_y)``;
+    - a pixel on an edge or a vertex belongs to the triangle of the lowest index, and powers are products, so the values differ from
+      scipy's own evaluation by a few roundings (tests/test_piv_convert_cpu.py has the measured bound);
+    - a frame whose triangulation has a degenerate simplex is evaluated by scipy on the host and copied into the outputs.
+
+    ``ValueError``, before the library is touched, for inputs that are not four arrays of one shape ``(F, R, C)``, a ``shape`` that is
+    not two integers of at least 4 and an unknown ``output``; scipy's own error for a frame that cannot be triangulated propagates.
+    ``output="torch"``: the three results are float64 tensors on the device."""
+    return _upsample_PIV_vectors(x_locations, y_locations, v_x, v_y, shape, device, output)[0]
+
+
+def _piv_frames(PIV_result, key):
+    """The 2-D arrays of ``PIV_result[key]``: ``scipy.io.loadmat``'s object array whose ``[k][0]`` is the frame, or a sequence of them."""
+    try:
+        listed = PIV_result[key]
+        frames = [a[0] if isinstance(a, np.ndarray) and a.dtype == object else a for a in (listed[k] for k in range(len(listed)))]
+        frames = [np.asarray(a) for a in frames]
+    except (KeyError, TypeError, IndexError):
+        raise ValueError(f"PIV_result[{key!r}] must hold one 2-D array per frame (a PIVlab file as scipy.io.loadmat returns it)") from None
+    if not frames or any(a.ndim != 2 or a.dtype == object or a.shape != frames[0].shape for a in frames):
+        raise ValueError(f"PIV_result[{key!r}] must hold one 2-D array per frame, all of one shape")
+    return frames
+
+
+def convert_PIV_result(PIV_result, movie, delta_x=1.0, delta_t=1.0, *, device=0, output="numpy"):
+    """The reference's ``convert_PIV_result`` (OF.py:2141-2230): a PIVlab result as a flow-result dictionary, the vectors upsampled
+    to every pixel by ``upsample_PIV_vectors`` on the GPU instead of two ``scipy.interpolate.griddata`` calls per frame.
+
+    ``PIV_result`` is what ``scipy.io.loadmat`` returns for a PIVlab file - ``PIV_result[key]`` an object array whose ``[k][0]`` is a
+    2-D array, for the keys ``'x'``, ``'y'``, ``'u_original'``, ``'v_original'`` - or a plain sequence of 2-D arrays per key.
+    ``movie`` is ``(T, N_i, N_j)``; only its shape is read.  Returns the reference's dictionary: ``v_x``, ``v_y``, ``speed`` (float64,
+    ``(T - 1, N_i, N_j)``), ``delta_x``, ``delta_t``, ``original_data`` (``movie`` itself), ``x_locations``, ``y_locations``,
+    ``PIV_v_x``, ``PIV_v_y`` (float64, one ``(R, C)`` frame per frame of ``PIV_result``).
+
+    As in the reference (OF.py:2167-2181) the locations are ``x * delta_x`` and the vectors ``u * delta_x / delta_t``, numpy on the
+    host, while the interpolation targets stay the pixel indices ``(x = j, y = i)``: that is consistent only for ``delta_x = 1``,
+    which the reference's script uses, and it is kept.  Non-square movies are served by the same rule (the reference raises a
+    broadcast error for them).  Frames of ``PIV_result`` past the first ``T - 1`` are unpacked and not upsampled, as in the reference;
+    fewer than ``T - 1`` is a ``ValueError``.  ``output="torch"``: ``v_x``, ``v_y`` and ``speed`` are device tensors, which
+    ``filter_PIV_flow_result`` and ``compare_flow_results`` take as they are (``original_data`` must then be a device tensor for the
+    filter); everything else is host data."""
+    _side(output, device)
+    shape = _movie_shape(movie)
+    frames = {key: _piv_frames(PIV_result, key) for key in PIV_KEYS}
+    if len({(len(f), f[0].shape) for f in frames.values()}) != 1:
+        raise ValueError("'x', 'y', 'u_original' and 'v_original' of PIV_result must hold the same number of frames of one shape")
+    if len(frames["x"]) < shape[0] - 1:
+        raise ValueError(f"PIV_result holds {len(frames['x'])} frames, the movie needs {shape[0] - 1}")
+    unpacked = {key: np.zeros((len(frames[key]),) + frames[key][0].shape) for key in PIV_KEYS}
+    for k in range(len(frames["x"])):
+        unpacked["x"][k] = frames["x"][k] * delta_x
+        unpacked["y"][k] = frames["y"][k] * delta_x
+        unpacked["u_original"][k] = frames["u_original"][k] * delta_x / delta_t
+        unpacked["v_original"][k] = frames["v_original"][k] * delta_x / delta_t
+    P = shape[0] - 1
+    v_x, v_y, speed = upsample_PIV_vectors(unpacked["x"][:P], unpacked["y"][:P], unpacked["u_original"][:P], unpacked["v_original"][:P],
+                                           shape[1:], device=device, output=output)
+    return {"v_x": v_x, "v_y": v_y, "speed": speed, "delta_x": delta_x, "delta_t": delta_t, "original_data": movie,
+            "x_locations": unpacked["x"], "y_locations": unpacked["y"], "PIV_v_x": unpacked["u_original"],
+            "PIV_v_y": unpacked["v_original"]}
 
 
 # ---------------------------------------------------------------------------------------------------------
