@@ -657,6 +657,42 @@ int vof_piv_upsample_host(vof_ctx* ctx, int n_frames, const double* points, cons
                           const int32_t* triangle_offsets, int frames_in_flight, double* v_x, double* v_y, double* speed,
                           int64_t* counts);
 
+/* optical_flow.conduct_piv: direct (spatial-domain) zero-normalised cross-correlation PIV of the n_pairs frame pairs of
+ * movie (n_pairs + 1 float64 frames of n_i x n_j), in n_passes passes (1 to 8) with integer window offsets from the pass
+ * before.  Pass p has the window size w_p = window_sizes[p], the search radius r_p = search_radii[p] and the step
+ * s_p = steps[p] (int32 each); its margin is m_p = r_0 + ... + r_p and its grid R_p = (n_i - w_p - 2 m_p) / s_p + 1,
+ * C_p likewise from n_j (integer division); window (a, b) has its top-left pixel at i0 = m_p + a s_p, j0 = m_p + b s_p.
+ * Refused with -1 and a message, before anything is uploaded: w outside [4, 64], r outside [1, 16], s < 1, a w that grows
+ * from one pass to the next, an empty grid (n_i or n_j < w_p + 2 m_p), R_p > 65535, a window whose LDS need
+ * 8 (w (w|1) + S (S|1) + 2 S D) bytes, S = w + 2 r, D = 2 r + 1, exceeds 160 KiB - 2 KiB (no accepted w and r does).
+ * float64, every operation single and uncontracted, in the order of tests/piv_flow_restatement.py:
+ *   offset: (0, 0) in pass 0; later the vector (u', v') of the pass before at a' = clamp(floor((2 (i0 - m_{p-1}) + w_p -
+ *     w_{p-1} + s_{p-1}) / (2 s_{p-1})), 0, R_{p-1} - 1), b' likewise: o_i = (int) floor(v' + 0.5), o_j = (int) floor(u' + 0.5),
+ *     (0, 0) if the vector is NaN.  |o| <= m_{p-1}, so no search region leaves the frame.  Computed on the device.
+ *   sums: A the w x w window of frame k at (i0, j0), B_d that of frame k + 1 at (i0 + o_i + d_i, j0 + o_j + d_j), d in
+ *     [-r, r]^2.  S_a, S_aa, S_b, S_bb, S_ab: each window row summed left to right from 0.0, the row sums added top to bottom
+ *     from 0.0, every product rounded before it is added.
+ *   correlation: n = w w, D_a = n S_aa - S_a S_a, D_b = n S_bb - S_b S_b, C(d) = (n S_ab - S_a S_b) / sqrt(D_a D_b);
+ *     !(D_a > 0): a flat window, u, v and correlation NaN; !(D_b > 0): C(d) = -inf.
+ *   peak: the first maximum of C in raster order over (d_i, d_j), c0; c0 = -inf: u and v NaN (counted as flat).
+ *   subpixel, per axis, where the peak is not on the border of the search range on that axis and both neighbours c-, c+ are
+ *     finite: den = 2.0 * ((c- - 2.0 * c0) + c+); den < 0: delta = (c- - c+) / den; otherwise delta = 0.
+ *   v = (double)(o_i + d_i) + delta_i (along rows), u = (double)(o_j + d_j) + delta_j (along columns), pixels per frame.
+ *   c0 < min_correlation (NaN: no threshold): u and v NaN, the correlation is kept; in every pass.
+ * u, v, correlation: the last pass, n_pairs x R x C doubles each.  counts (host, n_passes x 3 int64): windows that are flat
+ * (or have no valid displacement), whose peak lies on the border of the search range, that fell under the threshold.
+ * The movie must be finite.  Pairs are walked in chunks of frames_in_flight (0: sized from the free device memory, 16 at most);
+ * scratch per pair in flight: the vectors of the earlier passes and two int32 per window.  Integer atomics only: results
+ * are the same from call to call and for every frames_in_flight.
+ * Profiler: class VOF_K_REDUCE, `level` 7 the offsets, 8 + p the correlation of pass p.
+ * _dev: movie, u, v and correlation are device pointers; _host: host pointers, staged through the pinned bounce buffer. */
+int vof_piv_flow_dev(vof_ctx* ctx, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes,
+                     const int32_t* search_radii, const int32_t* steps, double min_correlation, int frames_in_flight, double* u,
+                     double* v, double* correlation, int64_t* counts);
+int vof_piv_flow_host(vof_ctx* ctx, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes,
+                      const int32_t* search_radii, const int32_t* steps, double min_correlation, int frames_in_flight, double* u,
+                      double* v, double* correlation, int64_t* counts);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

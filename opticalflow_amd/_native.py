@@ -141,6 +141,7 @@ TWINS = {
     "vof_intensity_correct": [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "vof_intensity_hist": [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp],
     "vof_piv_upsample": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
+    "vof_piv_flow": [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp, _vp, _vp],
 }
 SIGNATURES.update({name + twin: (C.c_int, args) for name, args in TWINS.items() for twin in ("_host", "_dev")})
 
@@ -707,6 +708,21 @@ class Solver:
         self._call("vof_piv_upsample", (v_x, v_y, speed), int(n_frames), _ptr(t["points"]), _ptr(t["values"]), _ptr(t["gradients"]),
                    _ptr(t["simplices"]), _ptr(t["neighbours"]), _ptr(t["transforms"]), _ptr(t["point_offsets"]),
                    _ptr(t["triangle_offsets"]), int(frames_in_flight), _ptr(v_x), _ptr(v_y), _ptr(speed), _ptr(counts))
+        return counts
+
+    # -- conduct_piv (vof_pivflow.hpp)
+    def piv_flow(self, movie, n_pairs, window_sizes, search_radii, steps, u, v, correlation, min_correlation=None, frames_in_flight=0):
+        """``vof_piv_flow_*``: cross-correlation PIV of the ``n_pairs`` pairs of ``movie`` (``n_pairs + 1`` float64 frames) in
+        ``len(window_sizes)`` passes into ``u``, ``v`` and ``correlation`` (float64, ``(n_pairs, R, C)`` of the last pass, numpy arrays or
+        device memory like the movie).  ``min_correlation=None``: no threshold.  Returns ``counts``, int64 ``(passes, 3)``: flat windows,
+        peaks on the border of the search range, vectors under the threshold."""
+        w, r, s = (np.ascontiguousarray(a, dtype=np.int32).ravel() for a in (window_sizes, search_radii, steps))
+        if not (w.size == r.size == s.size >= 1):
+            raise ValueError("window_sizes, search_radii and steps hold one entry per pass")
+        counts = np.zeros((w.size, 3), dtype=np.int64)
+        self._call("vof_piv_flow", (movie, u, v, correlation), _ptr(movie), int(n_pairs), w.size, _ptr(w), _ptr(r), _ptr(s),
+                   float("nan") if min_correlation is None else float(min_correlation), int(frames_in_flight), _ptr(u), _ptr(v),
+                   _ptr(correlation), _ptr(counts))
         return counts
 
     def field_moments_dev(self, field, n):

@@ -22,6 +22,7 @@
 #include "vof_farneback.hpp"
 #include "vof_intensity.hpp"
 #include "vof_piv.hpp"
+#include "vof_pivflow.hpp"
 #include "../../include/vof.h"
 
 #include <fcntl.h>
@@ -164,6 +165,7 @@ struct vof_ctx {
     double *dir_R = nullptr, *dir_C = nullptr, *dir_D = nullptr;   // blocked inverse: row panel, column panel, inverted diagonal tile
     int dir_ld = 0;                  // leading dimension of the dense blocks (m, or m rounded up to the tile size of the blocked inverse)
     long long direct_pairs = 0;      // pairs solved with the direct preconditioner since the context was created
+    size_t pivflow_lds[2] = {0, 0};  // dynamic LDS k_pivflow_correlate<PF_SHORT_RUN / PF_LONG_RUN> may ask for (raised on first need)
     // what a level-0 pass may take on besides its sweeps (plan_l0_pass decides; the requests travel in CycleIO / SmoothArgs)
     bool fuse_rr = true;        // VOF_FUSE_RR=0: the stand-alone kernel k_stream_resrestrict0 instead of the trailing stage of the
                                 // pre-smoothing pass (k_sweep0r, TRAIL = 2)
@@ -5154,6 +5156,103 @@ int vof_piv_upsample_host(vof_ctx* c, int n_frames, const double* points, const 
                           int frames_in_flight, double* v_x, double* v_y, double* speed, int64_t* counts) {
     return piv_upsample_impl(c, PivRequest{n_frames, points, values, gradients, transforms, simplices, neighbours, point_offsets, triangle_offsets},
                              frames_in_flight, v_x, v_y, speed, counts, true);
+}
+
+// ---- conduct_piv: windowed cross-correlation PIV of every pair of a stack (vof_pivflow.hpp) -----------------
+// The passes of a request, checked: what include/vof.h lists, and that every search region stays inside the frame for the largest
+// offset the pass before can hand on (its margin).  Nothing is uploaded before this returns 0.
+static int piv_flow_passes(vof_ctx* c, int n_passes, const int32_t* w, const int32_t* r, const int32_t* s, PfPass* P) {
+    if (n_passes < 1 || n_passes > PF_MAX_PASSES) { c->err = "PIV: n_passes must lie in [1, " + std::to_string(PF_MAX_PASSES) + "]"; return -1; }
+    int m = 0;
+    for (int p = 0; p < n_passes; ++p) {
+        const std::string at = "PIV pass " + std::to_string(p) + ": ";
+        if (w[p] < PF_MIN_W || w[p] > PF_MAX_W) { c->err = at + "the window size must lie in [4, 64]"; return -1; }
+        if (r[p] < 1 || r[p] > PF_MAX_R) { c->err = at + "the search radius must lie in [1, 16]"; return -1; }
+        if (s[p] < 1) { c->err = at + "the step must be >= 1"; return -1; }
+        if (p > 0 && w[p] > w[p - 1]) { c->err = at + "window sizes must not increase from pass to pass"; return -1; }
+        if (pf_lds_doubles(w[p], r[p]) * sizeof(double) > PF_LDS_LIMIT || pf_items(r[p]) > PF_BLOCK) {
+            c->err = at + "the window and its search region do not fit the LDS of a compute unit"; return -1;
+        }
+        m += r[p];
+        const int span = w[p] + 2 * m;
+        if (c->Ni < span || c->Nj < span) { c->err = at + "the grid is empty: the frame is smaller than window + 2 * margin = " + std::to_string(span); return -1; }
+        P[p] = PfPass{w[p], r[p], s[p], m, (c->Ni - span) / s[p] + 1, (c->Nj - span) / s[p] + 1};
+        if (P[p].R > 65535) { c->err = at + "more than 65535 rows of windows do not fit one launch"; return -1; }
+        // window (a, b) at m + a s; offsets |o| <= m - r, the margin of the pass before: rows [m + a s + o - r, ... + w + 2 r) of the frame
+        const int lo = m - (m - r[p]) - r[p], hi_i = m + (P[p].R - 1) * s[p] + (m - r[p]) + r[p] + w[p], hi_j = m + (P[p].C - 1) * s[p] + (m - r[p]) + r[p] + w[p];
+        if (lo < 0 || hi_i > c->Ni || hi_j > c->Nj) { c->err = at + "a search region leaves the frame"; return -1; }
+    }
+    return 0;
+}
+
+// one pass of np pairs; the run length of the hot loop goes with the radius (pf_run)
+static int piv_flow_launch(vof_ctx* c, const PfPass& p, int np, const double* frames, const int* off, double min_correlation, double* u, double* v,
+                           double* corr, unsigned long long* counts) {
+    const size_t lds = pf_lds_doubles(p.w, p.r) * sizeof(double);
+    const bool long_run = pf_run(p.r) == PF_LONG_RUN;
+    const void* kernel = long_run ? (const void*)k_pivflow_correlate<PF_LONG_RUN> : (const void*)k_pivflow_correlate<PF_SHORT_RUN>;
+    if (lds > c->pivflow_lds[long_run]) {                           // raised once per context and kernel
+        HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_LIMIT));
+        c->pivflow_lds[long_run] = PF_LDS_LIMIT;
+    }
+    const dim3 grid(p.C, p.R, np);
+    if (long_run) k_pivflow_correlate<PF_LONG_RUN><<<grid, PF_BLOCK, lds, c->stream>>>(p, frames, frame_stride(c), c->Nj, off, min_correlation, u, v, corr, counts);
+    else k_pivflow_correlate<PF_SHORT_RUN><<<grid, PF_BLOCK, lds, c->stream>>>(p, frames, frame_stride(c), c->Nj, off, min_correlation, u, v, corr, counts);
+    return 0;
+}
+
+static int piv_flow_impl(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
+                         const int32_t* steps, double min_correlation, int flight, double* u, double* v, double* correlation, int64_t* counts, bool host) {
+    if (int rc = FrameChunks::check(c, {movie, window_sizes, search_radii, steps, u, v, correlation, counts}, n_pairs, "n_pairs")) return rc;
+    PfPass P[PF_MAX_PASSES];
+    if (int rc = piv_flow_passes(c, n_passes, window_sizes, search_radii, steps, P)) return rc;
+    const int last = n_passes - 1;
+    FrameChunks fc(c, "PIV", n_pairs, flight, host);
+    fc.input(movie, true);
+    // per pair in flight: the vectors of every pass but the last, and the offsets of a pass at the size of the largest grid
+    double *d_u[PF_MAX_PASSES] = {}, *d_v[PF_MAX_PASSES] = {};
+    int* d_off = nullptr;
+    unsigned long long* d_counts = nullptr;
+    size_t most = 0;
+    for (int p = 0; p < last; ++p) {
+        fc.sc.per_unit(&d_u[p], (size_t)P[p].R * P[p].C); fc.sc.per_unit(&d_v[p], (size_t)P[p].R * P[p].C);
+        most = std::max(most, (size_t)P[p + 1].R * P[p + 1].C);
+    }
+    if (last > 0) fc.sc.per_unit(&d_off, 2 * most);
+    fc.sc.once(&d_counts, (size_t)3 * n_passes);
+    const size_t ob = (size_t)P[last].R * P[last].C * sizeof(double);
+    fc.output(u, ob); fc.output(v, ob); fc.output(correlation, ob);
+    if (int rc = fc.plan()) return rc;
+    HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)3 * n_passes * sizeof(unsigned long long), c->stream));
+    if (int rc = fc.run([&](int, int np, const double* const* in, void* const* out) -> int {
+            for (int p = 0; p < n_passes; ++p) {
+                if (p > 0) {
+                    Prof prof(c, VOF_K_REDUCE, PF_ST_OFFSETS);
+                    k_pivflow_offsets<<<dim3((P[p].R * P[p].C + PF_BLOCK - 1) / PF_BLOCK, np), PF_BLOCK, 0, c->stream>>>(P[p], P[p - 1], d_u[p - 1], d_v[p - 1], d_off);
+                }
+                double* pu = p == last ? (double*)out[0] : d_u[p];
+                double* pv = p == last ? (double*)out[1] : d_v[p];
+                double* pc = p == last ? (double*)out[2] : nullptr;
+                const double S = P[p].w + 2.0 * P[p].r;
+                Prof prof(c, VOF_K_REDUCE, PF_ST_PASS0 + p, 8.0 * (P[p].w * (double)P[p].w + S * S) * P[p].R * P[p].C);
+                const int rc = piv_flow_launch(c, P[p], np, in[0], p ? d_off : nullptr, min_correlation, pu, pv, pc, d_counts + 3 * p);
+                if (rc) return rc;
+            }
+            return 0;
+        })) return rc;
+    unsigned long long got[3 * PF_MAX_PASSES];
+    if (int rc = d2h_bounced(c, got, d_counts, (size_t)3 * n_passes * sizeof(unsigned long long))) return rc;
+    for (int k = 0; k < 3 * n_passes; ++k) counts[k] = (int64_t)got[k];
+    return 0;
+}
+
+int vof_piv_flow_dev(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
+                     const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts) {
+    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, false);
+}
+int vof_piv_flow_host(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
+                      const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts) {
+    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, true);
 }
 
 // the six stacks of two results as inputs of a frame-chunk walk, and those of one chunk as the kernels take them

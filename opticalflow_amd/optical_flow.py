@@ -65,7 +65,7 @@ atexit.register(release_device_memory)
 
 __all__ = ["variational_optical_flow", "conduct_optical_flow", "conduct_optical_flow_jit", "liu_shen_optical_flow_jit",
            "conduct_variational_optical_flow_deprecated", "vary_regularisation", "vary_boxsize", "vary_blursize", "compare_channel_flows", "make_fake_data_frame", "blur_movie",
-           "compare_flow_results", "filter_PIV_flow_result", "convert_PIV_result", "upsample_PIV_vectors", "piv_tables", "correct_intensity_change", "intensity_histograms",
+           "compare_flow_results", "filter_PIV_flow_result", "convert_PIV_result", "upsample_PIV_vectors", "piv_tables", "conduct_piv", "conduct_piv_flow", "piv_grid", "correct_intensity_change", "intensity_histograms",
            "apply_adaptive_threshold", "apply_clahe", "downsample_movie", "conduct_opencv_flow", "farneback_plan",
            "calcOpticalFlowFarneback", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_FARNEBACK_GAUSSIAN",
            "format_elapsed_time", "apply_constant_boundary_condition", "choose_pairs_in_flight",
@@ -1485,6 +1485,138 @@ def convert_PIV_result(PIV_result, movie, delta_x=1.0, delta_t=1.0, *, device=0,
     return {"v_x": v_x, "v_y": v_y, "speed": speed, "delta_x": delta_x, "delta_t": delta_t, "original_data": movie,
             "x_locations": unpacked["x"], "y_locations": unpacked["y"], "PIV_v_x": unpacked["u_original"],
             "PIV_v_y": unpacked["v_original"]}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The PIV vectors themselves: windowed cross-correlation of every frame pair on the device.  DESIGN.md section 20.
+# ---------------------------------------------------------------------------------------------------------
+PIV_MIN_WINDOW, PIV_MAX_WINDOW, PIV_MAX_RADIUS, PIV_MAX_PASSES = 4, 64, 16, 8    # PF_MIN_W, PF_MAX_W, PF_MAX_R, PF_MAX_PASSES of csrc/vof_pivflow.hpp
+PIV_LDS_LIMIT = 160 * 1024 - 2048                                                 # PF_LDS_LIMIT
+
+
+def _piv_lds_bytes(w, r):
+    """pf_lds_doubles of csrc/vof_pivflow.hpp in bytes: the window, the search region and its row sums, rows at odd strides."""
+    S, D = w + 2 * r, 2 * r + 1
+    return 8 * (w * (w | 1) + S * (S | 1) + 2 * S * D)
+
+
+def _piv_integers(name, values):
+    try:
+        listed = [values] if np.ndim(values) == 0 else list(values)
+        whole = [int(n) for n in listed]
+        if any(isinstance(n, bool) or n != m for n, m in zip(listed, whole)):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be integers, one per pass") from None
+    return whole
+
+
+def _piv_passes(shape, window_sizes, search_radii, steps):
+    """The passes as ``(w, r, s, m, R, C)`` tuples, with every check the library makes (include/vof.h) as a ``ValueError``."""
+    w, r = _piv_integers("window_sizes", window_sizes), _piv_integers("search_radii", search_radii)
+    s = [n // 2 for n in w] if steps is None else _piv_integers("steps", steps)
+    if not (1 <= len(w) <= PIV_MAX_PASSES) or len(r) != len(w) or len(s) != len(w):
+        raise ValueError(f"window_sizes, search_radii and steps must hold one entry per pass, 1 to {PIV_MAX_PASSES} passes")
+    try:
+        N_i, N_j = (int(n) for n in shape[-2:])
+    except (TypeError, ValueError):
+        raise ValueError("shape must end in (N_i, N_j)") from None
+    passes, m = [], 0
+    for p in range(len(w)):
+        if not PIV_MIN_WINDOW <= w[p] <= PIV_MAX_WINDOW:
+            raise ValueError(f"pass {p}: the window size must lie in [{PIV_MIN_WINDOW}, {PIV_MAX_WINDOW}], not {w[p]}")
+        if not 1 <= r[p] <= PIV_MAX_RADIUS:
+            raise ValueError(f"pass {p}: the search radius must lie in [1, {PIV_MAX_RADIUS}], not {r[p]}")
+        if s[p] < 1:
+            raise ValueError(f"pass {p}: the step must be at least 1, not {s[p]}")
+        if p and w[p] > w[p - 1]:
+            raise ValueError(f"pass {p}: window sizes must not increase from pass to pass ({w[p - 1]} then {w[p]})")
+        if _piv_lds_bytes(w[p], r[p]) > PIV_LDS_LIMIT:
+            raise ValueError(f"pass {p}: a {w[p]}-pixel window with radius {r[p]} does not fit the LDS of a compute unit")
+        m += r[p]
+        if min(N_i, N_j) < w[p] + 2 * m:
+            raise ValueError(f"pass {p}: the grid is empty: frames of {N_i} x {N_j} are smaller than window + 2 * margin = {w[p] + 2 * m}")
+        passes.append((w[p], r[p], s[p], m, (N_i - w[p] - 2 * m) // s[p] + 1, (N_j - w[p] - 2 * m) // s[p] + 1))
+        if passes[-1][4] > 65535:
+            raise ValueError(f"pass {p}: more than 65535 rows of windows do not fit one launch")
+    return passes
+
+
+def piv_grid(shape, window_sizes, search_radii, steps=None):
+    """The window grid of ``conduct_piv`` for frames of ``shape = (N_i, N_j)`` (a movie's shape is taken by its last two entries): per
+    pass a dict with the window size ``w``, radius ``r``, step ``s`` (``steps=None``: ``w // 2``), the margin ``m = r_0 + ... + r_p``,
+    the grid ``R = (N_i - w - 2 m) // s + 1`` and ``C`` likewise, and the 0-based window centres ``x = j0 + (w - 1) / 2``,
+    ``y = i0 + (w - 1) / 2`` as ``(R, C)`` arrays, window ``(a, b)`` having its top-left pixel at ``i0 = m + a s``, ``j0 = m + b s``.
+    With these margins no search region leaves the frame, whatever offset the pass before hands on.  A pure host function;
+    ``ValueError`` for everything ``conduct_piv`` refuses."""
+    grids = []
+    for w, r, s, m, R, C in _piv_passes(shape, window_sizes, search_radii, steps):
+        y, x = np.meshgrid(m + s * np.arange(R) + (w - 1) / 2, m + s * np.arange(C) + (w - 1) / 2, indexing="ij")
+        grids.append(dict(w=w, r=r, s=s, m=m, R=R, C=C, x=x, y=y))
+    return grids
+
+
+def conduct_piv(movie, window_sizes=(64, 32), search_radii=(16, 4), steps=None, min_correlation=None, smoothing_sigma=None, *, device=0,
+                frames_in_flight=0):
+    """Particle image velocimetry of every frame pair on the GPU: direct zero-normalised cross-correlation of interrogation windows,
+    in ``len(window_sizes)`` passes, each pass searching around the rounded vector of the pass before.  The reference imports such
+    vectors from PIVlab (``analysis/postprocess_PIV.py``); this makes them where the movie is.
+
+    ``movie`` is ``(T, N_i, N_j)``, a numpy array or a device tensor of any real dtype (read as float64), blurred on the device first
+    if ``smoothing_sigma`` is given.  Pass ``p`` correlates the ``w_p x w_p`` window of frame ``k`` at every point of ``piv_grid``
+    with the windows of frame ``k + 1`` displaced by ``offset + d``, ``d`` in ``[-r_p, r_p]^2``; the peak is the first maximum in
+    raster order, refined per axis by the three-point parabola unless it lies on the border of the search range (DESIGN.md section
+    20 has all of the arithmetic; the device is held to ``tests/piv_flow_restatement.py`` bit for bit).  ``min_correlation`` (the
+    ncorr script's 0.3, ``None``: off) makes the vectors of windows whose peak correlation is smaller NaN, in every pass.
+
+    Returns a PIVlab-shaped dict, which ``convert_PIV_result`` takes: ``'x'``, ``'y'`` (0-based window centres, ``x`` along the
+    columns), ``'u_original'`` (along the columns), ``'v_original'`` (along the rows), in pixels per frame, NaN for a missing vector
+    (a flat window, or one under the threshold), and ``'correlation'`` - float64 host arrays ``(T - 1, R, C)`` of the last pass - and
+    ``'counts'``, int64 ``(passes, 3)``: flat windows, peaks on the border of the search range, vectors under the threshold.
+
+    ``ValueError`` before the library is touched: fewer than 2 frames, window sizes outside [4, 64] or growing from pass to pass, radii
+    outside [1, 16], steps below 1, more than 8 passes, a frame smaller than ``w + 2 m`` of some pass.  The movie must be finite."""
+    shape = _movie_shape(movie, 2)
+    passes = _piv_passes(shape, window_sizes, search_radii, steps)
+    if min_correlation is not None:
+        try:
+            min_correlation = float(min_correlation)
+        except (TypeError, ValueError):
+            raise ValueError("min_correlation must be a number or None") from None
+    if smoothing_sigma is not None and not float(smoothing_sigma) > 0:
+        raise ValueError("smoothing_sigma must be positive or None")
+    on_device = _is_device_tensor(movie) and movie.is_cuda
+    if on_device and movie.device.index is not None:
+        device = movie.device.index
+    side = _side("torch" if on_device else "numpy", device)
+    T, (R, C) = shape[0], passes[-1][4:]
+    frames = side.frames(movie)
+    u, v, correlation = (side.empty((T - 1, R, C)) for _ in range(3))
+    with _device_context(shape[1], shape[2], 1, device) as solver:
+        if smoothing_sigma is not None:
+            frames = side.blurred(frames, gaussian_taps(smoothing_sigma), solver)
+        side.wait()
+        counts = solver.piv_flow(frames, T - 1, *(tuple(p[k] for p in passes) for k in range(3)), u, v, correlation, min_correlation,
+                                 frames_in_flight)
+    if not isinstance(u, np.ndarray):
+        u, v, correlation = (a.cpu().numpy() for a in (u, v, correlation))
+    last = piv_grid(shape, [p[0] for p in passes], [p[1] for p in passes], [p[2] for p in passes])[-1]
+    x, y = (np.repeat(last[key][None], T - 1, axis=0) for key in ("x", "y"))
+    return {"x": x, "y": y, "u_original": u, "v_original": v, "correlation": correlation, "counts": counts}
+
+
+def conduct_piv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *, device=0, output="numpy", **piv_arguments):
+    """``conduct_piv`` as a dense flow result: ``convert_PIV_result(conduct_piv(movie, smoothing_sigma=smoothing_sigma,
+    **piv_arguments), movie, delta_x, delta_t)`` with the peak correlations under ``'PIV_correlation'`` - the dictionary
+    ``filter_PIV_flow_result`` and ``compare_flow_results`` take, so PIV and the other estimators are compared without a PIVlab file.
+    ``piv_arguments``: ``window_sizes``, ``search_radii``, ``steps``, ``min_correlation``, ``frames_in_flight``.  ``output="torch"``:
+    ``v_x``, ``v_y`` and ``speed`` are device tensors (and ``movie`` should be one, for the filter).  Every frame pair needs at least
+    three vectors that are not collinear: scipy's error for a frame that cannot be triangulated propagates."""
+    _side(output, device)
+    PIV_result = conduct_piv(movie, smoothing_sigma=smoothing_sigma, device=device, **piv_arguments)
+    result = convert_PIV_result(PIV_result, movie, delta_x, delta_t, device=device, output=output)
+    result["PIV_correlation"] = PIV_result["correlation"]
+    return result
 
 
 # ---------------------------------------------------------------------------------------------------------
