@@ -693,6 +693,47 @@ int vof_piv_flow_host(vof_ctx* ctx, const double* movie, int n_pairs, int n_pass
                       const int32_t* search_radii, const int32_t* steps, double min_correlation, int frames_in_flight, double* u,
                       double* v, double* correlation, int64_t* counts);
 
+/* vof_piv_flow_* with two options, independent of each other; with deformation 0 and outlier_threshold NaN it is that call,
+ * bit for bit (vof_piv_flow_* is this call with everything off).  Grids, margins, limits and LDS need are unchanged.
+ * Refused with -1 and a message, besides what vof_piv_flow_* refuses: deformation or validate_last other than 0 or 1; an
+ * outlier_threshold that is neither NaN nor positive and finite; an outlier_epsilon that is not >= 0 and finite; validate_last
+ * with outlier_threshold NaN; validation_counts NULL with outlier_threshold given.
+ * float64, every operation single and uncontracted, only + - * / sqrt floor fabs fmin fmax, in the order of
+ * tests/piv_deform_restatement.py:
+ *   validation (outlier_threshold given) of the vectors of pass p before pass p + 1 uses them, and with validate_last of the
+ *     returned vectors of the last pass - the normalised median test (Westerweel & Scarano 2005), reading the unvalidated field
+ *     and writing a second one: a vector is valid when neither component is NaN; the neighbours of window (a, b) are the valid
+ *     ones among the up to eight others of its 3 x 3 neighbourhood inside the grid; fewer than 3: the window is left as it is
+ *     and not counted.  med of k values: sorted ascending (a fixed 8-input network that exchanges where y < x, absent values
+ *     +inf), the middle one for odd k, (lo + hi) * 0.5 for even k.  u_m = med(u_n), v_m = med(v_n).  Centre not valid: it becomes
+ *     (u_m, v_m), counted as filled.  Centre valid: r_u = fabs(u - u_m) / (med(fabs(u_n - u_m)) + outlier_epsilon), r_v likewise;
+ *     r_u > outlier_threshold || r_v > outlier_threshold: it becomes (u_m, v_m), counted as an outlier.  The correlation values are
+ *     never changed; counts keeps its meaning (what the correlation of the pass found).  On the integer path the offsets are then
+ *     taken from the validated vectors (a median of values bounded by m is bounded by m).
+ *   predictor from pass q = p - 1 at a real position (y, x): c = (double)m_q + (double)(w_q - 1) / 2.0; g = (y - c) / (double)s_q;
+ *     g = fmin(fmax(g, 0.0), (double)(R_q - 1)); lo = (int)floor(g), but max(R_q - 2, 0) if lo > R_q - 2; t = g - (double)lo;
+ *     hi = min(lo + 1, R_q - 1); likewise along the columns with C_q.  A vector that is not valid reads as (0, 0).  Bilinear:
+ *     top = F[lo][b] + t_b * (F[lo][b_hi] - F[lo][b]), bot likewise on row hi, value = top + t_a * (bot - top); U and V separately.
+ *   deformation, pass p >= 1: pixel (i, j) of the search region holds frame k + 1 at y = (double)i + V(i, j), x = (double)j +
+ *     U(i, j), (U, V) the predictor at ((double)i, (double)j); the region is rows i0 - r .. i0 + w + r - 1 and columns likewise -
+ *     no offset, always inside the frame; the sample by the split rule and the bilinear formula above with c = 0, s = 1 and
+ *     n = n_i resp. n_j (the clamp is part of the arithmetic).  Sums, C(d), peak, subpixel fit, threshold and counts as in
+ *     vof_piv_flow_* on that region; v = V_c + ((double)d_i + delta_i), u = U_c + ((double)d_j + delta_j), (U_c, V_c) the
+ *     predictor at the window centre (i0 + (w - 1) / 2.0, j0 + (w - 1) / 2.0).  Pass 0 is unchanged; one pass: no effect.
+ * validation_counts (host, n_passes x 2 int64, may be NULL when outlier_threshold is NaN): outliers and filled vectors per
+ * pass; the last row is zero unless validate_last.
+ * Scratch per pair in flight, besides that of vof_piv_flow_*: two doubles per window for the validated vectors (and the
+ * unvalidated ones of the last pass with validate_last); no offsets with deformation.
+ * Profiler: the validation shares `level` 7 with the offsets; a deformed pass keeps 8 + p. */
+int vof_piv_flow_ex_dev(vof_ctx* ctx, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes,
+                        const int32_t* search_radii, const int32_t* steps, double min_correlation, int frames_in_flight, double* u,
+                        double* v, double* correlation, int64_t* counts, int deformation, double outlier_threshold,
+                        double outlier_epsilon, int validate_last, int64_t* validation_counts);
+int vof_piv_flow_ex_host(vof_ctx* ctx, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes,
+                         const int32_t* search_radii, const int32_t* steps, double min_correlation, int frames_in_flight, double* u,
+                         double* v, double* correlation, int64_t* counts, int deformation, double outlier_threshold,
+                         double outlier_epsilon, int validate_last, int64_t* validation_counts);
+
 /* Mean and (population) variance of n device-resident doubles, deterministic two-pass reduction. */
 int vof_field_moments_dev(vof_ctx* ctx, const double* field_dev, size_t n, double* mean, double* variance);
 

@@ -142,6 +142,8 @@ TWINS = {
     "vof_intensity_hist": [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp],
     "vof_piv_upsample": [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp],
     "vof_piv_flow": [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp, _vp, _vp],
+    "vof_piv_flow_ex": [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double,
+                        C.c_int, _vp],
 }
 SIGNATURES.update({name + twin: (C.c_int, args) for name, args in TWINS.items() for twin in ("_host", "_dev")})
 
@@ -711,19 +713,28 @@ class Solver:
         return counts
 
     # -- conduct_piv (vof_pivflow.hpp)
-    def piv_flow(self, movie, n_pairs, window_sizes, search_radii, steps, u, v, correlation, min_correlation=None, frames_in_flight=0):
+    def piv_flow(self, movie, n_pairs, window_sizes, search_radii, steps, u, v, correlation, min_correlation=None, frames_in_flight=0, *,
+                 deformation=False, outlier_threshold=None, outlier_epsilon=0.1, validate_last=False):
         """``vof_piv_flow_*``: cross-correlation PIV of the ``n_pairs`` pairs of ``movie`` (``n_pairs + 1`` float64 frames) in
         ``len(window_sizes)`` passes into ``u``, ``v`` and ``correlation`` (float64, ``(n_pairs, R, C)`` of the last pass, numpy arrays or
         device memory like the movie).  ``min_correlation=None``: no threshold.  Returns ``counts``, int64 ``(passes, 3)``: flat windows,
-        peaks on the border of the search range, vectors under the threshold."""
+        peaks on the border of the search range, vectors under the threshold.
+
+        The call goes through ``vof_piv_flow_ex_*``, which with the keyword-only options left alone is ``vof_piv_flow_*``: ``deformation`` resamples the search regions of the later
+        passes by the interpolated vectors of the pass before, ``outlier_threshold`` (``None``: off) runs the normalised median test
+        with ``outlier_epsilon`` on the vectors of a pass before the next uses them, and with ``validate_last`` on the returned ones.
+        With ``outlier_threshold`` it returns ``(counts, validation_counts)``, the latter int64 ``(passes, 2)``: outliers, filled.  The
+        options go to the library as they are: it refuses what ``conduct_piv`` refuses."""
         w, r, s = (np.ascontiguousarray(a, dtype=np.int32).ravel() for a in (window_sizes, search_radii, steps))
         if not (w.size == r.size == s.size >= 1):
             raise ValueError("window_sizes, search_radii and steps hold one entry per pass")
         counts = np.zeros((w.size, 3), dtype=np.int64)
-        self._call("vof_piv_flow", (movie, u, v, correlation), _ptr(movie), int(n_pairs), w.size, _ptr(w), _ptr(r), _ptr(s),
+        validation_counts = None if outlier_threshold is None else np.zeros((w.size, 2), dtype=np.int64)
+        self._call("vof_piv_flow_ex", (movie, u, v, correlation), _ptr(movie), int(n_pairs), w.size, _ptr(w), _ptr(r), _ptr(s),
                    float("nan") if min_correlation is None else float(min_correlation), int(frames_in_flight), _ptr(u), _ptr(v),
-                   _ptr(correlation), _ptr(counts))
-        return counts
+                   _ptr(correlation), _ptr(counts), int(deformation), float("nan") if outlier_threshold is None else float(outlier_threshold),
+                   float(outlier_epsilon), int(validate_last), _ptr(validation_counts))
+        return counts if validation_counts is None else (counts, validation_counts)
 
     def field_moments_dev(self, field, n):
         """(mean, population variance) of ``n`` device-resident doubles."""

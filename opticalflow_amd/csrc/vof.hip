@@ -165,7 +165,7 @@ struct vof_ctx {
     double *dir_R = nullptr, *dir_C = nullptr, *dir_D = nullptr;   // blocked inverse: row panel, column panel, inverted diagonal tile
     int dir_ld = 0;                  // leading dimension of the dense blocks (m, or m rounded up to the tile size of the blocked inverse)
     long long direct_pairs = 0;      // pairs solved with the direct preconditioner since the context was created
-    size_t pivflow_lds[2] = {0, 0};  // dynamic LDS k_pivflow_correlate<PF_SHORT_RUN / PF_LONG_RUN> may ask for (raised on first need)
+    size_t pivflow_lds[4] = {0, 0, 0, 0};  // dynamic LDS k_pivflow_correlate<PF_SHORT_RUN / PF_LONG_RUN>, then their DEFORM variants, may ask for (raised on first need)
     // what a level-0 pass may take on besides its sweeps (plan_l0_pass decides; the requests travel in CycleIO / SmoothArgs)
     bool fuse_rr = true;        // VOF_FUSE_RR=0: the stand-alone kernel k_stream_resrestrict0 instead of the trailing stage of the
                                 // pre-smoothing pass (k_sweep0r, TRAIL = 2)
@@ -5185,64 +5185,111 @@ static int piv_flow_passes(vof_ctx* c, int n_passes, const int32_t* w, const int
     return 0;
 }
 
-// one pass of np pairs; the run length of the hot loop goes with the radius (pf_run)
+// one pass of np pairs; the run length of the hot loop goes with the radius (pf_run).  deform: the vectors the region is resampled by
+// (a pass after the first, off NULL), or NULL for the integer path.
 static int piv_flow_launch(vof_ctx* c, const PfPass& p, int np, const double* frames, const int* off, double min_correlation, double* u, double* v,
-                           double* corr, unsigned long long* counts) {
+                           double* corr, unsigned long long* counts, const PfDeform* deform = nullptr) {
     const size_t lds = pf_lds_doubles(p.w, p.r) * sizeof(double);
-    const bool long_run = pf_run(p.r) == PF_LONG_RUN;
-    const void* kernel = long_run ? (const void*)k_pivflow_correlate<PF_LONG_RUN> : (const void*)k_pivflow_correlate<PF_SHORT_RUN>;
-    if (lds > c->pivflow_lds[long_run]) {                           // raised once per context and kernel
-        HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_LIMIT));
-        c->pivflow_lds[long_run] = PF_LDS_LIMIT;
+    const int slot = (deform ? 2 : 0) + (pf_run(p.r) == PF_LONG_RUN ? 1 : 0);
+    const void* const kernels[4] = {(const void*)k_pivflow_correlate<PF_SHORT_RUN, false>, (const void*)k_pivflow_correlate<PF_LONG_RUN, false>,
+                                    (const void*)k_pivflow_correlate<PF_SHORT_RUN, true>, (const void*)k_pivflow_correlate<PF_LONG_RUN, true>};
+    if (lds > c->pivflow_lds[slot]) {                               // raised once per context and kernel
+        HIPCHK(hipFuncSetAttribute(kernels[slot], hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_LIMIT));
+        c->pivflow_lds[slot] = PF_LDS_LIMIT;
     }
     const dim3 grid(p.C, p.R, np);
-    if (long_run) k_pivflow_correlate<PF_LONG_RUN><<<grid, PF_BLOCK, lds, c->stream>>>(p, frames, frame_stride(c), c->Nj, off, min_correlation, u, v, corr, counts);
-    else k_pivflow_correlate<PF_SHORT_RUN><<<grid, PF_BLOCK, lds, c->stream>>>(p, frames, frame_stride(c), c->Nj, off, min_correlation, u, v, corr, counts);
+    const PfDeform df = deform ? *deform : PfDeform{};
+#define PF_LAUNCH(K, DEFORM) k_pivflow_correlate<K, DEFORM><<<grid, PF_BLOCK, lds, c->stream>>>(p, frames, frame_stride(c), c->Nj, off, min_correlation, u, v, corr, counts, df)
+    switch (slot) {
+        case 0: PF_LAUNCH(PF_SHORT_RUN, false); break;
+        case 1: PF_LAUNCH(PF_LONG_RUN, false); break;
+        case 2: PF_LAUNCH(PF_SHORT_RUN, true); break;
+        default: PF_LAUNCH(PF_LONG_RUN, true); break;
+    }
+#undef PF_LAUNCH
+    return 0;
+}
+
+// the options of vof_piv_flow_ex_*; the plain call is PivFlowOptions{}
+struct PivFlowOptions {
+    int deformation = 0; double outlier_threshold = NAN, outlier_epsilon = 0.1; int validate_last = 0; int64_t* validation_counts = nullptr;
+    bool validating() const { return !std::isnan(outlier_threshold); }
+};
+static int piv_flow_options(vof_ctx* c, const PivFlowOptions& o) {
+    if (o.deformation != 0 && o.deformation != 1) { c->err = "PIV: deformation must be 0 or 1"; return -1; }
+    if (o.validate_last != 0 && o.validate_last != 1) { c->err = "PIV: validate_last must be 0 or 1"; return -1; }
+    if (o.validating() && !(o.outlier_threshold > 0.0 && std::isfinite(o.outlier_threshold))) { c->err = "PIV: outlier_threshold must be positive and finite, or NaN for none"; return -1; }
+    if (!(o.outlier_epsilon >= 0.0 && std::isfinite(o.outlier_epsilon))) { c->err = "PIV: outlier_epsilon must be non-negative and finite"; return -1; }
+    if (o.validate_last && !o.validating()) { c->err = "PIV: validate_last needs an outlier_threshold"; return -1; }
+    if (o.validating() && !o.validation_counts) { c->err = "PIV: validation_counts is NULL with validation on"; return -1; }
     return 0;
 }
 
 static int piv_flow_impl(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
-                         const int32_t* steps, double min_correlation, int flight, double* u, double* v, double* correlation, int64_t* counts, bool host) {
+                         const int32_t* steps, double min_correlation, int flight, double* u, double* v, double* correlation, int64_t* counts, bool host,
+                         const PivFlowOptions& opt = PivFlowOptions{}) {
     if (int rc = FrameChunks::check(c, {movie, window_sizes, search_radii, steps, u, v, correlation, counts}, n_pairs, "n_pairs")) return rc;
+    if (int rc = piv_flow_options(c, opt)) return rc;
     PfPass P[PF_MAX_PASSES];
     if (int rc = piv_flow_passes(c, n_passes, window_sizes, search_radii, steps, P)) return rc;
     const int last = n_passes - 1;
+    const bool validating = opt.validating(), deform = opt.deformation != 0;
     FrameChunks fc(c, "PIV", n_pairs, flight, host);
     fc.input(movie, true);
-    // per pair in flight: the vectors of every pass but the last, and the offsets of a pass at the size of the largest grid
-    double *d_u[PF_MAX_PASSES] = {}, *d_v[PF_MAX_PASSES] = {};
+    // per pair in flight: the vectors of every pass but the last (and of the last where they are validated), the validated vectors at
+    // the size of the largest validated grid, and - on the integer path - the offsets of a pass at the size of the largest grid
+    double *d_u[PF_MAX_PASSES] = {}, *d_v[PF_MAX_PASSES] = {}, *d_val_u = nullptr, *d_val_v = nullptr;
     int* d_off = nullptr;
-    unsigned long long* d_counts = nullptr;
-    size_t most = 0;
-    for (int p = 0; p < last; ++p) {
+    unsigned long long* d_counts = nullptr;                         // 3 per pass, then the 2 of the validation per pass
+    const bool validated_last = validating && opt.validate_last;
+    size_t most = 0, most_validated = 0;
+    for (int p = 0; p < last + (validated_last ? 1 : 0); ++p) {
         fc.sc.per_unit(&d_u[p], (size_t)P[p].R * P[p].C); fc.sc.per_unit(&d_v[p], (size_t)P[p].R * P[p].C);
-        most = std::max(most, (size_t)P[p + 1].R * P[p + 1].C);
+        if (p < last) { most = std::max(most, (size_t)P[p + 1].R * P[p + 1].C); most_validated = std::max(most_validated, (size_t)P[p].R * P[p].C); }
     }
-    if (last > 0) fc.sc.per_unit(&d_off, 2 * most);
-    fc.sc.once(&d_counts, (size_t)3 * n_passes);
+    if (last > 0 && !deform) fc.sc.per_unit(&d_off, 2 * most);
+    if (last > 0 && validating) { fc.sc.per_unit(&d_val_u, most_validated); fc.sc.per_unit(&d_val_v, most_validated); }
+    fc.sc.once(&d_counts, (size_t)5 * n_passes);
     const size_t ob = (size_t)P[last].R * P[last].C * sizeof(double);
     fc.output(u, ob); fc.output(v, ob); fc.output(correlation, ob);
     if (int rc = fc.plan()) return rc;
-    HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)3 * n_passes * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)5 * n_passes * sizeof(unsigned long long), c->stream));
     if (int rc = fc.run([&](int, int np, const double* const* in, void* const* out) -> int {
+            const double *from_u = nullptr, *from_v = nullptr;       // the vectors the next pass starts from
             for (int p = 0; p < n_passes; ++p) {
-                if (p > 0) {
+                PfDeform df{};
+                if (p > 0 && deform) df = PfDeform{P[p - 1], from_u, from_v, c->Ni};
+                else if (p > 0) {
                     Prof prof(c, VOF_K_REDUCE, PF_ST_OFFSETS);
-                    k_pivflow_offsets<<<dim3((P[p].R * P[p].C + PF_BLOCK - 1) / PF_BLOCK, np), PF_BLOCK, 0, c->stream>>>(P[p], P[p - 1], d_u[p - 1], d_v[p - 1], d_off);
+                    k_pivflow_offsets<<<dim3((P[p].R * P[p].C + PF_BLOCK - 1) / PF_BLOCK, np), PF_BLOCK, 0, c->stream>>>(P[p], P[p - 1], from_u, from_v, d_off);
                 }
-                double* pu = p == last ? (double*)out[0] : d_u[p];
-                double* pv = p == last ? (double*)out[1] : d_v[p];
+                const bool raw_out = p == last && !validated_last;  // the last pass writes the outputs, unless the median test does
+                double* pu = raw_out ? (double*)out[0] : d_u[p];
+                double* pv = raw_out ? (double*)out[1] : d_v[p];
                 double* pc = p == last ? (double*)out[2] : nullptr;
-                const double S = P[p].w + 2.0 * P[p].r;
-                Prof prof(c, VOF_K_REDUCE, PF_ST_PASS0 + p, 8.0 * (P[p].w * (double)P[p].w + S * S) * P[p].R * P[p].C);
-                const int rc = piv_flow_launch(c, P[p], np, in[0], p ? d_off : nullptr, min_correlation, pu, pv, pc, d_counts + 3 * p);
-                if (rc) return rc;
+                {
+                    const double S = P[p].w + 2.0 * P[p].r;
+                    Prof prof(c, VOF_K_REDUCE, PF_ST_PASS0 + p, 8.0 * (P[p].w * (double)P[p].w + S * S) * P[p].R * P[p].C);
+                    const int rc = piv_flow_launch(c, P[p], np, in[0], p && !deform ? d_off : nullptr, min_correlation, pu, pv, pc, d_counts + 3 * p,
+                                                   p && deform ? &df : nullptr);
+                    if (rc) return rc;
+                }
+                from_u = pu; from_v = pv;
+                if (validating && (p < last || validated_last)) {   // Jacobi: from the raw vectors into a second field
+                    double* vu = p == last ? (double*)out[0] : d_val_u;
+                    double* vv = p == last ? (double*)out[1] : d_val_v;
+                    Prof prof(c, VOF_K_REDUCE, PF_ST_OFFSETS);
+                    k_pivflow_validate<<<dim3((P[p].R * P[p].C + PF_BLOCK - 1) / PF_BLOCK, np), PF_BLOCK, 0, c->stream>>>(
+                        P[p].R, P[p].C, pu, pv, opt.outlier_threshold, opt.outlier_epsilon, vu, vv, d_counts + 3 * n_passes + 2 * p);
+                    from_u = vu; from_v = vv;
+                }
             }
             return 0;
         })) return rc;
-    unsigned long long got[3 * PF_MAX_PASSES];
-    if (int rc = d2h_bounced(c, got, d_counts, (size_t)3 * n_passes * sizeof(unsigned long long))) return rc;
+    unsigned long long got[5 * PF_MAX_PASSES];
+    if (int rc = d2h_bounced(c, got, d_counts, (size_t)5 * n_passes * sizeof(unsigned long long))) return rc;
     for (int k = 0; k < 3 * n_passes; ++k) counts[k] = (int64_t)got[k];
+    if (validating) for (int k = 0; k < 2 * n_passes; ++k) opt.validation_counts[k] = (int64_t)got[3 * n_passes + k];
     return 0;
 }
 
@@ -5253,6 +5300,18 @@ int vof_piv_flow_dev(vof_ctx* c, const double* movie, int n_pairs, int n_passes,
 int vof_piv_flow_host(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
                       const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts) {
     return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, true);
+}
+int vof_piv_flow_ex_dev(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
+                        const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts,
+                        int deformation, double outlier_threshold, double outlier_epsilon, int validate_last, int64_t* validation_counts) {
+    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, false,
+                         PivFlowOptions{deformation, outlier_threshold, outlier_epsilon, validate_last, validation_counts});
+}
+int vof_piv_flow_ex_host(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
+                         const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts,
+                         int deformation, double outlier_threshold, double outlier_epsilon, int validate_last, int64_t* validation_counts) {
+    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, true,
+                         PivFlowOptions{deformation, outlier_threshold, outlier_epsilon, validate_last, validation_counts});
 }
 
 // the six stacks of two results as inputs of a frame-chunk walk, and those of one chunk as the kernels take them

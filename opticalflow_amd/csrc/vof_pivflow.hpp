@@ -3,6 +3,9 @@
 // tests/piv_flow_restatement.py - float64, every operation single and uncontracted, every window sum two-level (a window row left
 // to right from 0.0, the row sums top to bottom from 0.0, products rounded before they are added) - and the kernels are held to it
 // bit for bit.  Integer atomics only (the counts): results are the same from call to call and for every frames_in_flight.
+// Two options (DESIGN.md sections 20.7 to 20.9, tests/piv_deform_restatement.py): the normalised median test on the vectors of a pass
+// before the next one uses them (k_pivflow_validate), and window deformation, where the search region of a later pass is frame k + 1
+// resampled by the interpolated vectors of the pass before (the DEFORM staging of k_pivflow_correlate).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vof_piv.hpp"
@@ -43,6 +46,113 @@ __device__ __forceinline__ int pf_previous(int at, int w, const PfPass& q, int n
     const int num = 2 * (at - q.m) + w - q.w + q.s, den = 2 * q.s;
     int a = num >= 0 ? num / den : -((-num + den - 1) / den);     // floor division
     return a < 0 ? 0 : (a > n - 1 ? n - 1 : a);
+}
+
+// ---- the predictor of a deformed pass ------------------------------------------------------------------------------------------------
+// A real position on an axis of n nodes at c + s * index: g = clamp((pos - c) / s, 0, n - 1), lo = floor(g) but n - 2 at the last node
+// (0 where there is one node), t = g - lo, hi = min(lo + 1, n - 1).  Whatever comes in, NaN included, lo and hi lie in [0, n - 1].
+struct PfSplit { int lo, hi; double t; };
+__device__ __forceinline__ PfSplit pf_split(double pos, double c, double s, int n) {
+#pragma clang fp contract(off)
+    double g = (pos - c) / s;
+    g = fmin(fmax(g, 0.0), (double)(n - 1));
+    int lo = (int)floor(g);
+    if (lo > n - 2) lo = max(n - 2, 0);
+    return PfSplit{lo, min(lo + 1, n - 1), g - (double)lo};
+}
+__device__ __forceinline__ double pf_lerp2(double f00, double f01, double f10, double f11, double ta, double tb) {
+#pragma clang fp contract(off)
+    const double top = f00 + tb * (f01 - f00), bot = f10 + tb * (f11 - f10);
+    return top + ta * (bot - top);
+}
+// What a deformed pass reads of the pass before: its geometry and its vectors [pair][R][C], validated where validation is on.
+struct PfDeform { PfPass q; const double* u; const double* v; int Ni; };
+// (U, V) of pass q's vectors of one pair between the rows a.lo, a.hi and the columns b.lo, b.hi; a vector with a NaN reads as (0, 0).
+__device__ __forceinline__ void pf_predict(const double* __restrict__ u, const double* __restrict__ v, int C, const PfSplit& a, const PfSplit& b,
+                                           double& U, double& V) {
+    const int at[4] = {a.lo * C + b.lo, a.lo * C + b.hi, a.hi * C + b.lo, a.hi * C + b.hi};
+    double fu[4], fv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        fu[k] = u[at[k]]; fv[k] = v[at[k]];
+        if (fu[k] != fu[k] || fv[k] != fv[k]) { fu[k] = 0.0; fv[k] = 0.0; }
+    }
+    U = pf_lerp2(fu[0], fu[1], fu[2], fu[3], a.t, b.t);
+    V = pf_lerp2(fv[0], fv[1], fv[2], fv[3], a.t, b.t);
+}
+__device__ __forceinline__ double pf_centre(const PfPass& q) {
+#pragma clang fp contract(off)
+    return (double)q.m + (double)(q.w - 1) / 2.0;
+}
+
+// ---- the normalised median test (Westerweel & Scarano 2005) on the vectors of a pass: one thread per window, the pair is blockIdx.y ----
+// Compare and exchange where y < x: the 19 comparators of the 8-input network, absent neighbours +inf, so k values sort to s[0 .. k).
+__device__ __forceinline__ void pf_sort8(double (&s)[8]) {
+#define PF_CX(x, y) { const double lo_ = s[y] < s[x] ? s[y] : s[x], hi_ = s[y] < s[x] ? s[x] : s[y]; s[x] = lo_; s[y] = hi_; }
+    PF_CX(0, 1) PF_CX(2, 3) PF_CX(4, 5) PF_CX(6, 7) PF_CX(0, 2) PF_CX(1, 3) PF_CX(4, 6) PF_CX(5, 7) PF_CX(1, 2) PF_CX(5, 6) PF_CX(0, 4) PF_CX(3, 7)
+    PF_CX(1, 5) PF_CX(2, 6) PF_CX(1, 4) PF_CX(3, 6) PF_CX(2, 4) PF_CX(3, 5) PF_CX(3, 4)
+#undef PF_CX
+}
+// the median of the k finite values among the eight: the middle one, or (lo + hi) * 0.5
+__device__ __forceinline__ double pf_median8(double (&s)[8], int k) {
+#pragma clang fp contract(off)
+    pf_sort8(s);
+    const int i_lo = (k - 1) / 2, i_hi = k / 2;
+    double lo = s[0], hi = s[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) { if (i == i_lo) lo = s[i]; if (i == i_hi) hi = s[i]; }
+    return (k & 1) ? lo : (lo + hi) * 0.5;
+}
+// r = |x - med| / (med |x_n - med| + eps) of a centre x among its neighbours xn (absent: +inf)
+__device__ __forceinline__ double pf_residual(double x, double med, const double (&xn)[8], int k, double eps) {
+#pragma clang fp contract(off)
+    double dev[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dev[i] = xn[i] < INFINITY ? fabs(xn[i] - med) : INFINITY;
+    return fabs(x - med) / (pf_median8(dev, k) + eps);
+}
+// Jacobi style: reads (u, v), writes (u_out, v_out), [pair][R][C] each.  A window with fewer than three valid neighbours is copied; an
+// invalid centre becomes the medians (counts[1], filled); a valid one whose r_u or r_v exceeds the threshold too (counts[0], outliers).
+__global__ __launch_bounds__(PF_BLOCK) void k_pivflow_validate(int R, int C, const double* __restrict__ u, const double* __restrict__ v,
+                                                              double threshold, double eps, double* __restrict__ u_out,
+                                                              double* __restrict__ v_out, unsigned long long* __restrict__ counts) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * PF_BLOCK + threadIdx.x, pair = blockIdx.y;
+    if (t >= R * C) return;
+    const int a = t / C, b = t % C;
+    const double* pu = u + (size_t)pair * R * C;
+    const double* pv = v + (size_t)pair * R * C;
+    double un[8], vn[8];
+    int k = 0, slot = 0;
+#pragma unroll
+    for (int da = -1; da <= 1; ++da) {
+#pragma unroll
+        for (int db = -1; db <= 1; ++db) {
+            if (da == 0 && db == 0) continue;
+            const int aa = a + da, bb = b + db;
+            double x = INFINITY, y = INFINITY;
+            if (aa >= 0 && aa < R && bb >= 0 && bb < C) {
+                const double nu = pu[aa * C + bb], nv = pv[aa * C + bb];
+                if (!(nu != nu) && !(nv != nv)) { x = nu; y = nv; ++k; }
+            }
+            un[slot] = x; vn[slot] = y; ++slot;
+        }
+    }
+    double cu = pu[t], cv = pv[t];
+    if (k >= 3) {
+        double su[8], sv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { su[i] = un[i]; sv[i] = vn[i]; }
+        const double um = pf_median8(su, k), vm = pf_median8(sv, k);
+        if (cu != cu || cv != cv) {
+            cu = um; cv = vm;
+            atomicAdd(&counts[1], 1ULL);
+        } else {
+            const double ru = pf_residual(cu, um, un, k, eps), rv = pf_residual(cv, vm, vn, k, eps);
+            if (ru > threshold || rv > threshold) { cu = um; cv = vm; atomicAdd(&counts[0], 1ULL); }
+        }
+    }
+    u_out[(size_t)pair * R * C + t] = cu; v_out[(size_t)pair * R * C + t] = cv;
 }
 
 // ---- the offsets of a pass from the vectors of the pass before: one thread per window, the pair is blockIdx.y ----------------------
@@ -108,11 +218,17 @@ __device__ __forceinline__ void pf_steps(int jb, int w, const double (&xa)[K], c
 // of K registers, so a step of j costs one read of B and one (broadcast) read of A for K multiplications and K additions.
 // K = 5 from r = 10 on, 3 below (pf_run); runs of 3 in six waves for every radius were measured and are slower
 // (profiles/piv_flow_summary.md).
-template <int K>
+//
+// DEFORM (a pass after the first, off NULL): the region is rows [i0 - r, ... + S) of frame k + 1 resampled.  Pixel (i, j) holds the frame
+// at (i + V(i, j), j + U(i, j)), bilinear and clamped to the frame, (U, V) the bilinear predictor from the vectors of pass df.q.  The
+// splits of the S rows and S columns between the nodes of that pass are formed once, in the LDS of the row sums, which are not yet
+// in use; a pixel then costs four gathers of each vector grid, four of the frame and the two interpolations.  At the end thread 0
+// adds the predictor at the window's centre instead of the offset.  Everything between - sums, hot loop, peak - is the same code.
+template <int K, bool DEFORM>
 __global__ __launch_bounds__(PF_BLOCK) void k_pivflow_correlate(PfPass p, const double* __restrict__ frames, size_t fs, int Nj,
                                                                const int* __restrict__ off, double min_correlation,
                                                                double* __restrict__ u, double* __restrict__ v, double* __restrict__ corr,
-                                                               unsigned long long* __restrict__ counts) {
+                                                               unsigned long long* __restrict__ counts, PfDeform df) {
 #pragma clang fp contract(off)
     extern __shared__ double pf_lds[];
     __shared__ double rows_a[2 * PF_MAX_W];
@@ -135,8 +251,33 @@ __global__ __launch_bounds__(PF_BLOCK) void k_pivflow_correlate(PfPass p, const 
     const double* fb = frames + (size_t)(pair + 1) * fs + (size_t)(i0 + oi - r) * Nj + (j0 + oj - r);
 #pragma unroll 4
     for (int k = tid; k < w * w; k += PF_BLOCK) A[(k / w) * wP + k % w] = fa[(size_t)(k / w) * Nj + k % w];
+    if (!DEFORM) {
 #pragma unroll 4
-    for (int k = tid; k < S * S; k += PF_BLOCK) B[(k / S) * SP + k % S] = fb[(size_t)(k / S) * Nj + k % S];
+        for (int k = tid; k < S * S; k += PF_BLOCK) B[(k / S) * SP + k % S] = fb[(size_t)(k / S) * Nj + k % S];
+    } else {
+        double* const split_t = rb;                                 // [2 S]: rows, then columns
+        int* const split_lo = (int*)(rb + 2 * S);
+        const double cq = pf_centre(df.q), sq = (double)df.q.s;
+        for (int k = tid; k < 2 * S; k += PF_BLOCK) {
+            const PfSplit sp = k < S ? pf_split((double)(i0 - r + k), cq, sq, df.q.R) : pf_split((double)(j0 - r + k - S), cq, sq, df.q.C);
+            split_t[k] = sp.t; split_lo[k] = sp.lo;
+        }
+        __syncthreads();
+        const double* pu = df.u + (size_t)pair * df.q.R * df.q.C;
+        const double* pv = df.v + (size_t)pair * df.q.R * df.q.C;
+        const double* second = frames + (size_t)(pair + 1) * fs;
+        for (int k = tid; k < S * S; k += PF_BLOCK) {
+            const int y = k / S, x = k % S;
+            const PfSplit ga{split_lo[y], min(split_lo[y] + 1, df.q.R - 1), split_t[y]};
+            const PfSplit gb{split_lo[S + x], min(split_lo[S + x] + 1, df.q.C - 1), split_t[S + x]};
+            double U, V;
+            pf_predict(pu, pv, df.q.C, ga, gb, U, V);
+            const PfSplit fa2 = pf_split((double)(i0 - r + y) + V, 0.0, 1.0, df.Ni), fb2 = pf_split((double)(j0 - r + x) + U, 0.0, 1.0, Nj);
+            const double* r0 = second + (size_t)fa2.lo * Nj;
+            const double* r1 = second + (size_t)fa2.hi * Nj;
+            B[y * SP + x] = pf_lerp2(r0[fb2.lo], r0[fb2.hi], r1[fb2.lo], r1[fb2.hi], fa2.t, fb2.t);
+        }
+    }
     __syncthreads();
 
     // S_a and S_aa: a thread per row, then thread 0 adds the rows top to bottom
@@ -274,7 +415,16 @@ __global__ __launch_bounds__(PF_BLOCK) void k_pivflow_correlate(PfPass p, const 
         }
     }
     if (pi == 0 || pi == D - 1 || pj == 0 || pj == D - 1) atomicAdd(&counts[1], 1ULL);
-    double vv = (double)(oi + pi - r) + delta_i, uu = (double)(oj + pj - r) + delta_j;
+    double vv, uu;
+    if (!DEFORM) {
+        vv = (double)(oi + pi - r) + delta_i; uu = (double)(oj + pj - r) + delta_j;
+    } else {                                                        // the predictor at the window's centre, then d + delta
+        const double half = (double)(w - 1) / 2.0, cq = pf_centre(df.q), sq = (double)df.q.s;
+        double Uc, Vc;
+        pf_predict(df.u + (size_t)pair * df.q.R * df.q.C, df.v + (size_t)pair * df.q.R * df.q.C, df.q.C,
+                   pf_split((double)i0 + half, cq, sq, df.q.R), pf_split((double)j0 + half, cq, sq, df.q.C), Uc, Vc);
+        vv = Vc + ((double)(pi - r) + delta_i); uu = Uc + ((double)(pj - r) + delta_j);
+    }
     if (c0 < min_correlation) { uu = pf_nan(); vv = pf_nan(); atomicAdd(&counts[2], 1ULL); }
     u[win] = uu; v[win] = vv;
     if (corr) corr[win] = c0;

@@ -1556,8 +1556,32 @@ def piv_grid(shape, window_sizes, search_radii, steps=None):
     return grids
 
 
-def conduct_piv(movie, window_sizes=(64, 32), search_radii=(16, 4), steps=None, min_correlation=None, smoothing_sigma=None, *, device=0,
-                frames_in_flight=0):
+def _piv_options(deformation, outlier_threshold, outlier_epsilon, validate_last):
+    """The options of ``conduct_piv`` as the library takes them, with every check it makes as a ``ValueError``."""
+    if not isinstance(deformation, (bool, np.bool_)) or not isinstance(validate_last, (bool, np.bool_)):
+        raise ValueError("deformation and validate_last must be bools")
+
+    def number(name, value):
+        try:
+            if isinstance(value, (bool, np.bool_)):
+                raise TypeError
+            return float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number") from None
+    if outlier_threshold is not None:
+        outlier_threshold = number("outlier_threshold", outlier_threshold)
+        if not (0 < outlier_threshold < np.inf):
+            raise ValueError("outlier_threshold must be a positive finite number or None")
+    outlier_epsilon = number("outlier_epsilon", outlier_epsilon)
+    if not (0 <= outlier_epsilon < np.inf):
+        raise ValueError("outlier_epsilon must be a non-negative finite number")
+    if validate_last and outlier_threshold is None:
+        raise ValueError("validate_last needs an outlier_threshold")
+    return dict(deformation=bool(deformation), outlier_threshold=outlier_threshold, outlier_epsilon=outlier_epsilon, validate_last=bool(validate_last))
+
+
+def conduct_piv(movie, window_sizes=(64, 32), search_radii=(16, 4), steps=None, min_correlation=None, smoothing_sigma=None, *,
+                deformation=False, outlier_threshold=None, outlier_epsilon=0.1, validate_last=False, device=0, frames_in_flight=0):
     """Particle image velocimetry of every frame pair on the GPU: direct zero-normalised cross-correlation of interrogation windows,
     in ``len(window_sizes)`` passes, each pass searching around the rounded vector of the pass before.  The reference imports such
     vectors from PIVlab (``analysis/postprocess_PIV.py``); this makes them where the movie is.
@@ -1574,10 +1598,27 @@ def conduct_piv(movie, window_sizes=(64, 32), search_radii=(16, 4), steps=None, 
     (a flat window, or one under the threshold), and ``'correlation'`` - float64 host arrays ``(T - 1, R, C)`` of the last pass - and
     ``'counts'``, int64 ``(passes, 3)``: flat windows, peaks on the border of the search range, vectors under the threshold.
 
+    Two options, independent of each other and off by default (DESIGN.md sections 20.7 to 20.9; the device is held to
+    ``tests/piv_deform_restatement.py`` bit for bit):
+
+    * ``deformation=True``: window deformation.  From the second pass on the search region is frame ``k + 1`` resampled
+      (bilinearly) by the vectors of the pass before, interpolated (bilinearly) to every pixel, so the correlation finds only a
+      residual around zero and the vector is the interpolated one at the window's centre plus that residual.  With one pass it
+      changes nothing.
+    * ``outlier_threshold`` (PIVlab's 2; ``None``: off): the normalised median test of Westerweel & Scarano (2005) on the vectors
+      of a pass before the next one uses them.  A vector whose residual against the median of its (at least three) valid
+      neighbours, ``|u - u_m| / (median |u_n - u_m| + outlier_epsilon)`` in ``u`` or in ``v``, exceeds the threshold is replaced by
+      that median, and so is a missing vector.  ``validate_last=True`` applies it to the returned vectors too.  The result then has
+      ``'validation_counts'``, int64 ``(passes, 2)``: outliers and filled vectors per pass (the last row zero without
+      ``validate_last``); ``'counts'`` and ``'correlation'`` stay what the correlation found.
+
     ``ValueError`` before the library is touched: fewer than 2 frames, window sizes outside [4, 64] or growing from pass to pass, radii
-    outside [1, 16], steps below 1, more than 8 passes, a frame smaller than ``w + 2 m`` of some pass.  The movie must be finite."""
+    outside [1, 16], steps below 1, more than 8 passes, a frame smaller than ``w + 2 m`` of some pass, an ``outlier_threshold`` that is
+    not positive and finite, an ``outlier_epsilon`` that is not non-negative and finite, a ``deformation`` or ``validate_last`` that is
+    no bool, ``validate_last`` without a threshold.  The movie must be finite."""
     shape = _movie_shape(movie, 2)
     passes = _piv_passes(shape, window_sizes, search_radii, steps)
+    options = _piv_options(deformation, outlier_threshold, outlier_epsilon, validate_last)
     if min_correlation is not None:
         try:
             min_correlation = float(min_correlation)
@@ -1597,19 +1638,23 @@ def conduct_piv(movie, window_sizes=(64, 32), search_radii=(16, 4), steps=None, 
             frames = side.blurred(frames, gaussian_taps(smoothing_sigma), solver)
         side.wait()
         counts = solver.piv_flow(frames, T - 1, *(tuple(p[k] for p in passes) for k in range(3)), u, v, correlation, min_correlation,
-                                 frames_in_flight)
+                                 frames_in_flight, **options)
     if not isinstance(u, np.ndarray):
         u, v, correlation = (a.cpu().numpy() for a in (u, v, correlation))
     last = piv_grid(shape, [p[0] for p in passes], [p[1] for p in passes], [p[2] for p in passes])[-1]
     x, y = (np.repeat(last[key][None], T - 1, axis=0) for key in ("x", "y"))
-    return {"x": x, "y": y, "u_original": u, "v_original": v, "correlation": correlation, "counts": counts}
+    result = {"x": x, "y": y, "u_original": u, "v_original": v, "correlation": correlation, "counts": counts}
+    if options["outlier_threshold"] is not None:
+        result["counts"], result["validation_counts"] = counts
+    return result
 
 
 def conduct_piv_flow(movie, delta_x=1.0, delta_t=1.0, smoothing_sigma=None, *, device=0, output="numpy", **piv_arguments):
     """``conduct_piv`` as a dense flow result: ``convert_PIV_result(conduct_piv(movie, smoothing_sigma=smoothing_sigma,
     **piv_arguments), movie, delta_x, delta_t)`` with the peak correlations under ``'PIV_correlation'`` - the dictionary
     ``filter_PIV_flow_result`` and ``compare_flow_results`` take, so PIV and the other estimators are compared without a PIVlab file.
-    ``piv_arguments``: ``window_sizes``, ``search_radii``, ``steps``, ``min_correlation``, ``frames_in_flight``.  ``output="torch"``:
+    ``piv_arguments``: ``window_sizes``, ``search_radii``, ``steps``, ``min_correlation``, ``deformation``, ``outlier_threshold``,
+    ``outlier_epsilon``, ``validate_last``, ``frames_in_flight``.  ``output="torch"``:
     ``v_x``, ``v_y`` and ``speed`` are device tensors (and ``movie`` should be one, for the filter).  Every frame pair needs at least
     three vectors that are not collinear: scipy's error for a frame that cannot be triangulated propagates."""
     _side(output, device)
