@@ -1,4 +1,5 @@
-// vof.hip - host side of libvof.so: context, workspace, multigrid hierarchy, BiCGStab driver, C ABI.
+// vof.hip - the solver's source of libvof.so: context, workspace, multigrid hierarchy, BiCGStab driver and their part of the C ABI
+// (the pair calls: vof_pairs.hip; the frame-chunk calls: vof_frames.hip; what the three share: vof_host.hpp).
 //
 // Replaces the per-pair body of source/optical_flow.py::variational_optical_flow (OF.py:791-1186:
 // scipy.sparse assembly + PETSc KSP bcgs / composite PC) with a batched, matrix-free solve on one
@@ -11,19 +12,7 @@
 #include "vof_sweep0p.hpp"
 #include "vof_stream0.hpp"
 #include "vof_direct.hpp"
-#include "vof_boxflow.hpp"
-#include "vof_boxsweep.hpp"
-#include "vof_blursweep.hpp"
-#include "vof_compare.hpp"
-#include "vof_flowcompare.hpp"
-#include "vof_liushen.hpp"
-#include "vof_preprocess.hpp"
-#include "vof_resize.hpp"
-#include "vof_farneback.hpp"
-#include "vof_intensity.hpp"
-#include "vof_piv.hpp"
-#include "vof_pivflow.hpp"
-#include "../../include/vof.h"
+#include "vof_host.hpp"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -48,172 +37,15 @@ namespace {
 
 constexpr int COARSEST_MAX = 5;      // coarsen until max(n_i, n_j) <= COARSEST_MAX (5: dense inverse of <= 75 unknowns; was 9 = 243 unknowns, whose
                                      // Gauss-Jordan inversion took 4.4 ms per batch - the fused coarse-tail kernel makes the extra level free)
-constexpr int MAX_PROF_RECS = 32768;
-constexpr int MAX_LANES = 3;        // concurrent pair groups of one device solve (solve_range_dev, VOF_LANES)
-constexpr int MAX_LANE_GROUPS = 2;  // groups of pairs a lane runs one after the other in the two-phase solve (VOF_LANE_GROUPS)
 constexpr int AUTO_F64_AFTER = 8;   // vcycle_precision == 2: switch the V-cycle vectors to float64 after this many iterations
-
-struct Level {
-    int ni = 0, nj = 0;
-    size_t npts = 0;
-    void* C = nullptr;   // stored stencil [B][81][npts] (double or float); level 0: only for 1-level grids
-    // V-cycle vectors; element type is float or double (ctx->vfloat), allocations are sized for double
-    void* x = nullptr;  // levels >= 1
-    void* b = nullptr;  // levels >= 1
-    void* r = nullptr;  // residual scratch (all levels but the last)
-    void* x2 = nullptr; // ping-pong partner of x for the out-of-place fused sweeps
-};
-
-struct ProfRec {
-    hipEvent_t e0, e1;
-    int kid, level, units;
-    double bytes;  // algorithmic bytes of this launch (units x bytes per pair; SURVEY 8(d): per sweep / operator application performed)
-    double moved;  // minimal bytes the launch has to move (differs when one pass performs two sweeps)
-};
 
 }  // namespace
 
-struct vof_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int Ni = 0, Nj = 0, B = 0;
-    std::vector<Level> L;
-    double *kx = nullptr, *kb = nullptr, *kr = nullptr, *krh = nullptr, *kp = nullptr, *kv = nullptr, *kt = nullptr;
-    double* ky = nullptr;   // V-cycle outputs y = M p and z = M s (V-typed: float when vfloat)
-    double* kz = nullptr;
-    double* b32 = nullptr;  // V-typed copy of the V-cycle right-hand side (p or s) when vfloat
-    bool vfloat = false;    // V-cycle vectors stored as float32 (arithmetic stays FP64)
-    bool vcoarse32 = false; // vcycle_precision 3: float64 vectors on level 0, float32 on the levels below (the two meet in the fused
-                            // residual + restriction kernel and in the post-smoothing pass that interpolates the correction)
-    bool l0_handoff = true; // VOF_L0_HANDOFF=0: the level-0 hand-off vectors stay float64 in vcycle_precision 3 (see h32)
-    bool h32 = false;       // the cycles run now store their level-0 hand-off vectors as float32: the pre-smoothed iterate x and the
-                            // cycle's result (y, z).  Set per BiCGStab iteration where handoff32_ok holds, and by vof_debug_vcycle*
-    const PairParam* pp = nullptr;   // per-pair (alpha, beta, frame) overrides of the batch in solve_batch ("virtual pairs") or nullptr;
-                                     // written by solve_batch alone (BatchReq), nullptr outside it - the debug entry points rely on that
-    PairParam* pp_buf = nullptr;     // device storage for them (B entries, lazy)
-    // warm start (two-phase solve of a stack): interior solutions of the phase-1 pairs, and device storage for a batch's
-    // table of the saved solutions its pairs start from (BatchReq::guess; B entries, lazy)
-    double* warm_x = nullptr;
-    size_t warm_cap = 0;
-    int* warm_src = nullptr;
-    double* partials = nullptr;
-    int nblk = 0;
-    PairScalars* sc = nullptr;
-    int* active = nullptr;
-    int* alist = nullptr;        // slots of the pairs that were active at the host's last count, ascending (post_active_list)
-    int alist_n = 0;             // ... and how many: the pair dimension of a launch that takes the list
-    bool use_alist = true;       // VOF_ACTIVE_LIST=0: every launch covers all slots of the batch (no list)
-    double* func3 = nullptr;
-    double *W = nullptr, *invT = nullptr;
-    int nd = 0;
-    // host mirrors (pinned)
-    int* h_active = nullptr;
-    int* h_alist = nullptr;
-    PairScalars* h_sc = nullptr;
-    double* h_func3 = nullptr;
-    char* h_bounce = nullptr;        // pinned bounce buffer of the debug / test entry points (lazy)
-    hipEvent_t ev_batch[2] = {nullptr, nullptr};   // start / end of the batch in flight (vof_pair_stats.batch_ms)
-    // staging for the host-pointer API (allocated lazily)
-    double* st_movie = nullptr;
-    double* st_out[4] = {nullptr, nullptr, nullptr, nullptr};
-    double* st_out2[4] = {nullptr, nullptr, nullptr, nullptr};   // second output set (copy / solve overlap of the host API)
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_solved[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr}, ev_uploaded[2] = {nullptr, nullptr};
-    double* st_movie2 = nullptr;                                 // second frame buffer (upload of the next batch under the solve)
-    char* scratch = nullptr;                                             // the one scratch buffer of the blur, the box flow's general path, the sweeps, the comparison and the frame-wise calls (lazy, grown on demand; the Scratch of the call in progress carves it anew)
-    size_t scratch_bytes = 0;
-    bool bf_lds_set = false;                                             // box flow, fused kernel: dynamic LDS limit raised
-    bool bl_lds_set = false;                                             // tiled blur: dynamic LDS limit raised
-    bool ls_lds_set = false;                                             // Liu-Shen flow, fused kernel: dynamic LDS limit raised
-    double* tex_tab = nullptr;                                           // synthetic-texture tables (lazy)
-    size_t tex_cap = 0;
-    // GMRES fallback (allocated on first use): basis vectors V_0..V_m (each B * len0), per-pair state, partials, flags
-    double* gm_V = nullptr;
-    GmresState* gm_state = nullptr;
-    double* gm_partials = nullptr;
-    int* gm_cycle = nullptr;
-    int gm_m = 0;                // restart length the basis holds
-    int gm_want = 0;             // restart length it was asked for (> gm_m where the free memory cut it)
-    long long gmres_pairs = 0;   // pairs handed to the fallback since the context was created
-    struct Alloc { void* raw; char* user; size_t bytes; const char* name; int line; };
-    std::vector<Alloc> allocs;     // every device buffer of the context (raw != user only with guard regions)
-    int c_bytes_per_point = 0;     // stencil storage allocated per point of a stored level (120 float8 .. 648 float64)
-    size_t bytes = 0;
-    std::string err;
-    // state of the last setup
-    const double* frames = nullptr;  // device pointer to frame 0 of the current batch
-    int npairs = 0;
-    vof_params prm;
-    int cfmt = 0;   // storage format of the stored stencils of the current hierarchy: 0 double, 1 float, 2 CoefB16 (levels >= 1;
-                    // the stored level 0 of a one-level grid is always double)
-    bool fused = true;   // fused streaming 4-colour sweeps (false: one launch per colour)
-    bool fold_stored = false;   // stored levels, packed stencils (k_sweep_st): the coarse-grid correction interpolated inside the first
-                                // post-sweep (VOF_FOLD_STORED=1; measured: the sweep gets slower by what the stand-alone prolongation
-                                // kernel costs, so that one stays)
-    bool fuse_revisit = true;   // VOF_FUSE_REVISIT=0: between two visits of the W-cycle's revisited level, the post-smoothing sweep of one
-                                // visit and the pre-smoothing sweep of the next as two k_sweep_st launches instead of one k_sweep_st2 pass
-    int galerkin_fast = 1;      // VOF_GALERKIN_FAST, level-0 Galerkin product.  bit 0: a kernel of its own for the coarse points away from
-                                // the border; bit 1 (with bit 0): that kernel evaluates the closed form (last bits differ; off by
-                                // default).  0: the generic kernel for every point
-    // direct preconditioner (block-tridiagonal LU by image rows, vof_direct.hpp); buffers allocated on first use
-    bool direct_on = false;          // the batch in solve_batch is preconditioned by the direct solver instead of the multigrid cycle
-                                     // (BatchReq::direct; written by solve_batch alone)
-    int dir_cap = 0;                 // pairs the direct buffers hold
-    double *dir_T = nullptr, *dir_tabs = nullptr, *dir_W = nullptr, *dir_r = nullptr, *dir_y = nullptr, *dir_x = nullptr, *dir_t = nullptr;
-    int *dir_ipiv = nullptr, *dir_info = nullptr;
-    double *dir_R = nullptr, *dir_C = nullptr, *dir_D = nullptr;   // blocked inverse: row panel, column panel, inverted diagonal tile
-    int dir_ld = 0;                  // leading dimension of the dense blocks (m, or m rounded up to the tile size of the blocked inverse)
-    long long direct_pairs = 0;      // pairs solved with the direct preconditioner since the context was created
-    size_t pivflow_lds[4] = {0, 0, 0, 0};  // dynamic LDS k_pivflow_correlate<PF_SHORT_RUN / PF_LONG_RUN>, then their DEFORM variants, may ask for (raised on first need)
-    // what a level-0 pass may take on besides its sweeps (plan_l0_pass decides; the requests travel in CycleIO / SmoothArgs)
-    bool fuse_rr = true;        // VOF_FUSE_RR=0: the stand-alone kernel k_stream_resrestrict0 instead of the trailing stage of the
-                                // pre-smoothing pass (k_sweep0r, TRAIL = 2)
-    bool fuse_b = true;         // VOF_FUSE_B=0: the stand-alone kernels k_update_s / k_update_p instead of the vector update folded
-                                // into the cycle's first pre-smoothing pass (k_sweep0r, BF = 1 / 2)
-    int fused_ends = 3;         // VOF_FUSED_ENDS: bit 0 the batch prologue (b, x0, r0, r^), bit 1 the epilogue (residual norm, outputs,
-                                // functionals) in one pass of k_stream_apply0 each; 0: the stand-alone kernels
-    long sweep0r_min_blocks = 512;   // level 0, float64 vectors, even n_j: the register-resident pass k_sweep0r for launches of at least
-                                     // this many one-wave blocks, the LDS-ring pass k_sweep0m below (VOF_SWEEP0R_MIN_BLOCKS; the tests set 0)
-    int tail_first = -1;        // first level of the tail (-1: no tail for this grid)
-    size_t tail_lds = 0;        // dynamic LDS bytes of k_tail_cycle
-    TailArgs tail;              // levels / LDS layout; the operation list is rebuilt when the cycle parameters change
-    int tail_key[6] = {-9, -9, -9, -9, -9, -9};   // cycle parameters the operation list was built for
-    // profiler
-    bool prof = false;
-    int prof_kid = -1, prof_level = -1;  // filter (-1 = any)
-    std::vector<ProfRec> recs;
-    std::vector<hipEvent_t> free_events;
-    long long prof_dropped = 0;
-    double prof_ms[VOF_K_COUNT][16];
-    long long prof_n[VOF_K_COUNT][16];
-    long long prof_units[VOF_K_COUNT][16];
-    double prof_bytes[VOF_K_COUNT][16];
-    double prof_moved[VOF_K_COUNT][16];
-    int cur_units = 0;  // frame pairs the next launches process (active pairs of the batch)
-    // fault attribution (see the "debug switches" paragraph of include/vof.h)
-    int dbg_sync = 0;            // VOF_DEBUG_SYNC=1: synchronise + check after every launch scope; the first failure names its kernel class
-    long long dbg_seq = 0;       // launch scopes checked so far
-    std::string dbg_fault;       // the first failure
-    int dbg_fd = -1;             // VOF_DEBUG_SYNC_FILE: the scope in flight is written here before it is waited for (survives an abort)
-    bool dbg_canary = false;     // VOF_DEBUG_CANARY=1: every device buffer sits between two guard pages of a known pattern
-    bool dbg_alloc_log = false;  // VOF_DEBUG_ALLOC_LOG=1: base / size / name of every device buffer on stderr
-    bool dbg_poison = false;     // VOF_DEBUG_POISON=1: every new device buffer is filled with 0xFF bytes (NaN as float / double, -1 as int)
-    size_t part_per_pair = 0;    // doubles of `partials` per batch slot
-    // lanes (solve_range_dev): a lane is a copy of the context whose per-pair buffers are views of the slots [lane_lo, lane_lo +
-    // lane_slots) of the parent's, with a stream and batch events of its own (make_lane); it allocates nothing itself
-    vof_ctx* lane_parent = nullptr;
-    int lane_lo = 0, lane_slots = 0;
-    int dir_ok = -1;             // lane: the parent's direct_ok_for_fallback, decided before the lanes start (-1: ask)
-    hipStream_t lane_stream[MAX_LANES] = {};
-    hipEvent_t lane_ev[MAX_LANES][2] = {};
-    hipEvent_t ev_fork = nullptr;
-    hipEvent_t group_ev[MAX_LANES * MAX_LANE_GROUPS] = {};   // two-phase solve: a group's phase-1 solutions are in warm_x
-};
-
 static std::string g_create_error;
 
-namespace {
+// ---- what the other sources reach through vof_host.hpp
+namespace vof {
+namespace host {
 
 // VOF_DEBUG_SYNC: wait for the launches of the scope that has just ended and ask for their error, so that a fault is
 // reported against the kernel class and level that caused it instead of at some later synchronising call.
@@ -237,68 +69,6 @@ void dbg_sync_check(vof_ctx* c, const char* what, int level) {
         fflush(stderr);
     }
 }
-
-struct Prof {
-    vof_ctx* c;
-    bool on;
-    int dkid, dlevel;
-    ProfRec rec;
-    Prof(vof_ctx* c_, int kid, int level, double bytes_per_pair = 0.0, double moved_per_pair = -1.0) : c(c_), on(false), dkid(kid), dlevel(level) {
-        if (!c->prof) return;
-        if (c->prof_kid >= 0 && kid != c->prof_kid) return;
-        if (c->prof_level >= 0 && level != c->prof_level) return;
-        if ((int)c->recs.size() >= MAX_PROF_RECS) { c->prof_dropped++; return; }
-        if (c->free_events.size() >= 2) {
-            rec.e0 = c->free_events.back(); c->free_events.pop_back();
-            rec.e1 = c->free_events.back(); c->free_events.pop_back();
-        } else {
-            if (hipEventCreate(&rec.e0) != hipSuccess || hipEventCreate(&rec.e1) != hipSuccess) return;
-        }
-        rec.kid = kid; rec.level = level < 0 ? 0 : (level > 15 ? 15 : level);
-        rec.units = c->cur_units;
-        rec.bytes = bytes_per_pair * c->cur_units;
-        rec.moved = (moved_per_pair < 0.0 ? bytes_per_pair : moved_per_pair) * c->cur_units;
-        on = true;
-        hipEventRecord(rec.e0, c->stream);
-    }
-    ~Prof() {
-        if (on) {
-            hipEventRecord(rec.e1, c->stream);
-            c->recs.push_back(rec);
-        }
-        if (c->dbg_sync) dbg_sync_check(c, vof_kernel_name(dkid), dlevel);
-    }
-};
-
-void prof_collect(vof_ctx* c) {
-    if (c->recs.empty()) return;
-    hipStreamSynchronize(c->stream);
-    for (auto& r : c->recs) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) {
-            c->prof_ms[r.kid][r.level] += ms;
-            c->prof_n[r.kid][r.level] += 1;
-            c->prof_units[r.kid][r.level] += r.units;
-            c->prof_bytes[r.kid][r.level] += r.bytes;
-            c->prof_moved[r.kid][r.level] += r.moved;
-        }
-        c->free_events.push_back(r.e0);
-        c->free_events.push_back(r.e1);
-    }
-    c->recs.clear();
-}
-
-#define HIPCHK(call)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            char buf_[512];                                                                        \
-            snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            c->err = buf_;                                                                         \
-            if (!c->dbg_fault.empty()) c->err += " [" + c->dbg_fault + "]";                        \
-            return -2;                                                                             \
-        }                                                                                          \
-    } while (0)
 
 // Caller host memory (pageable) <-> device through a pinned bounce buffer on the context's stream: no null stream, and nothing
 // for the runtime to pin on the fly.  Every copy of the debug entry points, the box flow and Liu-Shen host
@@ -326,6 +96,43 @@ int h2d_bounced(vof_ctx* c, void* dev, const void* host, size_t bytes) {
     return 0;
 }
 
+// Releases one buffer of the context (a buffer that is re-allocated larger); nullptr is fine.
+int dev_free(vof_ctx* c, void* user) {
+    if (!user) return 0;
+    for (size_t i = 0; i < c->allocs.size(); ++i)
+        if ((void*)c->allocs[i].user == user) {
+            HIPCHK(hipFree(c->allocs[i].raw));
+            c->bytes -= c->allocs[i].bytes;
+            c->allocs.erase(c->allocs.begin() + (long)i);
+            return 0;
+        }
+    c->err = "internal: dev_free of a pointer the context does not own";
+    return -1;
+}
+
+}  // namespace host
+}  // namespace vof
+
+namespace {
+
+void prof_collect(vof_ctx* c) {
+    if (c->recs.empty()) return;
+    hipStreamSynchronize(c->stream);
+    for (auto& r : c->recs) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) {
+            c->prof_ms[r.kid][r.level] += ms;
+            c->prof_n[r.kid][r.level] += 1;
+            c->prof_units[r.kid][r.level] += r.units;
+            c->prof_bytes[r.kid][r.level] += r.bytes;
+            c->prof_moved[r.kid][r.level] += r.moved;
+        }
+        c->free_events.push_back(r.e0);
+        c->free_events.push_back(r.e1);
+    }
+    c->recs.clear();
+}
+
 // A range of caller host memory registered (pinned in place) while the object lives; move-only.  Where the registration does
 // not hold, copies from / to the range run as pageable ones.
 class HostPin {
@@ -342,46 +149,6 @@ public:
     bool ok() const { return p_ != nullptr; }
     void release() { if (p_) (void)hipHostUnregister(p_); p_ = nullptr; }   // (the return code is discarded, as it always was)
 };
-
-constexpr size_t DBG_GUARD = 4096;       // bytes of guard pattern on either side of a buffer (VOF_DEBUG_CANARY=1)
-constexpr int DBG_GUARD_BYTE = 0xC5;
-
-template <typename T>
-int dev_alloc_named(vof_ctx* c, T** p, size_t n, const char* name, int line) {
-    void* q = nullptr;
-    size_t bytes = std::max<size_t>(n * sizeof(T), 256);
-    if (c->dbg_canary) {
-        HIPCHK(hipMalloc(&q, bytes + 2 * DBG_GUARD));
-        HIPCHK(hipMemset(q, DBG_GUARD_BYTE, DBG_GUARD));
-        HIPCHK(hipMemset((char*)q + DBG_GUARD + bytes, DBG_GUARD_BYTE, DBG_GUARD));
-        c->allocs.push_back({q, (char*)q + DBG_GUARD, bytes, name, line});
-        *p = (T*)((char*)q + DBG_GUARD);
-    } else {
-        HIPCHK(hipMalloc(&q, bytes));
-        c->allocs.push_back({q, (char*)q, bytes, name, line});
-        *p = (T*)q;
-    }
-    c->bytes += bytes;
-    if (c->dbg_poison) HIPCHK(hipMemset(*p, 0xFF, bytes));
-    if (c->dbg_alloc_log)
-        fprintf(stderr, "vof alloc ctx=%p %s (vof.hip:%d) base=%p end=%p bytes=%zu\n", (void*)c, name, line, (void*)*p, (void*)((char*)*p + bytes), bytes);
-    return 0;
-}
-#define dev_alloc(c, p, n) dev_alloc_named(c, p, n, #p, __LINE__)
-
-// Releases one buffer of the context (a buffer that is re-allocated larger); nullptr is fine.
-int dev_free(vof_ctx* c, void* user) {
-    if (!user) return 0;
-    for (size_t i = 0; i < c->allocs.size(); ++i)
-        if ((void*)c->allocs[i].user == user) {
-            HIPCHK(hipFree(c->allocs[i].raw));
-            c->bytes -= c->allocs[i].bytes;
-            c->allocs.erase(c->allocs.begin() + (long)i);
-            return 0;
-        }
-    c->err = "internal: dev_free of a pointer the context does not own";
-    return -1;
-}
 
 constexpr int DEFAULT_COARSE_PRECISION = 3;
 inline int vof_params_default_coarse_precision() { return DEFAULT_COARSE_PRECISION; }
@@ -436,7 +203,7 @@ int dbg_check_canaries(vof_ctx* c, std::string* report) {
         if (first_lo >= 0 || first_hi >= 0) {
             ++bad;
             char line[256];
-            snprintf(line, sizeof line, "buffer %s (vof.hip:%d, %zu bytes at %p): written %s%ld bytes %s; ", a.name, a.line, a.bytes, (void*)a.user,
+            snprintf(line, sizeof line, "buffer %s (%s:%d, %zu bytes at %p): written %s%ld bytes %s; ", a.name, a.file, a.line, a.bytes, (void*)a.user,
                      first_hi >= 0 ? "" : "-", first_hi >= 0 ? first_hi : first_lo, first_hi >= 0 ? "past its end" : "before its start");
             if (report) *report += line;
         }
@@ -452,15 +219,12 @@ inline ActiveSet listed(const vof_ctx* c, const int* flags) { return ActiveSet{f
 // entries of the pair dimension of a launch that is given `a`
 inline int pair_slots(const vof_ctx* c, const ActiveSet& a, int np) { return a.list ? c->alist_n : np; }
 
-inline dim3 grid2d(int ni, int nj, int z) { return dim3((nj + BX - 1) / BX, (ni + BY - 1) / BY, z); }
 inline dim3 grid2d_colour(int ni, int nj, int colour, int z) {
     int cp = colour >> 1, cq = colour & 1;
     int mi = (ni - cp + 1) / 2, mj = (nj - cq + 1) / 2;
     return dim3(std::max(1, (mj + BX - 1) / BX), std::max(1, (mi + BY - 1) / BY), z);
 }
-const dim3 blk2d(BX, BY, 1);
 
-inline size_t frame_stride(const vof_ctx* c) { return (size_t)c->Ni * c->Nj; }
 
 // ---------------------------------------------------------------- level kernels
 // VT = storage type of the V-cycle vectors (float when ctx->vfloat, else double).
@@ -2535,400 +2299,6 @@ std::vector<HostRegion> plan_output_regions(double* const* outs, const std::vect
     return regions;
 }
 
-// ---- the scratch arena of one ABI call -----------------------------------------------------------
-// The blur, the box flow's general path, the sweeps, the channel comparison and the frame-wise calls take their device scratch
-// from the context's one buffer through a Scratch on the stack of the call: the call declares typed regions, plan() picks the
-// units in flight, grows the buffer and stores the addresses.  One walk measures and carves, so size and layout cannot disagree.
-// The rule: an arena is planned exactly once per ABI call, and every address taken from it is dead when the call returns.  A
-// helper that needs scratch declares it into its caller's arena (blur_regions, box_flow_regions, sweep_tail_regions) and never
-// plans one; no entry point that plans an arena calls another that does.
-struct Scratch {
-    struct Region { void* ptr; size_t fixed, unit; };              // ptr: where the carve stores the region's address; bytes: fixed + units * unit
-    vof_ctx* const c;
-    std::vector<Region> regions;
-    int units = 0; size_t bytes = 0;                               // what plan() settled on
-    explicit Scratch(vof_ctx* c_) : c(c_) {}
-    Scratch(const Scratch&) = delete;                              // the regions point at the caller's pointers
-    // The request.  *p is the region's address after plan(): `count` elements once per call, per unit in flight (align_units:
-    // each at a multiple of 256 bytes; returns the stride in elements), or per unit and once more (the frames of n pairs: n + 1).
-    static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-    template <class T> void once(T** p, size_t count) { regions.push_back({p, count * sizeof(T), 0}); }
-    template <class T> size_t per_unit(T** p, size_t count, bool align_units = false) {
-        regions.push_back({p, 0, align_units ? up256(count * sizeof(T)) : count * sizeof(T)});
-        return regions.back().unit / sizeof(T);
-    }
-    template <class T> void per_unit_plus_one(T** p, size_t count) { regions.push_back({p, count * sizeof(T), count * sizeof(T)}); }
-
-    // The layout, stated once: region after region, each at a multiple of 256 bytes.  Returns the bytes `n` units in flight
-    // take; a null base only measures.
-    size_t carve(char* base, int n) const {
-        size_t at = 0;
-        for (const Region& r : regions) {
-            if (base) { char* q = base + at; memcpy(r.ptr, &q, sizeof q); }
-            at += up256(r.fixed + (size_t)n * r.unit);
-        }
-        return at;
-    }
-
-    // The units in flight - min(want, at_most), or the largest count (one at least) that needs no more than the buffer or `share`
-    // of the memory that is free or the arena's - and the buffer.  Returns the count, or < 0 (out_of_memory(): the allocation failed).
-    int plan(int want, int at_most, double share) {
-        HIPCHK(hipSetDevice(c->device));
-        size_t budget = c->scratch_bytes, fr = 0, tot = 0;
-        units = std::max(1, std::min(want, at_most));
-        if (carve(nullptr, units) > budget) {
-            HIPCHK(hipMemGetInfo(&fr, &tot));
-            budget = std::max(budget, (size_t)(share * (double)(fr + budget)));
-        }
-        while (units > 1 && carve(nullptr, units) > budget) --units;
-        bytes = carve(nullptr, units);
-        if (bytes > c->scratch_bytes) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (int rc = dev_free(c, c->scratch)) return rc;
-            c->scratch = nullptr; c->scratch_bytes = 0;
-            if (int rc = dev_alloc(c, &c->scratch, bytes)) { (void)hipGetLastError(); return rc; }
-            c->scratch_bytes = bytes;
-        }
-        carve(c->scratch, units);
-        return units;
-    }
-    bool out_of_memory() const { return bytes > c->scratch_bytes; }   // the buffer does not hold the planned layout
-};
-
-// ---- stack chunks: the walk of the frame-wise and pair-wise calls through the scratch arena --------
-constexpr int PRE_MAX_FLIGHT = 16;        // units in flight when the caller leaves the number to the library
-constexpr int PRE_MAX_WANT = 4096;        // ... and at most when it does not (grid z)
-
-// One call of the adaptive threshold, CLAHE, the resize, Farnebaeck's flow, the result filter, the comparison of two results
-// or the Liu-Shen flow over a stack of `n` units (frames or pairs), on the stack of that call: the call declares
-// its regions into the arena sc, plan() sizes the chunk and carves the buffer, range() reduces a stack, run() walks the chunks.
-// An input holds one frame per unit, or - a pair stack - one more: pair k reads frames k and k + 1, so a chunk of nf pairs reads
-// nf + 1.  What a staged input holds is recorded here alone: nothing staged outlives the call.
-struct FrameChunks {
-    struct In { const double* stack; double* slot; int extra, k0, nf; };   // _host: slot holds frames [k0, k0 + nf + extra) of stack (nf 0: nothing)
-    struct Out { char* caller; size_t bytes; char* slot; };        // bytes per unit
-    vof_ctx* const c; const char* const what;                      // what: the call, for messages
-    const int n, want; const bool host;                            // units; the caller's frames_in_flight
-    const size_t fs;                                               // doubles per unit of an input stack
-    Scratch sc;
-    int cap = 0;                                                   // units in flight (plan)
-    PpRange* part = nullptr;                                       // the range reduction's partial records, then its result
-    double rg[3] = {};                                             // ... and what range() found
-    static constexpr int MAX_IN = 6, MAX_OUT = 3;                  // the comparison of two results reads six stacks
-    In in[MAX_IN] = {}; Out out[MAX_OUT] = {}; int n_in = 0, n_out = 0;
-
-    FrameChunks(vof_ctx* c_, const char* what_, int n_, int want_, bool host_) : c(c_), what(what_), n(n_), want(want_), host(host_), fs(frame_stride(c_)), sc(c_) {
-        sc.once(&part, (size_t)PP_RANGE_BLOCKS + 1);
-    }
-
-    // what every frame-wise entry point checks first
-    static int check(vof_ctx* c, std::initializer_list<const void*> pointers, int n, const char* n_name) {
-        if (!c) return -1;
-        for (const void* p : pointers) if (!p) { c->err = "NULL pointer"; return -1; }
-        if (n < 1) { c->err = std::string(n_name) + " must be >= 1"; return -1; }
-        return 0;
-    }
-
-    void input(const double* stack, bool pairs = false) {          // fs doubles per frame; pairs: a pair stack; _host: staged
-        if (host && pairs) sc.per_unit_plus_one(&in[n_in].slot, fs);
-        else if (host) sc.per_unit(&in[n_in].slot, fs);
-        in[n_in].extra = pairs ? 1 : 0;
-        in[n_in++].stack = stack;
-    }
-    void output(void* caller, size_t unit_bytes) {                 // _host: staged, then copied to `caller`
-        if (host) sc.per_unit(&out[n_out].slot, unit_bytes);
-        out[n_out].caller = (char*)caller; out[n_out++].bytes = unit_bytes;
-    }
-
-    // the chunk size - `want`, or 16 where that is left to the library, within a quarter of the free device memory - and the arena
-    int plan() {
-        const int rc = sc.plan(want > 0 ? want : PRE_MAX_FLIGHT, std::min(PRE_MAX_WANT, n), 0.25);
-        if (rc < 0 && sc.out_of_memory())
-            c->err = std::string(what) + ": no device memory for " + std::to_string(sc.bytes >> 20) + " MiB of scratch (" +
-                     std::to_string(sc.units) + " frame(s) in flight): " + c->err;
-        cap = rc;
-        return rc < 0 ? rc : 0;
-    }
-
-    // Units [k0, k0 + nf) of input s on the device: the caller's own memory, or the slot - uploaded unless it holds exactly these
-    int staged(int s, int k0, int nf, const double** p) {
-        In& i = in[s];
-        *p = host ? i.slot : i.stack + (size_t)k0 * fs;
-        if (!host || (i.nf == nf && i.k0 == k0)) return 0;
-        if (int rc = h2d_bounced(c, i.slot, i.stack + (size_t)k0 * fs, (size_t)(nf + i.extra) * fs * sizeof(double))) return rc;
-        i.k0 = k0; i.nf = nf;
-        return 0;
-    }
-
-    // rg = (max, min of the finite values, non-finite count) of the whole of input s (_host: chunk by chunk through its slot), to
-    // `report` too if there is one; then return code 1 and the message if anything is non-finite or outside the permitted [lo, hi]
-    int range(int s, double lo, double hi, const char* outside, const char* note = "", double* report = nullptr) {
-        PpRange* const rng = part + PP_RANGE_BLOCKS;
-        PpRange acc{-INFINITY, INFINITY, 0};
-        const int chunk = host ? cap : n;
-        for (int k0 = 0; k0 < n; k0 += chunk) {
-            const int nf = std::min(chunk, n - k0);
-            const double* src;
-            if (int rc = staged(s, k0, nf, &src)) return rc;
-            const size_t m = (size_t)nf * fs;
-            const int nb = (int)std::min<size_t>(PP_RANGE_BLOCKS, (m + 8 * PP_BLOCK - 1) / (8 * PP_BLOCK));
-            c->cur_units = nf;
-            {
-                Prof prof(c, VOF_K_PREPROCESS, PP_ST_RANGE, 8.0 * fs);
-                k_pp_range<<<nb, PP_BLOCK, 0, c->stream>>>(src, m, part);
-                k_pp_range_final<<<1, 64, 0, c->stream>>>(part, nb, rng);
-            }
-            HIPCHK(hipGetLastError());
-            PpRange r;
-            if (int rc = d2h_bounced(c, &r, rng, sizeof r)) return rc;
-            acc.vmax = std::max(acc.vmax, r.vmax); acc.vmin = std::min(acc.vmin, r.vmin); acc.bad += r.bad;
-        }
-        rg[0] = acc.vmax; rg[1] = acc.vmin; rg[2] = (double)acc.bad;
-        if (report) memcpy(report, rg, sizeof rg);
-        const char* found = rg[2] > 0 ? "non-finite values" : (rg[1] < lo || rg[0] > hi ? outside : nullptr);
-        if (!found) return 0;
-        c->err = std::string(what) + ": the movie holds " + found + note;
-        return 1;
-    }
-
-    // The chunks in turn: body(k0, nf, inputs, outputs) enqueues the kernels of units [k0, k0 + nf) - device pointers, one per
-    // declared input and output - and returns 0; _host: the outputs are then copied to the caller's arrays.
-    template <class Body>
-    int run(Body&& body) {
-        for (int k0 = 0; k0 < n; k0 += cap) {
-            const int nf = std::min(cap, n - k0);
-            const double* src[MAX_IN] = {}; void* dst[MAX_OUT] = {};
-            for (int s = 0; s < n_in; ++s) if (int rc = staged(s, k0, nf, &src[s])) return rc;
-            for (int a = 0; a < n_out; ++a) dst[a] = host ? out[a].slot : out[a].caller + (size_t)k0 * out[a].bytes;
-            c->cur_units = nf;
-            if (int rc = body(k0, nf, src, dst)) return rc;
-            HIPCHK(hipGetLastError());
-            for (int a = 0; host && a < n_out; ++a)
-                if (int rc = d2h_bounced(c, out[a].caller + (size_t)k0 * out[a].bytes, dst[a], (size_t)nf * out[a].bytes)) return rc;
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return 0;
-    }
-};
-
-// (count, mean, M2 = sum (x - mean)^2) of one chunk, exact two-pass; chunks are merged with Chan's formula
-struct Moments {
-    double n = 0, mean = 0, m2 = 0;
-    void merge(double nb, double meanb, double m2b) {
-        if (nb == 0) return;
-        double nt = n + nb, d = meanb - mean;
-        m2 += m2b + d * d * n * nb / nt;
-        mean += d * nb / nt;
-        n = nt;
-    }
-};
-
-// ---- sweeps of the box flow: what vary_boxsize and vary_blursize share --------------------------------------------
-constexpr int BS_MAX_CHUNK = 32;          // pairs per launch (grid z) at most; more adds nothing once the chip is full
-
-// Mean and variance of a field per list entry, shared by the box-size and the blur sweep: the two-pass reduction of
-// vof_field_moments_dev per pair on the device, sums [field][pass][entry][pair][3]; a pair is the unit the host merges.
-struct PairMoments {
-    double* d_mom; double* d_part;        // device: the sums; the partials of one chunk
-    size_t n_mom;                         // n_entries * P * 3
-    int n_entries, P, mom_blk;
-};
-
-inline int pair_moments_blocks(size_t fs) { return (int)std::min<size_t>(256, std::max<size_t>(1, (fs + 4 * RBLK - 1) / (4 * RBLK))); }
-
-// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote x: no host round trip in a sweep
-static void pair_moments_enqueue(vof_ctx* c, const PairMoments& m, const double* x, size_t fs, int field, int b, int k0, int np) {
-    const dim3 gm(m.mom_blk, np);
-    double* first = m.d_mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P + k0) * 3;
-    double* second = first + m.n_mom;
-    Prof prof(c, VOF_K_REDUCE, 0, 16.0 * fs);
-    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, nullptr, m.d_part);
-    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, first);
-    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, first, m.d_part);
-    k_sum3<<<np, 64, 0, c->stream>>>(m.d_part, m.mom_blk, second);
-}
-
-// mom: the host copy of d_mom.  Pairs merged in order with Chan's formula; per pair the arithmetic of chunk_moments
-static Moments pair_moments_merged(const PairMoments& m, const double* mom, size_t fs, int field, int b) {
-    Moments acc;
-    const double* first = mom + ((size_t)(2 * field) * m.n_entries * m.P + (size_t)b * m.P) * 3;
-    const double* second = first + m.n_mom;
-    const double n = (double)fs;
-    for (int k = 0; k < m.P; ++k) {
-        double mean = first[3 * k] / n;
-        const double s0 = second[3 * k], s1 = second[3 * k + 1];
-        mean += s0 / n;                                         // first-order correction of the rounded mean
-        acc.merge(n, mean, s1 - s0 * s0 / n);
-    }
-    return acc;
-}
-
-// what every sweep is asked for besides its list
-struct SweepBase {
-    const double* movie; int n_frames;
-    double delta_x, delta_t; int remodel, quirks;
-    const double* edges; int bins; int64_t* hist;               // speed
-    const int32_t* probe_ij; int n_probes; double* probe_out;
-    double* outs[4];                      // v_x, v_y, speed, net_remodelling: all NULL = stats only
-    bool host;                            // movie and outs are host memory
-};
-
-static int sweep_check(vof_ctx* c, const SweepBase& r, const void* stats) {
-    if (!r.movie) { c->err = "movie is NULL"; return -1; }
-    if (!stats) { c->err = "stats is NULL"; return -1; }
-    if (r.n_frames < 2) { c->err = "need at least two frames"; return -1; }
-    if (r.delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
-    if (r.edges && (r.bins < 1 || !r.hist)) { c->err = "histogram_edges needs histogram_bins >= 1 and histograms"; return -1; }
-    if (r.edges && !(r.edges[r.bins] > r.edges[0])) { c->err = "histogram_edges must increase"; return -1; }
-    if (r.probe_ij) {
-        if (r.n_probes < 1 || !r.probe_out) { c->err = "probe_ij needs n_probes >= 1 and probe_speeds"; return -1; }
-        for (int l = 0; l < r.n_probes; ++l)
-            if (r.probe_ij[2 * l] < 0 || r.probe_ij[2 * l] >= c->Ni || r.probe_ij[2 * l + 1] < 0 || r.probe_ij[2 * l + 1] >= c->Nj) {
-                c->err = "probe outside the image"; return -1;
-            }
-    }
-    const bool any = r.outs[0] || r.outs[1] || r.outs[2] || r.outs[3];
-    if (any && (!r.outs[0] || !r.outs[1] || !r.outs[2])) { c->err = "v_x, v_y and speed must be given together (or all NULL)"; return -1; }
-    if (any && r.remodel && !r.outs[3]) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
-    return 0;
-}
-
-// pairs a sweep keeps in flight at most: a _host sweep stages no more than the context's slots
-inline int sweep_want(const vof_ctx* c, const SweepBase& r) {
-    return std::min(std::min(r.n_frames - 1, BS_MAX_CHUNK), r.host ? c->B : BS_MAX_CHUNK);
-}
-
-// where the fields of pairs k0 .. of entry b go on the device: the caller's stacks (_dev with fields) or the chunk planes
-struct SweepDst {
-    double* f[4];
-    size_t oo;                            // offset of the chunk in the caller's stacks
-    bool keep_v, keep_g;                  // v_x / v_y and net_remodelling are wanted (speed always is)
-};
-
-static SweepDst sweep_dst(const SweepBase& r, double* const chunk_out[4], size_t fs, int b, int k0) {
-    SweepDst d;
-    const bool fields = r.outs[0] != nullptr;
-    d.oo = ((size_t)b * (r.n_frames - 1) + k0) * fs;
-    for (int f = 0; f < 4; ++f) d.f[f] = (fields && !r.host && r.outs[f]) ? r.outs[f] + d.oo : chunk_out[f];
-    d.keep_v = fields;
-    d.keep_g = r.remodel || (fields && !r.host && r.outs[3]);      // _host zero-fills on the host
-    return d;
-}
-
-// _host with fields: np pairs from the chunk planes into the caller's stacks; net_remodelling is zero where it was not computed
-static int sweep_copy_out(vof_ctx* c, const SweepBase& r, const SweepDst& d, size_t fs, int np) {
-    if (!r.host) return 0;
-    const size_t bytes = (size_t)np * fs * sizeof(double);
-    for (int f = 0; f < 4; ++f) {
-        if (!r.outs[f]) continue;
-        if (f == 3 && !r.remodel) memset(r.outs[f] + d.oo, 0, bytes);
-        else if (int rc = d2h_bounced(c, r.outs[f] + d.oo, d.f[f], bytes)) return rc;
-    }
-    return 0;
-}
-
-// The statistics every sweep keeps per list entry: histogram and non-finite count of the speed, the speed at the probes, mean
-// and variance of speed and net_remodelling.  What the kernels read and write are regions of the sweep's arena.  The counters
-// - the tail's, then the sweep's own - are the last regions the sweep declares: one span from d_bad to the arena's end, zeroed
-// by one memset and brought back by one copy.
-struct SweepTail {
-    const SweepBase* r; const char* name;
-    int n; size_t fs;
-    PairMoments pm;
-    size_t n_hist, n_probe, n_mom_all;
-    double *d_edges, *d_probe;
-    unsigned long long *d_bad, *d_hist;
-    int32_t* d_pij;
-    std::vector<unsigned long long> counters;     // host copy of the span (sweep_tail_finish)
-    const unsigned long long* host(const unsigned long long* dev) const { return counters.data() + (dev - d_bad); }
-};
-
-// declares the tail's regions, the counters last: the sweep's own counters follow, everything else of the sweep comes before
-static void sweep_tail_regions(Scratch& sc, SweepTail& t, const SweepBase& r, const char* name, int n) {
-    const int P = r.n_frames - 1;
-    t.r = &r; t.name = name; t.n = n; t.fs = frame_stride(sc.c);
-    t.n_hist = r.edges ? (size_t)n * r.bins : 0;
-    t.n_probe = r.probe_ij ? (size_t)n * P * r.n_probes : 0;
-    // moments: per field (speed, net_remodelling), pass, entry and pair the three sums of k_sum3; then the partials of a chunk
-    const size_t n_mom = (size_t)n * P * 3;
-    t.n_mom_all = 2 * (r.remodel ? 2 : 1) * n_mom;
-    t.pm = PairMoments{nullptr, nullptr, n_mom, n, P, pair_moments_blocks(t.fs)};
-    sc.once(&t.d_edges, r.edges ? (size_t)r.bins + 1 : 0);
-    sc.once(&t.d_probe, t.n_probe);
-    sc.once(&t.pm.d_mom, t.n_mom_all);
-    sc.per_unit(&t.pm.d_part, (size_t)3 * t.pm.mom_blk);
-    sc.once(&t.d_pij, r.probe_ij ? (size_t)2 * r.n_probes : 0);
-    sc.once(&t.d_bad, (size_t)n);
-    sc.once(&t.d_hist, t.n_hist);
-}
-
-// Plans the sweep's arena, zeroes the counters and uploads edges and probes.  Returns the pairs in flight (1 .. sweep_want) or
-// an error code (< 0); `unit`: what the planes of the message are counted for.
-static int sweep_tail_begin(Scratch& sc, SweepTail& t, const char* unit) {
-    vof_ctx* const c = sc.c;
-    const SweepBase& r = *t.r;
-    const int cap = sc.plan(sweep_want(c, r), r.n_frames - 1, 0.8);
-    if (cap < 0 && sc.units == 1 && sc.out_of_memory()) {       // not even one pair fits; a failed allocation of more stays what it is
-        c->err = std::string("the ") + t.name + " does not fit into the free device memory (" +
-                 std::to_string(sc.bytes / (t.fs * sizeof(double))) + " planes of n_i x n_j doubles" + unit + ")";
-        return -3;
-    }
-    if (cap < 0) return cap;
-    t.counters.resize((size_t)(c->scratch + sc.bytes - (char*)t.d_bad) / 8);
-    if (hipMemsetAsync(t.d_bad, 0, t.counters.size() * 8, c->stream) != hipSuccess) { c->err = "memset failed"; return -2; }
-    if (r.edges) if (int rc = h2d_bounced(c, t.d_edges, r.edges, (size_t)(r.bins + 1) * 8)) return rc;
-    if (r.probe_ij) if (int rc = h2d_bounced(c, t.d_pij, r.probe_ij, (size_t)2 * r.n_probes * sizeof(int32_t))) return rc;
-    return cap;
-}
-
-// pairs k0 .. k0 + np of entry b, enqueued behind the kernels that wrote them: first the counts and the probes of the speed ...
-static void sweep_tail_speed(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed) {
-    const SweepBase& r = *t.r;
-    Prof prof(c, VOF_K_REDUCE, 0);
-    const size_t m = (size_t)np * t.fs;
-    const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
-    k_bs_counts<<<nb, 256, 0, c->stream>>>(speed, m, t.d_edges, r.edges ? r.bins : 0, r.edges ? t.d_hist + (size_t)b * r.bins : nullptr,
-                                           t.d_bad + b);
-    if (r.probe_ij) {
-        const int nt = np * r.n_probes;
-        k_bs_probe<<<(nt + 255) / 256, 256, 0, c->stream>>>(speed, t.fs, c->Nj, np, t.d_pij, r.n_probes,
-                                                            t.d_probe + ((size_t)b * t.pm.P + k0) * r.n_probes);
-    }
-}
-
-// ... then, behind whatever the sweep adds on the same fields, the moments; asks for the error of the chunk's launches
-static int sweep_tail_moments(vof_ctx* c, const SweepTail& t, int b, int k0, int np, const double* speed, const double* gamma) {
-    const SweepBase& r = *t.r;
-    pair_moments_enqueue(c, t.pm, speed, t.fs, 0, b, k0, np);
-    if (r.remodel) pair_moments_enqueue(c, t.pm, gamma, t.fs, 1, b, k0, np);
-    if (hipGetLastError() != hipSuccess) { c->err = std::string(t.name) + ": launch failed"; return -2; }
-    return 0;
-}
-
-// waits for the sweep, brings the statistics back and fills the fields the two stats records share
-template <class Stats>
-static int sweep_tail_finish(vof_ctx* c, SweepTail& t, Stats* stats) {
-    const SweepBase& r = *t.r;
-    if (int rc = d2h_bounced(c, t.counters.data(), t.d_bad, t.counters.size() * 8)) return rc;
-    if (r.probe_ij) if (int rc = d2h_bounced(c, r.probe_out, t.d_probe, t.n_probe * 8)) return rc;
-    std::vector<double> mom(t.n_mom_all);
-    if (int rc = d2h_bounced(c, mom.data(), t.pm.d_mom, mom.size() * 8)) return rc;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "stream synchronize failed"; return -2; }
-    for (size_t i = 0; i < t.n_hist; ++i) r.hist[i] = (int64_t)t.host(t.d_hist)[i];
-    for (int b = 0; b < t.n; ++b) {
-        Stats& o = stats[b];
-        memset(&o, 0, sizeof o);
-        const Moments ms = pair_moments_merged(t.pm, mom.data(), t.fs, 0, b);
-        o.speed_mean = ms.mean; o.speed_variance = ms.m2 / ms.n;
-        if (r.remodel) {
-            const Moments mr = pair_moments_merged(t.pm, mom.data(), t.fs, 1, b);
-            o.remodelling_mean = mr.mean; o.remodelling_variance = mr.m2 / mr.n;
-        }
-        o.nonfinite_count = (int64_t)t.host(t.d_bad)[b];
-    }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -3159,11 +2529,13 @@ int vof_solve_stack_dev(vof_ctx* c, const double* movie, int n_frames, const vof
     return 0;
 }
 
+}  // extern "C"
+
 // Device staging of the host API: frames of one batch (+1) and TWO sets of output buffers, so that the device-to-host
 // copies of batch k (copy stream) overlap the solve of batch k+1 (main stream).  st_* serve vof_solve_stack_host,
 // vof_vary_regularisation_host, vof_debug_setup and - its chunks are the context's pairs - vof_box_flow_host; every other call
 // stages through its arena.
-static int ensure_staging(vof_ctx* c, bool double_buffer) {
+int vof::host::ensure_staging(vof_ctx* c, bool double_buffer) {
     const size_t fs = frame_stride(c);
     if (!c->st_movie) {
         if (int rc = dev_alloc(c, &c->st_movie, (size_t)(c->B + 1) * fs)) return rc;
@@ -3183,6 +2555,16 @@ static int ensure_staging(vof_ctx* c, bool double_buffer) {
     }
     return 0;
 }
+// the block reductions are this source's; the moments of the pair calls (vof_pairs.hip, pair_moments_enqueue) run through here
+void vof::host::pair_sums_enqueue(vof_ctx* c, const double* x, size_t fs, int nblk, int np, double* part, double* first, double* second) {
+    const dim3 gm(nblk, np);
+    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, nullptr, part);
+    k_sum3<<<np, 64, 0, c->stream>>>(part, nblk, first);
+    k_bs_moments<<<gm, RBLK, 0, c->stream>>>(x, fs, first, part);
+    k_sum3<<<np, 64, 0, c->stream>>>(part, nblk, second);
+}
+
+extern "C" {
 
 int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vof_params* p, double* v_x,
                          double* v_y, double* remodelling, double* speed, vof_pair_stats* stats) {
@@ -3339,77 +2721,6 @@ int vof_solve_stack_host(vof_ctx* c, const double* movie, int n_frames, const vo
     pin_b.release();
     hmark("unpinned");
     return rc_all;
-}
-
-// workspace of the blur of up to `frames` frames per blur_frames call, declared into the caller's arena: one chunk of
-// row-filtered frames, and room for the taps of `radius` where the caller does not bring its own (w null)
-constexpr int BLUR_CHUNK = 16;
-static void blur_regions(Scratch& sc, int frames, double** tmp, double** w = nullptr, int radius = 0) {
-    sc.once(tmp, (size_t)std::min(frames, BLUR_CHUNK) * frame_stride(sc.c));
-    if (w) sc.once(w, (size_t)2 * radius + 1);
-}
-
-// n_frames device-resident frames with the taps already on the device at w and the row-filtered chunk at tmp (blur_regions),
-// enqueued on the context's stream (out may alias in).  Radii BL_RMIN .. BL_RMAX take the LDS-tiled kernels, same bits as k_blur1d.
-static int blur_frames(vof_ctx* c, const double* in, double* out, int n_frames, int radius, double* tmp, const double* w) {
-    size_t fs = frame_stride(c);
-    const int chunk = std::min(n_frames, BLUR_CHUNK);
-    bool tiled = radius >= BL_RMIN && radius <= BL_RMAX;
-    if (const char* e = getenv("VOF_BLUR_TILED")) tiled = tiled && e[0] != '0';
-    if (tiled && !c->bl_lds_set) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_blur1d_tiled<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blur_tiled_lds(0, BL_RMAX)));
-        c->bl_lds_set = true;
-    }
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        int nf = std::min(chunk, n_frames - f0);
-        Prof p(c, VOF_K_RHS, 0);
-        if (tiled) {
-            const dim3 g0((c->Nj + BX - 1) / BX, (c->Ni + BL_TI - 1) / BL_TI, nf), g1(g0.x, (c->Ni + BL_TR - 1) / BL_TR, nf);
-            k_blur1d_tiled<0><<<g0, blk2d, blur_tiled_lds(0, radius), c->stream>>>(in + (size_t)f0 * fs, tmp, c->Ni, c->Nj, w, radius);
-            k_blur1d_tiled<1><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
-        } else {
-            dim3 g = grid2d(c->Ni, c->Nj, nf);
-            k_blur1d<0><<<g, blk2d, 0, c->stream>>>(in + (size_t)f0 * fs, tmp, c->Ni, c->Nj, w, radius);
-            k_blur1d<1><<<g, blk2d, 0, c->stream>>>(tmp, out + (size_t)f0 * fs, c->Ni, c->Nj, w, radius);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// The body of both blur entry points.  _dev: the frames where they lie.  _host: a chunk at a time up into a region of the arena,
-// blurred in place, down - as pageable asynchronous copies, as they always were: through the bounce buffer the call measured half
-// as slow again (profiles/r22_scratch_arena_summary.md).  The taps take the bounce buffer.
-static int blur_stack(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius, bool host) {
-    if (!c) return -1;
-    if (!in || !out || !weights) { c->err = "NULL pointer"; return -1; }
-    if (host && n_frames < 1) return 0;
-    if (n_frames < 1 || radius < 0 || radius > 4096) { c->err = "bad n_frames / radius"; return -1; }
-    const size_t fs = frame_stride(c);
-    Scratch sc(c);
-    double *io = nullptr, *tmp, *w;
-    if (host) sc.once(&io, (size_t)std::min(n_frames, BLUR_CHUNK) * fs);
-    blur_regions(sc, n_frames, &tmp, &w, radius);
-    if (int rc = sc.plan(1, 1, 0.8); rc < 0) return rc;
-    if (int rc = h2d_bounced(c, w, weights, (size_t)(2 * radius + 1) * sizeof(double))) return rc;
-    if (host) {
-        for (int f0 = 0; f0 < n_frames; f0 += BLUR_CHUNK) {
-            const int nf = std::min(BLUR_CHUNK, n_frames - f0);
-            HIPCHK(hipMemcpyAsync(io, in + (size_t)f0 * fs, (size_t)nf * fs * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            if (int rc = blur_frames(c, io, io, nf, radius, tmp, w)) return rc;
-            HIPCHK(hipMemcpyAsync(out + (size_t)f0 * fs, io, (size_t)nf * fs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-        }
-    } else if (int rc = blur_frames(c, in, out, n_frames, radius, tmp, w)) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int vof_blur_stack_dev(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius) {
-    return blur_stack(c, in, out, n_frames, weights, radius, false);
-}
-int vof_blur_stack_host(vof_ctx* c, const double* in, double* out, int n_frames, const double* weights, int radius) {
-    return blur_stack(c, in, out, n_frames, weights, radius, true);
 }
 
 // sum (x - shift), sum (x - shift)^2 over n device doubles -> out2 (host); uses ctx->partials / func3 as scratch
@@ -3967,1585 +3278,5 @@ int vof_debug_coarse_solve(vof_ctx* c, const double* r_host, double* e_host) {
     VDISPATCH(c, coarse_solve_t<VT>(c, (const VT*)c->kp, (VT*)c->kv, c->npairs, ALL_PAIRS));
     return dbg_down(c, e_host, c->kv, n);
 }
-
-// ---- box least-squares flow (conduct_optical_flow, OF.py:24-218) ------------------------------------------------
-constexpr int BF_GENERAL_CHUNK = 4;       // pairs per launch of the general path (its scratch: 11 planes per pair)
-constexpr int BF_FUSED_CHUNK = 16384;     // pairs per launch of the fused kernel (grid z)
-
-static int box_flow_check(vof_ctx* c, const double* movie, int n_frames, int box_size, double delta_t, int include_remodelling,
-                          const double* v_x, const double* v_y, const double* speed, const double* net_remodelling) {
-    if (!movie || !v_x || !v_y || !speed) { c->err = "NULL array pointer"; return -1; }
-    if (include_remodelling && !net_remodelling) { c->err = "net_remodelling is NULL with include_remodelling"; return -1; }
-    if (n_frames < 2) { c->err = "need at least two frames"; return -1; }
-    if (box_size < 1) { c->err = "box_size must be >= 1"; return -1; }
-    if (delta_t == 0.0) { c->err = "delta_t must not be 0"; return -1; }
-    return 0;
-}
-
-static bool box_flow_fused(int box_size) {                 // the fused kernel, or the general path: three kernels through scratch planes
-    const char* e = getenv("VOF_BOXFLOW_FUSED");
-    return box_size / 2 <= BF_HMAX && !(e && e[0] == '0');
-}
-// the planes of the general path, declared into the caller's arena where box_flow_pairs will take that path (none otherwise)
-static void box_flow_regions(Scratch& sc, int box_size, double** planes) {
-    sc.once(planes, box_flow_fused(box_size) ? 0 : (size_t)BF_GENERAL_CHUNK * 11 * frame_stride(sc.c));
-}
-
-// P pairs of a device-resident movie into device-resident outputs, enqueued on the context's stream; planes: box_flow_regions.
-static int box_flow_pairs(vof_ctx* c, double* planes, const double* movie, int P, int box_size, double delta_x, double delta_t,
-                          int include_remodelling, int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
-    const size_t fs = frame_stride(c);
-    BoxArgs a{};
-    a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj; a.h = box_size / 2;
-    a.cend = reference_quirks ? std::min(c->Ni, c->Nj) : c->Nj;      // OF.py:108 clamps the column window with N_i
-    a.quirks = reference_quirks ? 1 : 0;
-    a.n_box = (double)box_size * (double)box_size;
-    a.scale = delta_x / delta_t;
-    auto at = [&](int k0) {
-        a.movie = movie + (size_t)k0 * fs;
-        a.vx = v_x + (size_t)k0 * fs; a.vy = v_y + (size_t)k0 * fs; a.speed = speed + (size_t)k0 * fs;
-        a.gamma = net_remodelling ? net_remodelling + (size_t)k0 * fs : nullptr;
-    };
-    if (box_flow_fused(box_size)) {
-        if (!c->bf_lds_set) {
-            const int lds = (int)bf_fused_lds(BF_HMAX);
-            HIPCHK(hipFuncSetAttribute((const void*)k_boxflow_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIPCHK(hipFuncSetAttribute((const void*)k_boxflow_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            c->bf_lds_set = true;
-        }
-        const size_t lds = bf_fused_lds(a.h);
-        for (int k0 = 0; k0 < P; k0 += BF_FUSED_CHUNK) {
-            const int np = std::min(BF_FUSED_CHUNK, P - k0);
-            at(k0);
-            const dim3 g((c->Nj + BF_TJ - 1) / BF_TJ, (c->Ni + BF_TI - 1) / BF_TI, np);
-            c->cur_units = np;
-            Prof prof(c, VOF_K_RHS, 0);
-            if (include_remodelling) k_boxflow_fused<true><<<g, BF_THREADS, lds, c->stream>>>(a);
-            else k_boxflow_fused<false><<<g, BF_THREADS, lds, c->stream>>>(a);
-        }
-    } else {
-        double* der = planes;
-        double* rows = planes + (size_t)BF_GENERAL_CHUNK * 3 * fs;
-        for (int k0 = 0; k0 < P; k0 += BF_GENERAL_CHUNK) {
-            const int np = std::min(BF_GENERAL_CHUNK, P - k0);
-            at(k0);
-            const dim3 g = grid2d(c->Ni, c->Nj, np);
-            c->cur_units = np;
-            Prof prof(c, VOF_K_RHS, 0);
-            k_bf_derived<<<g, blk2d, 0, c->stream>>>(a, der);
-            if (include_remodelling) {
-                k_bf_hsum<true><<<g, blk2d, 0, c->stream>>>(a, der, rows);
-                k_bf_vsum<true><<<g, blk2d, 0, c->stream>>>(a, rows);
-            } else {
-                k_bf_hsum<false><<<g, blk2d, 0, c->stream>>>(a, der, rows);
-                k_bf_vsum<false><<<g, blk2d, 0, c->stream>>>(a, rows);
-            }
-        }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int vof_box_flow_dev(vof_ctx* c, const double* movie, int n_frames, int box_size, double delta_x, double delta_t, int include_remodelling,
-                     int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
-    if (!c) return -1;
-    if (int rc = box_flow_check(c, movie, n_frames, box_size, delta_t, include_remodelling, v_x, v_y, speed, net_remodelling)) return rc;
-    Scratch sc(c);
-    double* planes = nullptr;
-    box_flow_regions(sc, box_size, &planes);
-    if (int rc = sc.plan(1, 1, 0.8); rc < 0) return rc;
-    if (int rc = box_flow_pairs(c, planes, movie, n_frames - 1, box_size, delta_x, delta_t, include_remodelling, reference_quirks, v_x, v_y, speed,
-                                net_remodelling)) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int vof_box_flow_host(vof_ctx* c, const double* movie, int n_frames, int box_size, double delta_x, double delta_t, int include_remodelling,
-                      int reference_quirks, double* v_x, double* v_y, double* speed, double* net_remodelling) {
-    if (!c) return -1;
-    if (int rc = box_flow_check(c, movie, n_frames, box_size, delta_t, include_remodelling, v_x, v_y, speed, net_remodelling)) return rc;
-    Scratch sc(c);
-    double* planes = nullptr;
-    box_flow_regions(sc, box_size, &planes);
-    if (int rc = sc.plan(1, 1, 0.8); rc < 0) return rc;
-    if (int rc = ensure_staging(c, false)) return rc;
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
-    const int P = n_frames - 1;
-    double* outs[4] = {v_x, v_y, speed, include_remodelling ? net_remodelling : nullptr};
-    for (int k0 = 0; k0 < P; k0 += c->B) {
-        const int np = std::min(c->B, P - k0);
-        if (int rc = h2d_bounced(c, c->st_movie, movie + (size_t)k0 * fs, (size_t)(np + 1) * fb)) return rc;
-        if (int rc = box_flow_pairs(c, planes, c->st_movie, np, box_size, delta_x, delta_t, include_remodelling, reference_quirks, c->st_out[0],
-                                    c->st_out[1], c->st_out[2], include_remodelling ? c->st_out[3] : nullptr)) return rc;
-        for (int f = 0; f < 4; ++f)
-            if (outs[f])
-                if (int rc = d2h_bounced(c, outs[f] + (size_t)k0 * fs, c->st_out[f], (size_t)np * fb)) return rc;
-    }
-    if (!include_remodelling && net_remodelling) memset(net_remodelling, 0, (size_t)P * fb);
-    return 0;
-}
-
-// Frames k0 .. k0 + np of a pair chunk of sweep r on the device, *p: the caller's own (_dev), or `frames` - a per_unit_plus_one
-// region - where they are uploaded (_host) and, with device taps, blurred in place (tmp: blur_regions)
-static int pair_chunk_frames(vof_ctx* c, const SweepBase& r, int k0, int np, double* frames, const double* taps, int radius, double* tmp,
-                             const double** p) {
-    const size_t fs = frame_stride(c);
-    *p = r.movie + (size_t)k0 * fs;
-    if (r.host) {
-        if (int rc = h2d_bounced(c, frames, *p, (size_t)(np + 1) * fs * sizeof(double))) return rc;
-        *p = frames;
-    }
-    if (taps) {
-        if (int rc = blur_frames(c, *p, frames, np + 1, radius, tmp, taps)) return rc;
-        *p = frames;
-    }
-    return 0;
-}
-
-// ---- box-size sweep of the box flow (vary_boxsize; vof_boxsweep.hpp) ---------------------------------------------
-struct SweepReq : SweepBase {
-    const int32_t* boxes; int n_boxes;
-    const double* blur_w; int blur_r;
-    vof_boxsize_stats* stats;
-};
-
-static int vary_boxsize_impl(vof_ctx* c, const SweepReq& r) {
-    if (!c) return -1;
-    if (int rc = sweep_check(c, r, r.stats)) return rc;
-    if (!r.boxes || r.n_boxes < 1) { c->err = "the list of box sizes is empty"; return -1; }
-    for (int b = 0; b < r.n_boxes; ++b)
-        if (r.boxes[b] < 1) { c->err = "every box size must be >= 1"; return -1; }
-    if (r.blur_w && (r.blur_r < 0 || r.blur_r > 4096)) { c->err = "bad blur_radius"; return -1; }
-    const size_t fs = frame_stride(c);
-    const int P = r.n_frames - 1, NQ = r.remodel ? 8 : 5;
-    // the arena: cap + 1 frames, and per pair 3 derived planes, R / C / W of every quantity and 4 chunk outputs
-    Scratch sc(c);
-    double *frames, *der, *chunk_out[4], *blur_tmp = nullptr, *blur_w = nullptr;
-    SweepArgs s{};
-    s.fs = fs; s.Ni = c->Ni; s.Nj = c->Nj;
-    sc.per_unit_plus_one(&frames, fs);
-    sc.per_unit(&der, 3 * fs);
-    for (double** q : {&s.R, &s.C, &s.W}) sc.per_unit(q, (size_t)NQ * fs);
-    for (double*& q : chunk_out) sc.per_unit(&q, fs);
-    if (r.blur_w) blur_regions(sc, sweep_want(c, r) + 1, &blur_tmp, &blur_w, r.blur_r);
-    SweepTail tail;
-    sweep_tail_regions(sc, tail, r, "box-size sweep", r.n_boxes);
-    const int cap = sweep_tail_begin(sc, tail, " for one pair");
-    if (cap < 0) return cap;
-    s.der = der;
-    if (r.blur_w) if (int rc = h2d_bounced(c, blur_w, r.blur_w, (size_t)(2 * r.blur_r + 1) * sizeof(double))) return rc;
-
-    // the steps: a half width past the longer image side adds only zeros, so the chain ends there
-    const int h_stop = std::max(c->Ni, c->Nj);
-    std::vector<std::vector<int>> at_h;                 // list entries that map to each half width
-    for (int b = 0; b < r.n_boxes; ++b) {
-        const int h = std::min(r.boxes[b] / 2, h_stop);
-        if ((int)at_h.size() <= h) at_h.resize((size_t)h + 1);
-        at_h[h].push_back(b);
-    }
-    const int h_max = (int)at_h.size() - 1;
-    BoxArgs a{};
-    a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj;
-    a.cend = r.quirks ? std::min(c->Ni, c->Nj) : c->Nj;      // OF.py:108 clamps the column window with N_i
-    a.quirks = r.quirks ? 1 : 0;
-    a.scale = r.delta_x / r.delta_t;
-
-    for (int k0 = 0; k0 < P; k0 += cap) {
-        const int np = std::min(cap, P - k0);
-        const dim3 g = grid2d(c->Ni, c->Nj, np);
-        if (int rc = pair_chunk_frames(c, r, k0, np, frames, blur_w, r.blur_r, blur_tmp, &a.movie)) return rc;
-        c->cur_units = np;
-        { Prof prof(c, VOF_K_RHS, 0);
-          k_bf_derived<<<g, blk2d, 0, c->stream>>>(a, der);
-          if (r.remodel) k_bs_init<true><<<g, blk2d, 0, c->stream>>>(s);
-          else k_bs_init<false><<<g, blk2d, 0, c->stream>>>(s); }
-        for (int h = 0; h <= h_max; ++h) {
-            s.h = h;
-            a.h = h;
-            bool stepped = h == 0;
-            if (h >= 1) {
-                Prof prof(c, VOF_K_RHS, 0);
-                if (r.remodel) k_bs_grow<true><<<g, blk2d, 0, c->stream>>>(s);
-                else k_bs_grow<false><<<g, blk2d, 0, c->stream>>>(s);
-                if (at_h[h].empty()) {
-                    if (r.remodel) k_bs_window<true, true, false><<<g, blk2d, 0, c->stream>>>(s, a);
-                    else k_bs_window<false, true, false><<<g, blk2d, 0, c->stream>>>(s, a);
-                }
-            }
-            for (int b : at_h[h]) {
-                a.n_box = (double)r.boxes[b] * (double)r.boxes[b];
-                const SweepDst d = sweep_dst(r, chunk_out, fs, b, k0);
-                a.vx = d.keep_v ? d.f[0] : nullptr; a.vy = d.keep_v ? d.f[1] : nullptr; a.speed = d.f[2];
-                a.gamma = d.keep_g ? d.f[3] : nullptr;
-                {
-                    Prof prof(c, VOF_K_RHS, 0);
-                    if (!stepped) {              // the first entry of this half width takes the step with it
-                        if (r.remodel) k_bs_window<true, true, true><<<g, blk2d, 0, c->stream>>>(s, a);
-                        else k_bs_window<false, true, true><<<g, blk2d, 0, c->stream>>>(s, a);
-                        stepped = true;
-                    } else {
-                        if (r.remodel) k_bs_window<true, false, true><<<g, blk2d, 0, c->stream>>>(s, a);
-                        else k_bs_window<false, false, true><<<g, blk2d, 0, c->stream>>>(s, a);
-                    }
-                }
-                sweep_tail_speed(c, tail, b, k0, np, a.speed);
-                if (int rc = sweep_tail_moments(c, tail, b, k0, np, a.speed, a.gamma)) return rc;
-                if (int rc = sweep_copy_out(c, r, d, fs, np)) return rc;
-            }
-        }
-    }
-    if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
-    for (int b = 0; b < r.n_boxes; ++b) r.stats[b].box_size = r.boxes[b];
-    return 0;
-}
-
-#define VOF_BOXSIZE_ARGS                                                                                                              \
-    vof_ctx *c, const double *movie, int n_frames, const int32_t *box_sizes, int n_boxes, double delta_x, double delta_t,             \
-        int include_remodelling, int reference_quirks, const double *blur_weights, int blur_radius, const double *histogram_edges,    \
-        int histogram_bins, int64_t *histograms, const int32_t *probe_ij, int n_probes, double *probe_speeds,                         \
-        vof_boxsize_stats *stats, double *v_x, double *v_y, double *speed, double *net_remodelling
-#define VOF_BOXSIZE_REQ(host)                                                                                                         \
-    SweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges, histogram_bins, histograms,  \
-              probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, host},                                            \
-             box_sizes, n_boxes, blur_weights, blur_radius, stats}
-
-int vof_vary_boxsize_dev(VOF_BOXSIZE_ARGS) { return vary_boxsize_impl(c, VOF_BOXSIZE_REQ(false)); }
-int vof_vary_boxsize_host(VOF_BOXSIZE_ARGS) { return vary_boxsize_impl(c, VOF_BOXSIZE_REQ(true)); }
-
-// ---- blur sweep of the box flow (vary_blursize; vof_blursweep.hpp) -------------------------------------------------
-struct BlurSweepReq : SweepBase {
-    const double* taps; const int32_t* radii; int n_sigmas;     // the tap vectors (2 radii[s] + 1 each), concatenated
-    int box_size;
-    int abins; int64_t* ahist; double* awhist;                  // flow direction: counts and speed-weighted sums
-    const double* iedges; int ibins; int64_t* ihist;            // intensity of the blurred stack
-    vof_blursize_stats* stats;
-};
-
-// np.linspace(lo, hi, bins + 1) for hi - lo exactly representable: i * step + lo, the last one the stop itself
-static std::vector<double> linspace_edges(double lo, double hi, int bins) {
-    std::vector<double> e((size_t)bins + 1);
-    const volatile double step = (hi - lo) / (double)bins;
-    for (int i = 0; i < bins; ++i) { const volatile double t = (double)i * step; e[i] = t + lo; }
-    e[bins] = hi;
-    return e;
-}
-
-// sum P per-pair partial histograms of `bins` bins, part[pair][bin], in pair order
-static void sum_pair_histograms(const double* part, int P, int bins, double* out) {
-    for (int b = 0; b < bins; ++b) {
-        double w = 0.0;
-        for (int k = 0; k < P; ++k) w += part[(size_t)k * bins + b];
-        out[b] = w;
-    }
-}
-
-// The flow-direction histogram per list entry of a sweep - the sigmas of the blur sweep, the two channels of the comparison -:
-// counts and speed-weighted sums over `bins` bins of [-1, 1] (0: none).  Its integer counters belong to the span behind the
-// tail's d_bad (SweepTail), so the sweep calls regions() before sweep_tail_regions and counters() after it.
-struct DirectionHist {
-    int bins, n, P, blk; size_t fs;       // blk: blocks per pair, by the plane size only
-    double *d_edges, *d_wsum, *d_part;    // the sums [entry][pair][bin]; the partials of one chunk
-    unsigned long long* d_hist;
-    void regions(Scratch& sc, int bins_, int n_, int P_) {
-        bins = bins_; n = n_; P = P_; fs = frame_stride(sc.c);
-        blk = (int)std::min<size_t>(BZ_ANGLE_MAX_BLOCKS, std::max<size_t>(1, fs / (64 * BZ_ANGLE_PER_LANE)));
-        sc.once(&d_edges, bins ? (size_t)bins + 1 : 0);
-        sc.once(&d_wsum, (size_t)n * P * bins);
-        sc.per_unit(&d_part, (size_t)blk * bins);
-    }
-    void counters(Scratch& sc) { sc.once(&d_hist, (size_t)n * bins); }
-    int upload_edges(vof_ctx* c) const {                           // once the arena is planned
-        if (!bins) return 0;
-        const std::vector<double> e = linspace_edges(-1.0, 1.0, bins);
-        return h2d_bounced(c, d_edges, e.data(), e.size() * 8);
-    }
-    // pairs k0 .. k0 + np of entry e, enqueued behind the kernels that wrote the fields
-    void enqueue(vof_ctx* c, int e, int k0, int np, const double* vx, const double* vy, const double* speed) const {
-        if (!bins) return;
-        Prof prof(c, VOF_K_REDUCE, 0);
-        k_bz_angles<<<dim3(blk, np), 64, (size_t)bins * 64 * sizeof(double), c->stream>>>(vx, vy, speed, fs, d_edges, bins,
-                                                                                          d_hist + (size_t)e * bins, d_part);
-        const int nt = np * bins;
-        k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_part, blk, bins, np, d_wsum + ((size_t)e * P + k0) * bins);
-    }
-    // behind sweep_tail_finish: the counts from the tail's host copy, the weighted sums summed over the pairs in pair order
-    int finish(vof_ctx* c, const SweepTail& t, int64_t* hist, double* whist) const {
-        std::vector<double> wsum((size_t)n * P * bins);
-        if (bins) if (int rc = d2h_bounced(c, wsum.data(), d_wsum, wsum.size() * 8)) return rc;
-        for (size_t i = 0; i < (size_t)n * bins; ++i) hist[i] = (int64_t)t.host(d_hist)[i];
-        for (int e = 0; e < n; ++e) sum_pair_histograms(wsum.data() + (size_t)e * P * bins, P, bins, whist + (size_t)e * bins);
-        return 0;
-    }
-};
-
-static int vary_blursize_impl(vof_ctx* c, const BlurSweepReq& r) {
-    if (!c) return -1;
-    if (int rc = sweep_check(c, r, r.stats)) return rc;
-    if (!r.taps || !r.radii || r.n_sigmas < 1) { c->err = "the list of blur sizes is empty"; return -1; }
-    for (int s = 0; s < r.n_sigmas; ++s)
-        if (r.radii[s] < 0 || r.radii[s] > 4096) { c->err = "bad blur radius"; return -1; }
-    if (r.box_size < 1) { c->err = "box_size must be >= 1"; return -1; }
-    if (r.iedges && (r.ibins < 1 || !r.ihist)) { c->err = "intensity_edges needs intensity_bins >= 1 and intensity_histograms"; return -1; }
-    if (r.iedges && !(r.iedges[r.ibins] > r.iedges[0])) { c->err = "intensity_edges must increase"; return -1; }
-    if (r.abins < 0 || r.abins > BZ_MAX_ANGLE_BINS) { c->err = "angle_bins must be 0 .. " + std::to_string(BZ_MAX_ANGLE_BINS); return -1; }
-    if (r.abins && (!r.ahist || !r.awhist)) { c->err = "angle_bins needs angle_histograms and weighted_angle_histograms"; return -1; }
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
-    const int T = r.n_frames, P = T - 1, n = r.n_sigmas;
-    std::vector<size_t> tap_at(n);
-    size_t n_taps = 0;
-    for (int s = 0; s < n; ++s) { tap_at[s] = n_taps; n_taps += 2 * (size_t)r.radii[s] + 1; }
-    const size_t n_ihist = r.iedges ? (size_t)n * r.ibins : 0;
-    // the arena: the blurred stack, the movie (_host) and four chunk outputs per pair in flight; what the sweep's own kernels
-    // read and write: taps, intensity edges, the direction histogram's; the tail's; the sweep's counters
-    Scratch sc(c);
-    double *blurred, *up = nullptr, *chunk_out[4], *blur_tmp, *bf_planes = nullptr, *d_taps, *d_iedges;
-    unsigned long long *d_ihist, *d_ibad;
-    DirectionHist dir;
-    sc.once(&blurred, (size_t)T * fs);
-    if (r.host) sc.once(&up, (size_t)T * fs);
-    for (double*& q : chunk_out) sc.per_unit(&q, fs);
-    blur_regions(sc, T, &blur_tmp);
-    box_flow_regions(sc, r.box_size, &bf_planes);
-    sc.once(&d_taps, n_taps);
-    sc.once(&d_iedges, r.iedges ? (size_t)r.ibins + 1 : 0);
-    dir.regions(sc, r.abins, n, P);
-    SweepTail tail;
-    sweep_tail_regions(sc, tail, r, "blur sweep", n);
-    dir.counters(sc);
-    sc.once(&d_ihist, n_ihist);
-    sc.once(&d_ibad, 1);
-    const int cap = sweep_tail_begin(sc, tail, "");
-    if (cap < 0) return cap;
-    if (r.host) if (int rc = h2d_bounced(c, up, r.movie, (size_t)T * fb)) return rc;     // the movie goes up once
-    const double* movie = r.host ? up : r.movie;
-    if (int rc = h2d_bounced(c, d_taps, r.taps, n_taps * 8)) return rc;
-    if (r.iedges) if (int rc = h2d_bounced(c, d_iedges, r.iedges, (size_t)(r.ibins + 1) * 8)) return rc;
-    if (int rc = dir.upload_edges(c)) return rc;
-
-    for (int s = 0; s < n; ++s) {
-        if (int rc = blur_frames(c, movie, blurred, T, r.radii[s], blur_tmp, d_taps + tap_at[s])) return rc;
-        if (r.iedges) {
-            const size_t m = (size_t)T * fs;
-            const int nb = (int)std::min<size_t>(1024, (m + 4 * 256 - 1) / (4 * 256));
-            Prof prof(c, VOF_K_REDUCE, 0);
-            k_bs_counts<<<nb, 256, 0, c->stream>>>(blurred, m, d_iedges, r.ibins, d_ihist + (size_t)s * r.ibins, d_ibad);
-        }
-        for (int k0 = 0; k0 < P; k0 += cap) {
-            const int np = std::min(cap, P - k0);
-            const SweepDst d = sweep_dst(r, chunk_out, fs, s, k0);
-            // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
-            if (int rc = box_flow_pairs(c, bf_planes, blurred + (size_t)k0 * fs, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d.f[0], d.f[1],
-                                        d.f[2], d.keep_g ? d.f[3] : nullptr)) return rc;
-            sweep_tail_speed(c, tail, s, k0, np, d.f[2]);
-            dir.enqueue(c, s, k0, np, d.f[0], d.f[1], d.f[2]);
-            if (int rc = sweep_tail_moments(c, tail, s, k0, np, d.f[2], d.f[3])) return rc;
-            if (int rc = sweep_copy_out(c, r, d, fs, np)) return rc;
-        }
-    }
-    if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
-    if (int rc = dir.finish(c, tail, r.ahist, r.awhist)) return rc;
-    for (size_t t = 0; t < n_ihist; ++t) r.ihist[t] = (int64_t)tail.host(d_ihist)[t];
-    for (int s = 0; s < n; ++s) r.stats[s].sigma_index = s;
-    return 0;
-}
-
-#define VOF_BLURSIZE_ARGS                                                                                                             \
-    vof_ctx *c, const double *movie, int n_frames, const double *blur_weights, const int32_t *blur_radii, int n_sigmas, int box_size, \
-        double delta_x, double delta_t, int include_remodelling, int reference_quirks, const double *histogram_edges,                 \
-        int histogram_bins, int64_t *histograms, int angle_bins, int64_t *angle_histograms, double *weighted_angle_histograms,        \
-        const double *intensity_edges, int intensity_bins, int64_t *intensity_histograms, const int32_t *probe_ij, int n_probes,      \
-        double *probe_speeds, vof_blursize_stats *stats, double *v_x, double *v_y, double *speed, double *net_remodelling
-#define VOF_BLURSIZE_REQ(host)                                                                                                        \
-    BlurSweepReq{{movie, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges, histogram_bins,          \
-                  histograms, probe_ij, n_probes, probe_speeds, {v_x, v_y, speed, net_remodelling}, host},                            \
-                 blur_weights, blur_radii, n_sigmas, box_size, angle_bins, angle_histograms, weighted_angle_histograms,               \
-                 intensity_edges, intensity_bins, intensity_histograms, stats}
-
-int vof_vary_blursize_dev(VOF_BLURSIZE_ARGS) { return vary_blursize_impl(c, VOF_BLURSIZE_REQ(false)); }
-int vof_vary_blursize_host(VOF_BLURSIZE_ARGS) { return vary_blursize_impl(c, VOF_BLURSIZE_REQ(true)); }
-
-// ---- two channels of one movie: their box flows and the joint statistics (compare_channel_flows; vof_compare.hpp) --------
-struct CompareReq : SweepBase {           // movie, outs: channel a; the tail's two entries are the channels
-    const double* movie_b;
-    const double* taps[2]; int radius[2];
-    int box_size;
-    int abins; int64_t* ahist; double* awhist;                  // per-channel flow direction
-    int tbins; int64_t* thist; double* twhist;                  // angle between the two flows
-    const double* jedges[2]; int jbins[2]; const double* jmin; int64_t* jhist;     // the two speeds
-    int64_t* jcounts;
-    double* outs_b[4];
-    vof_compare_stats* stats;
-};
-
-static int compare_flows_impl(vof_ctx* c, const CompareReq& r) {
-    if (!c) return -1;
-    if (int rc = sweep_check(c, r, r.stats)) return rc;
-    if (!r.movie_b) { c->err = "movie_b is NULL"; return -1; }
-    for (int f = 0; f < 4; ++f)
-        if ((r.outs[f] != nullptr) != (r.outs_b[f] != nullptr)) { c->err = "the field stacks of both channels must be given together"; return -1; }
-    for (int ch = 0; ch < 2; ++ch)
-        if (r.taps[ch] && (r.radius[ch] < 0 || r.radius[ch] > 4096)) { c->err = "bad blur_radius"; return -1; }
-    if (r.box_size < 1) { c->err = "box_size must be >= 1"; return -1; }
-    if (r.abins < 0 || r.abins > CP_MAX_THETA_BINS) { c->err = "angle_bins must be 0 .. " + std::to_string(CP_MAX_THETA_BINS); return -1; }
-    if (r.abins && (!r.ahist || !r.awhist)) { c->err = "angle_bins needs angle_histograms and weighted_angle_histograms"; return -1; }
-    if (r.tbins < 1 || r.tbins > CP_MAX_THETA_BINS) { c->err = "relative_angle_bins must be 1 .. " + std::to_string(CP_MAX_THETA_BINS); return -1; }
-    if (!r.thist || !r.twhist || !r.jcounts) { c->err = "relative_angle_histogram, weighted_relative_angle_histogram and joint_counts are required"; return -1; }
-    const bool joint = r.jedges[0] || r.jedges[1];
-    if (joint) {
-        if (!r.jedges[0] || !r.jedges[1] || !r.jhist) { c->err = "joint_speed_edges_a, joint_speed_edges_b and joint_speed_histogram go together"; return -1; }
-        for (int ch = 0; ch < 2; ++ch) {
-            if (r.jbins[ch] < 1 || r.jbins[ch] > CP_MAX_SPEED_BINS) { c->err = "joint_speed_bins must be 1 .. " + std::to_string(CP_MAX_SPEED_BINS) + " per axis"; return -1; }
-            if (!(r.jedges[ch][r.jbins[ch]] > r.jedges[ch][0])) { c->err = "joint_speed_edges must increase"; return -1; }
-        }
-    }
-    const size_t fs = frame_stride(c);
-    const int P = r.n_frames - 1;
-    const int ba = joint ? r.jbins[0] : 0, bb = joint ? r.jbins[1] : 0;
-    const size_t n_taps[2] = {r.taps[0] ? 2 * (size_t)r.radius[0] + 1 : 0, r.taps[1] ? 2 * (size_t)r.radius[1] + 1 : 0};
-    const size_t n_twsum = (size_t)P * r.tbins, n_jhist = (size_t)ba * bb;
-    const int cp_blk = cp_blocks(fs);
-    // the arena: cap + 1 frames of the channel in progress and four chunk outputs per channel and pair in flight; what the
-    // comparison's own kernels read and write; the tail's; the comparison's counters
-    Scratch sc(c);
-    double *frames, *chunk_out[2][4], *blur_tmp = nullptr, *bf_planes = nullptr, *d_taps[2], *d_tedges, *d_jedges[2], *d_twsum, *d_tpart;
-    unsigned long long *d_thist, *d_jhist, *d_jc;
-    DirectionHist dir;
-    sc.per_unit_plus_one(&frames, fs);
-    for (auto& ch : chunk_out) for (double*& q : ch) sc.per_unit(&q, fs);
-    if (r.taps[0] || r.taps[1]) blur_regions(sc, sweep_want(c, r) + 1, &blur_tmp);
-    box_flow_regions(sc, r.box_size, &bf_planes);
-    for (int ch = 0; ch < 2; ++ch) { sc.once(&d_taps[ch], n_taps[ch]); sc.once(&d_jedges[ch], joint ? (size_t)r.jbins[ch] + 1 : 0); }
-    dir.regions(sc, r.abins, 2, P);
-    sc.once(&d_tedges, (size_t)r.tbins + 1);
-    sc.once(&d_twsum, n_twsum);
-    sc.per_unit(&d_tpart, (size_t)cp_blk * r.tbins);
-    SweepTail tail;
-    sweep_tail_regions(sc, tail, r, "channel comparison", 2);
-    dir.counters(sc);
-    sc.once(&d_thist, (size_t)r.tbins);
-    sc.once(&d_jhist, n_jhist);
-    sc.once(&d_jc, 2);
-    const int cap = sweep_tail_begin(sc, tail, " for one pair");
-    if (cap < 0) return cap;
-    for (int ch = 0; ch < 2; ++ch) {
-        if (r.taps[ch]) if (int rc = h2d_bounced(c, d_taps[ch], r.taps[ch], n_taps[ch] * 8)) return rc;
-        if (joint) if (int rc = h2d_bounced(c, d_jedges[ch], r.jedges[ch], ((size_t)r.jbins[ch] + 1) * 8)) return rc;
-    }
-    if (int rc = dir.upload_edges(c)) return rc;
-    {
-        const std::vector<double> e = linspace_edges(0.0, 1.0, r.tbins);
-        if (int rc = h2d_bounced(c, d_tedges, e.data(), e.size() * 8)) return rc;
-    }
-    SweepBase chan[2] = {r, r};            // a channel as a sweep of one entry: where its fields go
-    chan[1].movie = r.movie_b;
-    for (int f = 0; f < 4; ++f) chan[1].outs[f] = r.outs_b[f];
-
-    for (int k0 = 0; k0 < P; k0 += cap) {
-        const int np = std::min(cap, P - k0);
-        SweepDst d[2];
-        for (int ch = 0; ch < 2; ++ch) {
-            const double* src;
-            if (int rc = pair_chunk_frames(c, chan[ch], k0, np, frames, r.taps[ch] ? d_taps[ch] : nullptr, r.radius[ch], blur_tmp, &src)) return rc;
-            d[ch] = sweep_dst(chan[ch], chunk_out[ch], fs, 0, k0);
-            // exactly vof_box_flow_dev: the same kernels, the same choice between the fused and the general path
-            if (int rc = box_flow_pairs(c, bf_planes, src, np, r.box_size, r.delta_x, r.delta_t, r.remodel, r.quirks, d[ch].f[0], d[ch].f[1],
-                                        d[ch].f[2], d[ch].keep_g ? d[ch].f[3] : nullptr)) return rc;
-            sweep_tail_speed(c, tail, ch, k0, np, d[ch].f[2]);
-            dir.enqueue(c, ch, k0, np, d[ch].f[0], d[ch].f[1], d[ch].f[2]);
-            if (int rc = sweep_tail_moments(c, tail, ch, k0, np, d[ch].f[2], d[ch].f[3])) return rc;
-        }
-        {
-            CompareArgs a{};
-            a.vxa = d[0].f[0]; a.vya = d[0].f[1]; a.spa = d[0].f[2];
-            a.vxb = d[1].f[0]; a.vyb = d[1].f[1]; a.spb = d[1].f[2];
-            a.fs = fs;
-            a.tedges = d_tedges; a.tbins = r.tbins;
-            a.ea = d_jedges[0]; a.eb = d_jedges[1]; a.ba = ba; a.bb = bb;
-            a.has_min = r.jmin ? 1 : 0; a.min_b = r.jmin ? *r.jmin : 0.0;
-            a.clip = r.quirks ? 0 : 1;
-            a.thist = d_thist; a.jhist = d_jhist; a.counters = d_jc;
-            a.partials = d_tpart;
-            c->cur_units = np;
-            Prof prof(c, VOF_K_REDUCE, 0, 48.0 * fs);
-            k_cp_joint<<<dim3(cp_blk, np), 64, cp_lds(r.tbins, ba, bb), c->stream>>>(a);
-            const int nt = np * r.tbins;
-            k_bz_angle_sum<<<(nt + 255) / 256, 256, 0, c->stream>>>(d_tpart, cp_blk, r.tbins, np, d_twsum + (size_t)k0 * r.tbins);
-        }
-        if (hipGetLastError() != hipSuccess) { c->err = "channel comparison: launch failed"; return -2; }
-        for (int ch = 0; ch < 2; ++ch)
-            if (int rc = sweep_copy_out(c, chan[ch], d[ch], fs, np)) return rc;
-    }
-    if (int rc = sweep_tail_finish(c, tail, r.stats)) return rc;
-    if (int rc = dir.finish(c, tail, r.ahist, r.awhist)) return rc;
-    std::vector<double> twsum(n_twsum);
-    if (int rc = d2h_bounced(c, twsum.data(), d_twsum, n_twsum * 8)) return rc;
-    for (int b = 0; b < r.tbins; ++b) r.thist[b] = (int64_t)tail.host(d_thist)[b];
-    for (size_t t = 0; t < n_jhist; ++t) r.jhist[t] = (int64_t)tail.host(d_jhist)[t];
-    r.jcounts[0] = (int64_t)tail.host(d_jc)[0]; r.jcounts[1] = (int64_t)tail.host(d_jc)[1];
-    sum_pair_histograms(twsum.data(), P, r.tbins, r.twhist);
-    for (int ch = 0; ch < 2; ++ch) r.stats[ch].channel = ch;
-    return 0;
-}
-
-#define VOF_COMPARE_ARGS                                                                                                              \
-    vof_ctx *c, const double *movie_a, const double *movie_b, int n_frames, const double *blur_weights_a, int blur_radius_a,          \
-        const double *blur_weights_b, int blur_radius_b, int box_size, double delta_x, double delta_t, int include_remodelling,       \
-        int reference_quirks, const double *histogram_edges, int histogram_bins, int64_t *histograms, int angle_bins,                 \
-        int64_t *angle_histograms, double *weighted_angle_histograms, int relative_angle_bins, int64_t *relative_angle_histogram,     \
-        double *weighted_relative_angle_histogram, const double *joint_speed_edges_a, int joint_speed_bins_a,                         \
-        const double *joint_speed_edges_b, int joint_speed_bins_b, const double *joint_speed_min_b, int64_t *joint_speed_histogram,   \
-        int64_t *joint_counts, vof_compare_stats *stats, double *v_x_a, double *v_y_a, double *speed_a, double *net_remodelling_a,    \
-        double *v_x_b, double *v_y_b, double *speed_b, double *net_remodelling_b
-#define VOF_COMPARE_REQ(host)                                                                                                         \
-    CompareReq{{movie_a, n_frames, delta_x, delta_t, include_remodelling, reference_quirks, histogram_edges, histogram_bins,          \
-                histograms, nullptr, 0, nullptr, {v_x_a, v_y_a, speed_a, net_remodelling_a}, host},                                   \
-               movie_b, {blur_weights_a, blur_weights_b}, {blur_radius_a, blur_radius_b}, box_size, angle_bins, angle_histograms,     \
-               weighted_angle_histograms, relative_angle_bins, relative_angle_histogram, weighted_relative_angle_histogram,           \
-               {joint_speed_edges_a, joint_speed_edges_b}, {joint_speed_bins_a, joint_speed_bins_b}, joint_speed_min_b,               \
-               joint_speed_histogram, joint_counts, {v_x_b, v_y_b, speed_b, net_remodelling_b}, stats}
-
-int vof_compare_flows_dev(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(false)); }
-int vof_compare_flows_host(VOF_COMPARE_ARGS) { return compare_flows_impl(c, VOF_COMPARE_REQ(true)); }
-
-// ---- preprocessing: adaptive threshold and CLAHE (apply_adaptive_threshold, apply_clahe; vof_preprocess.hpp) ---------------
-static int adaptive_threshold_impl(vof_ctx* c, const double* movie, int n_frames, int window, double threshold, int flight, uint8_t* mask,
-                                   double* range, bool host) {
-    if (int rc = FrameChunks::check(c, {movie, mask}, n_frames, "n_frames")) return rc;
-    if (window < 3 || window % 2 == 0 || window > PP_MAX_WINDOW) { c->err = "window_size must be odd and 3 .. " + std::to_string(PP_MAX_WINDOW); return -1; }
-    if (c->Nj > PP_MAX_ROW) { c->err = "adaptive threshold: n_j must be <= " + std::to_string(PP_MAX_ROW); return -1; }
-    if (c->Ni > 65535 * PP_COL_ROWS) { c->err = "adaptive threshold: n_i too large"; return -1; }
-    if (std::isnan(threshold)) { c->err = "threshold is NaN"; return -1; }
-    const size_t fs = frame_stride(c);
-    FrameChunks fc(c, "adaptive threshold", n_frames, flight, host);
-    unsigned int* H;                                                                     // row sums
-    fc.sc.per_unit(&H, fs);
-    fc.input(movie);
-    fc.output(mask, fs);
-    if (int rc = fc.plan()) return rc;
-    if (int rc = fc.range(0, 0.0, INFINITY, "negative values", "", range)) return rc;
-    const double m = fc.rg[0];
-    if (!(m > 0)) { c->err = "adaptive threshold: the movie's maximum is not positive"; return 1; }
-    const int r = window / 2;
-    const int idelta = (int)std::max(-1024.0, std::min(1024.0, std::ceil(threshold)));   // u - mean lies in [-255, 255]
-    return fc.run([&](int, int nf, const double* const* in, void* const* out) {
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_ROWSUM, 12.0 * fs);
-            k_pp_rowsum<<<dim3(c->Ni, nf), PP_BLOCK, (size_t)c->Nj * sizeof(unsigned int), c->stream>>>(in[0], c->Ni, c->Nj, m, r, H);
-        }
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_THRESHOLD, 13.0 * fs);
-            k_pp_threshold<<<dim3((c->Nj + PP_BLOCK - 1) / PP_BLOCK, (c->Ni + PP_COL_ROWS - 1) / PP_COL_ROWS, nf), PP_BLOCK, 0, c->stream>>>(
-                in[0], H, c->Ni, c->Nj, m, r, idelta, (uint8_t*)out[0]);
-        }
-        return 0;
-    });
-}
-
-int vof_adaptive_threshold_dev(vof_ctx* c, const double* movie, int n_frames, int window_size, double threshold, int frames_in_flight,
-                               uint8_t* mask, double* range) {
-    return adaptive_threshold_impl(c, movie, n_frames, window_size, threshold, frames_in_flight, mask, range, false);
-}
-int vof_adaptive_threshold_host(vof_ctx* c, const double* movie, int n_frames, int window_size, double threshold, int frames_in_flight,
-                                uint8_t* mask, double* range) {
-    return adaptive_threshold_impl(c, movie, n_frames, window_size, threshold, frames_in_flight, mask, range, true);
-}
-
-static int clahe_impl(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int flight, double* out,
-                      double* range, bool host) {
-    if (int rc = FrameChunks::check(c, {movie, out}, n_frames, "n_frames")) return rc;
-    if (tiles_x < 1 || tiles_x > c->Nj - 1 || tiles_y < 1 || tiles_y > c->Ni - 1) {
-        c->err = "CLAHE: the tile grid must be 1 .. n_j - 1 by 1 .. n_i - 1"; return -1;
-    }
-    if (std::isnan(clip_limit)) { c->err = "clip_limit is NaN"; return -1; }
-    ClaheGeom g{};
-    g.ni = c->Ni; g.nj = c->Nj; g.tx = tiles_x; g.ty = tiles_y;
-    const bool pad = g.nj % g.tx != 0 || g.ni % g.ty != 0;          // one axis not dividing pads both, a dividing one by a full grid
-    g.pj = pad ? g.nj + (g.tx - g.nj % g.tx) : g.nj;
-    g.pi = pad ? g.ni + (g.ty - g.ni % g.ty) : g.ni;
-    g.tw = g.pj / g.tx; g.th = g.pi / g.ty;
-    const long long area = (long long)g.tw * g.th;
-    if (g.pi > 65535 || area > 0x7FFFFFFFLL) { c->err = "CLAHE: image too large"; return -1; }
-    if (clip_limit > 0) {
-        const double cl = clip_limit * (double)area / (double)PP_BINS;
-        g.clip = std::max(cl >= 2147483647.0 ? 2147483647 : (int)cl, 1);
-    }
-    g.lut_scale = (float)(PP_BINS - 1) / (float)area;
-    g.inv_tw = 1.0f / (float)g.tw; g.inv_th = 1.0f / (float)g.th;
-    const size_t fs = frame_stride(c);
-    const size_t ntiles = (size_t)g.tx * g.ty, hist_bytes = ntiles * PP_BINS * sizeof(unsigned int), lut_bytes = ntiles * PP_BINS * sizeof(uint16_t);
-    FrameChunks fc(c, "CLAHE", n_frames, flight, host);
-    unsigned int* hist;
-    uint16_t* lut;
-    fc.sc.per_unit(&hist, ntiles * PP_BINS);
-    fc.sc.per_unit(&lut, ntiles * PP_BINS);
-    fc.input(movie);
-    fc.output(out, fs * sizeof(double));
-    if (int rc = fc.plan()) return rc;
-    if (int rc = fc.range(0, 0.0, std::nextafter(65536.0, 0.0), "values outside [0, 65536)", "", range)) return rc;   // hi: the last double below 65536
-    const double padded = (double)g.pi * g.pj;
-    return fc.run([&](int, int nf, const double* const* in, void* const* dst) -> int {
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_HIST, 8.0 * padded + 2.0 * hist_bytes);   // the zero fill and the counters read back
-            HIPCHK(hipMemsetAsync(hist, 0, (size_t)nf * hist_bytes, c->stream));
-            k_pp_hist<<<dim3((g.pj + PP_BLOCK - 1) / PP_BLOCK, g.pi, nf), PP_BLOCK, 0, c->stream>>>(in[0], g, hist);
-        }
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_LUT, (g.clip > 0 ? 2.0 : 1.0) * hist_bytes + lut_bytes, (double)hist_bytes + lut_bytes);
-            k_pp_lut<<<dim3((unsigned)ntiles, nf), PP_BLOCK, 0, c->stream>>>(hist, g, lut);
-        }
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_BLEND, 24.0 * fs, 16.0 * fs);             // 4 table entries of 2 bytes from the cache
-            k_pp_blend<<<dim3((g.nj + PP_BLOCK - 1) / PP_BLOCK, g.ni, nf), PP_BLOCK, 0, c->stream>>>(in[0], g, lut, (double*)dst[0]);
-        }
-        return 0;
-    });
-}
-
-int vof_clahe_dev(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int frames_in_flight,
-                  double* out, double* range) {
-    return clahe_impl(c, movie, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight, out, range, false);
-}
-int vof_clahe_host(vof_ctx* c, const double* movie, int n_frames, double clip_limit, int tiles_x, int tiles_y, int frames_in_flight,
-                   double* out, double* range) {
-    return clahe_impl(c, movie, n_frames, clip_limit, tiles_x, tiles_y, frames_in_flight, out, range, true);
-}
-
-// ---- INTER_AREA downsampling (downsample_movie; vof_resize.hpp) --------------------------------------------------------------
-// One axis of cv2.resize's INTER_AREA: the two roundings of the scale, and computeResizeAreaTab in C++ double exactly as OpenCV
-// writes it; the entries of an output index are consecutive source indices, so (first index, count, weights) holds them.
-struct ResizeAxis {
-    double scale = 1.0;
-    int iscale = 1, kmax = 0;
-    std::vector<int> start, count;
-    std::vector<float> w;                  // [d * kmax + k]
-};
-
-static void resize_axis_scale(int ssize, int dsize, ResizeAxis* t) {
-    const double inv = (double)dsize / (double)ssize;
-    t->scale = 1.0 / inv;
-    t->iscale = (int)t->scale;
-}
-
-static bool resize_axis_table(int ssize, int dsize, ResizeAxis* t) {
-#pragma clang fp contract(off)
-    const double scale = t->scale;
-    std::vector<std::vector<float>> ws((size_t)dsize);
-    t->start.assign((size_t)dsize, 0);
-    t->count.assign((size_t)dsize, 0);
-    t->kmax = 0;
-    int prev_start = 0, prev_end = 0;
-    for (int d = 0; d < dsize; ++d) {
-        const double f1 = d * scale;
-        const double f2 = f1 + scale;
-        const double cw = std::min(scale, ssize - f1);
-        int s1 = (int)std::ceil(f1);
-        const int s2 = std::min((int)std::floor(f2), ssize - 1);
-        s1 = std::min(s1, s2);
-        std::vector<float>& w = ws[(size_t)d];
-        int first = s1;
-        if (s1 - f1 > 1e-3) { first = s1 - 1; w.push_back((float)((s1 - f1) / cw)); }
-        for (int s = s1; s < s2; ++s) w.push_back((float)(1.0 / cw));
-        if (f2 - s2 > 1e-3) {
-            if (w.empty()) first = s2;
-            w.push_back((float)(std::min(std::min(f2 - s2, 1.0), cw) / cw));
-        }
-        const int n = (int)w.size(), end = first + n;
-        // what the kernel's staging relies on: a non-empty run inside the row, runs that move right with d
-        if (n < 1 || first < 0 || end > ssize || first < prev_start || end < prev_end) return false;
-        prev_start = first; prev_end = end;
-        t->start[(size_t)d] = first; t->count[(size_t)d] = n;
-        t->kmax = std::max(t->kmax, n);
-    }
-    t->w.assign((size_t)dsize * t->kmax, 0.0f);
-    for (int d = 0; d < dsize; ++d) std::copy(ws[(size_t)d].begin(), ws[(size_t)d].end(), t->w.begin() + (size_t)d * t->kmax);
-    return true;
-}
-
-static int resize_area_impl(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int flight, double* out,
-                            bool host) {
-    if (int rc = FrameChunks::check(c, {movie, out}, n_frames, "n_frames")) return rc;
-    if (arithmetic != VOF_RESIZE_U8 && arithmetic != VOF_RESIZE_F64) { c->err = "resize: arithmetic must be VOF_RESIZE_U8 or VOF_RESIZE_F64"; return -1; }
-    if (out_i < 1 || out_i > c->Ni || out_j < 1 || out_j > c->Nj) {
-        c->err = "resize: 1 <= out_i <= n_i and 1 <= out_j <= n_j are required (downsampling only)"; return -1;
-    }
-    if (out_i > 65535) { c->err = "resize: out_i must be <= 65535"; return -1; }
-    const bool u8 = arithmetic == VOF_RESIZE_U8;
-    ResizeAxis ty, tx;
-    resize_axis_scale(c->Ni, out_i, &ty);
-    resize_axis_scale(c->Nj, out_j, &tx);
-    const bool fast = std::fabs(tx.scale - tx.iscale) < DBL_EPSILON && std::fabs(ty.scale - ty.iscale) < DBL_EPSILON;
-    std::vector<uint32_t> tab;                                          // start_y, count_y, start_x, count_x, w_y, w_x
-    if (fast) {
-        if ((long long)ty.iscale * out_i != c->Ni || (long long)tx.iscale * out_j != c->Nj) { c->err = "internal: resize scales"; return -1; }
-        if ((long long)ty.iscale * tx.iscale > 0x7FFFFFFFLL / 255) { c->err = "resize: more than 2^23 source pixels per output pixel"; return -1; }
-    } else {
-        if (!resize_axis_table(c->Ni, out_i, &ty) || !resize_axis_table(c->Nj, out_j, &tx)) { c->err = "internal: resize table"; return -1; }
-        tab.resize(2 * (size_t)out_i + 2 * (size_t)out_j + ty.w.size() + tx.w.size());
-        uint32_t* q = tab.data();
-        for (const ResizeAxis* t : {&ty, &tx}) {
-            memcpy(q, t->start.data(), t->start.size() * 4); q += t->start.size();
-            memcpy(q, t->count.data(), t->count.size() * 4); q += t->count.size();
-        }
-        memcpy(q, ty.w.data(), ty.w.size() * 4); q += ty.w.size();
-        memcpy(q, tx.w.data(), tx.w.size() * 4);
-    }
-    const size_t fs = frame_stride(c), os = (size_t)out_i * out_j;
-    FrameChunks fc(c, "resize", n_frames, flight, host);
-    int* q;                                                             // the axis tables on the device
-    fc.sc.once(&q, tab.size());
-    fc.input(movie);
-    fc.output(out, os * sizeof(double));
-    if (int rc = fc.plan()) return rc;
-    if (u8) if (int rc = fc.range(0, 0.0, 255.0, "values outside 0 .. 255", " (uint8 arithmetic)")) return rc;
-    RsAxis ay{}, ax{};
-    if (!fast) {
-        if (int rc = h2d_bounced(c, q, tab.data(), tab.size() * 4)) return rc;
-        ay.start = q; ay.count = q + out_i; ax.start = q + 2 * (size_t)out_i; ax.count = ax.start + out_j;
-        ay.w = (const float*)(ax.count + out_j); ax.w = ay.w + ty.w.size();
-        ay.kmax = ty.kmax; ax.kmax = tx.kmax;
-    }
-    const float scale_f = 1.0f / (float)(tx.iscale * ty.iscale);
-    const int half_up = tx.iscale == 2 && ty.iscale == 2;
-    return fc.run([&](int, int nf, const double* const* in, void* const* out_dev) {
-        const double* src = in[0];
-        double* dst = (double*)out_dev[0];
-        Prof prof(c, VOF_K_PREPROCESS, PP_ST_RESIZE, 8.0 * fs + 8.0 * os);
-        const dim3 grid((out_j + RS_BLOCK - 1) / RS_BLOCK, out_i, nf);
-        if (fast && u8) k_rs_fast<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, half_up, dst);
-        else if (fast) k_rs_fast<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ty.iscale, tx.iscale, scale_f, 0, dst);
-        else if (u8) k_rs_area<true><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
-        else k_rs_area<false><<<grid, RS_BLOCK, 0, c->stream>>>(src, c->Ni, c->Nj, out_i, out_j, ay, ax, dst);
-        return 0;
-    });
-}
-
-int vof_resize_area_dev(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int frames_in_flight, double* out) {
-    return resize_area_impl(c, movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out, false);
-}
-int vof_resize_area_host(vof_ctx* c, const double* movie, int n_frames, int out_i, int out_j, int arithmetic, int frames_in_flight, double* out) {
-    return resize_area_impl(c, movie, n_frames, out_i, out_j, arithmetic, frames_in_flight, out, true);
-}
-
-// ---- Farnebaeck's dense flow (conduct_opencv_flow; vof_farneback.hpp) ---------------------------------------------------------
-// The float32 planes of one pair in flight, each n_i * n_j floats long whatever the level (a level's planes are compact at
-// the start of their slots): FB_PLANES in all with the Gaussian window; FB_BOX_PLANES with the box window, whose V is five
-// double planes (the slot of ten float32 ones; a pair's planes start at a multiple of 256 bytes, so V is aligned).
-enum FbWindow { FB_GAUSSIAN, FB_BOX };
-struct FbPair {
-    float *tmp_a, *tmp_b, *image, *R[2], *M, *V, *flow[2];
-    explicit FbPair(float* q, size_t fs, FbWindow window) {
-        tmp_a = q; tmp_b = q + fs; image = q + 2 * fs; R[0] = q + 3 * fs; R[1] = q + 8 * fs; M = q + 13 * fs; V = q + 18 * fs;
-        flow[0] = V + (window == FB_BOX ? 10 : 5) * fs; flow[1] = flow[0] + 2 * fs;
-    }
-};
-
-static int farneback_impl(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes,
-                          const int* ksizes, const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig,
-                          FbWindow window, int winsize, const float* window_taps, int iterations, float flow_scale, double velocity_scale,
-                          int flight, double* v_x, double* v_y, double* speed, bool host) {
-    const bool box = window == FB_BOX;                                          // no taps: the window is two running sums
-    if (int rc = FrameChunks::check(c, {first, second, v_x, v_y, speed, level_sizes, ksizes, presmooth_taps, poly_tables, poly_ig,
-                                        box ? (const void*)first : window_taps}, n_pairs, "n_pairs")) return rc;
-    if (c->Ni < 16 || c->Nj < 16) { c->err = "Farneback flow: frames must be at least 16 x 16"; return -1; }
-    if (n_levels < 1 || n_levels > 64) { c->err = "Farneback flow: 1 .. 64 pyramid images"; return -1; }
-    if (poly_n < 1 || poly_n > FB_MAX_POLY_N) { c->err = "Farneback flow: poly_n must be 1 .. " + std::to_string(FB_MAX_POLY_N); return -1; }
-    if (winsize < 1 || winsize > FB_MAX_WINSIZE) { c->err = "Farneback flow: winsize must be 1 .. " + std::to_string(FB_MAX_WINSIZE); return -1; }
-    if (box && winsize < 2) {
-        c->err = "Farneback flow: the box window needs winsize >= 2 (at winsize 1 OpenCV's running sums start with row 0 and column 0 counted once too often)";
-        return -1;
-    }
-    if (iterations < 0) { c->err = "Farneback flow: iterations must be >= 0"; return -1; }
-    if (level_sizes[0] != c->Ni || level_sizes[1] != c->Nj) { c->err = "Farneback flow: level 0 must have the frame's size"; return -1; }
-    size_t n_taps = 0;
-    std::vector<size_t> tap_at((size_t)n_levels);
-    for (int k = 0; k < n_levels; ++k) {
-        const int h = level_sizes[2 * k], w = level_sizes[2 * k + 1];
-        if (h < 1 || w < 1 || h > c->Ni || w > c->Nj || h > 65535) { c->err = "Farneback flow: a level's size must be 1 .. the frame's (65535 rows at most)"; return -1; }
-        if (ksizes[k] < 1 || ksizes[k] % 2 == 0 || ksizes[k] > 65535) { c->err = "Farneback flow: a level's tap count must be odd"; return -1; }
-        tap_at[(size_t)k] = n_taps;
-        n_taps += (size_t)ksizes[k];
-    }
-    const int m = winsize / 2, poly_len = 3 * (2 * poly_n + 1);
-    std::vector<float> tab(n_taps + (size_t)poly_len + (box ? 0 : (size_t)m + 1));   // pre-smoothing taps | g, xg, xxg | Gaussian window taps
-    memcpy(tab.data(), presmooth_taps, n_taps * sizeof(float));
-    memcpy(tab.data() + n_taps, poly_tables, (size_t)poly_len * sizeof(float));
-    if (!box) memcpy(tab.data() + n_taps + poly_len, window_taps, ((size_t)m + 1) * sizeof(float));
-    const FbInvG ig{poly_ig[0], poly_ig[1], poly_ig[2], poly_ig[3]};
-    const size_t fs = frame_stride(c);
-    FrameChunks fc(c, "Farneback flow", n_pairs, flight, host);
-    float *planes, *d_tab;
-    const size_t ps = fc.sc.per_unit(&planes, (size_t)(box ? FB_BOX_PLANES : FB_PLANES) * fs, true);   // floats from a pair's planes to the next pair's
-    fc.sc.once(&d_tab, tab.size());
-    fc.input(first);
-    fc.input(second);
-    for (double* field : {v_x, v_y, speed}) fc.output(field, fs * sizeof(double));
-    if (int rc = fc.plan()) return rc;
-    for (int s = 0; s < 2; ++s) if (int rc = fc.range(s, -INFINITY, INFINITY, "")) return rc;
-    if (int rc = h2d_bounced(c, d_tab, tab.data(), tab.size() * sizeof(float))) return rc;
-    const float *d_poly = d_tab + n_taps, *d_win = d_poly + poly_len;
-    const FbPair q(planes, fs, window);
-    const double box_scale = 1.0 / (double)(winsize * winsize);
-    const size_t vblur_lds = (size_t)(FB_VB_ROWS + 2 * m) * FB_VB_COLS * sizeof(float);
-    return fc.run([&](int, int nf, const double* const* src, void* const* dst) -> int {
-        int cur = 0;                                                            // q.flow[cur]: the flow of the level in progress
-        for (int lv = n_levels - 1; lv >= 0; --lv) {
-            const int h = level_sizes[2 * lv], w = level_sizes[2 * lv + 1], r = ksizes[lv] / 2;
-            const size_t hw = (size_t)h * w;
-            const float* d_w = d_tab + tap_at[(size_t)lv];
-            const dim3 full((c->Nj + FB_BLOCK - 1) / FB_BLOCK, c->Ni, nf), rows((w + FB_BLOCK - 1) / FB_BLOCK, h, nf);
-            for (int role = 0; role < 2; ++role) {
-                {
-                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_LEVEL, 8.0 * fs + 12.0 * fs + 4.0 * hw);
-                    k_fb_smooth<double, true><<<full, FB_BLOCK, 0, c->stream>>>(src[role], fs, c->Ni, c->Nj, d_w, r, q.tmp_a, ps);
-                    k_fb_smooth<float, false><<<full, FB_BLOCK, 0, c->stream>>>(q.tmp_a, ps, c->Ni, c->Nj, d_w, r, q.tmp_b, ps);
-                    k_fb_resize<false><<<rows, FB_BLOCK, 0, c->stream>>>(q.tmp_b, ps, c->Ni, c->Nj, q.image, ps, h, w, 1.0 / ((double)h / c->Ni),
-                                                                         1.0 / ((double)w / c->Nj), 1, 1.0f);
-                }
-                {
-                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_POLY, 24.0 * hw);
-                    k_fb_polyexp<<<rows, FB_BLOCK, 0, c->stream>>>(q.image, ps, h, w, poly_n, d_poly, ig, q.R[role], ps);
-                }
-            }
-            {
-                Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_FLOW, 8.0 * hw);
-                if (lv == n_levels - 1) {
-                    for (int k = 0; k < nf; ++k) HIPCHK(hipMemsetAsync(q.flow[cur] + (size_t)k * ps, 0, 2 * hw * sizeof(float), c->stream));
-                } else {
-                    const int sh = level_sizes[2 * lv + 2], sw = level_sizes[2 * lv + 3];
-                    k_fb_resize<true><<<dim3(rows.x, h, 2 * nf), FB_BLOCK, 0, c->stream>>>(q.flow[cur ^ 1], ps, sh, sw, q.flow[cur], ps, h, w,
-                                                                                         1.0 / ((double)h / sh), 1.0 / ((double)w / sw), 2, flow_scale);
-                }
-            }
-            if (iterations > 0) {
-                Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_MATRICES, 68.0 * hw);
-                k_fb_matrices<<<rows, FB_BLOCK, 0, c->stream>>>(q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w);
-            }
-            for (int it = 0; it < iterations; ++it) {
-                const bool rebuild = it < iterations - 1;
-                if (box) {
-                    {
-                        Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_BOX_ROWS, 80.0 * hw, 60.0 * hw);     // the row leaving the window is re-read from the caches
-                        k_fb_box_rows<FB_BR_LOOK><<<dim3((w + FB_BR_BLOCK - 1) / FB_BR_BLOCK, 1, 5 * nf), FB_BR_BLOCK, 0, c->stream>>>(
-                            q.M, ps, (double*)q.V, ps / 2, h, w, m);
-                    }
-                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_BOX_UPDATE, (rebuild ? 148.0 : 88.0) * hw, (rebuild ? 108.0 : 48.0) * hw);   // likewise the column
-                    k_fb_box_update<<<dim3((h + FB_BU_ROWS - 1) / FB_BU_ROWS, 1, nf), FB_BLOCK, 0, c->stream>>>(
-                        (const double*)q.V, ps / 2, q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w, m, box_scale, rebuild ? 1 : 0);
-                    continue;
-                }
-                {
-                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_VBLUR, 40.0 * hw);
-                    k_fb_vblur<<<dim3((w + FB_VB_COLS - 1) / FB_VB_COLS, (h + FB_VB_ROWS - 1) / FB_VB_ROWS, 5 * nf), FB_BLOCK, vblur_lds, c->stream>>>(
-                        q.M, q.V, ps, h, w, m, d_win);
-                }
-                {
-                    Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_UPDATE, (rebuild ? 88.0 : 28.0) * hw);
-                    k_fb_update<<<rows, FB_BLOCK, 0, c->stream>>>(q.V, q.R[0], q.R[1], q.flow[cur], q.M, ps, h, w, m, d_win, rebuild ? 1 : 0);
-                }
-            }
-            HIPCHK(hipGetLastError());
-            cur ^= 1;
-        }
-        cur ^= 1;                                                               // the finished level 0
-        Prof prof(c, VOF_K_PREPROCESS, PP_ST_FB_OUT, 32.0 * fs);
-        k_fb_output<<<dim3((unsigned)((fs + FB_BLOCK - 1) / FB_BLOCK), 1, nf), FB_BLOCK, 0, c->stream>>>(q.flow[cur], ps, fs, velocity_scale, (double*)dst[0],
-                                                                                                        (double*)dst[1], (double*)dst[2]);
-        return 0;
-    });
-}
-
-int vof_farneback_dev(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
-                      const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, const float* window_taps,
-                      int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
-    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_GAUSSIAN, winsize,
-                          window_taps, iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, false);
-}
-int vof_farneback_host(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
-                       const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, const float* window_taps,
-                       int iterations, float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
-    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_GAUSSIAN, winsize,
-                          window_taps, iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, true);
-}
-int vof_farneback_box_dev(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
-                          const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, int iterations,
-                          float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
-    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_BOX, winsize, nullptr,
-                          iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, false);
-}
-int vof_farneback_box_host(vof_ctx* c, const double* first, const double* second, int n_pairs, int n_levels, const int* level_sizes, const int* ksizes,
-                           const float* presmooth_taps, int poly_n, const float* poly_tables, const double* poly_ig, int winsize, int iterations,
-                           float flow_scale, double velocity_scale, int frames_in_flight, double* v_x, double* v_y, double* speed) {
-    return farneback_impl(c, first, second, n_pairs, n_levels, level_sizes, ksizes, presmooth_taps, poly_n, poly_tables, poly_ig, FB_BOX, winsize, nullptr,
-                          iterations, flow_scale, velocity_scale, frames_in_flight, v_x, v_y, speed, true);
-}
-
-// ---- two finished flow results: the result filter and the comparison (filter_PIV_flow_result, compare_flow_results;
-// vof_flowcompare.hpp) ------------------------------------------------------------------------------
-static int flow_filter_impl(vof_ctx* c, const double* movie, int n_pairs, const double* weights, int radius, double intensity, double limit,
-                            int zero_low, int flight, double* v_x, double* v_y, double* speed, int64_t* counts, bool host) {
-    if (int rc = FrameChunks::check(c, {movie, weights, v_x, v_y, speed, counts}, n_pairs, "n_pairs")) return rc;
-    if (radius < 0 || radius > 4096) { c->err = "bad blur_radius"; return -1; }
-    if (std::isnan(intensity) || std::isnan(limit)) { c->err = "flow filter: a threshold is NaN"; return -1; }
-    const size_t fs = frame_stride(c);
-    FrameChunks fc(c, "flow filter", n_pairs, flight, host);
-    double *blurred, *tmp, *w;                                      // the blurred frames of one chunk: never a stack
-    unsigned long long* d_counts;
-    fc.sc.per_unit(&blurred, fs);
-    blur_regions(fc.sc, n_pairs, &tmp, &w, radius);
-    fc.sc.once(&d_counts, 2);
-    fc.input(movie); fc.input(v_x); fc.input(v_y); fc.input(speed);
-    fc.output(v_x, fs * sizeof(double)); fc.output(v_y, fs * sizeof(double)); fc.output(speed, fs * sizeof(double));
-    if (int rc = fc.plan()) return rc;
-    if (int rc = h2d_bounced(c, w, weights, (size_t)(2 * radius + 1) * sizeof(double))) return rc;
-    HIPCHK(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    if (int rc = fc.run([&](int, int nf, const double* const* in, void* const* out) -> int {
-            if (int rc = blur_frames(c, in[0], blurred, nf, radius, tmp, w)) return rc;
-            const size_t n = (size_t)nf * fs;
-            const int blocks = (int)std::min<size_t>(2048, (n + 8 * FC_BLOCK - 1) / (8 * FC_BLOCK));
-            Prof prof(c, VOF_K_REDUCE, FC_ST_MASK, 56.0 * fs);
-            k_fc_mask<<<blocks, FC_BLOCK, 0, c->stream>>>(blurred, in[1], in[2], in[3], n, intensity, limit, zero_low, (double*)out[0],
-                                                          (double*)out[1], (double*)out[2], d_counts);
-            return 0;
-        })) return rc;
-    unsigned long long h[2];
-    if (int rc = d2h_bounced(c, h, d_counts, sizeof h)) return rc;
-    counts[0] = (int64_t)h[0]; counts[1] = (int64_t)h[1];
-    return 0;
-}
-
-int vof_flow_filter_dev(vof_ctx* c, const double* movie, int n_pairs, const double* blur_weights, int blur_radius, double intensity_threshold,
-                        double speed_threshold, int zero_speed_under_low, int frames_in_flight, double* v_x, double* v_y, double* speed,
-                        int64_t* counts) {
-    return flow_filter_impl(c, movie, n_pairs, blur_weights, blur_radius, intensity_threshold, speed_threshold, zero_speed_under_low,
-                            frames_in_flight, v_x, v_y, speed, counts, false);
-}
-int vof_flow_filter_host(vof_ctx* c, const double* movie, int n_pairs, const double* blur_weights, int blur_radius, double intensity_threshold,
-                         double speed_threshold, int zero_speed_under_low, int frames_in_flight, double* v_x, double* v_y, double* speed,
-                         int64_t* counts) {
-    return flow_filter_impl(c, movie, n_pairs, blur_weights, blur_radius, intensity_threshold, speed_threshold, zero_speed_under_low,
-                            frames_in_flight, v_x, v_y, speed, counts, true);
-}
-
-// ---- the illumination correction and the intensity histograms (correct_intensity_change, intensity_histograms;
-// vof_intensity.hpp) ---------------------------------------------------------------------------------
-// The second blur of nf frames of b less the one frame ref, and the subtraction from target: the two fused passes, mid the
-// row-filtered frames between them.  Radii BL_RMIN .. BL_RMAX take the LDS tiles, the others global memory: same bits.
-static bool intensity_tiled(int radius) { return radius >= BL_RMIN && radius <= BL_RMAX; }
-
-static int intensity_passes(vof_ctx* c, const double* b, const double* ref, const double* target, int nf, int radius, const double* w,
-                            double* mid, double* out, double* drift) {
-    const size_t fs = frame_stride(c);
-    const bool tiled = intensity_tiled(radius);
-    const dim3 g0((c->Nj + BX - 1) / BX, (c->Ni + BL_TI - 1) / BL_TI, nf), g1(g0.x, (c->Ni + BL_TR - 1) / BL_TR, nf), g = grid2d(c->Ni, c->Nj, nf);
-    {
-        Prof prof(c, VOF_K_PREPROCESS, PP_ST_IC_AXIS0, 24.0 * fs, 16.0 * fs);       // the reference frame is re-read from the caches
-        if (tiled) k_ic_axis0_tiled<<<g0, blk2d, blur_tiled_lds(0, radius), c->stream>>>(b, ref, mid, c->Ni, c->Nj, w, radius);
-        else k_ic_axis0<<<g, blk2d, 0, c->stream>>>(b, ref, mid, c->Ni, c->Nj, w, radius);
-    }
-    {
-        Prof prof(c, VOF_K_PREPROCESS, PP_ST_IC_AXIS1, (drift ? 32.0 : 24.0) * fs);
-        if (tiled && drift) k_ic_axis1_tiled<true><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
-        else if (tiled) k_ic_axis1_tiled<false><<<g1, blk2d, blur_tiled_lds(1, radius), c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
-        else if (drift) k_ic_axis1<true><<<g, blk2d, 0, c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
-        else k_ic_axis1<false><<<g, blk2d, 0, c->stream>>>(mid, target, out, drift, c->Ni, c->Nj, w, radius);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int intensity_correct_impl(vof_ctx* c, const double* movie, int n_frames, const double* w1_host, int r1, const double* w2_host, int r2,
-                                  int reference_frame, int target, int flight, double* out, double* drift, bool host) {
-    if (int rc = FrameChunks::check(c, {movie, w2_host, out}, n_frames, "n_frames")) return rc;
-    if ((w1_host && (r1 < 0 || r1 > 4096)) || r2 < 0 || r2 > 4096) { c->err = "bad smoothing_radius / filter_radius"; return -1; }
-    if (reference_frame < 0 || reference_frame >= n_frames) { c->err = "intensity correction: reference_frame outside the stack"; return -1; }
-    if (target != VOF_INTENSITY_TARGET_BLURRED && target != VOF_INTENSITY_TARGET_ORIGINAL) { c->err = "intensity correction: unknown target"; return -1; }
-    const size_t fs = frame_stride(c);
-    FrameChunks fc(c, "intensity correction", n_frames, flight, host);
-    // once per call: the (blurred) reference frame and the taps; per frame in flight: the blurred frame and the row-filtered one,
-    // which is the first blur's scratch too (a chunk of at least BLUR_CHUNK frames is blurred BLUR_CHUNK at a time)
-    double *bref = nullptr, *blurred = nullptr, *mid, *w1 = nullptr, *w2;
-    if (w1_host || host) fc.sc.once(&bref, fs);
-    if (w1_host) { fc.sc.per_unit(&blurred, fs); fc.sc.once(&w1, (size_t)2 * r1 + 1); }
-    fc.sc.per_unit(&mid, fs);
-    fc.sc.once(&w2, (size_t)2 * r2 + 1);
-    fc.input(movie);
-    fc.output(out, fs * sizeof(double));
-    if (drift) fc.output(drift, fs * sizeof(double));
-    if (int rc = fc.plan()) return rc;
-    // the axis-0 tile takes up to 80 KiB of dynamic LDS, past the default limit: raised for its kernel before the walk, in every
-    // call that takes the tiles (a host-side setting of a few microseconds; the context keeps no record of it)
-    if (intensity_tiled(r2))
-        HIPCHK(hipFuncSetAttribute((const void*)k_ic_axis0_tiled, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blur_tiled_lds(0, BL_RMAX)));
-    if (w1_host) if (int rc = h2d_bounced(c, w1, w1_host, (size_t)(2 * r1 + 1) * sizeof(double))) return rc;
-    if (int rc = h2d_bounced(c, w2, w2_host, (size_t)(2 * r2 + 1) * sizeof(double))) return rc;
-    const double* ref = movie + (size_t)reference_frame * fs;
-    if (host) { if (int rc = h2d_bounced(c, bref, ref, fs * sizeof(double))) return rc; ref = bref; }
-    c->cur_units = 1;
-    if (w1_host) { if (int rc = blur_frames(c, ref, bref, 1, r1, mid, w1)) return rc; ref = bref; }
-    return fc.run([&](int, int nf, const double* const* in, void* const* dst) -> int {
-        const double* b = in[0];
-        if (w1_host) { if (int rc = blur_frames(c, in[0], blurred, nf, r1, mid, w1)) return rc; b = blurred; }
-        return intensity_passes(c, b, ref, target == VOF_INTENSITY_TARGET_BLURRED ? b : in[0], nf, r2, w2, mid, (double*)dst[0],
-                                drift ? (double*)dst[1] : nullptr);
-    });
-}
-
-int vof_intensity_correct_dev(vof_ctx* c, const double* movie, int n_frames, const double* smoothing_weights, int smoothing_radius,
-                              const double* filter_weights, int filter_radius, int reference_frame, int target, int frames_in_flight,
-                              double* out, double* drift) {
-    return intensity_correct_impl(c, movie, n_frames, smoothing_weights, smoothing_radius, filter_weights, filter_radius, reference_frame, target,
-                                  frames_in_flight, out, drift, false);
-}
-int vof_intensity_correct_host(vof_ctx* c, const double* movie, int n_frames, const double* smoothing_weights, int smoothing_radius,
-                               const double* filter_weights, int filter_radius, int reference_frame, int target, int frames_in_flight,
-                               double* out, double* drift) {
-    return intensity_correct_impl(c, movie, n_frames, smoothing_weights, smoothing_radius, filter_weights, filter_radius, reference_frame, target,
-                                  frames_in_flight, out, drift, true);
-}
-
-static int intensity_hist_impl(vof_ctx* c, const double* movie, int n_frames, const double* w_host, int radius, const double* edges_host, int bins,
-                               int flight, int64_t* counts, int64_t* nonfinite, bool host) {
-    if (int rc = FrameChunks::check(c, {movie, edges_host, counts, nonfinite}, n_frames, "n_frames")) return rc;
-    if (w_host && (radius < 0 || radius > 4096)) { c->err = "bad blur_radius"; return -1; }
-    if (bins < 1 || bins > IH_MAX_BINS) { c->err = "intensity histograms: bins must be 1 .. " + std::to_string(IH_MAX_BINS); return -1; }
-    if (!(edges_host[0] < edges_host[bins])) { c->err = "intensity histograms: the edges must increase"; return -1; }
-    const size_t fs = frame_stride(c);
-    FrameChunks fc(c, "intensity histograms", n_frames, flight, host);
-    double *blurred = nullptr, *tmp = nullptr, *w = nullptr, *edges;
-    unsigned long long *d_hist, *d_bad;                              // [frame in flight][bins], [frame in flight]
-    if (w_host) { fc.sc.per_unit(&blurred, fs); blur_regions(fc.sc, n_frames, &tmp, &w, radius); }
-    fc.sc.once(&edges, (size_t)bins + 1);
-    fc.sc.per_unit(&d_hist, (size_t)bins);
-    fc.sc.per_unit(&d_bad, 1);
-    fc.input(movie);
-    if (int rc = fc.plan()) return rc;
-    if (w_host) if (int rc = h2d_bounced(c, w, w_host, (size_t)(2 * radius + 1) * sizeof(double))) return rc;
-    if (int rc = h2d_bounced(c, edges, edges_host, ((size_t)bins + 1) * sizeof(double))) return rc;
-    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are copied out as they are");
-    const int blocks = (int)std::min<size_t>(IH_MAX_BLOCKS, (fs + (size_t)IH_PER_THREAD * IH_BLOCK - 1) / ((size_t)IH_PER_THREAD * IH_BLOCK));
-    return fc.run([&](int k0, int nf, const double* const* in, void* const*) -> int {
-        const double* x = in[0];
-        if (w_host) { if (int rc = blur_frames(c, in[0], blurred, nf, radius, tmp, w)) return rc; x = blurred; }
-        HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)nf * bins * sizeof(unsigned long long), c->stream));
-        HIPCHK(hipMemsetAsync(d_bad, 0, (size_t)nf * sizeof(unsigned long long), c->stream));
-        {
-            Prof prof(c, VOF_K_PREPROCESS, PP_ST_IH_COUNTS, 8.0 * fs);
-            k_ih_counts<<<dim3(blocks, nf), IH_BLOCK, 0, c->stream>>>(x, fs, edges, bins, d_hist, d_bad);
-        }
-        HIPCHK(hipGetLastError());
-        if (int rc = d2h_bounced(c, counts + (size_t)k0 * bins, d_hist, (size_t)nf * bins * sizeof(int64_t))) return rc;
-        return d2h_bounced(c, nonfinite + k0, d_bad, (size_t)nf * sizeof(int64_t));
-    });
-}
-
-int vof_intensity_hist_dev(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, int blur_radius, const double* edges,
-                           int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite) {
-    return intensity_hist_impl(c, movie, n_frames, blur_weights, blur_radius, edges, bins, frames_in_flight, counts, nonfinite, false);
-}
-int vof_intensity_hist_host(vof_ctx* c, const double* movie, int n_frames, const double* blur_weights, int blur_radius, const double* edges,
-                            int bins, int frames_in_flight, int64_t* counts, int64_t* nonfinite) {
-    return intensity_hist_impl(c, movie, n_frames, blur_weights, blur_radius, edges, bins, frames_in_flight, counts, nonfinite, true);
-}
-
-// ---- the dense part of convert_PIV_result (upsample_PIV_vectors; vof_piv.hpp) --------------------------------
-// What the kernels index with comes from the caller: every table is checked on the host before anything is uploaded.
-struct PivRequest {
-    int n_frames;
-    const double *points, *values, *grads, *transforms;
-    const int32_t *simplices, *neighbours, *pt_off, *tri_off;
-};
-
-static int piv_check(vof_ctx* c, const PivRequest& r, int* max_points, int* max_triangles) {
-    if (frame_stride(c) >= (size_t)PIV_NONE) { c->err = "PIV upsampling: frames of 2^31 pixels or more are not served"; return -1; }
-    if (r.pt_off[0] != 0 || r.tri_off[0] != 0) { c->err = "PIV upsampling: the offsets must start at 0"; return -1; }
-    *max_points = *max_triangles = 0;
-    for (int f = 0; f < r.n_frames; ++f) {
-        const int np = r.pt_off[f + 1] - r.pt_off[f], nt = r.tri_off[f + 1] - r.tri_off[f];
-        if (np < 0 || nt < 0 || (nt > 0 && np < 3)) { c->err = "PIV upsampling: bad offsets in frame " + std::to_string(f); return -1; }
-        *max_points = std::max(*max_points, np); *max_triangles = std::max(*max_triangles, nt);
-        const double* P = r.points + (size_t)2 * r.pt_off[f];
-        for (int k = 0; k < 2 * np; ++k)
-            if (!std::isfinite(P[k]) || !std::isfinite(r.values[(size_t)2 * r.pt_off[f] + k]) || !std::isfinite(r.grads[(size_t)4 * r.pt_off[f] + 2 * k]) ||
-                !std::isfinite(r.grads[(size_t)4 * r.pt_off[f] + 2 * k + 1])) {
-                c->err = "PIV upsampling: a point, a vector or a gradient of frame " + std::to_string(f) + " is not finite"; return -1;
-            }
-        for (size_t k = (size_t)3 * r.tri_off[f]; k < (size_t)3 * r.tri_off[f + 1]; ++k)
-            if (r.simplices[k] < 0 || r.simplices[k] >= np || r.neighbours[k] < -1 || r.neighbours[k] >= nt) {
-                c->err = "PIV upsampling: a simplex or a neighbour of frame " + std::to_string(f) + " is outside its tables"; return -1;
-            }
-        for (size_t k = (size_t)6 * r.tri_off[f]; k < (size_t)6 * r.tri_off[f + 1]; ++k)
-            if (!std::isfinite(r.transforms[k])) {
-                c->err = "PIV upsampling: frame " + std::to_string(f) + " has a degenerate simplex (its transform is not finite): evaluate it "
-                         "on the host and pass it without triangles";
-                return -1;
-            }
-    }
-    return 0;
-}
-
-static int piv_upsample_impl(vof_ctx* c, const PivRequest& r, int flight, double* v_x, double* v_y, double* speed, int64_t* counts, bool host) {
-    if (int rc = FrameChunks::check(c, {r.points, r.values, r.grads, r.transforms, r.simplices, r.neighbours, r.pt_off, r.tri_off, v_x, v_y, speed, counts},
-                                    r.n_frames, "n_frames")) return rc;
-    int mp = 0, mt = 0;
-    if (int rc = piv_check(c, r, &mp, &mt)) return rc;
-    const size_t fs = frame_stride(c);
-    FrameChunks fc(c, "PIV upsampling", r.n_frames, flight, host);
-    // per frame in flight: its tables at the size of the call's largest frame (a chunk's tables are uploaded frame after frame, so
-    // they fit whatever the frames), the coefficients and the map; once: the offsets and the counter
-    double *d_pts, *d_val, *d_grad, *d_tr, *d_coef;
-    int *d_simp, *d_nb, *d_map, *d_ptoff, *d_trioff;
-    unsigned long long* d_outside;
-    fc.sc.per_unit(&d_pts, (size_t)2 * mp); fc.sc.per_unit(&d_val, (size_t)2 * mp); fc.sc.per_unit(&d_grad, (size_t)4 * mp);
-    fc.sc.per_unit(&d_tr, (size_t)6 * mt); fc.sc.per_unit(&d_coef, (size_t)PIV_COEF * mt);
-    fc.sc.per_unit(&d_simp, (size_t)3 * mt); fc.sc.per_unit(&d_nb, (size_t)3 * mt);
-    fc.sc.per_unit(&d_map, fs);
-    fc.sc.once(&d_ptoff, (size_t)r.n_frames + 1); fc.sc.once(&d_trioff, (size_t)r.n_frames + 1);
-    fc.sc.once(&d_outside, 1);
-    fc.output(v_x, fs * sizeof(double)); fc.output(v_y, fs * sizeof(double)); fc.output(speed, fs * sizeof(double));
-    if (int rc = fc.plan()) return rc;
-    if (int rc = h2d_bounced(c, d_ptoff, r.pt_off, ((size_t)r.n_frames + 1) * sizeof(int32_t))) return rc;
-    if (int rc = h2d_bounced(c, d_trioff, r.tri_off, ((size_t)r.n_frames + 1) * sizeof(int32_t))) return rc;
-    HIPCHK(hipMemsetAsync(d_outside, 0, sizeof(unsigned long long), c->stream));
-    static_assert(PIV_NONE == 0x7f7f7f7f, "the map is filled bytewise");
-    if (int rc = fc.run([&](int k0, int nf, const double* const*, void* const* out) -> int {
-            const size_t p0 = r.pt_off[k0], np = (size_t)r.pt_off[k0 + nf] - p0, t0 = r.tri_off[k0], nt = (size_t)r.tri_off[k0 + nf] - t0;
-            int most = 0;                                           // triangles of the chunk's largest frame
-            for (int f = k0; f < k0 + nf; ++f) most = std::max(most, r.tri_off[f + 1] - r.tri_off[f]);
-            if (np) {
-                if (int rc = h2d_bounced(c, d_pts, r.points + 2 * p0, 2 * np * sizeof(double))) return rc;
-                if (int rc = h2d_bounced(c, d_val, r.values + 2 * p0, 2 * np * sizeof(double))) return rc;
-                if (int rc = h2d_bounced(c, d_grad, r.grads + 4 * p0, 4 * np * sizeof(double))) return rc;
-            }
-            if (nt) {
-                if (int rc = h2d_bounced(c, d_tr, r.transforms + 6 * t0, 6 * nt * sizeof(double))) return rc;
-                if (int rc = h2d_bounced(c, d_simp, r.simplices + 3 * t0, 3 * nt * sizeof(int32_t))) return rc;
-                if (int rc = h2d_bounced(c, d_nb, r.neighbours + 3 * t0, 3 * nt * sizeof(int32_t))) return rc;
-            }
-            const PivTables tb{d_pts, d_val, d_grad, d_tr, d_simp, d_nb, d_ptoff + k0, d_trioff + k0};
-            HIPCHK(hipMemsetAsync(d_map, 0x7f, (size_t)nf * fs * sizeof(int), c->stream));
-            if (most) {
-                {
-                    Prof prof(c, VOF_K_REDUCE, PIV_ST_COEFFS, 8.0 * (PIV_COEF + 20) * (double)nt / nf);
-                    k_piv_coeffs<<<dim3((most + PIV_BLOCK - 1) / PIV_BLOCK, nf), PIV_BLOCK, 0, c->stream>>>(tb, d_coef);
-                }
-                {
-                    Prof prof(c, VOF_K_REDUCE, PIV_ST_LOCATE);
-                    k_piv_locate<<<dim3((most + PIV_TRI_PER_BLOCK - 1) / PIV_TRI_PER_BLOCK, nf), PIV_BLOCK, 0, c->stream>>>(tb, d_coef, d_map, c->Ni, c->Nj);
-                }
-            }
-            Prof prof(c, VOF_K_REDUCE, PIV_ST_EVAL, 28.0 * fs);
-            k_piv_eval<<<dim3((unsigned)((fs + PIV_BLOCK - 1) / PIV_BLOCK), nf), PIV_BLOCK, 0, c->stream>>>(tb, d_coef, d_map, c->Ni, c->Nj, (double*)out[0],
-                                                                                                      (double*)out[1], (double*)out[2], d_outside);
-            return 0;
-        })) return rc;
-    unsigned long long outside;
-    if (int rc = d2h_bounced(c, &outside, d_outside, sizeof outside)) return rc;
-    counts[0] = (int64_t)outside; counts[1] = 0;
-    for (int f = 0; f < r.n_frames; ++f) counts[1] += r.tri_off[f + 1] == r.tri_off[f];
-    return 0;
-}
-
-int vof_piv_upsample_dev(vof_ctx* c, int n_frames, const double* points, const double* values, const double* gradients, const int32_t* simplices,
-                         const int32_t* neighbours, const double* transforms, const int32_t* point_offsets, const int32_t* triangle_offsets,
-                         int frames_in_flight, double* v_x, double* v_y, double* speed, int64_t* counts) {
-    return piv_upsample_impl(c, PivRequest{n_frames, points, values, gradients, transforms, simplices, neighbours, point_offsets, triangle_offsets},
-                             frames_in_flight, v_x, v_y, speed, counts, false);
-}
-int vof_piv_upsample_host(vof_ctx* c, int n_frames, const double* points, const double* values, const double* gradients, const int32_t* simplices,
-                          const int32_t* neighbours, const double* transforms, const int32_t* point_offsets, const int32_t* triangle_offsets,
-                          int frames_in_flight, double* v_x, double* v_y, double* speed, int64_t* counts) {
-    return piv_upsample_impl(c, PivRequest{n_frames, points, values, gradients, transforms, simplices, neighbours, point_offsets, triangle_offsets},
-                             frames_in_flight, v_x, v_y, speed, counts, true);
-}
-
-// ---- conduct_piv: windowed cross-correlation PIV of every pair of a stack (vof_pivflow.hpp) -----------------
-// The passes of a request, checked: what include/vof.h lists, and that every search region stays inside the frame for the largest
-// offset the pass before can hand on (its margin).  Nothing is uploaded before this returns 0.
-static int piv_flow_passes(vof_ctx* c, int n_passes, const int32_t* w, const int32_t* r, const int32_t* s, PfPass* P) {
-    if (n_passes < 1 || n_passes > PF_MAX_PASSES) { c->err = "PIV: n_passes must lie in [1, " + std::to_string(PF_MAX_PASSES) + "]"; return -1; }
-    int m = 0;
-    for (int p = 0; p < n_passes; ++p) {
-        const std::string at = "PIV pass " + std::to_string(p) + ": ";
-        if (w[p] < PF_MIN_W || w[p] > PF_MAX_W) { c->err = at + "the window size must lie in [4, 64]"; return -1; }
-        if (r[p] < 1 || r[p] > PF_MAX_R) { c->err = at + "the search radius must lie in [1, 16]"; return -1; }
-        if (s[p] < 1) { c->err = at + "the step must be >= 1"; return -1; }
-        if (p > 0 && w[p] > w[p - 1]) { c->err = at + "window sizes must not increase from pass to pass"; return -1; }
-        if (pf_lds_doubles(w[p], r[p]) * sizeof(double) > PF_LDS_LIMIT || pf_items(r[p]) > PF_BLOCK) {
-            c->err = at + "the window and its search region do not fit the LDS of a compute unit"; return -1;
-        }
-        m += r[p];
-        const int span = w[p] + 2 * m;
-        if (c->Ni < span || c->Nj < span) { c->err = at + "the grid is empty: the frame is smaller than window + 2 * margin = " + std::to_string(span); return -1; }
-        P[p] = PfPass{w[p], r[p], s[p], m, (c->Ni - span) / s[p] + 1, (c->Nj - span) / s[p] + 1};
-        if (P[p].R > 65535) { c->err = at + "more than 65535 rows of windows do not fit one launch"; return -1; }
-        // window (a, b) at m + a s; offsets |o| <= m - r, the margin of the pass before: rows [m + a s + o - r, ... + w + 2 r) of the frame
-        const int lo = m - (m - r[p]) - r[p], hi_i = m + (P[p].R - 1) * s[p] + (m - r[p]) + r[p] + w[p], hi_j = m + (P[p].C - 1) * s[p] + (m - r[p]) + r[p] + w[p];
-        if (lo < 0 || hi_i > c->Ni || hi_j > c->Nj) { c->err = at + "a search region leaves the frame"; return -1; }
-    }
-    return 0;
-}
-
-// one pass of np pairs; the run length of the hot loop goes with the radius (pf_run).  deform: the vectors the region is resampled by
-// (a pass after the first, off NULL), or NULL for the integer path.
-static int piv_flow_launch(vof_ctx* c, const PfPass& p, int np, const double* frames, const int* off, double min_correlation, double* u, double* v,
-                           double* corr, unsigned long long* counts, const PfDeform* deform = nullptr) {
-    const size_t lds = pf_lds_doubles(p.w, p.r) * sizeof(double);
-    const int slot = (deform ? 2 : 0) + (pf_run(p.r) == PF_LONG_RUN ? 1 : 0);
-    const void* const kernels[4] = {(const void*)k_pivflow_correlate<PF_SHORT_RUN, false>, (const void*)k_pivflow_correlate<PF_LONG_RUN, false>,
-                                    (const void*)k_pivflow_correlate<PF_SHORT_RUN, true>, (const void*)k_pivflow_correlate<PF_LONG_RUN, true>};
-    if (lds > c->pivflow_lds[slot]) {                               // raised once per context and kernel
-        HIPCHK(hipFuncSetAttribute(kernels[slot], hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_LIMIT));
-        c->pivflow_lds[slot] = PF_LDS_LIMIT;
-    }
-    const dim3 grid(p.C, p.R, np);
-    const PfDeform df = deform ? *deform : PfDeform{};
-#define PF_LAUNCH(K, DEFORM) k_pivflow_correlate<K, DEFORM><<<grid, PF_BLOCK, lds, c->stream>>>(p, frames, frame_stride(c), c->Nj, off, min_correlation, u, v, corr, counts, df)
-    switch (slot) {
-        case 0: PF_LAUNCH(PF_SHORT_RUN, false); break;
-        case 1: PF_LAUNCH(PF_LONG_RUN, false); break;
-        case 2: PF_LAUNCH(PF_SHORT_RUN, true); break;
-        default: PF_LAUNCH(PF_LONG_RUN, true); break;
-    }
-#undef PF_LAUNCH
-    return 0;
-}
-
-// the options of vof_piv_flow_ex_*; the plain call is PivFlowOptions{}
-struct PivFlowOptions {
-    int deformation = 0; double outlier_threshold = NAN, outlier_epsilon = 0.1; int validate_last = 0; int64_t* validation_counts = nullptr;
-    bool validating() const { return !std::isnan(outlier_threshold); }
-};
-static int piv_flow_options(vof_ctx* c, const PivFlowOptions& o) {
-    if (o.deformation != 0 && o.deformation != 1) { c->err = "PIV: deformation must be 0 or 1"; return -1; }
-    if (o.validate_last != 0 && o.validate_last != 1) { c->err = "PIV: validate_last must be 0 or 1"; return -1; }
-    if (o.validating() && !(o.outlier_threshold > 0.0 && std::isfinite(o.outlier_threshold))) { c->err = "PIV: outlier_threshold must be positive and finite, or NaN for none"; return -1; }
-    if (!(o.outlier_epsilon >= 0.0 && std::isfinite(o.outlier_epsilon))) { c->err = "PIV: outlier_epsilon must be non-negative and finite"; return -1; }
-    if (o.validate_last && !o.validating()) { c->err = "PIV: validate_last needs an outlier_threshold"; return -1; }
-    if (o.validating() && !o.validation_counts) { c->err = "PIV: validation_counts is NULL with validation on"; return -1; }
-    return 0;
-}
-
-static int piv_flow_impl(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
-                         const int32_t* steps, double min_correlation, int flight, double* u, double* v, double* correlation, int64_t* counts, bool host,
-                         const PivFlowOptions& opt = PivFlowOptions{}) {
-    if (int rc = FrameChunks::check(c, {movie, window_sizes, search_radii, steps, u, v, correlation, counts}, n_pairs, "n_pairs")) return rc;
-    if (int rc = piv_flow_options(c, opt)) return rc;
-    PfPass P[PF_MAX_PASSES];
-    if (int rc = piv_flow_passes(c, n_passes, window_sizes, search_radii, steps, P)) return rc;
-    const int last = n_passes - 1;
-    const bool validating = opt.validating(), deform = opt.deformation != 0;
-    FrameChunks fc(c, "PIV", n_pairs, flight, host);
-    fc.input(movie, true);
-    // per pair in flight: the vectors of every pass but the last (and of the last where they are validated), the validated vectors at
-    // the size of the largest validated grid, and - on the integer path - the offsets of a pass at the size of the largest grid
-    double *d_u[PF_MAX_PASSES] = {}, *d_v[PF_MAX_PASSES] = {}, *d_val_u = nullptr, *d_val_v = nullptr;
-    int* d_off = nullptr;
-    unsigned long long* d_counts = nullptr;                         // 3 per pass, then the 2 of the validation per pass
-    const bool validated_last = validating && opt.validate_last;
-    size_t most = 0, most_validated = 0;
-    for (int p = 0; p < last + (validated_last ? 1 : 0); ++p) {
-        fc.sc.per_unit(&d_u[p], (size_t)P[p].R * P[p].C); fc.sc.per_unit(&d_v[p], (size_t)P[p].R * P[p].C);
-        if (p < last) { most = std::max(most, (size_t)P[p + 1].R * P[p + 1].C); most_validated = std::max(most_validated, (size_t)P[p].R * P[p].C); }
-    }
-    if (last > 0 && !deform) fc.sc.per_unit(&d_off, 2 * most);
-    if (last > 0 && validating) { fc.sc.per_unit(&d_val_u, most_validated); fc.sc.per_unit(&d_val_v, most_validated); }
-    fc.sc.once(&d_counts, (size_t)5 * n_passes);
-    const size_t ob = (size_t)P[last].R * P[last].C * sizeof(double);
-    fc.output(u, ob); fc.output(v, ob); fc.output(correlation, ob);
-    if (int rc = fc.plan()) return rc;
-    HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)5 * n_passes * sizeof(unsigned long long), c->stream));
-    if (int rc = fc.run([&](int, int np, const double* const* in, void* const* out) -> int {
-            const double *from_u = nullptr, *from_v = nullptr;       // the vectors the next pass starts from
-            for (int p = 0; p < n_passes; ++p) {
-                PfDeform df{};
-                if (p > 0 && deform) df = PfDeform{P[p - 1], from_u, from_v, c->Ni};
-                else if (p > 0) {
-                    Prof prof(c, VOF_K_REDUCE, PF_ST_OFFSETS);
-                    k_pivflow_offsets<<<dim3((P[p].R * P[p].C + PF_BLOCK - 1) / PF_BLOCK, np), PF_BLOCK, 0, c->stream>>>(P[p], P[p - 1], from_u, from_v, d_off);
-                }
-                const bool raw_out = p == last && !validated_last;  // the last pass writes the outputs, unless the median test does
-                double* pu = raw_out ? (double*)out[0] : d_u[p];
-                double* pv = raw_out ? (double*)out[1] : d_v[p];
-                double* pc = p == last ? (double*)out[2] : nullptr;
-                {
-                    const double S = P[p].w + 2.0 * P[p].r;
-                    Prof prof(c, VOF_K_REDUCE, PF_ST_PASS0 + p, 8.0 * (P[p].w * (double)P[p].w + S * S) * P[p].R * P[p].C);
-                    const int rc = piv_flow_launch(c, P[p], np, in[0], p && !deform ? d_off : nullptr, min_correlation, pu, pv, pc, d_counts + 3 * p,
-                                                   p && deform ? &df : nullptr);
-                    if (rc) return rc;
-                }
-                from_u = pu; from_v = pv;
-                if (validating && (p < last || validated_last)) {   // Jacobi: from the raw vectors into a second field
-                    double* vu = p == last ? (double*)out[0] : d_val_u;
-                    double* vv = p == last ? (double*)out[1] : d_val_v;
-                    Prof prof(c, VOF_K_REDUCE, PF_ST_OFFSETS);
-                    k_pivflow_validate<<<dim3((P[p].R * P[p].C + PF_BLOCK - 1) / PF_BLOCK, np), PF_BLOCK, 0, c->stream>>>(
-                        P[p].R, P[p].C, pu, pv, opt.outlier_threshold, opt.outlier_epsilon, vu, vv, d_counts + 3 * n_passes + 2 * p);
-                    from_u = vu; from_v = vv;
-                }
-            }
-            return 0;
-        })) return rc;
-    unsigned long long got[5 * PF_MAX_PASSES];
-    if (int rc = d2h_bounced(c, got, d_counts, (size_t)5 * n_passes * sizeof(unsigned long long))) return rc;
-    for (int k = 0; k < 3 * n_passes; ++k) counts[k] = (int64_t)got[k];
-    if (validating) for (int k = 0; k < 2 * n_passes; ++k) opt.validation_counts[k] = (int64_t)got[3 * n_passes + k];
-    return 0;
-}
-
-int vof_piv_flow_dev(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
-                     const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts) {
-    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, false);
-}
-int vof_piv_flow_host(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
-                      const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts) {
-    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, true);
-}
-int vof_piv_flow_ex_dev(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
-                        const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts,
-                        int deformation, double outlier_threshold, double outlier_epsilon, int validate_last, int64_t* validation_counts) {
-    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, false,
-                         PivFlowOptions{deformation, outlier_threshold, outlier_epsilon, validate_last, validation_counts});
-}
-int vof_piv_flow_ex_host(vof_ctx* c, const double* movie, int n_pairs, int n_passes, const int32_t* window_sizes, const int32_t* search_radii,
-                         const int32_t* steps, double min_correlation, int frames_in_flight, double* u, double* v, double* correlation, int64_t* counts,
-                         int deformation, double outlier_threshold, double outlier_epsilon, int validate_last, int64_t* validation_counts) {
-    return piv_flow_impl(c, movie, n_pairs, n_passes, window_sizes, search_radii, steps, min_correlation, frames_in_flight, u, v, correlation, counts, true,
-                         PivFlowOptions{deformation, outlier_threshold, outlier_epsilon, validate_last, validation_counts});
-}
-
-// the six stacks of two results as inputs of a frame-chunk walk, and those of one chunk as the kernels take them
-struct FlowStacks { const double *vxa, *vya, *spa, *vxb, *vyb, *spb; };
-static int flow_stacks_check(vof_ctx* c, const FlowStacks& s, int n_pairs, double speed_min, double angle_min) {
-    if (int rc = FrameChunks::check(c, {s.vxa, s.vya, s.spa, s.vxb, s.vyb, s.spb}, n_pairs, "n_pairs")) return rc;
-    if (std::isnan(speed_min) || std::isnan(angle_min)) { c->err = "flow comparison: a threshold is NaN"; return -1; }
-    return 0;
-}
-static void flow_stacks_inputs(FrameChunks& fc, const FlowStacks& s) {
-    for (const double* p : {s.vxa, s.vya, s.spa, s.vxb, s.vyb, s.spb}) fc.input(p);
-}
-static FlowPlanes flow_planes(const double* const* in, size_t fs) { return FlowPlanes{in[0], in[1], in[2], in[3], in[4], in[5], fs}; }
-
-static int flow_extremes_impl(vof_ctx* c, const FlowStacks& s, int n_pairs, double speed_min, double angle_min, int quirks, int flight,
-                              double* extremes, bool host) {
-    if (int rc = flow_stacks_check(c, s, n_pairs, speed_min, angle_min)) return rc;
-    if (!extremes) { c->err = "NULL pointer"; return -1; }
-    const size_t fs = frame_stride(c);
-    const int blk = fc_blocks(fs);
-    FrameChunks fc(c, "flow extremes", n_pairs, flight, host);
-    FcExtremes *part, *acc;
-    fc.sc.per_unit(&part, (size_t)blk);
-    fc.sc.once(&acc, 1);
-    flow_stacks_inputs(fc, s);
-    if (int rc = fc.plan()) return rc;
-    const FcExtremes none{INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
-    if (int rc = h2d_bounced(c, acc, &none, sizeof none)) return rc;
-    if (int rc = fc.run([&](int, int nf, const double* const* in, void* const*) -> int {
-            Prof prof(c, VOF_K_REDUCE, FC_ST_EXTREMES, 48.0 * fs);
-            k_fc_extremes<<<dim3(blk, nf), FC_BLOCK, 0, c->stream>>>(flow_planes(in, fs), speed_min, angle_min, quirks ? 0 : 1, part);
-            k_fc_extremes_fold<<<1, 64, 0, c->stream>>>(part, blk * nf, acc);
-            return 0;
-        })) return rc;
-    static_assert(sizeof(FcExtremes) == 6 * sizeof(double), "extremes: six doubles");
-    return d2h_bounced(c, extremes, acc, sizeof(FcExtremes));
-}
-
-#define VOF_FLOW_STACKS_ARGS const double *v_x_a, const double *v_y_a, const double *speed_a, const double *v_x_b, const double *v_y_b, const double *speed_b
-#define VOF_FLOW_STACKS FlowStacks{v_x_a, v_y_a, speed_a, v_x_b, v_y_b, speed_b}
-
-int vof_flow_extremes_dev(vof_ctx* c, VOF_FLOW_STACKS_ARGS, int n_pairs, double speed_threshold, double angle_threshold, int reference_quirks,
-                          int frames_in_flight, double* extremes) {
-    return flow_extremes_impl(c, VOF_FLOW_STACKS, n_pairs, speed_threshold, angle_threshold, reference_quirks, frames_in_flight, extremes, false);
-}
-int vof_flow_extremes_host(vof_ctx* c, VOF_FLOW_STACKS_ARGS, int n_pairs, double speed_threshold, double angle_threshold, int reference_quirks,
-                           int frames_in_flight, double* extremes) {
-    return flow_extremes_impl(c, VOF_FLOW_STACKS, n_pairs, speed_threshold, angle_threshold, reference_quirks, frames_in_flight, extremes, true);
-}
-
-struct FlowCompareReq {
-    FlowStacks s; int n_pairs; double speed_min, angle_min; int quirks;
-    const double* edges[3]; int bins[3];                      // speed of a, speed of b, theta
-    int clamp_theta, flight;
-    int64_t *jhist, *thist, *counts;
-    bool host;
-};
-
-static int flow_compare_impl(vof_ctx* c, const FlowCompareReq& r) {
-    if (int rc = flow_stacks_check(c, r.s, r.n_pairs, r.speed_min, r.angle_min)) return rc;
-    if (!r.edges[0] || !r.edges[1] || !r.edges[2] || !r.jhist || !r.thist || !r.counts) { c->err = "NULL pointer"; return -1; }
-    for (int e = 0; e < 3; ++e) {
-        const int most = e < 2 ? CP_MAX_SPEED_BINS : CP_MAX_THETA_BINS;
-        if (r.bins[e] < 1 || r.bins[e] > most) {
-            c->err = std::string(e < 2 ? "joint_speed_bins must be 1 .. " : "angle_bins must be 1 .. ") + std::to_string(most) + (e < 2 ? " per axis" : "");
-            return -1;
-        }
-        bool rising = r.edges[e][r.bins[e]] > r.edges[e][0];
-        for (int b = 0; b < r.bins[e]; ++b) rising = rising && r.edges[e][b + 1] >= r.edges[e][b];
-        if (!rising) { c->err = e < 2 ? "joint_speed_edges must increase" : "angle_edges must increase"; return -1; }
-    }
-    const size_t fs = frame_stride(c);
-    const int blk = fc_blocks(fs);
-    const size_t nj = (size_t)r.bins[0] * r.bins[1];
-    FrameChunks fc(c, "flow comparison", r.n_pairs, r.flight, r.host);
-    double* d_edges[3];
-    unsigned long long *d_jhist, *d_thist, *d_counters;
-    for (int e = 0; e < 3; ++e) fc.sc.once(&d_edges[e], (size_t)r.bins[e] + 1);
-    fc.sc.once(&d_jhist, nj);
-    fc.sc.once(&d_thist, (size_t)r.bins[2]);
-    fc.sc.once(&d_counters, (size_t)FC_COUNTERS);
-    flow_stacks_inputs(fc, r.s);
-    if (int rc = fc.plan()) return rc;
-    for (int e = 0; e < 3; ++e)
-        if (int rc = h2d_bounced(c, d_edges[e], r.edges[e], ((size_t)r.bins[e] + 1) * sizeof(double))) return rc;
-    HIPCHK(hipMemsetAsync(d_jhist, 0, nj * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(d_thist, 0, (size_t)r.bins[2] * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(d_counters, 0, FC_COUNTERS * sizeof(unsigned long long), c->stream));
-    if (int rc = fc.run([&](int, int nf, const double* const* in, void* const*) -> int {
-            FcHistArgs a{};
-            a.p = flow_planes(in, fs);
-            a.speed_min = r.speed_min; a.angle_min = r.angle_min; a.clip = r.quirks ? 0 : 1; a.clamp_theta = r.clamp_theta ? 1 : 0;
-            a.ea = d_edges[0]; a.ba = r.bins[0]; a.eb = d_edges[1]; a.bb = r.bins[1];
-            a.tedges = d_edges[2]; a.tbins = r.bins[2];
-            a.jhist = d_jhist; a.thist = d_thist; a.counters = d_counters;
-            Prof prof(c, VOF_K_REDUCE, FC_ST_HISTOGRAMS, 48.0 * fs);
-            k_fc_histograms<<<dim3(blk, nf), FC_BLOCK, 0, c->stream>>>(a);
-            return 0;
-        })) return rc;
-    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counters are copied as they are");
-    if (int rc = d2h_bounced(c, r.jhist, d_jhist, nj * sizeof(int64_t))) return rc;
-    if (int rc = d2h_bounced(c, r.thist, d_thist, (size_t)r.bins[2] * sizeof(int64_t))) return rc;
-    return d2h_bounced(c, r.counts, d_counters, FC_COUNTERS * sizeof(int64_t));
-}
-
-#define VOF_FLOW_COMPARE_ARGS                                                                                                          \
-    vof_ctx *c, VOF_FLOW_STACKS_ARGS, int n_pairs, double speed_threshold, double angle_threshold, int reference_quirks,               \
-        const double *joint_speed_edges_a, int joint_speed_bins_a, const double *joint_speed_edges_b, int joint_speed_bins_b,          \
-        const double *angle_edges, int angle_bins, int clamp_angle, int frames_in_flight, int64_t *joint_speed_histogram,              \
-        int64_t *angle_histogram, int64_t *counts
-#define VOF_FLOW_COMPARE_REQ(host)                                                                                                     \
-    FlowCompareReq{VOF_FLOW_STACKS, n_pairs, speed_threshold, angle_threshold, reference_quirks,                                       \
-                   {joint_speed_edges_a, joint_speed_edges_b, angle_edges}, {joint_speed_bins_a, joint_speed_bins_b, angle_bins},     \
-                   clamp_angle, frames_in_flight, joint_speed_histogram, angle_histogram, counts, host}
-
-int vof_flow_compare_dev(VOF_FLOW_COMPARE_ARGS) { return flow_compare_impl(c, VOF_FLOW_COMPARE_REQ(false)); }
-int vof_flow_compare_host(VOF_FLOW_COMPARE_ARGS) { return flow_compare_impl(c, VOF_FLOW_COMPARE_REQ(true)); }
-
-// ---- Liu-Shen Jacobi flow (liu_shen_optical_flow_jit, OF.py:426-673) ----------------------------------------------
-constexpr int LS_HOST_CHUNK = 8;          // pairs per chunk of vof_liu_shen_host
-
-static int liu_shen_check(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, const double* ix, const double* iy,
-                          const double* ir, int initial_kind, int max_iterations, const double* v_x, const double* v_y,
-                          const double* speed, const double* remodelling) {
-    if (!movie || !v_x || !v_y || !speed || !remodelling || !ix || !iy || !ir) { c->err = "NULL array pointer"; return -1; }
-    if (n_frames < 2) { c->err = "need at least two frames"; return -1; }
-    if (initial_kind < 0 || initial_kind > 2) { c->err = "initial_kind must be 0 (scalar), 1 (plane) or 2 (stack)"; return -1; }
-    if (max_iterations < 1) { c->err = "max_iterations must be >= 1"; return -1; }
-    if (c->Ni < 3 || c->Nj < 3) { c->err = "the Liu-Shen flow needs image sides >= 3"; return -1; }
-    if (delta_x == 0.0 || delta_t == 0.0) { c->err = "delta_x and delta_t must not be 0"; return -1; }
-    return 0;
-}
-
-// iterations per launch: VOF_LIUSHEN_FUSE, read at every call
-static int liu_shen_depth(vof_ctx* c, int* depth) {
-    *depth = LS_KDEF;
-    if (const char* e = getenv("VOF_LIUSHEN_FUSE")) {
-        *depth = atoi(e);
-        if (*depth < 1 || *depth > LS_KMAX) { c->err = "VOF_LIUSHEN_FUSE must be 1 .. 8"; return -1; }
-    }
-    return 0;
-}
-
-// P pairs (at most 4096: a chunk of the walk) of a device-resident movie into device-resident outputs, enqueued on the context's
-// stream.  The iterates ping-pong between (v_x, v_y) and (speed, remodelling); ix / iy / ir are device arrays of initial_kind 1 / 2
-// (ix, iy may be any of the four outputs), sx / sy / sr the scalars of kind 0.  write_remodelling false leaves remodelling as scratch.
-static int liu_shen_pairs(vof_ctx* c, const double* movie, int P, double delta_x, double delta_t, double alpha, const double* ix,
-                          const double* iy, const double* ir, double sx, double sy, double sr, int kind, int iterations, int depth,
-                          double* v_x, double* v_y, double* speed, double* remodelling, bool write_remodelling) {
-    const size_t fs = frame_stride(c);
-    if (depth > 1 && !c->ls_lds_set) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_ls_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls_fused_lds(LS_KMAX)));
-        c->ls_lds_set = true;
-    }
-    const size_t n = (size_t)P * fs;
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    double* buf[2][2] = {{v_x, v_y}, {speed, remodelling}};
-    c->cur_units = P;
-    Prof prof(c, VOF_K_RHS, 0);
-    k_ls_init<<<nb, 256, 0, c->stream>>>(buf[0][0], buf[0][1], kind ? ix : nullptr, kind ? iy : nullptr, sx, sy, kind, fs, n, delta_t, delta_x);
-    LsArgs a{};
-    a.movie = movie; a.fs = fs; a.Ni = c->Ni; a.Nj = c->Nj; a.alpha = alpha;
-    int cur = 0;
-    for (int done = 0; done < iterations;) {
-        const int k = std::min(depth, iterations - done);
-        a.k = k;
-        a.sx = buf[cur][0]; a.sy = buf[cur][1]; a.dx = buf[cur ^ 1][0]; a.dy = buf[cur ^ 1][1];
-        if (depth == 1) {
-            k_ls_step<<<grid2d(c->Ni, c->Nj, P), blk2d, 0, c->stream>>>(a);
-        } else {
-            const dim3 g((c->Nj + LS_TJ - 1) / LS_TJ, (c->Ni + LS_TI - 1) / LS_TI, P);
-            k_ls_fused<<<g, LS_THREADS, ls_fused_lds(k), c->stream>>>(a);
-        }
-        done += k;
-        cur ^= 1;
-    }
-    k_ls_finish<<<nb, 256, 0, c->stream>>>(buf[cur][0], buf[cur][1], buf[0][0], buf[0][1], buf[1][0], write_remodelling ? buf[1][1] : nullptr,
-                                           kind ? ir : nullptr, sr, kind, fs, n, delta_x / delta_t);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// The pairs in chunks: all of them for device-resident arrays, LS_HOST_CHUNK staged at a time for host arrays.  _host keeps the
-// fourth iterate buffer in the arena and never uploads initial_remodelling: remodelling is filled on the host.
-static int liu_shen_impl(vof_ctx* c, const double* movie, int n_frames, double delta_x, double delta_t, double alpha,
-                         const double* initial_v_x, const double* initial_v_y, const double* initial_remodelling, int initial_kind,
-                         int max_iterations, double* v_x, double* v_y, double* speed, double* remodelling, bool host) {
-    if (!c) return -1;
-    if (int rc = liu_shen_check(c, movie, n_frames, delta_x, delta_t, initial_v_x, initial_v_y, initial_remodelling, initial_kind,
-                                max_iterations, v_x, v_y, speed, remodelling)) return rc;
-    if (!host && initial_kind && (initial_remodelling == remodelling || initial_remodelling == speed || initial_remodelling == v_x ||
-                                  initial_remodelling == v_y)) { c->err = "initial_remodelling must not be an output array"; return -1; }
-    int depth;
-    if (int rc = liu_shen_depth(c, &depth)) return rc;
-    const size_t fs = frame_stride(c), fb = fs * sizeof(double);
-    const int P = n_frames - 1;
-    const bool s = initial_kind == 0;
-    FrameChunks fc(c, "Liu-Shen flow", P, host ? LS_HOST_CHUNK : P, host);
-    double *fourth = nullptr, *plane_x = nullptr, *plane_y = nullptr;          // _host: the fourth iterate buffer, the planes of kind 1
-    fc.input(movie, true);
-    if (initial_kind == 2) { fc.input(initial_v_x); fc.input(initial_v_y); if (!host) fc.input(initial_remodelling); }
-    if (initial_kind == 1 && host) { fc.sc.once(&plane_x, fs); fc.sc.once(&plane_y, fs); }
-    if (host) fc.sc.per_unit(&fourth, fs);
-    for (double* o : {v_x, v_y, speed}) fc.output(o, fb);
-    if (int rc = fc.plan()) return rc;
-    if (plane_x) if (int rc = h2d_bounced(c, plane_x, initial_v_x, fb)) return rc;
-    if (plane_y) if (int rc = h2d_bounced(c, plane_y, initial_v_y, fb)) return rc;
-    if (int rc = fc.run([&](int k0, int np, const double* const* in, void* const* out) -> int {
-            const bool stack = initial_kind == 2;
-            return liu_shen_pairs(c, in[0], np, delta_x, delta_t, alpha, stack ? in[1] : host ? plane_x : initial_v_x,
-                                  stack ? in[2] : host ? plane_y : initial_v_y, stack ? in[3] : host ? nullptr : initial_remodelling,
-                                  s ? *initial_v_x : 0.0, s ? *initial_v_y : 0.0, s && !host ? *initial_remodelling : 0.0, initial_kind,
-                                  max_iterations, depth, (double*)out[0], (double*)out[1], (double*)out[2],
-                                  host ? fourth : remodelling + (size_t)k0 * fs, !host);
-        })) return rc;
-    // OF.py:507, 668: the initial remodelling comes back untouched
-    for (int k = 0; host && k < P; ++k) {
-        double* r = remodelling + (size_t)k * fs;
-        const double* ir = initial_remodelling + (initial_kind == 2 ? (size_t)k * fs : 0);
-        if (initial_kind == 0) std::fill(r, r + fs, *initial_remodelling);
-        else if (ir != r) memcpy(r, ir, fb);
-    }
-    return 0;
-}
-
-#define VOF_LIU_SHEN_ARGS                                                                                                             \
-    vof_ctx *c, const double *movie, int n_frames, double delta_x, double delta_t, double alpha, const double *initial_v_x,           \
-        const double *initial_v_y, const double *initial_remodelling, int initial_kind, int max_iterations, double *v_x, double *v_y, \
-        double *speed, double *remodelling
-#define VOF_LIU_SHEN_CALL(host)                                                                                                       \
-    liu_shen_impl(c, movie, n_frames, delta_x, delta_t, alpha, initial_v_x, initial_v_y, initial_remodelling, initial_kind,           \
-                  max_iterations, v_x, v_y, speed, remodelling, host)
-
-int vof_liu_shen_dev(VOF_LIU_SHEN_ARGS) { return VOF_LIU_SHEN_CALL(false); }
-int vof_liu_shen_host(VOF_LIU_SHEN_ARGS) { return VOF_LIU_SHEN_CALL(true); }
 
 }  // extern "C"

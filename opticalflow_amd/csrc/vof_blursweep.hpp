@@ -19,13 +19,35 @@ namespace vof {
 // Dynamic LDS: blur_tiled_lds(axis, radius), at most 80 KiB (AXIS 0 at BL_RMAX), so that two workgroups still share the
 // 160 KiB of a CU; the limit of the AXIS 0 kernel is raised once per context.  The sweep's largest radius is 60 (sigma 15);
 // above BL_RMAX k_blur1d stays the path.
-constexpr int BL_TI = 32;      // AXIS 0: output rows of a tile (8 per thread)
-constexpr int BL_TR = 16;      // AXIS 1: rows of a tile (4 per thread)
-constexpr int BL_RMAX = 64;    // (BL_TI + 2 * 64) * BX * 8 B = 81920 B
-constexpr int BL_RMIN = 1;     // radius 0 is a copy scaled by w[0]: nothing to share
 
-inline size_t blur_tiled_lds(int axis, int radius) {
-    return (axis == 0 ? (size_t)(BL_TI + 2 * radius) * BX : (size_t)BL_TR * (BX + 2 * radius)) * sizeof(double);
+// ==========================================================================================
+// Gaussian blur of the frames (OF.py:282-306: skimage.filters.gaussian == scipy.ndimage.gaussian_filter with
+// mode='nearest', truncate=4): two 1-D correlations, axis 0 then axis 1, with edge clamping.  The summation order
+// is the one of scipy's symmetric-kernel branch (NI_Correlate1D): centre tap first, then the mirrored pairs
+// from the outside in, so results agree with the host filter to the last bit or two.
+// ==========================================================================================
+template <int AXIS>
+__global__ __launch_bounds__(NT) void k_blur1d(const double* __restrict__ in, double* __restrict__ out, int Ni, int Nj,
+                                               const double* __restrict__ w, int radius) {
+#pragma clang fp contract(off)   // no FMA: the host filter rounds the product and the sum separately
+    int j = blockIdx.x * BX + threadIdx.x, i = blockIdx.y * BY + threadIdx.y, f = blockIdx.z;
+    if (i >= Ni || j >= Nj) return;
+    const double* src = in + (size_t)f * Ni * Nj;
+    double acc = src[(size_t)i * Nj + j] * w[radius];
+    for (int k = -radius; k < 0; ++k) {
+        double a, b;
+        if (AXIS == 0) {
+            int ia = min(max(i + k, 0), Ni - 1), ib = min(max(i - k, 0), Ni - 1);
+            a = src[(size_t)ia * Nj + j];
+            b = src[(size_t)ib * Nj + j];
+        } else {
+            int ja = min(max(j + k, 0), Nj - 1), jb = min(max(j - k, 0), Nj - 1);
+            a = src[(size_t)i * Nj + ja];
+            b = src[(size_t)i * Nj + jb];
+        }
+        acc += (a + b) * w[k + radius];
+    }
+    out[(size_t)f * Ni * Nj + (size_t)i * Nj + j] = acc;
 }
 
 template <int AXIS>

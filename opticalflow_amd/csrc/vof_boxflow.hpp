@@ -16,6 +16,7 @@
 // division and square root (integer-valued movies reproduce the reference's v_x, v_y, net_remodelling bit for bit).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vof_shared.hpp"
 
 namespace vof {
 

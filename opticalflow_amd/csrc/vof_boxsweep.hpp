@@ -140,21 +140,6 @@ __global__ void k_bs_window(SweepArgs s, BoxArgs a) {
 }
 
 // ---- statistics of one box over the pairs in flight -----------------------------------------------------------------
-constexpr int BS_LDS_BINS = 1024;    // histograms up to this many bins are counted per block in LDS first
-
-// np.histogram(x, bins, range)[0] for equal bins: scaled index, corrected against the two neighbouring edges (the bins+1
-// values of np.linspace, passed in); last bin closed on the right; values outside [first, last] and NaN dropped.
-__device__ __forceinline__ int bs_bin_of(double x, const double* __restrict__ edges, int bins) {
-#pragma clang fp contract(off)
-    const double first = edges[0], last = edges[bins];
-    if (!(x >= first && x <= last)) return -1;
-    int idx = (int)(((x - first) / (last - first)) * (double)bins);
-    if (idx == bins) --idx;
-    if (x < edges[idx]) --idx;
-    if (x >= edges[idx + 1] && idx != bins - 1) ++idx;
-    return idx;
-}
-
 // hist (bins counters, or nullptr) += counts of x[0 .. n); *nonfinite += number of NaN / Inf values.  Integer atomics only:
 // the result does not depend on the order of the blocks.
 __global__ __launch_bounds__(256) void k_bs_counts(const double* __restrict__ x, size_t n, const double* __restrict__ edges, int bins,
@@ -183,23 +168,6 @@ __global__ __launch_bounds__(256) void k_bs_counts(const double* __restrict__ x,
         for (int b = threadIdx.x; b < bins; b += blockDim.x)
             if (lh[b]) atomicAdd(&hist[b], (unsigned long long)lh[b]);
     if (threadIdx.x == 0 && lbad) atomicAdd(nonfinite, (unsigned long long)lbad);
-}
-
-// k_moments per pair in flight (grid y): sum (x - shift), sum (x - shift)^2 over the pair's plane, shift = 0 in the first pass
-// (first3 == nullptr) and the pair's own mean, first3[pair][0] / fs, in the second.  Partials [pair][3][nblk] for k_sum3.  A
-// pair is the unit the host merges, so the statistics of a sweep do not depend on how many pairs a launch holds.
-__global__ __launch_bounds__(RBLK) void k_bs_moments(const double* __restrict__ x, size_t fs, const double* __restrict__ first3,
-                                                     double* __restrict__ partials) {
-    const int pair = blockIdx.y;
-    const double shift = first3 ? first3[(size_t)pair * 3] / (double)fs : 0.0;
-    const double* xp = x + (size_t)pair * fs;
-    double s1 = 0, s2 = 0;
-    for (size_t i = (size_t)blockIdx.x * RBLK + threadIdx.x; i < fs; i += (size_t)gridDim.x * RBLK) {
-        const double d = xp[i] - shift;
-        s1 += d;
-        s2 += d * d;
-    }
-    block_store_partials(s1, s2, 0.0, partials, 3, gridDim.x, pair, blockIdx.x);
 }
 
 // out[pair][l] = speed[pair][probe_ij[2 l]][probe_ij[2 l + 1]]

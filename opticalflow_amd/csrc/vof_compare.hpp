@@ -27,9 +27,6 @@ namespace vof {
 // ascending order.  48 bytes are read per sample, nothing of field size is written.
 // Dynamic LDS: cp_lds(), (tbins * 64) doubles + (tbins + ba * bb) counters: 49408 B at the limits, 35800 B for the reference's
 // 50 and 50 x 50 bins - inside the default 64 KiB, no limit to raise.
-constexpr int CP_MAX_THETA_BINS = 64;
-constexpr int CP_MAX_SPEED_BINS = 1024;   // per axis of the 2-D histogram
-constexpr int CP_LDS_JOINT = 4096;        // ba * bb up to this are counted per block in LDS first
 constexpr int CP_PER_LANE = 16;           // samples a lane adds at least before a plane gets another block ...
 constexpr int CP_MAX_BLOCKS = 256;        // ... up to this many blocks per pair
 constexpr int CP_UNROLL = 4;

@@ -14,42 +14,10 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
+#include "vof_shared.hpp"
 
 namespace vof {
 
-constexpr int BX = 64;  // lanes along j
-constexpr int BY = 4;   // rows per block
-constexpr int NT = BX * BY;
-
-struct PairScalars {
-    double rho, alpha, omega, beta;
-    double bnorm2, rnorm2;
-    double tol2;      // rtol^2 * bnorm2
-    int iterations;
-    int converged;
-    int breakdown;
-    int halfstep;     // 1: converged at the half step, x += alpha y still pending; 2: done
-};
-
-// Per-pair overrides for "virtual pairs" (vary_regularisation batches several (speed_alpha, remodelling_alpha)
-// combinations of the same movie into one launch): regularisation parameters and the index of the pair's first frame.
-// Kernels take a `const PairParam* pp`; nullptr (the normal case) = kernel arguments / frame index = pair index.
-struct PairParam {
-    double alpha, beta;
-    int frame;   // index of the pair's first frame in the movie
-    int out;     // index of the pair's slot in the output stacks
-};
-
-// The pairs a launch serves.  flags[pair] != 0: the pair is still being solved (nullptr: every pair is).  list: the slots of the
-// pairs that were active when the host last counted them, ascending; the grid dimension that runs over the pairs then holds one
-// entry per listed pair instead of one per slot of the batch (nullptr: one per slot).  A block takes its pair from the list and
-// still checks the flag: pairs are switched off on the device between two counts (k_scalar), and those blocks leave as before.
-struct ActiveSet {
-    const int* flags;
-    const int* list;
-    __device__ __forceinline__ int pair(int slot) const { return list ? list[slot] : slot; }
-    __device__ __forceinline__ bool on(int pair) const { return !flags || flags[pair]; }
-};
 
 __device__ __forceinline__ int fold(int t, int n) { return t < 0 ? 1 : (t >= n ? n - 2 : t); }
 
@@ -1295,14 +1263,6 @@ __global__ void k_coarse_solve(const double* __restrict__ invT, int nd, const VT
 // Vector kernels of BiCGStab.  Per-pair scalars live on the device (no host sync inside an iteration);
 // reductions are two-stage and deterministic: per-block partials, summed in fixed order by k_scalar.
 // ------------------------------------------------------------------------------------------
-constexpr int RBLK = 256;  // threads per reduction block
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // Block sums of up to three values into slots 0 .. nslots_used - 1 of partials[pair][slot][blk]: wave sums, one word per wave
 // in LDS, thread 0 adds the waves in order.  c1 / c2 scale the finished sums of slots 1 / 2.  Every caller of one kernel shares
 // the scratch `s`: a barrier between two calls.
@@ -1679,21 +1639,6 @@ __global__ void k_sum3(const double* __restrict__ partials, int nblk, double* __
 // Hessenberg matrix) lives on the device.  Orthogonalisation: classical Gram-Schmidt, applied twice (CGS2), GM_NV basis
 // vectors per pass over w.
 // ------------------------------------------------------------------------------------------
-constexpr int GM_MAXM = 128;   // largest restart length
-constexpr int GM_NV = 8;       // basis vectors per multi-dot / multi-axpy launch
-
-struct GmresState {
-    double R[GM_MAXM * GM_MAXM];   // rotated Hessenberg matrix, column j at R + j * GM_MAXM (upper triangular)
-    double cs[GM_MAXM], sn[GM_MAXM];
-    double g[GM_MAXM + 1];         // rotated right-hand side; |g[k]| = residual norm after k steps
-    double y[GM_MAXM];             // solution of the k x k triangular system
-    double h[GM_MAXM + 2];         // current Hessenberg column (before the rotations)
-    double c[GM_MAXM + 2];         // coefficients of the current Gram-Schmidt pass
-    double scale;                  // 1 / norm of the vector to normalise next
-    int k;                         // columns built in this cycle
-    int est_converged;             // the cycle ended because the residual estimate met the tolerance
-};
-
 // active = cycle = pair still to be solved (true residual above the tolerance, iterations left)
 __global__ void k_gm_begin(PairScalars* __restrict__ sc, int* __restrict__ active, int* __restrict__ cycle, int np, int max_it) {
     int pair = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1944,6 +1889,23 @@ __global__ __launch_bounds__(RBLK) void k_moments(const double* __restrict__ x, 
         s2 += d * d;
     }
     block_store_partials(s1, s2, 0.0, partials, 3, gridDim.x, 0, blockIdx.x);
+}
+
+// k_moments per pair in flight (grid y): sum (x - shift), sum (x - shift)^2 over the pair's plane, shift = 0 in the first pass
+// (first3 == nullptr) and the pair's own mean, first3[pair][0] / fs, in the second.  Partials [pair][3][nblk] for k_sum3.  A
+// pair is the unit the host merges, so the statistics of a sweep do not depend on how many pairs a launch holds.
+__global__ __launch_bounds__(RBLK) void k_bs_moments(const double* __restrict__ x, size_t fs, const double* __restrict__ first3,
+                                                     double* __restrict__ partials) {
+    const int pair = blockIdx.y;
+    const double shift = first3 ? first3[(size_t)pair * 3] / (double)fs : 0.0;
+    const double* xp = x + (size_t)pair * fs;
+    double s1 = 0, s2 = 0;
+    for (size_t i = (size_t)blockIdx.x * RBLK + threadIdx.x; i < fs; i += (size_t)gridDim.x * RBLK) {
+        const double d = xp[i] - shift;
+        s1 += d;
+        s2 += d * d;
+    }
+    block_store_partials(s1, s2, 0.0, partials, 3, gridDim.x, pair, blockIdx.x);
 }
 
 // Strided sample of a field stack (subsample_velocities_for_visualisation, OF.py:1614-1632):
@@ -3701,36 +3663,6 @@ __global__ __launch_bounds__(128 * NS) void k_sweep0m(
 }
 
 // ==========================================================================================
-// Gaussian blur of the frames (OF.py:282-306: skimage.filters.gaussian == scipy.ndimage.gaussian_filter with
-// mode='nearest', truncate=4): two 1-D correlations, axis 0 then axis 1, with edge clamping.  The summation order
-// is the one of scipy's symmetric-kernel branch (NI_Correlate1D): centre tap first, then the mirrored pairs
-// from the outside in, so results agree with the host filter to the last bit or two.
-// ==========================================================================================
-template <int AXIS>
-__global__ __launch_bounds__(NT) void k_blur1d(const double* __restrict__ in, double* __restrict__ out, int Ni, int Nj,
-                                               const double* __restrict__ w, int radius) {
-#pragma clang fp contract(off)   // no FMA: the host filter rounds the product and the sum separately
-    int j = blockIdx.x * BX + threadIdx.x, i = blockIdx.y * BY + threadIdx.y, f = blockIdx.z;
-    if (i >= Ni || j >= Nj) return;
-    const double* src = in + (size_t)f * Ni * Nj;
-    double acc = src[(size_t)i * Nj + j] * w[radius];
-    for (int k = -radius; k < 0; ++k) {
-        double a, b;
-        if (AXIS == 0) {
-            int ia = min(max(i + k, 0), Ni - 1), ib = min(max(i - k, 0), Ni - 1);
-            a = src[(size_t)ia * Nj + j];
-            b = src[(size_t)ib * Nj + j];
-        } else {
-            int ja = min(max(j + k, 0), Nj - 1), jb = min(max(j - k, 0), Nj - 1);
-            a = src[(size_t)i * Nj + ja];
-            b = src[(size_t)i * Nj + jb];
-        }
-        acc += (a + b) * w[k + radius];
-    }
-    out[(size_t)f * Ni * Nj + (size_t)i * Nj + j] = acc;
-}
-
-// ==========================================================================================
 // k_tail_cycle: the coarse tail of the multigrid cycle in ONE launch, vectors resident in LDS.
 //
 // Levels whose whole grid fits one workgroup (<= 1024 points, i.e. 32 x 32 and coarser: three to four levels plus the
@@ -3742,32 +3674,6 @@ __global__ __launch_bounds__(NT) void k_blur1d(const double* __restrict__ in, do
 // in and the correction out.  The host compiles the cycle shape (V or one-level W, sweep counts) into a short list of
 // operations, so the kernel computes exactly what the per-level launches compute, in the same order.
 // ==========================================================================================
-constexpr int TAIL_THREADS = 256;
-constexpr int TAIL_MAX_LEVELS = 8;
-constexpr int TAIL_MAX_OPS = 160;
-constexpr int TAIL_MAX_PTS = 1024;    // points of the largest tail level
-constexpr int TAIL_MAX_SUB = 256;     // points per colour class of the largest tail level (= threads)
-enum TailOpCode { T_SMOOTH = 0, T_RESTRICT = 1, T_COARSE = 2, T_PROLONG = 3 };
-
-struct TailLevel {
-    int ni, nj;
-    int hj;                      // (nj + 1) / 2: row length of a colour sub-plane
-    int sub;                     // elements of a colour sub-plane ((ni + 1) / 2 * hj)
-    unsigned long long plane;    // CLay(ni, nj).plane
-    const void* C;               // stencil [pair][81][plane]; nullptr on the dense coarsest level
-    int xo, bo;                  // LDS offsets (in doubles) of x (3 x (ni + 2) x (nj + 2), zero halo) and b (3 x ni x nj)
-};
-struct TailArgs {
-    int nl;                      // tail levels; level nl - 1 is the coarsest (dense inverse)
-    int n_ops;
-    int ro;                      // LDS offset of the residual scratch (3 x points of tail level 0)
-    int nd;                      // unknowns of the coarsest level
-    const double* invT;          // [pair][nd][nd] transposed inverse
-    TailLevel L[TAIL_MAX_LEVELS];
-    // op_arg of T_SMOOTH: bit 0 = start from zero, bit 1 = reverse colour order, bits 2.. = number of sweeps
-    unsigned char op[TAIL_MAX_OPS], op_level[TAIL_MAX_OPS], op_arg[TAIL_MAX_OPS];
-};
-
 // one colour of a block-GS sweep (UPDATE) or of the residual r = b - A x (!UPDATE) on an LDS-resident level
 // The stencil words of a thread's point of colour c (the thread has one point per colour on a tail level), requested one
 // colour ahead of their use (see k_tail_cycle)

@@ -3,7 +3,7 @@
 // of the comparison over the six planes (v_x, v_y, speed of a and of b) of the pairs in flight.  DESIGN.md section 17.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vof_compare.hpp"
+#include "vof_shared.hpp"
 
 namespace vof {
 

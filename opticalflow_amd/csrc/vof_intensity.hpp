@@ -10,7 +10,7 @@
 // tap first, then k = -radius .. -1 as acc += (a + b) * w[k + radius], no FMA - so the bits are those of the unfused chain.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vof_blursweep.hpp"
+#include "vof_shared.hpp"
 #include "vof_farneback.hpp"
 
 namespace vof {

@@ -18,6 +18,7 @@
 //   k_ls_init / k_ls_finish   initial fields * delta_t / delta_x; fields * (delta_x / delta_t), speed, remodelling
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vof_shared.hpp"
 
 namespace vof {
 

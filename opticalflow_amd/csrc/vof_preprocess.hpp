@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "vof_shared.hpp"
 
 namespace vof {
 

@@ -1,7 +1,7 @@
 // vof_resize.hpp - cv2.resize(frame, (n_j, n_i), interpolation=cv2.INTER_AREA) of every frame of a stack when neither axis is
 // enlarged, on gfx950: the loop the reference's small-grid experiments run before the estimator (DESIGN.md section 15 has the
 // specification).  OpenCV 4's arithmetic is restated operation by operation: resizeArea_ with the two axis tables of
-// computeResizeAreaTab (built on the host, vof.hip) where a scale is fractional, resizeAreaFast_ where both are integers.
+// computeResizeAreaTab (built on the host, vof_frames.hip) where a scale is fractional, resizeAreaFast_ where both are integers.
 //
 // Both kernels share one skeleton.  A workgroup owns one output row and RS_BLOCK output columns, a lane one output pixel.  For
 // every source row the output row reads, the workgroup stages the contiguous piece of that row its columns need in LDS (16-byte

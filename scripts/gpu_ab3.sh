@@ -2,7 +2,7 @@
 # A/B/C of library builds + env on one box: scripts/gpu_ab3.sh "<flags B>" "<flags C>" ...; env EXTRA_ENV="VAR=val" adds a run of the default build under it
 cd opticalflow_amd/csrc
 i=0; LIBS=("")
-for F in "$@"; do i=$((i+1)); /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-value -shared -fPIC -pthread $F -o libvof_y$i.so vof.hip || exit 1; LIBS+=("$PWD/libvof_y$i.so"); done
+for F in "$@"; do i=$((i+1)); (cd ../.. && python -m opticalflow_amd.build --force --output opticalflow_amd/csrc/libvof_y$i.so -- $F) || exit 1; LIBS+=("$PWD/libvof_y$i.so"); done
 cd ../..
 LOG=$(mktemp); trap 'rm -f $LOG' EXIT
 show() { grep -E "^  (gs |residual|gs0|apply0) .*L[0-3] " | cut -c1-110; }

@@ -5,7 +5,7 @@ i=0
 LIBS=("")
 for F in "$@"; do
   i=$((i+1))
-  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-value -shared -fPIC -pthread $F -o libvof_x$i.so vof.hip || exit 1
+  (cd ../.. && python -m opticalflow_amd.build --force --output opticalflow_amd/csrc/libvof_x$i.so -- $F) || exit 1
   LIBS+=("$PWD/libvof_x$i.so")
 done
 cd ../..

@@ -14,6 +14,7 @@ FC_UNROLL = 4
 # csrc/vof_compare.hpp
 CP_PER_LANE = 16
 CP_MAX_BLOCKS = 256
+# csrc/vof_shared.hpp
 CP_LDS_JOINT = 4096       # 2-D counters that are counted in LDS first
 CP_MAX_THETA_BINS = 64
 CP_MAX_SPEED_BINS = 1024
@@ -21,7 +22,7 @@ CP_MAX_SPEED_BINS = 1024
 BZ_ANGLE_PER_LANE = 32
 BZ_ANGLE_MAX_BLOCKS = 256
 BZ_MAX_ANGLE_BINS = 128
-# csrc/vof_boxsweep.hpp, csrc/vof_device.hpp, csrc/vof.hip
+# csrc/vof_shared.hpp, csrc/vof_pairs.hip, csrc/vof_frames.hip
 BS_LDS_BINS = 1024        # k_bs_counts: more bins go to global atomics
 RBLK = 256                # threads of a reduction block
 BS_MAX_CHUNK = 32         # pairs per launch of a sweep at most
@@ -190,7 +191,7 @@ PLANTED_BINS = (50, 65)   # the joint bins of the planted case over (0, 6): both
 
 
 def scaled_index(x, edges):
-    """The first guess of bs_bin_of (vof_boxsweep.hpp) for values inside the range: ((x - first) / (last - first)) * bins in
+    """The first guess of bs_bin_of (vof_shared.hpp) for values inside the range: ((x - first) / (last - first)) * bins in
     float64, truncated.  bs_bin_of then corrects it against the two neighbouring edges."""
     edges = np.asarray(edges, dtype=np.float64)
     bins = edges.size - 1

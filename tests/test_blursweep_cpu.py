@@ -55,7 +55,7 @@ def test_stats_record_matches_the_header():
 
 
 def test_blur_switch_is_documented():
-    src = open(os.path.join(ROOT, "opticalflow_amd", "csrc", "vof.hip")).read()
+    src = open(os.path.join(ROOT, "opticalflow_amd", "csrc", "vof_pairs.hip")).read()
     assert 'getenv("VOF_BLUR_TILED")' in src
     assert "VOF_BLUR_TILED=0" in open(os.path.join(ROOT, "include", "vof.h")).read()
 

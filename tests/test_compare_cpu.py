@@ -31,7 +31,7 @@ def test_symbols_are_declared_exported_and_prototyped():
         res, args = _native.SIGNATURES[name]
         assert len(args) == len(decl.group(1).split(",")) == 38
     assert hasattr(_native.Solver, "compare_flows_host") and hasattr(_native.Solver, "compare_flows_dev")
-    assert "vof_compare.hpp" in build.DEPS
+    assert "vof_compare.hpp" in build.default_deps(build.CSRC, build.SOURCES[0])
 
 
 def test_stats_record_matches_the_header():
@@ -56,6 +56,7 @@ def test_bin_limits_agree_on_every_layer():
     64 KiB of a workgroup: (bins x 64) float64 columns, the theta counters, the 2-D counters and two static counters."""
     from opticalflow_amd import optical_flow as of
     src = open(os.path.join(ROOT, "opticalflow_amd", "csrc", "vof_compare.hpp")).read()
+    src += open(os.path.join(ROOT, "opticalflow_amd", "csrc", "vof_shared.hpp")).read()
     const = {k: int(v) for k, v in re.findall(r"constexpr int (CP_[A-Z_]+) = (\d+);", src)}
     assert const["CP_MAX_THETA_BINS"] == of.COMPARE_MAX_ANGLE_BINS == 64
     assert const["CP_MAX_SPEED_BINS"] == of.COMPARE_MAX_SPEED_BINS == 1024

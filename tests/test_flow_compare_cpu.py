@@ -36,7 +36,7 @@ def test_symbols_are_declared_exported_and_prototyped():
         assert _native.SIGNATURES[stem + "_dev"] == _native.SIGNATURES[stem + "_host"]
     for method in ("flow_filter", "flow_extremes", "flow_compare"):
         assert hasattr(_native.Solver, method)
-    assert "vof_flowcompare.hpp" in build.DEPS
+    assert "vof_flowcompare.hpp" in build.default_deps(build.CSRC, build.SOURCES[0])
     assert lib.vof_version() == 202 and len(_native.K_NAMES) == 17      # additive: the version and the profiler classes stay
 
 
@@ -47,6 +47,7 @@ def test_limits_agree_on_every_layer():
     from opticalflow_amd import optical_flow as of
     src = open(os.path.join(ROOT, "opticalflow_amd", "csrc", "vof_flowcompare.hpp")).read()
     old = open(os.path.join(ROOT, "opticalflow_amd", "csrc", "vof_compare.hpp")).read()
+    old += open(os.path.join(ROOT, "opticalflow_amd", "csrc", "vof_shared.hpp")).read()
     const = {k: int(v) for k, v in re.findall(r"constexpr int ((?:FC|CP)_[A-Z_]+) = (\d+);", src + old)}
     assert const["CP_MAX_THETA_BINS"] == of.COMPARE_MAX_ANGLE_BINS == 64 and const["CP_MAX_SPEED_BINS"] == of.COMPARE_MAX_SPEED_BINS == 1024
     assert const["FC_BLOCK"] % 64 == 0

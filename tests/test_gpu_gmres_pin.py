@@ -1,4 +1,4 @@
-"""Restarted GMRES (gmres_phase of csrc/vof.hip, the k_gm_* kernels and GmresState of csrc/vof_device.hpp) pinned through the public
+"""Restarted GMRES (gmres_phase of csrc/vof.hip, the k_gm_* kernels of csrc/vof_device.hpp, GmresState of csrc/vof_shared.hpp) pinned through the public
 entry, step by step.
 
 The other GMRES tests ask for the converged answer, and a method that restarts from b - A x repairs almost any error inside a cycle

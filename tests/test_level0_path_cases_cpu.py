@@ -20,10 +20,10 @@ def source(name):
 
 
 def test_restated_constants_are_the_library_s():
-    dev, hip, s0r = source("vof_device.hpp"), source("vof.hip"), source("vof_sweep0r.hpp")
+    dev, hip, s0r, ctx = source("vof_device.hpp"), source("vof.hip"), source("vof_sweep0r.hpp"), source("vof_host.hpp")
     assert int(re.search(r"constexpr int S0_W = (\d+)", dev).group(1)) == lc.S0_W
     assert int(re.search(r"constexpr int AUTO_F64_AFTER = (\d+)", hip).group(1)) == lc.AUTO_F64_AFTER
-    assert int(re.search(r"long sweep0r_min_blocks = (\d+)", hip).group(1)) == lc.DEFAULT_MIN_BLOCKS
+    assert int(re.search(r"long sweep0r_min_blocks = (\d+)", ctx).group(1)) == lc.DEFAULT_MIN_BLOCKS
     # the strip width, in the kernel's geometry (HALO = 4 NS + 2 EXT, OUT = S0_W - 2 HALO) and in the host's plan
     # (out = S0_W - 8 NSW - 4 with a trailing stage), and the band caps of pick_band_height: the numbers, whatever the layout
     m = re.search(r"HALO\s*=\s*(\d+)\s*\*\s*NS\s*\+\s*(\d+)\s*\*\s*EXT\s*,\s*OUT\s*=\s*S0_W\s*-\s*(\d+)\s*\*\s*HALO", s0r)

@@ -104,7 +104,7 @@ def test_symbols_are_declared_exported_and_prototyped():
     assert lib.vof_version() == 202
     assert hasattr(_native.Solver, "liu_shen_host") and hasattr(_native.Solver, "liu_shen_dev")
     assert "VOF_LIUSHEN_FUSE" in open(os.path.join(ROOT, "include", "vof.h")).read()
-    assert "vof_liushen.hpp" in build.DEPS
+    assert "vof_liushen.hpp" in build.default_deps(build.CSRC, build.SOURCES[0])
 
 
 def test_python_names_and_signatures():

@@ -27,7 +27,7 @@ def test_symbols_are_declared_exported_and_prototyped():
         assert len(args) == len(decl.group(1).split(",")) == n_args
     for method in ("adaptive_threshold_host", "adaptive_threshold_dev", "clahe_host", "clahe_dev"):
         assert hasattr(_native.Solver, method)
-    assert "vof_preprocess.hpp" in build.DEPS
+    assert "vof_preprocess.hpp" in build.default_deps(build.CSRC, build.SOURCES[0])
     assert "preprocess" in _native.K_NAMES and lib.vof_kernel_name(_native.K_NAMES.index("preprocess")).decode() == "preprocess"
 
 

@@ -31,7 +31,7 @@ def test_symbols_are_declared_exported_and_prototyped():
     assert values == {"VOF_RESIZE_U8": str(_native.RESIZE_U8), "VOF_RESIZE_F64": str(_native.RESIZE_F64)}
     for method in ("resize_area_host", "resize_area_dev"):
         assert hasattr(_native.Solver, method)
-    assert "vof_resize.hpp" in build.DEPS
+    assert "vof_resize.hpp" in build.default_deps(build.CSRC, build.SOURCES[0])
     assert len(_native.K_NAMES) == 17                                  # the profiler classes did not change: stage 6 of "preprocess"
 
 

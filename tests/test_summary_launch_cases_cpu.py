@@ -26,18 +26,18 @@ def constant(text, name):
 
 
 def test_restated_constants_are_the_library_s():
-    fc, cp, bz, bs = source("vof_flowcompare.hpp"), source("vof_compare.hpp"), source("vof_blursweep.hpp"), source("vof_boxsweep.hpp")
-    dev, hip = source("vof_device.hpp"), source("vof.hip")
+    fc, cp, bz = source("vof_flowcompare.hpp"), source("vof_compare.hpp"), source("vof_blursweep.hpp")
+    shared, pairs, frames = source("vof_shared.hpp"), source("vof_pairs.hip"), source("vof_frames.hip")
     for text, names in ((fc, ("FC_BLOCK", "FC_PER_LANE", "FC_MAX_BLOCKS", "FC_UNROLL")),
-                        (cp, ("CP_PER_LANE", "CP_MAX_BLOCKS", "CP_LDS_JOINT", "CP_MAX_THETA_BINS", "CP_MAX_SPEED_BINS")),
-                        (bz, ("BZ_ANGLE_PER_LANE", "BZ_ANGLE_MAX_BLOCKS", "BZ_MAX_ANGLE_BINS")), (bs, ("BS_LDS_BINS",)), (dev, ("RBLK",)),
-                        (hip, ("BS_MAX_CHUNK", "PRE_MAX_FLIGHT"))):
+                        (cp, ("CP_PER_LANE", "CP_MAX_BLOCKS")), (shared, ("CP_LDS_JOINT", "CP_MAX_THETA_BINS", "CP_MAX_SPEED_BINS")),
+                        (bz, ("BZ_ANGLE_PER_LANE", "BZ_ANGLE_MAX_BLOCKS", "BZ_MAX_ANGLE_BINS")), (shared, ("BS_LDS_BINS",)), (shared, ("RBLK",)),
+                        (pairs, ("BS_MAX_CHUNK",)), (frames, ("PRE_MAX_FLIGHT",))):
         for name in names:
             assert constant(text, name) == getattr(sl, name), name
 
 
 def test_restated_block_rules_are_the_library_s():
-    fc, cp, hip = source("vof_flowcompare.hpp"), source("vof_compare.hpp"), source("vof.hip")
+    fc, cp, hip = source("vof_flowcompare.hpp"), source("vof_compare.hpp"), source("vof_pairs.hip") + source("vof_frames.hip")
     # fc_blocks, cp_blocks: fs / (lanes * PER_LANE), at least 1, at most MAX_BLOCKS
     assert re.search(r"inline int fc_blocks\(size_t fs\) \{[^}]*fs / \(\(size_t\)FC_BLOCK \* FC_PER_LANE\);\s*"
                      r"return n < 1 \? 1 : \(n > \(size_t\)FC_MAX_BLOCKS \? FC_MAX_BLOCKS : \(int\)n\);", fc)
@@ -145,7 +145,7 @@ def test_the_planted_bins_need_both_corrections_of_bs_bin_of():
     """bs_bin_of as it stands: the scaled index, then one step down against edges[idx], one step up against edges[idx + 1].  Of
     the planted samples some sit where the scaled index alone is one too low (on an edge) and some where it is one too high (one
     ulp below an edge): a kernel without either correction miscounts them."""
-    bs = source("vof_boxsweep.hpp")
+    bs = source("vof_shared.hpp")
     assert re.search(r"int idx = \(int\)\(\(\(x - first\) / \(last - first\)\) \* \(double\)bins\);\s*if \(idx == bins\) --idx;\s*"
                      r"if \(x < edges\[idx\]\) --idx;\s*if \(x >= edges\[idx \+ 1\] && idx != bins - 1\) \+\+idx;", bs)
     a, b = sl.lattice_results((2,) + sl.MID, 51)
