@@ -8,6 +8,7 @@
 // operators; stopping rule ||b - A x|| <= rtol ||b|| (OF.py:1120,1126).  All frame pairs of a batch
 // advance together; per-pair scalars stay on the device.
 #include "vof_device.hpp"
+#include "vof_sweepst.hpp"
 #include "vof_sweep0r.hpp"
 #include "vof_sweep0p.hpp"
 #include "vof_stream0.hpp"
@@ -855,10 +856,8 @@ void sweep_level_t(vof_ctx* c, int l, const VT* x_in, VT* x_out, const VT* b, in
         if (c->cfmt == 3) launch(TypeTag<CoefF8>{}); else launch(TypeTag<CoefB16>{});
         return;
     }
-    CDISPATCH(c, l, {
-        SweepStored<CT> pol; pol.C = (const CW*)lv.C; pol.plane = CLay(lv.ni, lv.nj).plane;
-        k_sweep<SweepStored<CT>, GeoB, VT><<<g, GeoB::THREADS, lds, c->stream>>>(pol, lv.ni, lv.nj, TI, po, nx, ny, nslots, x_in, x_out, b, active, ecoarse, nci, ncj);
-    });
+    // (float32 / float64 stencils; a correction `ecoarse` was added by k_prolong_add before the sweep)
+    CDISPATCH(c, l, { k_sweep<CT, VT><<<g, GeoB::THREADS, lds, c->stream>>>((const CW*)lv.C, lv.ni, lv.nj, TI, po, nx, ny, nslots, x_in, x_out, b, active); });
 }
 
 // Stored level l between two visits (revisit_fusable): a reverse sweep x_in -> x_mid and a forward sweep x_mid -> x_out, which

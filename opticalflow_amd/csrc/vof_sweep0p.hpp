@@ -91,12 +91,8 @@ __global__ __launch_bounds__(64) void k_sweep0p(
     constexpr int NST = 2 * NS, po = PO;
     extern __shared__ double sw_lds[];
     char* iring = reinterpret_cast<char*>(sw_lds);
-    const unsigned nblocks = (unsigned)nxp * ny * nz;
-    unsigned lb = blockIdx.x;
-    if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
-    const int bxp = lb % nxp, by = (lb / nxp) % ny;
-    const int pair = act.pair(lb / (nxp * ny));
-    if (!act.on(pair)) return;
+    int bxp, by, pair;
+    if (!sw_strip(act, nxp, ny, nz, bxp, by, pair)) return;
     const int lane = threadIdx.x;
     const int p0 = by * TI - po;
     const int qsA = (2 * bxp) * G::OUT - G::HALO, qsB = qsA + G::OUT;

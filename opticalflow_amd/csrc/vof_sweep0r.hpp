@@ -139,9 +139,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FROM_ZERO &
     char* bring = dring + ND * DRB;
     constexpr bool BL = G::BL && BF == 0;
     int bph = 0;                                                            // BL: this step's slot pair (toggles every step)
+    // (the decode of sw_strip, written out: with the helper the compiler orders this kernel's scalar prologue differently)
     const unsigned nblocks = (unsigned)nx * ny * nz;
     unsigned lb = blockIdx.x;
-    if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see k_sweep
+    if ((nblocks & 7u) == 0) lb = (lb & 7u) * (nblocks >> 3) + (lb >> 3);   // XCD-aware remap, see sw_strip
     const int bxl = lb % nx, by = (lb / nx) % ny;
     const int bx = bxl < skip_first ? bxl : bxl + skip_count;
     const int pair = act.pair(lb / (nx * ny));
